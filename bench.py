@@ -17,6 +17,12 @@ the rows of a received part into place); `python bench.py --gpus N` launches its
 Outputs beyond 2 GB (configs[3]-sized: DSH_BENCH_N=100000 DSH_BENCH_P=10) are NOT gathered by default: every rank keeps
 its span (what `dashing-amd dist --ngpus -b` writes per device); the gathered variant is reported beside it.
 
+A plain run does only what the headline needs: set-up, --warmup untimed steps, --steps timed steps, then the line with
+`value` (pairs/s over the timed steps) and `ms_per_step`.  --dump-outputs DIR also writes the matrix of the last timed
+step (dump_outputs).  Everything else the line can carry -- the kernel phases and `roofline`, the PMC child passes,
+`cpu_baseline` and the parity checks, `configs`, `data_dependence`, the N-rank diagnostics and gathered variant -- is
+measured after the headline with --full.
+
 Prints ONE JSON line on rank 0 -- also when the run fails (then with "error").  `roofline` describes the dominant kernel
 (k_pair_counts_ls), timed with HIP events on the library's own stream; `roofline.binding` names the resource that
 actually bounds it (integer VALU issue -- the streaming-model HBM figure above 1 only says the kernel is not HBM-bound).
@@ -336,6 +342,24 @@ def self_launch(n_gpus, backend):
     return subprocess.call(argv, env=env)
 
 
+DUMP_WHOLE = 1 << 23   # floats: a matrix up to this size is written whole (32 MB)
+DUMP_DRAWS = 1 << 22   # else a fixed sample of it: 16 MB of values + 32 MB of positions
+
+
+def dump_outputs(out_dir, torch, dev, tri, count, name):
+    """--dump-outputs: the first `count` floats of the device buffer `tri`, what the last timed step left there for its
+    caller, as DIR/<name>.npy (float32).  A larger matrix is written as a fixed sample: the positions are np.unique of
+    DUMP_DRAWS seeded draws (the same for the same size), their values in <name>_sample.npy and the positions themselves
+    (float64, exact below 2^53) in <name>_sample_index.npy."""
+    os.makedirs(out_dir, exist_ok=True)
+    if count <= DUMP_WHOLE:
+        np.save(os.path.join(out_dir, name + ".npy"), tri[:count].cpu().numpy())
+        return
+    idx = np.unique(np.random.default_rng(0xD0D0).integers(0, count, DUMP_DRAWS))
+    np.save(os.path.join(out_dir, name + "_sample.npy"), tri[torch.from_numpy(idx).to(dev)].cpu().numpy())
+    np.save(os.path.join(out_dir, name + "_sample_index.npy"), idx.astype(np.float64))
+
+
 def flush_c_stdio():
     import ctypes
 
@@ -354,9 +378,14 @@ def main():
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--no-secondary", action="store_true", help="skip the per-config entries (configs[1], [3], [4]) and the data-dependence line")
     ap.add_argument("--no-pmc", action="store_true", help="do not run the rocprofv3 --pmc child passes (roofline.traffic, VALU counts)")
-    ap.add_argument("--what-if", action="store_true", help="also time the matrix-core what-if of the tile kernel (needs a library built with make WHATIF=1)")
+    ap.add_argument("--what-if", action="store_true", help="with --full, also time the matrix-core what-if of the tile kernel (needs a library built with make WHATIF=1)")
     ap.add_argument("--exchange", choices=("auto", "gather", "keep"), default="auto",
                     help="N>1: gather the spans on rank 0 (the BASELINE formulation) or keep every span on its rank; auto = gather up to 2 GB of output")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also measure and check everything else: kernel phases and roofline, the PMC passes, "
+                         "the CPU baseline and parity, the per-config entries, the data-dependence line, the N-rank diagnostics")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed to DIR/<name>.npy (float32; a fixed sample of a large matrix)")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.pmc_child:
@@ -364,6 +393,8 @@ def main():
         return
     if args.gpus < 1:
         sys.exit("bench.py: --gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        sys.exit("bench.py: --steps must be >= 1 and --warmup >= 0")
     backend = os.environ.get("DSH_BENCH_BACKEND", "nccl")
     if "WORLD_SIZE" not in os.environ:
         if args.gpus > 1:
@@ -660,6 +691,24 @@ def run(args, backend, world, rank, line, dist_on):
     ms_per_step = dt / args.steps * 1e3
     value = total_pairs * args.steps / dt
     line.update({"value": value, "ms_per_step": ms_per_step})
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, torch, dev, full, total_pairs if gather else my_pairs, "distances" if gather else "rank0_rows")
+    line["config"] = {"workload": "BASELINE configs[2]: %d synthetic sketches, p=%d (%d B each), all-pairs dist on MI355X" % (n, p, m),
+                      "n_sketches": n, "p": p, "k": K, "estimator": "ERTL_MLE", "result": "JI",
+                      "sharding": ("row sets: a tile-aligned row range of the final triangle per rank + top-up tile rows from its bottom (dsh_balance_rowsets: equal tiles + prepare per rank), plane matrix laid out per rank; pipelined point-to-point send of each rank's parts to rank 0, which puts the rows into place; no un-permute" if rows_of is not None else
+                                   "tile-count-balanced row ranges of the final triangle, one per rank (plane matrix laid out per range); point-to-point send of each span into place on rank 0, no un-permute") if multi else "single GPU"}
+    if multi:
+        line["multi_gpu"] = {
+            "ranks": world, "rccl_ranks": dist.get_world_size() if backend == "nccl" else 0, "backend": backend,
+            "exchange": exchange if gather else "none: every rank keeps its span (output %.1f GB > %.1f GB; --exchange gather collects it)" % (4 * total_pairs / 1e9, GATHER_LIMIT_BYTES / 1e9),
+            "exchange_library": rccl_info, "probe": probe, "row_bounds": bounds if rows_of is None else None,
+            "row_sets": rows_of.describe() if rows_of is not None else None, "pairs_per_rank": sizes,
+            "phase_ms_max_over_ranks": {"compute_incl_prepare": round(phases[0], 4), "exchange" if not use_cabi else "exchange_exposed_after_last_kernel": round(phases[1], 4)},
+            "exchange_bytes_into_rank0": 4 * (total_pairs - sizes[0]) if gather else 0,
+        }
+    if not args.full:  # a plain run ends with the headline; everything below is --full
+        ctx.close()
+        return
     gathered_variant = None
     if multi and not gather and args.exchange == "auto":
         # the second figure: the same step with every span collected on rank 0 (what bounds a configs[3]-sized job on 8 GPUs)
@@ -800,10 +849,6 @@ def run(args, backend, world, rank, line, dist_on):
         parity = par2 if parity is None else {**parity, "rank0_span_vs_cpu": par2}
 
     line.update({
-        "config": {"workload": "BASELINE configs[2]: %d synthetic sketches, p=%d (%d B each), all-pairs dist on MI355X" % (n, p, m),
-                   "n_sketches": n, "p": p, "k": K, "estimator": "ERTL_MLE", "result": "JI",
-                   "sharding": ("row sets: a tile-aligned row range of the final triangle per rank + top-up tile rows from its bottom (dsh_balance_rowsets: equal tiles + prepare per rank), plane matrix laid out per rank; pipelined point-to-point send of each rank's parts to rank 0, which puts the rows into place; no un-permute" if rows_of is not None else
-                                "tile-count-balanced row ranges of the final triangle, one per rank (plane matrix laid out per range); point-to-point send of each span into place on rank 0, no un-permute") if multi else "single GPU"},
         "roofline": roofline,
         "cpu_baseline": cpu,
         "parity_vs_cpu": parity,
@@ -812,17 +857,9 @@ def run(args, backend, world, rank, line, dist_on):
     if multi:
         diag = multi_gpu_diagnostics(ctx, torch, dist, dashing_amd, multigpu, dev, regs_d, n, p, rank, world, rows_of, bounds, NPARTS, use_cabi,
                                      km, reps, phase.get("mine_ms", [0.0, 0.0]), my_pairs, ms_per_step, buf, gather)
-        line["multi_gpu"] = {
-            **diag,
-            "ranks": world, "rccl_ranks": dist.get_world_size() if backend == "nccl" else 0, "backend": backend,
-            "exchange": exchange if gather else "none: every rank keeps its span (output %.1f GB > %.1f GB; --exchange gather collects it)" % (4 * total_pairs / 1e9, GATHER_LIMIT_BYTES / 1e9),
-            "exchange_library": rccl_info, "probe": probe, "row_bounds": bounds if rows_of is None else None,
-            "row_sets": rows_of.describe() if rows_of is not None else None, "pairs_per_rank": sizes,
-            "phase_ms_max_over_ranks": {"compute_incl_prepare": round(phases[0], 4), "exchange" if not use_cabi else "exchange_exposed_after_last_kernel": round(phases[1], 4),
-                                        "k_pair_counts": round(kphase[0], 4), "k_finalize": round(kphase[1], 4), "prepare": round(kphase[2], 4)},
-            "exchange_bytes_into_rank0": 4 * (total_pairs - sizes[0]) if gather else 0,
-            "gathered_variant": gathered_variant,
-        }
+        mg = line["multi_gpu"]
+        mg["phase_ms_max_over_ranks"].update({"k_pair_counts": round(kphase[0], 4), "k_finalize": round(kphase[1], 4), "prepare": round(kphase[2], 4)})
+        line["multi_gpu"] = {**diag, **mg, "gathered_variant": gathered_variant}
 
     if want_cfg:
         # ---- per-config entries: each guarded so that a failure costs its entry, not the line

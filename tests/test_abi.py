@@ -128,6 +128,28 @@ def test_bench_gpus_flag_never_falls_back_to_one_gpu():
     assert r.returncode != 0 and b"refusing" in r.stderr
 
 
+def test_bench_dump_outputs_whole_or_fixed_sample(tmp_path):
+    """`bench.py --dump-outputs DIR`: a matrix up to DUMP_WHOLE floats is written whole; a larger one as the same seeded
+    sample of positions every time (values + positions), float32 / float64, within 64 MB"""
+    import torch
+
+    import bench
+
+    small = torch.arange(1000, dtype=torch.float32)
+    bench.dump_outputs(str(tmp_path / "a"), torch, "cpu", small, 999, "distances")
+    got = np.load(tmp_path / "a" / "distances.npy")
+    assert got.dtype == np.float32 and (got == np.arange(999)).all()
+    count = bench.DUMP_WHOLE + 12345  # (below 2^24: every position is exact as a float32 value)
+    big = torch.arange(count + 7, dtype=torch.float32)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), torch, "cpu", big, count, "distances")
+    vals, idx = np.load(tmp_path / "b" / "distances_sample.npy"), np.load(tmp_path / "b" / "distances_sample_index.npy")
+    assert vals.dtype == np.float32 and idx.dtype == np.float64 and vals.size == idx.size > bench.DUMP_DRAWS // 2
+    assert (np.diff(idx) > 0).all() and idx[0] >= 0 and idx[-1] < count and (vals == idx).all()
+    assert (np.load(tmp_path / "c" / "distances_sample_index.npy") == idx).all()
+    assert sum(f.stat().st_size for f in (tmp_path / "b").iterdir()) <= 64 << 20
+
+
 def test_row_set_helpers_are_pure_host_functions():
     """dsh_balance_rowsets / dsh_rowsets_rank / dsh_exchange_mode need no device: the partition every rank computes for
     itself, how a rank's buffer is laid out under the exchange and how many floats it holds"""

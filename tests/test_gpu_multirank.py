@@ -108,7 +108,7 @@ def test_bench_gpus_flag_launches_ranks():
     one-GPU box the two ranks share cuda:0 over gloo (DSH_BENCH_BACKEND=gloo, a dry run of the N-rank code path)."""
     import json
 
-    r = _bench(["--gpus", "2", "--steps", "2", "--warmup", "1"], {"DSH_BENCH_BACKEND": "gloo", "DSH_BENCH_N": "3000"})
+    r = _bench(["--full", "--gpus", "2", "--steps", "2", "--warmup", "1"], {"DSH_BENCH_BACKEND": "gloo", "DSH_BENCH_N": "3000"})
     out = r.stdout.decode()
     assert r.returncode == 0, (out + r.stderr.decode())[-3000:]
     lines = [l for l in out.splitlines() if l.startswith("{")]
@@ -134,7 +134,7 @@ def test_bench_gpus_flag_refuses_missing_devices():
 
 
 def test_bench_measures_hbm_traffic_itself():
-    """roofline.traffic of the default bench line comes from two rocprofv3 --pmc child passes of the run itself (not only
+    """roofline.traffic of the --full bench line comes from two rocprofv3 --pmc child passes of the run itself (not only
     from the committed profiles/pmc_pair_kernel.json): non-null, of the size the tile kernel is known to move, and within
     a few percent of the algorithm-independent floor-to-ceiling window (compulsory bytes .. streaming-model bytes)"""
     import json
@@ -142,7 +142,7 @@ def test_bench_measures_hbm_traffic_itself():
 
     if shutil.which("rocprofv3") is None:
         pytest.skip("rocprofv3 not installed")
-    r = _bench(["--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-secondary"], {"DSH_BENCH_N": "4000"})
+    r = _bench(["--full", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-secondary"], {"DSH_BENCH_N": "4000"})
     out = r.stdout.decode()
     assert r.returncode == 0, (out + r.stderr.decode())[-3000:]
     line = json.loads([l for l in out.splitlines() if l.startswith("{")][-1])
@@ -153,9 +153,35 @@ def test_bench_measures_hbm_traffic_itself():
     streaming = (n * (n - 1) // 2) * (2 * (1 << p) + 4)
     assert compulsory < rf["traffic"] < streaming
     # --no-pmc: the hash-checked file or null, never a child pass
-    r = _bench(["--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--no-secondary", "--no-pmc"], {"DSH_BENCH_N": "4000"})
+    r = _bench(["--full", "--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--no-secondary", "--no-pmc"], {"DSH_BENCH_N": "4000"})
     line = json.loads([l for l in r.stdout.decode().splitlines() if l.startswith("{")][-1])
     assert "measured in this run" not in line["roofline"]["traffic_note"]
+
+
+def test_bench_plain_run_is_the_headline_and_dumps_its_last_step(tmp_path, oracle):
+    """a plain run (no --full) times exactly --steps steps and prints the headline alone; --dump-outputs writes the matrix
+    its last step left for the caller: the distances of the bench's seeded sketches, as the CPU oracle computes them"""
+    import json
+
+    import numpy as np
+
+    from dashing_amd import synth
+
+    n = 1000
+    r = _bench(["--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path / "out")], {"DSH_BENCH_N": str(n)})
+    out = r.stdout.decode()
+    assert r.returncode == 0, (out + r.stderr.decode())[-3000:]
+    lines = [l for l in out.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, out[-3000:]
+    line = json.loads(lines[0])
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["unit"] == "pairs/s" and line["higher_is_better"] is True
+    assert line["ms_per_step"] > 0 and line["value"] == pytest.approx(n * (n - 1) // 2 / (line["ms_per_step"] * 1e-3), rel=1e-9)
+    assert not {"roofline", "cpu_baseline", "parity_vs_cpu", "configs", "data_dependence"} & set(line), sorted(line)
+    assert os.listdir(tmp_path / "out") == ["distances.npy"]
+    got = np.load(tmp_path / "out" / "distances.npy")
+    assert got.dtype == np.float32 and got.size == n * (n - 1) // 2
+    want = oracle.dist_tri(synth.survey_sketches(n, 14, seed=0x5EED0000)[0])
+    assert np.allclose(got, want, rtol=1e-6, atol=1e-15)
 
 
 def test_bench_falls_back_when_the_library_cannot_load_rccl():
@@ -167,7 +193,7 @@ def test_bench_falls_back_when_the_library_cannot_load_rccl():
 
     common = {"DSH_BENCH_FORCE_DIST": "1", "DSH_BENCH_N": "3000", "MASTER_PORT": "29533"}
     common["MASTER_PORT"] = str(_free_port())
-    r = _bench(["--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-secondary", "--no-pmc"], dict(common, DSH_RCCL_LIB="/nonexistent/librccl.so"))
+    r = _bench(["--full", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-secondary", "--no-pmc"], dict(common, DSH_RCCL_LIB="/nonexistent/librccl.so"))
     out = r.stdout.decode()
     assert r.returncode == 0, (out + r.stderr.decode())[-3000:]
     lines = [l for l in out.splitlines() if l.startswith("{")]
@@ -176,7 +202,7 @@ def test_bench_falls_back_when_the_library_cannot_load_rccl():
     assert mg["exchange"] == "torch.distributed" and mg["rccl_ranks"] == 1
     assert mg["exchange_library"]["available_on_rank0"] is False and "cabi_fallback_reason" in mg["exchange_library"]
     assert json.loads(lines[0])["parity_vs_cpu"]["assembled_equals_single_gpu"] is True
-    r = _bench(["--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-secondary", "--no-pmc"], dict(common, MASTER_PORT=str(_free_port())))
+    r = _bench(["--full", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-secondary", "--no-pmc"], dict(common, MASTER_PORT=str(_free_port())))
     out = r.stdout.decode()
     assert r.returncode == 0, (out + r.stderr.decode())[-3000:]
     line = json.loads([l for l in out.splitlines() if l.startswith("{")][-1])
@@ -457,7 +483,7 @@ def test_bench_two_ranks_run_the_cabi_exchange_over_the_stand_in(tmp_path):
 
     if not os.path.exists(MOCK):
         subprocess.check_call(["make", "-s", "-C", os.path.dirname(MOCK)])
-    r = _bench(["--gpus", "2", "--steps", "3", "--warmup", "1"],
+    r = _bench(["--full", "--gpus", "2", "--steps", "3", "--warmup", "1"],
                {"DSH_BENCH_BACKEND": "gloo", "DSH_BENCH_EXCHANGE": "cabi-mock", "DSH_RCCL_LIB": MOCK, "DSH_BENCH_N": "3000",
                 "MOCK_RCCL_TIMEOUT_S": "240", "DSH_BENCH_PING_MB": "4"}, timeout=600)
     out = r.stdout.decode()
@@ -506,7 +532,7 @@ def test_bench_probe_falls_back_when_the_exchange_does_not_reproduce_the_matrix(
     if not os.path.exists(MOCK):
         subprocess.check_call(["make", "-s", "-C", os.path.dirname(MOCK)])
     for inject, want_path in ((1, "finalize_signal = 0"), (2, "fallback")):
-        r = _bench(["--gpus", "2", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"],
+        r = _bench(["--full", "--gpus", "2", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"],
                    {"DSH_BENCH_BACKEND": "gloo", "DSH_BENCH_EXCHANGE": "cabi-mock", "DSH_RCCL_LIB": MOCK, "DSH_BENCH_N": "2000",
                     "MOCK_RCCL_TIMEOUT_S": "240", "DSH_BENCH_NO_PING": "1", "DSH_BENCH_INJECT_PROBE_FAIL": str(inject)}, timeout=600)
         out = r.stdout.decode()

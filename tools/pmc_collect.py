@@ -3,7 +3,7 @@
 with the hash of the kernel sources it was measured on.
 
   python tools/pmc_collect.py --tag r2a [--env DSH_BENCH_N=100000 --env DSH_BENCH_P=10] [--steps 3]
-      [--passes kt,fetch,write,sq1,sq2] [--cmd "python bench.py --no-cpu-baseline"]
+      [--passes kt,fetch,write,sq1,sq2] [--cmd "python bench.py --full --no-cpu-baseline"]
 
 Passes (each its own process; --pmc is never combined with a trace domain other than --kernel-trace,
 as MI355X_MICROARCH.md / the gpurun rules prescribe):
@@ -83,7 +83,7 @@ def main():
     ap.add_argument("--env", action="append", default=[])
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--passes", default="kt,fetch,write,sq1,sq2")
-    ap.add_argument("--cmd", default="python %s --no-cpu-baseline --no-secondary --no-pmc" % os.path.join(ROOT, "bench.py"))
+    ap.add_argument("--cmd", default="python %s --full --no-cpu-baseline --no-secondary --no-pmc" % os.path.join(ROOT, "bench.py"))
     args = ap.parse_args()
     env = dict(kv.split("=", 1) for kv in args.env)
     outdir = os.path.join(ROOT, "gpurun_out", args.tag)
