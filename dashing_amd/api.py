@@ -22,6 +22,7 @@ SYMBOLS = [
     "dsh_backend_name", "dsh_device_count", "dsh_create", "dsh_destroy", "dsh_last_error",
     "dsh_synchronize", "dsh_sketches_alloc", "dsh_upload_sketches", "dsh_download_sketches", "dsh_copy_sketches_device",
     "dsh_attach_device_sketches", "dsh_sketch_batch", "dsh_sketch_batch_async", "dsh_sketch_batch_device", "dsh_sketch_fastx_batch_async",
+    "dsh_sketch_records", "dsh_sketch_records_async", "dsh_sketch_records_device",
     "dsh_clear_sketches", "dsh_cardinalities", "dsh_dist_rows", "dsh_dist_rows_device",
     "dsh_dist_rows_async", "dsh_dist_rows_device_async", "dsh_wait", "dsh_wait_event",
     "dsh_event_record", "dsh_event_wait", "dsh_event_query",
@@ -100,6 +101,9 @@ def load_library():
     lib.dsh_sketch_batch_async.argtypes = [vp, vp, vp, C.c_uint32, u64, i32, i32]
     lib.dsh_sketch_fastx_batch_async.argtypes = [vp, vp, vp, vp, C.c_uint32, u64, i32, i32, vp]
     lib.dsh_sketch_batch_device.argtypes = [vp, vp, vp, C.c_uint32, u64, i32, i32]
+    lib.dsh_sketch_records.argtypes = [vp, vp, vp, C.c_uint32, u64, i32, i32, vp]
+    lib.dsh_sketch_records_async.argtypes = [vp, vp, vp, C.c_uint32, u64, i32, i32]
+    lib.dsh_sketch_records_device.argtypes = [vp, vp, vp, C.c_uint32, u64, i32, i32]
     lib.dsh_clear_sketches.argtypes = [vp, u64, u64]
     lib.dsh_cardinalities.argtypes = [vp, i32, vp]
     lib.dsh_dist_rows.argtypes = [vp, i32, i32, i32, u64, u64, vp]
@@ -170,7 +174,7 @@ def backend_name():
     return load_library().dsh_backend_name().decode()
 
 
-ABI_VERSION = 6  # include/dashing_hip.h DSH_ABI_VERSION this binding was written against
+ABI_VERSION = 7  # include/dashing_hip.h DSH_ABI_VERSION this binding was written against
 
 
 def abi_version():
@@ -433,6 +437,29 @@ class Context:
     def sketch_batch_device(self, seq_ptr, genome_off, first_slot=0, k=31, canon=True):
         off = np.ascontiguousarray(genome_off, np.uint64)
         self._ck(self._lib.dsh_sketch_batch_device(
+            self._h, C.c_void_p(seq_ptr), off.ctypes.data, off.size - 1, first_slot, k, int(bool(canon))))
+
+    # ---- per-record sketches (dsh_sketch_records*): record r = seq[rec_off[r]:rec_off[r+1]], no separators, its row is
+    # OVERWRITTEN with the record's own registers (all zero for a record shorter than k)
+    def sketch_records(self, seq, rec_off, first_slot=0, k=31, canon=True, want_regs=True):
+        seq = np.ascontiguousarray(seq, np.uint8)
+        off = np.ascontiguousarray(rec_off, np.uint64)
+        nr = off.size - 1
+        out = np.zeros((nr, 1 << self.p), np.uint8) if want_regs else None
+        self._ck(self._lib.dsh_sketch_records(
+            self._h, seq.ctypes.data if seq.size else None, off.ctypes.data, nr, first_slot, k,
+            int(bool(canon)), out.ctypes.data if want_regs else None))
+        return out
+
+    def sketch_records_async(self, seq_pinned, rec_off, first_slot=0, k=31, canon=True):
+        """seq_pinned: numpy view of PinnedArray memory; complete after wait()"""
+        off = np.ascontiguousarray(rec_off, np.uint64)
+        self._ck(self._lib.dsh_sketch_records_async(
+            self._h, seq_pinned.ctypes.data, off.ctypes.data, off.size - 1, first_slot, k, int(bool(canon))))
+
+    def sketch_records_device(self, seq_ptr, rec_off, first_slot=0, k=31, canon=True):
+        off = np.ascontiguousarray(rec_off, np.uint64)
+        self._ck(self._lib.dsh_sketch_records_device(
             self._h, C.c_void_p(seq_ptr), off.ctypes.data, off.size - 1, first_slot, k, int(bool(canon))))
 
     # ---- compare waist

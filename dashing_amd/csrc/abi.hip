@@ -56,7 +56,7 @@ static void release_ctx(dsh_ctx *c)
     for (DevBuf *b : {&c->gather_full, &c->gather_local, &c->regs_own, &c->card, &c->planes, &c->exc, &c->exc_n, &c->excv,
                       &c->keys, &c->tailhist, &c->hist, &c->cidx_rec, &c->cidx_ent, &c->colS_n, &c->colS_key, &c->colS_card, &c->colS_th, &c->colS_rl, &c->rowoff, &c->xch_stage, &c->xch_tab, &c->place_tab, &c->sig, &c->perm, &c->items, &c->cum, &c->tiles,
                       &c->outbuf, &c->outbuf2[0], &c->outbuf2[1], &c->seqbuf, &c->workbuf, &c->phase_cyc, &c->rawbuf, &c->fx_tab,
-                      &c->fx_summ, &c->fx_state, &c->fx_declen, &c->fx_status})
+                      &c->fx_summ, &c->fx_state, &c->fx_declen, &c->fx_status, &c->recbuf})
         b->release();
     if (c->pin_perm) (void)hipHostFree(c->pin_perm);
     c->pin_perm = nullptr;
@@ -67,7 +67,8 @@ static void release_ctx(dsh_ctx *c)
     c->pin_xch.release();
     c->pin_sig.release();
     c->pin_fx.release();
-    for (hipEvent_t *e : {&c->ev_fx, &c->ev_work, &c->ev_lists, &c->ev_perm, &c->ev_keys, &c->ev_filled[0], &c->ev_filled[1],
+    c->pin_rec.release();
+    for (hipEvent_t *e : {&c->ev_fx, &c->ev_work, &c->ev_rec, &c->ev_lists, &c->ev_perm, &c->ev_keys, &c->ev_filled[0], &c->ev_filled[1],
                           &c->ev_drained[0], &c->ev_drained[1], &c->ev_aux_fork, &c->ev_aux_join, &c->ev_xch_tab, &c->ev_place_done, &c->ev_first_tiles, &c->ev_sig}) {
         if (*e) (void)hipEventDestroy(*e);
         *e = nullptr;
@@ -240,6 +241,8 @@ int dsh_clear_sketches(dsh_ctx *c, uint64_t first, uint64_t n)
     return DSH_OK;
 }
 
+static int run_sketch_work(dsh_ctx *c, const uint8_t *d_seq, const std::vector<SketchWork> &work, int k, int canon);
+
 static int sketch_common(dsh_ctx *c, const uint8_t *d_seq, const uint64_t *genome_off,
                          uint32_t n_genomes, uint64_t first_slot, int k, int canon)
 {
@@ -276,6 +279,12 @@ static int sketch_common(dsh_ctx *c, const uint8_t *d_seq, const uint64_t *genom
             work.push_back(w);
         }
     }
+    return run_sketch_work(c, d_seq, work, k, canon);
+}
+
+// upload a k_sketch work list and launch it (sketch_common; the long records of dsh_sketch_records)
+static int run_sketch_work(dsh_ctx *c, const uint8_t *d_seq, const std::vector<SketchWork> &work, int k, int canon)
+{
     if (work.empty()) return DSH_OK;
     // the work list travels through page-locked staging (rewritten only after its previous upload has run),
     // so nothing here waits: the blocking entry points synchronise, dsh_sketch_batch_async returns
@@ -365,6 +374,145 @@ int dsh_sketch_batch_device(dsh_ctx *c, const void *d_seq, const uint64_t *genom
     if (n_genomes == 0) return DSH_OK;
     if (!d_seq || ((uintptr_t)d_seq & 31)) return fail(c, DSH_EINVAL, "d_seq must be 32-byte aligned and padded by 128 bytes");
     rc = sketch_common(c, (const uint8_t *)d_seq, genome_off, n_genomes, first_slot, k, canon);
+    if (rc) return rc;
+    invalidate(c);
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return DSH_OK;
+}
+
+// ---- per-record sketches: one row per record, overwritten (k_sketch_records)
+// The host splits the records by length.  Records that fit a run of kRecRunSpan bases go to k_sketch_records in runs of
+// whole consecutive records (a workgroup each); longer ones are ordinary genomes for k_sketch, after their rows are
+// cleared.  Above kMaxPRecords every row is cleared and all records take k_sketch (its GLOBAL variant).
+// rec_off is relative to d_seq (32-byte aligned, padded by 128 bytes).
+static int records_common(dsh_ctx *c, const uint8_t *d_seq, const uint64_t *rec_off, uint32_t n, uint64_t first_slot, int k,
+                          int canon)
+{
+    uint8_t *regs = (uint8_t *)c->regs_own.ptr;
+    const int p = c->p;
+    if (p > kMaxPRecords) {
+        HIPCHK(c, hipMemsetAsync(regs + (first_slot << p), 0, (size_t)n << p, c->stream));
+        return sketch_common(c, d_seq, rec_off, n, first_slot, k, canon);
+    }
+    std::vector<RecRun> runs;
+    std::vector<uint2> segs;
+    std::vector<uint32_t> zero;  // rows of the long records
+    std::vector<SketchWork> work;
+    uint64_t total_subs = 0;
+    for (uint32_t r = 0; r < n; ++r)
+        if (rec_off[r + 1] - (rec_off[r] & ~31ull) > kRecRunSpan) total_subs += (rec_off[r + 1] - (rec_off[r] & ~31ull) + kSketchSub - 1) / kSketchSub;
+    // (sketch_common's rule for the sub-chunks per workgroup)
+    const uint32_t subs_cap = p <= 13 ? 16u : (p == 14 ? 64u : 128u);
+    const uint32_t kSubsPerWG = (uint32_t)std::min<uint64_t>(subs_cap, std::max<uint64_t>(16, total_subs / 1024));
+    RecRun cur{};
+    bool open = false;
+    auto close = [&]() {
+        if (open) runs.push_back(cur);
+        open = false;
+    };
+    for (uint32_t r = 0; r < n; ++r) {
+        const uint64_t b = rec_off[r], e = rec_off[r + 1];
+        const uint64_t slot = first_slot + r;
+        if (e - (b & ~31ull) > kRecRunSpan) {  // long: k_sketch
+            close();
+            zero.push_back((uint32_t)slot);
+            const uint64_t c0 = b & ~31ull;
+            const uint64_t nsub = (e - c0 + kSketchSub - 1) / kSketchSub;
+            if (e - b < (uint64_t)k) continue;
+            for (uint64_t s = 0; s < nsub; s += kSubsPerWG)
+                work.push_back(SketchWork{b, e, c0 + s * kSketchSub, (uint32_t)std::min<uint64_t>(kSubsPerWG, nsub - s), (uint32_t)slot});
+            continue;
+        }
+        if (open && (e - cur.base > kRecRunSpan || cur.nrec == kRecRunRecs || (e > b && cur.nseg == kRecRunSegs))) close();
+        if (!open) {
+            cur = RecRun{b & ~31ull, (uint32_t)segs.size(), 0, (uint32_t)slot, 0, 0, 0};
+            open = true;
+        }
+        if (e > b) {
+            segs.push_back(make_uint2((uint32_t)(b - cur.base), cur.nrec));
+            ++cur.nseg;
+            cur.span = (uint32_t)(e - cur.base);
+        }
+        ++cur.nrec;
+    }
+    close();
+    // one upload: runs, segments, rows to clear
+    const size_t rb = runs.size() * sizeof(RecRun), sb = segs.size() * sizeof(uint2), zb = zero.size() * sizeof(uint32_t);
+    const size_t so = (rb + 15) & ~(size_t)15, zo = so + ((sb + 15) & ~(size_t)15), tot = zo + zb;
+    if (tot) {
+        if (c->rec_in_flight) {
+            HIPCHK(c, hipEventSynchronize(c->ev_rec));
+            c->rec_in_flight = false;
+        }
+        HIPCHK(c, c->pin_rec.ensure(tot));
+        HIPCHK(c, c->recbuf.ensure(tot));
+        uint8_t *h = (uint8_t *)c->pin_rec.ptr;
+        if (rb) std::memcpy(h, runs.data(), rb);
+        if (sb) std::memcpy(h + so, segs.data(), sb);
+        if (zb) std::memcpy(h + zo, zero.data(), zb);
+        HIPCHK(c, launch_upload(c->stream, c->recbuf.ptr, c->pin_rec.ptr, tot));
+        if (!c->ev_rec) HIPCHK(c, hipEventCreateWithFlags(&c->ev_rec, hipEventDisableTiming));
+        HIPCHK(c, hipEventRecord(c->ev_rec, c->stream));
+        c->rec_in_flight = true;
+    }
+    const uint8_t *d = (const uint8_t *)c->recbuf.ptr;
+    HIPCHK(c, launch_zero_rows(c->stream, (const uint32_t *)(d + zo), (uint32_t)zero.size(), p, regs));
+    HIPCHK(c, launch_sketch_records(c->stream, d_seq, (const RecRun *)d, (uint32_t)runs.size(), (const uint2 *)(d + so), k, p,
+                                    canon, regs));
+    return run_sketch_work(c, d_seq, work, k, canon);
+}
+
+// the records' checks: everything is refused before anything is enqueued
+static int records_check(dsh_ctx *c, const uint64_t *rec_off, uint32_t n_records, uint64_t first_slot, int k)
+{
+    int rc = sketch_check(c, rec_off, n_records, first_slot, k);
+    if (rc) return rc;
+    for (uint32_t r = 0; r < n_records; ++r)
+        if (rec_off[r + 1] < rec_off[r]) return fail(c, DSH_EINVAL, "rec_off not monotone at %u", r);
+    if (first_slot + n_records > 0xFFFFFFFFull) return fail(c, DSH_EINVAL, "slots beyond 2^32");
+    return DSH_OK;
+}
+
+int dsh_sketch_records_async(dsh_ctx *c, const uint8_t *seq, const uint64_t *rec_off, uint32_t n_records, uint64_t first_slot,
+                             int k, int canon)
+{
+    int rc = records_check(c, rec_off, n_records, first_slot, k);
+    if (rc) return rc;
+    if ((rc = bind(c))) return rc;
+    if (n_records == 0) return DSH_OK;
+    const uint64_t lo = rec_off[0], hi = rec_off[n_records];
+    if (hi > lo && !seq) return fail(c, DSH_EINVAL, "seq is NULL");
+    const uint64_t shift = lo & 31;
+    HIPCHK(c, c->seqbuf.ensure((size_t)(hi - lo) + shift + 256));
+    if (hi > lo)
+        HIPCHK(c, hipMemcpyAsync((uint8_t *)c->seqbuf.ptr + shift, seq + lo, (size_t)(hi - lo), hipMemcpyHostToDevice, c->stream));
+    std::vector<uint64_t> off(n_records + 1);
+    for (uint32_t r = 0; r <= n_records; ++r) off[r] = rec_off[r] - lo + shift;
+    rc = records_common(c, (const uint8_t *)c->seqbuf.ptr, off.data(), n_records, first_slot, k, canon);
+    if (rc) return rc;
+    invalidate(c);
+    return DSH_OK;
+}
+
+int dsh_sketch_records(dsh_ctx *c, const uint8_t *seq, const uint64_t *rec_off, uint32_t n_records, uint64_t first_slot, int k,
+                       int canon, uint8_t *regs_out)
+{
+    int rc = dsh_sketch_records_async(c, seq, rec_off, n_records, first_slot, k, canon);
+    if (rc) return rc;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (regs_out) return dsh_download_sketches(c, first_slot, n_records, regs_out);
+    return DSH_OK;
+}
+
+int dsh_sketch_records_device(dsh_ctx *c, const void *d_seq, const uint64_t *rec_off, uint32_t n_records, uint64_t first_slot,
+                              int k, int canon)
+{
+    int rc = records_check(c, rec_off, n_records, first_slot, k);
+    if (rc) return rc;
+    if ((rc = bind(c))) return rc;
+    if (n_records == 0) return DSH_OK;
+    if (!d_seq || ((uintptr_t)d_seq & 31)) return fail(c, DSH_EINVAL, "d_seq must be 32-byte aligned and padded by 128 bytes");
+    rc = records_common(c, (const uint8_t *)d_seq, rec_off, n_records, first_slot, k, canon);
     if (rc) return rc;
     invalidate(c);
     HIPCHK(c, hipStreamSynchronize(c->stream));

@@ -145,6 +145,10 @@ struct dsh_ctx {
     PinBuf pin_work;                    // sketch work list of the call in flight
     hipEvent_t ev_work = nullptr;
     bool work_in_flight = false;
+    PinBuf pin_rec;                     // dsh_sketch_records: runs, segments and rows to clear of the call in flight
+    DevBuf recbuf;
+    hipEvent_t ev_rec = nullptr;
+    bool rec_in_flight = false;
     PinBuf pin_lists;                   // tiles then items of the call in flight
     hipEvent_t ev_lists = nullptr;      // recorded after their upload; waited on before they are rewritten
     bool lists_in_flight = false;

@@ -10,6 +10,7 @@
 #include <atomic>
 #include <sys/stat.h>
 #include <unistd.h>
+#include <zlib.h>
 
 #include <algorithm>
 #include <cstdarg>
@@ -65,7 +66,12 @@ static void usage(const char *sub)
         "  --device INT             GPU ordinal [0]\n"
         "  --ngpus INT | --devices a,b,..  (dist) share the rows of the matrix between several GPUs: -b to a file is written\n"
         "                           by every GPU at its own offsets, other outputs are gathered to the first GPU over RCCL\n", kVersion, sub);
-    if (!std::strcmp(sub, "sketch")) {
+    if (!std::strcmp(sub, "sketch_by_seq") || !std::strcmp(sub, "dist_by_seq"))
+        std::fprintf(stderr, "  (by-seq: every sequence RECORD of every input, in input order, is one sketch, labelled by its name -- the\n"
+                             "   header up to the first space or tab; sketch_by_seq writes them with -o into this tool's own `sketch -o`\n"
+                             "   container + FILE.labels.gz, not upstream's by-seq layout; dist_by_seq --presketched FILE reads that back;\n"
+                             "   dist_by_seq refuses -Q, more than one device and -W)\n");
+    if (!std::strcmp(sub, "sketch") || !std::strcmp(sub, "sketch_by_seq")) {
         std::fprintf(stderr, "  -c, --skip-cached        skip genomes whose .hll already exists\n"
                              "  -o FILE                  write all sketches into one file (+ FILE.labels.gz) instead of one .hll per genome\n");
     } else {
@@ -776,9 +782,126 @@ static int hll_main(int argc, char **argv)
     return EXIT_SUCCESS;
 }
 
-static int dist_main(int argc, char **argv)
+// ---- per-record sketches: sketch_by_seq / dist_by_seq (src/dashing.cpp:470-557, src/sketch_and_cmp.h:540-602,
+// src/distbyseq.cpp).  Every record of every input, in input order, is one sketch named by its kseq name.
+struct Records {
+    std::vector<uint8_t> seq;    // the records back to back, no separator
+    std::vector<uint64_t> off;   // record r = seq[off[r], off[r+1])
+    std::vector<std::string> names;
+};
+
+static void read_records(const Opts &o, Records &R)
+{
+    for (const auto &path : o.inpaths) {
+        std::vector<uint64_t> st;
+        if (append_fastx_records(path, R.seq, st, R.names) < 0) die("Could not open %s", path.c_str());
+        R.off.insert(R.off.end(), st.begin(), st.end());
+    }
+    R.off.push_back(R.seq.size());
+    if (R.names.empty()) die("No sequence records in the inputs.");
+}
+
+// "<FILE>.labels.gz" back: one label per line
+static std::vector<std::string> read_labels_gz(const std::string &path)
+{
+    gzFile fp = gzopen(path.c_str(), "rb");
+    if (!fp) die("Could not open labels %s", path.c_str());
+    std::vector<std::string> v;
+    std::string cur;
+    char buf[1 << 16];
+    while (gzgets(fp, buf, sizeof buf)) {
+        cur += buf;
+        if (!cur.empty() && cur.back() == '\n') {
+            cur.pop_back();
+            v.push_back(cur);
+            cur.clear();
+        }
+    }
+    if (!cur.empty()) v.push_back(cur);
+    gzclose(fp);
+    return v;
+}
+
+// the records into slots [first, first + n): batches of at most kRecordsBatchBytes bases (or one record, if longer)
+// through two page-locked buffers that take turns behind tickets, dsh_sketch_records_async (rows overwritten)
+static const size_t kRecordsBatchBytes = (size_t)256 << 20;
+static void sketch_records_batched(dsh_ctx *ctx, const Records &R, uint64_t first, int k, int canon)
+{
+    const size_t n = R.names.size();
+    size_t cap = kRecordsBatchBytes;
+    for (size_t r = 0; r < n; ++r) cap = std::max<size_t>(cap, R.off[r + 1] - R.off[r]);
+    cap = std::min<size_t>(cap, std::max<size_t>(R.seq.size(), 1));
+    uint8_t *buf[2] = {(uint8_t *)dsh_alloc_host(cap), (uint8_t *)dsh_alloc_host(cap)};
+    if (!buf[0] || !buf[1]) die("could not allocate %zu bytes of pinned host memory", cap);
+    uint64_t ticket[2] = {0, 0};
+    bool used[2] = {false, false};
+    std::vector<uint64_t> off;
+    int b = 0;
+    for (size_t r0 = 0; r0 < n;) {
+        size_t r1 = r0 + 1;
+        while (r1 < n && R.off[r1 + 1] - R.off[r0] <= cap && r1 - r0 < ((size_t)1 << 30)) ++r1;
+        if (used[b]) DSH(ctx, dsh_event_wait(ctx, ticket[b]));
+        const size_t bytes = R.off[r1] - R.off[r0];
+        if (bytes) std::memcpy(buf[b], R.seq.data() + R.off[r0], bytes);
+        off.assign(R.off.begin() + r0, R.off.begin() + r1 + 1);
+        for (auto &x : off) x -= R.off[r0];
+        DSH(ctx, dsh_sketch_records_async(ctx, buf[b], off.data(), (uint32_t)(r1 - r0), first + r0, k, canon));
+        DSH(ctx, dsh_event_record(ctx, &ticket[b]));
+        used[b] = true;
+        b ^= 1;
+        r0 = r1;
+    }
+    DSH(ctx, dsh_wait(ctx));
+    dsh_free_host(buf[0]);
+    dsh_free_host(buf[1]);
+}
+
+static int sketch_by_seq_main(int argc, char **argv)
+{
+    Opts o = parse(argc, argv, false);
+    const std::string &output_file = o.out_sizes;
+    if (output_file.empty()) {
+        std::fprintf(stderr, "sketch_by_seq writes every record's sketch into ONE file: -o FILE is required.\n");
+        usage("sketch_by_seq");
+    }
+    Records R;
+    read_records(o, R);
+    const size_t n = R.names.size(), m = (size_t)1 << o.S;
+    CtxFuture cf(o.device, n, o.S);
+    dsh_ctx *ctx = cf.get();
+    sketch_records_batched(ctx, R, 0, o.k, o.canon);
+    std::vector<uint8_t> all(n * m);
+    DSH(ctx, dsh_download_sketches(ctx, 0, n, all.data()));
+    if (write_hll_multi(output_file, all.data(), n, o.S, o.estim)) die("Failed to write sketches to file");
+    if (write_labels_gz(output_file + ".labels.gz", R.names)) die("Failed to write sequence labels to file");
+    leave(ctx);
+    return EXIT_SUCCESS;
+}
+
+static int dist_main(int argc, char **argv, bool by_seq = false)
 {
     Opts o = parse(argc, argv, true);
+    // dist_by_seq: the records (or a sketch_by_seq file) take the place of the genomes, their names that of the paths
+    Records R;
+    std::vector<uint8_t> pre;  // --presketched: the sketch_by_seq stream
+    if (by_seq) {
+        if (!o.querypaths.empty()) die("dist_by_seq does not take -Q: every record is compared with every other.");
+        if (o.devices.size() > 1) die("dist_by_seq runs on one device: --ngpus / --devices are not supported.");
+        if (o.cache) die("dist_by_seq does not take -W: records have no per-genome sketch files to cache.");
+        if (o.presketched) {
+            if (o.inpaths.size() != 1) die("dist_by_seq --presketched takes ONE sketch_by_seq file.");
+            int p = 0;
+            size_t cnt = 0;
+            if (read_hll_multi(o.inpaths[0], pre, p, cnt)) die("Could not read sketches from %s", o.inpaths[0].c_str());
+            if (p != o.S) die("Sketches in %s have p=%d but -S is %d", o.inpaths[0].c_str(), p, o.S);
+            R.names = read_labels_gz(o.inpaths[0] + ".labels.gz");
+            if (R.names.size() != cnt) die("%s holds %zu sketches but its labels %zu names", o.inpaths[0].c_str(), cnt, R.names.size());
+        } else {
+            read_records(o, R);
+        }
+        o.inpaths = R.names;
+        o.avoid_sorting = 1;
+    }
     std::FILE *ofp = stdout, *pairofp = stdout;
     if (!o.out_sizes.empty() && !(ofp = std::fopen(o.out_sizes.c_str(), "w"))) die("Could not open file at %s for writing.", o.out_sizes.c_str());
     if (!o.out_dists.empty() && !(pairofp = std::fopen(o.out_dists.c_str(), "wb"))) die("Could not open file at %s for writing.", o.out_dists.c_str());
@@ -797,10 +920,17 @@ static int dist_main(int argc, char **argv)
     const size_t n = o.inpaths.size();
     const double t_start = now_s();
     since_launch("dist: options parsed, context thread about to start");
-    CtxFuture cf(o.device, n, o.S, o.presketched ? 0 : staging_bytes_for(o.inpaths));  // the HIP runtime comes up while the first batch is read
+    CtxFuture cf(o.device, n, o.S, (o.presketched || by_seq) ? 0 : staging_bytes_for(o.inpaths));  // the HIP runtime comes up while the first batch is read
     dsh_ctx *ctx = nullptr;
     const double t_fill0 = now_s();
-    if (o.presketched) {  // sketch.read(path), src/sketch_and_cmp.h:318-324
+    if (by_seq) {  // the records into [0, nr) and, as queries of an asymmetric measure, once more into [nr, n)
+        ctx = cf.get();
+        const size_t nrec = R.names.size();
+        for (size_t s0 = 0; s0 < n; s0 += nrec) {
+            if (o.presketched) DSH(ctx, dsh_upload_sketches(ctx, pre.data(), s0, nrec));
+            else sketch_records_batched(ctx, R, s0, o.k, o.canon);
+        }
+    } else if (o.presketched) {  // sketch.read(path), src/sketch_and_cmp.h:318-324
         ctx = cf.get();
         // read on all host threads into a staging matrix, upload in batches
         const size_t m = (size_t)1 << o.S, batch = std::max<size_t>(1, ((size_t)256 << 20) / m);
@@ -1070,12 +1200,14 @@ int main(int argc, char **argv)
     // if the host threads are needed elsewhere between the parallel regions.)
     since_launch("main() entered");
     if (argc < 2 || !std::strcmp(argv[1], "-h") || !std::strcmp(argv[1], "--help")) {
-        std::fprintf(stderr, "%s\nUsage: dashing-amd <subcommand> [options...]\nSubcommands:\n  sketch\n  dist (also: cmp, setdist)\n  union | fold | view   (utilities on .hll files)\n  printmat              (binary distance matrix -> text)\n  hll                   (cardinality of the k-mers of a set of files)\n", kVersion);
+        std::fprintf(stderr, "%s\nUsage: dashing-amd <subcommand> [options...]\nSubcommands:\n  sketch\n  dist (also: cmp, setdist)\n  sketch_by_seq | dist_by_seq   (one sketch per sequence record)\n  union | fold | view   (utilities on .hll files)\n  printmat              (binary distance matrix -> text)\n  hll                   (cardinality of the k-mers of a set of files)\n", kVersion);
         return EXIT_FAILURE;
     }
     const std::string sub(argv[1]);
     if (sub == "sketch") return sketch_main(argc - 1, argv + 1);
     if (sub == "dist" || sub == "cmp" || sub == "setdist") return dist_main(argc - 1, argv + 1);
+    if (sub == "sketch_by_seq") return sketch_by_seq_main(argc - 1, argv + 1);
+    if (sub == "dist_by_seq") return dist_main(argc - 1, argv + 1, /*by_seq=*/true);
     if (sub == "union") return union_main(argc - 1, argv + 1);
     if (sub == "view") return view_main(argc - 1, argv + 1);
     if (sub == "fold") return fold_main(argc - 1, argv + 1);

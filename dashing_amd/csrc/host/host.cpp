@@ -8,6 +8,7 @@
 #include <zlib.h>
 
 #include <algorithm>
+#include <cctype>
 #include <cerrno>
 #include <cstring>
 
@@ -337,16 +338,32 @@ struct FastxParser {
     int state = 0;
     bool at_line_start = true, skipping_line = false;
     size_t seq_len = 0, qual_len = 0;
+    // records mode (append_fastx_records): no separator; every record's start (bytes emitted before it) and its kseq
+    // name -- the header text behind '>' / '@' up to the first white space -- are kept instead
+    std::vector<uint64_t> *starts = nullptr;
+    std::vector<std::string> *names = nullptr;
+    uint64_t emitted = 0;
+    bool in_name = false;
     explicit FastxParser(Sink &s) : out(s) {}
     void take(const char *p, size_t len)  // a piece of a line's content
     {
-        if (skipping_line || len == 0) return;
+        if (len == 0) return;
+        if (skipping_line) {
+            if (in_name) {
+                size_t t = 0;
+                while (t < len && !std::isspace((unsigned char)p[t])) ++t;
+                names->back().append(p, t);
+                if (t < len) in_name = false;
+            }
+            return;
+        }
         if (std::memchr(p, '\r', len)) {  // rare: strip carriage returns the slow way
             for (size_t t = 0; t < len; ++t) {
                 if (p[t] == '\r') continue;
                 if (state == 1) {
                     out.push((uint8_t)p[t]);
                     ++seq_len;
+                    ++emitted;
                 } else if (state == 2) {
                     ++qual_len;
                 }
@@ -356,6 +373,7 @@ struct FastxParser {
         if (state == 1) {
             out.append((const uint8_t *)p, len);
             seq_len += len;
+            emitted += len;
         } else if (state == 2) {
             qual_len += len;
         }
@@ -373,11 +391,18 @@ struct FastxParser {
                 }
                 at_line_start = false;
                 if (state != 2 && (c == '>' || c == '@')) {  // new record header
-                    if (nrec) out.push('N');
+                    if (starts) {
+                        starts->push_back(emitted);
+                        names->emplace_back();
+                        in_name = true;
+                    } else if (nrec) {
+                        out.push('N');
+                    }
                     ++nrec;
                     state = 1;
                     seq_len = qual_len = 0;
                     skipping_line = true;
+                    ++i;  // (the '>' / '@' itself)
                 } else if (state == 1 && c == '+') {  // FASTQ separator line
                     state = 2;
                     skipping_line = true;
@@ -389,6 +414,7 @@ struct FastxParser {
             if (nl) {
                 at_line_start = true;
                 skipping_line = false;
+                in_name = false;
                 if (state == 2 && qual_len >= seq_len) state = 0;
                 i = e + 1;
             } else {
@@ -399,11 +425,14 @@ struct FastxParser {
 };
 
 template <class Sink>
-long parse_fastx(const std::string &path, Sink &sink)
+long parse_fastx(const std::string &path, Sink &sink, std::vector<uint64_t> *starts = nullptr,
+                 std::vector<std::string> *names = nullptr)
 {
     InStream in;  // plain text through read(2) (zlib's transparent mode copies every byte once more), gzip, zstd
     if (in.open(path) != 0) return -1;
     FastxParser<Sink> ps(sink);
+    ps.starts = starts;
+    ps.names = names;
     std::vector<char> buf(1 << 20);
     ssize_t n;
     while ((n = in.read(buf.data(), buf.size())) > 0) ps.feed(buf.data(), (size_t)n);
@@ -416,6 +445,23 @@ long append_fastx(const std::string &path, std::vector<uint8_t> &out)
 {
     VecSink s{out};
     return parse_fastx(path, s);
+}
+
+long append_fastx_records(const std::string &path, std::vector<uint8_t> &out, std::vector<uint64_t> &starts,
+                          std::vector<std::string> &names)
+{
+    const uint64_t base = out.size();
+    const size_t s0 = starts.size(), n0 = names.size();
+    VecSink s{out};
+    const long nrec = parse_fastx(path, s, &starts, &names);
+    if (nrec < 0) {
+        out.resize(base);
+        starts.resize(s0);
+        names.resize(n0);
+        return nrec;
+    }
+    for (size_t i = s0; i < starts.size(); ++i) starts[i] += base;
+    return nrec;
 }
 
 long append_fastx_into(const std::string &path, uint8_t *dst, size_t cap, size_t &len)

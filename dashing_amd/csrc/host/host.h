@@ -35,6 +35,11 @@ long append_fastx(const std::string &path, std::vector<uint8_t> &out);
 // Same into caller-owned memory (e.g. page-locked staging): appends at dst[len...] and advances len; -2 if the
 // `cap` bytes would not hold it.  An uncompressed file never yields more sequence bytes than its size.
 long append_fastx_into(const std::string &path, uint8_t *dst, size_t cap, size_t &len);
+// Records mode (sketch_by_seq / dist_by_seq): every record's sequence appended with NO separator; starts gets each
+// record's offset in `out`, names its kseq name (the header text behind '>' / '@' up to the first space or tab).  Same
+// inputs as append_fastx (FASTA, FASTQ also multi-line, gzip, zstd, pipes, CRLF).  Returns the number of records, or -1.
+long append_fastx_records(const std::string &path, std::vector<uint8_t> &out, std::vector<uint64_t> &starts,
+                          std::vector<std::string> &names);
 // The raw bytes of a plain file, as they lie on disk, appended at dst[len...] (the parse happens on the device:
 // dsh_sketch_fastx_batch_async).  Returns 0, -1 if the file cannot be opened or read, -2 if `cap` would not hold it (the
 // file grew since it was sized).

@@ -72,6 +72,24 @@ long dshh_append_fastx(const char *path, uint8_t *out, size_t cap, size_t *len)
     return n;
 }
 
+// records mode: sequence at out[*len ..) with no separator, record starts (offsets into out) and names ('\n'-joined);
+// -1 open failure, -2 a buffer too small
+long dshh_append_fastx_records(const char *path, uint8_t *out, size_t cap, size_t *len, uint64_t *starts, size_t starts_cap,
+                               char *names, size_t names_cap)
+{
+    std::vector<uint8_t> v;
+    std::vector<uint64_t> st;
+    std::vector<std::string> nm;
+    const long n = append_fastx_records(path, v, st, nm);
+    if (n < 0) return n;
+    if (*len + v.size() > cap || st.size() > starts_cap) return -2;
+    if (!v.empty()) std::memcpy(out + *len, v.data(), v.size());
+    for (size_t i = 0; i < st.size(); ++i) starts[i] = st[i] + *len;
+    if (pack(nm, names, names_cap) < 0) return -2;
+    *len += v.size();
+    return n;
+}
+
 // the CLI's streaming loader path: parse straight into caller-owned (page-locked) memory at dst[*len ..), no growth
 long dshh_append_fastx_into(const char *path, uint8_t *dst, size_t cap, size_t *len)
 {

@@ -22,6 +22,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <algorithm>
 #include <cstdlib>
 #include <mutex>
 #include <vector>
@@ -418,6 +419,179 @@ hipError_t launch_sketch(hipStream_t st, const uint8_t *seq, const SketchWork *w
     }
     if (k == 31) return launch_sketch_v<false, true, 31, 256>(st, seq, work, nwork, k, p, canon, regs, sketch_lds(rb, 256));
     return launch_sketch_v<false, true, 0, 256>(st, seq, work, nwork, k, p, canon, regs, sketch_lds(rb, 256));
+}
+
+
+// ---- per-record sketches (dsh_sketch_records) ------------------------------------------------
+// One workgroup owns a run of whole, consecutive records (kernels.h, RecRun): at most kRecRunSpan bases, so ONE step of
+// 256 lanes x 32 start positions covers it.  Phase A: every lane packs its 32 bases as k_sketch does (pack32_perm, the
+// right neighbour's words through LDS), and a k-mer start is valid iff its k bases are valid (V) AND no segment starts
+// inside it (S: bit i = a segment starts at base B + i).  Each valid k-mer leaves one word in LDS, indexed by its start
+// position: value | index << 6 | segment << (6 + p) (0 = no k-mer there; value >= 1).  Phase B writes the run's rows,
+// tile by tile: a tile of kRecTile word registers holds kRecTile >> p whole rows (p <= 12) or a kRecTile-register piece
+// of one row (p = 13 ... 17); the entries of the segments it covers are max-ed into it (ds_max_u32), then every lane packs
+// 16 registers to bytes and writes them with one 16-byte store -- the rows are OVERWRITTEN, whole, in one pass: no
+// pre-clear, no CAS, rows of records shorter than k come out zero.  The pack clears the tile behind itself.
+constexpr uint32_t kRecNT = 256;
+constexpr uint32_t kRecTile = 4096;                            // word registers of a tile (16 KiB)
+constexpr uint32_t kRecPairWords = kRecRunSpan / 32 * 33;      // one word per start position, 33 per lane (no bank conflicts)
+constexpr size_t kRecLds = (size_t)(kRecPairWords + kRecTile + 2 * kRecRunSegs + 1) * 4;
+
+template <bool CANON>
+__global__ __launch_bounds__(kRecNT) void k_sketch_records(const uint8_t *__restrict__ seq, const RecRun *__restrict__ runs,
+                                                           const uint2 *__restrict__ segs, int k, int p,
+                                                           uint8_t *__restrict__ regs)
+{
+    extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
+    uint32_t *pairs = lds;
+    uint32_t *tile = lds + kRecPairWords;
+    // (phase A only) the packed words of every lane and of the (empty) position behind the last: inside the tile
+    uint64_t *xF = reinterpret_cast<uint64_t *>(tile);
+    uint64_t *xR = xF + (kRecNT + 1);
+    uint32_t *xV = reinterpret_cast<uint32_t *>(xR + (kRecNT + 1));
+    uint32_t *sst = tile + kRecTile;      // segment starts relative to the run's base, then the run's end
+    uint32_t *sslot = sst + kRecRunSegs + 1;  // segment -> slot relative to slot0
+    const int tid = threadIdx.x;
+    const RecRun rr = runs[blockIdx.x];
+    const uint32_t nseg = rr.nseg, span = rr.span;
+
+    const uint32_t B = (uint32_t)tid * 32u;
+    uint64_t F0 = 0, R0 = 0;
+    uint32_t V0 = 0;
+    if (B < span) {
+        const uint4 *src = reinterpret_cast<const uint4 *>(seq + rr.base + B);
+        pack32_perm(src[0], src[1], F0, R0, V0);
+    }
+    for (uint32_t i = tid; i < nseg; i += kRecNT) {
+        const uint2 sg = segs[rr.seg0 + i];
+        sst[i] = sg.x;
+        sslot[i] = sg.y;
+    }
+    if (tid == 0) sst[nseg] = span;
+    __syncthreads();
+    if (B < span) {
+        const uint32_t lo = sst[0] > B ? sst[0] - B : 0u;  // (the run's first base need not be 32-aligned)
+        const uint32_t hi = span - B;
+        uint32_t rmask = hi >= 32 ? 0xFFFFFFFFu : ((1u << hi) - 1);
+        rmask = lo >= 32 ? 0u : (rmask & ~((1u << lo) - 1));
+        V0 &= rmask;
+    }
+    xF[tid] = F0; xR[tid] = R0; xV[tid] = V0;
+    if (tid == 0) { xF[kRecNT] = 0; xR[kRecNT] = 0; xV[kRecNT] = 0; }  // (span <= kRecRunSpan: nothing behind the last lane)
+    __syncthreads();
+    if (B < span) {
+        const uint64_t F1 = xF[tid + 1], R1 = xR[tid + 1];
+        const uint64_t V = (uint64_t)V0 | ((uint64_t)xV[tid + 1] << 32);
+        // the segment holding base B (-1 in front of the first) and the segment starts among bases B + 1 ... B + 63
+        uint32_t a = 0, b = nseg;
+        while (a < b) {
+            const uint32_t m = (a + b) >> 1;
+            if (sst[m] <= B) a = m + 1;
+            else b = m;
+        }
+        const int seg_b = (int)a - 1;
+        uint64_t S = 0;
+        for (uint32_t q = a; q < nseg && sst[q] < B + 64u; ++q) S |= 1ull << (sst[q] - B);
+        // a k-mer at j: bases j ... j + k - 1 valid, no segment starts at j + 1 ... j + k - 1
+        const uint32_t ok = (uint32_t)(valid_windows(V, k) & valid_windows(~S >> 1, k - 1));
+        const uint32_t sl = (uint32_t)S;
+        const uint64_t kmask = k == 32 ? ~0ull : ((1ull << (2 * k)) - 1);
+        const int fshift = 64 - 2 * k;
+        const uint64_t guard = 1ull << (p - 1);
+        uint32_t *out = pairs + (uint32_t)tid * 33u;
+#pragma unroll
+        for (int j = 0; j < 32; ++j) {
+            uint32_t e = 0;
+            if ((ok >> j) & 1u) {
+                const uint64_t fh = j ? ((F0 << (2 * j)) | (F1 >> (64 - 2 * j))) : F0;
+                const uint64_t rl = j ? ((R0 >> (2 * j)) | (R1 << (64 - 2 * j))) : R0;
+                const uint64_t fw = fh >> fshift, rc = rl & kmask;
+                const uint64_t h = wang64((CANON && rc < fw) ? rc : fw);
+                const uint32_t idx = (uint32_t)(h >> (64 - p));
+                const uint32_t val = (uint32_t)__builtin_clzll((h << p) | guard) + 1u;  // (exact: no high-word shortcut)
+                const uint32_t seg = (uint32_t)(seg_b + __builtin_popcount(sl & (j == 31 ? ~0u : ((2u << j) - 1u))));
+                e = val | (idx << 6) | (seg << (6 + p));
+            }
+            out[j] = e;
+        }
+    }
+    __syncthreads();
+    for (uint32_t w = tid; w < kRecTile; w += kRecNT) tile[w] = 0;  // (the exchange words lay here)
+    __syncthreads();
+
+    // Phase B: tiles in slot order
+    const uint32_t G = p <= 12 ? (kRecTile >> p) : 1u;        // rows per tile
+    const uint32_t pieces = p <= 12 ? 1u : ((1u << p) / kRecTile);  // tiles per row
+    const uint32_t imask = (1u << p) - 1u;
+    uint32_t sa = 0;  // first segment of the tile's rows
+    for (uint32_t r = 0; r < rr.nrec; r += G) {
+        const uint32_t nr = min(G, rr.nrec - r);
+        uint32_t sb = sa;
+        while (sb < nseg && sslot[sb] < r + nr) ++sb;
+        const uint32_t pa = sst[sa], pe = sst[sb];  // (sa == sb: an empty range)
+        for (uint32_t piece = 0; piece < pieces; ++piece) {
+            const uint32_t pbase = piece * kRecTile;
+            for (uint32_t x = pa + tid; x < pe; x += kRecNT) {
+                const uint32_t e = pairs[x + (x >> 5)];
+                if (!e) continue;
+                const uint32_t idx = (e >> 6) & imask;
+                uint32_t w;
+                if (pieces == 1) {
+                    w = ((sslot[e >> (6 + p)] - r) << p) | idx;
+                } else {
+                    w = idx - pbase;
+                    if (w >= kRecTile) continue;
+                }
+                atomicMax(&tile[w], e & 63u);  // ds_max_u32
+            }
+            __syncthreads();
+            const uint32_t nbytes = pieces == 1 ? (nr << p) : kRecTile;
+            if ((uint32_t)tid * 16u < nbytes) {
+                uint4 *t4 = reinterpret_cast<uint4 *>(tile) + tid * 4;
+                const uint4 q0 = t4[0], q1 = t4[1], q2 = t4[2], q3 = t4[3];
+                uint4 o;
+                o.x = q0.x | (q0.y << 8) | (q0.z << 16) | (q0.w << 24);
+                o.y = q1.x | (q1.y << 8) | (q1.z << 16) | (q1.w << 24);
+                o.z = q2.x | (q2.y << 8) | (q2.z << 16) | (q2.w << 24);
+                o.w = q3.x | (q3.y << 8) | (q3.z << 16) | (q3.w << 24);
+                const uint4 z = make_uint4(0, 0, 0, 0);
+                t4[0] = z; t4[1] = z; t4[2] = z; t4[3] = z;
+                *reinterpret_cast<uint4 *>(regs + ((uint64_t)(rr.slot0 + r) << p) + pbase + (uint32_t)tid * 16u) = o;
+            }
+            __syncthreads();
+        }
+        sa = sb;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_zero_rows(const uint32_t *__restrict__ slots, uint32_t nslots, int p,
+                                                   uint8_t *__restrict__ regs)
+{
+    const uint32_t chunks = (1u << p) >> 4;  // 16-byte pieces of a row
+    for (uint32_t s = blockIdx.x; s < nslots; s += gridDim.x) {
+        uint4 *row = reinterpret_cast<uint4 *>(regs + ((uint64_t)slots[s] << p));
+        for (uint32_t c = threadIdx.x; c < chunks; c += 256) row[c] = make_uint4(0, 0, 0, 0);
+    }
+}
+
+hipError_t launch_sketch_records(hipStream_t st, const uint8_t *seq, const RecRun *runs, uint32_t nruns, const uint2 *segs,
+                                 int k, int p, int canon, uint8_t *regs)
+{
+    if (nruns == 0) return hipSuccess;
+    const void *fn = canon ? reinterpret_cast<const void *>(k_sketch_records<true>)
+                           : reinterpret_cast<const void *>(k_sketch_records<false>);
+    hipError_t e = ensure_dynamic_lds(fn, kRecLds);
+    if (e != hipSuccess) return e;
+    if (canon) hipLaunchKernelGGL(k_sketch_records<true>, dim3(nruns), dim3(kRecNT), kRecLds, st, seq, runs, segs, k, p, regs);
+    else hipLaunchKernelGGL(k_sketch_records<false>, dim3(nruns), dim3(kRecNT), kRecLds, st, seq, runs, segs, k, p, regs);
+    return hipGetLastError();
+}
+
+hipError_t launch_zero_rows(hipStream_t st, const uint32_t *slots, uint32_t nslots, int p, uint8_t *regs)
+{
+    if (nslots == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_zero_rows, dim3(std::min<uint32_t>(nslots, 4096u)), dim3(256), 0, st, slots, nslots, p, regs);
+    return hipGetLastError();
 }
 
 }  // namespace dsh

@@ -55,10 +55,10 @@ extern "C" {
 typedef struct dsh_ctx dsh_ctx;
 
 /* ABI version: bumped whenever an entry point changes its signature or a table its layout (6: dsh_exchange_* take a
- * row-set table instead of bounds + world).  A host compiled against another DSH_ABI_VERSION links fine but would pass
+ * row-set table instead of bounds + world; 7: dsh_sketch_records*).  A host compiled against another DSH_ABI_VERSION links fine but would pass
  * shifted arguments: compare with dsh_abi_version() once at start-up.  (A bounds array handed to a function that now
  * parses a row-set table is refused, not over-read: its first word, 0, is not a valid world.) */
-#define DSH_ABI_VERSION 6
+#define DSH_ABI_VERSION 7
 int dsh_abi_version(void);
 
 /* ---- context ---------------------------------------------------------------------------- */
@@ -114,6 +114,23 @@ int dsh_sketch_batch_async(dsh_ctx *ctx, const uint8_t *seq_pinned, const uint64
 /* Same with `seq` already on the device (d_seq device pointer; genome_off stays on the host). */
 int dsh_sketch_batch_device(dsh_ctx *ctx, const void *d_seq, const uint64_t *genome_off,
                             uint32_t n_genomes, uint64_t first_slot, int k, int canon);
+/* Per-record sketches (upstream's sketch_by_seq / dist_by_seq, src/sketch_and_cmp.h:540-602): one sketch per RECORD.
+ * Record r is seq[rec_off[r] .. rec_off[r+1]), the records lie back to back with NO separator between them, and its
+ * registers go to slot first_slot + r.  k-mers never span two records, even where the bases on both sides of a boundary
+ * are valid; inside a record the rules of dsh_sketch_batch hold (case folded, a non-ACGT byte resets the window).
+ * Unlike dsh_sketch_batch the rows are OVERWRITTEN, not max-merged: afterwards row first_slot + r holds exactly the
+ * registers of record r alone, and a record shorter than k has an all-zero row.  Slots outside
+ * [first_slot, first_slot + n_records) are not touched.  k in [1,32], any p of dsh_sketches_alloc.
+ * Errors, returned before anything is enqueued: DSH_EINVAL for a rec_off that decreases, a k outside [1,32] or slots out
+ * of range; DSH_ESTATE before dsh_sketches_alloc.  The three forms take `seq` and their lifetimes exactly as the
+ * dsh_sketch_batch trio does (host, page-locked host + dsh_wait, device: 32-byte aligned and padded by 128 bytes, rec_off
+ * relative to d_seq and on the host). */
+int dsh_sketch_records(dsh_ctx *ctx, const uint8_t *seq, const uint64_t *rec_off, uint32_t n_records, uint64_t first_slot,
+                       int k, int canon, uint8_t *regs_out);
+int dsh_sketch_records_async(dsh_ctx *ctx, const uint8_t *seq_pinned, const uint64_t *rec_off, uint32_t n_records,
+                             uint64_t first_slot, int k, int canon);
+int dsh_sketch_records_device(dsh_ctx *ctx, const void *d_seq, const uint64_t *rec_off, uint32_t n_records,
+                              uint64_t first_slot, int k, int canon);
 /* The same with the PARSE on the device, as in the reference where Encoder::for_each(func, path) reads the records itself
  * (src/sketch_and_cmp.h:338-342): `raw` holds the bytes of plain FASTA files as they lie on disk -- genome g's at
  * raw[genome_off[g] .. genome_off[g] + raw_len[g]) (several files of one genome: back to back with a '\n' between them),
