@@ -439,7 +439,13 @@ static void fill_sketches(CtxFuture &cf, const Opts &o, bool write_files, bool s
                 // batch is retired).
                 uint8_t kind = 0;
                 for (const auto &f : files[i]) {
-                    if (len && dst[len - 1] != '\n') dst[len++] = '\n';
+                    if (len && dst[len - 1] != '\n') {
+                        if (len == cap) {  // (a file grew after its region was sized: no room for the separator)
+                            raw_ok = false;
+                            break;
+                        }
+                        dst[len++] = '\n';
+                    }
                     const size_t at = len;
                     const long rc = read_raw_into(f, dst, cap, len);
                     if (rc == -1) die("Could not open %s", f.c_str());
@@ -462,6 +468,11 @@ static void fill_sketches(CtxFuture &cf, const Opts &o, bool write_files, bool s
                 std::vector<uint8_t>().swap(zseq[i]);
             } else {
                 for (const auto &f : files[i]) {
+                    if (len && len == cap) {  // (the same: no room for the separator)
+#pragma omp critical
+                        late.push_back(slot_of[t]);
+                        break;
+                    }
                     if (len) dst[len++] = 'N';
                     const long rc = append_fastx_into(f, dst, cap, len);
                     if (rc == -1) die("Could not open %s", f.c_str());

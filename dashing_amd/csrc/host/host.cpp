@@ -308,6 +308,8 @@ struct VecSink {
     bool overflow = false;
     void push(uint8_t b) { out.push_back(b); }
     void append(const uint8_t *p, size_t len) { out.insert(out.end(), p, p + len); }
+    size_t size() const { return out.size(); }
+    void truncate(size_t n) { out.resize(n); }
 };
 struct BufSink {  // caller-owned memory (page-locked staging): no growth, overflow is recorded
     uint8_t *dst;
@@ -327,102 +329,219 @@ struct BufSink {  // caller-owned memory (page-locked staging): no growth, overf
             overflow = true;
         }
     }
+    size_t size() const { return len; }
+    void truncate(size_t n) { len = n < len ? n : len; }
 };
 
-// FASTA/FASTQ state machine over a stream of text blocks: 0 = expect header, 1 = sequence lines, 2 = quality
-// lines; whole line pieces are handed to the sink at once (memchr for the newline), not byte by byte
+// klib's kseq_read over a stream of text blocks, one state per place where kseq_read / ks_getuntil2 can stand when a
+// block ends; whole line pieces go to the sink at once (memchr for the newline), not byte by byte.  What kseq does:
+//   - no header character pending (the file's start, behind a FASTQ record): skip byte by byte, mid-line too, to '>' / '@'
+//   - the name runs to the first isspace byte; unless that was '\n' the rest of the line is the comment
+//   - sequence: at a line start '>' '@' end the record (the next one's header), '+' starts the quality, '\n' is skipped;
+//     any other byte begins a line that is read to its '\n' (or EOF)
+//   - a line read that took at least one byte drops ONE trailing '\r' if the string it appends to is longer than 1 byte;
+//     every other '\r' is a byte like any other (for the encoder: an invalid base)
+//   - FASTQ: the rest of the '+' line (EOF first: error), then whole quality lines, at least one, until the quality is as
+//     long as the sequence or EOF; another length is an error
+//   - dashing's encoder reads while kseq_read >= 0: the first error ends the file, its record contributes nothing
 template <class Sink>
 struct FastxParser {
+    enum State { SCAN, NAME, COMMENT, SEQ_BOL, SEQ_LINE, PLUS, QUAL, DONE };
     Sink &out;
     long nrec = 0;
-    int state = 0;
-    bool at_line_start = true, skipping_line = false;
-    size_t seq_len = 0, qual_len = 0;
+    State st = SCAN;
     // records mode (append_fastx_records): no separator; every record's start (bytes emitted before it) and its kseq
     // name -- the header text behind '>' / '@' up to the first white space -- are kept instead
     std::vector<uint64_t> *starts = nullptr;
     std::vector<std::string> *names = nullptr;
-    uint64_t emitted = 0;
-    bool in_name = false;
+    uint64_t emitted = 0, mark_emitted = 0;
+    size_t mark = 0;                                   // the sink's length in front of the current record
+    uint64_t seq_len = 0, qual_len = 0, qual_cr = 0;  // qual_cr: the '\r' bytes that end the quality string so far
+    bool got = false;      // the current ks_getuntil2 has taken a byte (its `gotany`)
+    bool cr_held = false;  // the sequence line so far ends with a '\r' that is not emitted yet
     explicit FastxParser(Sink &s) : out(s) {}
-    void take(const char *p, size_t len)  // a piece of a line's content
+
+    void begin_record()
     {
-        if (len == 0) return;
-        if (skipping_line) {
-            if (in_name) {
-                size_t t = 0;
-                while (t < len && !std::isspace((unsigned char)p[t])) ++t;
-                names->back().append(p, t);
-                if (t < len) in_name = false;
-            }
-            return;
+        mark = out.size();
+        mark_emitted = emitted;
+        if (starts) {
+            starts->push_back(emitted);
+            names->emplace_back();
+        } else if (nrec) {
+            out.push('N');
         }
-        if (std::memchr(p, '\r', len)) {  // rare: strip carriage returns the slow way
-            for (size_t t = 0; t < len; ++t) {
-                if (p[t] == '\r') continue;
-                if (state == 1) {
-                    out.push((uint8_t)p[t]);
-                    ++seq_len;
-                    ++emitted;
-                } else if (state == 2) {
-                    ++qual_len;
-                }
-            }
-            return;
+        ++nrec;
+        seq_len = 0;
+        got = false;
+        st = NAME;
+    }
+    void drop_record()  // kseq_read returned < 0 in this record
+    {
+        out.truncate(mark);
+        emitted = mark_emitted;
+        if (starts) {
+            starts->pop_back();
+            names->pop_back();
         }
-        if (state == 1) {
-            out.append((const uint8_t *)p, len);
-            seq_len += len;
-            emitted += len;
-        } else if (state == 2) {
-            qual_len += len;
-        }
+        --nrec;
+        st = DONE;
+    }
+    void emit(const char *p, size_t n)
+    {
+        out.append((const uint8_t *)p, n);
+        emitted += n;
+        seq_len += n;
+    }
+    void end_seq_line()  // the line read took a byte: a held '\r' goes unless it would be the sequence's only byte
+    {
+        if (cr_held && seq_len == 0) emit("\r", 1);
+        cr_held = false;
+    }
+    void end_qual_line()
+    {
+        if (qual_len > 1 && qual_cr) --qual_len, --qual_cr;
+        if (qual_len >= seq_len) end_fastq();
+        else got = false;
+    }
+    void end_fastq()
+    {
+        if (qual_len != seq_len) drop_record();
+        else st = SCAN;
     }
     void feed(const char *buf, size_t N)
     {
         size_t i = 0;
         while (i < N) {
-            if (at_line_start) {
-                const char c = buf[i];
-                if (c == '\n') {  // empty line
-                    if (state == 2 && qual_len >= seq_len) state = 0;
+            switch (st) {
+            case DONE:
+                return;
+            case SCAN: {
+                while (i < N && buf[i] != '>' && buf[i] != '@') ++i;
+                if (i < N) {
                     ++i;
-                    continue;
+                    begin_record();
                 }
-                at_line_start = false;
-                if (state != 2 && (c == '>' || c == '@')) {  // new record header
-                    if (starts) {
-                        starts->push_back(emitted);
-                        names->emplace_back();
-                        in_name = true;
-                    } else if (nrec) {
-                        out.push('N');
-                    }
-                    ++nrec;
-                    state = 1;
-                    seq_len = qual_len = 0;
-                    skipping_line = true;
-                    ++i;  // (the '>' / '@' itself)
-                } else if (state == 1 && c == '+') {  // FASTQ separator line
-                    state = 2;
-                    skipping_line = true;
-                }
+                break;
             }
-            const char *nl = (const char *)std::memchr(buf + i, '\n', N - i);
-            const size_t e = nl ? (size_t)(nl - buf) : N;
-            take(buf + i, e - i);
-            if (nl) {
-                at_line_start = true;
-                skipping_line = false;
-                in_name = false;
-                if (state == 2 && qual_len >= seq_len) state = 0;
-                i = e + 1;
-            } else {
-                i = e;
+            case NAME: {
+                size_t t = i;
+                while (t < N && !std::isspace((unsigned char)buf[t])) ++t;
+                if (names) names->back().append(buf + i, t - i);
+                if (t > i) got = true;
+                i = t;
+                if (t < N) {
+                    got = true;
+                    st = buf[t] == '\n' ? SEQ_BOL : COMMENT;
+                    ++i;
+                }
+                break;
+            }
+            case COMMENT:
+            case PLUS: {
+                const char *nl = (const char *)std::memchr(buf + i, '\n', N - i);
+                if (!nl) {
+                    i = N;
+                    break;
+                }
+                i = (size_t)(nl - buf) + 1;
+                if (st == PLUS) {
+                    qual_len = qual_cr = 0;
+                    got = false;
+                    st = QUAL;
+                } else {
+                    st = SEQ_BOL;
+                }
+                break;
+            }
+            case SEQ_BOL:
+            case SEQ_LINE:
+                // the hot loop: one memchr and one append per line; a line's first byte goes with the rest of it (it is not
+                // part of ks_getuntil2's read, hence `first`)
+                for (;;) {
+                    size_t first = 0;
+                    if (st == SEQ_BOL) {
+                        if (i == N) break;
+                        const char c = buf[i];
+                        if (c == '\n') {
+                            ++i;
+                            continue;
+                        }
+                        if (c == '>' || c == '@' || c == '+') {
+                            ++i;
+                            if (c == '+') st = PLUS;
+                            else begin_record();
+                            break;
+                        }
+                        st = SEQ_LINE;
+                        got = cr_held = false;
+                        first = 1;
+                    }
+                    const char *nl = (const char *)std::memchr(buf + i, '\n', N - i);
+                    const size_t e = nl ? (size_t)(nl - buf) : N;
+                    if (e > i) {
+                        if (e > i + first) got = true;
+                        if (cr_held) emit("\r", 1);
+                        cr_held = buf[e - 1] == '\r';
+                        emit(buf + i, e - i - (cr_held ? 1 : 0));
+                    }
+                    if (!nl) {
+                        i = N;
+                        break;
+                    }
+                    got = true;
+                    end_seq_line();
+                    st = SEQ_BOL;
+                    i = e + 1;
+                }
+                break;
+            case QUAL: {
+                const char *nl = (const char *)std::memchr(buf + i, '\n', N - i);
+                const size_t e = nl ? (size_t)(nl - buf) : N;
+                if (e > i) {
+                    got = true;
+                    qual_len += e - i;
+                    size_t t = e;
+                    while (t > i && buf[t - 1] == '\r') --t;
+                    qual_cr = t == i ? qual_cr + (e - i) : e - t;
+                }
+                if (nl) {
+                    end_qual_line();
+                    i = e + 1;
+                } else {
+                    i = e;
+                }
+                break;
+            }
             }
         }
     }
+    void finish()  // the end of the file
+    {
+        switch (st) {
+        case NAME:
+            if (!got) drop_record();  // a header character and nothing behind it: kseq_read's normal end, no record
+            break;
+        case SEQ_LINE:
+            if (got) end_seq_line();
+            else if (cr_held) emit("\r", 1);
+            cr_held = false;
+            break;
+        case PLUS:
+            drop_record();  // no quality string
+            break;
+        case QUAL:
+            if (got && qual_len > 1 && qual_cr) --qual_len, --qual_cr;
+            end_fastq();
+            break;
+        default:
+            break;
+        }
+        if (st != DONE) st = DONE;
+    }
 };
+
+constexpr size_t kFastxReadBlock = size_t(1) << 20;  // the parser's read block (tests put line ends across it)
 
 template <class Sink>
 long parse_fastx(const std::string &path, Sink &sink, std::vector<uint64_t> *starts = nullptr,
@@ -433,10 +552,13 @@ long parse_fastx(const std::string &path, Sink &sink, std::vector<uint64_t> *sta
     FastxParser<Sink> ps(sink);
     ps.starts = starts;
     ps.names = names;
-    std::vector<char> buf(1 << 20);
-    ssize_t n;
-    while ((n = in.read(buf.data(), buf.size())) > 0) ps.feed(buf.data(), (size_t)n);
-    return n < 0 ? -1 : ps.nrec;
+    std::vector<char> buf(kFastxReadBlock);
+    ssize_t n = 0;
+    while (ps.st != FastxParser<Sink>::DONE && (n = in.read(buf.data(), buf.size())) > 0) ps.feed(buf.data(), (size_t)n);
+    if (ps.st == FastxParser<Sink>::DONE) return ps.nrec;  // (an error record: the rest of the file is not read)
+    if (n < 0) return -1;
+    ps.finish();
+    return ps.nrec;
 }
 
 }  // namespace

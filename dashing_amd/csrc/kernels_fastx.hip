@@ -3,9 +3,9 @@
 // The reference's hot loop 1 includes the parse: Encoder::for_each(func, path) reads every record with kseq and feeds
 // its sequence to the k-mer loop (src/sketch_and_cmp.h:338-342).  Through round 5 the host parsed (16 threads
 // at 0.6 GB/s each) and the GPU idled 98.7 % of BASELINE configs[1] end to end.  Here the host only read()s the raw file
-// bytes into page-locked staging; three small kernels turn them into what the host parser (host/host.cpp FastxParser)
-// would have produced -- header lines become ONE invalid byte ('N': k-mers never span records), '\n' and '\r' vanish,
-// everything else is copied (k_sketch validates and case-folds the bases itself) -- at the SAME offsets of a second
+// bytes into page-locked staging; three small kernels turn them into what kseq (and the host parser, host/host.cpp
+// FastxParser, a port of it) would have produced -- header lines become ONE invalid byte ('N': k-mers never span records),
+// '\n' vanishes, a '\r' vanishes where kseq drops it (before '\n', or the genome's last byte), everything else is copied (k_sketch validates and case-folds the bases itself) -- at the SAME offsets of a second
 // buffer, the rest of every genome's region filled with 'N', so that the sketch work list is known to the host before a
 // byte has been decoded (no length travels back).
 //
@@ -22,7 +22,7 @@
 // What does not keep its format's promise -- a first byte that is neither '>' nor '@', a FASTA line that begins with '+',
 // FASTQ lines 4r that are not '@' headers or 4r + 2 that are not '+' lines, a sequence line that begins with '@' '>' '+',
 // a record whose quality line is not as long as its sequence line (multi-line or cut-off records: kseq's record state
-// decides those) -- raises the genome's status word:
+// decides those), a FASTQ '\r' that does not vanish or that begins a line (kseq counts it) -- raises the genome's status word:
 // nothing of it is emitted (its region becomes all 'N': no k-mer) and the host parses that file itself.  HBM-bound
 // byte work: no MFMA.
 #include <hip/hip_runtime.h>
@@ -60,7 +60,7 @@ __device__ __forceinline__ uint32_t eq4(uint32_t w, uint32_t pat)
 }
 
 struct LaneMasks {
-    uint64_t nl, nl_real, cr, hc, pl, at, valid;
+    uint64_t nl, nl_real, cr, crd, hc, pl, at, valid;
     uint32_t w[16];
 };
 
@@ -97,6 +97,14 @@ __device__ __forceinline__ void lane_masks(const uint8_t *__restrict__ raw, uint
     m.pl = (((uint64_t)pl[1] << 32) | pl[0]) & valid;
 }
 
+// the '\r' bytes that vanish: those before a '\n' and the genome's last raw byte (kseq's ks_getuntil2 drops one '\r' that
+// ends a line read); every other '\r' is a byte like any other.  nb: the byte behind the lane, if has_next (bits behind
+// `valid` lie behind the genome's end: chunks are whole kFastxChunk but the genome's last)
+__device__ __forceinline__ void lane_cr_drop(LaneMasks &m, bool has_next, uint32_t nb)
+{
+    m.crd = m.cr & ((m.nl >> 1) | ((uint64_t)(!has_next || nb == '\n') << 63));
+}
+
 // ---- FASTA ----------------------------------------------------------------------------------------------------------------
 // the lane's transfer function: with a newline inside, whatever came in is forgotten
 __device__ __forceinline__ uint32_t lane_fn(const LaneMasks &m)
@@ -115,7 +123,7 @@ __device__ __forceinline__ uint64_t lane_out(const LaneMasks &m, uint32_t s, uin
     const uint64_t hsx = hdr_start | (s == FX_HDR ? 1ull : 0ull);
     const uint64_t x = ~m.nl;
     const uint64_t span = (x + hsx) ^ x;  // from every header start to its newline, inclusive
-    return (~span & ~m.nl & ~m.cr) | hdr_start;
+    return (~span & ~m.nl & ~m.crd) | hdr_start;
 }
 
 // ---- FASTQ (strict four-line records) ---------------------------------------------------------------------------------------
@@ -195,6 +203,7 @@ __global__ __launch_bounds__(256) void k_fastx_scan(const uint8_t *__restrict__ 
     const uint64_t next = ck.begin + at + 64;
     const bool has_next = have && next < g.off + g.rawlen;
     const uint32_t nb = has_next ? raw[next] : 0u;  // (the byte behind this lane: the next lane's, or the next chunk's, first)
+    lane_cr_drop(m, has_next, nb);
     uint32_t total;
     if (g.fmt == 0) {
         // not plain FASTA: the genome does not begin with '>', or a line begins with '+'
@@ -216,6 +225,10 @@ __global__ __launch_bounds__(256) void k_fastx_scan(const uint8_t *__restrict__ 
         }
     } else {
         if (have && ck.begin + at == g.off && (m.w[0] & 0xFFu) != '@') atomicOr(&status[ck.genome], 1u);
+        // a '\r' that does not vanish, or one that begins a line: kseq counts it in the sequence or quality length (a first
+        // line "\r\n" keeps its '\r': ks_getuntil2 drops it only from a string longer than one byte) -- refused
+        if ((m.cr & ~m.crd) || (m.nl_real & ((m.cr >> 1) | ((uint64_t)(has_next && nb == '\r') << 63))))
+            atomicOr(&status[ck.genome], 1u);
         const uint32_t ex = wg_scan_fn(fn_add((uint32_t)__popcll(m.nl_real)), sh, total);
         uint64_t q[4];
         lane_line_index(m.nl_real, fn_apply(ex, 0), q);
@@ -351,6 +364,9 @@ __global__ __launch_bounds__(256) void k_fastx_compact(const uint8_t *__restrict
     const uint32_t have = at < ck.len ? (ck.len - at < 64u ? ck.len - at : 64u) : 0u;
     LaneMasks m;
     lane_masks(raw, ck.begin + at, have, m);
+    const uint64_t next = ck.begin + at + 64;
+    const bool has_next = have && next < g.off + g.rawlen;
+    lane_cr_drop(m, has_next, has_next ? raw[next] : 0u);
     uint32_t total_fn;
     uint64_t hs, keep;
     if (g.fmt == 0) {
@@ -359,7 +375,7 @@ __global__ __launch_bounds__(256) void k_fastx_compact(const uint8_t *__restrict
     } else {
         const uint32_t ex = wg_scan_fn(fn_add((uint32_t)__popcll(m.nl_real)), sh, total_fn);
         keep = lane_out_fastq(m, fn_apply(ex, st.y & 3u), hs);
-        // The host parser ends a record's quality when it holds as many bytes as the sequence ('\r' not counted): a
+        // kseq ends a record's quality when it holds as many bytes as the sequence (a line's final '\r' not counted): a
         // quality line of ANOTHER length would shift its reading of every later line.  Per record that is a comparison of two
         // line lengths that may lie chunks apart; as ONE number per genome: F = sum over records r of H(r) x (sequence bytes -
         // quality bytes) with H a 64-bit mix of the record's number, in wrapping arithmetic -- linear in the bytes, so every

@@ -136,16 +136,18 @@ int dsh_sketch_records_device(dsh_ctx *ctx, const void *d_seq, const uint64_t *r
  * raw[genome_off[g] .. genome_off[g] + raw_len[g]) (several files of one genome: back to back with a '\n' between them),
  * its region [genome_off[g], genome_off[g+1]) at least that long, every genome_off[g] a multiple of 32.  The library
  * copies the raw bytes to the device and decodes them there into what kseq would hand the encoder, then sketches as
- * dsh_sketch_batch_async does.  A genome that begins with '>' is FASTA: header lines ('>' or '@' first) end a record (one
- * invalid byte: k-mers never span records), '\n' and '\r' vanish, everything else is sequence (validated and case-folded
- * by the sketch kernel as above).  A genome that begins with '@' is FASTQ in four-line records: of every four lines the
- * second is sequence.  What does not keep its format's promise is REFUSED per genome, never guessed at -- a first byte
+ * dsh_sketch_batch_async does (kseq: current klib's kseq_read).  A genome that begins with '>' is FASTA: header lines ('>'
+ * or '@' first) end a record (one invalid byte: k-mers never span records), '\n' vanishes, a '\r' vanishes when a '\n'
+ * follows it or it is the genome's last byte (kseq drops one '\r' that ends a line) and is otherwise an invalid byte,
+ * everything else is sequence (validated and case-folded by the sketch kernel as above).  A genome that begins with '@' is
+ * FASTQ in four-line records: of every four lines the second is sequence.  What does not keep its format's promise is
+ * REFUSED per genome, never guessed at -- a FASTQ file with a '\r' that does not vanish or that begins a line, a first byte
  * that is neither, a FASTA line that begins with '+', a FASTQ file whose lines 4r are not '@' headers or 4r + 2 not '+'
  * lines, in which a sequence line begins with '@', '>' or '+', or in which some record's quality line is not exactly as
  * long as its sequence line (multi-line records, cut-off files: the record state of kseq decides those; the length rule
  * is checked as a 64-bit fingerprint over all records) -- : status_out[g] != 0, NOTHING goes into its slot, and the host
  * parses that genome itself
- * (dsh_sketch_batch).  status_out: n_genomes words of page-locked host memory (or NULL), valid after dsh_wait.  `raw` must
+ * (dsh_sketch_batch) as kseq does: up to kseq's first error in a file, whose record contributes nothing.  status_out: n_genomes words of page-locked host memory (or NULL), valid after dsh_wait.  `raw` must
  * stay untouched until then.  Compressed inputs and pipes are the host's business (inflate, then either entry point). */
 int dsh_sketch_fastx_batch_async(dsh_ctx *ctx, const uint8_t *raw_pinned, const uint64_t *genome_off,
                                  const uint64_t *raw_len, uint32_t n_genomes, uint64_t first_slot, int k, int canon,

@@ -498,3 +498,60 @@ def test_full_teardown_and_timing_marks_change_nothing(genomes, tmp_path):
         if "DSH_TIMING" in env:
             assert b"[timing] main() entered" in r.stderr and b"leaving" in r.stderr
     assert outs[0] == outs[1] == outs[2]
+
+
+def test_device_and_host_parse_equal_kseq_on_damaged_inputs(tmp_path, oracle):
+    """Inputs where kseq and a parser that drops every '\\r' part ways -- a lone '\\r' in FASTA and FASTQ sequence lines, in a
+    header, '\\r\\r\\n' --, text before the first header, FASTQ whose quality goes wrong at a later record (kseq keeps the
+    records before it), a FASTQ file that ends on its '+' line, and a genome of two files, the second with text before its
+    header: `dist` with device parsing and with DSH_HOST_PARSE=1 write the same bytes, and every genome's registers equal
+    the oracle's over the records kseq reads (tests/kseq_ref.py)."""
+    import ctypes as C
+
+    from kseq_ref import parse as kseq_parse  # (tests/kseq_ref.py)
+
+    g = [bytes(x) for x in synth.synthetic_genomes(6, 40000, seed=0xCE5)]
+    fq = lambda rs, q=None: b"".join(b"@r%d\n%s\n+\n%s\n" % (i, r, (q or {}).get(i, b"I" * len(r))) for i, r in enumerate(rs))
+    reads = [g[3][i * 150 : (i + 1) * 150] for i in range(100)]
+    texts = {
+        "lone_cr.fa": b">a\n" + b"\n".join(g[0][i : i + 35] + (b"\r" if i % 700 == 0 else b"") + g[0][i + 35 : i + 70] for i in range(0, 30000, 70)) + b"\n",
+        "cr_in_header.fa": b">a\rb c\n" + g[1][:20000] + b"\n>d\r\r\n" + g[1][20000:30000] + b"\r\r\n",
+        "text_first.fa": b"xx ACGT " + synth.to_fasta(np.frombuffer(g[2][:25000], np.uint8), "t"),
+        "bad_qual.fq": fq(reads[:60], {40: b"I" * 149}),
+        "cr_qual.fq": fq(reads[60:], {10: b"I" * 70 + b"\r" + b"I" * 79}),
+        "ends_on_plus.fq": fq(reads[:30]) + b"@z\n" + g[4][:150] + b"\n+",
+        "cr_seq.fq": fq([r[:70] + b"\r" + r[70:] if i == 3 else r for i, r in enumerate(reads[:50])], {3: b"I" * 151}),
+        "part2.fa": b"junk\n>p2\n" + g[5][:20000] + b"\n",
+    }
+    for name, t in texts.items():
+        (tmp_path / name).write_bytes(t)
+    part1 = tmp_path / "part1.fa"
+    part1.write_bytes(b">p1\n" + g[5][20000:40000] + b"\n")
+    inputs = [str(tmp_path / n) for n in texts if n != "part2.fa"] + ["%s %s" % (part1, tmp_path / "part2.fa")]
+    lst = tmp_path / "in.txt"
+    lst.write_text("\n".join(inputs) + "\n")
+    outs = {}
+    for mode, env in (("device", {}), ("host", {"DSH_HOST_PARSE": "1"})):
+        pre = tmp_path / ("cache_" + mode)
+        pre.mkdir()
+        o = tmp_path / (mode + ".bin")
+        r = subprocess.run([CLI, "dist", "-k", "21", "-S", "12", "-p", "4", "-b", "--avoid-sorting", "-W", "-P", str(pre), "-O", str(o), "-F", str(lst)],
+                           capture_output=True, timeout=300, env=dict(os.environ, **env))
+        assert r.returncode == 0, r.stderr.decode()[-2000:]
+        outs[mode] = (o.read_bytes(), {f: (pre / f).read_bytes() for f in sorted(os.listdir(pre))})
+    assert outs["device"] == outs["host"]
+    hostlib = C.CDLL(os.path.join(ROOT, "dashing_amd", "libdashing_host.so"))
+    hostlib.dshh_read_hll.argtypes = [C.c_char_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_int)]
+    seqs = []
+    for inp in inputs:
+        parts = [b"N".join(s for _, s in kseq_parse(open(f, "rb").read())[0]) for f in inp.split(" ")]
+        seqs.append(np.frombuffer(b"N".join(parts), np.uint8))
+    want = oracle_regs(oracle, seqs, 21, 12)
+    names = sorted(os.listdir(tmp_path / "cache_device"))
+    for i, inp in enumerate(inputs):
+        base = os.path.basename(inp.split(" ")[-1])  # (a genome of several files is named after the text behind the first space)
+        f = next(n for n in names if n.startswith(base + "."))
+        buf = np.zeros(1 << 12, np.uint8)
+        p_ = C.c_int(0)
+        assert hostlib.dshh_read_hll(str(tmp_path / "cache_device" / f).encode(), buf.ctypes.data, buf.size, C.byref(p_)) == 0
+        assert (buf == want[i]).all(), inp

@@ -160,3 +160,29 @@ def test_refusals(inputs, tmp_path):
     assert r.returncode != 0 and b"-W" in r.stderr
     r = subprocess.run([CLI, "dist_by_seq", "--devices", "0,0", *paths], capture_output=True, timeout=120)
     assert r.returncode != 0 and b"one device" in r.stderr
+
+
+def test_sketch_by_seq_follows_kseq_on_damaged_inputs(oracle, tmp_path):
+    """a lone '\\r' in a sequence line and in a header, text before the first header, and a FASTQ whose quality goes wrong
+    at a later record: the rows are the oracle's registers of the records kseq reads (tests/kseq_ref.py), the labels are
+    kseq's names, and the record that fails ends its file"""
+    from kseq_ref import parse as kseq_parse  # (tests/kseq_ref.py)
+
+    g = [bytes(x) for x in synth.synthetic_genomes(3, 6000, seed=0xB7)]
+    fa = b"xx>pre\n>a\rcomment\n" + g[0][:3000] + b"\r" + g[0][3000:] + b"\n>b\n" + g[1][:2000] + b"\r\r\n" + g[1][2000:4000] + b"\n"
+    fq = b"".join(b"@q%d\n%s\n+\n%s\n" % (i, g[2][i * 500 : (i + 1) * 500], b"I" * (500 if i != 6 else 499)) for i in range(10))
+    paths = []
+    for name, t in (("d.fa", fa), ("d.fq", fq)):
+        (tmp_path / name).write_bytes(t)
+        paths.append(str(tmp_path / name))
+    recs = [(n.decode(), np.frombuffer(s, np.uint8)) for t in (fa, fq) for n, s in kseq_parse(t)[0]]
+    assert [n for n, _ in recs] == ["pre", "a", "b"] + ["q%d" % i for i in range(6)]
+    out = str(tmp_path / "recs.hll")
+    run("sketch_by_seq", "-k", 21, "-S", 10, "-o", out, *paths)
+    want = oracle_regs(oracle, recs, 21, 10)
+    raw = gzip.open(out).read()
+    rec = 28 + (1 << 10)
+    assert len(raw) == len(recs) * rec
+    for i in range(len(recs)):
+        assert raw[i * rec + 28:(i + 1) * rec] == want[i].tobytes(), recs[i][0]
+    assert gzip.open(out + ".labels.gz").read().decode().split("\n")[:-1] == [n for n, _ in recs]

@@ -1,8 +1,9 @@
 """GPU parity of the device-side FASTA / FASTQ decode (dsh_sketch_fastx_batch_async, kernels_fastx.hip): the registers of raw file
-bytes decoded ON THE DEVICE equal, bit for bit, the CPU oracle's registers of the sequence the HOST parser
-(host/host.cpp FastxParser, through libdashing_host.so) extracts from the same file -- the reference's
-Encoder::for_each(func, path) includes the parse (src/sketch_and_cmp.h:338-342).  What is not plain FASTA is refused per
-genome (status != 0, nothing sketched), never guessed at."""
+bytes decoded ON THE DEVICE equal, bit for bit, the CPU oracle's registers of the records kseq reads from the same file
+(tests/kseq_ref.py, a port of klib's kseq_read) -- the reference's Encoder::for_each(func, path) includes the parse
+(src/sketch_and_cmp.h:338-342).  The HOST parser (host/host.cpp FastxParser, through libdashing_host.so), which takes every
+genome the device refuses, must give the same sequence.  What the device cannot decode is refused per genome (status != 0,
+nothing sketched), never guessed at."""
 import ctypes as C
 import os
 
@@ -11,6 +12,8 @@ import pytest
 
 import dashing_amd
 from dashing_amd import synth
+from fastx_gen import damage, fasta, fastq  # (tests/fastx_gen.py)
+from kseq_ref import parse as kseq_parse  # (tests/kseq_ref.py)
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -35,22 +38,18 @@ def host_parse(host, tmp_path, name, data):
     return buf[: n.value].copy()
 
 
-def fasta(rng, records, width, eol=b"\n", final_eol=True, blank_every=0):
-    out = []
-    for i, (name, seq) in enumerate(records):
-        out.append(b">" + name + eol)
-        s = bytes(seq)
-        if width <= 0:
-            out.append(s + eol)
-        else:
-            for x in range(0, len(s), width):
-                out.append(s[x : x + width] + eol)
-                if blank_every and (x // width) % blank_every == blank_every - 1:
-                    out.append(eol)
-    data = b"".join(out)
-    if not final_eol and data.endswith(eol):
-        data = data[: -len(eol)]
-    return data
+def kseq_seq(data):
+    """what dashing's encoder sees of this file: kseq's records, one 'N' between two (k-mers never span records)"""
+    recs, _ = kseq_parse(data)
+    return np.frombuffer(b"N".join(q for _, q in recs), np.uint8)
+
+
+def reference_seq(host, tmp_path, name, data):
+    """kseq's sequence for this file, after checking that the host parser gives the same"""
+    want = kseq_seq(data)
+    got = host_parse(host, tmp_path, name, data)
+    assert got.tobytes() == want.tobytes(), "%s: the host parser differs from kseq" % name
+    return want
 
 
 def check(ctx, oracle, host, tmp_path, files, k=31, p=10, canon=True, expect_status=None):
@@ -60,7 +59,7 @@ def check(ctx, oracle, host, tmp_path, files, k=31, p=10, canon=True, expect_sta
     if got is None:
         got = np.zeros((len(files), 1 << p), np.uint8)
         ctx._ck(ctx._lib.dsh_download_sketches(ctx._h, 0, len(files), got.ctypes.data))
-    seqs = [host_parse(host, tmp_path, "f%d.fa" % i, f) for i, f in enumerate(files)]
+    seqs = [reference_seq(host, tmp_path, "f%d.fa" % i, f) for i, f in enumerate(files)]
     for g, (f, s) in enumerate(zip(files, seqs)):
         refused = expect_status is not None and expect_status[g]
         assert bool(status[g]) == bool(refused), "genome %d: status %d" % (g, status[g])
@@ -133,21 +132,10 @@ def test_what_is_not_plain_fasta_is_refused_not_guessed(ctx, oracle, host, tmp_p
     check(ctx, oracle, host, tmp_path, files, expect_status=[0, 1, 1, 1, 0, 0, 1, 1])
 
 
-def fastq(rng, reads, eol=b"\n", final_eol=True, qual=None):
-    out = []
-    for i, r in enumerate(reads):
-        q = qual(i, len(r)) if qual else bytes(rng.integers(33, 75, len(r), dtype=np.uint8))
-        out.append(b"@read%d some text\n".replace(b"\n", eol) % i + bytes(r) + eol + b"+" + eol + q + eol)
-    data = b"".join(out)
-    if not final_eol and data.endswith(eol):
-        data = data[: -len(eol)]
-    return data
-
-
 def test_fastq_in_strict_four_line_records(ctx, oracle, host, tmp_path):
     """FASTQ (a genome that begins with '@'): line index modulo 4 by counting newlines, the sequence lines kept, one invalid
     byte per record.  Quality lines may hold any character -- '@', '+', '>' first included --, reads from 1 base to longer
-    than a chunk, CRLF, no newline at the end; registers equal the oracle's on the HOST parser's sequence."""
+    than a chunk, CRLF, no newline at the end; registers equal the oracle's on kseq's (and the host parser's) sequence."""
     rng = np.random.default_rng(7)
     g = genomes(1, 400_000, 13, decorate=True)[0]
 
@@ -229,10 +217,12 @@ _FZ_FIRST = int(os.environ.get("DSH_FASTX_FUZZ_FIRST", "0"))
 
 @pytest.mark.parametrize("case", range(_FZ_FIRST, _FZ_FIRST + int(os.environ.get("DSH_FASTX_FUZZ_CASES", "40"))))
 def test_fastx_fuzz_accepted_means_equal_to_the_host_parser(ctx, oracle, host, tmp_path, case):
-    """Random FASTA and FASTQ texts, well-formed and damaged (lines dropped, doubled, cut, swapped; '+', '@', '>' put at line
-    starts; blank lines; CRLF): whatever the device ACCEPTS (status 0) must give the registers of the host parser's
-    sequence -- the device may refuse more than strictly necessary, it may never differ silently -- and what is well-formed
-    must be accepted."""
+    """Random FASTA and FASTQ texts, well-formed and damaged (tests/fastx_gen.py::damage: lines dropped, doubled, cut,
+    swapped; '+', '@', '>' put at line starts; blank lines; CRLF; lone '\\r' and '\\r\\r\\n' anywhere; text before and between
+    records; empty reads; a cut on a '+' line; quality of the wrong length): whatever the device ACCEPTS (status 0) must give
+    the registers of kseq's records -- the device may refuse more than strictly necessary, it may never differ silently --,
+    what is well-formed must be accepted, and the host parser (which takes what the device refuses) must equal kseq too, so
+    that the device's registers equal the host parser's as well."""
     rng = np.random.default_rng(0xFA57 + case)
     g = genomes(1, 60_000, 1000 + case, decorate=bool(case & 1))[0]
     files, must_accept = [], []
@@ -244,7 +234,6 @@ def test_fastx_fuzz_accepted_means_equal_to_the_host_parser(ctx, oracle, host, t
             recs = [(bytes(rng.integers(33, 126, int(rng.integers(0, 90)), dtype=np.uint8)), g[a:b]) for a, b in zip(cuts[:-1], cuts[1:])]
             data = fasta(rng, recs, int(rng.choice([0, 1, 7, 60, 63, 64, 65, 80, 200, 5000])), eol=eol, final_eol=bool(rng.random() < 0.7),
                          blank_every=int(rng.choice([0, 0, 3, 11])))
-            ok = True
         else:  # FASTQ
             lens = [int(x) for x in rng.integers(1, int(rng.choice([50, 300, 3000])), int(rng.integers(1, 120)))]
             at, rds = 0, []
@@ -252,34 +241,9 @@ def test_fastx_fuzz_accepted_means_equal_to_the_host_parser(ctx, oracle, host, t
                 rds.append(g[at : at + L])
                 at = (at + L) % (len(g) - 3000)
             data = fastq(rng, rds, eol=eol, final_eol=bool(rng.random() < 0.7))
-            ok = True
-        if rng.random() < 0.5:  # damage it
-            lines = data.split(eol)
-            for _ in range(int(rng.integers(1, 4))):
-                if len(lines) < 2:
-                    break
-                i = int(rng.integers(0, len(lines)))
-                kind = int(rng.integers(0, 7))
-                if kind == 0:
-                    del lines[i]
-                elif kind == 1:
-                    lines.insert(i, lines[i])
-                elif kind == 2:
-                    lines[i] = lines[i][: len(lines[i]) // 2]
-                elif kind == 3:
-                    lines.insert(i, b"")
-                elif kind == 4:
-                    lines[i] = bytes([int(rng.choice(list(b"+@>")))]) + lines[i]
-                elif kind == 5 and i + 1 < len(lines):
-                    lines[i], lines[i + 1] = lines[i + 1], lines[i]
-                else:
-                    lines[i] = lines[i] + bytes(rng.integers(33, 126, 5, dtype=np.uint8))
-            data = eol.join(lines)
-            if rng.random() < 0.5 and len(data) > 4:  # single bytes overwritten: structure characters, NUL, high bytes, lone '\r' / '\n'
-                buf = bytearray(data)
-                for _ in range(int(rng.integers(1, 6))):
-                    buf[int(rng.integers(1, len(buf)))] = int(rng.choice(list(b"\n\r>@+\x00\xff NacgtACGT")))
-                data = bytes(buf)
+        ok = True
+        if rng.random() < 0.5:
+            data = damage(rng, data, eol)
             ok = False
         files.append(data)
         must_accept.append(ok)
@@ -288,12 +252,76 @@ def test_fastx_fuzz_accepted_means_equal_to_the_host_parser(ctx, oracle, host, t
     status = ctx.sketch_fastx_batch(files, 0, k, True)
     got = ctx.download(0, len(files))
     for gi, f in enumerate(files):
+        s = reference_seq(host, tmp_path, "z%d.fa" % gi, f)
         if must_accept[gi]:
             assert status[gi] == 0, "case %d genome %d: a well-formed file was refused" % (case, gi)
         if status[gi]:
             assert not got[gi].any(), "a refused genome must contribute nothing"
             continue
-        s = host_parse(host, tmp_path, "z%d.fa" % gi, f)
         seq, off = synth.concat_for_device([s])
         want = oracle.sketch_batch(seq, off, k, p, True)[0]
-        assert (got[gi] == want).all(), "case %d genome %d: accepted, but %d registers differ from the host parser's" % (case, gi, int((got[gi] != want).sum()))
+        assert (got[gi] == want).all(), "case %d genome %d: accepted, but %d registers differ from kseq's" % (case, gi, int((got[gi] != want).sum()))
+
+
+def _cr_variants(base, positions):
+    """base with a lone '\\r' put in front of each of the given raw offsets (one variant per offset)"""
+    return [base[:x] + b"\r" + base[x:] for x in positions if 0 < x <= len(base)]
+
+
+@pytest.mark.parametrize("k,p", [(5, 10), (31, 10), (5, 14), (31, 14)])
+def test_carriage_returns_at_lane_and_chunk_edges(ctx, oracle, host, tmp_path, k, p):
+    """kseq drops a '\\r' only where it ends a line read (before '\\n', or as the file's last byte) and only from a string longer
+    than one byte; any other '\\r' is a byte (FASTA: an invalid base; FASTQ: it counts in the length).  A lone '\\r' at every
+    offset of a 64-byte lane and on the 16 KB chunk edge, '\\r\\n' split across a lane and a chunk edge, '\\r\\r\\n', a '\\r' at
+    the end with and without a '\\n' behind it -- in FASTA sequence lines and headers, FASTQ sequence and quality lines: the
+    device refuses the genome or equals kseq.  Plain CRLF files are accepted."""
+    rng = np.random.default_rng(21)
+    g = genomes(1, 40000, 31, decorate=False)[0]
+    C = 16384
+    files = []
+    # FASTA: a header of 8 bytes, then 70-column lines; lanes are 64 bytes of the raw text
+    fa = fasta(rng, [(b"h1 x y", g[:20000]), (b"h2", g[20000:30000])], 70)
+    hdr2 = fa.index(b">h2")
+    pos = [192 + o for o in range(64)] + [C - 1, C, C + 1] + [hdr2 + 1, hdr2 + 3, 2]  # sequence lines, lane 3; chunk edge; headers
+    files += _cr_variants(fa, pos)
+    # '\\r\\n' with the '\\r' as a lane's / a chunk's last byte: lines end exactly there
+    for edge in (64 * 7, C, 2 * C):
+        t = b">e\n" + g[: edge - 3 - 1] + b"\r\n" + g[edge : edge + 5000] + b"\r\n"
+        assert t[edge - 1 : edge + 1] == b"\r\n"
+        files.append(t)
+        files.append(t[: edge - 1] + b"\r\r" + t[edge:])  # '\\r\\r\\n' across the edge
+    files += [fa + b"\r", fa[:-1] + b"\r", fa[:-1] + b"\r\n", fa[:-1] + b"\r\r"]
+    crlf = fasta(rng, [(b"c1", g[:30000]), (b"c2", g[30000:])], 61, eol=b"\r\n")
+    must_n = len(files)
+    files += [crlf, crlf[:-2], crlf[:-1]]  # CRLF; its last line without '\\r\\n'; without '\\n' (a '\\r' is the last byte)
+    # FASTQ: reads of 100 bases, records of 3 + 101 + 2 + 101 = 207 bytes
+    reads = [g[i * 100 : (i + 1) * 100] for i in range(200)]
+    fq = b"".join(b"@r\n" + r + b"\n+\n" + bytes(rng.integers(33, 75, 100, dtype=np.uint8)) + b"\n" for r in reads)
+    rec0 = 207 * 80  # the 80th record: around raw offset 16 560
+    fq_pos = [rec0 + 3 + o for o in range(0, 100, 7)] + [rec0 + 3 + 104 + o for o in range(0, 100, 7)] + [rec0 + 1, rec0 + 104]
+    fq_pos += [C - 1, C, C + 1]
+    files += _cr_variants(fq, fq_pos)
+    files += [fq[:-1] + b"\r", fq + b"\r", fq[:-1] + b"\r\r\n"]
+    fq_crlf = fq.replace(b"\n", b"\r\n")
+    must_fq = len(files)
+    files += [fq_crlf, fq_crlf[:-1]]
+    # kseq's "longer than one byte": a first quality line "\\r" counts one byte (record a fails, b is never read); a first
+    # sequence line "\\r" likewise
+    files += [b"@a\n\n+\n\r\n@b\nACGTACGTAC\n+\nIIIIIIIIII\n", b"@a\n\r\n+\nI\n@b\nACGTACGTAC\n+\nIIIIIIIIII\n",
+              b"@a\n\r\n+\n\n@b\nACGTACGTAC\n+\nIIIIIIIIII\n"]
+    for lo in range(0, len(files), 64):
+        part = files[lo : lo + 64]
+        ctx.alloc(len(part), p)
+        status = ctx.sketch_fastx_batch(part, 0, k, True)
+        got = ctx.download(0, len(part))
+        for j, f in enumerate(part):
+            gi = lo + j
+            s = reference_seq(host, tmp_path, "cr%d.fa" % gi, f)
+            if must_n <= gi < must_n + 3 or must_fq <= gi < must_fq + 2:
+                assert status[j] == 0, "file %d: a CRLF file was refused" % gi
+            if status[j]:
+                assert not got[j].any(), "a refused genome must contribute nothing"
+                continue
+            seq, off = synth.concat_for_device([s])
+            want = oracle.sketch_batch(seq, off, k, p, True)[0]
+            assert (got[j] == want).all(), "file %d: accepted, but %d registers differ from kseq's" % (gi, int((got[j] != want).sum()))

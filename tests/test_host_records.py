@@ -1,13 +1,14 @@
 """The host reader's records mode (dshh_append_fastx_records, sketch_by_seq / dist_by_seq): record starts and kseq names
-equal a small Python reference parse, and the records back to back equal what dshh_append_fastx gives with its 'N'
+equal the kseq port tests/kseq_ref.py, and the records back to back equal what dshh_append_fastx gives with its 'N'
 separators taken out."""
 import ctypes as C
 import gzip
 import os
-import re
 
 import numpy as np
 import pytest
+
+from kseq_ref import parse as kseq_parse  # (tests/kseq_ref.py)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -59,29 +60,10 @@ def genome(host, path, cap=1 << 20):
 
 
 def reference(text):
-    """kseq's view: records with their names (header up to the first white space) and sequences (FASTA: every line up
-    to the next header; FASTQ: sequence lines up to '+', then as many quality bytes as sequence bytes)"""
-    lines = text.replace("\r", "").split("\n")
-    recs, i = [], 0
-    while i < len(lines):
-        ln = lines[i]
-        if not ln or ln[0] not in ">@":
-            i += 1
-            continue
-        name = re.split(r"[ \t]", ln[1:], maxsplit=1)[0]
-        i += 1
-        seq = ""
-        while i < len(lines) and not (lines[i][:1] in (">", "@") or lines[i][:1] == "+"):
-            seq += lines[i]
-            i += 1
-        if i < len(lines) and lines[i][:1] == "+":
-            i += 1
-            q = 0
-            while i < len(lines) and q < len(seq):
-                q += len(lines[i])
-                i += 1
-        recs.append((name, seq))
-    return recs
+    """kseq's view (tests/kseq_ref.py, a port of klib's kseq_read): the records read before the first error, with their
+    names (header up to the first white space) and sequences"""
+    recs, _ = kseq_parse(text.encode("latin-1"))
+    return [(n.decode("latin-1"), s.decode("latin-1")) for n, s in recs]
 
 
 CASES = {
