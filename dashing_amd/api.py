@@ -29,9 +29,12 @@ SYMBOLS = [
     "dsh_comm_available", "dsh_comm_library", "dsh_comm_wait", "dsh_exchange_mode", "dsh_exchange_rows_device_async",
     "dsh_exchange_collect_async", "dsh_exchange_place_device", "dsh_exchange_probe_parts_async", "dsh_diag_spin_start", "dsh_diag_spin_stop", "dsh_abi_version", "dsh_preload", "dsh_comm_unique_id", "dsh_comm_init", "dsh_comm_destroy", "dsh_comm_rank", "dsh_collect_spans", "dsh_collect_spans_async",
     "dsh_allgather_device", "dsh_dist_collect", "dsh_range_parts", "dsh_dist_rows_parts_device_async", "dsh_collect_parts_async",
-    "dsh_dist_rect", "dsh_knn", "dsh_shard_plan", "dsh_dist_shard_device", "dsh_unpermute_device", "dsh_unpermute_staged_device", "dsh_unpermute_blocks_device", "dsh_tri_span", "dsh_tri_index", "dsh_partition_rows", "dsh_balance_rows", "dsh_balance_rowsets", "dsh_rowsets_from_bounds", "dsh_rowsets_rank", "dsh_alloc_host", "dsh_free_host",
+    "dsh_dist_rect", "dsh_knn", "dsh_dist_threshold", "dsh_dist_threshold_device", "dsh_dist_rect_threshold", "dsh_shard_plan", "dsh_dist_shard_device", "dsh_unpermute_device", "dsh_unpermute_staged_device", "dsh_unpermute_blocks_device", "dsh_tri_span", "dsh_tri_index", "dsh_partition_rows", "dsh_balance_rows", "dsh_balance_rowsets", "dsh_rowsets_from_bounds", "dsh_rowsets_rank", "dsh_alloc_host", "dsh_free_host",
     "dsh_set_profiling", "dsh_last_kernel_ms", "dsh_last_part_info", "dsh_finalize_phase_cycles", "dsh_set_option", "dsh_get_info", "dsh_stream",
 ]
+
+
+ERANGE = -34  # DSH_ERANGE: dist_threshold_device's capacity was too small (the exception carries n_hits)
 
 
 class DshError(RuntimeError):
@@ -145,6 +148,9 @@ def load_library():
     lib.dsh_collect_parts_async.argtypes = [vp, u64, vp, C.c_uint32, vp, vp, i32]
     lib.dsh_dist_rect.argtypes = [vp, i32, i32, i32, u64, u64, u64, u64, vp]
     lib.dsh_knn.argtypes = [vp, i32, i32, i32, u64, u64, u64, u64, C.c_uint32, vp, vp]
+    lib.dsh_dist_threshold.argtypes = [vp, i32, i32, i32, u64, u64, C.c_float, vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(u64)]
+    lib.dsh_dist_threshold_device.argtypes = [vp, i32, i32, i32, u64, u64, C.c_float, vp, vp, vp, u64, C.POINTER(u64)]
+    lib.dsh_dist_rect_threshold.argtypes = [vp, i32, i32, i32, u64, u64, u64, u64, C.c_float, vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(u64)]
     lib.dsh_shard_plan.argtypes = [vp, i32, C.c_uint32, vp]
     lib.dsh_dist_shard_device.argtypes = [vp, i32, i32, i32, C.c_uint32, C.c_uint32, vp]
     lib.dsh_unpermute_device.argtypes = [vp, vp, vp]
@@ -527,6 +533,63 @@ class Context:
             self._ck(self._lib.dsh_knn(self._h, estim, result_type, k, q_begin, q_end, r_begin, r_end, nn,
                                        idx.ctypes.data, val.ctypes.data))
         return idx, val
+
+    # ---- thresholded output (CSR of the pairs that pass; include/dashing_hip.h has the contract)
+    def _take_hits(self, colp, valp, nh):
+        """numpy copies of the library-allocated col/val, which are released here"""
+        try:
+            col = np.ctypeslib.as_array(C.cast(colp, C.POINTER(C.c_uint32)), (nh,)).copy() if nh else np.zeros(0, np.uint32)
+            val = np.ctypeslib.as_array(C.cast(valp, C.POINTER(C.c_float)), (nh,)).copy() if nh else np.zeros(0, np.float32)
+        finally:
+            self._lib.dsh_free_host(colp)
+            self._lib.dsh_free_host(valp)
+        return col, val
+
+    def dist_threshold(self, threshold, row_begin=0, row_end=None, estim=ESTIM_ERTL_MLE, result_type=JI, k=31):
+        """(row_ptr uint64 [rows + 1], col uint32, val float32): the pairs (i, j > i) of rows [row_begin, row_end) whose
+        value passes `threshold` (similarities v >= t, distances v <= t), rows and columns ascending"""
+        row_end = self.n if row_end is None else min(row_end, self.n)
+        rows = max(row_end - row_begin, 0)
+        row_ptr = np.zeros(rows + 1, np.uint64)
+        colp, valp, nh = C.c_void_p(), C.c_void_p(), C.c_uint64()
+        self._ck(self._lib.dsh_dist_threshold(self._h, estim, result_type, k, row_begin, row_end, threshold,
+                                              row_ptr.ctypes.data, C.byref(colp), C.byref(valp), C.byref(nh)))
+        col, val = self._take_hits(colp, valp, int(nh.value))
+        return row_ptr, col, val
+
+    def dist_threshold_count(self, threshold, row_begin=0, row_end=None, estim=ESTIM_ERTL_MLE, result_type=JI, k=31):
+        """row_ptr alone (counts only: nothing is emitted)"""
+        row_end = self.n if row_end is None else min(row_end, self.n)
+        row_ptr = np.zeros(max(row_end - row_begin, 0) + 1, np.uint64)
+        nh = C.c_uint64()
+        self._ck(self._lib.dsh_dist_threshold(self._h, estim, result_type, k, row_begin, row_end, threshold,
+                                              row_ptr.ctypes.data, None, None, C.byref(nh)))
+        return row_ptr
+
+    def dist_threshold_device(self, row_ptr_ptr, col_ptr, val_ptr, cap, threshold, row_begin=0, row_end=None,
+                              estim=ESTIM_ERTL_MLE, result_type=JI, k=31):
+        """device buffers of the caller (row_ptr [rows + 1] uint64, col / val of `cap` entries); returns n_hits.  If the
+        hits do not fit, raises DshError with code ERANGE and the true count in its attribute n_hits: row_ptr is complete
+        and the first `cap` hits are written."""
+        row_end = self.n if row_end is None else row_end
+        nh = C.c_uint64()
+        rc = self._lib.dsh_dist_threshold_device(self._h, estim, result_type, k, row_begin, row_end, threshold,
+                                                 C.c_void_p(row_ptr_ptr), C.c_void_p(col_ptr), C.c_void_p(val_ptr), cap, C.byref(nh))
+        if rc:
+            err = DshError(rc, self._lib.dsh_last_error(self._h).decode())
+            if rc == ERANGE:
+                err.n_hits = int(nh.value)
+            raise err
+        return int(nh.value)
+
+    def dist_rect_threshold(self, threshold, q_begin, q_end, r_begin, r_end, estim=ESTIM_ERTL_MLE, result_type=JI, k=31):
+        """as dist_threshold for the rectangle of dist_rect: one row per query, col = reference slot"""
+        row_ptr = np.zeros(max(q_end - q_begin, 0) + 1, np.uint64)
+        colp, valp, nh = C.c_void_p(), C.c_void_p(), C.c_uint64()
+        self._ck(self._lib.dsh_dist_rect_threshold(self._h, estim, result_type, k, q_begin, q_end, r_begin, r_end, threshold,
+                                                   row_ptr.ctypes.data, C.byref(colp), C.byref(valp), C.byref(nh)))
+        col, val = self._take_hits(colp, valp, int(nh.value))
+        return row_ptr, col, val
 
     # ---- multi-GPU shards (sorted-order spans + one un-permute)
     def shard_plan(self, nshards, estim=ESTIM_ERTL_MLE):

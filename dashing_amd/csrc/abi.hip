@@ -56,7 +56,8 @@ static void release_ctx(dsh_ctx *c)
     for (DevBuf *b : {&c->gather_full, &c->gather_local, &c->regs_own, &c->card, &c->planes, &c->exc, &c->exc_n, &c->excv,
                       &c->keys, &c->tailhist, &c->hist, &c->cidx_rec, &c->cidx_ent, &c->colS_n, &c->colS_key, &c->colS_card, &c->colS_th, &c->colS_rl, &c->rowoff, &c->xch_stage, &c->xch_tab, &c->place_tab, &c->sig, &c->perm, &c->items, &c->cum, &c->tiles,
                       &c->outbuf, &c->outbuf2[0], &c->outbuf2[1], &c->seqbuf, &c->workbuf, &c->phase_cyc, &c->rawbuf, &c->fx_tab,
-                      &c->fx_summ, &c->fx_state, &c->fx_declen, &c->fx_status, &c->recbuf})
+                      &c->fx_summ, &c->fx_state, &c->fx_declen, &c->fx_status, &c->recbuf, &c->thr_vals, &c->thr_cnt, &c->thr_off,
+                      &c->thr_total, &c->thr_col, &c->thr_val, &c->thr_rowptr})
         b->release();
     if (c->pin_perm) (void)hipHostFree(c->pin_perm);
     c->pin_perm = nullptr;
@@ -1096,6 +1097,11 @@ int dsh_set_option(dsh_ctx *c, const char *name, int64_t v)
     if (!std::strcmp(name, "knn_square_budget_bytes")) {
         if (v < 0) return fail(c, DSH_EINVAL, "knn_square_budget_bytes must be >= 0");
         c->knn_square_budget = (uint64_t)v;
+        return DSH_OK;
+    }
+    if (!std::strcmp(name, "threshold_band_bytes")) {
+        if (v < 4) return fail(c, DSH_EINVAL, "threshold_band_bytes must be at least 4");
+        c->threshold_band_bytes = (uint64_t)v;
         return DSH_OK;
     }
     if (!std::strcmp(name, "sort")) {

@@ -3,6 +3,7 @@
 //   abi.hip       context, resident sketches, sketch waist, cardinalities, compare entry points, tickets, options
 //   engine.hip    prepare() (per-sketch pass, layout, bit-planes, position index) and run_pairs() (tile kernel + k_finalize)
 //   knn.hip       dsh_knn
+//   threshold.hip dsh_dist_threshold*, dsh_dist_rect_threshold (values that pass a threshold, as CSR)
 //   exchange.hip  RCCL: dsh_comm_*, dsh_collect_*, dsh_allgather_device, dsh_dist_collect
 //   plan.cpp      the pure-host planner (layout, tiles, bands, parts, work items, row partitions)
 #pragma once
@@ -168,6 +169,10 @@ struct dsh_ctx {
     uint64_t cum_budget = 8ull << 30;  // scratch for C(v) per pair slot: larger jobs run in bands (2 -> 8 GiB: -1.5 % at 100 000 x p=10)
     int sort_mode = -1;  // -1 auto (key-ordered columns for triangle calls of >= range_sort_min_rows rows), 0 never
     int range_sort_min_rows = 1024;  // smaller row ranges keep the cached identity layout (a rebuild costs more than it saves)
+    // dsh_dist_threshold* (threshold.hip): a band's dense values, its per-chunk counts and offsets, the running total,
+    // and for the host forms the band's hits and the row pointer on their way out
+    DevBuf thr_vals, thr_cnt, thr_off, thr_total, thr_col, thr_val, thr_rowptr;
+    uint64_t threshold_band_bytes = (uint64_t)1 << 30;  // a band of dsh_dist_threshold* holds at most this much float32
     uint64_t knn_square_budget = (uint64_t)96 << 30;  // all-vs-all kNN keeps an n x n float matrix in HBM up to this size
     int pair_mfma = 0;  // WHAT-IF only (built with `make WHATIF=1`): 1 = the AND+popcount tile kernel on the matrix cores
     int finalize_stop = 0;  // profiling only: k_finalize leaves after phase 1..4 (results are then meaningless)
@@ -241,6 +246,14 @@ inline bool use_lockstep(const dsh_ctx *c)
     // wherever a plane is at least one chunk (p >= 9): since the kernel needs one barrier per k-row it beats the
     // free-running one at every precision (profiles/r3f/lockstep_ab.jsonl: -5 % at p = 10 ... -17 % at p = 16)
     return !(c->pair_mfma || c->W < (uint32_t)c->kc);
+}
+
+// similarity measures rank descending and pass a threshold with v >= t, distances ascending and v <= t (emt2nntype,
+// src/dashing.h:268-280): dsh_knn's order and dsh_dist_threshold's direction
+inline bool measure_descending(int result_type)
+{
+    return !(result_type == DSH_MASH_DIST || result_type == DSH_FULL_MASH_DIST || result_type == DSH_CONTAINMENT_DIST ||
+             result_type == DSH_FULL_CONTAINMENT_DIST || result_type == DSH_SYMMETRIC_CONTAINMENT_DIST);
 }
 
 inline bool whole_sorted(const dsh_ctx *c) { return c->planes_valid && c->lay.whole; }

@@ -83,7 +83,11 @@ static void usage(const char *sub)
             "  -E/-I/-m                 ORIGINAL / ERTL_IMPROVED / ERTL_MLE estimator [ERTL_MLE]\n"
             "  -W, --cache-sketches     read/write <genome>.w.<k>.spacing.<S>.hll next to the input (or in -P)\n"
             "  -H, --presketched        inputs are .hll files\n"
-            "  --avoid-sorting          keep input order (default: largest file first)\n");
+            "  --avoid-sorting          keep input order (default: largest file first)\n"
+            "  --threshold FLOAT        emit only the pairs that pass: value >= FLOAT for the similarity measures, <= FLOAT for\n"
+            "                           the distances.  Text: '#Threshold<TAB>measure<TAB>op<TAB>FLOAT', then name_i<TAB>name_j<TAB>value\n"
+            "                           per hit; -b: u64 n, u64 nnz, u64 row_ptr[n+1], u32 col[nnz], f32 val[nnz]; with -Q one row\n"
+            "                           per query.  Not with --nearest-neighbors, -U, -T or several devices.\n");
     }
     std::exit(EXIT_FAILURE);
 }
@@ -93,13 +97,15 @@ struct Opts {
     int estim = ERTL_MLE, result_type = JI, fmt = UT_TSV;
     int cache = 0, presketched = 0, avoid_sorting = 0, skip_cached = 0;
     unsigned nneighbors = 0;  // --nearest-neighbors
+    bool has_threshold = false;  // --threshold: only the pairs that pass, as (name, name, value) lines or CSR (-b)
+    float threshold = 0.f;
     int rccl = 0;             // --rccl: deliver the rows through the RCCL exchange of the C-ABI even with one device
     std::vector<int> devices;  // --devices a,b,... / --ngpus G: GPUs sharing the all-pairs rows (binary output)
     std::string paths_file, prefix, suffix, spacing, out_sizes, out_dists;
     std::vector<std::string> inpaths, querypaths;
 };
 
-enum { OPT_PRESKETCHED = 1000, OPT_AVOID_SORT, OPT_DEVICE, OPT_NPERBATCH, OPT_NN, OPT_NGPUS, OPT_DEVICES, OPT_RCCL, OPT_UNSUPPORTED };
+enum { OPT_PRESKETCHED = 1000, OPT_AVOID_SORT, OPT_DEVICE, OPT_NPERBATCH, OPT_NN, OPT_NGPUS, OPT_DEVICES, OPT_RCCL, OPT_THRESHOLD, OPT_UNSUPPORTED };
 
 static Opts parse(int argc, char **argv, bool is_dist)
 {
@@ -125,7 +131,7 @@ static Opts parse(int argc, char **argv, bool is_dist)
         {"use-bb-minhash", no_argument, nullptr, OPT_UNSUPPORTED}, {"use-range-minhash", no_argument, nullptr, OPT_UNSUPPORTED},
         {"use-bloom-filter", no_argument, nullptr, OPT_UNSUPPORTED}, {"use-nthash", no_argument, nullptr, OPT_UNSUPPORTED},
         {"use-cyclic-hash", no_argument, nullptr, OPT_UNSUPPORTED}, {"countmin", no_argument, nullptr, OPT_UNSUPPORTED},
-        {"nearest-neighbors", required_argument, nullptr, OPT_NN},
+        {"nearest-neighbors", required_argument, nullptr, OPT_NN}, {"threshold", required_argument, nullptr, OPT_THRESHOLD},
         // second arm of result_cmp (src/dashing.h:577-588); flag numbers as in DIST_LONG_OPTS
         {"sizes", no_argument, nullptr, 'Z'}, {"containment-index", no_argument, nullptr, 131},
         {"containment-dist", no_argument, nullptr, 132}, {"full-containment-dist", no_argument, nullptr, 133},
@@ -189,6 +195,13 @@ static Opts parse(int argc, char **argv, bool is_dist)
             if (std::atoi(optarg) <= 0) die("--nearest-neighbors needs a positive count");
             o.nneighbors = (unsigned)std::atoi(optarg);
             break;
+        case OPT_THRESHOLD: {
+            char *end = nullptr;
+            o.threshold = std::strtof(optarg, &end);
+            if (end == optarg || *end || o.threshold != o.threshold) die("--threshold needs a number, got '%s'", optarg);
+            o.has_threshold = true;
+            break;
+        }
         case '8': case 'y': case 'J': case OPT_UNSUPPORTED:
             die("this option selects a sketch type / emitter outside the HLL sketch+dist hot path");
         default: usage(is_dist ? "dist" : "sketch");
@@ -913,6 +926,12 @@ static int dist_main(int argc, char **argv, bool by_seq = false)
         o.inpaths = R.names;
         o.avoid_sorting = 1;
     }
+    if (o.has_threshold) {
+        if (o.nneighbors) die("--threshold does not go with --nearest-neighbors: choose one selection.");
+        if (o.fmt == UPPER_TRIANGULAR) die("--threshold does not go with -U: a PHYLIP matrix is dense.");
+        if (o.fmt == FULL_TSV) die("--threshold does not go with -T: a full TSV matrix is dense.");
+        if (o.devices.size() > 1) die("--threshold runs on one device: --ngpus / --devices are not supported.");
+    }
     std::FILE *ofp = stdout, *pairofp = stdout;
     if (!o.out_sizes.empty() && !(ofp = std::fopen(o.out_sizes.c_str(), "w"))) die("Could not open file at %s for writing.", o.out_sizes.c_str());
     if (!o.out_dists.empty() && !(pairofp = std::fopen(o.out_dists.c_str(), "wb"))) die("Could not open file at %s for writing.", o.out_dists.c_str());
@@ -970,7 +989,42 @@ static int dist_main(int argc, char **argv, bool by_seq = false)
     if (ofp != stdout) std::fclose(ofp);
     // distances (dist_loop, src/sketch_and_cmp.h:785-880)
     const uint64_t total = n ? (uint64_t)n * (n - 1) / 2 : 0;
-    if (o.nneighbors) {  // nndist_loop (src/sketch_and_cmp.h:712-783)
+    if (o.has_threshold) {  // only the pairs that pass (dsh_dist_threshold / dsh_dist_rect_threshold): no dense matrix
+        if (nq >= n && nq) die("Wrong number of query/references. (ip size: %zu, nq: %zu", n, nq);
+        const size_t nr = n - nq, rows = nq ? nq : n;
+        std::vector<uint64_t> row_ptr(rows + 1);
+        uint32_t *col = nullptr;
+        float *val = nullptr;
+        uint64_t nnz = 0;
+        if (nq) DSH(ctx, dsh_dist_rect_threshold(ctx, o.estim, o.result_type, o.k, nr, n, 0, nr, o.threshold, row_ptr.data(), &col, &val, &nnz));
+        else DSH(ctx, dsh_dist_threshold(ctx, o.estim, o.result_type, o.k, 0, n, o.threshold, row_ptr.data(), &col, &val, &nnz));
+        if (o.fmt == BINARY) {
+            const uint64_t hdr[2] = {(uint64_t)rows, nnz};
+            if (std::fwrite(hdr, sizeof(uint64_t), 2, pairofp) != 2 || std::fwrite(row_ptr.data(), sizeof(uint64_t), rows + 1, pairofp) != rows + 1 ||
+                std::fwrite(col, sizeof(uint32_t), nnz, pairofp) != nnz || std::fwrite(val, sizeof(float), nnz, pairofp) != nnz)
+                die("Error writing to binary file");
+        } else {
+            static const char *const kMeasure[9] = {"MASH_DIST", "JI", "SIZES", "FULL_MASH_DIST", "FULL_CONTAINMENT_DIST", "CONTAINMENT_INDEX",
+                                                    "CONTAINMENT_DIST", "SYMMETRIC_CONTAINMENT_INDEX", "SYMMETRIC_CONTAINMENT_DIST"};
+            const bool dist = o.result_type == 0 || o.result_type == 3 || o.result_type == 4 || o.result_type == 6 || o.result_type == 8;
+            std::fprintf(pairofp, "#Threshold\t%s\t%s\t%.6g\n", kMeasure[o.result_type], dist ? "<=" : ">=", (double)o.threshold);
+            std::string s;
+            char num[64];
+            for (size_t r = 0; r < rows; ++r) {
+                s.clear();
+                const std::string &name = o.inpaths[nq ? nr + r : r];
+                for (uint64_t h = row_ptr[r]; h < row_ptr[r + 1]; ++h) {
+                    s += name;
+                    s += '\t';
+                    s += o.inpaths[col[h]];
+                    s.append(num, (size_t)std::snprintf(num, sizeof num, "\t%.6g\n", (double)val[h]));  // format_ut_row's number format
+                }
+                std::fwrite(s.data(), 1, s.size(), pairofp);
+            }
+        }
+        dsh_free_host(col);
+        dsh_free_host(val);
+    } else if (o.nneighbors) {  // nndist_loop (src/sketch_and_cmp.h:712-783)
         const size_t nr = nq ? n - nq : n, npairs = nq ? nq : n;
         unsigned nn = o.nneighbors;
         const size_t possible = nq ? nr : (n ? n - 1 : 0);

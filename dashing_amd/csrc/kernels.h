@@ -138,6 +138,26 @@ hipError_t launch_topk_merge(hipStream_t st, const float *vals, uint64_t ld, int
                              uint64_t ncols, const uint32_t *perm, int descending, uint32_t nn, uint32_t *st_idx,
                              float *st_val);
 
+// thresholded output (kernels_threshold.hip, threshold.hip): the rows of a band buffer -- rows [row0, row0 + rows) of the
+// packed triangle of n sketches back to back (row i: n - 1 - i values, columns i + 1 ...), or rows x ncols of a rectangle
+// (columns col0 ...) -- each cut into nchunks chunks of kThrChunk values (nchunks covers the longest row)
+constexpr uint32_t kThrChunk = 4096;
+struct ThrRows {
+    int rect;
+    uint64_t n, row0;      // triangle
+    uint64_t ncols, col0;  // rectangle
+    uint64_t rows;
+    uint32_t nchunks;
+};
+// cnt[rows * nchunks]: hits per chunk (similarity measures pass with v >= t, distances with v <= t; NaN never)
+hipError_t launch_thr_count(hipStream_t st, const float *vals, const ThrRows &g, float t, int descending, uint32_t *cnt);
+// off[m + 1] = *total + exclusive scan of cnt[m] (m = rows * nchunks), row_ptr[r] = off[r * nchunks], *total = off[m]
+hipError_t launch_thr_scan(hipStream_t st, const uint32_t *cnt, uint64_t m, uint32_t nchunks, uint64_t *off, uint64_t *row_ptr,
+                           uint64_t *total);
+// hit number h (in row-major, column-ascending order) goes to col/val[h - sub] if that is below cap
+hipError_t launch_thr_emit(hipStream_t st, const float *vals, const ThrRows &g, float t, int descending, const uint64_t *off,
+                           uint64_t sub, uint64_t cap, uint32_t *col, float *val);
+
 // in-order upload of a small page-locked host buffer by a kernel (no runtime copy on the ctx stream)
 hipError_t launch_upload(hipStream_t st, void *dst, const void *src_pinned, size_t bytes);
 

@@ -22,9 +22,7 @@ int dsh_knn(dsh_ctx *c, int estim, int result_type, int k, uint64_t qb, uint64_t
     if (qb >= qe || nn == 0) return DSH_OK;
     if (!idx_out || !val_out) return DSH_EINVAL;
     // similarity measures rank descending, distances ascending (emt2nntype, src/dashing.h:268-280)
-    const int descending = !(result_type == DSH_MASH_DIST || result_type == DSH_FULL_MASH_DIST ||
-                             result_type == DSH_CONTAINMENT_DIST || result_type == DSH_FULL_CONTAINMENT_DIST ||
-                             result_type == DSH_SYMMETRIC_CONTAINMENT_DIST);
+    const int descending = measure_descending(result_type);
     const uint64_t nq = qe - qb, nr = re > rb ? re - rb : 0;
     const bool overlap = qb < re && rb < qe;
     if (qb == 0 && rb == 0 && qe == c->n && re == c->n && c->n > 1 &&

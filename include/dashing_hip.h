@@ -32,6 +32,7 @@ extern "C" {
 #define DSH_ENODEV (-19)  /* no usable gfx950 device */
 #define DSH_EIO (-5)      /* HIP runtime error / file error */
 #define DSH_ESTATE (-11)  /* call sequence error (e.g. dist before sketches are loaded) */
+#define DSH_ERANGE (-34)  /* the result does not fit the capacity the caller gave (dsh_dist_threshold_device) */
 
 /* sketch::hll::EstimationMethod values selected by dist_main, src/distmain.cpp:37,59-62
  * (-E ORIGINAL, -I ERTL_IMPROVED, default/-m ERTL_MLE). */
@@ -57,7 +58,9 @@ typedef struct dsh_ctx dsh_ctx;
 /* ABI version: bumped whenever an entry point changes its signature or a table its layout (6: dsh_exchange_* take a
  * row-set table instead of bounds + world; 7: dsh_sketch_records*).  A host compiled against another DSH_ABI_VERSION links fine but would pass
  * shifted arguments: compare with dsh_abi_version() once at start-up.  (A bounds array handed to a function that now
- * parses a row-set table is refused, not over-read: its first word, 0, is not a valid world.) */
+ * parses a row-set table is refused, not over-read: its first word, 0, is not a valid world.)
+ * Entry points that were only ADDED since leave the number alone and are detected by symbol (dlsym):
+ * dsh_dist_threshold, dsh_dist_threshold_device, dsh_dist_rect_threshold. */
 #define DSH_ABI_VERSION 7
 int dsh_abi_version(void);
 
@@ -232,6 +235,41 @@ int dsh_dist_rect(dsh_ctx *ctx, int estim, int result_type, int k, uint64_t q_be
  * queries x all references. */
 int dsh_knn(dsh_ctx *ctx, int estim, int result_type, int k, uint64_t q_begin, uint64_t q_end,
             uint64_t r_begin, uint64_t r_end, uint32_t nn, uint32_t *idx_out, float *val_out);
+
+/* ---- thresholded output: sparse hits instead of the dense matrix --------------------------------
+ * Replaces what a dereplication or clustering client does with the output of dist_loop / partdist_loop
+ * (src/sketch_and_cmp.h:785-830, src/dashing.h:660-712): scan the whole matrix for the pairs with, say, Jaccard >= t and
+ * drop the rest.  Here the selection runs on the device, band by band (bands of whole rows of at most
+ * "threshold_band_bytes" of float32, option, default 1 GiB), and only the hits leave it, as CSR:
+ *   row_ptr  [rows + 1] uint64, relative to the first row of the call (row_ptr[0] = 0, row_ptr[rows] = n_hits)
+ *   col      [n_hits] uint32, original slot numbers, ascending inside a row
+ *   val      [n_hits] float32
+ * The values are exactly the float32 values dsh_dist_rows / dsh_dist_rect give for the same estim, result_type and k
+ * (that path computes them); a value passes by a float32 comparison with `threshold`: v >= threshold for the similarity
+ * forms (JI, SIZES, CONTAINMENT_INDEX, SYMMETRIC_CONTAINMENT_INDEX), v <= threshold for the *_DIST forms (dsh_knn's
+ * rule, emt2nntype, src/dashing.h:268-280); NaN never passes.  The same call on the same sketches gives the same bytes,
+ * whatever the band size.  The calls are synchronous and leave the context free for any other call.
+ * Triangle form: rows i in [row_begin,row_end) (row_end is cut at n; rows = what is left), columns j > i, in the ONE
+ * orientation dsh_dist_rows computes, result_cmp(lhs = sketch_j, rhs = sketch_i): for the asymmetric measures
+ * (CONTAINMENT_INDEX, CONTAINMENT_DIST, FULL_CONTAINMENT_DIST) the pair (i,j) is tested in that orientation only.
+ * An empty range, n < 2, a threshold nothing passes and one everything passes are all valid.
+ *   dsh_dist_threshold         host result.  row_ptr_out is the caller's [rows + 1]; *col_out / *val_out are allocated by
+ *                              the library as dsh_alloc_host allocates (the number of hits is not known before the pass,
+ *                              and counting first would pay the compare twice) and are released by the caller with
+ *                              dsh_free_host, also when there is no hit.  col_out = val_out = NULL: counts only.
+ *   dsh_dist_threshold_device  caller-owned DEVICE buffers: d_row_ptr [rows + 1] uint64, d_col / d_val of `cap` entries
+ *                              (both NULL: counts only).  row_ptr and *n_hits are always complete; with *n_hits > cap
+ *                              the first cap hits are written, nothing beyond, and the call returns DSH_ERANGE with a
+ *                              message in dsh_last_error: call again with room for *n_hits.
+ *   dsh_dist_rect_threshold    queries [q_begin,q_end) x references [r_begin,r_end) as dsh_dist_rect, one row per query,
+ *                              col = reference slot; host result with the conventions of dsh_dist_threshold. */
+int dsh_dist_threshold(dsh_ctx *ctx, int estim, int result_type, int k, uint64_t row_begin, uint64_t row_end, float threshold,
+                       uint64_t *row_ptr_out, uint32_t **col_out, float **val_out, uint64_t *n_hits);
+int dsh_dist_threshold_device(dsh_ctx *ctx, int estim, int result_type, int k, uint64_t row_begin, uint64_t row_end,
+                              float threshold, void *d_row_ptr, void *d_col, void *d_val, uint64_t cap, uint64_t *n_hits);
+int dsh_dist_rect_threshold(dsh_ctx *ctx, int estim, int result_type, int k, uint64_t q_begin, uint64_t q_end, uint64_t r_begin,
+                            uint64_t r_end, float threshold, uint64_t *row_ptr_out, uint32_t **col_out, float **val_out,
+                            uint64_t *n_hits);
 
 /* ---- multi-GPU shards of the full triangle ------------------------------------------------
  * Every rank holds all sketches (dsh_upload/attach) and computes one shard; no collective is
@@ -442,6 +480,7 @@ int dsh_finalize_phase_cycles(dsh_ctx *ctx, uint64_t *out16);
  * hardware needs:
  *   resources     "cum_budget_bytes"        scratch for the pair counts C(v) (default 8 GiB): larger jobs run in bands
  *                 "knn_square_budget_bytes" all-vs-all dsh_knn keeps an n x n float matrix in HBM up to this size (96 GiB)
+ *                 "threshold_band_bytes"    dsh_dist_threshold* computes bands of whole rows of at most this much float32 (1 GiB)
  *   layout        "sort"                    -1 auto | 0 | 1: key-ordered plane columns (0 = identity: the slow, simple layout)
  *                 "range_sort_min_rows"     row ranges shorter than this keep the cached identity layout (default 1024)
  *                 "emax" / "elow"           caps of the listed upper / lower register tail, 0..255, -1 auto (per precision);
