@@ -29,7 +29,7 @@ SYMBOLS = [
     "dsh_comm_available", "dsh_comm_library", "dsh_comm_wait", "dsh_exchange_mode", "dsh_exchange_rows_device_async",
     "dsh_exchange_collect_async", "dsh_exchange_place_device", "dsh_exchange_probe_parts_async", "dsh_diag_spin_start", "dsh_diag_spin_stop", "dsh_abi_version", "dsh_preload", "dsh_comm_unique_id", "dsh_comm_init", "dsh_comm_destroy", "dsh_comm_rank", "dsh_collect_spans", "dsh_collect_spans_async",
     "dsh_allgather_device", "dsh_dist_collect", "dsh_range_parts", "dsh_dist_rows_parts_device_async", "dsh_collect_parts_async",
-    "dsh_dist_rect", "dsh_knn", "dsh_dist_threshold", "dsh_dist_threshold_device", "dsh_dist_rect_threshold", "dsh_shard_plan", "dsh_dist_shard_device", "dsh_unpermute_device", "dsh_unpermute_staged_device", "dsh_unpermute_blocks_device", "dsh_tri_span", "dsh_tri_index", "dsh_partition_rows", "dsh_balance_rows", "dsh_balance_rowsets", "dsh_rowsets_from_bounds", "dsh_rowsets_rank", "dsh_alloc_host", "dsh_free_host",
+    "dsh_dist_rect", "dsh_knn", "dsh_dist_threshold", "dsh_dist_threshold_device", "dsh_dist_rect_threshold", "dsh_dist_pairs", "dsh_dist_pairs_device", "dsh_dist_pairs_csr", "dsh_shard_plan", "dsh_dist_shard_device", "dsh_unpermute_device", "dsh_unpermute_staged_device", "dsh_unpermute_blocks_device", "dsh_tri_span", "dsh_tri_index", "dsh_partition_rows", "dsh_balance_rows", "dsh_balance_rowsets", "dsh_rowsets_from_bounds", "dsh_rowsets_rank", "dsh_alloc_host", "dsh_free_host",
     "dsh_set_profiling", "dsh_last_kernel_ms", "dsh_last_part_info", "dsh_finalize_phase_cycles", "dsh_set_option", "dsh_get_info", "dsh_stream",
 ]
 
@@ -151,6 +151,9 @@ def load_library():
     lib.dsh_dist_threshold.argtypes = [vp, i32, i32, i32, u64, u64, C.c_float, vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(u64)]
     lib.dsh_dist_threshold_device.argtypes = [vp, i32, i32, i32, u64, u64, C.c_float, vp, vp, vp, u64, C.POINTER(u64)]
     lib.dsh_dist_rect_threshold.argtypes = [vp, i32, i32, i32, u64, u64, u64, u64, C.c_float, vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(u64)]
+    lib.dsh_dist_pairs.argtypes = [vp, i32, vp, C.c_uint32, i32, vp, vp, u64, vp]
+    lib.dsh_dist_pairs_device.argtypes = [vp, i32, vp, C.c_uint32, i32, vp, vp, u64, vp]
+    lib.dsh_dist_pairs_csr.argtypes = [vp, i32, vp, C.c_uint32, i32, u64, u64, vp, vp, vp]
     lib.dsh_shard_plan.argtypes = [vp, i32, C.c_uint32, vp]
     lib.dsh_dist_shard_device.argtypes = [vp, i32, i32, i32, C.c_uint32, C.c_uint32, vp]
     lib.dsh_unpermute_device.argtypes = [vp, vp, vp]
@@ -590,6 +593,47 @@ class Context:
                                                    row_ptr.ctypes.data, C.byref(colp), C.byref(valp), C.byref(nh)))
         col, val = self._take_hits(colp, valp, int(nh.value))
         return row_ptr, col, val
+
+    # ---- an explicit list of pairs (include/dashing_hip.h has the contract)
+    @staticmethod
+    def _types(result_types):
+        return np.ascontiguousarray(np.atleast_1d(np.asarray(result_types, np.int32)).reshape(-1))
+
+    def dist_pairs(self, lhs, rhs, result_types=(JI,), estim=ESTIM_ERTL_MLE, k=31):
+        """float32 [n_types][n_pairs]: out[t][x] = result_cmp(lhs = sketch lhs[x], rhs = sketch rhs[x], result_types[t]),
+        bit for bit the value of dist_rows at (i = rhs, j = lhs > i) and of dist_rect at [query = rhs][reference = lhs]"""
+        lhs = np.ascontiguousarray(lhs, np.uint32).reshape(-1)
+        rhs = np.ascontiguousarray(rhs, np.uint32).reshape(-1)
+        if lhs.size != rhs.size:
+            raise ValueError("lhs and rhs differ in length")
+        ty = self._types(result_types)
+        out = np.zeros((ty.size, lhs.size), np.float32)
+        self._ck(self._lib.dsh_dist_pairs(self._h, estim, ty.ctypes.data, ty.size, k, lhs.ctypes.data, rhs.ctypes.data,
+                                          lhs.size, out.ctypes.data))
+        return out
+
+    def dist_pairs_device(self, lhs_ptr, rhs_ptr, n_pairs, out_ptr, result_types=(JI,), estim=ESTIM_ERTL_MLE, k=31):
+        """device buffers of the caller: lhs / rhs uint32 [n_pairs], out float32 [n_types][n_pairs]"""
+        ty = self._types(result_types)
+        self._ck(self._lib.dsh_dist_pairs_device(self._h, estim, ty.ctypes.data, ty.size, k, C.c_void_p(lhs_ptr),
+                                                 C.c_void_p(rhs_ptr), n_pairs, C.c_void_p(out_ptr)))
+
+    def dist_pairs_csr(self, row_ptr, col, row_begin=0, result_types=(JI,), estim=ESTIM_ERTL_MLE, k=31):
+        """the hits of dist_threshold / dist_rect_threshold again: hit h of row r is (lhs = col[h], rhs = row_begin + r);
+        float32 [n_types][n_hits]"""
+        row_ptr = np.ascontiguousarray(row_ptr, np.uint64).reshape(-1)
+        col = np.ascontiguousarray(col, np.uint32).reshape(-1)
+        if row_ptr.size < 1:
+            raise ValueError("row_ptr holds rows + 1 entries")
+        rows = row_ptr.size - 1
+        nh = int(row_ptr[-1]) - int(row_ptr[0])
+        if nh > 0 and int(row_ptr[-1]) > col.size:
+            raise ValueError("col is shorter than row_ptr says")
+        ty = self._types(result_types)
+        out = np.zeros((ty.size, max(nh, 0)), np.float32)
+        self._ck(self._lib.dsh_dist_pairs_csr(self._h, estim, ty.ctypes.data, ty.size, k, row_begin, rows, row_ptr.ctypes.data,
+                                              col.ctypes.data, out.ctypes.data))
+        return out
 
     # ---- multi-GPU shards (sorted-order spans + one un-permute)
     def shard_plan(self, nshards, estim=ESTIM_ERTL_MLE):

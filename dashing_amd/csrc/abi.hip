@@ -57,7 +57,8 @@ static void release_ctx(dsh_ctx *c)
                       &c->keys, &c->tailhist, &c->hist, &c->cidx_rec, &c->cidx_ent, &c->colS_n, &c->colS_key, &c->colS_card, &c->colS_th, &c->colS_rl, &c->rowoff, &c->xch_stage, &c->xch_tab, &c->place_tab, &c->sig, &c->perm, &c->items, &c->cum, &c->tiles,
                       &c->outbuf, &c->outbuf2[0], &c->outbuf2[1], &c->seqbuf, &c->workbuf, &c->phase_cyc, &c->rawbuf, &c->fx_tab,
                       &c->fx_summ, &c->fx_state, &c->fx_declen, &c->fx_status, &c->recbuf, &c->thr_vals, &c->thr_cnt, &c->thr_off,
-                      &c->thr_total, &c->thr_col, &c->thr_val, &c->thr_rowptr})
+                      &c->thr_total, &c->thr_col, &c->thr_val, &c->thr_rowptr, &c->pairs_card, &c->pairs_hist, &c->pairs_lhs,
+                      &c->pairs_rhs, &c->pairs_out, &c->pairs_err})
         b->release();
     if (c->pin_perm) (void)hipHostFree(c->pin_perm);
     c->pin_perm = nullptr;
@@ -69,8 +70,9 @@ static void release_ctx(dsh_ctx *c)
     c->pin_sig.release();
     c->pin_fx.release();
     c->pin_rec.release();
+    c->pin_pairs.release();
     for (hipEvent_t *e : {&c->ev_fx, &c->ev_work, &c->ev_rec, &c->ev_lists, &c->ev_perm, &c->ev_keys, &c->ev_filled[0], &c->ev_filled[1],
-                          &c->ev_drained[0], &c->ev_drained[1], &c->ev_aux_fork, &c->ev_aux_join, &c->ev_xch_tab, &c->ev_place_done, &c->ev_first_tiles, &c->ev_sig}) {
+                          &c->ev_drained[0], &c->ev_drained[1], &c->ev_aux_fork, &c->ev_aux_join, &c->ev_xch_tab, &c->ev_place_done, &c->ev_first_tiles, &c->ev_sig, &c->ev_pairs}) {
         if (*e) (void)hipEventDestroy(*e);
         *e = nullptr;
     }
@@ -1102,6 +1104,11 @@ int dsh_set_option(dsh_ctx *c, const char *name, int64_t v)
     if (!std::strcmp(name, "threshold_band_bytes")) {
         if (v < 4) return fail(c, DSH_EINVAL, "threshold_band_bytes must be at least 4");
         c->threshold_band_bytes = (uint64_t)v;
+        return DSH_OK;
+    }
+    if (!std::strcmp(name, "pairs_chunk")) {
+        if (v < 1 || v > (1 << 24)) return fail(c, DSH_EINVAL, "pairs_chunk must be in [1, 2^24]");
+        c->pairs_chunk = (uint64_t)v;
         return DSH_OK;
     }
     if (!std::strcmp(name, "sort")) {

@@ -4,6 +4,7 @@
 //   engine.hip    prepare() (per-sketch pass, layout, bit-planes, position index) and run_pairs() (tile kernel + k_finalize)
 //   knn.hip       dsh_knn
 //   threshold.hip dsh_dist_threshold*, dsh_dist_rect_threshold (values that pass a threshold, as CSR)
+//   pairs.hip     dsh_dist_pairs* (values of an explicit list of pairs, the direct form)
 //   exchange.hip  RCCL: dsh_comm_*, dsh_collect_*, dsh_allgather_device, dsh_dist_collect
 //   plan.cpp      the pure-host planner (layout, tiles, bands, parts, work items, row partitions)
 #pragma once
@@ -174,6 +175,13 @@ struct dsh_ctx {
     DevBuf thr_vals, thr_cnt, thr_off, thr_total, thr_col, thr_val, thr_rowptr;
     uint64_t threshold_band_bytes = (uint64_t)1 << 30;  // a band of dsh_dist_threshold* holds at most this much float32
     uint64_t knn_square_budget = (uint64_t)96 << 30;  // all-vs-all kNN keeps an n x n float matrix in HBM up to this size
+    // dsh_dist_pairs* (pairs.hip): the path's OWN cardinalities (nothing of the dense path's derived state is read or
+    // written), a chunk's histograms, the host forms' chunk of the list and of the result, the error words
+    DevBuf pairs_card, pairs_hist, pairs_lhs, pairs_rhs, pairs_out, pairs_err;
+    PinBuf pin_pairs;                   // host forms: a chunk of the list on its way to the device
+    hipEvent_t ev_pairs = nullptr;      // its upload has run
+    int pairs_card_estim = -1;          // estimator pairs_card was computed under (-1: none), dropped by invalidate()
+    uint64_t pairs_chunk = 1u << 18;    // option: pairs per launch (scratch is 64 counters per pair of a chunk)
     int pair_mfma = 0;  // WHAT-IF only (built with `make WHATIF=1`): 1 = the AND+popcount tile kernel on the matrix cores
     int finalize_stop = 0;  // profiling only: k_finalize leaves after phase 1..4 (results are then meaningless)
     int finalize_timing = 0;  // profiling only: the s_memtime-stamped instance of k_finalize (same results, per-phase cycles)
@@ -263,6 +271,7 @@ inline void invalidate(dsh_ctx *c)
     c->planes_valid = false;
     c->card_estim = -1;
     c->hk32_valid = false;
+    c->pairs_card_estim = -1;
 }
 
 // hipStreamWaitValue32 on this device (asked once): what lets the parts of a call announce themselves from inside k_finalize

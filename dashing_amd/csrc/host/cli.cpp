@@ -22,6 +22,7 @@
 #include <cstring>
 #include <string>
 #include <thread>
+#include <unordered_map>
 #include <vector>
 
 #include "../../../include/dashing_hip.h"
@@ -87,7 +88,13 @@ static void usage(const char *sub)
             "  --threshold FLOAT        emit only the pairs that pass: value >= FLOAT for the similarity measures, <= FLOAT for\n"
             "                           the distances.  Text: '#Threshold<TAB>measure<TAB>op<TAB>FLOAT', then name_i<TAB>name_j<TAB>value\n"
             "                           per hit; -b: u64 n, u64 nnz, u64 row_ptr[n+1], u32 col[nnz], f32 val[nnz]; with -Q one row\n"
-            "                           per query.  Not with --nearest-neighbors, -U, -T or several devices.\n");
+            "                           per query.  Not with --nearest-neighbors, -U, -T or several devices.\n"
+            "  --pairs FILE             emit only the pairs FILE lists, one per line as name_a<TAB>name_b (input names as given\n"
+            "                           here; record names with dist_by_seq), in FILE's order: name_a<TAB>name_b and one value per\n"
+            "                           measure.  --measures LIST: comma-separated from MASH_DIST, JI, SIZES, FULL_MASH_DIST,\n"
+            "                           FULL_CONTAINMENT_DIST, CONTAINMENT_INDEX, CONTAINMENT_DIST, SYMMETRIC_CONTAINMENT_INDEX,\n"
+            "                           SYMMETRIC_CONTAINMENT_DIST [the measure the other flags select].  Not with -Q,\n"
+            "                           --nearest-neighbors, --threshold, -b or several devices.\n");
     }
     std::exit(EXIT_FAILURE);
 }
@@ -99,13 +106,14 @@ struct Opts {
     unsigned nneighbors = 0;  // --nearest-neighbors
     bool has_threshold = false;  // --threshold: only the pairs that pass, as (name, name, value) lines or CSR (-b)
     float threshold = 0.f;
+    std::string pairs_file, measures;  // --pairs FILE [--measures LIST]: only the listed pairs (dsh_dist_pairs)
     int rccl = 0;             // --rccl: deliver the rows through the RCCL exchange of the C-ABI even with one device
     std::vector<int> devices;  // --devices a,b,... / --ngpus G: GPUs sharing the all-pairs rows (binary output)
     std::string paths_file, prefix, suffix, spacing, out_sizes, out_dists;
     std::vector<std::string> inpaths, querypaths;
 };
 
-enum { OPT_PRESKETCHED = 1000, OPT_AVOID_SORT, OPT_DEVICE, OPT_NPERBATCH, OPT_NN, OPT_NGPUS, OPT_DEVICES, OPT_RCCL, OPT_THRESHOLD, OPT_UNSUPPORTED };
+enum { OPT_PRESKETCHED = 1000, OPT_AVOID_SORT, OPT_DEVICE, OPT_NPERBATCH, OPT_NN, OPT_NGPUS, OPT_DEVICES, OPT_RCCL, OPT_THRESHOLD, OPT_PAIRS, OPT_MEASURES, OPT_UNSUPPORTED };
 
 static Opts parse(int argc, char **argv, bool is_dist)
 {
@@ -132,6 +140,7 @@ static Opts parse(int argc, char **argv, bool is_dist)
         {"use-bloom-filter", no_argument, nullptr, OPT_UNSUPPORTED}, {"use-nthash", no_argument, nullptr, OPT_UNSUPPORTED},
         {"use-cyclic-hash", no_argument, nullptr, OPT_UNSUPPORTED}, {"countmin", no_argument, nullptr, OPT_UNSUPPORTED},
         {"nearest-neighbors", required_argument, nullptr, OPT_NN}, {"threshold", required_argument, nullptr, OPT_THRESHOLD},
+        {"pairs", required_argument, nullptr, OPT_PAIRS}, {"measures", required_argument, nullptr, OPT_MEASURES},
         // second arm of result_cmp (src/dashing.h:577-588); flag numbers as in DIST_LONG_OPTS
         {"sizes", no_argument, nullptr, 'Z'}, {"containment-index", no_argument, nullptr, 131},
         {"containment-dist", no_argument, nullptr, 132}, {"full-containment-dist", no_argument, nullptr, 133},
@@ -202,6 +211,8 @@ static Opts parse(int argc, char **argv, bool is_dist)
             o.has_threshold = true;
             break;
         }
+        case OPT_PAIRS: o.pairs_file = optarg; break;
+        case OPT_MEASURES: o.measures = optarg; break;
         case '8': case 'y': case 'J': case OPT_UNSUPPORTED:
             die("this option selects a sketch type / emitter outside the HLL sketch+dist hot path");
         default: usage(is_dist ? "dist" : "sketch");
@@ -932,12 +943,39 @@ static int dist_main(int argc, char **argv, bool by_seq = false)
         if (o.fmt == FULL_TSV) die("--threshold does not go with -T: a full TSV matrix is dense.");
         if (o.devices.size() > 1) die("--threshold runs on one device: --ngpus / --devices are not supported.");
     }
+    static const char *const kMeasureNames[9] = {"MASH_DIST", "JI", "SIZES", "FULL_MASH_DIST", "FULL_CONTAINMENT_DIST", "CONTAINMENT_INDEX",
+                                                 "CONTAINMENT_DIST", "SYMMETRIC_CONTAINMENT_INDEX", "SYMMETRIC_CONTAINMENT_DIST"};
+    const bool with_pairs = !o.pairs_file.empty();
+    std::vector<std::pair<std::string, std::string>> pair_names;
+    std::vector<int> pair_types;
+    if (!o.measures.empty() && !with_pairs) die("--measures goes with --pairs only.");
+    if (with_pairs) {
+        if (!o.querypaths.empty()) die("--pairs does not go with -Q: the list names the pairs, from all inputs.");
+        if (o.nneighbors) die("--pairs does not go with --nearest-neighbors: choose one selection.");
+        if (o.has_threshold) die("--pairs does not go with --threshold: choose one selection.");
+        if (o.fmt == BINARY) die("--pairs does not go with -b: the output is one text line per pair.");
+        if (o.devices.size() > 1) die("--pairs runs on one device: --ngpus / --devices are not supported.");
+        const long bad = read_pairs_file(o.pairs_file, pair_names);
+        if (bad < 0) die("Could not open %s", o.pairs_file.c_str());
+        if (bad > 0) die("%s, line %ld: a pair is two names separated by one tab.", o.pairs_file.c_str(), bad);
+        if (o.measures.empty()) pair_types.push_back(o.result_type);
+        for (size_t b = 0; b <= o.measures.size() && !o.measures.empty();) {  // (an empty element, a trailing comma included, is no measure)
+            const size_t e = std::min(o.measures.find(',', b), o.measures.size());
+            const std::string name = o.measures.substr(b, e - b);
+            int t = 0;
+            while (t < 9 && name != kMeasureNames[t]) ++t;
+            if (t == 9) die("--measures: unknown measure '%s'", name.c_str());
+            pair_types.push_back(t);
+            b = e + 1;
+        }
+        if (pair_types.empty() || pair_types.size() > 9) die("--measures takes one to nine names.");
+    }
     std::FILE *ofp = stdout, *pairofp = stdout;
     if (!o.out_sizes.empty() && !(ofp = std::fopen(o.out_sizes.c_str(), "w"))) die("Could not open file at %s for writing.", o.out_sizes.c_str());
     if (!o.out_dists.empty() && !(pairofp = std::fopen(o.out_dists.c_str(), "wb"))) die("Could not open file at %s for writing.", o.out_dists.c_str());
     // asymmetric measure without -Q: all references are also the queries (src/distmain.cpp:120-125)
     const bool symmetric = !(o.result_type == 4 || o.result_type == 5 || o.result_type == 6);  // src/dashing.h:389-399
-    if (o.querypaths.empty() && !symmetric) {
+    if (o.querypaths.empty() && !symmetric && !with_pairs) {  // (a pair list names its own pairs, each in one orientation)
         o.querypaths = o.inpaths;
         std::fprintf(stderr, "Note: No query files provided, but an asymmetric distance was requested. Switching to a query/reference format with all references as queries.\n");
     }
@@ -948,6 +986,19 @@ static int dist_main(int argc, char **argv, bool by_seq = false)
     const size_t nq = o.querypaths.size();
     for (auto &q : o.querypaths) o.inpaths.push_back(q);  // queries follow the references (src/distmain.cpp:130-133)
     const size_t n = o.inpaths.size();
+    std::vector<uint32_t> lhs, rhs;  // --pairs: the slots of the listed names, looked up before anything is sketched
+    if (with_pairs) {
+        std::unordered_map<std::string, uint32_t> slot_of;
+        for (size_t i = n; i-- > 0;) slot_of[o.inpaths[i]] = (uint32_t)i;  // (a name given twice: its first slot)
+        lhs.resize(pair_names.size());
+        rhs.resize(pair_names.size());
+        for (size_t x = 0; x < pair_names.size(); ++x) {
+            const auto a = slot_of.find(pair_names[x].first), b = slot_of.find(pair_names[x].second);
+            if (a == slot_of.end()) die("%s: '%s' is not one of the inputs.", o.pairs_file.c_str(), pair_names[x].first.c_str());
+            if (b == slot_of.end()) die("%s: '%s' is not one of the inputs.", o.pairs_file.c_str(), pair_names[x].second.c_str());
+            lhs[x] = a->second, rhs[x] = b->second;
+        }
+    }
     const double t_start = now_s();
     since_launch("dist: options parsed, context thread about to start");
     CtxFuture cf(o.device, n, o.S, (o.presketched || by_seq) ? 0 : staging_bytes_for(o.inpaths));  // the HIP runtime comes up while the first batch is read
@@ -989,7 +1040,21 @@ static int dist_main(int argc, char **argv, bool by_seq = false)
     if (ofp != stdout) std::fclose(ofp);
     // distances (dist_loop, src/sketch_and_cmp.h:785-880)
     const uint64_t total = n ? (uint64_t)n * (n - 1) / 2 : 0;
-    if (o.has_threshold) {  // only the pairs that pass (dsh_dist_threshold / dsh_dist_rect_threshold): no dense matrix
+    if (with_pairs) {  // only the listed pairs (dsh_dist_pairs): the first name is lhs, the second rhs of result_cmp
+        const size_t np = pair_names.size(), nt = pair_types.size();
+        std::vector<float> vals(std::max<size_t>(np * nt, 1));
+        DSH(ctx, dsh_dist_pairs(ctx, o.estim, pair_types.data(), (uint32_t)nt, o.k, lhs.data(), rhs.data(), np, vals.data()));
+        std::string s;
+        char num[64];
+        for (size_t x = 0; x < np; ++x) {
+            s = pair_names[x].first;
+            s += '\t';
+            s += pair_names[x].second;
+            for (size_t t = 0; t < nt; ++t) s.append(num, (size_t)std::snprintf(num, sizeof num, "\t%.6g", (double)vals[t * np + x]));  // --threshold's number format
+            s += '\n';
+            std::fwrite(s.data(), 1, s.size(), pairofp);
+        }
+    } else if (o.has_threshold) {  // only the pairs that pass (dsh_dist_threshold / dsh_dist_rect_threshold): no dense matrix
         if (nq >= n && nq) die("Wrong number of query/references. (ip size: %zu, nq: %zu", n, nq);
         const size_t nr = n - nq, rows = nq ? nq : n;
         std::vector<uint64_t> row_ptr(rows + 1);

@@ -14,6 +14,32 @@
 
 namespace dshh {
 
+long read_pairs_file(const std::string &path, std::vector<std::pair<std::string, std::string>> &out)
+{
+    gzFile fp = gzopen(path.c_str(), "rb");
+    if (!fp) return -1;
+    std::string line;
+    char buf[65536];
+    long lineno = 0, bad = 0;
+    auto take = [&]() {
+        ++lineno;
+        while (!line.empty() && (line.back() == '\n' || line.back() == '\r')) line.pop_back();
+        if (!line.empty() && !bad) {
+            const size_t tab = line.find('\t');
+            if (tab == std::string::npos || tab == 0 || tab + 1 == line.size() || line.find('\t', tab + 1) != std::string::npos) bad = lineno;
+            else out.emplace_back(line.substr(0, tab), line.substr(tab + 1));
+        }
+        line.clear();
+    };
+    while (gzgets(fp, buf, sizeof buf)) {
+        line += buf;
+        if (!line.empty() && line.back() == '\n') take();
+    }
+    if (!line.empty()) take();
+    gzclose(fp);
+    return bad;
+}
+
 std::vector<std::string> read_paths_file(const std::string &path)
 {
     std::vector<std::string> out;

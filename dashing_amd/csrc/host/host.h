@@ -6,6 +6,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <string>
+#include <utility>
 #include <vector>
 
 namespace dshh {
@@ -18,6 +19,10 @@ enum Estim { ORIGINAL = 0, ERTL_IMPROVED = 1, ERTL_MLE = 2 };
 // ---- input handling ---------------------------------------------------------------------
 // get_paths: one path per line (used for -F / -Q, src/distmain.cpp:113-114).
 std::vector<std::string> read_paths_file(const std::string &path);
+// `dist --pairs FILE`: one pair per line, two names separated by a tab (a trailing '\r' is dropped, empty lines are
+// skipped).  Returns 0, -1 if the file cannot be opened, or the 1-based number of the first line without exactly two
+// non-empty fields.
+long read_pairs_file(const std::string &path, std::vector<std::pair<std::string, std::string>> &out);
 // for_each_substr (src/substrs.h:7-26): a "genome" may be several files joined by ' '.
 std::vector<std::string> split_genome_paths(const std::string &s, char sep = ' ');
 // posix_fsizes (src/finalizers.cpp:23-27): total size of the files of one genome entry.

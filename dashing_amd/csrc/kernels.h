@@ -158,6 +158,24 @@ hipError_t launch_thr_scan(hipStream_t st, const uint32_t *cnt, uint64_t m, uint
 hipError_t launch_thr_emit(hipStream_t st, const float *vals, const ThrRows &g, float t, int descending, const uint64_t *off,
                            uint64_t sub, uint64_t cap, uint32_t *col, float *val);
 
+// explicit pair lists (kernels_pairs.hip, pairs.hip): histograms are [cnt][64] counters, uint16 for p <= kPairsMaxP16
+// (a bin holds at most 2^p), uint32 above
+constexpr int kPairsMaxP16 = 15;
+struct PairsTypes {
+    int t[9];
+};
+// hist[x] = histogram of max(sketch lhs[x], sketch rhs[x]) for x in [0, cnt); lhs == nullptr: of sketch first + x alone.
+// err (device, 2 x u64, may be nullptr with lhs == nullptr): [0] = min over the pairs naming a slot >= n of xbase + x,
+// [1] = min over the named sketches that hold an out-of-range register; the caller initialises both to ~0
+hipError_t launch_pairs_hist(hipStream_t st, const uint8_t *regs, uint64_t n, int p, const uint32_t *lhs, const uint32_t *rhs,
+                             uint64_t first, uint64_t xbase, uint64_t cnt, void *hist, unsigned long long *err);
+// card[first + x] = estimate of hist[x], x in [0, cnt)
+hipError_t launch_pairs_card(hipStream_t st, const void *hist, uint64_t first, uint64_t cnt, int p, int estim, double *card);
+// out[t * out_stride + x] = float(result_cmp(card[lhs[x]], card[rhs[x]], estimate of hist[x], types.t[t], ksinv))
+hipError_t launch_pairs_finish(hipStream_t st, const void *hist, const uint32_t *lhs, const uint32_t *rhs, uint64_t n, uint64_t cnt,
+                               int p, int estim, const double *card, const PairsTypes &types, uint32_t n_types, double ksinv,
+                               float *out, uint64_t out_stride);
+
 // in-order upload of a small page-locked host buffer by a kernel (no runtime copy on the ctx stream)
 hipError_t launch_upload(hipStream_t st, void *dst, const void *src_pinned, size_t bytes);
 

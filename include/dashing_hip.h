@@ -271,6 +271,50 @@ int dsh_dist_rect_threshold(dsh_ctx *ctx, int estim, int result_type, int k, uin
                             uint64_t r_end, float threshold, uint64_t *row_ptr_out, uint32_t **col_out, float **val_out,
                             uint64_t *n_hits);
 
+/* ---- an explicit list of pairs ------------------------------------------------------------------
+ * Replaces result_cmp (src/dashing.h:568-592) called pair by pair: what a client does with the hits of
+ * dsh_dist_threshold*, the lists of dsh_knn or the edges of a graph it keeps when it wants THOSE pairs again -- under
+ * another measure, in the other orientation, with the set sizes -- without a second dense pass:
+ *   out[t * n_pairs + x] = float(result_cmp(lhs = sketch[lhs[x]], rhs = sketch[rhs[x]], result_types[t], 1/k)),
+ * 1/k being the float of dist_loop (src/sketch_and_cmp.h:797).  One read of the two register rows serves all n_types
+ * measures (n_types <= 9).  The pairs are computed in the DIRECT form -- the exact histogram of max(a, b), then the
+ * same estimator code as the dense path -- so:
+ *   Values.  For every pair and every measure the float32 is bit for bit the one dsh_dist_rows writes at
+ *     dsh_tri_index(n, i, j) when lhs = j > rhs = i, and the one dsh_dist_rect writes at [query = rhs][reference = lhs]
+ *     for any two slots.  (dsh_knn's values use the double 1/k of nndist_loop, :729: they are not these.)
+ *   Any pair is legal: lhs < rhs, lhs == rhs (the sketch with itself: what the formulas give, J = 1 for a non-empty
+ *     sketch), repeated pairs, any order.  Output x belongs to input x.
+ *   n_pairs == 0 and n_types == 0 succeed and write nothing.  DSH_EINVAL before anything is enqueued for a slot >= n (host
+ *     and CSR forms; the device form checks on the device and fails the call after it, `out` then being unspecified), a
+ *     result_type outside 0..8, n_types > 9, a row_ptr that decreases or a col out of range; DSH_ESTATE without sketches.
+ *   Out-of-range registers (a value above 64 - p + 1): if a sketch NAMED BY A PAIR holds one the call fails with the
+ *     dense path's code (DSH_EINVAL) and a message that names the sketch, `out` unspecified; sketches no pair names are
+ *     not judged.
+ *   The context's derived state is not touched: a pairs call between two dense calls changes neither's bytes, and
+ *     costs neither a layout.  The cardinalities this path keeps (all n sketches, computed by the first call after the
+ *     sketches or the estimator changed) are its own.
+ *   Synchronous, on the ctx stream; the device form waits for the device once, at its end.  The list is worked off in
+ *     chunks of "pairs_chunk" pairs (option, default 2^18; no result depends on it): scratch is 128 bytes (p <= 15;
+ *     256 above) per pair of one chunk, whatever n_pairs is.
+ *   Cost: 2 * 2^p bytes read per pair, against the dense path's fixed cost for all pairs.  Measured on one MI355X
+ *     (profiles/pairs1/bench_pairs.jsonl): 179 M pairs/s at 10 000 x p=14, 1.3 G pairs/s at 100 000 x p=10;
+ *     at 0.1 % of all pairs 41x and 77x faster than dsh_dist_rows_device of the full triangle.  Below about 5 % (p = 14)
+ *     or 8 % (p = 10) of all pairs, ask for the pairs; above, compute the triangle.
+ *   dsh_dist_pairs          lhs, rhs, out in host memory
+ *   dsh_dist_pairs_device   d_lhs, d_rhs (uint32 [n_pairs]) and d_out (float32 [n_types][n_pairs]) in DEVICE memory; the
+ *                           lists must be complete when the call is made (the ctx stream waits for no other stream)
+ *   dsh_dist_pairs_csr      the pairs of a CSR result as dsh_dist_threshold* / dsh_dist_rect_threshold write it: hit h of
+ *                           row r (row_ptr[r] <= h < row_ptr[r + 1]) is the pair (lhs = col[h], rhs = row_begin + r) --
+ *                           the orientation both dense paths compute.  n_hits = row_ptr[rows] - row_ptr[0];
+ *                           out[t * n_hits + (h - row_ptr[0])].  Under the measure that selected the hits this returns
+ *                           their `val`. */
+int dsh_dist_pairs(dsh_ctx *ctx, int estim, const int *result_types, uint32_t n_types, int k, const uint32_t *lhs,
+                   const uint32_t *rhs, uint64_t n_pairs, float *out);
+int dsh_dist_pairs_device(dsh_ctx *ctx, int estim, const int *result_types, uint32_t n_types, int k, const void *d_lhs,
+                          const void *d_rhs, uint64_t n_pairs, void *d_out);
+int dsh_dist_pairs_csr(dsh_ctx *ctx, int estim, const int *result_types, uint32_t n_types, int k, uint64_t row_begin,
+                       uint64_t rows, const uint64_t *row_ptr, const uint32_t *col, float *out);
+
 /* ---- multi-GPU shards of the full triangle ------------------------------------------------
  * Every rank holds all sketches (dsh_upload/attach) and computes one shard; no collective is
  * needed inside the compare.  Internally the plane matrix is laid out in (threshold, min value)
