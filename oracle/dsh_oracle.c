@@ -464,6 +464,8 @@ double dsho_jaccard_from(double ca, double cb, double us)
 /* dist_loop and partdist_loop pass ksinv as a FLOAT (src/sketch_and_cmp.h:797, src/dashing.h:664); nndist_loop
  * (--nearest-neighbors) keeps the DOUBLE 1./k (src/sketch_and_cmp.h:729).  dsho_knn raises this flag for its duration. */
 static int g_ksinv_double = 0;
+/* tests/knn_ref.py: a dense rectangle with the values dsho_knn reports (the oracle is not called concurrently) */
+void dsho_set_ksinv_double(int on) { g_ksinv_double = on ? 1 : 0; }
 
 /* result_cmp for JI / MASH_DIST / FULL_MASH_DIST, src/dashing.h:568-592; ksinv is the
  * float 1./k promoted to double (src/sketch_and_cmp.h:797). */

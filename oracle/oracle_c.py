@@ -91,6 +91,8 @@ def _bind(lib):
     lib.dsho_knn.restype = None
     lib.dsho_knn.argtypes = [_u8p, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_uint64,
                              C.c_uint64, C.c_uint64, C.c_uint32, np.ctypeslib.ndpointer(np.uint32, flags="C_CONTIGUOUS"), _f32p]
+    lib.dsho_set_ksinv_double.restype = None
+    lib.dsho_set_ksinv_double.argtypes = [C.c_int]
     lib.dsho_num_threads.restype = C.c_int
     return lib
 
@@ -206,11 +208,17 @@ def dist_rows(regs, row_begin, row_end, estim=ERTL_MLE, result_type=JI, k=31, li
     return out[:done]
 
 
-def dist_rect(qregs, rregs, estim=ERTL_MLE, result_type=JI, k=31):
+def dist_rect(qregs, rregs, estim=ERTL_MLE, result_type=JI, k=31, ksinv_double=False):
+    """ksinv_double: the double 1/k of --nearest-neighbors (what knn() reports) instead of dist's float 1/k"""
     q = np.ascontiguousarray(qregs, np.uint8)
     r = np.ascontiguousarray(rregs, np.uint8)
     out = np.zeros((q.shape[0], r.shape[0]), np.float32)
-    load().dsho_dist_rect(q, q.shape[0], r, r.shape[0], int(q.shape[1]).bit_length() - 1, estim, result_type, k, out)
+    lib = load()
+    lib.dsho_set_ksinv_double(int(ksinv_double))
+    try:
+        lib.dsho_dist_rect(q, q.shape[0], r, r.shape[0], int(q.shape[1]).bit_length() - 1, estim, result_type, k, out)
+    finally:
+        lib.dsho_set_ksinv_double(0)
     return out
 
 

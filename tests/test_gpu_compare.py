@@ -626,6 +626,10 @@ def test_adversarial_registers(ctx, oracle, p):
 def test_knn_vs_oracle(ctx, oracle, rt):
     """--nearest-neighbors: k best per sketch, similarity descending / distance ascending, ties by
     lower index (identical sketches and the empty sketch create exact ties)."""
+    # The index-exact comparison with the ORACLE holds on this seed only: of the 19 200 adjacent entries of the oracle's
+    # nn = 64 lists, 4 (JI), 7 (MASH_DIST) and 3 (SYMMETRIC_CONTAINMENT_INDEX; 1 of 1 500 at nn = 5) lie within twice the
+    # 1e-6 value contract of each other, where the device may order them either way.  tests/test_gpu_knn.py checks the
+    # selection without that luck: against the numpy model on the device's own values, and tolerantly against the oracle.
     n, p = 300, 10
     regs = synth.synthetic_sketches(n, p, seed=55)
     regs[7] = regs[8] = regs[9]
@@ -650,6 +654,9 @@ def test_knn_vs_oracle(ctx, oracle, rt):
 def test_knn_all_vs_all_paths_agree(ctx, oracle, rt):
     """All-vs-all kNN computes each pair once into an n x n matrix (both orientations -- the containment
     measures are asymmetric); the block-of-queries fallback must select exactly the same neighbours."""
+    # (index-exact against the oracle at nn = 7 only: at nn = 64 the oracle's lists of this collection hold 11 of 44 800
+    # adjacent entries (JI) and 56 (FULL_CONTAINMENT_DIST, 54 of 700 rows) within twice the 1e-6 contract -- see
+    # tests/test_gpu_knn.py, test_square_and_bands_against_the_oracle, for the comparison that does not depend on that)
     n, p = 700, 12
     regs = synth.related_sketches(n, p, seed=91)[0]
     ctx.set_sketches(regs)
@@ -685,6 +692,8 @@ def test_knn_bands_match_square_at_c3_size(ctx, rt):
 
 def test_knn_more_neighbours_than_the_band_path_takes(ctx, oracle):
     """nn > 1024 (the band path keeps a sketch's running list in LDS) falls back to query blocks"""
+    # (1 050 of 1 099 candidates index-exact against the oracle: it passes as long as no two of a row's values lie within
+    # the 1e-6 contract; tests/test_gpu_knn.py has nn = 1023 / 1024 / 1025 against the model on the device's own values)
     n, p = 1100, 10
     regs = synth.synthetic_sketches(n, p, seed=5)
     ctx.set_sketches(regs)
