@@ -166,10 +166,14 @@ def test_capacity(ctx):
     assert hits > 100
     dev = torch.device("cuda:0")
     GUARD, CAN_U, CAN_F = 64, 0xDEADBEEF, -12345.5
-    for cap in (hits, hits - 1, 0):
-        rp = torch.full((n + 1,), -1, dtype=torch.int64, device=dev)
-        col = torch.full((cap + GUARD,), CAN_U - (1 << 32), dtype=torch.int32, device=dev)  # (bit pattern 0xDEADBEEF)
-        val = torch.full((cap + GUARD,), CAN_F, dtype=torch.float32, device=dev)
+    for cap, mis in ((hits, 0), (hits - 1, 0), (0, 0), (hits, 1), (hits - 1, 2), (0, 3)):
+        # mis: row_ptr, col and val start that many items behind the tensor's (aligned) start, with canaries in front
+        rp = torch.full((mis + n + 1,), -1, dtype=torch.int64, device=dev)
+        col = torch.full((mis + cap + GUARD,), CAN_U - (1 << 32), dtype=torch.int32, device=dev)  # (bit pattern 0xDEADBEEF)
+        val = torch.full((mis + cap + GUARD,), CAN_F, dtype=torch.float32, device=dev)
+        rp_all, col_all, val_all = rp, col, val
+        rp, col, val = rp[mis:], col[mis:], val[mis:]
+        assert col.data_ptr() == col_all.data_ptr() + 4 * mis and rp.data_ptr() == rp_all.data_ptr() + 8 * mis
         torch.cuda.synchronize()
         if cap == hits:
             assert ctx.dist_threshold_device(rp.data_ptr(), col.data_ptr(), val.data_ptr(), cap, 0.03, estim=2, result_type=D.JI, k=31) == hits
@@ -183,6 +187,7 @@ def test_capacity(ctx):
         v = val.cpu().numpy()
         assert np.array_equal(c[:cap], full[1][:cap]) and np.array_equal(v[:cap].view(np.uint32), full[2][:cap].view(np.uint32))
         assert (c[cap:] == CAN_U).all() and (v[cap:] == np.float32(CAN_F)).all()
+        assert (rp_all[:mis] == -1).all() and (col_all[:mis] == CAN_U - (1 << 32)).all() and (val_all[:mis] == CAN_F).all()
         # counts only on the device: NULL col/val
         rp2 = torch.zeros((n + 1,), dtype=torch.int64, device=dev)
         assert ctx.dist_threshold_device(rp2.data_ptr(), 0, 0, 0, 0.03, estim=2, result_type=D.JI, k=31) == hits
