@@ -609,9 +609,8 @@ int dsh_sketch_fastx_batch_async(dsh_ctx *c, const uint8_t *raw, const uint64_t 
 int dsh_cardinalities(dsh_ctx *c, int estim, double *out)
 {
     if (!c || !out) return DSH_EINVAL;
-    int rc = bind(c);
+    int rc = enter(c);
     if (rc) return rc;
-    if (!c->have_sketches) return fail(c, DSH_ESTATE, "no sketches loaded");
     if (estim < 0 || estim > 2) return fail(c, DSH_EINVAL, "bad estimator %d", estim);
     if (c->card_estim != estim || c->card_from != 0) {
         // same per-sketch pass as prepare() (thresholds/exception lists come out identical)
@@ -627,50 +626,28 @@ int dsh_cardinalities(dsh_ctx *c, int estim, double *out)
 
 int dsh_dist_rows_device_async(dsh_ctx *c, int estim, int result_type, int k, uint64_t rb, uint64_t re, void *d_out)
 {
-    if (!c) return DSH_EINVAL;
-    int rc = bind(c);
+    int rc = enter(c);
     if (rc) return rc;
-    if (!c->have_sketches) return fail(c, DSH_ESTATE, "no sketches loaded");
     reset_prof(c);
     if (re > c->n) re = c->n;
     if (rb >= re || c->n < 2) return DSH_OK;
     if (!d_out) return DSH_EINVAL;
-    PairJob j;
-    j.estim = estim;
-    j.result_type = result_type;
-    j.k = k;
-    j.rect = 0;
-    j.row_begin = rb;
-    j.row_end = re;
-    j.col_begin = j.col_end = 0;
-    j.base_index = dsh_tri_span(c->n, 0, rb);
-    j.d_out = (float *)d_out;
-    return run_pairs(c, j);
+    return run_pairs(c, PairJob::triangle(estim, result_type, k, rb, re, dsh_tri_span(c->n, 0, rb), d_out));
 }
 
 int dsh_dist_rows_parts_device_async(dsh_ctx *c, int estim, int result_type, int k, uint64_t rb, uint64_t re, void *d_out,
                                      uint32_t nparts)
 {
     if (!c || nparts == 0) return DSH_EINVAL;
-    int rc = bind(c);
+    int rc = enter(c);
     if (rc) return rc;
-    if (!c->have_sketches) return fail(c, DSH_ESTATE, "no sketches loaded");
     reset_prof(c);
     c->parts_done = 0;
     if (re > c->n) re = c->n;
     if (rb >= re || c->n < 2) return DSH_OK;  // (no rows: no parts, no events -- dsh_collect_parts_async knows)
     if (!d_out) return DSH_EINVAL;
-    PairJob j;
-    j.estim = estim;
-    j.result_type = result_type;
-    j.k = k;
-    j.rect = 0;
+    PairJob j = PairJob::triangle(estim, result_type, k, rb, re, dsh_tri_span(c->n, 0, rb), d_out);
     j.nparts = nparts;
-    j.row_begin = rb;
-    j.row_end = re;
-    j.col_begin = j.col_end = 0;
-    j.base_index = dsh_tri_span(c->n, 0, rb);
-    j.d_out = (float *)d_out;
     return run_pairs(c, j);
 }
 
@@ -684,10 +661,8 @@ int dsh_dist_rows_device(dsh_ctx *c, int estim, int result_type, int k, uint64_t
 
 int dsh_dist_rows_async(dsh_ctx *c, int estim, int result_type, int k, uint64_t rb, uint64_t re, float *out)
 {
-    if (!c) return DSH_EINVAL;
-    int rc = bind(c);
+    int rc = enter(c);
     if (rc) return rc;
-    if (!c->have_sketches) return fail(c, DSH_ESTATE, "no sketches loaded");
     if (re > c->n) re = c->n;
     const uint64_t span = dsh_tri_span(c->n, rb, re);
     if (span == 0) return DSH_OK;
@@ -810,28 +785,15 @@ int dsh_wait_event(dsh_ctx *c, void *hip_event)
 
 int dsh_dist_rect(dsh_ctx *c, int estim, int result_type, int k, uint64_t qb, uint64_t qe, uint64_t rb, uint64_t re, float *out)
 {
-    if (!c) return DSH_EINVAL;
-    int rc = bind(c);
+    int rc = enter(c);
     if (rc) return rc;
-    if (!c->have_sketches) return fail(c, DSH_ESTATE, "no sketches loaded");
     if (qe > c->n || re > c->n) return fail(c, DSH_EINVAL, "slots out of range");
     reset_prof(c);
     if (qb >= qe || rb >= re) return DSH_OK;
     if (!out) return DSH_EINVAL;
     const uint64_t cnt = (qe - qb) * (re - rb);
     HIPCHK(c, c->outbuf.ensure(cnt * sizeof(float)));
-    PairJob j;
-    j.estim = estim;
-    j.result_type = result_type;
-    j.k = k;
-    j.rect = 1;
-    j.row_begin = qb;
-    j.row_end = qe;
-    j.col_begin = rb;
-    j.col_end = re;
-    j.base_index = 0;
-    j.d_out = (float *)c->outbuf.ptr;
-    rc = run_pairs(c, j);
+    rc = run_pairs(c, PairJob::rectangle(estim, result_type, k, qb, qe, rb, re, c->outbuf.ptr));
     if (rc) return rc;
     HIPCHK(c, hipMemcpyAsync(out, c->outbuf.ptr, cnt * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -897,25 +859,16 @@ int dsh_dist_shard_device(dsh_ctx *c, int estim, int result_type, int k, uint32_
                           uint32_t nshards, void *d_span)
 {
     if (!c || nshards == 0 || shard >= nshards) return DSH_EINVAL;
-    int rc = bind(c);
+    int rc = enter(c);
     if (rc) return rc;
-    if (!c->have_sketches) return fail(c, DSH_ESTATE, "no sketches loaded");
     reset_prof(c);
     if ((rc = prepare(c, estim, 1))) return rc;
     if (c->n < 2) return DSH_OK;
     std::vector<uint32_t> tb;
     shard_bounds(c, nshards, tb);
-    PairJob j;
-    j.estim = estim;
-    j.result_type = result_type;
-    j.k = k;
-    j.rect = 0;
+    const uint64_t sb = std::min<uint64_t>(c->n, (uint64_t)tb[shard] * kTile), se = std::min<uint64_t>(c->n, (uint64_t)tb[shard + 1] * kTile);
+    PairJob j = PairJob::triangle(estim, result_type, k, sb, se, dsh_tri_span(c->n, 0, sb), d_span);
     j.sorted_rows = 1;
-    j.row_begin = std::min<uint64_t>(c->n, (uint64_t)tb[shard] * kTile);
-    j.row_end = std::min<uint64_t>(c->n, (uint64_t)tb[shard + 1] * kTile);
-    j.col_begin = j.col_end = 0;
-    j.base_index = dsh_tri_span(c->n, 0, j.row_begin);
-    j.d_out = (float *)d_span;
     if (j.row_begin >= j.row_end) return DSH_OK;
     if (!d_span) return DSH_EINVAL;
     if ((rc = run_pairs(c, j))) return rc;

@@ -297,10 +297,22 @@ inline void reset_prof(dsh_ctx *c)
     c->ev_used = 0;
 }
 
-// one pass of the compare path over a set of pairs (engine.hip)
+// what every entry point that reads the resident sketches starts with (reset_prof stays with the entry point: where it
+// stands relative to the argument checks differs between them)
+inline int enter(dsh_ctx *c)
+{
+    if (!c) return DSH_EINVAL;
+    int rc = bind(c);
+    if (rc) return rc;
+    if (!c->have_sketches) return fail(c, DSH_ESTATE, "no sketches loaded");
+    return DSH_OK;
+}
+
+// one pass of the compare path over a set of pairs (engine.hip).  A job starts as one of the two named forms; the rarer
+// switches are then set by name where they apply.
 struct PairJob {
-    int estim, result_type, k;
-    int rect;
+    int estim = 0, result_type = 0, k = 0;
+    int rect = 0;
     int sorted_rows = 0;  // rows (and the output) are in sorted plane-column order (shards)
     int square = 0;       // full triangle, each value written at (i,j) and (j,i) of an n x n matrix
     uint32_t nparts = 0;  // > 0: triangle rows in (at most) this many parts of a key-ordered layout, an event per part
@@ -309,10 +321,31 @@ struct PairJob {
     float *d_out2 = nullptr;
     uint64_t knn_ld = 0, knn_rows = 0;
     int ksinv_double = 0; // 1./k as a double (nndist_loop, src/sketch_and_cmp.h:729) instead of the float of dist_loop (:797)
-    uint64_t row_begin, row_end, col_begin, col_end;
-    uint64_t base_index;
-    float *d_out;
+    uint64_t row_begin = 0, row_end = 0, col_begin = 0, col_end = 0;
+    uint64_t base_index = 0;
+    float *d_out = nullptr;
     std::vector<uint64_t> extra;  // (with nparts) further row segments {b0, e0, ...} behind row_end: a row set (plan.h)
+
+    // rows [rb, re) of the packed triangle, the value of pair (i, j) at tri(i, j) - base_index of `out`
+    static PairJob triangle(int estim, int result_type, int k, uint64_t rb, uint64_t re, uint64_t base_index, void *out)
+    {
+        PairJob j;
+        j.estim = estim, j.result_type = result_type, j.k = k;
+        j.row_begin = rb, j.row_end = re;
+        j.base_index = base_index;
+        j.d_out = (float *)out;
+        return j;
+    }
+    // rows [qb, qe) x columns [rb, re), row-major in `out`
+    static PairJob rectangle(int estim, int result_type, int k, uint64_t qb, uint64_t qe, uint64_t rb, uint64_t re, void *out)
+    {
+        PairJob j;
+        j.estim = estim, j.result_type = result_type, j.k = k;
+        j.rect = 1;
+        j.row_begin = qb, j.row_end = qe, j.col_begin = rb, j.col_end = re;
+        j.d_out = (float *)out;
+        return j;
+    }
 };
 
 // cardinalities + thresholds/lists + planes + position index for the current sketch matrix.  want_sorted < 0: whatever

@@ -240,64 +240,57 @@ int prepare(dsh_ctx *c, int estim, int want_sorted, bool card_only, uint64_t wan
     return DSH_OK;
 }
 
-int run_pairs(dsh_ctx *c, const PairJob &job)
+// ---- run_pairs(): its steps, in the order they run ----
+namespace {
+
+// the layout a job runs on
+struct JobLayout {
+    int want_sorted = 0;
+    uint64_t lrb = 0, lre = 0;  // the rows a key-ordered layout is made for
+    bool with_parts = false;    // the job's parts become final one by one (an event or a flag per part)
+    bool with_extra = false;    // further row segments behind the range (row sets, plan.h)
+};
+
+// what the steps of one call share
+struct PairRun {
+    plan::Tuning tu;
+    std::vector<uint64_t> item_off;  // first item of every band in the call's item list (+ the end)
+    plan::U4 *pinT = nullptr, *pinF = nullptr, *pinI = nullptr;  // page-locked staging: [tile kernel's list | k_finalize's list | items]
+    bool signal = false;      // the parts announce themselves from inside k_finalize (else: an event per part)
+    bool sig_upload = false;  // the signal block still has to travel (it goes with the first band's lists)
+    FinalizeLaunch fin{};     // the call-invariant arguments of k_finalize; the band and the segment fill in theirs
+    hipEvent_t e_call0 = nullptr;                             // (profiling, with parts) the call's start
+    std::vector<std::pair<size_t, hipEvent_t>> ev_part_t;     // (profiling) part -> a timing event behind its last segment
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> evp, evf;  // (profiling) per band: around the tile kernel, around k_finalize
+};
+
+// Triangle rows [rb,re): the plane matrix is laid out for exactly that range (wanted rows first, both
+// parts key-ordered), so every tile is homogeneous and the result lands at its final packed position --
+// whatever the range (a full triangle, one rank's rows, a row block of the CLI).  Tiny ranges and
+// rectangles keep the identity layout, which stays cached across calls; a call with parts (an event per part:
+// the pipelined exchange) always gets the key-ordered layout of its range, however short, so that its parts
+// are the ones dsh_range_parts reports to the other ranks.
+JobLayout choose_layout(const dsh_ctx *c, const PairJob &job)
 {
-    // Triangle rows [rb,re): the plane matrix is laid out for exactly that range (wanted rows first, both
-    // parts key-ordered), so every tile is homogeneous and the result lands at its final packed position --
-    // whatever the range (a full triangle, one rank's rows, a row block of the CLI).  Tiny ranges and
-    // rectangles keep the identity layout, which stays cached across calls; a call with parts (an event per part:
-    // the pipelined exchange) always gets the key-ordered layout of its range, however short, so that its parts
-    // are the ones dsh_range_parts reports to the other ranks.
+    JobLayout jl;
     const uint64_t jre = std::min<uint64_t>(job.row_end, c->n);
     const bool full_tri = !job.rect && job.row_begin == 0 && jre >= c->n;
-    const bool with_parts = job.nparts > 0 && !job.rect && !job.sorted_rows;
-    int want_sorted = 0;
-    uint64_t lrb = 0, lre = c->n;
-    if (job.sorted_rows) want_sorted = 1;
+    jl.with_parts = job.nparts > 0 && !job.rect && !job.sorted_rows;
+    jl.lre = c->n;
+    if (job.sorted_rows) jl.want_sorted = 1;
     else if (!job.rect && jre > job.row_begin &&
-             (with_parts || (c->sort_mode != 0 && (full_tri || jre - job.row_begin >= (uint64_t)c->range_sort_min_rows)))) {
-        want_sorted = 1;
-        lrb = job.row_begin;
-        lre = jre;
-    }
-    c->parts_done = 0;
-    c->part_ready_ms.clear();
-    c->part_floats.clear();
-    hipEvent_t e_call0 = nullptr;
-    std::vector<std::pair<size_t, hipEvent_t>> ev_part_t;  // (profiling) part -> a timing event behind its last segment
-    if (with_parts) {  // the signal block of the parts (kernels.h kSig*; used when the call turns out to signal, below)
-        HIPCHK(c, c->sig.ensure((size_t)kSigWords * sizeof(uint32_t)));
-        if (c->sig_gen == 0) {  // (first use: the flags must not hold garbage that passes for a generation)
-            HIPCHK(c, hipMemsetAsync(c->sig.ptr, 0, (size_t)kSigWords * sizeof(uint32_t), c->stream));  // (and the tile counters, which clear themselves from then on)
-            c->sig_gen = 1;
-        }
-    }
-    if (c->profiling && with_parts) {
-        e_call0 = next_event(c);
-        if (e_call0) (void)hipEventRecord(e_call0, c->stream);
-        // the call's start on the device's wall clock: signalled parts stamp their completion on the same
-        HIPCHK(c, launch_wall_stamp(c->stream, reinterpret_cast<unsigned long long *>((uint32_t *)c->sig.ptr + kSigT0)));
+             (jl.with_parts || (c->sort_mode != 0 && (full_tri || jre - job.row_begin >= (uint64_t)c->range_sort_min_rows)))) {
+        jl.want_sorted = 1;
+        jl.lrb = job.row_begin;
+        jl.lre = jre;
     }
     // extra segments (row sets, plan.h): only with a key-ordered layout of the range and parts (the exchange)
-    const bool with_extra = want_sorted && with_parts && !job.extra.empty() && lre > lrb;
-    if (!job.extra.empty() && !with_extra) return fail(c, DSH_EINVAL, "internal: extra row segments need a key-ordered range with parts");
-    int rc = prepare(c, job.estim, want_sorted, false, lrb, lre, with_parts ? job.nparts : 1, with_parts && job.rowsorted,
-                     with_extra ? &job.extra : nullptr);
-    if (rc) return rc;
-    if (job.result_type < 0 || job.result_type > 8)
-        return fail(c, DSH_EINVAL, "unsupported result_type %d", job.result_type);
-    if (job.k < 1) return fail(c, DSH_EINVAL, "bad k %d", job.k);
-    const auto t_l0 = std::chrono::steady_clock::now();
-    const plan::Layout &L = c->lay;
-    plan::PairPlan &pp = c->pp;
-    plan::PairQuery q;
-    q.rect = job.rect;
-    q.sorted_rows = job.sorted_rows;
-    q.want_parts = with_parts;
-    q.row_begin = job.row_begin;
-    q.row_end = job.row_end;
-    q.col_begin = job.col_begin;
-    q.col_end = job.col_end;
+    jl.with_extra = jl.want_sorted && jl.with_parts && !job.extra.empty() && jl.lre > jl.lrb;
+    return jl;
+}
+
+plan::Tuning tuning_of(const dsh_ctx *c)
+{
     plan::Tuning tu;
     tu.W = c->W;
     tu.kc = c->kc;
@@ -308,102 +301,320 @@ int run_pairs(dsh_ctx *c, const PairJob &job)
     tu.part_band_tiles = (uint32_t)c->part_band_tiles;
     tu.overflow_frag_max_permille = (uint32_t)c->overflow_frag_permille;
     tu.tail_bands = (uint32_t)c->tail_bands;
-    // Tiles, bands and segments of the whole job first; the work items and the two device lists are made, uploaded and
-    // launched BAND BY BAND: the host plans band b + 1 while the GPU runs band b (at 100 000 x p=10 the plan of 306 000
-    // tiles took the host 8 ms that nothing hid, round 4 / profiles/r4y).
-    if (!plan::build_tiles(L, q, tu, pp)) {
-        pp.T.clear();
-        return DSH_OK;
-    }
-    const std::vector<plan::U4> &T = pp.T, &I = pp.items;
-    c->last_bands = pp.bands.size();
-    std::vector<uint64_t> item_off(pp.bands.size() + 1, 0);
-    for (size_t bi = 0; bi < pp.bands.size(); ++bi) item_off[bi + 1] = item_off[bi] + plan::band_item_count(tu, pp, bi);
-    const uint64_t nitems_total = item_off.back();
+    return tu;
+}
+
+// room for the call's lists on the device and in page-locked staging, and for a band's C(v)
+int reserve_lists(dsh_ctx *c, PairRun &r)
+{
+    plan::PairPlan &pp = c->pp;
+    const std::vector<plan::U4> &T = pp.T;
+    r.item_off.assign(pp.bands.size() + 1, 0);
+    for (size_t bi = 0; bi < pp.bands.size(); ++bi) r.item_off[bi + 1] = r.item_off[bi] + plan::band_item_count(r.tu, pp, bi);
+    const uint64_t nitems_total = r.item_off.back();
     pp.items.reserve(nitems_total);
-    // tile and item lists travel through page-locked staging, so nothing below needs the host to wait
+    // tile and item lists travel through page-locked staging, so nothing in the band loop needs the host to wait
     if (c->lists_in_flight) {  // the previous call's upload (long done unless calls are issued back to back)
         HIPCHK(c, hipEventSynchronize(c->ev_lists));
         c->lists_in_flight = false;
     }
     static_assert(sizeof(plan::U4) == sizeof(uint4), "plan::U4 must have the layout of uint4");
     HIPCHK(c, c->pin_lists.ensure((2 * T.size() + std::max<uint64_t>(nitems_total, 1)) * sizeof(uint4)));
-    plan::U4 *pinT = (plan::U4 *)c->pin_lists.ptr, *pinF = pinT + T.size(), *pinI = pinF + T.size();
+    r.pinT = (plan::U4 *)c->pin_lists.ptr, r.pinF = r.pinT + T.size(), r.pinI = r.pinF + T.size();
     HIPCHK(c, c->tiles.ensure(2 * T.size() * sizeof(uint4)));  // [tile kernel's list | k_finalize's list]
     HIPCHK(c, c->items.ensure(std::max<uint64_t>(nitems_total, 1) * sizeof(uint4)));
     if (!c->ev_lists) HIPCHK(c, hipEventCreateWithFlags(&c->ev_lists, hipEventDisableTiming));
     HIPCHK(c, c->cum.ensure(std::max<uint64_t>(pp.per_tile_bytes * pp.max_band, 256)));
+    return DSH_OK;
+}
+
+// a signalling call's generation, and its signal block staged for the upload with the first band's lists
+int stage_signal_block(dsh_ctx *c, PairRun &r)
+{
+    ++c->sig_gen;
+    if (c->sig_gen == 0) c->sig_gen = 1;
+    // the parts' tile totals (host -> device through page-locked staging), their counters cleared
+    if (c->sig_in_flight) {
+        HIPCHK(c, hipEventSynchronize(c->ev_sig));
+        c->sig_in_flight = false;
+    }
+    // the words kSigPartCnt .. kSigStamp of the block lie one behind the other: the parts' counters (zero), their totals,
+    // the call's generation, the stamp switch -- uploaded with the first band's lists, in one launch (the tile counters
+    // clear themselves: k_finalize_signal)
+    static_assert(kSigPartTotal == kSigPartCnt + kSigMaxParts && kSigGen == kSigPartTotal + kSigMaxParts && kSigStamp == kSigGen + 1, "signal block layout");
+    HIPCHK(c, c->pin_sig.ensure((2 * kSigMaxParts + 2) * sizeof(uint32_t)));
+    uint32_t *blk = (uint32_t *)c->pin_sig.ptr, *tot = blk + kSigMaxParts;
+    for (uint32_t qd = 0; qd < kSigMaxParts; ++qd) blk[qd] = 0u;
+    for (uint32_t qd = 0; qd < kSigMaxParts; ++qd) tot[qd] = qd < c->pp.part_tiles.size() ? c->pp.part_tiles[qd] : 0u;
+    tot[kSigMaxParts] = c->sig_gen;                   // kSigGen
+    tot[kSigMaxParts + 1] = c->profiling ? 1u : 0u;   // kSigStamp
+    r.sig_upload = true;
+    return DSH_OK;
+}
+
+// what every k_finalize launch of the call is given alike (the buffers are in place: nothing below moves them)
+FinalizeLaunch finalize_invariants(const dsh_ctx *c, const PairJob &job, bool with_extra)
+{
+    const plan::Layout &L = c->lay;
+    FinalizeLaunch f{};
+    f.cum_bytes = c->cum_bytes;
+    FinalizeArgs &a = f.a;
+    a.cum = c->cum.ptr;  // the band's C(v); a tile's block is named by its descriptor
+    a.perm = L.sorted ? (const uint32_t *)c->perm.ptr : nullptr;
+    a.rowoff = L.rowsorted ? (const uint64_t *)c->rowoff.ptr : nullptr;
+    a.pbase = L.pbase;
+    a.p = c->p;
+    a.estim = job.estim;
+    a.result_type = job.result_type;
+    a.ksinv = job.ksinv_double ? 1. / (double)job.k : (double)(float)(1. / (double)job.k);
+    a.nS = (const uint32_t *)c->colS_n.ptr;
+    a.keyS = (const uint32_t *)c->colS_key.ptr;
+    a.cardS = (const double *)c->colS_card.ptr;
+    a.thS = (const uint8_t *)c->colS_th.ptr;
+    a.rl = (const uint32_t *)c->colS_rl.ptr;
+    a.E = c->rl_stride;
+    a.cidx_rec = (const uint32_t *)c->cidx_rec.ptr;
+    a.cidx_ent = (const uint32_t *)c->cidx_ent.ptr;
+    a.nbuckets = c->nbuckets;
+    a.ent_stride = c->ent_stride;
+    a.n = c->n;
+    a.ncols = L.ncols;
+    a.rect = job.rect;
+    a.sorted_out = job.sorted_rows;
+    a.square = job.square;
+    a.knn = job.knn;
+    a.out2 = job.d_out2;
+    a.knn_ld = job.knn_ld;
+    a.knn_rows = job.knn_rows;
+    a.stop = c->finalize_stop;
+    a.phase_cyc = c->finalize_timing ? (unsigned long long *)c->phase_cyc.ptr : nullptr;
+    a.row_begin = job.row_begin;
+    // (with extra segments every pair of a launched tile is this rank's: the runs of the layout lie in row order and
+    // whole 128-column blocks are wanted or not, plan.h)
+    a.row_end = with_extra ? c->n : job.row_end;
+    a.col_begin = job.col_begin;
+    a.col_end = job.col_end;
+    a.base_index = job.base_index;
+    a.out = job.d_out;
+    return f;
+}
+
+// this band's items and list entries: planned, staged, uploaded (the uploads read the staging when they run: it is
+// not touched again before ev_lists of this call has passed)
+int upload_band(dsh_ctx *c, PairRun &r, size_t bi)
+{
+    plan::PairPlan &pp = c->pp;
+    const auto &bd = pp.bands[bi];
+    const uint32_t nt = (uint32_t)(bd.second - bd.first);
+    const size_t nT = pp.T.size();
+    const auto t_b0 = std::chrono::steady_clock::now();
+    plan::build_band_items(r.tu, pp, bi);
+    if (pp.band_items[bi].first != r.item_off[bi] || pp.band_items[bi].second != r.item_off[bi + 1])
+        return fail(c, DSH_EIO, "internal: band %zu has %zu items, %llu were planned for", bi,
+                    pp.band_items[bi].second - pp.band_items[bi].first, (unsigned long long)(r.item_off[bi + 1] - r.item_off[bi]));
+    plan::emit_band_lists(c->lay, pp, bi, r.pinT, r.pinF);
+    const uint32_t ni = (uint32_t)(r.item_off[bi + 1] - r.item_off[bi]);
+    if (ni) std::memcpy(r.pinI + r.item_off[bi], pp.items.data() + r.item_off[bi], (size_t)ni * sizeof(uint4));
+    c->host_lists_us += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_b0).count();
+    UploadSegs up;
+    uint32_t nseg = 0;
+    if (r.sig_upload) up.add(nseg, (uint32_t *)c->sig.ptr + kSigPartCnt, c->pin_sig.ptr, (2 * kSigMaxParts + 2) * sizeof(uint32_t));
+    up.add(nseg, (uint4 *)c->tiles.ptr + bd.first, r.pinT + bd.first, (size_t)nt * sizeof(uint4));
+    up.add(nseg, (uint4 *)c->tiles.ptr + nT + bd.first, r.pinF + bd.first, (size_t)nt * sizeof(uint4));
+    up.add(nseg, (uint4 *)c->items.ptr + r.item_off[bi], r.pinI + r.item_off[bi], (size_t)ni * sizeof(uint4));
+    HIPCHK(c, launch_upload_segs(c->stream, up, nseg));
+    if (r.sig_upload) {
+        if (!c->ev_sig) HIPCHK(c, hipEventCreateWithFlags(&c->ev_sig, hipEventDisableTiming));
+        HIPCHK(c, hipEventRecord(c->ev_sig, c->stream));
+        c->sig_in_flight = true;
+        r.sig_upload = false;
+    }
+    HIPCHK(c, hipEventRecord(c->ev_lists, c->stream));
+    c->lists_in_flight = true;
+    return DSH_OK;
+}
+
+int launch_tile_kernel(dsh_ctx *c, const PairRun &r, size_t bi, uint64_t nslots)
+{
+    const plan::Layout &L = c->lay;
+    const plan::PairPlan &pp = c->pp;
+    const uint4 *dt = (const uint4 *)c->tiles.ptr + pp.bands[bi].first;
+    const uint4 *di = (const uint4 *)c->items.ptr + r.item_off[bi];
+    const uint32_t ni = (uint32_t)(r.item_off[bi + 1] - r.item_off[bi]);
+    if (c->pair_mfma)
+        HIPCHK(c, launch_pair_counts_mfma(c->stream, c->kc, c->cum_bytes, (const uint32_t *)c->planes.ptr,
+                                          L.Npad, c->Kpad, c->W, L.P, dt, di, ni, c->cum.ptr, nslots));
+    else if (use_lockstep(c))
+        HIPCHK(c, launch_pair_counts_lockstep(c->stream, c->kc, c->cum_bytes, (const uint32_t *)c->planes.ptr,
+                                              L.Npad, c->Kpad, c->W, L.P, dt, di, ni, bi < pp.band_frags.size() ? pp.band_frags[bi] : 0u,
+                                              c->cum.ptr, nslots));
+    else
+        HIPCHK(c, launch_pair_counts(c->stream, c->kc, c->cum_bytes, (const uint32_t *)c->planes.ptr,
+                                     L.Npad, c->Kpad, c->W, L.P, dt, di, ni, c->cum.ptr, nslots));
+    return DSH_OK;
+}
+
+// k_finalize over one band, and the marks of the parts it completes
+int finalize_band(dsh_ctx *c, PairRun &r, size_t bi)
+{
+    const plan::PairPlan &pp = c->pp;
+    const auto &bd = pp.bands[bi];
+    // signal mode: ONE launch over the band's tiles; the parts announce themselves (k_finalize_signal)
+    std::vector<plan::Seg> one_seg;
+    if (r.signal) {
+        plan::Seg all{bd.first, bd.second, -1, 1};
+        for (const plan::Seg &sg : pp.segs[bi]) all.hist_bins = std::max(all.hist_bins, sg.hist_bins);
+        one_seg.push_back(all);
+    }
+    // (without flags -- finalize_signal = 0, or a device without stream wait-value -- one launch and one event per part)
+    for (const plan::Seg &sg : r.signal ? one_seg : pp.segs[bi]) {
+        hipStream_t fst = c->stream;
+        FinalizeLaunch &f = r.fin;
+        f.a.hist_bins = sg.hist_bins;
+        f.a.tiles = (const uint4 *)c->tiles.ptr + pp.T.size() + sg.b;
+        f.nslots = (uint64_t)(sg.e - sg.b) * kTile * kTile;
+        f.a.sig = r.signal ? (uint32_t *)c->sig.ptr : nullptr;
+        if (c->aux_join_pending) {  // (the position index is built on the second stream)
+            HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_aux_join, 0));
+            c->aux_join_pending = false;
+        }
+        HIPCHK(c, launch_finalize(fst, f));
+        if (sg.part >= 0) {  // this segment completes a part: its span of the matrix is final
+            const size_t qp = (size_t)sg.part;
+            while (c->ev_part.size() <= qp) {
+                hipEvent_t e = nullptr;
+                HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+                c->ev_part.push_back(e);
+            }
+            HIPCHK(c, hipEventRecord(c->ev_part[qp], fst));
+            c->parts_done = (uint32_t)qp + 1;
+            if (r.e_call0) {
+                hipEvent_t te = next_event(c);
+                if (te) {
+                    (void)hipEventRecord(te, fst);
+                    r.ev_part_t.emplace_back(qp, te);
+                }
+            }
+        }
+    }
+    return DSH_OK;
+}
+
+// (profiling) waits for the call and reads its timing events back
+int read_profile(dsh_ctx *c, const PairRun &r)
+{
+    const plan::Layout &L = c->lay;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (auto &e : r.evp) {
+        float ms = 0;
+        (void)hipEventElapsedTime(&ms, e.first, e.second);
+        c->pair_ms += ms;
+        if (c->Kpad) c->pair_launches++;
+    }
+    for (auto &e : r.evf) {
+        float ms = 0;
+        (void)hipEventElapsedTime(&ms, e.first, e.second);
+        c->fin_ms += ms;
+    }
+    // when every part of the call was final (from the start of the call, prepare included) and how many floats of the
+    // rank's buffer it holds: what a model of the pipelined exchange needs (dsh_last_part_info)
+    auto fill_part_floats = [&] {  // how many floats of the rank's buffer every part holds
+        for (size_t i = 0; i < c->part_floats.size(); ++i) {
+            if (L.rowsorted && i + 1 < L.part_w.size()) c->part_floats[i] = L.rowoff_w[L.part_w[i + 1]] - L.rowoff_w[L.part_w[i]];
+            else if (!L.rowsorted && L.extra.empty() && i + 1 < L.parts.size()) c->part_floats[i] = plan::tri_span(c->n, L.parts[i], L.parts[i + 1]);
+            else if (!L.rowsorted) c->part_floats[i] = plan::rowset_span(c->n, L.rb, L.re, L.extra);
+        }
+    };
+    if (r.signal && r.e_call0 && c->wall_clock_khz > 0) {
+        std::vector<unsigned long long> st(kSigMaxParts + 1);
+        HIPCHK(c, hipMemcpy(st.data(), (uint32_t *)c->sig.ptr + kSigPartTime, kSigMaxParts * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+        HIPCHK(c, hipMemcpy(&st[kSigMaxParts], (uint32_t *)c->sig.ptr + kSigT0, sizeof(unsigned long long), hipMemcpyDeviceToHost));
+        c->part_ready_ms.assign(c->parts_done, 0.0);
+        c->part_floats.assign(c->parts_done, 0);
+        for (size_t i = 0; i < c->part_ready_ms.size(); ++i)
+            c->part_ready_ms[i] = (double)(long long)(st[i] - st[kSigMaxParts]) / (double)c->wall_clock_khz;
+        fill_part_floats();
+    } else if (r.e_call0 && !r.ev_part_t.empty()) {
+        c->part_ready_ms.assign(c->parts_done, 0.0);
+        c->part_floats.assign(c->parts_done, 0);
+        for (auto &pe : r.ev_part_t) {
+            float ms = 0;
+            (void)hipEventElapsedTime(&ms, r.e_call0, pe.second);
+            if (pe.first < c->part_ready_ms.size()) c->part_ready_ms[pe.first] = ms;
+        }
+        fill_part_floats();
+    }
+    return DSH_OK;
+}
+
+}  // namespace
+
+int run_pairs(dsh_ctx *c, const PairJob &job)
+{
+    PairRun r;
+    const JobLayout jl = choose_layout(c, job);
+    c->parts_done = 0;
+    c->part_ready_ms.clear();
+    c->part_floats.clear();
+    if (jl.with_parts) {  // the signal block of the parts (kernels.h kSig*; used when the call turns out to signal, below)
+        HIPCHK(c, c->sig.ensure((size_t)kSigWords * sizeof(uint32_t)));
+        if (c->sig_gen == 0) {  // (first use: the flags must not hold garbage that passes for a generation)
+            HIPCHK(c, hipMemsetAsync(c->sig.ptr, 0, (size_t)kSigWords * sizeof(uint32_t), c->stream));  // (and the tile counters, which clear themselves from then on)
+            c->sig_gen = 1;
+        }
+    }
+    if (c->profiling && jl.with_parts) {
+        r.e_call0 = next_event(c);
+        if (r.e_call0) (void)hipEventRecord(r.e_call0, c->stream);
+        // the call's start on the device's wall clock: signalled parts stamp their completion on the same
+        HIPCHK(c, launch_wall_stamp(c->stream, reinterpret_cast<unsigned long long *>((uint32_t *)c->sig.ptr + kSigT0)));
+    }
+    if (!job.extra.empty() && !jl.with_extra) return fail(c, DSH_EINVAL, "internal: extra row segments need a key-ordered range with parts");
+    int rc = prepare(c, job.estim, jl.want_sorted, false, jl.lrb, jl.lre, jl.with_parts ? job.nparts : 1, jl.with_parts && job.rowsorted,
+                     jl.with_extra ? &job.extra : nullptr);
+    if (rc) return rc;
+    if (job.result_type < 0 || job.result_type > 8)
+        return fail(c, DSH_EINVAL, "unsupported result_type %d", job.result_type);
+    if (job.k < 1) return fail(c, DSH_EINVAL, "bad k %d", job.k);
+    const auto t_l0 = std::chrono::steady_clock::now();
+    plan::PairPlan &pp = c->pp;
+    plan::PairQuery q;
+    q.rect = job.rect;
+    q.sorted_rows = job.sorted_rows;
+    q.want_parts = jl.with_parts;
+    q.row_begin = job.row_begin;
+    q.row_end = job.row_end;
+    q.col_begin = job.col_begin;
+    q.col_end = job.col_end;
+    r.tu = tuning_of(c);
+    // Tiles, bands and segments of the whole job first; the work items and the two device lists are made, uploaded and
+    // launched BAND BY BAND: the host plans band b + 1 while the GPU runs band b (at 100 000 x p=10 the plan of 306 000
+    // tiles took the host 8 ms that nothing hid, round 4 / profiles/r4y).
+    if (!plan::build_tiles(c->lay, q, r.tu, pp)) {
+        pp.T.clear();
+        return DSH_OK;
+    }
+    c->last_bands = pp.bands.size();
+    if ((rc = reserve_lists(c, r))) return rc;
     c->host_lists_us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_l0).count();  // (until the first band can be planned)
 
     // Part signalling (kernels.h, k_finalize_signal): with parts, ONE k_finalize launch per band; the parts' flags are
     // written from inside it and the copy stream waits for them with hipStreamWaitValue32 (exchange.hip).  Not with the
     // stamped / general instances (profiling aids, rectangles) and not where the device lacks stream wait-value.
-    bool signal = false, sig_upload = false;
-    if (with_parts && pp.nparts >= 1 && pp.nparts <= kSigMaxParts && !c->finalize_timing && !c->finalize_stop && c->finalize_signal != 0) {
-        signal = device_can_wait_value(c);
-        if (!signal && c->finalize_signal == 1) return fail(c, DSH_ENODEV, "option finalize_signal = 1, but the device does not support hipStreamWaitValue32");
+    if (jl.with_parts && pp.nparts >= 1 && pp.nparts <= kSigMaxParts && !c->finalize_timing && !c->finalize_stop && c->finalize_signal != 0) {
+        r.signal = device_can_wait_value(c);
+        if (!r.signal && c->finalize_signal == 1) return fail(c, DSH_ENODEV, "option finalize_signal = 1, but the device does not support hipStreamWaitValue32");
     }
-    c->parts_signalled = signal;
-    if (signal) {
-        ++c->sig_gen;
-        if (c->sig_gen == 0) c->sig_gen = 1;
-        // the parts' tile totals (host -> device through page-locked staging), their counters cleared
-        if (c->sig_in_flight) {
-            HIPCHK(c, hipEventSynchronize(c->ev_sig));
-            c->sig_in_flight = false;
-        }
-        // the words kSigPartCnt .. kSigStamp of the block lie one behind the other: the parts' counters (zero), their totals,
-        // the call's generation, the stamp switch -- uploaded with the first band's lists, in one launch (the tile counters
-        // clear themselves: k_finalize_signal)
-        static_assert(kSigPartTotal == kSigPartCnt + kSigMaxParts && kSigGen == kSigPartTotal + kSigMaxParts && kSigStamp == kSigGen + 1, "signal block layout");
-        HIPCHK(c, c->pin_sig.ensure((2 * kSigMaxParts + 2) * sizeof(uint32_t)));
-        uint32_t *blk = (uint32_t *)c->pin_sig.ptr, *tot = blk + kSigMaxParts;
-        for (uint32_t qd = 0; qd < kSigMaxParts; ++qd) blk[qd] = 0u;
-        for (uint32_t qd = 0; qd < kSigMaxParts; ++qd) tot[qd] = qd < pp.part_tiles.size() ? pp.part_tiles[qd] : 0u;
-        tot[kSigMaxParts] = c->sig_gen;                   // kSigGen
-        tot[kSigMaxParts + 1] = c->profiling ? 1u : 0u;   // kSigStamp
-        sig_upload = true;
-    }
-    const float ksinv_f = (float)(1. / (double)job.k);
+    c->parts_signalled = r.signal;
+    if (r.signal && (rc = stage_signal_block(c, r))) return rc;
     if (c->finalize_timing) {
         HIPCHK(c, c->phase_cyc.ensure(16 * sizeof(unsigned long long)));
         HIPCHK(c, hipMemsetAsync(c->phase_cyc.ptr, 0, 16 * sizeof(unsigned long long), c->stream));
     }
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> evp, evf;
+    r.fin = finalize_invariants(c, job, jl.with_extra);
     for (size_t bi = 0; bi < pp.bands.size(); ++bi) {
-        const auto &bd = pp.bands[bi];
-        const uint32_t nt = (uint32_t)(bd.second - bd.first);
-        const uint64_t nslots = (uint64_t)nt * kTile * kTile;
-        // this band's items and list entries: planned, staged, uploaded (the uploads read the staging when they run: it is
-        // not touched again before ev_lists of this call has passed)
-        const auto t_b0 = std::chrono::steady_clock::now();
-        plan::build_band_items(tu, pp, bi);
-        if (pp.band_items[bi].first != item_off[bi] || pp.band_items[bi].second != item_off[bi + 1])
-            return fail(c, DSH_EIO, "internal: band %zu has %zu items, %llu were planned for", bi,
-                        pp.band_items[bi].second - pp.band_items[bi].first, (unsigned long long)(item_off[bi + 1] - item_off[bi]));
-        plan::emit_band_lists(L, pp, bi, pinT, pinF);
-        const uint32_t ni = (uint32_t)(item_off[bi + 1] - item_off[bi]);
-        if (ni) std::memcpy(pinI + item_off[bi], I.data() + item_off[bi], (size_t)ni * sizeof(uint4));
-        c->host_lists_us += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_b0).count();
-        {
-            UploadSegs up;
-            uint32_t nseg = 0;
-            if (sig_upload) up.add(nseg, (uint32_t *)c->sig.ptr + kSigPartCnt, c->pin_sig.ptr, (2 * kSigMaxParts + 2) * sizeof(uint32_t));
-            up.add(nseg, (uint4 *)c->tiles.ptr + bd.first, pinT + bd.first, (size_t)nt * sizeof(uint4));
-            up.add(nseg, (uint4 *)c->tiles.ptr + T.size() + bd.first, pinF + bd.first, (size_t)nt * sizeof(uint4));
-            up.add(nseg, (uint4 *)c->items.ptr + item_off[bi], pinI + item_off[bi], (size_t)ni * sizeof(uint4));
-            HIPCHK(c, launch_upload_segs(c->stream, up, nseg));
-            if (sig_upload) {
-                if (!c->ev_sig) HIPCHK(c, hipEventCreateWithFlags(&c->ev_sig, hipEventDisableTiming));
-                HIPCHK(c, hipEventRecord(c->ev_sig, c->stream));
-                c->sig_in_flight = true;
-                sig_upload = false;
-            }
-        }
-        HIPCHK(c, hipEventRecord(c->ev_lists, c->stream));
-        c->lists_in_flight = true;
-        const uint4 *dt = (const uint4 *)c->tiles.ptr + bd.first;
-        const uint4 *di = (const uint4 *)c->items.ptr + item_off[bi];
+        const uint64_t nslots = (uint64_t)(pp.bands[bi].second - pp.bands[bi].first) * kTile * kTile;
+        if ((rc = upload_band(c, r, bi))) return rc;
         hipEvent_t a = nullptr, b = nullptr, d = nullptr;
         if (c->profiling) {
             a = next_event(c);
@@ -411,149 +622,23 @@ int run_pairs(dsh_ctx *c, const PairJob &job)
             d = next_event(c);
             if (a) (void)hipEventRecord(a, c->stream);
         }
-        if (c->pair_mfma)
-            HIPCHK(c, launch_pair_counts_mfma(c->stream, c->kc, c->cum_bytes, (const uint32_t *)c->planes.ptr,
-                                              L.Npad, c->Kpad, c->W, L.P, dt, di, ni, c->cum.ptr, nslots));
-        else if (use_lockstep(c))
-            HIPCHK(c, launch_pair_counts_lockstep(c->stream, c->kc, c->cum_bytes, (const uint32_t *)c->planes.ptr,
-                                                  L.Npad, c->Kpad, c->W, L.P, dt, di, ni, bi < pp.band_frags.size() ? pp.band_frags[bi] : 0u,
-                                                  c->cum.ptr, nslots));
-        else
-            HIPCHK(c, launch_pair_counts(c->stream, c->kc, c->cum_bytes, (const uint32_t *)c->planes.ptr,
-                                         L.Npad, c->Kpad, c->W, L.P, dt, di, ni, c->cum.ptr, nslots));
+        if ((rc = launch_tile_kernel(c, r, bi, nslots))) return rc;
         if (b) (void)hipEventRecord(b, c->stream);
         if (bi == 0) {  // (the destination of an exchange may post its receives behind its first tile kernel, exchange.hip)
             if (!c->ev_first_tiles) HIPCHK(c, hipEventCreateWithFlags(&c->ev_first_tiles, hipEventDisableTiming));
             HIPCHK(c, hipEventRecord(c->ev_first_tiles, c->stream));
         }
-        // signal mode: ONE launch over the band's tiles; the parts announce themselves (k_finalize_signal)
-        std::vector<plan::Seg> one_seg;
-        if (signal) {
-            plan::Seg all{bd.first, bd.second, -1, 1};
-            for (const plan::Seg &sg : pp.segs[bi]) all.hist_bins = std::max(all.hist_bins, sg.hist_bins);
-            one_seg.push_back(all);
-        }
-        // (without flags -- finalize_signal = 0, or a device without stream wait-value -- one launch and one event per part)
-        for (const plan::Seg &sg : signal ? one_seg : pp.segs[bi]) {
-            hipStream_t fst = c->stream;
-            FinalizeLaunch f;
-            f.cum = c->cum.ptr;  // the band's C(v); a tile's block is named by its descriptor
-            f.cum_bytes = c->cum_bytes;
-            f.cum_stride = nslots;
-            f.hist_bins = sg.hist_bins;
-            f.nS = (const uint32_t *)c->colS_n.ptr;
-            f.keyS = (const uint32_t *)c->colS_key.ptr;
-            f.cardS = (const double *)c->colS_card.ptr;
-            f.thS = (const uint8_t *)c->colS_th.ptr;
-            f.rl = (const uint32_t *)c->colS_rl.ptr;
-            f.E = c->rl_stride;
-            f.nslots = (uint64_t)(sg.e - sg.b) * kTile * kTile;
-            f.tiles = (const uint4 *)c->tiles.ptr + T.size() + sg.b;
-            f.perm = L.sorted ? (const uint32_t *)c->perm.ptr : nullptr;
-            f.rowoff = L.rowsorted ? (const uint64_t *)c->rowoff.ptr : nullptr;
-            f.pbase = L.pbase;
-            f.cidx_rec = (const uint32_t *)c->cidx_rec.ptr;
-            f.cidx_ent = (const uint32_t *)c->cidx_ent.ptr;
-            f.nbuckets = c->nbuckets;
-            f.ent_stride = c->ent_stride;
-            f.p = c->p;
-            f.estim = job.estim;
-            f.result_type = job.result_type;
-            f.ksinv = job.ksinv_double ? 1. / (double)job.k : (double)ksinv_f;
-            f.n = c->n;
-            f.ncols = L.ncols;
-            f.stop = c->finalize_stop;
-            f.phase_cyc = c->finalize_timing ? (unsigned long long *)c->phase_cyc.ptr : nullptr;
-            f.rect = job.rect;
-            f.sorted_out = job.sorted_rows;
-            f.square = job.square;
-            f.knn = job.knn;
-            f.out2 = job.d_out2;
-            f.knn_ld = job.knn_ld;
-            f.knn_rows = job.knn_rows;
-            f.row_begin = job.row_begin;
-            // (with extra segments every pair of a launched tile is this rank's: the runs of the layout lie in row order and
-            // whole 128-column blocks are wanted or not, plan.h)
-            f.row_end = with_extra ? c->n : job.row_end;
-            f.col_begin = job.col_begin;
-            f.col_end = job.col_end;
-            f.base_index = job.base_index;
-            f.out = job.d_out;
-            if (signal) f.sig = (uint32_t *)c->sig.ptr;
-            if (c->aux_join_pending) {  // (the position index is built on the second stream)
-                HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_aux_join, 0));
-                c->aux_join_pending = false;
-            }
-            HIPCHK(c, launch_finalize(fst, f));
-            if (sg.part >= 0) {  // this segment completes a part: its span of the matrix is final
-                const size_t qp = (size_t)sg.part;
-                while (c->ev_part.size() <= qp) {
-                    hipEvent_t e = nullptr;
-                    HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-                    c->ev_part.push_back(e);
-                }
-                HIPCHK(c, hipEventRecord(c->ev_part[qp], fst));
-                c->parts_done = (uint32_t)qp + 1;
-                if (e_call0) {
-                    hipEvent_t te = next_event(c);
-                    if (te) {
-                        (void)hipEventRecord(te, fst);
-                        ev_part_t.emplace_back(qp, te);
-                    }
-                }
-            }
-        }
+        r.fin.a.nslots = nslots;  // (the band's stride: the distance between two planes of its C(v))
+        if ((rc = finalize_band(c, r, bi))) return rc;
         if (d) (void)hipEventRecord(d, c->stream);
         if (a && b && d) {
-            evp.emplace_back(a, b);
-            evf.emplace_back(b, d);
+            r.evp.emplace_back(a, b);
+            r.evf.emplace_back(b, d);
         }
     }
-    if (signal) c->parts_done = pp.nparts;  // (every part's flag will be written by the launches above)
+    if (r.signal) c->parts_done = pp.nparts;  // (every part's flag will be written by the launches above)
     // everything is enqueued; the blocking entry points synchronise, the *_async ones return here
-    if (c->profiling) {
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        for (auto &e : evp) {
-            float ms = 0;
-            (void)hipEventElapsedTime(&ms, e.first, e.second);
-            c->pair_ms += ms;
-            if (c->Kpad) c->pair_launches++;
-        }
-        for (auto &e : evf) {
-            float ms = 0;
-            (void)hipEventElapsedTime(&ms, e.first, e.second);
-            c->fin_ms += ms;
-        }
-        // when every part of the call was final (from the start of the call, prepare included) and how many floats of the
-        // rank's buffer it holds: what a model of the pipelined exchange needs (dsh_last_part_info)
-        auto fill_part_floats = [&] {  // how many floats of the rank's buffer every part holds
-            for (size_t i = 0; i < c->part_floats.size(); ++i) {
-                if (L.rowsorted && i + 1 < L.part_w.size()) c->part_floats[i] = L.rowoff_w[L.part_w[i + 1]] - L.rowoff_w[L.part_w[i]];
-                else if (!L.rowsorted && L.extra.empty() && i + 1 < L.parts.size()) c->part_floats[i] = plan::tri_span(c->n, L.parts[i], L.parts[i + 1]);
-                else if (!L.rowsorted) c->part_floats[i] = plan::rowset_span(c->n, L.rb, L.re, L.extra);
-            }
-        };
-        if (signal && e_call0 && c->wall_clock_khz > 0) {
-            std::vector<unsigned long long> st(kSigMaxParts + 1);
-            HIPCHK(c, hipMemcpy(st.data(), (uint32_t *)c->sig.ptr + kSigPartTime, kSigMaxParts * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-            HIPCHK(c, hipMemcpy(&st[kSigMaxParts], (uint32_t *)c->sig.ptr + kSigT0, sizeof(unsigned long long), hipMemcpyDeviceToHost));
-            c->part_ready_ms.assign(c->parts_done, 0.0);
-            c->part_floats.assign(c->parts_done, 0);
-            for (size_t i = 0; i < c->part_ready_ms.size(); ++i)
-                c->part_ready_ms[i] = (double)(long long)(st[i] - st[kSigMaxParts]) / (double)c->wall_clock_khz;
-            fill_part_floats();
-        } else if (e_call0 && !ev_part_t.empty()) {
-            c->part_ready_ms.assign(c->parts_done, 0.0);
-            c->part_floats.assign(c->parts_done, 0);
-            for (auto &pe : ev_part_t) {
-                float ms = 0;
-                (void)hipEventElapsedTime(&ms, e_call0, pe.second);
-                if (pe.first < c->part_ready_ms.size()) c->part_ready_ms[pe.first] = ms;
-            }
-            fill_part_floats();
-        }
-    }
-    return DSH_OK;
+    return c->profiling ? read_profile(c, r) : DSH_OK;
 }
 
 }  // namespace dsh

@@ -517,9 +517,8 @@ int dsh_exchange_rows_device_async(dsh_ctx *c, int estim, int result_type, int k
                                    int dst, void *d_local)
 {
     if (!c || !rowsets || nparts == 0 || rank < 0) return DSH_EINVAL;
-    int rc = bind(c);
+    int rc = enter(c);
     if (rc) return rc;
-    if (!c->have_sketches) return fail(c, DSH_ESTATE, "no sketches loaded");
     plan::RowSets rs;
     if ((rc = parse_table(c, c->n, rowsets, dst, rs))) return rc;
     if ((uint32_t)rank >= rs.world) return fail(c, DSH_EINVAL, "bad rank %d (world %u)", rank, rs.world);
@@ -553,19 +552,10 @@ int dsh_exchange_rows_device_async(dsh_ctx *c, int estim, int result_type, int k
     }
     if (!d_local) return DSH_EINVAL;
     c->pass_from_zero = from_zero;
-    PairJob j;
-    j.estim = estim;
-    j.result_type = result_type;
-    j.k = k;
-    j.rect = 0;
+    PairJob j = PairJob::triangle(estim, result_type, k, m.rb, m.re, dsh_tri_span(c->n, 0, m.rb), d_local);
     j.nparts = rank == dst ? 1 : m.kreq;
     j.rowsorted = m.rowsorted ? 1 : 0;
-    j.row_begin = m.rb;
-    j.row_end = m.re;
     j.extra = m.extra;
-    j.col_begin = j.col_end = 0;
-    j.base_index = dsh_tri_span(c->n, 0, m.rb);
-    j.d_out = (float *)d_local;
     rc = run_pairs(c, j);
     c->pass_from_zero = false;
     return rc;
@@ -785,9 +775,8 @@ int dsh_exchange_place_device(dsh_ctx *c, const uint64_t *rowsets, int src, uint
                               void *d_final)
 {
     if (!c || !rowsets || nparts == 0 || src < 0 || !d_final) return DSH_EINVAL;
-    int rc = bind(c);
+    int rc = enter(c);
     if (rc) return rc;
-    if (!c->have_sketches) return fail(c, DSH_ESTATE, "no sketches loaded");
     const uint64_t n = c->n;
     plan::RowSets rs;
     if ((rc = parse_table(c, n, rowsets, dst, rs))) return rc;
@@ -971,10 +960,8 @@ int dsh_allgather_device(dsh_ctx *c, const void *d_send, uint64_t bytes_per_rank
 
 int dsh_dist_collect(dsh_ctx *c, int estim, int result_type, int k, const uint64_t *bounds, int dst, float *out)
 {
-    if (!c) return DSH_EINVAL;
-    int rc = bind(c);
+    int rc = enter(c);
     if (rc) return rc;
-    if (!c->have_sketches) return fail(c, DSH_ESTATE, "no sketches loaded");
     const int world = c->comm ? c->comm_world : 1, rank = c->comm ? c->comm_rank : 0;
     const uint64_t n = c->n, total = dsh_tri_span(n, 0, n);
     if (!bounds) {

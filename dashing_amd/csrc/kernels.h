@@ -52,38 +52,68 @@ hipError_t launch_pair_counts_mfma(hipStream_t st, int kc, int cum_bytes, const 
                                    const uint4 *tiles, const uint4 *items, uint32_t nitems, void *cum,
                                    uint64_t nslots);
 
-struct FinalizeLaunch {
+// the by-value argument of k_finalize / k_finalize_signal (kernels_compare.hip): filled by run_pairs (engine.hip), ntiles
+// by launch_finalize.  Member order and types are the kernels' argument layout: its ~70 dwords already press on the
+// scalar registers (kernels_compare.hip, finalize_block), so nothing is added or reordered here in passing.
+struct FinalizeArgs {
     const void *cum;
-    int cum_bytes;  // 2 or 4
-    uint64_t cum_stride;  // pair slots of the whole band (distance between two planes of cum)
-    uint64_t nslots;      // pair slots to finalize (a band, or a segment of it: cum/tiles point at its first tile)
-    const uint4 *tiles;
-    const uint32_t *perm;
-    const uint64_t *rowoff = nullptr;  // row-sorted parts: out index = rowoff[layout position of the pair's row] + column offset
-    int hist_bins, pbase, p, estim, result_type;  // hist_bins: max over the launch's tiles of (largest - smallest value + 1)
+    uint64_t nslots;       // distance between two planes of cum (pair slots of the band)
+    const uint4 *tiles;    // {row block, col block, plane begin, plane end} per tile
+    const uint32_t *perm;  // plane-matrix column -> sketch index (nullptr: identity)
+    // row-sorted parts (plan.h): the output buffer holds the wanted rows in KEY order, the row at layout position s
+    // starting at rowoff[s]; nullptr: the rows' span of the packed triangle in final order
+    const uint64_t *rowoff;
+    int hist_bins;  // histogram columns allocated per lane (>= the value span of any tile of the launch)
+    int pbase;  // plane pl is the threshold v = pbase + 1 + pl
+    int p;
+    int estim;
+    int result_type;
     double ksinv;
-    // per column of the layout, in layout order (k_build_colindex): listed registers, key, cardinality, tail histogram,
-    // compact list (position << 8 | value, E entries per column); the position index of the column blocks
-    const uint32_t *nS, *keyS;
-    const double *cardS;
-    const uint8_t *thS;
-    const uint32_t *rl;
+    // per COLUMN of the layout, in layout order (k_build_colindex): nothing below waits for the permutation
+    const uint32_t *nS;       // [Npad] listed registers of the column's sketch
+    const uint32_t *keyS;     // [Npad] hi << 18 | T << 12 | L << 6 | lo
+    const double *cardS;      // [Npad]
+    const uint8_t *thS;       // [Npad][64]: how many listed registers have each value above the sketch's T
+    const uint32_t *rl;       // [Npad][E]: the listed registers, position << 8 | value
     uint32_t E;
-    const uint32_t *cidx_rec;
-    const uint32_t *cidx_ent;
+    const uint32_t *cidx_rec; // position index of the column blocks: [blocks][nbuckets][RK + 1] records
+    const uint32_t *cidx_ent; // [blocks][ent_stride] all entries in bucket order (buckets with more than RK entries)
     uint32_t nbuckets, ent_stride;
-    uint64_t n, ncols;  // collection size (output dimension); real columns of the plane matrix
-    int rect, sorted_out, square;
-    int knn = 0;          // band-wise nearest neighbours: out = V[band rows][knn_ld], out2 = Vt[columns][knn_rows]
-    float *out2 = nullptr;
-    uint64_t knn_ld = 0, knn_rows = 0;
-    int stop = 0;  // profiling: k_finalize leaves after phase `stop`
-    unsigned long long *phase_cyc = nullptr;  // profiling: per-phase cycle sums of the full kernel (8 x u64, device)
-    uint64_t row_begin, row_end, col_begin, col_end, base_index;
+    uint64_t n;      // sketches in the collection = dimension of the output matrix
+    uint64_t ncols;  // real columns of the plane matrix (a sub-collection when only a row range is wanted)
+    // triangle mode: rows [row_begin,row_end) (original indices), out index = tri(i,j) - base_index
+    // rect mode (rect != 0): i in [row_begin,row_end) x j in [col_begin,col_end), row-major
+    int rect;
+    // sorted_out != 0 (triangle mode only): rows and the output index are in plane-column
+    // (sorted) order instead of original sketch order -- used for multi-GPU shards, whose spans
+    // are gathered first and un-permuted once (k_unpermute)
+    int sorted_out;
+    // square != 0 (triangle tiles, all rows): every pair is written at BOTH out[i*n+j] and
+    // out[j*n+i] of an n x n matrix (the all-vs-all nearest-neighbour path: each pair computed once)
+    int square;
+    // knn != 0 (whole key-ordered layout, rows = plane columns [row_begin,row_end) like sorted_out): the pair (si, sj),
+    // si < sj, is written twice -- out[(si - row_begin) * knn_ld + sj] is a candidate of row si, out2[sj * knn_rows +
+    // (si - row_begin)] a candidate of row sj -- for the band-wise nearest-neighbour selection (k_topk_merge)
+    int knn;
+    float *out2;
+    uint64_t knn_ld, knn_rows;
+    int stop;             // profiling only (option "finalize_stop"): leave after phase 1..4 with a dummy store
+    uint32_t ntiles;      // tiles of this launch
+    unsigned long long *phase_cyc;  // profiling only (TIMED instances): shader-clock cycles per phase, summed over waves
+    uint64_t row_begin, row_end, col_begin, col_end;
+    uint64_t base_index;
     float *out;
-    // part signalling (k_finalize_signal): the call's signal block (layout below), the generation value that marks a part
-    // final, whether completion times are stamped (profiling).  nullptr: completion is marked by events between launches.
-    uint32_t *sig = nullptr;
+    // part signalling (k_finalize_signal; kernels.h kSig*): counters and flags of the call's parts; the generation value
+    // that marks a part final and the stamp switch live in the block itself (two kernel arguments fewer)
+    uint32_t *sig;
+};
+static_assert(sizeof(FinalizeArgs) == 272, "the kernel argument of k_finalize changed its layout");
+// a launch of k_finalize over a band of tiles or a segment of it (a.cum / a.tiles point at its first tile): the kernel's
+// arguments and the two host-only quantities that pick the instance and size the launch
+struct FinalizeLaunch {
+    FinalizeArgs a;
+    int cum_bytes;    // 2 or 4
+    uint64_t nslots;  // pair slots to finalize (a.nslots: those of the whole band)
 };
 hipError_t launch_finalize(hipStream_t st, const FinalizeLaunch &f);
 // the signal block of a call with parts, in 32-bit words: per part a flag (= the generation of the call that completed

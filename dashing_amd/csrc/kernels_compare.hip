@@ -1021,60 +1021,8 @@ hipError_t launch_pair_counts_mfma(hipStream_t st, int kc, int cum_bytes, const 
 
 // ------------------------------------------------------------------------------------------
 // finalize: one lane per pair slot of a band of tiles.  128 threads per block = one tile row
-// (consecutive lanes = consecutive j: coalesced cum reads and output writes).
-struct FinalizeArgs {
-    const void *cum;
-    uint64_t nslots;       // distance between two planes of cum (pair slots of the band)
-    const uint4 *tiles;    // {row block, col block, plane begin, plane end} per tile
-    const uint32_t *perm;  // plane-matrix column -> sketch index (nullptr: identity)
-    // row-sorted parts (plan.h): the output buffer holds the wanted rows in KEY order, the row at layout position s
-    // starting at rowoff[s]; nullptr: the rows' span of the packed triangle in final order
-    const uint64_t *rowoff;
-    int hist_bins;  // histogram columns allocated per lane (>= the value span of any tile of the launch)
-    int pbase;  // plane pl is the threshold v = pbase + 1 + pl
-    int p;
-    int estim;
-    int result_type;
-    double ksinv;
-    // per COLUMN of the layout, in layout order (k_build_colindex): nothing below waits for the permutation
-    const uint32_t *nS;       // [Npad] listed registers of the column's sketch
-    const uint32_t *keyS;     // [Npad] hi << 18 | T << 12 | L << 6 | lo
-    const double *cardS;      // [Npad]
-    const uint8_t *thS;       // [Npad][64]: how many listed registers have each value above the sketch's T
-    const uint32_t *rl;       // [Npad][E]: the listed registers, position << 8 | value
-    uint32_t E;
-    const uint32_t *cidx_rec; // position index of the column blocks: [blocks][nbuckets][RK + 1] records
-    const uint32_t *cidx_ent; // [blocks][ent_stride] all entries in bucket order (buckets with more than RK entries)
-    uint32_t nbuckets, ent_stride;
-    uint64_t n;      // sketches in the collection = dimension of the output matrix
-    uint64_t ncols;  // real columns of the plane matrix (a sub-collection when only a row range is wanted)
-    // triangle mode: rows [row_begin,row_end) (original indices), out index = tri(i,j) - base_index
-    // rect mode (rect != 0): i in [row_begin,row_end) x j in [col_begin,col_end), row-major
-    int rect;
-    // sorted_out != 0 (triangle mode only): rows and the output index are in plane-column
-    // (sorted) order instead of original sketch order -- used for multi-GPU shards, whose spans
-    // are gathered first and un-permuted once (k_unpermute)
-    int sorted_out;
-    // square != 0 (triangle tiles, all rows): every pair is written at BOTH out[i*n+j] and
-    // out[j*n+i] of an n x n matrix (the all-vs-all nearest-neighbour path: each pair computed once)
-    int square;
-    // knn != 0 (whole key-ordered layout, rows = plane columns [row_begin,row_end) like sorted_out): the pair (si, sj),
-    // si < sj, is written twice -- out[(si - row_begin) * knn_ld + sj] is a candidate of row si, out2[sj * knn_rows +
-    // (si - row_begin)] a candidate of row sj -- for the band-wise nearest-neighbour selection (k_topk_merge)
-    int knn;
-    float *out2;
-    uint64_t knn_ld, knn_rows;
-    int stop;             // profiling only (option "finalize_stop"): leave after phase 1..4 with a dummy store
-    uint32_t ntiles;      // tiles of this launch
-    unsigned long long *phase_cyc;  // profiling only (TIMED instances): shader-clock cycles per phase, summed over waves
-    uint64_t row_begin, row_end, col_begin, col_end;
-    uint64_t base_index;
-    float *out;
-    // part signalling (k_finalize_signal; kernels.h kSig*): counters and flags of the call's parts; the generation value
-    // that marks a part final and the stamp switch live in the block itself (two kernel arguments fewer)
-    uint32_t *sig;
-};
-
+// (consecutive lanes = consecutive j: coalesced cum reads and output writes).  Its argument is FinalizeArgs (kernels.h).
+//
 // The two sparse tails of a pair's histogram without walking lists.  The block's 128 lanes share sketch i (one tile
 // row); the tile has the dense planes v in (Lp, T].
 //   upper tail (x > T): a lane's bins start as i's tail histogram + sketch j's (tailhist, one byte per value) -- that
@@ -2050,35 +1998,23 @@ hipError_t launch_pair_counts_lockstep(hipStream_t st, int kc, int cum_bytes, co
 hipError_t launch_finalize(hipStream_t st, const FinalizeLaunch &f)
 {
     if (f.nslots == 0) return hipSuccess;
-    FinalizeArgs a;
-    a.rowoff = f.rowoff;
-    a.cum = f.cum; a.nslots = f.cum_stride; a.tiles = f.tiles; a.perm = f.perm; a.hist_bins = f.hist_bins; a.pbase = f.pbase;
-    a.p = f.p; a.estim = f.estim; a.result_type = f.result_type; a.ksinv = f.ksinv;
-    a.nS = f.nS; a.keyS = f.keyS; a.cardS = f.cardS; a.thS = f.thS; a.rl = f.rl; a.E = f.E;
-    a.cidx_rec = f.cidx_rec; a.cidx_ent = f.cidx_ent; a.nbuckets = f.nbuckets; a.ent_stride = f.ent_stride;
-    a.n = f.n; a.ncols = f.ncols; a.rect = f.rect; a.sorted_out = f.sorted_out; a.square = f.square;
-    a.knn = f.knn; a.out2 = f.out2; a.knn_ld = f.knn_ld; a.knn_rows = f.knn_rows;
-    a.row_begin = f.row_begin; a.row_end = f.row_end; a.col_begin = f.col_begin;
-    a.col_end = f.col_end; a.base_index = f.base_index; a.out = f.out;
-    a.stop = f.stop;
-    a.phase_cyc = f.phase_cyc;
-    a.sig = f.sig;
+    FinalizeArgs a = f.a;
     a.ntiles = (uint32_t)(f.nslots / ((uint64_t)kTile * kTile));
-    const size_t lds = (64 + 128 + 8) * sizeof(uint32_t) + (size_t)f.hist_bins * 128 * (f.cum_bytes == 2 ? 2 : 4);
+    const size_t lds = (64 + 128 + 8) * sizeof(uint32_t) + (size_t)a.hist_bins * 128 * (f.cum_bytes == 2 ? 2 : 4);
     const uint32_t blocks = (a.ntiles + 7u) / 8u * 8u * 128u;  // (whole groups of 8 tiles: a tile's 128 rows on one XCD)
-    const bool timed = f.phase_cyc != nullptr;  // profiling only
-    const bool general = f.rect || f.square || f.sorted_out || f.knn;
-    if (f.sig && (general || timed)) return hipErrorInvalidValue;  // (the signalling instance is the plain triangle's)
+    const bool timed = a.phase_cyc != nullptr;  // profiling only
+    const bool general = a.rect || a.square || a.sorted_out || a.knn;
+    if (a.sig && (general || timed)) return hipErrorInvalidValue;  // (the signalling instance is the plain triangle's)
 #define DSH_FIN(CT, RK)                                                                                                  \
     do {                                                                                                                 \
         if (general) hipLaunchKernelGGL((k_finalize<CT, RK, false, true>), dim3(blocks), dim3(128), lds, st, a);        \
         else if (timed) hipLaunchKernelGGL((k_finalize<CT, RK, true, false>), dim3(blocks), dim3(128), lds, st, a);      \
-        else if (f.sig) hipLaunchKernelGGL((k_finalize_signal<CT, RK>), dim3(blocks), dim3(128), lds, st, a); \
+        else if (a.sig) hipLaunchKernelGGL((k_finalize_signal<CT, RK>), dim3(blocks), dim3(128), lds, st, a); \
         else hipLaunchKernelGGL((k_finalize<CT, RK, false, false>), dim3(blocks), dim3(128), lds, st, a);                \
     } while (0)
     // (the record width follows the precision like k_build_colindex: colindex_inline)
     if (f.cum_bytes != 2) DSH_FIN(uint32_t, 3);
-    else if (colindex_inline(f.p, f.E) == 3) DSH_FIN(uint16_t, 3);
+    else if (colindex_inline(a.p, a.E) == 3) DSH_FIN(uint16_t, 3);
     else DSH_FIN(uint16_t, 7);
 #undef DSH_FIN
     return hipGetLastError();

@@ -20,10 +20,8 @@ struct PairsQuery {
 
 int check_query(dsh_ctx *c, int estim, const int *result_types, uint32_t n_types, int k, PairsQuery &q)
 {
-    if (!c) return DSH_EINVAL;
-    int rc = bind(c);
+    int rc = enter(c);
     if (rc) return rc;
-    if (!c->have_sketches) return fail(c, DSH_ESTATE, "no sketches loaded");
     if (estim < 0 || estim > 2) return fail(c, DSH_EINVAL, "bad estimator %d", estim);
     if (n_types > 9) return fail(c, DSH_EINVAL, "%u result types: at most 9", n_types);
     if (n_types && !result_types) return DSH_EINVAL;

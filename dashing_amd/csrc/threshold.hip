@@ -108,17 +108,8 @@ int run_threshold(dsh_ctx *c, const ThrQuery &q, uint64_t *n_hits)
         HIPCHK(c, c->thr_cnt.ensure(m * sizeof(uint32_t)));
         HIPCHK(c, c->thr_off.ensure((m + 1) * sizeof(uint64_t)));
         if (span) {
-            PairJob j;
-            j.estim = q.estim;
-            j.result_type = q.result_type;
-            j.k = q.k;
-            j.rect = q.rect;
-            j.row_begin = b0;
-            j.row_end = b1;
-            j.col_begin = q.rect ? q.cb : 0;
-            j.col_end = q.rect ? q.ce : 0;
-            j.base_index = q.rect ? 0 : dsh_tri_span(c->n, 0, b0);
-            j.d_out = (float *)c->thr_vals.ptr;
+            const PairJob j = q.rect ? PairJob::rectangle(q.estim, q.result_type, q.k, b0, b1, q.cb, q.ce, c->thr_vals.ptr)
+                                     : PairJob::triangle(q.estim, q.result_type, q.k, b0, b1, dsh_tri_span(c->n, 0, b0), c->thr_vals.ptr);
             if ((rc = run_pairs(c, j))) break;
         }
         const float *vals = (const float *)c->thr_vals.ptr;
@@ -197,16 +188,6 @@ int run_threshold(dsh_ctx *c, const ThrQuery &q, uint64_t *n_hits)
     return DSH_OK;
 }
 
-int check_common(dsh_ctx *c)
-{
-    if (!c) return DSH_EINVAL;
-    int rc = bind(c);
-    if (rc) return rc;
-    if (!c->have_sketches) return fail(c, DSH_ESTATE, "no sketches loaded");
-    reset_prof(c);
-    return DSH_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -214,8 +195,9 @@ extern "C" {
 int dsh_dist_threshold(dsh_ctx *c, int estim, int result_type, int k, uint64_t rb, uint64_t re, float threshold,
                        uint64_t *row_ptr_out, uint32_t **col_out, float **val_out, uint64_t *n_hits)
 {
-    int rc = check_common(c);
+    int rc = enter(c);
     if (rc) return rc;
+    reset_prof(c);
     if (!row_ptr_out) return DSH_EINVAL;
     if ((col_out == nullptr) != (val_out == nullptr)) return fail(c, DSH_EINVAL, "col_out and val_out go together");
     if (re > c->n) re = c->n;
@@ -233,8 +215,9 @@ int dsh_dist_threshold(dsh_ctx *c, int estim, int result_type, int k, uint64_t r
 int dsh_dist_threshold_device(dsh_ctx *c, int estim, int result_type, int k, uint64_t rb, uint64_t re, float threshold,
                               void *d_row_ptr, void *d_col, void *d_val, uint64_t cap, uint64_t *n_hits)
 {
-    int rc = check_common(c);
+    int rc = enter(c);
     if (rc) return rc;
+    reset_prof(c);
     if (!d_row_ptr) return DSH_EINVAL;
     if ((d_col == nullptr) != (d_val == nullptr)) return fail(c, DSH_EINVAL, "d_col and d_val go together");
     if (re > c->n) re = c->n;
@@ -250,8 +233,9 @@ int dsh_dist_threshold_device(dsh_ctx *c, int estim, int result_type, int k, uin
 int dsh_dist_rect_threshold(dsh_ctx *c, int estim, int result_type, int k, uint64_t qb, uint64_t qe, uint64_t rb, uint64_t re,
                             float threshold, uint64_t *row_ptr_out, uint32_t **col_out, float **val_out, uint64_t *n_hits)
 {
-    int rc = check_common(c);
+    int rc = enter(c);
     if (rc) return rc;
+    reset_prof(c);
     if (qe > c->n || re > c->n) return fail(c, DSH_EINVAL, "slots out of range");
     if (!row_ptr_out) return DSH_EINVAL;
     if ((col_out == nullptr) != (val_out == nullptr)) return fail(c, DSH_EINVAL, "col_out and val_out go together");

@@ -128,6 +128,25 @@ def test_distance_measures_against_the_dense_rectangle(ctx, n, p):
                 dense = check_all_vs_all(ctx, n, nn, budgets_for(n), estim, rt, 21, dense)
 
 
+def test_mash_values_are_the_same_bits_on_all_three_paths(ctx):
+    """All three paths go through the general instance of k_finalize with exact histograms and 1/k as a DOUBLE (PairJob's
+    ksinv_double); only the layout differs.  A path that lost the switch would hand over the float and move a Mash distance
+    by an ulp -- inside every tolerance above -- so each row's values are compared bit for bit across the paths.  (Indices
+    may differ under ties.)  n = 300 is three tile rows, the last one partial, and three bands of 128 rows."""
+    import dashing_amd
+
+    n, p, nn = 300, 10, 5
+    ctx.set_sketches(shape_regs(n, p, seed=100 + n))
+    got = all_paths(ctx, n, nn, [0], result_type=dashing_amd.MASH_DIST, k=21)
+    assert [name for name, _ in got] == ["square", "bands@128", "blocks"]
+    want = got[0][1][1]
+    assert want.shape == (n, nn) and want.dtype == np.float32
+    for name, (_, val) in got[1:]:
+        assert val.shape == (n, nn) and val.dtype == np.float32
+        differ = np.argwhere(val.view(np.uint32) != want.view(np.uint32))
+        assert differ.size == 0, (name, differ[:5])
+
+
 # ---- 3. edges ----------------------------------------------------------------------------------------------------------
 def test_nn_values_around_the_lanes_and_the_band_paths_limit(ctx):
     """nn around the 64 lanes that stride the running list in LDS, the two ends of the band path's range (1024 stays on the
