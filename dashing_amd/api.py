@@ -29,7 +29,8 @@ SYMBOLS = [
     "dsh_comm_available", "dsh_comm_library", "dsh_comm_wait", "dsh_exchange_mode", "dsh_exchange_rows_device_async",
     "dsh_exchange_collect_async", "dsh_exchange_place_device", "dsh_exchange_probe_parts_async", "dsh_diag_spin_start", "dsh_diag_spin_stop", "dsh_abi_version", "dsh_preload", "dsh_comm_unique_id", "dsh_comm_init", "dsh_comm_destroy", "dsh_comm_rank", "dsh_collect_spans", "dsh_collect_spans_async",
     "dsh_allgather_device", "dsh_dist_collect", "dsh_range_parts", "dsh_dist_rows_parts_device_async", "dsh_collect_parts_async",
-    "dsh_dist_rect", "dsh_knn", "dsh_dist_threshold", "dsh_dist_threshold_device", "dsh_dist_rect_threshold", "dsh_dist_pairs", "dsh_dist_pairs_device", "dsh_dist_pairs_csr", "dsh_shard_plan", "dsh_dist_shard_device", "dsh_unpermute_device", "dsh_unpermute_staged_device", "dsh_unpermute_blocks_device", "dsh_tri_span", "dsh_tri_index", "dsh_partition_rows", "dsh_balance_rows", "dsh_balance_rowsets", "dsh_rowsets_from_bounds", "dsh_rowsets_rank", "dsh_alloc_host", "dsh_free_host",
+    "dsh_dist_rect", "dsh_knn", "dsh_dist_threshold", "dsh_dist_threshold_device", "dsh_dist_rect_threshold", "dsh_dist_pairs", "dsh_dist_pairs_device", "dsh_dist_pairs_csr",
+    "dsh_fold", "dsh_fold_device", "dsh_upload_sketches_folded", "dsh_upload_sketches_folded_device", "dsh_union_groups", "dsh_union_groups_device", "dsh_shard_plan", "dsh_dist_shard_device", "dsh_unpermute_device", "dsh_unpermute_staged_device", "dsh_unpermute_blocks_device", "dsh_tri_span", "dsh_tri_index", "dsh_partition_rows", "dsh_balance_rows", "dsh_balance_rowsets", "dsh_rowsets_from_bounds", "dsh_rowsets_rank", "dsh_alloc_host", "dsh_free_host",
     "dsh_set_profiling", "dsh_last_kernel_ms", "dsh_last_part_info", "dsh_finalize_phase_cycles", "dsh_set_option", "dsh_get_info", "dsh_stream",
 ]
 
@@ -154,6 +155,14 @@ def load_library():
     lib.dsh_dist_pairs.argtypes = [vp, i32, vp, C.c_uint32, i32, vp, vp, u64, vp]
     lib.dsh_dist_pairs_device.argtypes = [vp, i32, vp, C.c_uint32, i32, vp, vp, u64, vp]
     lib.dsh_dist_pairs_csr.argtypes = [vp, i32, vp, C.c_uint32, i32, u64, u64, vp, vp, vp]
+    # derived sketches: bound by name, so that a library built before they existed still loads (calling one then fails)
+    for name, args in (("dsh_fold", [vp, u64, u64, i32, vp]), ("dsh_fold_device", [vp, u64, u64, i32, vp]),
+                       ("dsh_upload_sketches_folded", [vp, vp, i32, u64, u64]),
+                       ("dsh_upload_sketches_folded_device", [vp, vp, i32, u64, u64]),
+                       ("dsh_union_groups", [vp, vp, vp, u64, vp]), ("dsh_union_groups_device", [vp, vp, vp, u64, vp])):
+        fn = getattr(lib, name, None)
+        if fn is not None:
+            fn.argtypes = args
     lib.dsh_shard_plan.argtypes = [vp, i32, C.c_uint32, vp]
     lib.dsh_dist_shard_device.argtypes = [vp, i32, i32, i32, C.c_uint32, C.c_uint32, vp]
     lib.dsh_unpermute_device.argtypes = [vp, vp, vp]
@@ -407,6 +416,54 @@ class Context:
     def clear(self, first_slot=0, n=None):
         n = self.n - first_slot if n is None else n
         self._ck(self._lib.dsh_clear_sketches(self._h, first_slot, n))
+
+    # ---- derived sketches (fold to a lower p, union by groups)
+    def _derive(self, name):
+        fn = getattr(self._lib, name, None)
+        if fn is None:
+            raise DshError(-22, "%s does not export %s: rebuild it" % (lib_path(), name))
+        return fn
+
+    def fold(self, new_p, first_slot=0, n=None):
+        """rows [first_slot, first_slot + n) folded to precision new_p: uint8 [n][2^new_p]"""
+        n = self.n - first_slot if n is None else n
+        out = np.zeros((n, 1 << max(int(new_p), 0)), np.uint8)
+        self._ck(self._derive("dsh_fold")(self._h, first_slot, n, new_p, out.ctypes.data))
+        return out
+
+    def fold_device(self, out_ptr, new_p, first_slot=0, n=None):
+        n = self.n - first_slot if n is None else n
+        self._ck(self._derive("dsh_fold_device")(self._h, first_slot, n, new_p, C.c_void_p(out_ptr)))
+
+    def upload_folded(self, regs, src_p=None, first_slot=0):
+        """host rows at precision src_p >= p (default: from regs.shape[1]), folded on the device into the slots"""
+        regs = np.ascontiguousarray(regs, np.uint8)
+        assert regs.ndim == 2
+        if src_p is None:
+            src_p = int(regs.shape[1]).bit_length() - 1
+        assert regs.shape[1] == (1 << src_p)
+        self._ck(self._derive("dsh_upload_sketches_folded")(self._h, regs.ctypes.data, src_p, first_slot, regs.shape[0]))
+
+    def upload_folded_device(self, ptr, src_p, n, first_slot=0):
+        self._ck(self._derive("dsh_upload_sketches_folded_device")(self._h, C.c_void_p(ptr), src_p, first_slot, n))
+
+    @staticmethod
+    def _groups(group_ptr, members):
+        gp = np.ascontiguousarray(group_ptr, np.uint64).reshape(-1)
+        mem = np.ascontiguousarray(members, np.uint32).reshape(-1)
+        assert gp.size >= 1 and (gp.size == 1 or int(gp[-1]) <= mem.size)
+        return gp, mem
+
+    def union_groups(self, group_ptr, members):
+        """uint8 [n_groups][2^p]: row g = element-wise max of the resident rows members[group_ptr[g]:group_ptr[g + 1]]"""
+        gp, mem = self._groups(group_ptr, members)
+        out = np.zeros((gp.size - 1, 1 << self.p), np.uint8)
+        self._ck(self._derive("dsh_union_groups")(self._h, gp.ctypes.data, mem.ctypes.data, gp.size - 1, out.ctypes.data))
+        return out
+
+    def union_groups_device(self, out_ptr, group_ptr, members):
+        gp, mem = self._groups(group_ptr, members)
+        self._ck(self._derive("dsh_union_groups_device")(self._h, gp.ctypes.data, mem.ctypes.data, gp.size - 1, C.c_void_p(out_ptr)))
 
     # ---- sketch waist
     def sketch_batch(self, seq, genome_off, first_slot=0, k=31, canon=True, want_regs=True):

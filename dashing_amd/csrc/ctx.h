@@ -5,6 +5,7 @@
 //   knn.hip       dsh_knn
 //   threshold.hip dsh_dist_threshold*, dsh_dist_rect_threshold (values that pass a threshold, as CSR)
 //   pairs.hip     dsh_dist_pairs* (values of an explicit list of pairs, the direct form)
+//   derive.hip    dsh_fold*, dsh_upload_sketches_folded*, dsh_union_groups* (new sketches out of resident ones)
 //   exchange.hip  RCCL: dsh_comm_*, dsh_collect_*, dsh_allgather_device, dsh_dist_collect
 //   plan.cpp      the pure-host planner (layout, tiles, bands, parts, work items, row partitions)
 #pragma once
@@ -182,6 +183,10 @@ struct dsh_ctx {
     hipEvent_t ev_pairs = nullptr;      // its upload has run
     int pairs_card_estim = -1;          // estimator pairs_card was computed under (-1: none), dropped by invalidate()
     uint64_t pairs_chunk = 1u << 18;    // option: pairs per launch (scratch is 64 counters per pair of a chunk)
+    // dsh_fold*, dsh_upload_sketches_folded*, dsh_union_groups* (derive.hip): the error word, a chunk of source rows or of
+    // folded rows on its way through the device, the groups' CSR and the partial unions of groups cut into chunks
+    DevBuf derive_err, derive_stage, derive_ptr, derive_mem, derive_dst, derive_part[2], derive_out;
+    uint64_t derive_chunk_bytes = (uint64_t)256 << 20;  // option: source rows staged per step of the host forms
     int pair_mfma = 0;  // WHAT-IF only (built with `make WHATIF=1`): 1 = the AND+popcount tile kernel on the matrix cores
     int finalize_stop = 0;  // profiling only: k_finalize leaves after phase 1..4 (results are then meaningless)
     int finalize_timing = 0;  // profiling only: the s_memtime-stamped instance of k_finalize (same results, per-phase cycles)

@@ -8,6 +8,7 @@
 #include <omp.h>
 
 #include <atomic>
+#include <fstream>
 #include <sys/stat.h>
 #include <unistd.h>
 #include <zlib.h>
@@ -24,6 +25,8 @@
 #include <thread>
 #include <unordered_map>
 #include <vector>
+
+#include <hip/hip_runtime_api.h>  // (--groups: the unions' device buffer)
 
 #include "../../../include/dashing_hip.h"
 #include "host.h"
@@ -94,7 +97,12 @@ static void usage(const char *sub)
             "                           measure.  --measures LIST: comma-separated from MASH_DIST, JI, SIZES, FULL_MASH_DIST,\n"
             "                           FULL_CONTAINMENT_DIST, CONTAINMENT_INDEX, CONTAINMENT_DIST, SYMMETRIC_CONTAINMENT_INDEX,\n"
             "                           SYMMETRIC_CONTAINMENT_DIST [the measure the other flags select].  Not with -Q,\n"
-            "                           --nearest-neighbors, --threshold, -b or several devices.\n");
+            "                           --nearest-neighbors, --threshold, -b or several devices.\n"
+            "  --groups FILE            compare the UNIONS of groups of inputs instead of the inputs: FILE lists name<TAB>group per\n"
+            "                           line, every input exactly once; the groups, in order of first appearance, take the\n"
+            "                           inputs' place in every output (labels, -o sizes, all formats, --threshold,\n"
+            "                           --nearest-neighbors).  Not with --pairs, -Q, dist_by_seq or several devices.\n"
+            "  --presketched            .hll files sketched at a HIGHER precision than -S are folded to -S as they are loaded\n");
     }
     std::exit(EXIT_FAILURE);
 }
@@ -106,6 +114,7 @@ struct Opts {
     unsigned nneighbors = 0;  // --nearest-neighbors
     bool has_threshold = false;  // --threshold: only the pairs that pass, as (name, name, value) lines or CSR (-b)
     float threshold = 0.f;
+    std::string groups_file;  // --groups FILE: the unions of named groups are compared instead of the inputs (dsh_union_groups)
     std::string pairs_file, measures;  // --pairs FILE [--measures LIST]: only the listed pairs (dsh_dist_pairs)
     int rccl = 0;             // --rccl: deliver the rows through the RCCL exchange of the C-ABI even with one device
     std::vector<int> devices;  // --devices a,b,... / --ngpus G: GPUs sharing the all-pairs rows (binary output)
@@ -113,7 +122,7 @@ struct Opts {
     std::vector<std::string> inpaths, querypaths;
 };
 
-enum { OPT_PRESKETCHED = 1000, OPT_AVOID_SORT, OPT_DEVICE, OPT_NPERBATCH, OPT_NN, OPT_NGPUS, OPT_DEVICES, OPT_RCCL, OPT_THRESHOLD, OPT_PAIRS, OPT_MEASURES, OPT_UNSUPPORTED };
+enum { OPT_PRESKETCHED = 1000, OPT_AVOID_SORT, OPT_DEVICE, OPT_NPERBATCH, OPT_NN, OPT_NGPUS, OPT_DEVICES, OPT_RCCL, OPT_THRESHOLD, OPT_PAIRS, OPT_MEASURES, OPT_GROUPS, OPT_UNSUPPORTED };
 
 static Opts parse(int argc, char **argv, bool is_dist)
 {
@@ -140,7 +149,7 @@ static Opts parse(int argc, char **argv, bool is_dist)
         {"use-bloom-filter", no_argument, nullptr, OPT_UNSUPPORTED}, {"use-nthash", no_argument, nullptr, OPT_UNSUPPORTED},
         {"use-cyclic-hash", no_argument, nullptr, OPT_UNSUPPORTED}, {"countmin", no_argument, nullptr, OPT_UNSUPPORTED},
         {"nearest-neighbors", required_argument, nullptr, OPT_NN}, {"threshold", required_argument, nullptr, OPT_THRESHOLD},
-        {"pairs", required_argument, nullptr, OPT_PAIRS}, {"measures", required_argument, nullptr, OPT_MEASURES},
+        {"pairs", required_argument, nullptr, OPT_PAIRS}, {"groups", required_argument, nullptr, OPT_GROUPS}, {"measures", required_argument, nullptr, OPT_MEASURES},
         // second arm of result_cmp (src/dashing.h:577-588); flag numbers as in DIST_LONG_OPTS
         {"sizes", no_argument, nullptr, 'Z'}, {"containment-index", no_argument, nullptr, 131},
         {"containment-dist", no_argument, nullptr, 132}, {"full-containment-dist", no_argument, nullptr, 133},
@@ -213,6 +222,7 @@ static Opts parse(int argc, char **argv, bool is_dist)
         }
         case OPT_PAIRS: o.pairs_file = optarg; break;
         case OPT_MEASURES: o.measures = optarg; break;
+        case OPT_GROUPS: o.groups_file = optarg; break;
         case '8': case 'y': case 'J': case OPT_UNSUPPORTED:
             die("this option selects a sketch type / emitter outside the HLL sketch+dist hot path");
         default: usage(is_dist ? "dist" : "sketch");
@@ -916,6 +926,7 @@ static int sketch_by_seq_main(int argc, char **argv)
 static int dist_main(int argc, char **argv, bool by_seq = false)
 {
     Opts o = parse(argc, argv, true);
+    if (by_seq && !o.groups_file.empty()) die("--groups does not go with dist_by_seq: the groups name input files.");
     // dist_by_seq: the records (or a sketch_by_seq file) take the place of the genomes, their names that of the paths
     Records R;
     std::vector<uint8_t> pre;  // --presketched: the sketch_by_seq stream
@@ -970,12 +981,18 @@ static int dist_main(int argc, char **argv, bool by_seq = false)
         }
         if (pair_types.empty() || pair_types.size() > 9) die("--measures takes one to nine names.");
     }
+    const bool with_groups = !o.groups_file.empty();
+    if (with_groups) {
+        if (with_pairs) die("--groups does not go with --pairs: a pair list names inputs, not groups.");
+        if (!o.querypaths.empty()) die("--groups does not go with -Q: every group is compared with every other.");
+        if (o.devices.size() > 1 || o.rccl) die("--groups runs on one device: --ngpus / --devices are not supported.");
+    }
     std::FILE *ofp = stdout, *pairofp = stdout;
     if (!o.out_sizes.empty() && !(ofp = std::fopen(o.out_sizes.c_str(), "w"))) die("Could not open file at %s for writing.", o.out_sizes.c_str());
     if (!o.out_dists.empty() && !(pairofp = std::fopen(o.out_dists.c_str(), "wb"))) die("Could not open file at %s for writing.", o.out_dists.c_str());
     // asymmetric measure without -Q: all references are also the queries (src/distmain.cpp:120-125)
     const bool symmetric = !(o.result_type == 4 || o.result_type == 5 || o.result_type == 6);  // src/dashing.h:389-399
-    if (o.querypaths.empty() && !symmetric && !with_pairs) {  // (a pair list names its own pairs, each in one orientation)
+    if (o.querypaths.empty() && !symmetric && !with_pairs && !with_groups) {  // (a pair list names its own pairs, each in one orientation; the groups take their turn below)
         o.querypaths = o.inpaths;
         std::fprintf(stderr, "Note: No query files provided, but an asymmetric distance was requested. Switching to a query/reference format with all references as queries.\n");
     }
@@ -983,9 +1000,45 @@ static int dist_main(int argc, char **argv, bool by_seq = false)
         sort_paths_by_fsize(o.inpaths);
         sort_paths_by_fsize(o.querypaths);
     }
-    const size_t nq = o.querypaths.size();
+    size_t nq = o.querypaths.size();
     for (auto &q : o.querypaths) o.inpaths.push_back(q);  // queries follow the references (src/distmain.cpp:130-133)
-    const size_t n = o.inpaths.size();
+    size_t n = o.inpaths.size();
+    // --groups: group names in order of first appearance, and the members of each as input slots
+    std::vector<std::string> group_names;
+    std::vector<uint64_t> group_ptr;
+    std::vector<uint32_t> group_members;
+    if (with_groups) {
+        std::unordered_map<std::string, uint32_t> slot_of, group_of;
+        for (size_t i = n; i-- > 0;) slot_of[o.inpaths[i]] = (uint32_t)i;
+        if (slot_of.size() != n) die("--groups: an input is given twice.");
+        std::vector<uint32_t> gid(n, ~0u);
+        std::ifstream gf(o.groups_file);
+        if (!gf) die("Could not open %s", o.groups_file.c_str());
+        std::string line;
+        for (long ln = 1; std::getline(gf, line); ++ln) {
+            if (!line.empty() && line.back() == '\r') line.pop_back();
+            if (line.empty()) continue;
+            const size_t tab = line.find('\t');
+            if (tab == std::string::npos || tab == 0 || tab + 1 == line.size() || line.find('\t', tab + 1) != std::string::npos)
+                die("%s, line %ld: a line is a name and a group separated by one tab.", o.groups_file.c_str(), ln);
+            const std::string name = line.substr(0, tab), grp = line.substr(tab + 1);
+            const auto it = slot_of.find(name);
+            if (it == slot_of.end()) die("%s: '%s' is not one of the inputs.", o.groups_file.c_str(), name.c_str());
+            if (gid[it->second] != ~0u) die("%s: '%s' is named twice.", o.groups_file.c_str(), name.c_str());
+            const auto g = group_of.emplace(grp, (uint32_t)group_names.size());
+            if (g.second) group_names.push_back(grp);
+            gid[it->second] = g.first->second;
+        }
+        for (size_t i = 0; i < n; ++i)
+            if (gid[i] == ~0u) die("%s: the input '%s' has no group.", o.groups_file.c_str(), o.inpaths[i].c_str());
+        const size_t ng = group_names.size();
+        group_ptr.assign(ng + 1, 0);
+        for (size_t i = 0; i < n; ++i) ++group_ptr[gid[i] + 1];
+        for (size_t g = 0; g < ng; ++g) group_ptr[g + 1] += group_ptr[g];
+        group_members.resize(n);
+        std::vector<uint64_t> fill(group_ptr.begin(), group_ptr.end() - 1);
+        for (size_t i = 0; i < n; ++i) group_members[fill[gid[i]]++] = (uint32_t)i;
+    }
     std::vector<uint32_t> lhs, rhs;  // --pairs: the slots of the listed names, looked up before anything is sketched
     if (with_pairs) {
         std::unordered_map<std::string, uint32_t> slot_of;
@@ -1016,23 +1069,80 @@ static int dist_main(int argc, char **argv, bool by_seq = false)
         // read on all host threads into a staging matrix, upload in batches
         const size_t m = (size_t)1 << o.S, batch = std::max<size_t>(1, ((size_t)256 << 20) / m);
         std::vector<uint8_t> stage(std::min(n, batch) * m);
-        for (size_t b0 = 0; b0 < n; b0 += batch) {
-            const size_t b1 = std::min(n, b0 + batch);
+        // a file sketched at a higher precision than -S is folded on the device (dsh_upload_sketches_folded): its
+        // registers wait here until the batch is read, then go run by run of equal p.  At most 256 MiB of them are held: a
+        // batch ends before the file that would exceed that
+        std::vector<std::vector<uint8_t>> hi(std::min(n, batch));
+        std::vector<int> hi_p(std::min(n, batch));
+        std::vector<uint8_t> run;
+        for (size_t b0 = 0, b1; b0 < n; b0 = b1) {
+            b1 = std::min(n, b0 + batch);
+            std::atomic<size_t> held{0};
+            std::atomic<int64_t> cut{(int64_t)b1};
 #pragma omp parallel for schedule(dynamic, 16) num_threads(o.nthreads)
             for (int64_t i = (int64_t)b0; i < (int64_t)b1; ++i) {
+                if (i >= cut.load()) continue;  // behind a file that did not fit: the next batch
                 int p = 0;
                 std::vector<uint8_t> r;
                 if (read_hll(o.inpaths[i], r, p)) die("Could not read sketch %s", o.inpaths[i].c_str());
-                if (p != o.S) die("Sketch %s has p=%d but -S is %d", o.inpaths[i].c_str(), p, o.S);
-                std::memcpy(stage.data() + (size_t)(i - (int64_t)b0) * m, r.data(), m);
+                if (p < o.S) die("Sketch %s has p=%d but -S is %d", o.inpaths[i].c_str(), p, o.S);
+                hi_p[i - b0] = p;
+                if (p == o.S) {
+                    std::memcpy(stage.data() + (size_t)(i - (int64_t)b0) * m, r.data(), m);
+                } else if (held.fetch_add(r.size()) + r.size() > ((size_t)256 << 20) && i > (int64_t)b0) {
+                    for (int64_t c = cut.load(); i < c && !cut.compare_exchange_weak(c, i);) {}
+                } else {
+                    hi[i - b0].swap(r);
+                }
             }
-            DSH(ctx, dsh_upload_sketches(ctx, stage.data(), b0, b1 - b0));
+            b1 = (size_t)cut.load();
+            for (size_t i = b0; i < b1;) {
+                const int p = hi_p[i - b0];
+                const size_t mp = (size_t)1 << p, cap = std::max<size_t>(1, ((size_t)256 << 20) / mp);
+                size_t j = i + 1;
+                while (j < b1 && hi_p[j - b0] == p && j - i < cap) ++j;
+                if (p == o.S) {
+                    DSH(ctx, dsh_upload_sketches(ctx, stage.data() + (i - b0) * m, i, j - i));
+                } else {
+                    run.resize((j - i) * mp);
+                    for (size_t x = i; x < j; ++x) std::memcpy(run.data() + (x - i) * mp, hi[x - b0].data(), mp);
+                    DSH(ctx, dsh_upload_sketches_folded(ctx, run.data(), p, i, j - i));
+                }
+                i = j;
+            }
+            for (auto &h : hi) std::vector<uint8_t>().swap(h);
         }
     } else {
         fill_sketches(cf, o, /*write_files=*/o.cache != 0, false);
         ctx = cf.get();
     }
     if (g_timing) std::fprintf(stderr, "[timing] all sketches resident after %.3f s\n", now_s() - t_fill0);
+    if (with_groups) {
+        // the unions go into a device buffer that a second context takes as its sketch matrix; from here on the groups
+        // are the collection.  An asymmetric measure wants every reference once more as a query: the groups twice
+        const size_t ng = group_names.size(), copies = symmetric ? 1 : 2;
+        if (!symmetric) {
+            std::fprintf(stderr, "Note: No query files provided, but an asymmetric distance was requested. Switching to a query/reference format with all references as queries.\n");
+            const std::vector<uint32_t> once(group_members);
+            for (size_t g = 0; g < ng; ++g) {
+                group_names.push_back(group_names[g]);
+                group_ptr.push_back(group_ptr.back() + (group_ptr[g + 1] - group_ptr[g]));
+                group_members.insert(group_members.end(), once.begin() + (long)group_ptr[g], once.begin() + (long)group_ptr[g + 1]);
+            }
+            nq = ng;
+        }
+        void *d_union = nullptr;
+        if (hipSetDevice(o.device) != hipSuccess || hipMalloc(&d_union, std::max<size_t>((copies * ng) << o.S, 256)) != hipSuccess)
+            die("[dashing-amd] no device memory for the unions of %zu groups", ng);
+        DSH(ctx, dsh_union_groups_device(ctx, group_ptr.data(), group_members.data(), copies * ng, d_union));
+        dsh_ctx *gctx = nullptr;
+        if (int rc = dsh_create(o.device, &gctx)) die("[dashing-amd] dsh_create(device %d) = %d", o.device, rc);
+        DSH(gctx, dsh_attach_device_sketches(gctx, d_union, copies * ng, o.S));
+        dsh_destroy(ctx);
+        ctx = gctx;  // (the buffer lives as long as the process)
+        o.inpaths = group_names;
+        n = copies * ng;
+    }
     // sizes (src/sketch_and_cmp.h:372-385)
     std::vector<double> card(std::max<size_t>(n, 1));
     DSH(ctx, dsh_cardinalities(ctx, o.estim, card.data()));

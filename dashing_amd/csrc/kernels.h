@@ -206,6 +206,17 @@ hipError_t launch_pairs_finish(hipStream_t st, const void *hist, const uint32_t 
                                int p, int estim, const double *card, const PairsTypes &types, uint32_t n_types, double ksinv,
                                float *out, uint64_t out_stride);
 
+// derived sketches (kernels_derive.hip, derive.hip)
+// rows [n][2^ps] at src (any alignment) folded to [n][2^pd] at dst (any alignment), pd <= ps; *err (device, starts at ~0) =
+// min over the rows that hold a register above 64 - ps + 1 of row0 + row
+hipError_t launch_fold(hipStream_t st, const uint8_t *src, uint64_t n, int ps, int pd, uint64_t row0, uint8_t *dst,
+                       unsigned long long *err);
+// row v in [0, nv) = byte-wise max of the rows mem[ptr[v] .. ptr[v + 1]) of src (mem == nullptr: the rows ptr[v] .. ptr[v + 1)
+// themselves), written to row dst[v] of out_a, or with bit 31 of dst[v] set to row dst[v] & 0x7FFFFFFF of out_b
+// (dst == nullptr: row v of out_a).  src, out_b 16-byte aligned; out_a any alignment.
+hipError_t launch_union_groups(hipStream_t st, const uint8_t *src, int p, const uint64_t *ptr, const uint32_t *mem,
+                               const uint32_t *dst, uint64_t nv, uint8_t *out_a, uint8_t *out_b);
+
 // in-order upload of a small page-locked host buffer by a kernel (no runtime copy on the ctx stream)
 hipError_t launch_upload(hipStream_t st, void *dst, const void *src_pinned, size_t bytes);
 

@@ -60,7 +60,8 @@ typedef struct dsh_ctx dsh_ctx;
  * shifted arguments: compare with dsh_abi_version() once at start-up.  (A bounds array handed to a function that now
  * parses a row-set table is refused, not over-read: its first word, 0, is not a valid world.)
  * Entry points that were only ADDED since leave the number alone and are detected by symbol (dlsym):
- * dsh_dist_threshold, dsh_dist_threshold_device, dsh_dist_rect_threshold. */
+ * dsh_dist_threshold, dsh_dist_threshold_device, dsh_dist_rect_threshold, dsh_dist_pairs*, dsh_fold*,
+ * dsh_upload_sketches_folded*, dsh_union_groups*. */
 #define DSH_ABI_VERSION 7
 int dsh_abi_version(void);
 
@@ -315,6 +316,45 @@ int dsh_dist_pairs_device(dsh_ctx *ctx, int estim, const int *result_types, uint
 int dsh_dist_pairs_csr(dsh_ctx *ctx, int estim, const int *result_types, uint32_t n_types, int k, uint64_t row_begin,
                        uint64_t rows, const uint64_t *row_ptr, const uint32_t *col, float *out);
 
+/* ---- derived sketches: fold to a lower p, union by groups ------------------------------------------
+ * Replaces hll_t::compress (fold to a lower precision) and hll_t::operator+= (register-wise maximum) of the reference's
+ * sketch library, as src/dashing.cpp:570-590 and src/union.cpp:33-58 use them one file at a time on the host: here they
+ * make NEW sketch rows out of resident ones on the device, so that a matrix sketched once at a high p is compared at a
+ * cheaper one, and a collection is collapsed into pan-sketches, without a trip over PCIe.  The result of a *_device form
+ * is a plain [rows][2^p] matrix that dsh_attach_device_sketches takes as it is (16-byte aligned for that).
+ *   Fold.  d = p - new_p; register j of a folded row is the maximum over the source registers idx in [j << d, (j+1) << d)
+ *     of: 0 for an empty register, v + d where low = idx & (2^d - 1) is 0, else clz_d(low) + 1 (leading zeros of low in
+ *     its d-bit field) -- what sketching the same input at new_p would have given.  new_p == p is a copy.
+ *   Union.  out[g] = byte-wise max of the resident rows members[group_ptr[g] .. group_ptr[g+1]); an empty group gives an
+ *     all-zero row; a slot may repeat inside a group and appear in several.  group_ptr [n_groups + 1] uint64 and members
+ *     uint32 are HOST arrays in both forms (the call copies them to the device).
+ *   Execution.  Synchronous, on the ctx stream; the *_device forms wait for the device once, at their end.
+ *   Host forms.  Rows travel through bounded scratch: chunks of at most "derive_chunk_bytes" of source rows (option,
+ *     default 256 MiB, at least one row; no result depends on it), so a call of any size works.  Page-locked memory from
+ *     dsh_alloc_host makes the copies DMA; any host pointer works.  (dsh_union_groups stages its whole result.)
+ *   No derived state touched.  dsh_fold* and dsh_union_groups* write only the caller's buffer (any alignment) and touch
+ *     none of the context's derived state: a dense call before and after gives the same bytes and builds no new layout.
+ *   dsh_upload_sketches_folded* writes slots [first_slot, first_slot + n) of a matrix from dsh_sketches_alloc
+ *     (overwritten, other slots untouched) and invalidates exactly as dsh_upload_sketches does; with src_p == p it equals
+ *     dsh_upload_sketches byte for byte.  d_regs: [n][2^src_p], any alignment (16-byte aligned is the fast path).
+ *   Validation.  Fold and the folded upload fail with DSH_EINVAL and a message that names the sketch (slot number) when a
+ *     source register exceeds 64 - src_p + 1, found on the device while the rows stream by; the output is then
+ *     unspecified.  Union does not judge registers.
+ *   Argument errors, before anything is enqueued: DSH_EINVAL for slots out of range, new_p outside [4, p], src_p outside
+ *     [p, 24], a group_ptr that decreases or a member >= n; DSH_ESTATE without sketches (the folded upload: without
+ *     dsh_sketches_alloc).  n == 0 and n_groups == 0 succeed and write nothing.
+ *   Cost.  Pure streaming: fold moves 1 + 2^-d bytes per source byte, union 1 + groups/members; a device-to-device copy
+ *     of the same source moves 2.  Not yet measured on the device (tools/bench_derive.py does it). */
+/* rows [first_slot, first_slot+n) of the resident matrix folded to new_p (4 <= new_p <= p): out [n][2^new_p] */
+int dsh_fold(dsh_ctx *ctx, uint64_t first_slot, uint64_t n, int new_p, uint8_t *regs_out);
+int dsh_fold_device(dsh_ctx *ctx, uint64_t first_slot, uint64_t n, int new_p, void *d_out);
+/* rows at src_p >= the context's p, folded on the device INTO slots [first_slot, first_slot+n) (overwritten) */
+int dsh_upload_sketches_folded(dsh_ctx *ctx, const uint8_t *regs, int src_p, uint64_t first_slot, uint64_t n);
+int dsh_upload_sketches_folded_device(dsh_ctx *ctx, const void *d_regs, int src_p, uint64_t first_slot, uint64_t n);
+/* out[g] = max over members[group_ptr[g] .. group_ptr[g+1]) of the resident rows; group_ptr, members on the HOST */
+int dsh_union_groups(dsh_ctx *ctx, const uint64_t *group_ptr, const uint32_t *members, uint64_t n_groups, uint8_t *regs_out);
+int dsh_union_groups_device(dsh_ctx *ctx, const uint64_t *group_ptr, const uint32_t *members, uint64_t n_groups, void *d_out);
+
 /* ---- multi-GPU shards of the full triangle ------------------------------------------------
  * Every rank holds all sketches (dsh_upload/attach) and computes one shard; no collective is
  * needed inside the compare.  Internally the plane matrix is laid out in (threshold, min value)
@@ -525,6 +565,8 @@ int dsh_finalize_phase_cycles(dsh_ctx *ctx, uint64_t *out16);
  *   resources     "cum_budget_bytes"        scratch for the pair counts C(v) (default 8 GiB): larger jobs run in bands
  *                 "knn_square_budget_bytes" all-vs-all dsh_knn keeps an n x n float matrix in HBM up to this size (96 GiB)
  *                 "threshold_band_bytes"    dsh_dist_threshold* computes bands of whole rows of at most this much float32 (1 GiB)
+ *                 "derive_chunk_bytes"      the host forms of dsh_fold / dsh_upload_sketches_folded move at most this many bytes
+ *                                           of source rows per step (256 MiB; at least one row)
  *   layout        "sort"                    -1 auto | 0 | 1: key-ordered plane columns (0 = identity: the slow, simple layout)
  *                 "range_sort_min_rows"     row ranges shorter than this keep the cached identity layout (default 1024)
  *                 "emax" / "elow"           caps of the listed upper / lower register tail, 0..255, -1 auto (per precision);
