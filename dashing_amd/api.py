@@ -30,6 +30,7 @@ SYMBOLS = [
     "dsh_exchange_collect_async", "dsh_exchange_place_device", "dsh_exchange_probe_parts_async", "dsh_diag_spin_start", "dsh_diag_spin_stop", "dsh_abi_version", "dsh_preload", "dsh_comm_unique_id", "dsh_comm_init", "dsh_comm_destroy", "dsh_comm_rank", "dsh_collect_spans", "dsh_collect_spans_async",
     "dsh_allgather_device", "dsh_dist_collect", "dsh_range_parts", "dsh_dist_rows_parts_device_async", "dsh_collect_parts_async",
     "dsh_dist_rect", "dsh_knn", "dsh_dist_threshold", "dsh_dist_threshold_device", "dsh_dist_rect_threshold", "dsh_dist_pairs", "dsh_dist_pairs_device", "dsh_dist_pairs_csr",
+    "dsh_cluster_threshold", "dsh_cluster_threshold_device", "dsh_cluster_pairs", "dsh_cluster_csr",
     "dsh_fold", "dsh_fold_device", "dsh_upload_sketches_folded", "dsh_upload_sketches_folded_device", "dsh_union_groups", "dsh_union_groups_device", "dsh_shard_plan", "dsh_dist_shard_device", "dsh_unpermute_device", "dsh_unpermute_staged_device", "dsh_unpermute_blocks_device", "dsh_tri_span", "dsh_tri_index", "dsh_partition_rows", "dsh_balance_rows", "dsh_balance_rowsets", "dsh_rowsets_from_bounds", "dsh_rowsets_rank", "dsh_alloc_host", "dsh_free_host",
     "dsh_set_profiling", "dsh_last_kernel_ms", "dsh_last_part_info", "dsh_finalize_phase_cycles", "dsh_set_option", "dsh_get_info", "dsh_stream",
 ]
@@ -155,11 +156,15 @@ def load_library():
     lib.dsh_dist_pairs.argtypes = [vp, i32, vp, C.c_uint32, i32, vp, vp, u64, vp]
     lib.dsh_dist_pairs_device.argtypes = [vp, i32, vp, C.c_uint32, i32, vp, vp, u64, vp]
     lib.dsh_dist_pairs_csr.argtypes = [vp, i32, vp, C.c_uint32, i32, u64, u64, vp, vp, vp]
-    # derived sketches: bound by name, so that a library built before they existed still loads (calling one then fails)
+    # derived sketches and clusters: bound by name, so that a library built before they existed still loads (calling one then fails)
     for name, args in (("dsh_fold", [vp, u64, u64, i32, vp]), ("dsh_fold_device", [vp, u64, u64, i32, vp]),
                        ("dsh_upload_sketches_folded", [vp, vp, i32, u64, u64]),
                        ("dsh_upload_sketches_folded_device", [vp, vp, i32, u64, u64]),
-                       ("dsh_union_groups", [vp, vp, vp, u64, vp]), ("dsh_union_groups_device", [vp, vp, vp, u64, vp])):
+                       ("dsh_union_groups", [vp, vp, vp, u64, vp]), ("dsh_union_groups_device", [vp, vp, vp, u64, vp]),
+                       ("dsh_cluster_threshold", [vp, i32, i32, i32, C.c_float, vp, C.POINTER(u64)]),
+                       ("dsh_cluster_threshold_device", [vp, i32, i32, i32, C.c_float, vp, C.POINTER(u64)]),
+                       ("dsh_cluster_pairs", [vp, u64, vp, vp, u64, vp, vp, C.POINTER(u64)]),
+                       ("dsh_cluster_csr", [vp, u64, u64, u64, vp, vp, vp, vp, C.POINTER(u64)])):
         fn = getattr(lib, name, None)
         if fn is not None:
             fn.argtypes = args
@@ -691,6 +696,60 @@ class Context:
         self._ck(self._lib.dsh_dist_pairs_csr(self._h, estim, ty.ctypes.data, ty.size, k, row_begin, rows, row_ptr.ctypes.data,
                                               col.ctypes.data, out.ctypes.data))
         return out
+
+    # ---- clusters: connected components on the device (include/dashing_hip.h has the contract)
+    def cluster_threshold(self, threshold, estim=ESTIM_ERTL_MLE, result_type=JI, k=31):
+        """(labels uint32 [n], n_clusters): labels[x] = the smallest slot of x's connected component in the graph of the
+        hits of dist_threshold(threshold, ...) over all rows"""
+        labels = np.zeros(self.n, np.uint32)
+        nc = C.c_uint64()
+        self._ck(self._derive("dsh_cluster_threshold")(self._h, estim, result_type, k, threshold, labels.ctypes.data, C.byref(nc)))
+        return labels, int(nc.value)
+
+    def cluster_threshold_device(self, labels_ptr, threshold, estim=ESTIM_ERTL_MLE, result_type=JI, k=31):
+        """labels into the caller's device buffer (uint32 [n]); returns n_clusters"""
+        nc = C.c_uint64()
+        self._ck(self._derive("dsh_cluster_threshold_device")(self._h, estim, result_type, k, threshold, C.c_void_p(labels_ptr), C.byref(nc)))
+        return int(nc.value)
+
+    @staticmethod
+    def _labels_in(n_nodes, labels_in):
+        if labels_in is None:
+            return None
+        li = np.ascontiguousarray(labels_in, np.uint32).reshape(-1)
+        if li.size != n_nodes:
+            raise ValueError("labels_in holds one label per node")
+        return li
+
+    def cluster_pairs(self, n_nodes, lhs, rhs, labels_in=None):
+        """(labels, n_clusters) of the graph on n_nodes nodes with the edges (lhs[x], rhs[x]); labels_in: an earlier
+        labelling to continue from.  Needs no sketches."""
+        lhs = np.ascontiguousarray(lhs, np.uint32).reshape(-1)
+        rhs = np.ascontiguousarray(rhs, np.uint32).reshape(-1)
+        if lhs.size != rhs.size:
+            raise ValueError("lhs and rhs differ in length")
+        li = self._labels_in(n_nodes, labels_in)
+        labels = np.zeros(max(int(n_nodes), 0), np.uint32)
+        nc = C.c_uint64()
+        self._ck(self._derive("dsh_cluster_pairs")(self._h, n_nodes, lhs.ctypes.data, rhs.ctypes.data, lhs.size,
+                                                   None if li is None else li.ctypes.data, labels.ctypes.data, C.byref(nc)))
+        return labels, int(nc.value)
+
+    def cluster_csr(self, n_nodes, row_ptr, col, row_begin=0, labels_in=None):
+        """as cluster_pairs for the hits of dist_threshold / dist_rect_threshold: hit h of row r is the edge
+        (row_begin + r, col[h])"""
+        row_ptr = np.ascontiguousarray(row_ptr, np.uint64).reshape(-1)
+        col = np.ascontiguousarray(col, np.uint32).reshape(-1)
+        if row_ptr.size < 1:
+            raise ValueError("row_ptr holds rows + 1 entries")
+        if int(row_ptr[-1]) > int(row_ptr[0]) and int(row_ptr[-1]) > col.size:
+            raise ValueError("col is shorter than row_ptr says")
+        li = self._labels_in(n_nodes, labels_in)
+        labels = np.zeros(max(int(n_nodes), 0), np.uint32)
+        nc = C.c_uint64()
+        self._ck(self._derive("dsh_cluster_csr")(self._h, n_nodes, row_begin, row_ptr.size - 1, row_ptr.ctypes.data, col.ctypes.data,
+                                                 None if li is None else li.ctypes.data, labels.ctypes.data, C.byref(nc)))
+        return labels, int(nc.value)
 
     # ---- multi-GPU shards (sorted-order spans + one un-permute)
     def shard_plan(self, nshards, estim=ESTIM_ERTL_MLE):

@@ -5,6 +5,7 @@
 //   knn.hip       dsh_knn
 //   threshold.hip dsh_dist_threshold*, dsh_dist_rect_threshold (values that pass a threshold, as CSR)
 //   pairs.hip     dsh_dist_pairs* (values of an explicit list of pairs, the direct form)
+//   cluster.hip   dsh_cluster_* (connected components at a threshold, or of a caller's graph)
 //   derive.hip    dsh_fold*, dsh_upload_sketches_folded*, dsh_union_groups* (new sketches out of resident ones)
 //   exchange.hip  RCCL: dsh_comm_*, dsh_collect_*, dsh_allgather_device, dsh_dist_collect
 //   plan.cpp      the pure-host planner (layout, tiles, bands, parts, work items, row partitions)
@@ -183,6 +184,10 @@ struct dsh_ctx {
     hipEvent_t ev_pairs = nullptr;      // its upload has run
     int pairs_card_estim = -1;          // estimator pairs_card was computed under (-1: none), dropped by invalidate()
     uint64_t pairs_chunk = 1u << 18;    // option: pairs per launch (scratch is 64 counters per pair of a chunk)
+    // dsh_cluster_* (cluster.hip): parent[n], the root count + error word, a chunk of the caller's edges (or the CSR's row
+    // pointer and a chunk of its columns), a seed labelling and the labels of the host forms
+    DevBuf cc_parent, cc_state, cc_lhs, cc_rhs, cc_rowptr, cc_seed, cc_labels;
+    uint64_t cluster_chunk = 1u << 20;  // option: edges per launch of dsh_cluster_pairs / dsh_cluster_csr
     // dsh_fold*, dsh_upload_sketches_folded*, dsh_union_groups* (derive.hip): the error word, a chunk of source rows or of
     // folded rows on its way through the device, the groups' CSR and the partial unions of groups cut into chunks
     DevBuf derive_err, derive_stage, derive_ptr, derive_mem, derive_dst, derive_part[2], derive_out;

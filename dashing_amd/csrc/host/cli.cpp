@@ -92,6 +92,12 @@ static void usage(const char *sub)
             "                           the distances.  Text: '#Threshold<TAB>measure<TAB>op<TAB>FLOAT', then name_i<TAB>name_j<TAB>value\n"
             "                           per hit; -b: u64 n, u64 nnz, u64 row_ptr[n+1], u32 col[nnz], f32 val[nnz]; with -Q one row\n"
             "                           per query.  Not with --nearest-neighbors, -U, -T or several devices.\n"
+            "  --cluster FLOAT          emit the single-linkage clusters at FLOAT instead of distances: the connected components of\n"
+            "                           the graph whose edges are --threshold FLOAT's pairs, computed on the device.  Text:\n"
+            "                           '#Cluster<TAB>measure<TAB>op<TAB>FLOAT', then name<TAB>cluster<TAB>representative per input in\n"
+            "                           output order, clusters numbered from 0 by their first member, which represents them;\n"
+            "                           -b: u64 n, u64 n_clusters, u32 labels[n] (label = slot of the representative).  Not with\n"
+            "                           --threshold, --nearest-neighbors, --pairs, -Q, -U, -T or several devices.\n"
             "  --pairs FILE             emit only the pairs FILE lists, one per line as name_a<TAB>name_b (input names as given\n"
             "                           here; record names with dist_by_seq), in FILE's order: name_a<TAB>name_b and one value per\n"
             "                           measure.  --measures LIST: comma-separated from MASH_DIST, JI, SIZES, FULL_MASH_DIST,\n"
@@ -114,6 +120,8 @@ struct Opts {
     unsigned nneighbors = 0;  // --nearest-neighbors
     bool has_threshold = false;  // --threshold: only the pairs that pass, as (name, name, value) lines or CSR (-b)
     float threshold = 0.f;
+    bool has_cluster = false;  // --cluster: the connected components of --threshold's graph (dsh_cluster_threshold)
+    float cluster_t = 0.f;
     std::string groups_file;  // --groups FILE: the unions of named groups are compared instead of the inputs (dsh_union_groups)
     std::string pairs_file, measures;  // --pairs FILE [--measures LIST]: only the listed pairs (dsh_dist_pairs)
     int rccl = 0;             // --rccl: deliver the rows through the RCCL exchange of the C-ABI even with one device
@@ -122,7 +130,7 @@ struct Opts {
     std::vector<std::string> inpaths, querypaths;
 };
 
-enum { OPT_PRESKETCHED = 1000, OPT_AVOID_SORT, OPT_DEVICE, OPT_NPERBATCH, OPT_NN, OPT_NGPUS, OPT_DEVICES, OPT_RCCL, OPT_THRESHOLD, OPT_PAIRS, OPT_MEASURES, OPT_GROUPS, OPT_UNSUPPORTED };
+enum { OPT_PRESKETCHED = 1000, OPT_AVOID_SORT, OPT_DEVICE, OPT_NPERBATCH, OPT_NN, OPT_NGPUS, OPT_DEVICES, OPT_RCCL, OPT_THRESHOLD, OPT_CLUSTER, OPT_PAIRS, OPT_MEASURES, OPT_GROUPS, OPT_UNSUPPORTED };
 
 static Opts parse(int argc, char **argv, bool is_dist)
 {
@@ -149,6 +157,7 @@ static Opts parse(int argc, char **argv, bool is_dist)
         {"use-bloom-filter", no_argument, nullptr, OPT_UNSUPPORTED}, {"use-nthash", no_argument, nullptr, OPT_UNSUPPORTED},
         {"use-cyclic-hash", no_argument, nullptr, OPT_UNSUPPORTED}, {"countmin", no_argument, nullptr, OPT_UNSUPPORTED},
         {"nearest-neighbors", required_argument, nullptr, OPT_NN}, {"threshold", required_argument, nullptr, OPT_THRESHOLD},
+        {"cluster", required_argument, nullptr, OPT_CLUSTER},
         {"pairs", required_argument, nullptr, OPT_PAIRS}, {"groups", required_argument, nullptr, OPT_GROUPS}, {"measures", required_argument, nullptr, OPT_MEASURES},
         // second arm of result_cmp (src/dashing.h:577-588); flag numbers as in DIST_LONG_OPTS
         {"sizes", no_argument, nullptr, 'Z'}, {"containment-index", no_argument, nullptr, 131},
@@ -218,6 +227,13 @@ static Opts parse(int argc, char **argv, bool is_dist)
             o.threshold = std::strtof(optarg, &end);
             if (end == optarg || *end || o.threshold != o.threshold) die("--threshold needs a number, got '%s'", optarg);
             o.has_threshold = true;
+            break;
+        }
+        case OPT_CLUSTER: {
+            char *end = nullptr;
+            o.cluster_t = std::strtof(optarg, &end);
+            if (end == optarg || *end || o.cluster_t != o.cluster_t) die("--cluster needs a number, got '%s'", optarg);
+            o.has_cluster = true;
             break;
         }
         case OPT_PAIRS: o.pairs_file = optarg; break;
@@ -954,6 +970,15 @@ static int dist_main(int argc, char **argv, bool by_seq = false)
         if (o.fmt == FULL_TSV) die("--threshold does not go with -T: a full TSV matrix is dense.");
         if (o.devices.size() > 1) die("--threshold runs on one device: --ngpus / --devices are not supported.");
     }
+    if (o.has_cluster) {
+        if (o.has_threshold) die("--cluster does not go with --threshold: choose the clusters or the pairs.");
+        if (o.nneighbors) die("--cluster does not go with --nearest-neighbors: choose one selection.");
+        if (!o.pairs_file.empty()) die("--cluster does not go with --pairs: the clusters are those of all pairs.");
+        if (!o.querypaths.empty()) die("--cluster does not go with -Q: every input is clustered with every other.");
+        if (o.fmt == UPPER_TRIANGULAR) die("--cluster does not go with -U: the output is one line per input.");
+        if (o.fmt == FULL_TSV) die("--cluster does not go with -T: the output is one line per input.");
+        if (o.devices.size() > 1 || o.rccl) die("--cluster runs on one device: --ngpus / --devices are not supported.");
+    }
     static const char *const kMeasureNames[9] = {"MASH_DIST", "JI", "SIZES", "FULL_MASH_DIST", "FULL_CONTAINMENT_DIST", "CONTAINMENT_INDEX",
                                                  "CONTAINMENT_DIST", "SYMMETRIC_CONTAINMENT_INDEX", "SYMMETRIC_CONTAINMENT_DIST"};
     const bool with_pairs = !o.pairs_file.empty();
@@ -991,7 +1016,8 @@ static int dist_main(int argc, char **argv, bool by_seq = false)
     if (!o.out_sizes.empty() && !(ofp = std::fopen(o.out_sizes.c_str(), "w"))) die("Could not open file at %s for writing.", o.out_sizes.c_str());
     if (!o.out_dists.empty() && !(pairofp = std::fopen(o.out_dists.c_str(), "wb"))) die("Could not open file at %s for writing.", o.out_dists.c_str());
     // asymmetric measure without -Q: all references are also the queries (src/distmain.cpp:120-125)
-    const bool symmetric = !(o.result_type == 4 || o.result_type == 5 || o.result_type == 6);  // src/dashing.h:389-399
+    // (--cluster tests every pair once, in the triangle's orientation: no query/reference format for it)
+    const bool symmetric = o.has_cluster || !(o.result_type == 4 || o.result_type == 5 || o.result_type == 6);  // src/dashing.h:389-399
     if (o.querypaths.empty() && !symmetric && !with_pairs && !with_groups) {  // (a pair list names its own pairs, each in one orientation; the groups take their turn below)
         o.querypaths = o.inpaths;
         std::fprintf(stderr, "Note: No query files provided, but an asymmetric distance was requested. Switching to a query/reference format with all references as queries.\n");
@@ -1163,6 +1189,32 @@ static int dist_main(int argc, char **argv, bool by_seq = false)
             for (size_t t = 0; t < nt; ++t) s.append(num, (size_t)std::snprintf(num, sizeof num, "\t%.6g", (double)vals[t * np + x]));  // --threshold's number format
             s += '\n';
             std::fwrite(s.data(), 1, s.size(), pairofp);
+        }
+    } else if (o.has_cluster) {  // the connected components of the pairs that pass (dsh_cluster_threshold): no pair leaves the device
+        std::vector<uint32_t> labels(std::max<size_t>(n, 1));
+        uint64_t n_clusters = 0;
+        DSH(ctx, dsh_cluster_threshold(ctx, o.estim, o.result_type, o.k, o.cluster_t, labels.data(), &n_clusters));
+        if (o.fmt == BINARY) {
+            const uint64_t hdr[2] = {(uint64_t)n, n_clusters};
+            if (std::fwrite(hdr, sizeof(uint64_t), 2, pairofp) != 2 || std::fwrite(labels.data(), sizeof(uint32_t), n, pairofp) != n)
+                die("Error writing to binary file");
+        } else {
+            const bool dist = o.result_type == 0 || o.result_type == 3 || o.result_type == 4 || o.result_type == 6 || o.result_type == 8;
+            std::fprintf(pairofp, "#Cluster\t%s\t%s\t%.6g\n", kMeasureNames[o.result_type], dist ? "<=" : ">=", (double)o.cluster_t);  // --threshold's number format
+            // clusters are numbered by ascending representative: a label is its cluster's first member, so the numbers
+            // are handed out in one pass
+            std::vector<uint32_t> index(std::max<size_t>(n, 1));
+            uint32_t next = 0;
+            std::string s;
+            char num[32];
+            for (size_t x = 0; x < n; ++x) {
+                if (labels[x] == x) index[x] = next++;
+                s = o.inpaths[x];
+                s.append(num, (size_t)std::snprintf(num, sizeof num, "\t%u\t", index[labels[x]]));
+                s += o.inpaths[labels[x]];
+                s += '\n';
+                std::fwrite(s.data(), 1, s.size(), pairofp);
+            }
         }
     } else if (o.has_threshold) {  // only the pairs that pass (dsh_dist_threshold / dsh_dist_rect_threshold): no dense matrix
         if (nq >= n && nq) die("Wrong number of query/references. (ip size: %zu, nq: %zu", n, nq);

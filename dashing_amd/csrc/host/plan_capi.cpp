@@ -1,7 +1,8 @@
 // plan_capi.cpp -- CPU test hook of the pure-host planner (../plan.cpp): builds a layout and a pair plan for given
 // per-sketch keys exactly as engine.hip does and checks the plan against its contract, so the schedule that replaces
 // dist_loop / perform_core_op (src/sketch_and_cmp.h:785-880, :699-710) is unit-tested without a GPU
-// (tests/test_plan.py).  Built into libdashing_host.so; not part of the GPU C-ABI.
+// (tests/test_plan.py).  Also the sequential build of the clusters' union-find (dsh_plan_uf_labels, at the end).  Built into
+// libdashing_host.so; not part of the GPU C-ABI.
 #include <algorithm>
 #include <cstdarg>
 #include <cstdio>
@@ -9,6 +10,7 @@
 #include <vector>
 
 #include "../plan.h"
+#include "../uf.h"
 
 using namespace dsh;
 using namespace dsh::plan;
@@ -374,5 +376,27 @@ int dshh_plan_check_rowset(uint64_t n, const uint32_t *keys, const uint64_t *tab
 
 // first row of the second run of a row-sorted range (plan::rowsorted_split), re when the range stays one run
 uint64_t dshh_rowsorted_split(uint64_t n, uint64_t rb, uint64_t re) { return rowsorted_split(n, rb, re); }
+
+// the union-find of the threshold clusters (../uf.h, the code the device kernels compile) run sequentially: labels_out[x] =
+// the smallest node of x's component in the graph of the n_edges edges (lhs[e], rhs[e]).  Returns 0, -1 for an edge that
+// names a node >= n, and the step-bound code (1 find, 2 hook) when a loop overran step_cap -- the give-up path, which the
+// device kernels must never reach, is tested here (tests/test_cluster_host.py).
+int dsh_plan_uf_labels(uint64_t n, const uint32_t *lhs, const uint32_t *rhs, uint64_t n_edges, uint32_t step_cap, uint32_t *labels_out)
+{
+    if (n > 0xFFFFFFFFull) return -1;
+    std::vector<uint32_t> parent(n);
+    for (uint64_t x = 0; x < n; ++x) parent[x] = (uint32_t)x;
+    for (uint64_t e = 0; e < n_edges; ++e) {
+        if (lhs[e] >= n || rhs[e] >= n) return -1;
+        uint32_t why = 0;
+        if (uf_unite<UfPlain>(parent.data(), lhs[e], rhs[e], step_cap, &why) == kUfOverrun) return (int)why;
+    }
+    for (uint64_t x = 0; x < n; ++x) {
+        const uint32_t l = uf_find<UfPlain>(parent.data(), (uint32_t)x, step_cap);
+        if (l == kUfOverrun) return (int)kUfErrFind;
+        labels_out[x] = l;
+    }
+    return 0;
+}
 
 }  // extern "C"

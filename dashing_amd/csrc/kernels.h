@@ -188,6 +188,22 @@ hipError_t launch_thr_scan(hipStream_t st, const uint32_t *cnt, uint64_t m, uint
 hipError_t launch_thr_emit(hipStream_t st, const float *vals, const ThrRows &g, float t, int descending, const uint64_t *off,
                            uint64_t sub, uint64_t cap, uint32_t *col, float *val);
 
+// threshold clusters (kernels_cluster.hip, cluster.hip): a union-find over parent[n] with parent[x] <= x (uf.h).  cap bounds
+// every loop (n + 1); err is one device word that a step-bound overrun sets (it starts at 0)
+hipError_t launch_cc_init(hipStream_t st, uint32_t *parent, uint64_t n);
+hipError_t launch_cc_seed(hipStream_t st, uint32_t *parent, const uint32_t *labels_in, uint64_t n, uint32_t cap, uint32_t *err);
+hipError_t launch_cc_edges(hipStream_t st, uint32_t *parent, const uint32_t *lhs, const uint32_t *rhs, uint64_t n_edges, uint64_t n,
+                           uint32_t cap, uint32_t *err);
+// hits [h0, h0 + cnt) of a CSR (row_ptr [rows + 1] whole on the device, counted from 0; col = the columns of THESE hits):
+// hit h of row r unites row_begin + r with its column
+hipError_t launch_cc_csr(hipStream_t st, uint32_t *parent, const uint64_t *row_ptr, uint64_t rows, uint64_t row_begin,
+                         const uint32_t *col, uint64_t h0, uint64_t cnt, uint64_t n, uint32_t cap, uint32_t *err);
+// a band of triangle rows as launch_thr_count takes it: every passing value unites its row and its column
+hipError_t launch_cc_band(hipStream_t st, const float *vals, const ThrRows &g, float t, int descending, uint32_t *parent, uint32_t cap,
+                          uint32_t *err);
+// labels[x] = root of x (the smallest member of its component), *n_roots += the roots (the caller zeroes it)
+hipError_t launch_cc_labels(hipStream_t st, uint32_t *parent, uint64_t n, uint32_t cap, uint32_t *labels, uint64_t *n_roots, uint32_t *err);
+
 // explicit pair lists (kernels_pairs.hip, pairs.hip): histograms are [cnt][64] counters, uint16 for p <= kPairsMaxP16
 // (a bin holds at most 2^p), uint32 above
 constexpr int kPairsMaxP16 = 15;

@@ -61,7 +61,8 @@ typedef struct dsh_ctx dsh_ctx;
  * parses a row-set table is refused, not over-read: its first word, 0, is not a valid world.)
  * Entry points that were only ADDED since leave the number alone and are detected by symbol (dlsym):
  * dsh_dist_threshold, dsh_dist_threshold_device, dsh_dist_rect_threshold, dsh_dist_pairs*, dsh_fold*,
- * dsh_upload_sketches_folded*, dsh_union_groups*. */
+ * dsh_upload_sketches_folded*, dsh_union_groups*, dsh_cluster_threshold, dsh_cluster_threshold_device, dsh_cluster_pairs,
+ * dsh_cluster_csr. */
 #define DSH_ABI_VERSION 7
 int dsh_abi_version(void);
 
@@ -355,6 +356,54 @@ int dsh_upload_sketches_folded_device(dsh_ctx *ctx, const void *d_regs, int src_
 int dsh_union_groups(dsh_ctx *ctx, const uint64_t *group_ptr, const uint32_t *members, uint64_t n_groups, uint8_t *regs_out);
 int dsh_union_groups_device(dsh_ctx *ctx, const uint64_t *group_ptr, const uint32_t *members, uint64_t n_groups, void *d_out);
 
+/* ---- clusters at a threshold: connected components on the device --------------------------------------
+ * Replaces what a dereplication or clustering client does with the hits of dsh_dist_threshold*: build the graph whose
+ * edges are the passing pairs and read off its connected components (single linkage) with a union-find on the host.  At
+ * 100 000 sketches a loose threshold gives 10^8 to 10^9 hits -- gigabytes of col / val that exist only to be united; here
+ * they are united where they are computed and `n` labels leave the device.
+ *   The result.  Let G be the graph on the slots 0..n-1 whose edges are exactly the hits of
+ *     dsh_dist_threshold(ctx, estim, result_type, k, 0, n, threshold, ...): the same float32 values, the same predicate
+ *     (v >= threshold for the similarity forms, v <= threshold for the *_DIST forms, NaN never) and, for the asymmetric
+ *     measures, the ONE orientation of the triangle.  labels[x] is the smallest slot of the connected component of x;
+ *     *n_clusters is the number of x with labels[x] == x.  This has one answer: it depends on no band size, launch
+ *     geometry or order of arrival of atomics, and the same call gives the same bytes.
+ *   How.  A union-find over parent[n] in device memory with parent[x] <= x at all times; its only writes are the hook
+ *     (compare-and-swap of a root under a SMALLER root) and path shortening (atomic minimum with an ancestor), so the
+ *     root a component ends with is its smallest member and no renumbering pass exists.  Every loop of the kernels counts
+ *     its steps against n + 1; an overrun -- unreachable while the invariant holds -- fails the call with DSH_EIO and the
+ *     message "internal: union-find step bound exceeded" instead of hanging the device.
+ *   dsh_cluster_threshold         labels_out: host uint32 [n].  Bands of whole rows as dsh_dist_threshold ("threshold_band_bytes",
+ *                                 at most 2^20 rows), computed by the dense path into a library-owned buffer and walked once;
+ *                                 no hit is written, no host wait between bands, one wait at the end.  The effects on the
+ *                                 context's cached state are exactly those of dsh_dist_threshold on rows [0, n): the dense
+ *                                 calls before and after give the same bytes.
+ *   dsh_cluster_threshold_device  d_labels: caller-owned DEVICE uint32 [n]; exactly n labels are written.
+ *   dsh_cluster_pairs             the components of a caller's graph on n_nodes nodes (n_nodes is the caller's choice: no
+ *                                 sketches are needed, only the stream and scratch): edges (lhs[x], rhs[x]) in host memory, in
+ *                                 any order, self loops and repeated edges legal.  labels_in NULL, or [n_nodes]: an earlier
+ *                                 labelling to continue from (x starts united with labels_in[x]) -- how the hits of several
+ *                                 row ranges, ranks or calls are merged: pass the labels_out of one call to the next.
+ *   dsh_cluster_csr               the same for a CSR as dsh_dist_threshold* / dsh_dist_rect_threshold write it: hit h of row r
+ *                                 (row_ptr[r] <= h < row_ptr[r + 1]) is the edge (row_begin + r, col[h]).
+ *   The edge list is worked off in chunks of "cluster_chunk" edges (option, default 2^20; no result depends on it): device
+ *     scratch is 8 bytes per edge of one chunk (CSR: 4, and 8 per row) whatever the length of the list.
+ *   Errors, before anything is enqueued: DSH_EINVAL for a node, col or labels_in entry >= n_nodes, a row_ptr that decreases,
+ *     rows outside [0, n_nodes) and n_nodes (or n) > 2^32 - 1; DSH_ESTATE for the threshold forms without sketches.
+ *     n == 0, n < 2, n_pairs == 0 and rows == 0 succeed; a NaN threshold gives n singletons.
+ *   Synchronous, on the ctx stream.  Cost model: the dense path's cost for the triangle plus ONE read of
+ *     each band (4 bytes per pair) and two small reads of parent[] per hit; dsh_dist_threshold_device + dsh_cluster_csr
+ *     reads each band twice and writes 8 bytes per hit.  Not yet measured on the device (tools/bench_cluster.py does it).
+ *   Not built: a multi-GPU form (merge per-rank labels with dsh_cluster_pairs' labels_in), clusters of a rectangle, and
+ *     linkages other than single. */
+int dsh_cluster_threshold(dsh_ctx *ctx, int estim, int result_type, int k, float threshold, uint32_t *labels_out,
+                          uint64_t *n_clusters);
+int dsh_cluster_threshold_device(dsh_ctx *ctx, int estim, int result_type, int k, float threshold, void *d_labels,
+                                 uint64_t *n_clusters);
+int dsh_cluster_pairs(dsh_ctx *ctx, uint64_t n_nodes, const uint32_t *lhs, const uint32_t *rhs, uint64_t n_pairs,
+                      const uint32_t *labels_in, uint32_t *labels_out, uint64_t *n_clusters);
+int dsh_cluster_csr(dsh_ctx *ctx, uint64_t n_nodes, uint64_t row_begin, uint64_t rows, const uint64_t *row_ptr, const uint32_t *col,
+                    const uint32_t *labels_in, uint32_t *labels_out, uint64_t *n_clusters);
+
 /* ---- multi-GPU shards of the full triangle ------------------------------------------------
  * Every rank holds all sketches (dsh_upload/attach) and computes one shard; no collective is
  * needed inside the compare.  Internally the plane matrix is laid out in (threshold, min value)
@@ -565,6 +614,7 @@ int dsh_finalize_phase_cycles(dsh_ctx *ctx, uint64_t *out16);
  *   resources     "cum_budget_bytes"        scratch for the pair counts C(v) (default 8 GiB): larger jobs run in bands
  *                 "knn_square_budget_bytes" all-vs-all dsh_knn keeps an n x n float matrix in HBM up to this size (96 GiB)
  *                 "threshold_band_bytes"    dsh_dist_threshold* computes bands of whole rows of at most this much float32 (1 GiB)
+ *                 "cluster_chunk"           dsh_cluster_pairs / dsh_cluster_csr unite at most this many edges per launch (2^20)
  *                 "derive_chunk_bytes"      the host forms of dsh_fold / dsh_upload_sketches_folded move at most this many bytes
  *                                           of source rows per step (256 MiB; at least one row)
  *   layout        "sort"                    -1 auto | 0 | 1: key-ordered plane columns (0 = identity: the slow, simple layout)
