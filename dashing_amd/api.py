@@ -31,6 +31,7 @@ SYMBOLS = [
     "dsh_allgather_device", "dsh_dist_collect", "dsh_range_parts", "dsh_dist_rows_parts_device_async", "dsh_collect_parts_async",
     "dsh_dist_rect", "dsh_knn", "dsh_dist_threshold", "dsh_dist_threshold_device", "dsh_dist_rect_threshold", "dsh_dist_pairs", "dsh_dist_pairs_device", "dsh_dist_pairs_csr",
     "dsh_cluster_threshold", "dsh_cluster_threshold_device", "dsh_cluster_pairs", "dsh_cluster_csr",
+    "dsh_greedy_threshold", "dsh_greedy_threshold_device",
     "dsh_fold", "dsh_fold_device", "dsh_upload_sketches_folded", "dsh_upload_sketches_folded_device", "dsh_union_groups", "dsh_union_groups_device", "dsh_shard_plan", "dsh_dist_shard_device", "dsh_unpermute_device", "dsh_unpermute_staged_device", "dsh_unpermute_blocks_device", "dsh_tri_span", "dsh_tri_index", "dsh_partition_rows", "dsh_balance_rows", "dsh_balance_rowsets", "dsh_rowsets_from_bounds", "dsh_rowsets_rank", "dsh_alloc_host", "dsh_free_host",
     "dsh_set_profiling", "dsh_last_kernel_ms", "dsh_last_part_info", "dsh_finalize_phase_cycles", "dsh_set_option", "dsh_get_info", "dsh_stream",
 ]
@@ -164,7 +165,9 @@ def load_library():
                        ("dsh_cluster_threshold", [vp, i32, i32, i32, C.c_float, vp, C.POINTER(u64)]),
                        ("dsh_cluster_threshold_device", [vp, i32, i32, i32, C.c_float, vp, C.POINTER(u64)]),
                        ("dsh_cluster_pairs", [vp, u64, vp, vp, u64, vp, vp, C.POINTER(u64)]),
-                       ("dsh_cluster_csr", [vp, u64, u64, u64, vp, vp, vp, vp, C.POINTER(u64)])):
+                       ("dsh_cluster_csr", [vp, u64, u64, u64, vp, vp, vp, vp, C.POINTER(u64)]),
+                       ("dsh_greedy_threshold", [vp, i32, i32, i32, C.c_float, vp, C.POINTER(u64)]),
+                       ("dsh_greedy_threshold_device", [vp, i32, i32, i32, C.c_float, vp, C.POINTER(u64)])):
         fn = getattr(lib, name, None)
         if fn is not None:
             fn.argtypes = args
@@ -711,6 +714,21 @@ class Context:
         nc = C.c_uint64()
         self._ck(self._derive("dsh_cluster_threshold_device")(self._h, estim, result_type, k, threshold, C.c_void_p(labels_ptr), C.byref(nc)))
         return int(nc.value)
+
+    # ---- greedy representatives in slot order (include/dashing_hip.h has the contract)
+    def greedy_threshold(self, threshold, estim=ESTIM_ERTL_MLE, result_type=JI, k=31):
+        """(labels uint32 [n], n_reps): x is a representative (labels[x] == x) iff no earlier representative hits it in
+        the graph of the hits of dist_threshold(threshold, ...); every other slot gets its smallest such representative"""
+        labels = np.zeros(self.n, np.uint32)
+        nr = C.c_uint64()
+        self._ck(self._derive("dsh_greedy_threshold")(self._h, estim, result_type, k, threshold, labels.ctypes.data, C.byref(nr)))
+        return labels, int(nr.value)
+
+    def greedy_threshold_device(self, labels_ptr, threshold, estim=ESTIM_ERTL_MLE, result_type=JI, k=31):
+        """labels into the caller's device buffer (uint32 [n]); returns n_reps"""
+        nr = C.c_uint64()
+        self._ck(self._derive("dsh_greedy_threshold_device")(self._h, estim, result_type, k, threshold, C.c_void_p(labels_ptr), C.byref(nr)))
+        return int(nr.value)
 
     @staticmethod
     def _labels_in(n_nodes, labels_in):

@@ -60,7 +60,7 @@ static void release_ctx(dsh_ctx *c)
                       &c->thr_total, &c->thr_col, &c->thr_val, &c->thr_rowptr, &c->pairs_card, &c->pairs_hist, &c->pairs_lhs,
                       &c->pairs_rhs, &c->pairs_out, &c->pairs_err, &c->derive_err, &c->derive_stage, &c->derive_ptr, &c->derive_mem,
                       &c->derive_dst, &c->derive_part[0], &c->derive_part[1], &c->derive_out, &c->cc_parent, &c->cc_state, &c->cc_lhs,
-                      &c->cc_rhs, &c->cc_rowptr, &c->cc_seed, &c->cc_labels})
+                      &c->cc_rhs, &c->cc_rowptr, &c->cc_seed, &c->cc_labels, &c->gr_assign, &c->gr_state, &c->gr_labels})
         b->release();
     if (c->pin_perm) (void)hipHostFree(c->pin_perm);
     c->pin_perm = nullptr;
@@ -1069,6 +1069,11 @@ int dsh_set_option(dsh_ctx *c, const char *name, int64_t v)
     if (!std::strcmp(name, "cluster_chunk")) {
         if (v < 1 || v > (1 << 26)) return fail(c, DSH_EINVAL, "cluster_chunk must be in [1, 2^26]");
         c->cluster_chunk = (uint64_t)v;
+        return DSH_OK;
+    }
+    if (!std::strcmp(name, "greedy_band_rows")) {
+        if (v < 1 || v > (long long)kGreedyMaxRows) return fail(c, DSH_EINVAL, "greedy_band_rows must be in [1, %u]", kGreedyMaxRows);
+        c->greedy_band_rows = (uint64_t)v;
         return DSH_OK;
     }
     if (!std::strcmp(name, "derive_chunk_bytes")) {

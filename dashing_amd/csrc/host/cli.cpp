@@ -98,6 +98,14 @@ static void usage(const char *sub)
             "                           output order, clusters numbered from 0 by their first member, which represents them;\n"
             "                           -b: u64 n, u64 n_clusters, u32 labels[n] (label = slot of the representative).  Not with\n"
             "                           --threshold, --nearest-neighbors, --pairs, -Q, -U, -T or several devices.\n"
+            "  --representatives FLOAT  emit greedy representatives at FLOAT instead of distances: walk the inputs in output order\n"
+            "                           (largest file first by default, the order given with --avoid-sorting); an input that no\n"
+            "                           earlier representative passes --threshold FLOAT's test with becomes a representative, every\n"
+            "                           other input joins its FIRST such representative.  Computed on the device.  Text:\n"
+            "                           '#Representatives<TAB>measure<TAB>op<TAB>FLOAT', then name<TAB>cluster<TAB>representative<TAB>value\n"
+            "                           per input, clusters numbered from 0 by ascending representative, value = the pair's value\n"
+            "                           ('-' for a representative); -b: u64 n, u64 n_reps, u32 labels[n].  Not with --cluster,\n"
+            "                           --threshold, --nearest-neighbors, --pairs, -Q, -U, -T or several devices.\n"
             "  --pairs FILE             emit only the pairs FILE lists, one per line as name_a<TAB>name_b (input names as given\n"
             "                           here; record names with dist_by_seq), in FILE's order: name_a<TAB>name_b and one value per\n"
             "                           measure.  --measures LIST: comma-separated from MASH_DIST, JI, SIZES, FULL_MASH_DIST,\n"
@@ -122,6 +130,8 @@ struct Opts {
     float threshold = 0.f;
     bool has_cluster = false;  // --cluster: the connected components of --threshold's graph (dsh_cluster_threshold)
     float cluster_t = 0.f;
+    bool has_reps = false;  // --representatives: the greedy pass in output order over --threshold's graph (dsh_greedy_threshold)
+    float reps_t = 0.f;
     std::string groups_file;  // --groups FILE: the unions of named groups are compared instead of the inputs (dsh_union_groups)
     std::string pairs_file, measures;  // --pairs FILE [--measures LIST]: only the listed pairs (dsh_dist_pairs)
     int rccl = 0;             // --rccl: deliver the rows through the RCCL exchange of the C-ABI even with one device
@@ -130,7 +140,7 @@ struct Opts {
     std::vector<std::string> inpaths, querypaths;
 };
 
-enum { OPT_PRESKETCHED = 1000, OPT_AVOID_SORT, OPT_DEVICE, OPT_NPERBATCH, OPT_NN, OPT_NGPUS, OPT_DEVICES, OPT_RCCL, OPT_THRESHOLD, OPT_CLUSTER, OPT_PAIRS, OPT_MEASURES, OPT_GROUPS, OPT_UNSUPPORTED };
+enum { OPT_PRESKETCHED = 1000, OPT_AVOID_SORT, OPT_DEVICE, OPT_NPERBATCH, OPT_NN, OPT_NGPUS, OPT_DEVICES, OPT_RCCL, OPT_THRESHOLD, OPT_CLUSTER, OPT_REPS, OPT_PAIRS, OPT_MEASURES, OPT_GROUPS, OPT_UNSUPPORTED };
 
 static Opts parse(int argc, char **argv, bool is_dist)
 {
@@ -157,7 +167,7 @@ static Opts parse(int argc, char **argv, bool is_dist)
         {"use-bloom-filter", no_argument, nullptr, OPT_UNSUPPORTED}, {"use-nthash", no_argument, nullptr, OPT_UNSUPPORTED},
         {"use-cyclic-hash", no_argument, nullptr, OPT_UNSUPPORTED}, {"countmin", no_argument, nullptr, OPT_UNSUPPORTED},
         {"nearest-neighbors", required_argument, nullptr, OPT_NN}, {"threshold", required_argument, nullptr, OPT_THRESHOLD},
-        {"cluster", required_argument, nullptr, OPT_CLUSTER},
+        {"cluster", required_argument, nullptr, OPT_CLUSTER}, {"representatives", required_argument, nullptr, OPT_REPS},
         {"pairs", required_argument, nullptr, OPT_PAIRS}, {"groups", required_argument, nullptr, OPT_GROUPS}, {"measures", required_argument, nullptr, OPT_MEASURES},
         // second arm of result_cmp (src/dashing.h:577-588); flag numbers as in DIST_LONG_OPTS
         {"sizes", no_argument, nullptr, 'Z'}, {"containment-index", no_argument, nullptr, 131},
@@ -234,6 +244,13 @@ static Opts parse(int argc, char **argv, bool is_dist)
             o.cluster_t = std::strtof(optarg, &end);
             if (end == optarg || *end || o.cluster_t != o.cluster_t) die("--cluster needs a number, got '%s'", optarg);
             o.has_cluster = true;
+            break;
+        }
+        case OPT_REPS: {
+            char *end = nullptr;
+            o.reps_t = std::strtof(optarg, &end);
+            if (end == optarg || *end || o.reps_t != o.reps_t) die("--representatives needs a number, got '%s'", optarg);
+            o.has_reps = true;
             break;
         }
         case OPT_PAIRS: o.pairs_file = optarg; break;
@@ -979,6 +996,16 @@ static int dist_main(int argc, char **argv, bool by_seq = false)
         if (o.fmt == FULL_TSV) die("--cluster does not go with -T: the output is one line per input.");
         if (o.devices.size() > 1 || o.rccl) die("--cluster runs on one device: --ngpus / --devices are not supported.");
     }
+    if (o.has_reps) {  // (what --cluster refuses, and --cluster)
+        if (o.has_cluster) die("--representatives does not go with --cluster: choose the representatives or the components.");
+        if (o.has_threshold) die("--representatives does not go with --threshold: choose the representatives or the pairs.");
+        if (o.nneighbors) die("--representatives does not go with --nearest-neighbors: choose one selection.");
+        if (!o.pairs_file.empty()) die("--representatives does not go with --pairs: the representatives are those of all pairs.");
+        if (!o.querypaths.empty()) die("--representatives does not go with -Q: every input is tested against every earlier one.");
+        if (o.fmt == UPPER_TRIANGULAR) die("--representatives does not go with -U: the output is one line per input.");
+        if (o.fmt == FULL_TSV) die("--representatives does not go with -T: the output is one line per input.");
+        if (o.devices.size() > 1 || o.rccl) die("--representatives runs on one device: --ngpus / --devices are not supported.");
+    }
     static const char *const kMeasureNames[9] = {"MASH_DIST", "JI", "SIZES", "FULL_MASH_DIST", "FULL_CONTAINMENT_DIST", "CONTAINMENT_INDEX",
                                                  "CONTAINMENT_DIST", "SYMMETRIC_CONTAINMENT_INDEX", "SYMMETRIC_CONTAINMENT_DIST"};
     const bool with_pairs = !o.pairs_file.empty();
@@ -1016,8 +1043,8 @@ static int dist_main(int argc, char **argv, bool by_seq = false)
     if (!o.out_sizes.empty() && !(ofp = std::fopen(o.out_sizes.c_str(), "w"))) die("Could not open file at %s for writing.", o.out_sizes.c_str());
     if (!o.out_dists.empty() && !(pairofp = std::fopen(o.out_dists.c_str(), "wb"))) die("Could not open file at %s for writing.", o.out_dists.c_str());
     // asymmetric measure without -Q: all references are also the queries (src/distmain.cpp:120-125)
-    // (--cluster tests every pair once, in the triangle's orientation: no query/reference format for it)
-    const bool symmetric = o.has_cluster || !(o.result_type == 4 || o.result_type == 5 || o.result_type == 6);  // src/dashing.h:389-399
+    // (--cluster and --representatives test every pair once, in the triangle's orientation: no query/reference format for them)
+    const bool symmetric = o.has_cluster || o.has_reps || !(o.result_type == 4 || o.result_type == 5 || o.result_type == 6);  // src/dashing.h:389-399
     if (o.querypaths.empty() && !symmetric && !with_pairs && !with_groups) {  // (a pair list names its own pairs, each in one orientation; the groups take their turn below)
         o.querypaths = o.inpaths;
         std::fprintf(stderr, "Note: No query files provided, but an asymmetric distance was requested. Switching to a query/reference format with all references as queries.\n");
@@ -1213,6 +1240,41 @@ static int dist_main(int argc, char **argv, bool by_seq = false)
                 s.append(num, (size_t)std::snprintf(num, sizeof num, "\t%u\t", index[labels[x]]));
                 s += o.inpaths[labels[x]];
                 s += '\n';
+                std::fwrite(s.data(), 1, s.size(), pairofp);
+            }
+        }
+    } else if (o.has_reps) {  // the greedy pass in output order (dsh_greedy_threshold): no pair leaves the device
+        std::vector<uint32_t> labels(std::max<size_t>(n, 1));
+        uint64_t n_reps = 0;
+        DSH(ctx, dsh_greedy_threshold(ctx, o.estim, o.result_type, o.k, o.reps_t, labels.data(), &n_reps));
+        if (o.fmt == BINARY) {
+            const uint64_t hdr[2] = {(uint64_t)n, n_reps};
+            if (std::fwrite(hdr, sizeof(uint64_t), 2, pairofp) != 2 || std::fwrite(labels.data(), sizeof(uint32_t), n, pairofp) != n)
+                die("Error writing to binary file");
+        } else {
+            const bool dist = o.result_type == 0 || o.result_type == 3 || o.result_type == 4 || o.result_type == 6 || o.result_type == 8;
+            std::fprintf(pairofp, "#Representatives\t%s\t%s\t%.6g\n", kMeasureNames[o.result_type], dist ? "<=" : ">=", (double)o.reps_t);  // --threshold's number format
+            // the value of every non-representative against its label: ONE list of pairs (lhs = the input, rhs = its
+            // representative), by dsh_dist_pairs' contract bit for bit the triangle's value
+            std::vector<uint32_t> plhs, prhs;
+            for (size_t x = 0; x < n; ++x)
+                if (labels[x] != x) plhs.push_back((uint32_t)x), prhs.push_back(labels[x]);
+            std::vector<float> pv(std::max<size_t>(plhs.size(), 1));
+            const int type = o.result_type;
+            if (!plhs.empty()) DSH(ctx, dsh_dist_pairs(ctx, o.estim, &type, 1, o.k, plhs.data(), prhs.data(), plhs.size(), pv.data()));
+            // clusters are numbered by ascending representative; a representative comes before its members
+            std::vector<uint32_t> index(std::max<size_t>(n, 1));
+            uint32_t next = 0;
+            size_t at = 0;
+            std::string s;
+            char num[64];
+            for (size_t x = 0; x < n; ++x) {
+                if (labels[x] == x) index[x] = next++;
+                s = o.inpaths[x];
+                s.append(num, (size_t)std::snprintf(num, sizeof num, "\t%u\t", index[labels[x]]));
+                s += o.inpaths[labels[x]];
+                if (labels[x] == x) s += "\t-\n";
+                else s.append(num, (size_t)std::snprintf(num, sizeof num, "\t%.6g\n", (double)pv[at++]));
                 std::fwrite(s.data(), 1, s.size(), pairofp);
             }
         }

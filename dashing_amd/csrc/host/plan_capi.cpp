@@ -1,7 +1,8 @@
 // plan_capi.cpp -- CPU test hook of the pure-host planner (../plan.cpp): builds a layout and a pair plan for given
 // per-sketch keys exactly as engine.hip does and checks the plan against its contract, so the schedule that replaces
 // dist_loop / perform_core_op (src/sketch_and_cmp.h:785-880, :699-710) is unit-tested without a GPU
-// (tests/test_plan.py).  Also the sequential build of the clusters' union-find (dsh_plan_uf_labels, at the end).  Built into
+// (tests/test_plan.py).  Also the sequential build of the clusters' union-find (dsh_plan_uf_labels, at the end) and the band rule of
+// the greedy representatives (dshh_greedy_bands).  Built into
 // libdashing_host.so; not part of the GPU C-ABI.
 #include <algorithm>
 #include <cstdarg>
@@ -376,6 +377,22 @@ int dshh_plan_check_rowset(uint64_t n, const uint32_t *keys, const uint64_t *tab
 
 // first row of the second run of a row-sorted range (plan::rowsorted_split), re when the range stays one run
 uint64_t dshh_rowsorted_split(uint64_t n, uint64_t rb, uint64_t re) { return rowsorted_split(n, rb, re); }
+
+// the bands of dsh_greedy_threshold* (plan::greedy_band_end, the loop of greedy.hip): bounds[0] = 0, bounds[q + 1] = the end
+// of band q, for the triangle of n sketches.  Returns the number of bands (0 for n < 2), or -1 when they do not fit cap
+// boundaries (tests/test_greedy_plan.py).
+int64_t dshh_greedy_bands(uint64_t n, uint64_t band_bytes, uint64_t row_cap, uint64_t *bounds, uint64_t cap)
+{
+    const uint64_t band_floats = std::max<uint64_t>(band_bytes / sizeof(float), 1);
+    uint64_t nb = 0;
+    if (cap) bounds[0] = 0;
+    for (uint64_t b0 = 0; b0 + 1 < n;) {
+        b0 = greedy_band_end(n, b0, band_floats, row_cap);
+        if (++nb >= cap) return -1;
+        bounds[nb] = b0;
+    }
+    return (int64_t)nb;
+}
 
 // the union-find of the threshold clusters (../uf.h, the code the device kernels compile) run sequentially: labels_out[x] =
 // the smallest node of x's component in the graph of the n_edges edges (lhs[e], rhs[e]).  Returns 0, -1 for an edge that

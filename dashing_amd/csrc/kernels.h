@@ -204,6 +204,16 @@ hipError_t launch_cc_band(hipStream_t st, const float *vals, const ThrRows &g, f
 // labels[x] = root of x (the smallest member of its component), *n_roots += the roots (the caller zeroes it)
 hipError_t launch_cc_labels(hipStream_t st, uint32_t *parent, uint64_t n, uint32_t cap, uint32_t *labels, uint64_t *n_roots, uint32_t *err);
 
+// greedy representatives (kernels_greedy.hip, greedy.hip): assign[n] starts as assign[x] = x (launch_cc_init) and only
+// decreases; assign[x] < x: x is covered by that representative.  Per band of triangle rows, in stream order:
+constexpr uint32_t kGreedyMaxRows = 8192;  // rows of a band: k_greedy_diag keeps their entries in LDS (32 KiB)
+// the band's rows among themselves (g.rows <= kGreedyMaxRows): afterwards assign[row0 .. row0 + rows) is final
+hipError_t launch_greedy_diag(hipStream_t st, const float *vals, const ThrRows &g, float t, int descending, uint32_t *assign);
+// every representative row of the band lowers assign[j] to itself for its passing columns j >= row0 + rows
+hipError_t launch_greedy_band(hipStream_t st, const float *vals, const ThrRows &g, float t, int descending, uint32_t *assign);
+// after the last band: labels[x] = assign[x], *n_reps += the x with assign[x] == x (the caller zeroes it)
+hipError_t launch_greedy_labels(hipStream_t st, const uint32_t *assign, uint64_t n, uint32_t *labels, uint64_t *n_reps);
+
 // explicit pair lists (kernels_pairs.hip, pairs.hip): histograms are [cnt][64] counters, uint16 for p <= kPairsMaxP16
 // (a bin holds at most 2^p), uint32 above
 constexpr int kPairsMaxP16 = 15;

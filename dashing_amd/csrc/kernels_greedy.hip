@@ -1,0 +1,182 @@
+// kernels_greedy.hip -- greedy representatives at a threshold (greedy.hip): the lexicographically first
+// maximal independent set of the hit graph in slot order, every other slot labelled with its first representative.
+//
+// assign is a uint32 [n] array in device memory that starts as assign[x] = x and only ever decreases: assign[x] < x means
+// "x is covered by the representative assign[x]".  The bands of the triangle come in ascending row order, so when band
+// [b0, b1) is reached every row below b0 has said all it has to say: assign[b0..b1) is final EXCEPT for what the band's
+// own rows do to each other.
+//   k_greedy_diag    settles that: ONE workgroup holds assign[b0..b1) in LDS and walks the band's rows in ascending order.
+//                    A row whose entry is still itself is a representative: its in-band values (the columns (i, b1)) are
+//                    tested and a passing column whose entry is still itself takes i -- rows ascend, so the first
+//                    representative to reach a column is its smallest, and every column belongs to one thread: no
+//                    atomics.  A covered row costs a read of LDS and no barrier; a representative row one barrier (and
+//                    every batch of 16 rows two).  The loop visits every row once.  The entries go back to assign at the
+//                    end.
+//   k_greedy_band    the geometry of k_cc_band (kernels_cluster.hip: ThrRows, one wave per 4096-value chunk of a row, one
+//                    aligned float4 per lane per step, ragged edges value by value).  Now assign[b0..b1) is final: a wave
+//                    whose row is covered returns at once, a representative's wave lowers assign[j] to i for every passing
+//                    column j >= b1 (the in-band columns belong to k_greedy_diag and are skipped, whole chunks of them
+//                    without a load).  atomicMin commutes: the result is the smallest representative whatever the order.
+//                    The read in front of it only spares the atomic where nothing would change (assign[j] never grows, so
+//                    a stale value errs towards one atomic too many).  Accesses to assign here are relaxed agent-scope
+//                    atomics, as in UfDevice.  No loop depends on what another thread does.
+//   k_greedy_labels  a launch of its own, after the last band: labels[x] = assign[x]; representatives counted with
+//                    __ballot + popcount and one atomicAdd per wave
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+
+#include "kernels.h"
+
+namespace dsh {
+
+namespace {
+
+constexpr uint32_t kStep = 256;  // values a wave takes per step: one float4 per lane (kernels_threshold.hip)
+constexpr uint32_t kDiagThreads = 1024;
+constexpr uint32_t kDiagCols = kGreedyMaxRows / kDiagThreads;  // band columns a thread of k_greedy_diag owns
+constexpr uint32_t kDiagBatch = 16;                            // rows whose values it loads at once
+
+__device__ __forceinline__ bool thr_pass(float v, float t, int descending) { return descending ? v >= t : v <= t; }  // NaN: neither
+
+__device__ __forceinline__ uint32_t ld_assign(const uint32_t *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+// rows <= kGreedyMaxRows (the host's band rule); one workgroup.  Thread t owns the band columns t, t + 1024, ...
+// The rows are taken kDiagBatch at a time: first every thread loads, for the batch's rows that are still themselves, the
+// values at its columns and keeps one pass bit per (row, column) -- the loads of a batch are independent of each other, so
+// their latencies overlap instead of adding up row by row --, then the batch's rows are settled one after the other from
+// the bits and LDS alone.  A row that was covered before its batch is neither loaded nor visited.
+__global__ __launch_bounds__(kDiagThreads) void k_greedy_diag(const float *__restrict__ vals, ThrRows g, float t, int descending,
+                                                               uint32_t *assign)
+{
+    __shared__ uint32_t cur[kGreedyMaxRows];
+    const uint32_t rows = (uint32_t)g.rows, b0 = (uint32_t)g.row0;
+    const uint64_t first = g.n - 1 - g.row0;  // values of the band's first row
+    for (uint32_t r = threadIdx.x; r < rows; r += kDiagThreads) cur[r] = assign[g.row0 + r];
+    for (uint32_t r0 = 0; r0 + 1 < rows; r0 += kDiagBatch) {  // (the band's last row has no in-band column)
+        const uint32_t nb = rows - 1 - r0 < kDiagBatch ? rows - 1 - r0 : kDiagBatch;
+        __syncthreads();  // every write of the batches before (and the load above) has landed
+        uint32_t live = 0;  // rows of the batch that are still themselves: the same in every thread
+#pragma unroll
+        for (uint32_t rr = 0; rr < kDiagBatch; ++rr)
+            if (rr < nb && cur[r0 + rr] == b0 + r0 + rr) live |= 1u << rr;
+        __syncthreads();  // nobody writes before everybody has read
+        if (!live) continue;
+        uint32_t bits[kDiagCols];
+        const uint64_t rowoff0 = (uint64_t)r0 * first - (uint64_t)r0 * (r0 - 1) / 2;  // (thr_row of kernels_threshold.hip)
+#pragma unroll
+        for (uint32_t v = 0; v < kDiagCols; ++v) {
+            bits[v] = 0;
+            const uint32_t col = threadIdx.x + v * kDiagThreads;
+            if (col >= rows || col <= r0) continue;
+            // every load is issued, none under a branch (a value that is not wanted is read from vals[0] and dropped): the
+            // compiler may then put all of them in flight before it waits for the first
+            float x[kDiagBatch];
+            uint64_t rowoff = rowoff0;
+#pragma unroll
+            for (uint32_t rr = 0; rr < kDiagBatch; ++rr) {
+                const uint32_t r = r0 + rr;
+                const bool want = ((live >> rr) & 1u) && col > r;
+                x[rr] = vals[want ? rowoff + (col - r - 1) : 0];
+                rowoff += first - r;  // row r + 1 starts behind the n - 1 - (row0 + r) values of row r
+            }
+#pragma unroll
+            for (uint32_t rr = 0; rr < kDiagBatch; ++rr)
+                if (((live >> rr) & 1u) && col > r0 + rr && thr_pass(x[rr], t, descending)) bits[v] |= 1u << rr;
+        }
+        for (uint32_t rr = 0; rr < nb; ++rr) {
+            // cur[r] is settled: rows to the left of r wrote it before their barrier, rows to the right never do
+            const uint32_t r = r0 + rr;
+            if (!((live >> rr) & 1u) || cur[r] != b0 + r) continue;  // covered: before the batch, or by a row of it
+#pragma unroll
+            for (uint32_t v = 0; v < kDiagCols; ++v) {
+                const uint32_t col = threadIdx.x + v * kDiagThreads;
+                if (((bits[v] >> rr) & 1u) && cur[col] == b0 + col) cur[col] = b0 + r;
+            }
+            __syncthreads();
+        }
+    }
+    __syncthreads();
+    for (uint32_t r = threadIdx.x; r < rows; r += kDiagThreads) assign[g.row0 + r] = cur[r];
+}
+
+// block (r, y) holds four waves, wave w the chunk 4 y + w of band row r (k_cc_band)
+__global__ __launch_bounds__(256) void k_greedy_band(const float *__restrict__ vals, ThrRows g, float t, int descending, uint32_t *assign)
+{
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const uint64_t r = blockIdx.x;
+    const uint32_t ch = blockIdx.y * 4 + wave;
+    if (ch >= g.nchunks) return;
+    const uint64_t i = g.row0 + r;
+    const uint64_t first = g.n - 1 - g.row0;
+    const uint64_t len = g.n - 1 - i;
+    const uint64_t inband = g.rows - 1 - r;  // the row's first values: columns inside the band (inband <= len)
+    const uint64_t cb = (uint64_t)ch * kThrChunk;
+    const uint64_t ce = len - cb < kThrChunk ? len : cb + kThrChunk;  // (read only where cb < len)
+    if (cb >= len || ce <= inband) return;  // past the row, or wholly inside the band's own columns
+    if (ld_assign(assign + i) != (uint32_t)i) return;  // covered: the row has nothing to say
+    const uint64_t rowoff = r * first - r * (r - 1) / 2;
+    const uint32_t colbase = (uint32_t)(i + 1);
+    const uint64_t begin = rowoff + (cb > inband ? cb : inband), end = rowoff + ce;
+    for (uint64_t idx = (begin & ~(uint64_t)3) + 4 * lane; idx < end; idx += kStep) {
+        uint32_t m = 0;
+        if (idx >= begin && idx + 4 <= end) {
+            const float4 q = *reinterpret_cast<const float4 *>(vals + idx);
+            m = (thr_pass(q.x, t, descending) ? 1u : 0u) | (thr_pass(q.y, t, descending) ? 2u : 0u) |
+                (thr_pass(q.z, t, descending) ? 4u : 0u) | (thr_pass(q.w, t, descending) ? 8u : 0u);
+        } else {
+#pragma unroll
+            for (int c = 0; c < 4; ++c)
+                if (idx + c >= begin && idx + c < end) m |= (thr_pass(vals[idx + c], t, descending) ? 1u : 0u) << c;
+        }
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            if (!((m >> c) & 1u)) continue;
+            uint32_t *a = assign + (colbase + (uint32_t)(idx + c - rowoff));
+            if (ld_assign(a) > (uint32_t)i) (void)atomicMin(a, (uint32_t)i);
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void k_greedy_labels(const uint32_t *__restrict__ assign, uint64_t n, uint32_t *__restrict__ labels,
+                                                       unsigned long long *n_reps)
+{
+    const uint64_t nround = (n + 255) / 256 * 256;  // whole waves take part in the ballot
+    for (uint64_t x = (uint64_t)blockIdx.x * 256 + threadIdx.x; x < nround; x += (uint64_t)gridDim.x * 256) {
+        bool rep = false;
+        if (x < n) {
+            const uint32_t l = assign[x];
+            labels[x] = l;
+            rep = l == (uint32_t)x;
+        }
+        const unsigned long long b = __ballot(rep);
+        if ((threadIdx.x & 63u) == 0 && b) atomicAdd(n_reps, (unsigned long long)__popcll(b));
+    }
+}
+
+}  // namespace
+
+hipError_t launch_greedy_diag(hipStream_t st, const float *vals, const ThrRows &g, float t, int descending, uint32_t *assign)
+{
+    if (g.rows < 2 || g.rect) return hipSuccess;  // (one row has no in-band column)
+    if (g.rows > kGreedyMaxRows) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_greedy_diag, dim3(1), dim3(kDiagThreads), 0, st, vals, g, t, descending, assign);
+    return hipGetLastError();
+}
+
+hipError_t launch_greedy_band(hipStream_t st, const float *vals, const ThrRows &g, float t, int descending, uint32_t *assign)
+{
+    if (g.rows == 0 || g.rect) return hipSuccess;
+    hipLaunchKernelGGL(k_greedy_band, dim3((uint32_t)g.rows, (g.nchunks + 3) / 4), dim3(256), 0, st, vals, g, t, descending, assign);
+    return hipGetLastError();
+}
+
+hipError_t launch_greedy_labels(hipStream_t st, const uint32_t *assign, uint64_t n, uint32_t *labels, uint64_t *n_reps)
+{
+    if (!n) return hipSuccess;
+    const uint32_t grid = (uint32_t)std::min<uint64_t>(std::max<uint64_t>((n + 255) / 256, 1), 8192);
+    hipLaunchKernelGGL(k_greedy_labels, dim3(grid), dim3(256), 0, st, assign, n, labels, reinterpret_cast<unsigned long long *>(n_reps));
+    return hipGetLastError();
+}
+
+}  // namespace dsh

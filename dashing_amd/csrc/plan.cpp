@@ -19,6 +19,17 @@ uint64_t tri_span(uint64_t n, uint64_t rb, uint64_t re)
     return cnt * (n - 1) - (rb + re - 1) * cnt / 2;
 }
 
+uint64_t greedy_band_end(uint64_t n, uint64_t b0, uint64_t band_floats, uint64_t row_cap)
+{
+    const uint64_t max_rows = std::min<uint64_t>(std::max<uint64_t>(row_cap, 1), 1u << 20);
+    uint64_t b1 = b0, span = 0;
+    do {
+        span += n - 1 - b1;
+        ++b1;
+    } while (b1 < n && b1 - b0 < max_rows && span + (n - 1 - b1) <= band_floats);
+    return b1;
+}
+
 void partition_rows(uint64_t n, uint32_t nparts, uint32_t align, uint64_t *bounds)
 {
     if (align == 0) align = 1;

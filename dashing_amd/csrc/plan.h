@@ -41,6 +41,9 @@ void balance_rows(uint64_t n, uint32_t nparts, uint64_t *bounds);
 // rows [rb, re) cut into nparts consecutive parts of about equal pair counts, every cut a whole number of 128-row
 // tile rows after rb (fewer parts if the range has fewer tile rows); out gets the boundaries
 void range_parts(uint64_t n, uint64_t rb, uint64_t re, uint32_t nparts, std::vector<uint64_t> &out);
+// the band of dsh_greedy_threshold* that starts at triangle row b0 < n: whole rows [b0, b1), at most band_floats values
+// (one row at least), at most 2^20 rows -- the rule of dsh_dist_threshold* -- and at most row_cap rows (>= 1); returns b1
+uint64_t greedy_band_end(uint64_t n, uint64_t b0, uint64_t band_floats, uint64_t row_cap);
 
 // ---- row sets: a rank's rows as a range plus top-up tile rows --------------------------------------------------------
 // Contiguous row ranges on 128-row boundaries cannot give every rank the same number of tiles when the ranges are a

@@ -62,7 +62,7 @@ typedef struct dsh_ctx dsh_ctx;
  * Entry points that were only ADDED since leave the number alone and are detected by symbol (dlsym):
  * dsh_dist_threshold, dsh_dist_threshold_device, dsh_dist_rect_threshold, dsh_dist_pairs*, dsh_fold*,
  * dsh_upload_sketches_folded*, dsh_union_groups*, dsh_cluster_threshold, dsh_cluster_threshold_device, dsh_cluster_pairs,
- * dsh_cluster_csr. */
+ * dsh_cluster_csr, dsh_greedy_threshold, dsh_greedy_threshold_device. */
 #define DSH_ABI_VERSION 7
 int dsh_abi_version(void);
 
@@ -404,6 +404,57 @@ int dsh_cluster_pairs(dsh_ctx *ctx, uint64_t n_nodes, const uint32_t *lhs, const
 int dsh_cluster_csr(dsh_ctx *ctx, uint64_t n_nodes, uint64_t row_begin, uint64_t rows, const uint64_t *row_ptr, const uint32_t *col,
                     const uint32_t *labels_in, uint32_t *labels_out, uint64_t *n_clusters);
 
+/* ---- greedy representatives at a threshold: the greedy pass in slot order, on the device ---------------
+ * Replaces what a dereplication client does with the hits of dsh_dist_threshold* when it wants REPRESENTATIVES rather than
+ * components (CD-HIT, dRep, galah): walk the inputs in priority order, make an input no earlier representative covers a
+ * representative, and give every other input to its first representative -- a sequential pass on the host over 10^8 to
+ * 10^9 hits at 100 000 sketches and a loose threshold.  Single linkage (dsh_cluster_threshold) does not answer this:
+ * components chain, and the smallest slot of a component represents members it does not resemble at all.
+ *   The result.  Let hit(i, j), i < j, be "the pair (i, j) is a hit of dsh_dist_threshold(ctx, estim, result_type, k, 0, n,
+ *     threshold, ...)": the same float32 value, the same predicate (v >= threshold for the similarity forms, v <= threshold
+ *     for the *_DIST forms, NaN never) and, for the asymmetric measures, the ONE orientation of the triangle.  Priority is
+ *     slot order (the caller orders the slots).  The representative set R is defined by: x is in R iff there is no r in R
+ *     with r < x and hit(r, x) -- the lexicographically first maximal independent set of the hit graph.  labels[x] = x
+ *     for x in R; otherwise labels[x] is the SMALLEST r in R with r < x and hit(r, x).  *n_reps is the number of x with
+ *     labels[x] == x.  Consequences: labels[x] <= x; labels[labels[x]] == labels[x]; every non-representative passes the
+ *     threshold against its label; no two representatives pass against each other; and the labels of the slots [0, m) are
+ *     those of a call on the first m sketches alone (prefix property): appending inputs never relabels earlier ones.  This
+ *     has one answer: it depends on no band size, launch geometry or order of arrival of atomics.
+ *   How.  One uint32 assign[n] in device memory, assign[x] = x at the start and only ever lowered; assign[x] < x means
+ *     "covered by that representative".  Bands of whole rows in ascending order, as dsh_cluster_threshold computes them.
+ *     Per band [b0, b1): k_greedy_diag -- ONE workgroup with assign[b0..b1) in LDS walks the band's rows in ascending order;
+ *     a row that is still itself covers the passing in-band columns that are still themselves (each column belongs to one
+ *     thread: no atomics; one barrier per representative row; the values are loaded 16 rows at a time, so that their
+ *     latencies overlap; a row covered before its batch touches no memory) -- then k_greedy_band: every
+ *     representative row of the band lowers assign[j] to itself (atomic minimum) for its passing columns j >= b1; a covered
+ *     row's waves return at once.  k_greedy_labels writes the labels and counts after the last band.  No loop waits for
+ *     another thread, so unlike the union-find of the clusters there is no step bound and no give-up path.
+ *   dsh_greedy_threshold         labels_out: host uint32 [n].
+ *   dsh_greedy_threshold_device  d_labels: caller-owned DEVICE uint32 [n]; exactly n labels are written.
+ *   Execution.  Synchronous, on the ctx stream; no host wait between bands, one wait at the end.  The band rule is
+ *     dsh_dist_threshold's ("threshold_band_bytes", at most 2^20 rows) with one more cap, "greedy_band_rows" rows (option,
+ *     default 4096, 1..8192; no result depends on it): it bounds the LDS of k_greedy_diag at 32 KiB.  The effects on the
+ *     context's cached state are exactly those of dsh_dist_threshold on rows [0, n): the dense calls before and after give
+ *     the same bytes.
+ *   Errors, before anything is enqueued: DSH_EINVAL for a NULL context, a NULL output with n > 0 and n > 2^32 - 1;
+ *     DSH_ESTATE without sketches.  n == 0 and n < 2 succeed; a NaN threshold gives n representatives.
+ *   Cost model: the dense path's cost for the triangle, ONE read of each band outside its diagonal block
+ *     by the rows that are representatives (4 bytes per pair of those rows; a covered row costs nothing), one atomic per
+ *     hit that lowers a label, and the sequential diagonal: per band, one barrier per representative row and one round of
+ *     global loads per 16 rows, in ONE workgroup.  Its worst case is a threshold nothing passes (every row a
+ *     representative).  Measured on one MI355X (tools/bench_greedy.py, profiles/greedy1; G = this call,
+ *     C = dsh_cluster_threshold_device, A = the dense call): at 100 000 x p=10 (A = 288 ms) G - A = 10.0 / 9.1 / 7.5 ms at
+ *     0.1 % / 1 % / 50 % hits beside C - A = 3.5 / 7.2 / 16.4 ms, and 94 ms where nothing passes (C - A = 3.5 ms), about
+ *     four fifths of it k_greedy_diag; at 10 000 x p=14 (A = 14.1 ms) G - A = 5.5 / 4.6 / 1.5 ms and 7.7 ms where nothing
+ *     passes, C - A within 1.3 ms of zero.  G - A is below A everywhere.
+ *   Not built: a caller-given priority permutation (the caller orders the slots); assignment to the BEST representative
+ *     rather than the first; a continuation that adds new slots at the cost of the new rows only; a rectangle form; CSR or
+ *     edge-list forms (a sequential host pass over hits that are already on the host is linear); a multi-GPU form. */
+int dsh_greedy_threshold(dsh_ctx *ctx, int estim, int result_type, int k, float threshold, uint32_t *labels_out,
+                         uint64_t *n_reps);
+int dsh_greedy_threshold_device(dsh_ctx *ctx, int estim, int result_type, int k, float threshold, void *d_labels,
+                                uint64_t *n_reps);
+
 /* ---- multi-GPU shards of the full triangle ------------------------------------------------
  * Every rank holds all sketches (dsh_upload/attach) and computes one shard; no collective is
  * needed inside the compare.  Internally the plane matrix is laid out in (threshold, min value)
@@ -615,6 +666,7 @@ int dsh_finalize_phase_cycles(dsh_ctx *ctx, uint64_t *out16);
  *                 "knn_square_budget_bytes" all-vs-all dsh_knn keeps an n x n float matrix in HBM up to this size (96 GiB)
  *                 "threshold_band_bytes"    dsh_dist_threshold* computes bands of whole rows of at most this much float32 (1 GiB)
  *                 "cluster_chunk"           dsh_cluster_pairs / dsh_cluster_csr unite at most this many edges per launch (2^20)
+ *                 "greedy_band_rows"        a band of dsh_greedy_threshold* holds at most this many rows (4096; 1..8192)
  *                 "derive_chunk_bytes"      the host forms of dsh_fold / dsh_upload_sketches_folded move at most this many bytes
  *                                           of source rows per step (256 MiB; at least one row)
  *   layout        "sort"                    -1 auto | 0 | 1: key-ordered plane columns (0 = identity: the slow, simple layout)
