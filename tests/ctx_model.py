@@ -2,6 +2,11 @@
 for the helper itself): a host-side model of the resident register matrix, the operation table, the seeded generator and
 the comparison of every query with the CPU oracle evaluated on the model.  Plain helper module; no fixtures.
 
+Two tables: the first (QUERY_KINDS, MUTATOR_KINDS, OPTION_*; generate) is the state of the library when the sequence tests
+were written and does not move -- tests/test_ctx_model.py pins what generate() returns --, the second (QUERY_KINDS2, ...;
+generate2, tests/test_gpu_ctx_sequences_derived.py) adds thresholded hits, pair lists, derived sketches, threshold
+clusters and greedy representatives and draws from both.
+
 An operation is a tuple that holds recipes (seeds, lengths, row specs), never arrays, so a printed sequence can be pasted
 into a directed test as it stands:
 
@@ -14,8 +19,10 @@ into a directed test as it stands:
     ("fastx", first, seed, [[len, ...], ...], width, k, canon)   one in-memory FASTA file per genome, max-merge
     ("attach", n, p, seed, kind)                           a new torch tensor is attached
     ("reattach", [(row, rowspec), ...])                    the attached tensor changed with torch, attached again
+    ("upfold", form, first, src_p, [rowspec, ...])         rows built at src_p >= p, folded into the slots; form: "host" | "device"
+    ("unite", first, [[member, ...], ...])                 union_groups_device of the resident rows, copied into the slots
     ("opt", name, value)                                   a speed knob: no effect on the model
-    ("query", kind, {...})                                 see QUERY_KINDS
+    ("query", kind, {...})                                 see QUERY_KINDS and QUERY_KINDS2
 
 A rowspec is ("law", seed, card) | ("uni", seed) | ("zero",) | ("sat",) | ("dup", j) | ("bad", seed, card, pos, value).
 """
@@ -23,6 +30,11 @@ import numpy as np
 
 from dashing_amd import synth
 
+import cluster_ref
+import derive_ref
+import greedy_ref
+import pairs_ref
+import thr_ref
 from fastx_gen import fasta
 from kseq_ref import parse as kseq_parse
 
@@ -38,6 +50,18 @@ OPTION_VALUES = {
     "cum_budget_bytes": [1 << 20, 1 << 22, 8 << 30], "range_sort_min_rows": [1, 64, 1024],
     "knn_square_budget_bytes": [0, 96 << 30], "part_band_tiles": [1, 16, 2048], "finalize_signal": [-1, 0, 1],
 }
+# The second table (generate2): the calls that came after the first one was drawn up.  generate() draws from the tables
+# above, so a key added THERE would move every sequence it returns; these are drawn by generate2 alone.
+QUERY_KINDS2 = ["fold", "union", "thr", "pairs", "cluster", "greedy"]
+MUTATOR_KINDS2 = ["upfold", "unite"]
+OPTION_DEFAULTS2 = {"threshold_band_bytes": 1 << 30, "greedy_band_rows": 4096, "cluster_chunk": 1 << 20, "derive_chunk_bytes": 256 << 20}
+OPTION_VALUES2 = {
+    "threshold_band_bytes": [64 << 10, 1 << 20, 1 << 30], "greedy_band_rows": [1, 7, 129, 4096], "cluster_chunk": [1, 4096, 1 << 20],
+    "derive_chunk_bytes": [1, 1 << 14, 256 << 20],
+}
+FRACS = {"none": 0.0, "1/n": None, "1%": 0.01, "50%": 0.5, "all": 1.0}  # hit fractions of a threshold (None: 1 / n)
+SEED_BASE2 = 0x5E2000
+STEPS2 = 24
 P_CHOICES = [4, 6, 8, 9, 10, 11, 12, 13, 14, 15, 16, 18]
 SEED_BASE = 0x5E0000
 STEPS = 30
@@ -221,9 +245,30 @@ class Model:
                 self.regs[r] = row(spec, self.p, before)
             rr = [r for r, _ in op[1]]
             return min(rr), max(rr) + 1
+        if t == "upfold":
+            _, _, first, src_p, specs = op
+            assert src_p >= self.p and not any(x[0] in ("dup", "bad") for x in specs)
+            new = derive_ref.fold(rows(specs, src_p, None), self.p)
+            self.regs[first : first + len(new)] = new
+            return first, first + len(new)
+        if t == "unite":
+            _, first, groups = op
+            gp, mem = group_arrays(groups, self.n)
+            new = derive_ref.union_groups(self.regs, gp, mem)  # (of the rows BEFORE the operation: the slots may be members)
+            self.regs[first : first + len(new)] = new
+            return first, first + len(new)
         if t == "opt":
             return None
         raise AssertionError(op)
+
+
+def group_arrays(groups, n):
+    """(group_ptr uint64, members uint32) of a list of member lists.  group_ptr starts at len(groups) % 3, not at 0: the
+    members in front of it belong to no group and name no sketch (n + 7), so a library that read them would refuse them"""
+    lead = len(groups) % 3
+    gp = np.cumsum([lead] + [len(g) for g in groups]).astype(np.uint64)
+    mem = np.array([n + 7] * lead + [m for g in groups for m in g], np.uint32)
+    return gp, mem
 
 
 def mutator_kind(op):
@@ -239,6 +284,7 @@ class CtxQueries:
 
     def __init__(self, ctx):
         self.ctx = ctx
+        self.reserved = []  # guarded device buffers allocated ahead of a query (reserve)
 
     def card(self, estim):
         return self.ctx.cardinalities(estim)
@@ -285,8 +331,108 @@ class CtxQueries:
         self.ctx.wait()
         return pd.cpu().numpy()[:span]
 
+    # ---- the kinds of QUERY_KINDS2
+    def _new_guarded(self, items, dtype, misalign=0):
+        import torch
+
+        import guard
+
+        return guard.Guarded(items, dtype, front=4096, back=4096, misalign=misalign, device=torch.device("cuda:0"))
+
+    def reserve(self, op):
+        """The guarded buffers the device form of query `op` will ask for, allocated NOW.  guard.Guarded fills its buffer
+        with torch and then waits for the whole device; a caller that must put no host wait between an asynchronous
+        sketch call and the query reserves before that call (n and p as they are now: sketch calls keep them)."""
+        kind, q = op[1], op[2]
+        if kind not in QUERY_KINDS2 or q.get("form") != "device":
+            return
+        n, p = self.ctx.n, self.ctx.p
+        if kind == "fold":
+            want = [(q["cnt"] << q["new_p"], np.uint8, 0)]
+        elif kind == "union":
+            want = [(len(q["groups"]) << p, np.uint8, 0)]
+        else:  # one label buffer per call and threshold: two thresholds, and a greedy query also asks for the components
+            want = [(n, np.uint32, q.get("misalign", 0))] * (4 if kind == "greedy" else 2)
+        self.reserved += [(w, self._new_guarded(*w)) for w in want]
+
+    def release(self):
+        self.reserved = []
+
+    def _guarded(self, items, dtype, misalign=0):
+        for x, (w, buf) in enumerate(self.reserved):
+            if w == (items, dtype, misalign):
+                del self.reserved[x]
+                return buf
+        return self._new_guarded(items, dtype, misalign)
+
+    def _take(self, buf, what):
+        buf.check(what)
+        assert buf.unwritten() == 0, "%s left %d elements of the span unwritten" % (what, buf.unwritten())
+        return buf.host().copy()
+
+    def fold(self, new_p, first, cnt, form):
+        if form == "host":
+            return self.ctx.fold(new_p, first, cnt)
+        buf = self._guarded(cnt << new_p, np.uint8)
+        self.ctx.fold_device(buf.ptr, new_p, first, cnt)
+        return self._take(buf, "fold_device").reshape(cnt, 1 << new_p)
+
+    def union(self, gp, mem, form):
+        if form == "host":
+            return self.ctx.union_groups(gp, mem)
+        ng = gp.size - 1
+        buf = self._guarded(ng << self.ctx.p, np.uint8)
+        self.ctx.union_groups_device(buf.ptr, gp, mem)
+        return self._take(buf, "union_groups_device").reshape(ng, 1 << self.ctx.p)
+
+    def thr(self, t, rb, re, estim, rt, k):
+        return self.ctx.dist_threshold(t, rb, re, estim=estim, result_type=rt, k=k)
+
+    def pairs(self, lhs, rhs, estim, rt, k):
+        return self.ctx.dist_pairs(lhs, rhs, (rt,), estim=estim, k=k)[0]
+
+    def _labels(self, host, device, t, estim, rt, k, form, misalign):
+        if form == "host":
+            return host(t, estim=estim, result_type=rt, k=k)
+        buf = self._guarded(self.ctx.n, np.uint32, misalign)
+        cnt = device(buf.ptr, t, estim=estim, result_type=rt, k=k)
+        return self._take(buf, device.__name__), cnt
+
+    def cluster(self, t, estim, rt, k, form, misalign=0):
+        return self._labels(self.ctx.cluster_threshold, self.ctx.cluster_threshold_device, t, estim, rt, k, form, misalign)
+
+    def greedy(self, t, estim, rt, k, form, misalign=0):
+        return self._labels(self.ctx.greedy_threshold, self.ctx.greedy_threshold_device, t, estim, rt, k, form, misalign)
+
+    def cluster_of_hits(self, row_ptr, col):
+        return self.ctx.cluster_csr(self.ctx.n, row_ptr, col)
+
+    def overlapped(self, estim, rt, k):
+        """a dist_rows_async into pinned memory in front of what the `with` holds, waited for behind it: its bytes are those
+        of the synchronous dense rows (the check of tests/test_gpu_threshold_sequences.py)"""
+        return _Overlap(self.ctx, estim, rt, k)
+
     def set_option(self, name, value):
         self.ctx.set_option(name, value)
+
+
+class _Overlap:
+    def __init__(self, ctx, estim, rt, k):
+        self.ctx, self.a = ctx, dict(estim=estim, result_type=rt, k=k)
+
+    def __enter__(self):
+        import dashing_amd
+
+        n = self.ctx.n
+        self.span = dashing_amd.tri_span(n, 0, n)
+        self.pin = dashing_amd.PinnedArray(max(self.span, 1), np.float32)
+        self.ctx.dist_rows_async(self.pin.array, 0, n, **self.a)
+
+    def __exit__(self, etype, *a):
+        self.ctx.wait()
+        if etype is None:
+            dense = self.ctx.dist_rows(0, self.ctx.n, **self.a)
+            assert self.pin.array[: self.span].tobytes() == dense.tobytes(), "the overlapped dense rows differ from the synchronous ones"
 
 
 def _answer(Q, regs, kind, q, rt, oracle):
@@ -344,6 +490,9 @@ def run_query(Q, regs, op, oracle, options, log=None, fresh=None):
     kinds that need a knob set it for the query and put the current value back).  `log` collects what was compared."""
     kind, q = op[1], op[2]
     log = [] if log is None else log
+    if kind in QUERY_KINDS2:
+        with Q.overlapped(q["estim"], q["rt"], q["k"]) if q.get("overlap") else _Null():
+            return _run_query2(Q, regs, kind, q, oracle, log, fresh)
     Qs = [Q] + ([fresh] if fresh is not None else [])
     temp = _Null()
     if kind == "range_sorted":  # the range's own key-ordered layout, however short
@@ -390,6 +539,238 @@ def run_query(Q, regs, op, oracle, options, log=None, fresh=None):
         if fresh is not None:
             assert _answer(fresh, regs, kind, q, rt, None)[0].tobytes() == got.tobytes(), "result differs from a fresh context"
         return got
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the kinds of QUERY_KINDS2.  Registers, hits, pair values and labels have ONE answer each: every comparison below is one
+# of bytes or integers, except the two the suite already has between device and oracle VALUES (_close above, and
+# compare_with_oracle of tests/test_gpu_threshold.py).
+#
+# Order matters: the threshold held to the oracle's graph is computed from the MODEL alone, so the call under test runs at
+# it BEFORE anything else touches the context -- it is the call that meets whatever the mutator left behind.  The dense
+# triangle of the same context (the old path) comes after it, and the threshold taken out of that triangle last.
+
+GAP = 2e-6  # the gap of the oracle's values a threshold must sit in (tests/test_gpu_cluster.py, test_against_oracle)
+
+
+def _oracle_values(regs, q, oracle):
+    """(the oracle's values of the triangle under the query's measure, its values of the underlying index or None)"""
+    e, rt, k = q["estim"], q["rt"], q["k"]
+    iw = oracle.dist_tri(regs, e, INDEX_OF[rt], k) if rt in INDEX_OF else None
+    return oracle.dist_tri(regs, e, rt, k), iw
+
+
+def _dense_checked(Q, regs, q, ov, iw, log):
+    """the dense triangle of the same context under the query's measure, compared with the oracle the way a "tri" query
+    is (the index on all pairs first)"""
+    n, e, rt, k = regs.shape[0], q["estim"], q["rt"], q["k"]
+    ig = None
+    if iw is not None:
+        ig = Q.rows(0, n, e, INDEX_OF[rt], k)
+        _close(ig, iw)
+        log.append(("index_full", INDEX_OF[rt], ig.size))
+    got = Q.rows(0, n, e, rt, k)
+    assert got.shape == ov.shape
+    _close(got, ov, ig, iw)
+    log.append(("close", rt, ig is not None, got.size))
+    return got
+
+
+def own_threshold(dense, frac, rt, n):
+    """a value that OCCURS in the dense triangle, at that quantile (quantile_thresholds of tests/test_gpu_cluster.py)"""
+    from test_gpu_cluster import quantile_thresholds
+
+    ts = quantile_thresholds(dense, rt, n)
+    return ts[["none", "all", "1/n", "1%", "50%"].index(frac)] if len(ts) > 1 else ts[0]
+
+
+def jump_floor(iw, rt, k):
+    """The distance measures of INDEX_OF jump where their index is 0, and there device and oracle may take different sides
+    (_close leaves exactly those pairs out).  On either side such a pair lies at a distance of 1 - (4e-9) ** (1 / k) or
+    more: its index is below 1e-9 on the oracle, so below 1e-9 + 1e-12 on the device (_close of the index), the argument
+    x of the distance formulas is the index or 2 j / (1 + j), below 4e-9 either way, and -log(x) / k >= 1 - x ** (1 / k).
+    BELOW that value the pair is no hit for both, and the oracle's graph is the device's; at or above it the oracle's
+    graph does not bind the device's.  Returns that value where the oracle sees such a pair, else None."""
+    if iw is None or rt in thr_ref.SIMILARITY or not (np.abs(iw) < 1e-9).any():
+        return None
+    return 1.0 - (4e-9) ** (1.0 / k)
+
+
+def outside(vals, sim, nothing):
+    """a threshold outside the values by a thousandth of their scale, on the side where nothing passes or everything does"""
+    d = 1e-3 * max(float(np.abs(vals).max()), 1.0)
+    return float(vals.max()) + d if nothing == sim else float(vals.min()) - d  # (similarities pass with v >= t)
+
+
+def gap_choice(ov, frac, sim, n, below=None):
+    """(t, gap): a threshold inside a gap of the oracle's values near the quantile `frac`, and the width of that gap
+    (gap_threshold of tests/test_gpu_cluster.py: the widest gap among the 200 values around the quantile).  Where those
+    200 hold no gap above GAP the window moves outwards, 200 values at a time, the side towards the nearer end first, and
+    stops at the first that does.  `below` (jump_floor, distances only): only the values under it are looked at, so t
+    stays under it.  If no window holds a gap the result is (t, 0.0): there is no oracle graph for that fraction --
+    except for "none" and "all", which ask for the empty and the full graph and get a threshold outside() all values
+    ("all" only without `below`).  No finite value at all: every threshold gives the empty graph.
+
+    Example: JI values 0.9 0.9 0.9 0.2 0.1 (best first), frac "1%" -> the quantile is the first value; its window holds
+    the gap 0.9 | 0.2, so (0.55, 0.7).  Five values of 0.9 and frac "50%": no gap anywhere, (0.9, 0.0); frac "none":
+    (0.901, 0.002)."""
+    from test_gpu_cluster import gap_threshold
+
+    vals = np.asarray(ov, np.float64)
+    vals = vals[np.isfinite(vals)]
+    if not vals.size:
+        return 0.5, float("inf")
+    total = vals.size
+    if below is not None:
+        assert not sim
+        vals = vals[vals < below - 1e-3]
+    f = 1.0 / n if FRACS[frac] is None else FRACS[frac]
+    if vals.size >= 2:
+        at = min(f * total / vals.size, 1.0)  # the same number of values from the best end
+        step = 200.0 / vals.size
+        order = [at] + [g for x in range(1, int(np.ceil(1.0 / step)) + 1)
+                        for g in ((at - x * step, at + x * step) if at <= 0.5 else (at + x * step, at - x * step)) if 0.0 <= g <= 1.0]
+        for g in order:
+            t, gap = gap_threshold(vals, g, sim)
+            if gap > GAP:
+                return t, gap
+    if frac == "none":
+        return (outside(vals, sim, True), float("inf")) if vals.size else (below / 2, below)
+    if frac == "all" and below is None:
+        return outside(vals, sim, False), float("inf")
+    return (float(vals[0]) if vals.size else 0.5), 0.0
+
+
+def _oracle_graph(ov, iw, frac, rt, k, n, log, what):
+    """(t, hits of the oracle's values at t) where the oracle's graph binds the device's, else None (logged)"""
+    sim = rt in thr_ref.SIMILARITY
+    below = jump_floor(iw, rt, k)
+    t, gap = gap_choice(ov, frac, sim, n, below)
+    if not gap > GAP or thr_ref.undecided(ov, t).any() or (below is not None and t >= below):
+        log.append(("skip_oracle", what, frac, gap))
+        return None
+    with np.errstate(invalid="ignore"):
+        hit = (ov.astype(np.float64) >= t) if sim else (ov.astype(np.float64) <= t)
+    return t, hit
+
+
+def pair_list(seed, m, n):
+    rng = np.random.default_rng(seed)
+    lhs, rhs = rng.integers(0, n, m).astype(np.uint32), rng.integers(0, n, m).astype(np.uint32)
+    rep = rng.integers(0, m, m // 4)  # repeats: a quarter of the list says again what another entry says
+    lhs[rep], rhs[rep] = lhs[(rep * 7 + 1) % m], rhs[(rep * 7 + 1) % m]
+    return lhs, rhs
+
+
+def _same_as_fresh(fresh, got, again, what):
+    if fresh is not None:
+        other = again(fresh)
+        a = got if isinstance(got, tuple) else (got,)
+        b = other if isinstance(other, tuple) else (other,)
+        assert len(a) == len(b) and all(np.asarray(x).tobytes() == np.asarray(y).tobytes() for x, y in zip(a, b)), \
+            "%s differs from a fresh context" % what
+
+
+def _run_query2(Q, regs, kind, q, oracle, log, fresh):
+    n = regs.shape[0]
+    if kind == "fold":
+        a = (q["new_p"], q["first"], q["cnt"], q["form"])
+        got = Q.fold(*a)
+        want = derive_ref.fold(regs[q["first"] : q["first"] + q["cnt"]], q["new_p"])
+        assert got.dtype == np.uint8 and got.shape == want.shape and got.tobytes() == want.tobytes(), "fold differs from the model"
+        log.append(("fold", q["form"], got.size))
+        _same_as_fresh(fresh, got, lambda F: F.fold(*a), "fold")
+        return got
+    if kind == "union":
+        gp, mem = group_arrays(q["groups"], n)
+        got = Q.union(gp, mem, q["form"])
+        want = derive_ref.union_groups(regs, gp, mem)
+        assert got.dtype == np.uint8 and got.shape == want.shape and got.tobytes() == want.tobytes(), "union differs from the model"
+        log.append(("union", q["form"], max(len(g) for g in q["groups"])))
+        _same_as_fresh(fresh, got, lambda F: F.union(gp, mem, q["form"]), "union")
+        return got
+    e, rt, k = q["estim"], q["rt"], q["k"]
+    sim = rt in thr_ref.SIMILARITY
+    ov, iw = _oracle_values(regs, q, oracle)  # (the CPU alone: the context has not been touched yet)
+    if kind == "pairs":
+        lhs, rhs = pair_list(q["seed"], q["m"], n)
+        got = Q.pairs(lhs, rhs, e, rt, k)  # first; what it is held to follows
+        assert got.dtype == np.float32
+        dense = _dense_checked(Q, regs, q, ov, iw, log)
+        rect = Q.rect(0, n, 0, n, e, rt, k)
+        assert pairs_ref.same_bits(got, pairs_ref.pick_rect(rect, lhs, rhs)), "pair values differ from the dense rectangle"
+        hi = lhs > rhs
+        assert pairs_ref.same_bits(got[hi], pairs_ref.pick_tri(dense, n, lhs[hi], rhs[hi])), "pair values differ from the dense triangle"
+        log.append(("pairs", lhs.size, int(hi.sum())))
+        _same_as_fresh(fresh, got, lambda F: F.pairs(lhs, rhs, e, rt, k), "pairs")
+        return got
+    if kind == "thr":
+        from test_gpu_threshold import compare_with_oracle
+
+        rb, re = q["rb"], q["re"]
+        found = _oracle_graph(ov, iw, q["frac"], rt, k, n, log, "thr")
+        below = jump_floor(iw, rt, k)
+        fin = ov[np.isfinite(ov)].astype(np.float64)
+        if found:
+            t = found[0]
+        elif fin.size:  # no gap at that fraction: everything for a fraction above a half (never into the jump), else nothing
+            t = outside(fin, sim, not (FRACS[q["frac"]] is not None and FRACS[q["frac"]] > 0.5 and below is None))
+        else:
+            t = 0.5
+        held = not thr_ref.undecided(ov, t).any() and (below is None or t < below)
+        got = Q.thr(t, rb, re, e, rt, k)  # first
+        assert thr_ref.same(got, thr_ref.tri(Q.rows(rb, re, e, rt, k), n, rb, re, t, rt)), "hits differ from the dense rows"
+        if held:
+            lo, span = int(thr_ref.row_lengths(n, 0, rb).sum()), int(thr_ref.row_lengths(n, rb, re).sum())
+            compare_with_oracle(got, ov[lo : lo + span], n, rb, re, t, rt)
+        _dense_checked(Q, regs, q, ov, iw, log)
+        log.append(("thr", q["frac"], int(got[1].size), held, bool(found)))
+        _same_as_fresh(fresh, got, lambda F: F.thr(t, rb, re, e, rt, k), "thr")
+        return got
+    assert kind in ("cluster", "greedy"), kind
+    i, j = np.triu_indices(n, 1)
+    form, mis = q["form"], q.get("misalign", 0)
+    dense = None
+
+    def labels_at(X, t):
+        """(component labels, count) and, for a greedy query, (greedy labels, count) behind them.  The call the query is
+        about runs FIRST: for a greedy query the components are wanted only for the references that follow."""
+        first = X.greedy(t, e, rt, k, form, mis) if kind == "greedy" else ()
+        out = X.cluster(t, e, rt, k, form, mis) + first
+        assert all(np.asarray(x).dtype == np.uint32 and np.shape(x) == (n,) for x in out[0::2]), "labels are uint32 [n]"
+        return tuple(np.asarray(x, np.uint64 if np.ndim(x) == 0 else np.uint32) for x in out)
+
+    def check(t, hit, by_definition):
+        got = labels_at(Q, t)
+        comp, nc = got[0], int(got[1])
+        want, wc = (cluster_ref.labels if by_definition else cluster_ref.labels_fast)(n, i[hit], j[hit])
+        assert np.array_equal(comp, want) and nc == wc, "cluster labels at t = %.9g" % t
+        if kind == "cluster" and not by_definition and int(hit.sum()) <= 20000:
+            # the graph form over the same hits, in edge chunks of "cluster_chunk" (one edge per launch at its smallest value)
+            rp, col, _ = thr_ref.tri(dense, n, 0, n, t, rt)
+            via, vc = Q.cluster_of_hits(rp, col)
+            assert np.array_equal(via, want) and vc == wc, "cluster_csr over the hits at t = %.9g" % t
+        if kind == "greedy":
+            lab, nr = got[2], int(got[3])
+            if by_definition:
+                h = np.zeros((n, n), bool)
+                h[i, j] = hit
+                want, wr = greedy_ref.labels_from_definition(n, h)
+            else:
+                rp, col, _ = thr_ref.tri(dense, n, 0, n, t, rt)
+                want, wr = greedy_ref.labels(n, rp, col)
+            assert np.array_equal(lab, want) and nr == wr, "greedy labels at t = %.9g" % t
+            assert np.array_equal(comp[lab], comp), "a greedy cluster leaves its component at t = %.9g" % t
+        _same_as_fresh(fresh, got, lambda F: labels_at(F, t), kind)
+        return int(got[-1])
+
+    found = _oracle_graph(ov, iw, q["frac"], rt, k, n, log, kind)
+    gcnt = check(found[0], found[1], True) if found else None  # first: the label call itself meets what the mutator left
+    dense = _dense_checked(Q, regs, q, ov, iw, log)
+    t_own = own_threshold(dense, q["frac"], rt, n)
+    cnt = check(t_own, thr_ref.passes(dense, t_own, rt), False)
+    log.append((kind, q["frac"], form, cnt, 1 < cnt < n, bool(found), gcnt is not None and 1 < gcnt < n))
+    return cnt
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -527,3 +908,105 @@ def walk(ops):
 
 def fmt(ops):
     return "\n".join("    %r," % (op,) for op in ops)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the second generator: the old and the new kinds together.  It has its own seed base and draws nothing through generate().
+
+
+def _rowspec2(rng):
+    """a row built at a precision of its own: nothing that refers to the resident matrix ("dup") or that is refused ("bad")"""
+    u = rng.random()
+    if u < 0.15:
+        return ("zero",)
+    if u < 0.3:
+        return ("sat",)
+    if u < 0.45:
+        return ("uni", int(rng.integers(1 << 30)))
+    return ("law", int(rng.integers(1 << 30)), int(10 ** rng.uniform(0.5, 8.6)))
+
+
+def _groups(rng, n, ng):
+    """member lists: about one in four holds 65..300 members (more than a union level takes in one piece: the group is cut
+    into chunks whose partial unions are united again), repeated as needed at small n; about one in seven is empty"""
+    out = []
+    for _ in range(ng):
+        u = rng.random()
+        size = int(rng.integers(65, 301)) if u < 0.25 else (0 if u < 0.4 else int(rng.integers(1, 7)))
+        out.append([int(x) for x in rng.integers(0, n, size)])
+    return out
+
+
+def _mutator2(rng, kind, n, p, attached):
+    if kind in MUTATOR_KINDS:
+        return _mutator(rng, kind, n, p, attached)
+    pre = [("set", n, p, int(rng.integers(1 << 30)), "law")] if attached else []  # (the library writes only into its own)
+    cnt = int(rng.integers(1, min(n - 1, 4) + 1))
+    first = int(rng.integers(0, n - cnt + 1))
+    if kind == "upfold":
+        src_p = int(rng.integers(p, min(p + 6, 18) + 1))
+        form = str(rng.choice(["host", "device"]))
+        return pre + [("upfold", form, first, src_p, [_rowspec2(rng) for _ in range(cnt)])], n, p, False
+    if kind == "unite":
+        return pre + [("unite", first, _groups(rng, n, cnt))], n, p, False
+    raise AssertionError(kind)
+
+
+def _query2(rng, kind, n, p):
+    if kind in QUERY_KINDS:
+        return _query(rng, kind, n)
+    q = {"estim": int(rng.integers(0, 3)), "rt": int(rng.integers(0, 9)), "k": int(rng.choice([15, 21, 31, 32])),
+         "fresh": bool(rng.random() < 0.25), "overlap": bool(rng.random() < 0.25)}
+    form = str(rng.choice(["host", "device"]))
+    if kind == "fold":
+        first = int(rng.integers(0, n))
+        q.update(new_p=int(rng.integers(4, p + 1)), first=first, cnt=int(rng.integers(1, n - first + 1)), form=form)
+    elif kind == "union":
+        q.update(groups=_groups(rng, n, int(rng.integers(1, 6))), form=form)
+    elif kind == "thr":
+        q["rb"] = int(rng.integers(0, n - 1))
+        q["re"] = n if rng.random() < 0.5 else int(rng.integers(q["rb"] + 1, n + 1))
+        q["frac"] = str(rng.choice(sorted(FRACS)))
+    elif kind == "pairs":
+        q.update(seed=int(rng.integers(1 << 30)), m=int(rng.integers(1, 2001)))
+    else:  # cluster, greedy: mostly the thresholds at which the graph is neither empty nor whole
+        q.update(frac=str(rng.choice(["none", "1/n", "1%", "50%", "all"], p=[0.1, 0.3, 0.3, 0.2, 0.1])), form=form,
+                 misalign=int(rng.choice([0, 1, 3])))
+    return ("query", kind, q)
+
+
+def generate2(case, steps=STEPS2):
+    """as generate(), over both tables: a first matrix, then `steps` steps of [option] [mutators] query"""
+    rng = np.random.default_rng(SEED_BASE2 + case)
+    n, p = _shape(rng)
+    ops = [("set", n, p, int(rng.integers(1 << 30)), str(rng.choice(["law", "related", "uniform"])))]
+    attached = False
+    for _ in range(steps):
+        if rng.random() < 0.5:
+            values = OPTION_VALUES2 if rng.random() < 0.7 else OPTION_VALUES
+            name = str(rng.choice(sorted(values)))
+            ops.append(("opt", name, int(rng.choice(values[name]))))
+        for _ in range(int(rng.choice([0, 1, 2], p=[0.15, 0.6, 0.25]))):
+            kind = str(rng.choice(MUTATOR_KINDS2 if rng.random() < 0.3 else MUTATOR_KINDS))
+            more, n, p, attached = _mutator2(rng, kind, n, p, attached)
+            ops += more
+        ops.append(_query2(rng, str(rng.choice(QUERY_KINDS2 if rng.random() < 0.75 else QUERY_KINDS)), n, p))
+    return ops
+
+
+def walk2(ops):
+    """per query of a sequence: (kind, kind of the last register mutator since the previous query or None, names of the
+    options that were set to ANOTHER value since the previous query, whether a dense call is enqueued in front of it)"""
+    out, last_mut, opts = [], None, set()
+    cur = dict(OPTION_DEFAULTS, **OPTION_DEFAULTS2)
+    for op in ops:
+        if op[0] == "query":
+            out.append((op[1], last_mut, frozenset(opts), bool(op[2].get("overlap"))))
+            last_mut, opts = None, set()
+        elif op[0] == "opt":
+            if cur[op[1]] != op[2]:
+                opts.add(op[1])
+            cur[op[1]] = op[2]
+        else:
+            last_mut = mutator_kind(op)
+    return out

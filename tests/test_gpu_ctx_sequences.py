@@ -12,10 +12,18 @@ import numpy as np
 import pytest
 
 import dashing_amd
-from ctx_model import (OPTION_DEFAULTS, OPTION_VALUES, CtxQueries, Model, fasta_files, fmt, generate, matrix, row, rows,
-                       run_query, sequences)  # (tests/ctx_model.py)
+from ctx_model import (OPTION_DEFAULTS, OPTION_DEFAULTS2, OPTION_VALUES, CtxQueries, Model, fasta_files, fmt, generate,
+                       group_arrays, matrix, row, rows, run_query, sequences)  # (tests/ctx_model.py)
 
 pytestmark = pytest.mark.gpu
+
+
+def _query_behind_async(ops, x):
+    """the query that follows ops[x] directly, if ops[x] is a sketch call in the asynchronous form; else None"""
+    op = ops[x]
+    if op[0] in ("sketch", "records") and op[1] == "async" and x + 1 < len(ops) and ops[x + 1][0] == "query":
+        return ops[x + 1]
+    return None
 
 
 class Driver:
@@ -25,10 +33,11 @@ class Driver:
         self.ctx, self.oracle, self.label = ctx, oracle, label
         self.Q = CtxQueries(ctx)
         self.model = Model()
-        self.options = dict(OPTION_DEFAULTS)
+        self.options = dict(OPTION_DEFAULTS, **OPTION_DEFAULTS2)
         self.fresh = None    # the second context (at most one per test)
         self.tensor = None   # the attached torch tensor
         self.pending = None  # (lo, hi, staging) of an asynchronous sketch call whose rows are still to be checked
+        self.upcoming = None  # the query right behind the asynchronous sketch call that is about to be made
         self.done = []
 
     # ---- life cycle
@@ -36,7 +45,7 @@ class Driver:
         try:
             if self.pending:
                 self.ctx.wait()
-            for name, v in OPTION_DEFAULTS.items():
+            for name, v in dict(OPTION_DEFAULTS, **OPTION_DEFAULTS2).items():
                 self.ctx.set_option(name, v)
             if self.tensor is not None:
                 self.ctx.alloc(2, 10)  # the shared context must not keep a pointer into a tensor that is about to go
@@ -53,8 +62,11 @@ class Driver:
         self.close()
 
     def run(self, ops):
-        for op in ops:
+        for x, op in enumerate(ops):
             self.done.append(op)
+            # the query right behind an asynchronous sketch call follows it with no host wait: what its device form needs
+            # from torch is allocated before the call (CtxQueries.reserve)
+            self.upcoming = _query_behind_async(ops, x)
             try:
                 self.step(op)
             except (AssertionError, dashing_amd.DshError) as e:
@@ -71,6 +83,8 @@ class Driver:
             self.flush()
         else:
             self.flush()
+            if self.upcoming is not None:
+                self.Q.reserve(self.upcoming)
             self.mutate(op)
 
     def flush(self):
@@ -133,6 +147,22 @@ class Driver:
                 self.tensor[r] = torch.from_numpy(row(spec, p, before)).to("cuda")
             torch.cuda.synchronize()
             ctx.attach_device(self.tensor.data_ptr(), self.model.n, p)
+        elif t == "upfold":
+            _, form, first, src_p, specs = op
+            src = rows(specs, src_p, None)
+            if form == "host":
+                ctx.upload_folded(src, src_p, first)
+            else:
+                d = torch.from_numpy(src).to("cuda")
+                torch.cuda.synchronize()
+                ctx.upload_folded_device(d.data_ptr(), src_p, len(specs), first)
+        elif t == "unite":  # the unions into a buffer of the caller, and from there into the slots (src_p == p: a copy)
+            _, first, groups = op
+            gp, mem = group_arrays(groups, self.model.n)
+            d = torch.full((len(groups) << p,), 0xA5, dtype=torch.uint8, device="cuda")
+            torch.cuda.synchronize()
+            ctx.union_groups_device(d.data_ptr(), gp, mem)
+            ctx.upload_folded_device(d.data_ptr(), p, len(groups), first)
         else:
             raise AssertionError(op)
         lo, hi = self.model.apply(op, self.oracle)
@@ -167,8 +197,24 @@ class Driver:
             finally:
                 self.ctx.set_option("range_sort_min_rows", self.options["range_sort_min_rows"])
             return
-        fresh = self.fresh_queries() if q.get("fresh") else None
-        return run_query(self.Q, self.model.regs, op, self.oracle, self.options, fresh=fresh)
+        fresh = _Lazy(self.fresh_queries) if q.get("fresh") else None
+        try:
+            return run_query(self.Q, self.model.regs, op, self.oracle, self.options, fresh=fresh)
+        finally:
+            self.Q.release()
+
+
+class _Lazy:
+    """the second context, set up when it is first asked something: behind the first call on the context under test where
+    that matters (its upload would otherwise stand between a mutator and that call)"""
+
+    def __init__(self, make):
+        self._make, self._q = make, None
+
+    def __getattr__(self, name):
+        if self._q is None:
+            self._q = self._make()
+        return getattr(self._q, name)
 
 
 def Qy(kind, estim=2, rt=1, k=31, fresh=True, **kw):

@@ -86,10 +86,13 @@ def test_representatives_are_not_components(ctx):
 
 def test_long_rows_cross_chunks(ctx):
     """rows longer than one chunk of the band kernel (4096 values), starting at every alignment; duplicates of sketch 3 a
-    chunk and two chunks further on"""
+    chunk and two chunks further on.  With greedy_band_rows = 8192 the first band holds 8192 rows and a thread of
+    k_greedy_diag owns eight band columns (t, t + 1024, ...): the duplicates at 4100 and 7777 are then settled inside the
+    band, in the fifth and the eighth column of their threads"""
     n, p = 9000, 8
     regs = synth.synthetic_sketches(n, p, seed=5)
     regs[4100] = regs[3]
+    regs[7777] = regs[3]
     regs[8999] = regs[3]
     ctx.set_sketches(regs)
     dense = ctx.dist_rows(estim=2, result_type=D.JI, k=31)
@@ -103,6 +106,12 @@ def test_long_rows_cross_chunks(ctx):
                 assert got[0][3] == 3 and got[0][4100] == 3 and got[0][8999] == 3
             ctx.set_option("greedy_band_rows", 129)
             assert_labels(ctx.greedy_threshold(t, estim=2, result_type=D.JI, k=31), want, (t, 129))
+            ctx.set_option("greedy_band_rows", 8192)
+            wide = ctx.greedy_threshold(t, estim=2, result_type=D.JI, k=31)
+            assert_labels(wide, want, (t, 8192))
+            if t == 1.0:
+                assert wide[0][3] == 3 and wide[0][4100] == 3 and wide[0][7777] == 3 and wide[0][8999] == 3
+                assert got[0][7777] == 3
             restore(ctx)
     finally:
         restore(ctx)
