@@ -999,6 +999,8 @@ int dsh_get_info(dsh_ctx *c, const char *name, int64_t *out)
     else if (!std::strcmp(name, "emax")) *out = c->emax;
     else if (!std::strcmp(name, "elow")) *out = c->elow;
     else if (!std::strcmp(name, "kc")) *out = c->kc;
+    else if (!std::strcmp(name, "pair_groups")) *out = c->pair_groups;
+    else if (!std::strcmp(name, "pair_round")) *out = c->pp.band_round.empty() ? 0 : c->pp.band_round[0];  // the round the last call's first band ran in
     else if (!std::strcmp(name, "tile")) *out = kTile;
     else if (!std::strcmp(name, "parts_done")) *out = c->parts_done;
     else if (!std::strcmp(name, "parts_signalled")) *out = c->parts_signalled ? 1 : 0;
@@ -1021,7 +1023,7 @@ int dsh_get_info(dsh_ctx *c, const char *name, int64_t *out)
     else if (!std::strcmp(name, "lockstep")) *out = c->planes_valid && use_lockstep(c) ? 1 : 0;
     else if (!std::strcmp(name, "tiles")) *out = (int64_t)c->pp.T.size();
     else if (!std::strcmp(name, "bands")) *out = (int64_t)c->last_bands;
-    else if (!std::strcmp(name, "items")) *out = (int64_t)c->pp.items.size();  // work items of the tile kernel (rounds of 512)
+    else if (!std::strcmp(name, "items")) *out = (int64_t)c->pp.items.size();  // work items of the tile kernel (rounds of 256 x pair_groups)
     else if (!std::strcmp(name, "frag_items")) {  // ... of which overflow fragments (plan.h)
         uint64_t f = 0;
         for (uint32_t x : c->pp.band_frags) f += x;
@@ -1043,7 +1045,13 @@ int dsh_set_option(dsh_ctx *c, const char *name, int64_t v)
     if (!std::strcmp(name, "kc")) {
         if (v != 0 && v != 16 && v != 32) return fail(c, DSH_EINVAL, "kc must be 0 (auto), 16 or 32");
         c->kc_opt = (int)v;
-        c->planes_valid = false;  // Kpad depends on kc
+        c->planes_valid = false;  // Kpad depends on kc (and pair_groups = auto on kc)
+        return DSH_OK;
+    }
+    if (!std::strcmp(name, "pair_groups")) {
+        if (v != 0 && v != 2 && v != 3) return fail(c, DSH_EINVAL, "pair_groups must be 0 (auto), 2 or 3");
+        c->pair_groups_opt = (int)v;
+        c->planes_valid = false;  // three groups force kc = 16: Kpad depends on kc
         return DSH_OK;
     }
     if (!std::strcmp(name, "cum_budget_bytes")) {

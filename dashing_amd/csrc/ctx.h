@@ -161,7 +161,10 @@ struct dsh_ctx {
     int emax = 0, elow = 0, cum_bytes = 4;
     // options
     int kc = 16;      // k-rows per LDS stage in effect (set by prepare from kc_opt)
-    int kc_opt = 0;   // 0 auto: 32 where a plane is at least that long (p >= 10), else 16 (profiles/r3f/lockstep_ab.jsonl)
+    int kc_opt = 0;   // 0 auto: 16 with three items per workgroup (the default); with two, 32 where a plane is at least that long (p >= 10)
+    int pair_groups = 3;      // lockstep tile kernel: work items per workgroup of 256 x pair_groups threads in effect (set by prepare)
+    int pair_groups_opt = 0;  // 0 auto (3, or 2 where kc = 32 is asked for; a band of <= 512 items keeps 2: plan.h) | 2 | 3 (3 needs
+                              // kc = 16: auto kc becomes 16)
     int emax_opt = -1;  // cap of the listed upper tail; -1: auto_list_cap(p, true)
     int elow_opt = -1;  // cap of the listed lower tail; -1: auto_list_cap(p, false)
     int part_band_tiles = 2048;       // a part of at least this many tiles gets its own launch of the tile kernel (plan.cpp)

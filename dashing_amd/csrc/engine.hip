@@ -116,6 +116,9 @@ int prepare(dsh_ctx *c, int estim, int want_sorted, bool card_only, uint64_t wan
     if (!keep_layout) {
         if (c->p > kMaxPCompare)
             return fail(c, DSH_EINVAL, "the compare path takes p <= %d (p=%d: sketching and cardinalities only)", kMaxPCompare, c->p);
+        // three items per workgroup exist at 16-row stages only (LDS, kernels.h)
+        if (c->pair_groups_opt == 3 && c->kc_opt == 32)
+            return fail(c, DSH_EINVAL, "pair_groups = 3 needs kc = 16 (or kc = 0, auto)");
         // the keys are downloaded once per per-sketch pass: a later layout (next row block) needs no
         // device round trip and so does not wait for the work still queued on the stream
         const auto t_h0 = std::chrono::steady_clock::now();
@@ -139,7 +142,10 @@ int prepare(dsh_ctx *c, int estim, int want_sorted, bool card_only, uint64_t wan
         c->cum_bytes = c->p <= 15 ? 2 : 4;
         const uint64_t m = 1ull << c->p;
         c->W = (uint32_t)std::max<uint64_t>(1, m / 32);
-        c->kc = c->kc_opt ? c->kc_opt : (c->W >= 32 ? 32 : 16);
+        // auto: three items per workgroup (and with them 16-row stages) wherever the lockstep kernel runs, unless the
+        // caller asks for 32-row stages (profiles/r7g: -9 % of the step at C3, -3 % at 100 000 x p = 10, -11 % at p = 16)
+        c->pair_groups = c->pair_groups_opt ? c->pair_groups_opt : (c->kc_opt == 32 ? 2 : 3);
+        c->kc = c->pair_groups == 3 ? 16 : c->kc_opt ? c->kc_opt : (c->W >= 32 ? 32 : 16);
         if (want_sorted && !reuse_host_layout) {
             // perm, then (whole collection only) its inverse for the un-permute of the shard path
             const uint64_t nperm = L.perm.size();
@@ -298,6 +304,8 @@ plan::Tuning tuning_of(const dsh_ctx *c)
     tu.cum_budget = c->cum_budget;
     tu.nsplit = c->nsplit;
     tu.lockstep = use_lockstep(c);
+    tu.round_items = 256u * (uint32_t)c->pair_groups;  // a workgroup per CU, pair_groups items each
+    tu.small_round_items = c->pair_groups_opt == 0 && c->pair_groups == 3 ? 512u : 0u;  // auto: a band may keep two where that costs less (plan.h)
     tu.part_band_tiles = (uint32_t)c->part_band_tiles;
     tu.overflow_frag_max_permille = (uint32_t)c->overflow_frag_permille;
     tu.tail_bands = (uint32_t)c->tail_bands;
@@ -445,7 +453,7 @@ int launch_tile_kernel(dsh_ctx *c, const PairRun &r, size_t bi, uint64_t nslots)
         HIPCHK(c, launch_pair_counts_mfma(c->stream, c->kc, c->cum_bytes, (const uint32_t *)c->planes.ptr,
                                           L.Npad, c->Kpad, c->W, L.P, dt, di, ni, c->cum.ptr, nslots));
     else if (use_lockstep(c))
-        HIPCHK(c, launch_pair_counts_lockstep(c->stream, c->kc, c->cum_bytes, (const uint32_t *)c->planes.ptr,
+        HIPCHK(c, launch_pair_counts_lockstep(c->stream, c->kc, (int)(pp.band_round[bi] / 256), c->cum_bytes, (const uint32_t *)c->planes.ptr,
                                               L.Npad, c->Kpad, c->W, L.P, dt, di, ni, bi < pp.band_frags.size() ? pp.band_frags[bi] : 0u,
                                               c->cum.ptr, nslots));
     else

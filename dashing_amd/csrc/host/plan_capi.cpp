@@ -39,11 +39,14 @@ struct Err {
 // layout), 2 sorted_rows (whole sorted layout, rows [rb,re) index plane columns: shards / band-wise kNN), 3 triangle
 // rows in ROW-SORTED parts (the wanted rows one key-ordered run, parts = runs of whole tile rows of that order).
 // stats out: [0] tiles, [1] bands, [2] items, [3] parts with an event, [4] planes per tile x 100, [5] Npad, [6] P,
-// [7] rounds of 512 items summed over the bands (a round of fragments counted as one), [8] overflow fragments.
+// [7] rounds summed over the bands, each in its own round (a round of fragments counted as one), [8] overflow fragments,
+// [9] (with round_items given) the round the first band was planned for.
+// round_items: the tile kernel's round (256 x the items per workgroup, engine.hip); 0 = the planner's default
 // extra: further wanted segments {b0, e0, ...} (plan.h, row sets; modes 0 and 3 with a sorted layout only)
 static int plan_check(uint64_t n, const uint32_t *keys, int mode, int want_sorted, uint64_t rb, uint64_t re, uint64_t cb,
                       uint64_t ce, uint32_t nparts, int want_parts, int p, uint64_t cum_budget, int lockstep, int nsplit,
-                      int ls_item_chunks, const std::vector<uint64_t> &extra, uint64_t *stats, char *err, size_t cap)
+                      int ls_item_chunks, const std::vector<uint64_t> &extra, uint64_t *stats, char *err, size_t cap,
+                      uint32_t round_items = 0)
 {
     Err E{err, cap};
     if (re > n) re = n;
@@ -141,6 +144,8 @@ static int plan_check(uint64_t n, const uint32_t *keys, int mode, int want_sorte
     tu.nsplit = nsplit;
     tu.lockstep = lockstep && tu.W >= (uint32_t)tu.kc;
     tu.ls_item_chunks = ls_item_chunks;
+    if (round_items) tu.round_items = round_items;
+    if (round_items > 512) tu.small_round_items = 512;  // (as engine.hip under pair_groups = auto)
     PairQuery q;
     q.rect = mode == 1;
     q.sorted_rows = mode == 2;
@@ -257,8 +262,11 @@ static int plan_check(uint64_t n, const uint32_t *keys, int mode, int want_sorte
         // overflow fragments (plan.h): the band's LAST band_frags items, each inside one plane, equal in length, at most one
         // round of them; the whole items in front of them a whole number of rounds
         const uint32_t nfr = bi < pp.band_frags.size() ? pp.band_frags[bi] : 0u;
-        if (nfr > bi_.second - bi_.first || nfr > tu.round_items) return E.fail("band %zu: %u fragments", bi, nfr);
-        if (nfr && (!tu.lockstep || (bi_.second - bi_.first - nfr) % tu.round_items)) return E.fail("band %zu: fragments behind %zu whole items", bi, bi_.second - bi_.first - nfr);
+        const uint32_t bri = bi < pp.band_round.size() ? pp.band_round[bi] : 0u;  // the round this band was planned for
+        if (bri != tu.round_items && !(tu.small_round_items && bri == tu.small_round_items)) return E.fail("band %zu: round of %u items", bi, bri);
+        if (bi == 0 && round_items) stats[9] = bri;  // (dshh_plan_check_ri only: its callers pass ten slots)
+        if (nfr > bi_.second - bi_.first || nfr > bri) return E.fail("band %zu: %u fragments", bi, nfr);
+        if (nfr && (!tu.lockstep || (bi_.second - bi_.first - nfr) % bri)) return E.fail("band %zu: fragments behind %zu whole items", bi, bi_.second - bi_.first - nfr);
         stats[8] += nfr;
         for (size_t it = bi_.first; it < bi_.second; ++it) {
             const U4 &I = pp.items[it];
@@ -343,7 +351,8 @@ static int plan_check(uint64_t n, const uint32_t *keys, int mode, int want_sorte
     stats[7] = 0;
     for (size_t b = 0; b < pp.band_items.size(); ++b) {
         const uint32_t nfr = b < pp.band_frags.size() ? pp.band_frags[b] : 0u;
-        stats[7] += (pp.band_items[b].second - pp.band_items[b].first - nfr + tu.round_items - 1) / tu.round_items + (nfr ? 1 : 0);
+        const uint32_t bri = pp.band_round[b];
+        stats[7] += (pp.band_items[b].second - pp.band_items[b].first - nfr + bri - 1) / bri + (nfr ? 1 : 0);
     }
     return 0;
 }
@@ -356,6 +365,17 @@ int dshh_plan_check(uint64_t n, const uint32_t *keys, int mode, int want_sorted,
 {
     return plan_check(n, keys, mode, want_sorted, rb, re, cb, ce, nparts, want_parts, p, cum_budget, lockstep, nsplit, ls_item_chunks,
                       std::vector<uint64_t>(), stats, err, cap);
+}
+
+// the same check with the tile kernel's round given (a multiple of 256: 256 x the items per workgroup)
+int dshh_plan_check_ri(uint64_t n, const uint32_t *keys, int mode, int want_sorted, uint64_t rb, uint64_t re, uint64_t cb,
+                       uint64_t ce, uint32_t nparts, int want_parts, int p, uint64_t cum_budget, int lockstep, int nsplit,
+                       int ls_item_chunks, uint32_t round_items, uint64_t *stats, char *err, size_t cap)
+{
+    Err E{err, cap};
+    if (round_items == 0 || round_items % 256) return E.fail("round_items %u is not a positive multiple of 256", round_items);
+    return plan_check(n, keys, mode, want_sorted, rb, re, cb, ce, nparts, want_parts, p, cum_budget, lockstep, nsplit, ls_item_chunks,
+                      std::vector<uint64_t>(), stats, err, cap, round_items);
 }
 
 // the rows of ONE rank of a row-set table (plan.h): main range + extra segments, row-sorted parts (rowsorted != 0: what a

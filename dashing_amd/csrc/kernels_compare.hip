@@ -24,7 +24,7 @@
 //   k_build_colindex  per 128-column block: its sketches' listed registers bucketed by (position, tail)
 //   k_transform(_t)   uint8 registers [N][m] -> bit-plane matrix planes[K][Npad] (u32 words, row kk = plane*W + word,
 //                     sketch index fastest)
-//   k_pair_counts_ls  128x128-sketch tiles, two per 512-thread workgroup, AND and BCNT batches phase-locked across the waves
+//   k_pair_counts_ls  128x128-sketch tiles, three per 768-thread workgroup, AND and BCNT batches phase-locked across the waves
 //                     of a SIMD (one barrier per k-row); plane rows streamed through double-buffered LDS by LDS-DMA, each
 //                     lane owns an 8x8 block of pairs; writes C(v) per pair.  (k_pair_counts: the free-running form, p < 9)
 //   k_finalize        one lane per pair: C(v) differences + the two tail joins -> histogram (LDS column) -> estimator -> J
@@ -678,8 +678,8 @@ __global__ __launch_bounds__(256) void k_pair_counts(const uint32_t *__restrict_
 // per ~4.42, but an AND stream of one wave next to a BCNT stream of another costs 8.03 cycles per (AND,BCNT) pair
 // instead of 6.49, whatever the order, batch size or register banks inside a wave (profiles/ubench/pair_sched.txt:
 // batch64 8.0, batch64_wg512_bar 6.4-6.8, ..._bar_ldsspread 6.9).  Independent workgroups drift apart; here ONE
-// 512-thread workgroup per CU (8 waves = 2 per SIMD) takes TWO work items (waves 0-3 item 2b, waves 4-7 item 2b+1, each
-// with its own LDS staging) and every k-row is: 64 ANDs into temporaries | 64 BCNTs | s_barrier (round 2 also had a
+// workgroup of 256 * GROUPS threads per CU (4 * GROUPS waves = GROUPS per SIMD) takes GROUPS work items (waves 4g .. 4g+3
+// item GROUPS * b + g, each group with its own LDS staging) and every k-row is: 64 ANDs into temporaries | 64 BCNTs | s_barrier (round 2 also had a
 // barrier between the two batches; it is not needed -- see the k loop -- and costs 4 %).  The
 // operands of the next k-row are read from LDS during the BCNT phase (the AND phase was their last use), one 16-byte
 // read per quarter of the phase (all 8 waves arrive together: 32 ds_read_b128 at once back up the LDS queue).
@@ -690,42 +690,53 @@ __global__ __launch_bounds__(256) void k_pair_counts(const uint32_t *__restrict_
 // Measured per k-row (s_memtime, profiles/r2k): 955 cycles in the k loop + 40 per-chunk overhead, of which 850 are the
 // two phases and their barriers, ~65 the LDS operand reads, ~40 the arrival of the DMA data; folding the chunk
 // transition into the last row of a chunk (no extra barrier, no exposed LDS latency) was slower (14.7 vs 14.4 ms).
-// A half whose item is shorter (or missing) keeps executing the same instruction stream on stale LDS data -- the
+// A group whose item is shorter (or missing) keeps executing the same instruction stream on stale LDS data -- the
 // barriers need every wave -- and simply stores nothing.
+// GROUPS = 3 (the default, profiles/r7g): a third wave per SIMD fills the issue slots the other two leave at s_waitcnt
+// and LDS issue, and one barrier covers 1.5 x the VALU work: 6.34 cycles per (AND, BCNT) pair instead of 7.16 at C3
+// (10.45 -> 9.2 ms).  155 VGPRs fit the 168 of three waves per SIMD; three double-buffered stagings fit the CU's 160 KiB
+// of LDS at KC = 16 only (96 KiB), so GROUPS = 3 exists for KC = 16.  GROUPS = 2 compiles to the instruction stream the
+// kernel had before the parameter existed and stays selectable (option pair_groups): the tests hold the default to it.
 // FRAG: the instance for overflow fragments (plan.h) -- items that are pieces of ONE plane; their partial counts are
 // added to the plane's C(v) block (cleared by k_zero_frag_blocks) instead of stored.  A launch of its own behind the
 // whole items', so that the kernel of every other call stays exactly as it was.
-template <int KC, typename CT, bool FRAG = false>
-__global__ __launch_bounds__(512) void k_pair_counts_ls(const uint32_t *__restrict__ planes, uint32_t Npad,
-                                                         uint32_t Kpad, uint32_t W, uint32_t P,
-                                                         const uint4 *__restrict__ tiles,
-                                                         const uint4 *__restrict__ items, uint32_t nitems,
-                                                         CT *__restrict__ cum, uint64_t nslots)
+template <int KC, typename CT, bool FRAG = false, int GROUPS = 2>
+__global__ __launch_bounds__(256 * GROUPS) void k_pair_counts_ls(const uint32_t *__restrict__ planes, uint32_t Npad,
+                                                                  uint32_t Kpad, uint32_t W, uint32_t P,
+                                                                  const uint4 *__restrict__ tiles,
+                                                                  const uint4 *__restrict__ items, uint32_t nitems,
+                                                                  CT *__restrict__ cum, uint64_t nslots)
 {
-    extern __shared__ __attribute__((aligned(16))) uint32_t smem[];  // [half][2][A|B][KC][128]
+    static_assert(GROUPS == 2 || (GROUPS == 3 && KC == 16), "three groups: 16-row stages only (LDS)");
+    extern __shared__ __attribute__((aligned(16))) uint32_t smem[];  // [group][2][A|B][KC][128]
     constexpr int NPASS = KC / 8;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave8 = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int half = wave8 >> 2, wave = wave8 & 3;
+    const int grp = wave8 >> 2, wave = wave8 & 3;
     const int ii = (wave >> 1) * 64 + (lane >> 3) * 8;
     const int jj = (wave & 1) * 64 + (lane & 7) * 8;
-    const uint32_t mine = 2 * blockIdx.x + (uint32_t)half, other = 2 * blockIdx.x + (uint32_t)(1 - half);
+    const uint32_t mine = GROUPS * blockIdx.x + (uint32_t)grp;
     uint4 item = make_uint4(0, 0, 0, 0);
     if (mine < nitems) item = items[mine];
-    uint32_t other_len = 0;
-    if (other < nitems) {
-        const uint4 o = items[other];
-        other_len = o.z > o.y ? o.z - o.y : 0;
+    uint32_t other_len = 0;  // the longest item of the workgroup's other groups
+#pragma unroll
+    for (int g = 1; g < GROUPS; ++g) {
+        const uint32_t other = GROUPS * blockIdx.x + (uint32_t)(GROUPS == 2 ? 1 - grp : (grp + g) % GROUPS);
+        if (other < nitems) {
+            const uint4 o = items[other];
+            const uint32_t len = o.z > o.y ? o.z - o.y : 0;
+            other_len = len > other_len ? len : other_len;
+        }
     }
     const uint32_t my_len = item.z > item.y ? item.z - item.y : 0;
-    const uint32_t trips = my_len > other_len ? my_len : other_len;
+    const uint32_t trips = my_len > other_len ? my_len : other_len;  // the same number in every wave of the workgroup
     const uint32_t tile_id = item.x;
     const uint4 tile = tiles[tile_id];
     const uint64_t lrow = (uint64_t)(wave * 2 + (lane >> 5));
     const uint32_t *gA = planes + lrow * Npad + (uint64_t)tile.x * kTile + (lane & 31) * 4;
     const uint32_t *gB = planes + lrow * Npad + (uint64_t)tile.y * kTile + (lane & 31) * 4;
     const uint64_t pass_stride = (uint64_t)8 * Npad;
-    uint32_t *hsm = smem + half * (4 * KC * 128);
+    uint32_t *hsm = smem + grp * (4 * KC * 128);
     const uint32_t lds_base = (uint32_t)(uintptr_t)(lds_ptr_t)hsm + wave * 1024;  // bytes
     auto stage = [&](uint32_t chunk, int buf) {
         const uint32_t la = lds_base + buf * (2 * KC * 512);
@@ -780,6 +791,10 @@ __global__ __launch_bounds__(512) void k_pair_counts_ls(const uint32_t *__restri
         // k-row, after the BCNT batch.  Measured on C3 (profiles/r3f): barrier after both batches 11.40 ms; after the BCNT
         // batch only 10.91 (both waves of a SIMD start their ANDs together and are still together when the BCNTs begin);
         // after the AND batch only 14.2; every second row 12.3; + full unroll 10.55; + KC = 32 10.41.
+        // Barrier safety: every wave of the workgroup runs `trips` trips of this loop and, in each, the same KC
+        // s_barrier behind the __syncthreads above.  trips depends only on blockIdx.x, nitems and the lengths of the
+        // workgroup's items, which every wave reads alike; the only exit in front of the loop is the workgroup-uniform
+        // trips == 0.  Nothing inside a trip may depend on `active` or on the wave except data.
 #pragma unroll
         for (uint32_t kk = 0; kk < (uint32_t)KC; ++kk) {
             {
@@ -811,7 +826,7 @@ __global__ __launch_bounds__(512) void k_pair_counts_ls(const uint32_t *__restri
             flush_due = active && it + 1 == my_len;
             flush_pl = ch / cpp;
         } else {
-            flush_due = active && ((ch + 1) & (cpp - 1)) == 0;  // the same chunk in both halves (items are whole planes)
+            flush_due = active && ((ch + 1) & (cpp - 1)) == 0;  // the same chunk in every group (items are whole planes)
             flush_pl = (ch + 1) / cpp - 1;
         }
     }
@@ -1933,34 +1948,36 @@ hipError_t launch_pair_counts(hipStream_t st, int kc, int cum_bytes, const uint3
     }
 }
 
-template <int KC, typename CT>
+// whole items (FRAG = false) or overflow fragments of the lockstep kernel: GROUPS items per workgroup of 256 * GROUPS threads
+template <int KC, typename CT, bool FRAG, int GROUPS>
 static hipError_t launch_pcl(hipStream_t st, const uint32_t *planes, uint32_t Npad, uint32_t Kpad, uint32_t W,
                              uint32_t P, const uint4 *tiles, const uint4 *items, uint32_t nitems, void *cum,
                              uint64_t nslots)
 {
-    const size_t lds = (size_t)KC * 4096;  // two halves, each double-buffered A|B
-    hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void *>(k_pair_counts_ls<KC, CT>), lds);
+    const size_t lds = (size_t)GROUPS * KC * 2048;  // per group: double-buffered A|B
+    hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void *>(k_pair_counts_ls<KC, CT, FRAG, GROUPS>), lds);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((k_pair_counts_ls<KC, CT>), dim3((nitems + 1) / 2), dim3(512), lds, st, planes, Npad, Kpad, W,
-                       P, tiles, items, nitems, reinterpret_cast<CT *>(cum), nslots);
+    hipLaunchKernelGGL((k_pair_counts_ls<KC, CT, FRAG, GROUPS>), dim3((nitems + GROUPS - 1) / GROUPS), dim3(256 * GROUPS), lds, st,
+                       planes, Npad, Kpad, W, P, tiles, items, nitems, reinterpret_cast<CT *>(cum), nslots);
     return hipGetLastError();
 }
 
-template <int KC, typename CT>
-static hipError_t launch_pcl_frag(hipStream_t st, const uint32_t *planes, uint32_t Npad, uint32_t Kpad, uint32_t W, uint32_t P,
-                                  const uint4 *tiles, const uint4 *frags, uint32_t nfrag, void *cum, uint64_t nslots)
+// the instance for (kc, groups); three groups exist at 16-row stages only (32-row stages of three groups: 192 KiB of LDS)
+template <typename CT, bool FRAG>
+static hipError_t launch_pcl_sel(hipStream_t st, int kc, int groups, const uint32_t *planes, uint32_t Npad, uint32_t Kpad,
+                                 uint32_t W, uint32_t P, const uint4 *tiles, const uint4 *items, uint32_t nitems, void *cum,
+                                 uint64_t nslots)
 {
-    const size_t lds = (size_t)KC * 4096;
-    hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void *>(k_pair_counts_ls<KC, CT, true>), lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((k_pair_counts_ls<KC, CT, true>), dim3((nfrag + 1) / 2), dim3(512), lds, st, planes, Npad, Kpad, W, P, tiles, frags,
-                       nfrag, reinterpret_cast<CT *>(cum), nslots);
-    return hipGetLastError();
+#define DSH_PCL(KC, GROUPS) launch_pcl<KC, CT, FRAG, GROUPS>(st, planes, Npad, Kpad, W, P, tiles, items, nitems, cum, nslots)
+    if (groups == 3) return kc == 16 ? DSH_PCL(16, 3) : hipErrorInvalidValue;
+    if (groups != 2) return hipErrorInvalidValue;
+    return kc == 16 ? DSH_PCL(16, 2) : kc == 32 ? DSH_PCL(32, 2) : hipErrorInvalidValue;
+#undef DSH_PCL
 }
 
-hipError_t launch_pair_counts_lockstep(hipStream_t st, int kc, int cum_bytes, const uint32_t *planes, uint32_t Npad,
-                                       uint32_t Kpad, uint32_t W, uint32_t P, const uint4 *tiles, const uint4 *items,
-                                       uint32_t nitems, uint32_t nfrag, void *cum, uint64_t nslots)
+hipError_t launch_pair_counts_lockstep(hipStream_t st, int kc, int groups, int cum_bytes, const uint32_t *planes,
+                                       uint32_t Npad, uint32_t Kpad, uint32_t W, uint32_t P, const uint4 *tiles,
+                                       const uint4 *items, uint32_t nitems, uint32_t nfrag, void *cum, uint64_t nslots)
 {
     if (nitems == 0 || Kpad == 0) return hipSuccess;
     if (nfrag) {  // the band's last nfrag items are overflow fragments: the whole items first, then the fragments' launch
@@ -1971,28 +1988,15 @@ hipError_t launch_pair_counts_lockstep(hipStream_t st, int kc, int cum_bytes, co
         else hipLaunchKernelGGL((k_zero_frag_blocks<uint32_t>), dim3(nfrag), dim3(256), 0, st, fr, W / (uint32_t)kc, (uint32_t *)cum, nslots);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
-        e = launch_pair_counts_lockstep(st, kc, cum_bytes, planes, Npad, Kpad, W, P, tiles, items, nitems - nfrag, 0, cum, nslots);
+        e = launch_pair_counts_lockstep(st, kc, groups, cum_bytes, planes, Npad, Kpad, W, P, tiles, items, nitems - nfrag, 0, cum, nslots);
         if (e != hipSuccess) return e;
-        if (cum_bytes == 2)
-            return kc == 16 ? launch_pcl_frag<16, uint16_t>(st, planes, Npad, Kpad, W, P, tiles, fr, nfrag, cum, nslots)
-                 : kc == 32 ? launch_pcl_frag<32, uint16_t>(st, planes, Npad, Kpad, W, P, tiles, fr, nfrag, cum, nslots) : hipErrorInvalidValue;
-        return kc == 16 ? launch_pcl_frag<16, uint32_t>(st, planes, Npad, Kpad, W, P, tiles, fr, nfrag, cum, nslots)
-             : kc == 32 ? launch_pcl_frag<32, uint32_t>(st, planes, Npad, Kpad, W, P, tiles, fr, nfrag, cum, nslots) : hipErrorInvalidValue;
+        if (cum_bytes == 2) return launch_pcl_sel<uint16_t, true>(st, kc, groups, planes, Npad, Kpad, W, P, tiles, fr, nfrag, cum, nslots);
+        return launch_pcl_sel<uint32_t, true>(st, kc, groups, planes, Npad, Kpad, W, P, tiles, fr, nfrag, cum, nslots);
     }
     if (W < (uint32_t)kc)  // plane boundaries inside a chunk (p < 9): the kernel with the in-loop flush
         return launch_pair_counts(st, kc, cum_bytes, planes, Npad, Kpad, W, P, tiles, items, nitems, cum, nslots);
-    if (cum_bytes == 2) {
-        switch (kc) {
-        case 16: return launch_pcl<16, uint16_t>(st, planes, Npad, Kpad, W, P, tiles, items, nitems, cum, nslots);
-        case 32: return launch_pcl<32, uint16_t>(st, planes, Npad, Kpad, W, P, tiles, items, nitems, cum, nslots);
-        default: return hipErrorInvalidValue;
-        }
-    }
-    switch (kc) {
-    case 16: return launch_pcl<16, uint32_t>(st, planes, Npad, Kpad, W, P, tiles, items, nitems, cum, nslots);
-    case 32: return launch_pcl<32, uint32_t>(st, planes, Npad, Kpad, W, P, tiles, items, nitems, cum, nslots);
-    default: return hipErrorInvalidValue;
-    }
+    if (cum_bytes == 2) return launch_pcl_sel<uint16_t, false>(st, kc, groups, planes, Npad, Kpad, W, P, tiles, items, nitems, cum, nslots);
+    return launch_pcl_sel<uint32_t, false>(st, kc, groups, planes, Npad, Kpad, W, P, tiles, items, nitems, cum, nslots);
 }
 
 hipError_t launch_finalize(hipStream_t st, const FinalizeLaunch &f)

@@ -635,6 +635,7 @@ bool build_tiles(const Layout &L, const PairQuery &job, const Tuning &tu, PairPl
     pp.segs.clear();
     pp.items.clear();
     pp.band_frags.clear();
+    pp.band_round.clear();
     pp.nparts = 0;
     pp.max_band = 0;
     const uint32_t NT = L.Npad / kTile;
@@ -828,11 +829,10 @@ bool build_tiles(const Layout &L, const PairQuery &job, const Tuning &tu, PairPl
 
 // overflow fragments (plan.h, Tuning): of `ni` one-plane items, how many are cut (the last `over`) and into how many
 // fragments each (`f`); over = 0: none
-static void overflow_fragments(const Tuning &tu, uint32_t cpp, uint64_t piece, uint64_t ni, uint64_t &over, uint32_t &f)
+static void overflow_fragments(const Tuning &tu, uint64_t RI, uint32_t cpp, uint64_t piece, uint64_t ni, uint64_t &over, uint32_t &f)
 {
     over = 0;
     f = 1;
-    const uint64_t RI = tu.round_items;
     if (!tu.lockstep || tu.nsplit != 0 || RI == 0 || tu.overflow_frag_max_permille == 0 || piece != cpp || cpp < 2 || ni == 0) return;
     // (a band of less than a round -- the tail band of an exchange call can hold a few dozen items -- is all overflow)
     const uint64_t o = ni % RI;
@@ -842,6 +842,13 @@ static void overflow_fragments(const Tuning &tu, uint32_t cpp, uint64_t piece, u
     if (ff < 2) return;
     over = o;
     f = ff;
+}
+
+// the round a band of `ni` items runs in (plan.h, Tuning::small_round_items)
+static uint32_t band_round_items(const Tuning &tu, uint64_t ni)
+{
+    if (!tu.lockstep || tu.small_round_items == 0 || tu.small_round_items >= tu.round_items) return tu.round_items;
+    return ni <= 2 * (uint64_t)tu.small_round_items ? tu.small_round_items : tu.round_items;
 }
 
 // work items of band bi, appended to pp.items (bands in order): {tile index in band, chunk begin, chunk end, fragment?}
@@ -868,7 +875,7 @@ void build_band_items(const Tuning &tu, PairPlan &pp, size_t bi)
     piece = (piece + cpp - 1) / cpp * cpp;
     const size_t i0 = I.size();
     const uint32_t maxpieces = (uint32_t)((maxlen + piece - 1) / piece);
-    // Piece-major, so that neighbours in launch order share planes.  The lockstep kernel pairs consecutive items: inside
+    // Piece-major, so that neighbours in launch order share planes.  The lockstep kernel runs 2 or 3 consecutive items side by side: inside
     // a group of pieces equal lengths are kept together, longest first, tiles in order (only a tile's last piece can be
     // shorter; with whole-plane pieces every item of the group has the same length and nothing moves).  One counting
     // pass, one placing pass: at 100 000 sketches the host plans 306 000 tiles and nothing hides it (profiles/r4y).
@@ -908,7 +915,10 @@ void build_band_items(const Tuning &tu, PairPlan &pp, size_t bi)
     // overflow fragments: the band's last `over` items (whole planes all of them: piece = one plane) in f pieces each
     uint64_t over = 0;
     uint32_t f = 1;
-    overflow_fragments(tu, cpp, piece, I.size() - i0, over, f);
+    const uint32_t RI = band_round_items(tu, I.size() - i0);
+    overflow_fragments(tu, RI, cpp, piece, I.size() - i0, over, f);
+    if (pp.band_round.size() <= bi) pp.band_round.resize(bi + 1, 0);
+    pp.band_round[bi] = RI;
     if (pp.band_frags.size() <= bi) pp.band_frags.resize(bi + 1, 0);
     pp.band_frags[bi] = 0;
     if (over) {
@@ -985,7 +995,7 @@ uint64_t band_item_count(const Tuning &tu, const PairPlan &pp, size_t bi)
     }
     uint64_t over = 0;
     uint32_t f = 1;
-    overflow_fragments(tu, cpp, piece, cnt, over, f);
+    overflow_fragments(tu, band_round_items(tu, cnt), cpp, piece, cnt, over, f);
     return cnt - over + over * f;
 }
 

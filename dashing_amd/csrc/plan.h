@@ -173,12 +173,21 @@ struct Tuning {
     int ls_item_chunks = 64;  // lockstep kernel: work items of at most about this many K-chunks (whole planes; 16/32/64 within noise, profiles/rd5j)
     uint32_t part_band_tiles = 2048;  // a part of at least this many tiles also ends the band of the tile kernel
     // Tail bands (jobs with parts = the exchange; jobs of at most 64 rounds of one-plane items, in bands of at most 16).  The lockstep
-    // tile kernel runs in ROUNDS of round_items work items (2 per workgroup, one workgroup per CU); a rank's parts only
+    // tile kernel runs in ROUNDS of round_items work items (2 or 3 per workgroup, one workgroup per CU: engine.hip sets
+    // 256 x the context's pair_groups; the default here is the planner's own, for its host-only tests); a rank's parts only
     // become final during k_finalize, i.e. after the whole tile kernel, and its link then needs longer for them than
     // k_finalize takes.  So the tile kernel is cut into a head band and `tail_bands` tail bands at multiples of a round
     // (a cut elsewhere rounds every band up: +1 round, profiles/r4i): the head's parts travel while the tails compute.
     // Each tail takes tail_permille of the rounds left; no cut is made if it would add a round.
     uint32_t round_items = 512;
+    // A band of at most two rounds of small_round_items keeps that round (two items per workgroup where round_items
+    // means three; engine.hip launches what PairPlan::band_round says), fragments and all.  Three items per workgroup are
+    // measured on bands of many rounds (profiles/r7g), where they win 13 %; a round lasts as long as one item, and an item
+    // at three waves per SIMD takes 1.33 of one at two (3 x 6.34 against 2 x 7.16 cycles per pair), so a band of up to
+    // 512 items would take a third longer and one of 769 .. 1 024 items 2.65 instead of 2.0.  In between (513 .. 768) the
+    // better round depends on the fragments; such bands last 0.2 ms and keep the schedule they had.  0: always
+    // round_items (the option pair_groups names a number).
+    uint32_t small_round_items = 0;
     // Overflow fragments: a band of one-plane items whose count is a little above a multiple of a round would spend a
     // whole round on the few items left over (3 614 items = 7 rounds + 30 items: 1.56 ms instead of 1.37).  When the
     // overflow is at most overflow_frag_max_permille of a round, those items are cut into f equal fragments of a plane
@@ -202,6 +211,7 @@ struct PairPlan {
     std::vector<U4> T;                                   // {row block, col block, plane begin, plane end}, launch order
     std::vector<std::pair<size_t, size_t>> bands;        // tile ranges, one tile-kernel launch each
     std::vector<std::pair<size_t, size_t>> band_items;   // item ranges of the bands
+    std::vector<uint32_t> band_round;                    // the round each band's items were planned for (Tuning::small_round_items)
     std::vector<std::vector<Seg>> segs;                  // per band
     std::vector<U4> items;                               // {tile index in band, chunk begin, chunk end, 1 for a fragment of a plane}
     std::vector<uint32_t> band_frags;                    // per band: its LAST band_frags[b] items are fragments

@@ -673,10 +673,17 @@ int dsh_finalize_phase_cycles(dsh_ctx *ctx, uint64_t *out16);
  *                 "range_sort_min_rows"     row ranges shorter than this keep the cached identity layout (default 1024)
  *                 "emax" / "elow"           caps of the listed upper / lower register tail, 0..255, -1 auto (per precision);
  *                                           0 / 0 = bit-planes over the whole value range (adversarial register laws)
- *   tile kernel   "kc"                      0 auto | 16 | 32 k-rows per LDS stage
+ *   tile kernel   "kc"                      0 auto | 16 | 32 k-rows per LDS stage (auto: 16 with three work items per
+ *                                           workgroup; with two, 32 where a plane has at least 32 words)
+ *                 "pair_groups"             0 auto | 2 | 3 work items per workgroup of 256 x that many threads (waves per
+ *                                           SIMD); auto = 3, or 2 where kc = 32 is asked for.  3 needs 16-row stages (LDS):
+ *                                           with kc = 32 the next compare call fails with DSH_EINVAL.  A round of the
+ *                                           kernel is 256 x pair_groups items.  Under auto a launch of at most 512 items
+ *                                           (one round of two) still runs two per workgroup; 3 given by name always
+ *                                           runs three.  Results do not depend on it.
  *                 "nsplit"                  pieces per tile, 0 auto (work items of at most 64 chunks)
  *                 "overflow_frag_permille"  0..1000 (default 500): a band whose one-plane work items number at most that
- *                                           share of a round above a multiple of 512 has the items left over cut into
+ *                                           share of a round above a multiple of a round has the items left over cut into
  *                                           fragments that ADD their counts; 0 = never
  *   exchange      "part_band_tiles"         a part of at least this many tiles also ends a launch of the tile kernel (2048)
  *                 "xch_tail_bands"          0..8 (default 2): a job with parts of at most 64 rounds has its tile kernel cut
@@ -695,7 +702,7 @@ int dsh_finalize_phase_cycles(dsh_ctx *ctx, uint64_t *out16);
  * ("pair_mfma" exists only in a library built with `make WHATIF=1`: the matrix-core what-if the north star excludes.) */
 int dsh_set_option(dsh_ctx *ctx, const char *name, int64_t value);
 /* Derived state of the last prepared sketch matrix: "planes" (dense bit-planes used), "vlo",
- * "vhi", "pbase", "threshold", "emax", "elow", "kc", "tile", "npad", "kpad", "cum_bytes", "sorted", "ncols", "lockstep", "tiles", "bands", "items" (work items of the tile kernel),
+ * "vhi", "pbase", "threshold", "emax", "elow", "kc", "pair_groups" (as the last prepare put them into effect), "pair_round" (work items per round of the last dist call's first launch of the tile kernel: 256 x the items per workgroup it ran with), "tile", "npad", "kpad", "cum_bytes", "sorted", "ncols", "lockstep", "tiles", "bands", "items" (work items of the tile kernel),
  * "words_per_plane", "avg_tile_planes_x100" (of the last dist call), "frag_items", "parts_done", "parts_signalled",
  * "place_kernel_us" (with profiling on: device time of the last dsh_exchange_place_device's placement kernel),
  * "sketch_kernel_us" / "fastx_decode_us" (with profiling on: k_sketch / the FASTA-FASTQ decode kernels of the last sketch call). */

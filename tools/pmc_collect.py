@@ -55,6 +55,9 @@ def source_hash():
     return h.hexdigest()
 
 
+PASS_LIMIT_S = 300
+
+
 def short_name(k):
     k = re.sub(r"\(.*$", "", k)
     k = k.replace("void ", "")
@@ -69,6 +72,7 @@ def run_pass(name, counters, cmd, env, outdir):
         argv = ["rocprofv3", "--kernel-trace", "--stats", "-d", d, "-o", "p", "--output-format", "csv", "--"] + cmd
     else:
         argv = ["rocprofv3", "--pmc"] + counters + ["-d", d, "-o", "p", "--output-format", "csv", "--"] + cmd
+    argv = ["timeout", "-k", "10", str(PASS_LIMIT_S)] + argv  # every pass under a limit of its own
     e = dict(os.environ)
     e.update(env)
     e["TMPDIR"] = "/tmp"
@@ -95,6 +99,10 @@ def main():
         cmd = base + ["--steps", str(steps), "--warmup", "1" if name == "kt" else "0"]
         rc, d = run_pass(name, PASSES.get(name), cmd, env, outdir)
         summary["passes"][name] = {"rc": rc}
+        if rc != 0:  # a pass that failed, faulted or ran into its limit ends the collection: nothing more is started on the device
+            json.dump(summary, open(os.path.join(outdir, "pmc_summary.json"), "w"), indent=1)
+            sys.stderr.write("pmc_collect: pass %s ended with status %d (see %s): stopping\n" % (name, rc, os.path.join(outdir, name + ".log")))
+            return 1
         if name == "kt":
             for f in glob.glob(os.path.join(d, "**", "*kernel_stats.csv"), recursive=True):
                 shutil.copy(f, os.path.join(outdir, "kernel_stats.csv"))

@@ -87,6 +87,36 @@ def body(order, tmp_bank_shift=0, ops="and+bcnt", barrier=False, lds=-1, spread=
     return lines
 
 
+def body_pp(rows, first_row):
+    """one PHASE PAIR of the lockstep tile kernel over `rows` k-rows (1 or 2): rows x 64 ANDs | rows x 64 BCNTs with the
+    next operands' ds_read_b128 spread over them (one in front of every 16 BCNTs) | ONE s_barrier.  Row 1's operands are
+    v32..v47 and its temporaries the 64 registers behind row 0's."""
+    lines = ["s_waitcnt lgkmcnt(0)"]
+    pairs = [(r, c) for r in range(8) for c in range(8)]
+    ops = [(A0, B0), (A1, B1)]
+    for k in range(rows):
+        for i, (r, c) in enumerate(pairs):
+            lines.append("v_and_b32 v%d, v%d, v%d" % (TMP0 + 64 * k + i, ops[k][0] + r, ops[k][1] + c))
+    for k in range(rows):
+        o = ((first_row + k) % 16) * 512
+        a, b = ops[k]
+        rd = ["ds_read_b128 v[%d:%d], v8 offset:%d" % (a, a + 3, o), "ds_read_b128 v[%d:%d], v8 offset:%d" % (a + 4, a + 7, o + 16),
+              "ds_read_b128 v[%d:%d], v9 offset:%d" % (b, b + 3, 8192 + o), "ds_read_b128 v[%d:%d], v9 offset:%d" % (b + 4, b + 7, 8192 + o + 16)]
+        for i, (r, c) in enumerate(pairs):
+            if i % 16 == 0:
+                lines.append(rd.pop(0))
+            lines.append("v_bcnt_u32_b32 v%d, v%d, v%d" % (ACC0 + 8 * r + c, TMP0 + 64 * k + i, ACC0 + 8 * r + c))
+    lines.append("s_barrier")
+    return lines
+
+
+# one barrier per phase pair and the spread LDS reads, as k_pair_counts_ls issues them: name, k-rows per phase pair, threads
+PP_VARIANTS = [
+    ("pp_batch64_wg512", 1, 512),    # two waves per SIMD: k_pair_counts_ls<.., GROUPS = 2>
+    ("pp_batch128_wg512", 2, 512),   # two k-rows per phase pair
+    ("pp_batch64_wg768", 1, 768),    # three waves per SIMD, GROUPS = 3 (168 VGPRs: registers renumbered, see kernel_pp)
+]
+
 VARIANTS = [
     # name, order, tmp_bank_shift, ops
     ("alt", 1, 0, "and+bcnt"),
@@ -182,12 +212,76 @@ __global__ __launch_bounds__(%d) void k_%s(uint32_t *out, uint64_t *cyc, uint32_
 """ % (wg, name, asm, clob)
 
 
+def kernel_pp(name, rows, wg):
+    """a PP_VARIANTS kernel.  768 threads leave 168 VGPRs per lane: accumulators and temporaries move down to v32..v95 and
+    v96..v159 (the second k-row's operands, v32..v47, are not needed with one row per phase pair)."""
+    global ACC0, TMP0
+    keep = (ACC0, TMP0)
+    if wg > 512:
+        assert rows == 1
+        ACC0, TMP0 = 32, 96
+    try:
+        used = [8, 9] + list(range(A0, B0 + 8)) + (list(range(A1, B1 + 8)) if rows == 2 else []) + list(range(ACC0, ACC0 + 64)) + list(range(TMP0, TMP0 + 64 * rows))
+        clob = ", ".join('"v%d"' % i for i in used)
+        L = []
+        for r in range(8):
+            L.append("v_mul_lo_u32 v%d, %%[tid], %%[m%d]" % (A0 + r, r % 2))
+            L.append("v_xor_b32 v%d, v%d, %%[seed]" % (A0 + r, A0 + r))
+            L.append("v_mul_lo_u32 v%d, %%[tid], %%[m%d]" % (B0 + r, (r + 1) % 2))
+            L.append("v_add_u32 v%d, v%d, %%[seed]" % (B0 + r, B0 + r))
+        L.append("v_lshrrev_b32 v8, 3, %[tid]")
+        L.append("v_and_b32 v8, 7, v8")
+        L.append("v_lshlrev_b32 v8, 5, v8")
+        L.append("v_and_b32 v9, 7, %[tid]")
+        L.append("v_lshlrev_b32 v9, 5, v9")
+        if rows == 2:
+            for r in range(8):
+                L.append("v_mul_lo_u32 v%d, v%d, %%[m1]" % (A1 + r, A0 + r))
+                L.append("v_mul_lo_u32 v%d, v%d, %%[m0]" % (B1 + r, B0 + r))
+        for i in range(64):
+            L.append("v_mov_b32 v%d, 0" % (ACC0 + i))
+        L.append("s_memtime %[t0]")
+        L.append("s_waitcnt lgkmcnt(0)")
+        L.append("1:")
+        for row in range(0, ROWS_PER_ITER, rows):
+            L += body_pp(rows, row)
+        L.append("s_sub_u32 %[it], %[it], 1")
+        L.append("s_cmp_lg_u32 %[it], 0")
+        L.append("s_cbranch_scc1 1b")
+        L.append("s_memtime %[t1]")
+        L.append("s_waitcnt lgkmcnt(0)")
+        L.append("v_mov_b32 %[res], 0")
+        for i in range(64):
+            L.append("v_xor_b32 %%[res], %%[res], v%d" % (ACC0 + i))
+        asm = "\\n\\t".join(L)
+    finally:
+        ACC0, TMP0 = keep
+    return """
+__global__ __launch_bounds__(%d) void k_%s(uint32_t *out, uint64_t *cyc, uint32_t seed, int iters)
+{
+    extern __shared__ uint32_t pad[];  // sized by the host to pin workgroups per CU
+    uint32_t res;
+    uint64_t t0, t1;
+    int it = iters;
+    const uint32_t tid = threadIdx.x + blockIdx.x * blockDim.x;
+    asm volatile("%s"
+                 : [res] "=&v"(res), [t0] "=&s"(t0), [t1] "=&s"(t1), [it] "+s"(it)
+                 : [tid] "v"(tid), [seed] "v"(seed), [m0] "v"(2654435761u), [m1] "v"(40503u)
+                 : %s, "scc", "memory");
+    out[blockIdx.x * blockDim.x + threadIdx.x] = res + (pad == nullptr);
+    if ((threadIdx.x & 63) == 0) cyc[blockIdx.x * (blockDim.x / 64) + (threadIdx.x >> 6)] = t1 - t0;
+}
+""" % (wg, name, asm, clob)
+
+
 def main():
     o = sys.stdout
     o.write("// GENERATED by tools/ubench/gen_pair_sched.py -- do not edit.\n")
     o.write("#include <hip/hip_runtime.h>\n#include <cstdio>\n#include <cstdint>\n#include <vector>\n#include <algorithm>\n")
     for v in VARIANTS:
         o.write(kernel(*v))
+    for v in PP_VARIANTS:
+        o.write(kernel_pp(*v))
     o.write("""
 typedef void (*kern_t)(uint32_t *, uint64_t *, uint32_t, int);
 static void run(const char *name, kern_t k, int wg_per_cu, uint32_t seed, int pairs_per_row, int wg_threads = 256)
@@ -231,6 +325,10 @@ int main()
                     continue
                 # 512-thread workgroups: ONE per CU gives the same 2 waves per SIMD as two 256-thread ones
                 o.write('    run("%s", k_%s, %d, %du, 64, %d);\n' % (v[0], v[0], wg * 256 // thr, seed, thr))
+    # one barrier per phase pair (k_pair_counts_ls): ONE workgroup per CU -- 2 waves per SIMD at 512 threads, 3 at 768
+    o.write('    printf("-- one barrier per phase pair, spread LDS reads, one workgroup per CU\\n");\n')
+    for name, rows, thr in PP_VARIANTS:
+        o.write('    run("%s", k_%s, 1, 3u, 64, %d);\n' % (name, name, thr))
     o.write("    return 0;\n}\n")
 
 
