@@ -13,6 +13,7 @@ ESTIM_ORIGINAL, ESTIM_ERTL_IMPROVED, ESTIM_ERTL_MLE = 0, 1, 2
 MASH_DIST, JI, FULL_MASH_DIST = 0, 1, 3  # bns::EmissionType, src/enums.h:13-23
 SIZES, FULL_CONTAINMENT_DIST, CONTAINMENT_INDEX, CONTAINMENT_DIST = 2, 4, 5, 6
 SYMMETRIC_CONTAINMENT_INDEX, SYMMETRIC_CONTAINMENT_DIST = 7, 8
+GREEDY_FIRST, GREEDY_BEST = 0, 1  # assign_mode of dsh_greedy_extend*
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
@@ -31,7 +32,7 @@ SYMBOLS = [
     "dsh_allgather_device", "dsh_dist_collect", "dsh_range_parts", "dsh_dist_rows_parts_device_async", "dsh_collect_parts_async",
     "dsh_dist_rect", "dsh_knn", "dsh_dist_threshold", "dsh_dist_threshold_device", "dsh_dist_rect_threshold", "dsh_dist_pairs", "dsh_dist_pairs_device", "dsh_dist_pairs_csr",
     "dsh_cluster_threshold", "dsh_cluster_threshold_device", "dsh_cluster_pairs", "dsh_cluster_csr",
-    "dsh_greedy_threshold", "dsh_greedy_threshold_device",
+    "dsh_greedy_threshold", "dsh_greedy_threshold_device", "dsh_greedy_extend", "dsh_greedy_extend_device",
     "dsh_fold", "dsh_fold_device", "dsh_upload_sketches_folded", "dsh_upload_sketches_folded_device", "dsh_union_groups", "dsh_union_groups_device", "dsh_shard_plan", "dsh_dist_shard_device", "dsh_unpermute_device", "dsh_unpermute_staged_device", "dsh_unpermute_blocks_device", "dsh_tri_span", "dsh_tri_index", "dsh_partition_rows", "dsh_balance_rows", "dsh_balance_rowsets", "dsh_rowsets_from_bounds", "dsh_rowsets_rank", "dsh_alloc_host", "dsh_free_host",
     "dsh_set_profiling", "dsh_last_kernel_ms", "dsh_last_part_info", "dsh_finalize_phase_cycles", "dsh_set_option", "dsh_get_info", "dsh_stream",
 ]
@@ -167,7 +168,9 @@ def load_library():
                        ("dsh_cluster_pairs", [vp, u64, vp, vp, u64, vp, vp, C.POINTER(u64)]),
                        ("dsh_cluster_csr", [vp, u64, u64, u64, vp, vp, vp, vp, C.POINTER(u64)]),
                        ("dsh_greedy_threshold", [vp, i32, i32, i32, C.c_float, vp, C.POINTER(u64)]),
-                       ("dsh_greedy_threshold_device", [vp, i32, i32, i32, C.c_float, vp, C.POINTER(u64)])):
+                       ("dsh_greedy_threshold_device", [vp, i32, i32, i32, C.c_float, vp, C.POINTER(u64)]),
+                       ("dsh_greedy_extend", [vp, i32, i32, i32, C.c_float, i32, u64, vp, vp, C.POINTER(u64)]),
+                       ("dsh_greedy_extend_device", [vp, i32, i32, i32, C.c_float, i32, u64, vp, vp, C.POINTER(u64)])):
         fn = getattr(lib, name, None)
         if fn is not None:
             fn.argtypes = args
@@ -728,6 +731,42 @@ class Context:
         """labels into the caller's device buffer (uint32 [n]); returns n_reps"""
         nr = C.c_uint64()
         self._ck(self._derive("dsh_greedy_threshold_device")(self._h, estim, result_type, k, threshold, C.c_void_p(labels_ptr), C.byref(nr)))
+        return int(nr.value)
+
+    # ---- the same behind a labelling of the first slots; first or best representative
+    @staticmethod
+    def _extend_args(first_new, labels_in, assign):
+        mode = {"first": GREEDY_FIRST, "best": GREEDY_BEST}.get(assign, assign)
+        if mode not in (GREEDY_FIRST, GREEDY_BEST) or isinstance(mode, bool):
+            raise ValueError("assign is 'first' or 'best', got %r" % (assign,))
+        if first_new < 0:
+            raise ValueError("first_new is negative")
+        li = None
+        if labels_in is not None:
+            li = np.ascontiguousarray(labels_in, np.uint32).reshape(-1)
+            if li.size != first_new:
+                raise ValueError("labels_in holds one label per slot below first_new")
+        # (first_new > 0 without labels_in, and labels_in of length 0 with first_new == 0: the library's own rule decides)
+        return mode, li, (li.ctypes.data if li is not None and li.size else None)
+
+    def greedy_extend(self, threshold, first_new=0, labels_in=None, assign="first", estim=ESTIM_ERTL_MLE, result_type=JI, k=31):
+        """(labels uint32 [n], n_reps): the slots below first_new keep labels_in (their representatives are taken as
+        given), every later slot is a representative iff no representative before it hits it, else it goes to the smallest
+        ("first") or to the best-valued ("best"; ties to the smallest) representative that hits it"""
+        mode, li, lip = self._extend_args(first_new, labels_in, assign)
+        labels = np.zeros(self.n, np.uint32)
+        nr = C.c_uint64()
+        self._ck(self._derive("dsh_greedy_extend")(self._h, estim, result_type, k, threshold, mode, first_new, lip,
+                                                   labels.ctypes.data if labels.size else None, C.byref(nr)))
+        return labels, int(nr.value)
+
+    def greedy_extend_device(self, labels_ptr, threshold, first_new=0, labels_in=None, assign="first", estim=ESTIM_ERTL_MLE,
+                             result_type=JI, k=31):
+        """labels into the caller's device buffer (uint32 [n]); labels_in stays a host array; returns n_reps"""
+        mode, li, lip = self._extend_args(first_new, labels_in, assign)
+        nr = C.c_uint64()
+        self._ck(self._derive("dsh_greedy_extend_device")(self._h, estim, result_type, k, threshold, mode, first_new, lip,
+                                                          C.c_void_p(labels_ptr), C.byref(nr)))
         return int(nr.value)
 
     @staticmethod

@@ -60,7 +60,7 @@ static void release_ctx(dsh_ctx *c)
                       &c->thr_total, &c->thr_col, &c->thr_val, &c->thr_rowptr, &c->pairs_card, &c->pairs_hist, &c->pairs_lhs,
                       &c->pairs_rhs, &c->pairs_out, &c->pairs_err, &c->derive_err, &c->derive_stage, &c->derive_ptr, &c->derive_mem,
                       &c->derive_dst, &c->derive_part[0], &c->derive_part[1], &c->derive_out, &c->cc_parent, &c->cc_state, &c->cc_lhs,
-                      &c->cc_rhs, &c->cc_rowptr, &c->cc_seed, &c->cc_labels, &c->gr_assign, &c->gr_state, &c->gr_labels})
+                      &c->cc_rhs, &c->cc_rowptr, &c->cc_seed, &c->cc_labels, &c->gr_assign, &c->gr_state, &c->gr_labels, &c->gr_best})
         b->release();
     if (c->pin_perm) (void)hipHostFree(c->pin_perm);
     c->pin_perm = nullptr;

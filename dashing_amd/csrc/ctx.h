@@ -7,6 +7,7 @@
 //   pairs.hip     dsh_dist_pairs* (values of an explicit list of pairs, the direct form)
 //   cluster.hip   dsh_cluster_* (connected components at a threshold, or of a caller's graph)
 //   greedy.hip    dsh_greedy_threshold* (greedy representatives at a threshold, in slot order)
+//   greedy_extend.hip  dsh_greedy_extend* (the same behind a labelling of the first slots; first or best representative)
 //   derive.hip    dsh_fold*, dsh_upload_sketches_folded*, dsh_union_groups* (new sketches out of resident ones)
 //   exchange.hip  RCCL: dsh_comm_*, dsh_collect_*, dsh_allgather_device, dsh_dist_collect
 //   plan.cpp      the pure-host planner (layout, tiles, bands, parts, work items, row partitions)
@@ -194,6 +195,7 @@ struct dsh_ctx {
     uint64_t cluster_chunk = 1u << 20;  // option: edges per launch of dsh_cluster_pairs / dsh_cluster_csr
     // dsh_greedy_threshold* (greedy.hip): assign[n], the count of representatives and the labels of the host form
     DevBuf gr_assign, gr_state, gr_labels;
+    DevBuf gr_best;                     // dsh_greedy_extend* in BEST mode (greedy_extend.hip): one 64-bit key per new slot
     uint64_t greedy_band_rows = 4096;   // option: a band holds at most this many rows (k_greedy_diag's LDS; 1..kGreedyMaxRows)
     // dsh_fold*, dsh_upload_sketches_folded*, dsh_union_groups* (derive.hip): the error word, a chunk of source rows or of
     // folded rows on its way through the device, the groups' CSR and the partial unions of groups cut into chunks

@@ -106,6 +106,12 @@ static void usage(const char *sub)
             "                           per input, clusters numbered from 0 by ascending representative, value = the pair's value\n"
             "                           ('-' for a representative); -b: u64 n, u64 n_reps, u32 labels[n].  Not with --cluster,\n"
             "                           --threshold, --nearest-neighbors, --pairs, -Q, -U, -T or several devices.\n"
+            "  --assign first|best      with --representatives: an input that is no representative joins the FIRST representative\n"
+            "                           that passes the test with it [first], or the one with the BEST value (ties: the first).\n"
+            "  --extend FILE            with --representatives and --avoid-sorting: FILE is the -b output of an earlier\n"
+            "                           --representatives run over the first n_old inputs of this run, in this order; those keep\n"
+            "                           their labels and only the inputs behind them are judged, against the old representatives\n"
+            "                           and each other.  Outputs keep their formats.\n"
             "  --pairs FILE             emit only the pairs FILE lists, one per line as name_a<TAB>name_b (input names as given\n"
             "                           here; record names with dist_by_seq), in FILE's order: name_a<TAB>name_b and one value per\n"
             "                           measure.  --measures LIST: comma-separated from MASH_DIST, JI, SIZES, FULL_MASH_DIST,\n"
@@ -132,6 +138,9 @@ struct Opts {
     float cluster_t = 0.f;
     bool has_reps = false;  // --representatives: the greedy pass in output order over --threshold's graph (dsh_greedy_threshold)
     float reps_t = 0.f;
+    int assign_mode = DSH_GREEDY_FIRST;  // --assign first|best (dsh_greedy_extend)
+    bool has_assign = false;
+    std::string extend_file;  // --extend FILE: the labels of an earlier --representatives -b run over the first inputs
     std::string groups_file;  // --groups FILE: the unions of named groups are compared instead of the inputs (dsh_union_groups)
     std::string pairs_file, measures;  // --pairs FILE [--measures LIST]: only the listed pairs (dsh_dist_pairs)
     int rccl = 0;             // --rccl: deliver the rows through the RCCL exchange of the C-ABI even with one device
@@ -140,7 +149,7 @@ struct Opts {
     std::vector<std::string> inpaths, querypaths;
 };
 
-enum { OPT_PRESKETCHED = 1000, OPT_AVOID_SORT, OPT_DEVICE, OPT_NPERBATCH, OPT_NN, OPT_NGPUS, OPT_DEVICES, OPT_RCCL, OPT_THRESHOLD, OPT_CLUSTER, OPT_REPS, OPT_PAIRS, OPT_MEASURES, OPT_GROUPS, OPT_UNSUPPORTED };
+enum { OPT_PRESKETCHED = 1000, OPT_AVOID_SORT, OPT_DEVICE, OPT_NPERBATCH, OPT_NN, OPT_NGPUS, OPT_DEVICES, OPT_RCCL, OPT_THRESHOLD, OPT_CLUSTER, OPT_REPS, OPT_ASSIGN, OPT_EXTEND, OPT_PAIRS, OPT_MEASURES, OPT_GROUPS, OPT_UNSUPPORTED };
 
 static Opts parse(int argc, char **argv, bool is_dist)
 {
@@ -168,6 +177,7 @@ static Opts parse(int argc, char **argv, bool is_dist)
         {"use-cyclic-hash", no_argument, nullptr, OPT_UNSUPPORTED}, {"countmin", no_argument, nullptr, OPT_UNSUPPORTED},
         {"nearest-neighbors", required_argument, nullptr, OPT_NN}, {"threshold", required_argument, nullptr, OPT_THRESHOLD},
         {"cluster", required_argument, nullptr, OPT_CLUSTER}, {"representatives", required_argument, nullptr, OPT_REPS},
+        {"assign", required_argument, nullptr, OPT_ASSIGN}, {"extend", required_argument, nullptr, OPT_EXTEND},
         {"pairs", required_argument, nullptr, OPT_PAIRS}, {"groups", required_argument, nullptr, OPT_GROUPS}, {"measures", required_argument, nullptr, OPT_MEASURES},
         // second arm of result_cmp (src/dashing.h:577-588); flag numbers as in DIST_LONG_OPTS
         {"sizes", no_argument, nullptr, 'Z'}, {"containment-index", no_argument, nullptr, 131},
@@ -253,6 +263,13 @@ static Opts parse(int argc, char **argv, bool is_dist)
             o.has_reps = true;
             break;
         }
+        case OPT_ASSIGN:
+            if (!std::strcmp(optarg, "first")) o.assign_mode = DSH_GREEDY_FIRST;
+            else if (!std::strcmp(optarg, "best")) o.assign_mode = DSH_GREEDY_BEST;
+            else die("--assign takes 'first' or 'best', got '%s'", optarg);
+            o.has_assign = true;
+            break;
+        case OPT_EXTEND: o.extend_file = optarg; break;
         case OPT_PAIRS: o.pairs_file = optarg; break;
         case OPT_MEASURES: o.measures = optarg; break;
         case OPT_GROUPS: o.groups_file = optarg; break;
@@ -1006,6 +1023,27 @@ static int dist_main(int argc, char **argv, bool by_seq = false)
         if (o.fmt == FULL_TSV) die("--representatives does not go with -T: the output is one line per input.");
         if (o.devices.size() > 1 || o.rccl) die("--representatives runs on one device: --ngpus / --devices are not supported.");
     }
+    if (o.has_assign && !o.has_reps) die("--assign goes with --representatives only.");
+    // --extend: u64 n_old, u64 n_reps, u32 labels[n_old], as --representatives -b wrote it for the first n_old inputs
+    std::vector<uint32_t> extend_labels;
+    if (!o.extend_file.empty()) {
+        if (!o.has_reps) die("--extend goes with --representatives only.");
+        if (!o.avoid_sorting) die("--extend needs --avoid-sorting: sorting by size would interleave the old inputs and the new.");
+        std::FILE *ef = std::fopen(o.extend_file.c_str(), "rb");
+        if (!ef) die("--extend: could not open %s", o.extend_file.c_str());
+        uint64_t hdr[2] = {0, 0};
+        if (std::fread(hdr, sizeof(uint64_t), 2, ef) != 2) die("--extend: %s is too short for the header of a --representatives -b file", o.extend_file.c_str());
+        if (std::fseek(ef, 0, SEEK_END) != 0) die("--extend: could not read %s", o.extend_file.c_str());
+        const long fsize = std::ftell(ef);
+        if (hdr[0] > 0xFFFFFFFFull || fsize < 0 || (uint64_t)fsize != 16 + 4 * hdr[0])
+            die("--extend: %s has the wrong length for the %llu labels its header announces", o.extend_file.c_str(), (unsigned long long)hdr[0]);
+        extend_labels.resize((size_t)hdr[0]);
+        if (std::fseek(ef, 16, SEEK_SET) != 0 || std::fread(extend_labels.data(), sizeof(uint32_t), extend_labels.size(), ef) != extend_labels.size())
+            die("--extend: could not read %s", o.extend_file.c_str());
+        std::fclose(ef);
+        if (o.groups_file.empty() && extend_labels.size() > o.inpaths.size())
+            die("--extend: %s labels %zu inputs but this run has only %zu", o.extend_file.c_str(), extend_labels.size(), o.inpaths.size());
+    }
     static const char *const kMeasureNames[9] = {"MASH_DIST", "JI", "SIZES", "FULL_MASH_DIST", "FULL_CONTAINMENT_DIST", "CONTAINMENT_INDEX",
                                                  "CONTAINMENT_DIST", "SYMMETRIC_CONTAINMENT_INDEX", "SYMMETRIC_CONTAINMENT_DIST"};
     const bool with_pairs = !o.pairs_file.empty();
@@ -1243,10 +1281,15 @@ static int dist_main(int argc, char **argv, bool by_seq = false)
                 std::fwrite(s.data(), 1, s.size(), pairofp);
             }
         }
-    } else if (o.has_reps) {  // the greedy pass in output order (dsh_greedy_threshold): no pair leaves the device
+    } else if (o.has_reps) {  // the greedy pass in output order (dsh_greedy_threshold / dsh_greedy_extend): no pair leaves the device
         std::vector<uint32_t> labels(std::max<size_t>(n, 1));
         uint64_t n_reps = 0;
-        DSH(ctx, dsh_greedy_threshold(ctx, o.estim, o.result_type, o.k, o.reps_t, labels.data(), &n_reps));
+        if (extend_labels.size() > n) die("--extend: %s labels %zu inputs but this run has only %zu", o.extend_file.c_str(), extend_labels.size(), n);
+        if (o.has_assign || !o.extend_file.empty())
+            DSH(ctx, dsh_greedy_extend(ctx, o.estim, o.result_type, o.k, o.reps_t, o.assign_mode, extend_labels.size(),
+                                       extend_labels.empty() ? nullptr : extend_labels.data(), labels.data(), &n_reps));
+        else
+            DSH(ctx, dsh_greedy_threshold(ctx, o.estim, o.result_type, o.k, o.reps_t, labels.data(), &n_reps));
         if (o.fmt == BINARY) {
             const uint64_t hdr[2] = {(uint64_t)n, n_reps};
             if (std::fwrite(hdr, sizeof(uint64_t), 2, pairofp) != 2 || std::fwrite(labels.data(), sizeof(uint32_t), n, pairofp) != n)

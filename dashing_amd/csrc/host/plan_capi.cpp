@@ -414,6 +414,23 @@ int64_t dshh_greedy_bands(uint64_t n, uint64_t band_bytes, uint64_t row_cap, uin
     return (int64_t)nb;
 }
 
+// the bands of old rows of dsh_greedy_extend* (plan::greedy_old_band, the first loop of greedy_extend.hip) for m old slots
+// of n: bounds[2 q], bounds[2 q + 1] = band q.  Returns the number of bands, or -1 when they do not fit cap words or m > n
+// (tests/test_greedy_extend_plan.py).
+int64_t dshh_greedy_extend_bands(const uint32_t *labels_in, uint64_t m, uint64_t n, uint64_t band_bytes, uint64_t *bounds, uint64_t cap)
+{
+    if (m > n) return -1;
+    const uint64_t band_floats = std::max<uint64_t>(band_bytes / sizeof(float), 1);
+    uint64_t nb = 0, b0 = 0, b1 = 0;
+    for (uint64_t from = 0; greedy_old_band(labels_in, m, n - m, from, band_floats, b0, b1); from = b1) {
+        if (2 * nb + 2 > cap) return -1;
+        bounds[2 * nb] = b0;
+        bounds[2 * nb + 1] = b1;
+        ++nb;
+    }
+    return (int64_t)nb;
+}
+
 // the union-find of the threshold clusters (../uf.h, the code the device kernels compile) run sequentially: labels_out[x] =
 // the smallest node of x's component in the graph of the n_edges edges (lhs[e], rhs[e]).  Returns 0, -1 for an edge that
 // names a node >= n, and the step-bound code (1 find, 2 hook) when a loop overran step_cap -- the give-up path, which the

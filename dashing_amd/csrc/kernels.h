@@ -215,6 +215,18 @@ hipError_t launch_greedy_diag(hipStream_t st, const float *vals, const ThrRows &
 hipError_t launch_greedy_band(hipStream_t st, const float *vals, const ThrRows &g, float t, int descending, uint32_t *assign);
 // after the last band: labels[x] = assign[x], *n_reps += the x with assign[x] == x (the caller zeroes it)
 hipError_t launch_greedy_labels(hipStream_t st, const uint32_t *assign, uint64_t n, uint32_t *labels, uint64_t *n_reps);
+// dsh_greedy_extend* (greedy_extend.hip): slots below first_new keep the caller's labels; best[n - first_new] (BEST mode,
+// else nullptr) starts as 0 and holds per new slot the largest key (value, then smaller slot) of a representative that hits it.
+// Rows of a rectangle [g.row0, g.row0 + g.rows) x [g.col0 = first_new, n): every row that is a representative lowers
+// assign[j] to itself and (best != nullptr) raises best[j - first_new] for its passing columns
+hipError_t launch_greedy_rect(hipStream_t st, const float *vals, const ThrRows &g, float t, int descending, uint32_t *assign, uint64_t *best);
+// a band of triangle rows at or behind first_new, after launch_greedy_diag and IN THE PLACE of launch_greedy_band: its
+// representative rows raise best for all their passing columns and lower assign for those >= row0 + rows
+hipError_t launch_greedy_best(hipStream_t st, const float *vals, const ThrRows &g, float t, int descending, uint32_t *assign, uint64_t *best,
+                              uint64_t first_new);
+// labels[x] = assign[x], or for a covered x >= first_new with best != nullptr the slot its key names; *n_reps += the x with labels[x] == x
+hipError_t launch_greedy_extend_labels(hipStream_t st, const uint32_t *assign, const uint64_t *best, uint64_t first_new, uint64_t n,
+                                       uint32_t *labels, uint64_t *n_reps);
 
 // explicit pair lists (kernels_pairs.hip, pairs.hip): histograms are [cnt][64] counters, uint16 for p <= kPairsMaxP16
 // (a bin holds at most 2^p), uint32 above

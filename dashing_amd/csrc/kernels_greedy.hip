@@ -22,6 +22,21 @@
 //                    atomics, as in UfDevice.  No loop depends on what another thread does.
 //   k_greedy_labels  a launch of its own, after the last band: labels[x] = assign[x]; representatives counted with
 //                    __ballot + popcount and one atomicAdd per wave
+//
+// dsh_greedy_extend* (greedy_extend.hip) adds three kernels; the three above are not changed.  Slots below
+// m = first_new keep the labels the caller gives (assign[x] = labels_in[x]); in BEST mode best[n - m] holds, per new slot,
+// the largest key of a representative that hits it -- 0: none; high word: the value as an order-preserving integer (the
+// two zeros made one, complemented for the distances: a larger key is a better value); low word 0xFFFFFFFF - r: among equal
+// values the smallest representative wins.  A plain 64-bit atomic maximum, which commutes like the minimum on assign.
+//   k_greedy_rect    the geometry of k_greedy_band on the rows of a RECTANGLE (old rows [b0, b1) x the new columns [m, n),
+//                    row r at r * ncols: any alignment mod 4): a wave whose old row is not a representative returns at once;
+//                    a passing column is lowered in assign and, in BEST, raised in best
+//   k_greedy_best    BEST only, in the place of k_greedy_band: the band's representative rows (final after k_greedy_diag)
+//                    raise best for ALL their passing columns, the in-band ones included (a passing column of a
+//                    representative row is never a representative: no test), and lower assign for the columns >= b1 as
+//                    k_greedy_band does -- the band's out-of-band part is read once, its diagonal block a second time
+//   k_greedy_extend_labels  labels[x] = assign[x] for old slots and in FIRST; in BEST a covered new slot takes the slot its
+//                    key names; representatives counted as in k_greedy_labels
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -154,6 +169,117 @@ __global__ __launch_bounds__(256) void k_greedy_labels(const uint32_t *__restric
     }
 }
 
+__device__ __forceinline__ unsigned long long ld_best(const unsigned long long *p)
+{
+    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// larger key = better value: the float's bits as an integer of the same order (-0.0 taken as +0.0 first, the bit-exact
+// form of v + 0.0f: equal as float32 must mean equal here), complemented where a smaller value is better; NaN never passes
+__device__ __forceinline__ unsigned long long best_key(float v, int descending, uint32_t r)
+{
+    uint32_t u = __float_as_uint(v);
+    if (u == 0x80000000u) u = 0u;
+    u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+    if (!descending) u = ~u;
+    return ((unsigned long long)u << 32) | (unsigned long long)(0xFFFFFFFFu - r);
+}
+
+// One wave, one chunk [begin, end) of the values of representative row i (row starts at rowoff, its first value belongs to
+// column colbase): a passing column j is lowered in assign if j >= min_from, and raised in best (if there is one).
+__device__ __forceinline__ void greedy_walk(const float *__restrict__ vals, uint64_t rowoff, uint64_t begin, uint64_t end, uint32_t colbase,
+                                            uint32_t i, uint32_t lane, float t, int descending, uint32_t *assign, uint32_t min_from,
+                                            unsigned long long *best, uint32_t m)
+{
+    for (uint64_t idx = (begin & ~(uint64_t)3) + 4 * lane; idx < end; idx += kStep) {
+        float v[4] = {0.f, 0.f, 0.f, 0.f};
+        uint32_t hit = 0;
+        if (idx >= begin && idx + 4 <= end) {
+            const float4 q = *reinterpret_cast<const float4 *>(vals + idx);
+            v[0] = q.x, v[1] = q.y, v[2] = q.z, v[3] = q.w;
+#pragma unroll
+            for (int c = 0; c < 4; ++c) hit |= (thr_pass(v[c], t, descending) ? 1u : 0u) << c;
+        } else {
+#pragma unroll
+            for (int c = 0; c < 4; ++c)
+                if (idx + c >= begin && idx + c < end) {
+                    v[c] = vals[idx + c];
+                    hit |= (thr_pass(v[c], t, descending) ? 1u : 0u) << c;
+                }
+        }
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            if (!((hit >> c) & 1u)) continue;
+            const uint32_t j = colbase + (uint32_t)(idx + c - rowoff);
+            if (j >= min_from) {
+                uint32_t *a = assign + j;
+                if (ld_assign(a) > i) (void)atomicMin(a, i);
+            }
+            if (best) {
+                unsigned long long *b = best + (j - m);
+                const unsigned long long key = best_key(v[c], descending, i);
+                if (ld_best(b) < key) (void)atomicMax(b, key);  // (best only grows: a stale value errs towards one atomic too many)
+            }
+        }
+    }
+}
+
+// g.rect = 1: rows [g.row0, g.row0 + g.rows) of the collection against the columns [g.col0, g.col0 + g.ncols) = [m, n)
+__global__ __launch_bounds__(256) void k_greedy_rect(const float *__restrict__ vals, ThrRows g, float t, int descending, uint32_t *assign,
+                                                     unsigned long long *best)
+{
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const uint64_t r = blockIdx.x;
+    const uint32_t ch = blockIdx.y * 4 + wave;
+    if (ch >= g.nchunks) return;
+    const uint64_t cb = (uint64_t)ch * kThrChunk;
+    if (cb >= g.ncols) return;
+    const uint64_t i = g.row0 + r;
+    if (ld_assign(assign + i) != (uint32_t)i) return;  // not a representative: the row has nothing to say
+    const uint64_t ce = g.ncols - cb < kThrChunk ? g.ncols : cb + kThrChunk;
+    const uint64_t rowoff = r * g.ncols;
+    greedy_walk(vals, rowoff, rowoff + cb, rowoff + ce, (uint32_t)g.col0, (uint32_t)i, lane, t, descending, assign, 0u, best,
+                (uint32_t)g.col0);
+}
+
+// a band of triangle rows as k_greedy_band takes it, after k_greedy_diag; m <= g.row0
+__global__ __launch_bounds__(256) void k_greedy_best(const float *__restrict__ vals, ThrRows g, float t, int descending, uint32_t *assign,
+                                                     unsigned long long *best, uint32_t m)
+{
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const uint64_t r = blockIdx.x;
+    const uint32_t ch = blockIdx.y * 4 + wave;
+    if (ch >= g.nchunks) return;
+    const uint64_t i = g.row0 + r;
+    const uint64_t first = g.n - 1 - g.row0;
+    const uint64_t len = g.n - 1 - i;
+    const uint64_t cb = (uint64_t)ch * kThrChunk;
+    if (cb >= len) return;
+    if (ld_assign(assign + i) != (uint32_t)i) return;  // covered
+    const uint64_t ce = len - cb < kThrChunk ? len : cb + kThrChunk;
+    const uint64_t rowoff = r * first - r * (r - 1) / 2;
+    greedy_walk(vals, rowoff, rowoff + cb, rowoff + ce, (uint32_t)(i + 1), (uint32_t)i, lane, t, descending, assign,
+                (uint32_t)(g.row0 + g.rows), best, m);
+}
+
+__global__ __launch_bounds__(256) void k_greedy_extend_labels(const uint32_t *__restrict__ assign, const unsigned long long *__restrict__ best,
+                                                              uint64_t m, uint64_t n, uint32_t *__restrict__ labels,
+                                                              unsigned long long *n_reps)
+{
+    const uint64_t nround = (n + 255) / 256 * 256;  // whole waves take part in the ballot
+    for (uint64_t x = (uint64_t)blockIdx.x * 256 + threadIdx.x; x < nround; x += (uint64_t)gridDim.x * 256) {
+        bool rep = false;
+        if (x < n) {
+            uint32_t l = assign[x];
+            if (best && x >= m && l != (uint32_t)x) l = 0xFFFFFFFFu - (uint32_t)best[x - m];
+            labels[x] = l;
+            rep = l == (uint32_t)x;
+        }
+        const unsigned long long b = __ballot(rep);
+        if ((threadIdx.x & 63u) == 0 && b) atomicAdd(n_reps, (unsigned long long)__popcll(b));
+    }
+}
+
 }  // namespace
 
 hipError_t launch_greedy_diag(hipStream_t st, const float *vals, const ThrRows &g, float t, int descending, uint32_t *assign)
@@ -176,6 +302,35 @@ hipError_t launch_greedy_labels(hipStream_t st, const uint32_t *assign, uint64_t
     if (!n) return hipSuccess;
     const uint32_t grid = (uint32_t)std::min<uint64_t>(std::max<uint64_t>((n + 255) / 256, 1), 8192);
     hipLaunchKernelGGL(k_greedy_labels, dim3(grid), dim3(256), 0, st, assign, n, labels, reinterpret_cast<unsigned long long *>(n_reps));
+    return hipGetLastError();
+}
+
+hipError_t launch_greedy_rect(hipStream_t st, const float *vals, const ThrRows &g, float t, int descending, uint32_t *assign, uint64_t *best)
+{
+    if (g.rows == 0 || g.ncols == 0) return hipSuccess;
+    if (!g.rect) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_greedy_rect, dim3((uint32_t)g.rows, (g.nchunks + 3) / 4), dim3(256), 0, st, vals, g, t, descending, assign,
+                       reinterpret_cast<unsigned long long *>(best));
+    return hipGetLastError();
+}
+
+hipError_t launch_greedy_best(hipStream_t st, const float *vals, const ThrRows &g, float t, int descending, uint32_t *assign, uint64_t *best,
+                              uint64_t first_new)
+{
+    if (g.rows == 0) return hipSuccess;
+    if (g.rect || !best || first_new > g.row0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_greedy_best, dim3((uint32_t)g.rows, (g.nchunks + 3) / 4), dim3(256), 0, st, vals, g, t, descending, assign,
+                       reinterpret_cast<unsigned long long *>(best), (uint32_t)first_new);
+    return hipGetLastError();
+}
+
+hipError_t launch_greedy_extend_labels(hipStream_t st, const uint32_t *assign, const uint64_t *best, uint64_t first_new, uint64_t n,
+                                       uint32_t *labels, uint64_t *n_reps)
+{
+    if (!n) return hipSuccess;
+    const uint32_t grid = (uint32_t)std::min<uint64_t>(std::max<uint64_t>((n + 255) / 256, 1), 8192);
+    hipLaunchKernelGGL(k_greedy_extend_labels, dim3(grid), dim3(256), 0, st, assign, reinterpret_cast<const unsigned long long *>(best),
+                       first_new, n, labels, reinterpret_cast<unsigned long long *>(n_reps));
     return hipGetLastError();
 }
 

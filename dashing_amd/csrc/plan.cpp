@@ -30,6 +30,20 @@ uint64_t greedy_band_end(uint64_t n, uint64_t b0, uint64_t band_floats, uint64_t
     return b1;
 }
 
+bool greedy_old_band(const uint32_t *labels_in, uint64_t m, uint64_t ncols, uint64_t from, uint64_t band_floats, uint64_t &b0, uint64_t &b1)
+{
+    const uint64_t max_rows = std::min<uint64_t>(std::max<uint64_t>(band_floats / std::max<uint64_t>(ncols, 1), 1), 1u << 20);
+    uint64_t x = from;
+    while (x < m && labels_in[x] != x) ++x;
+    if (x >= m) return false;
+    b0 = x;
+    b1 = x + 1;
+    const uint64_t stop = std::min<uint64_t>(m, b0 + max_rows);
+    for (++x; x < stop; ++x)
+        if (labels_in[x] == x) b1 = x + 1;
+    return true;
+}
+
 void partition_rows(uint64_t n, uint32_t nparts, uint32_t align, uint64_t *bounds)
 {
     if (align == 0) align = 1;

@@ -62,7 +62,7 @@ typedef struct dsh_ctx dsh_ctx;
  * Entry points that were only ADDED since leave the number alone and are detected by symbol (dlsym):
  * dsh_dist_threshold, dsh_dist_threshold_device, dsh_dist_rect_threshold, dsh_dist_pairs*, dsh_fold*,
  * dsh_upload_sketches_folded*, dsh_union_groups*, dsh_cluster_threshold, dsh_cluster_threshold_device, dsh_cluster_pairs,
- * dsh_cluster_csr, dsh_greedy_threshold, dsh_greedy_threshold_device. */
+ * dsh_cluster_csr, dsh_greedy_threshold, dsh_greedy_threshold_device, dsh_greedy_extend, dsh_greedy_extend_device. */
 #define DSH_ABI_VERSION 7
 int dsh_abi_version(void);
 
@@ -447,13 +447,69 @@ int dsh_cluster_csr(dsh_ctx *ctx, uint64_t n_nodes, uint64_t row_begin, uint64_t
  *     0.1 % / 1 % / 50 % hits beside C - A = 3.5 / 7.2 / 16.4 ms, and 94 ms where nothing passes (C - A = 3.5 ms), about
  *     four fifths of it k_greedy_diag; at 10 000 x p=14 (A = 14.1 ms) G - A = 5.5 / 4.6 / 1.5 ms and 7.7 ms where nothing
  *     passes, C - A within 1.3 ms of zero.  G - A is below A everywhere.
- *   Not built: a caller-given priority permutation (the caller orders the slots); assignment to the BEST representative
- *     rather than the first; a continuation that adds new slots at the cost of the new rows only; a rectangle form; CSR or
- *     edge-list forms (a sequential host pass over hits that are already on the host is linear); a multi-GPU form. */
+ *   Not built: a caller-given priority permutation (the caller orders the slots); a rectangle form; CSR or edge-list
+ *     forms (a sequential host pass over hits that are already on the host is linear); a multi-GPU form.  Assignment to
+ *     the BEST representative and a continuation behind an existing labelling are dsh_greedy_extend*, below. */
 int dsh_greedy_threshold(dsh_ctx *ctx, int estim, int result_type, int k, float threshold, uint32_t *labels_out,
                          uint64_t *n_reps);
 int dsh_greedy_threshold_device(dsh_ctx *ctx, int estim, int result_type, int k, float threshold, void *d_labels,
                                 uint64_t *n_reps);
+
+/* ---- greedy representatives, continued: extend a labelling, assign to the best representative --------------
+ * What the users of CD-HIT, dRep and galah ask for next.  A collection grows: a release appends a few per cent of genomes
+ * to a database that is already dereplicated, and by the prefix property above the old labels cannot change -- only the
+ * pairs (old representative, new slot) and (new, new) matter: m (n - m) + (n - m)^2 / 2 pairs instead of n^2 / 2 for m old
+ * slots, at most (no row of an old slot that is not a representative is computed where a whole band holds none).  And a
+ * covered slot may go to the BEST representative that hits it rather than the first (CD-HIT -g 1).
+ *   The result.  hit(i, j), i < j, and v(i, j), its value, are those of dsh_dist_threshold(ctx, estim, result_type, k, 0, n,
+ *     threshold, ...): the same float32, the same predicate, the same single orientation.  m = first_new.
+ *     Old slots: labels[x] = labels_in[x] for x < m; old slots are never re-judged, in either mode.
+ *     R_old = {x < m : labels_in[x] == x} is taken as given: it need not be what a full call would have produced, so
+ *     extending a set of representatives chosen elsewhere is legal and defined.
+ *     New slots x >= m, in ascending order: x is in R iff no r in R_old or in R with m <= r < x has hit(r, x).  Otherwise
+ *       DSH_GREEDY_FIRST: labels[x] is the smallest such r;
+ *       DSH_GREEDY_BEST:  labels[x] is the such r with the best v(r, x) -- the largest for the similarity forms, the
+ *         smallest for the *_DIST forms, compared as float32 (so -0.0 equals +0.0); ties go to the smallest r.
+ *     *n_reps is the number of x in [0, n) with labels[x] == x.  This has one answer: it depends on no band size, launch
+ *     geometry or order of arrival of atomics.
+ *   Consequences.  first_new == 0 with DSH_GREEDY_FIRST equals dsh_greedy_threshold byte for byte.  If labels_in is the
+ *     first m labels of a full call (first_new == 0) in the same mode, the result is that full call's result.
+ *     first_new == n copies labels_in and counts.  BEST and FIRST have the same representatives.  In BEST every covered
+ *     x >= m still passes against its label, and no other representative r < x has a strictly better value.
+ *   How.  assign[n] as above, started from labels_in below m.  In BEST one uint64 best[n - m], 0 = none, raised with a plain
+ *     64-bit atomic maximum: the high word is the value as an order-preserving integer (the two zeros made one,
+ *     complemented for the *_DIST forms), the low word 0xFFFFFFFF - r.  Phase 1: bands of old rows from a representative
+ *     to a representative (at most "threshold_band_bytes" of values and 2^20 rows; a stretch without one is skipped),
+ *     computed as the rectangle [b0, b1) x [m, n) -- bit for bit the triangle's values, see dsh_dist_pairs above -- and
+ *     walked by k_greedy_rect: a wave of a row that is no representative returns at once, a passing column is lowered in
+ *     assign and, in BEST, raised in best.  Phase 2: the band loop of dsh_greedy_threshold started at row m with
+ *     k_greedy_diag and k_greedy_band unchanged; in BEST k_greedy_best stands in k_greedy_band's place: the band's
+ *     representative rows raise best for all their passing columns, in-band ones included, and lower assign for the
+ *     later ones (one read of a band outside its diagonal block, the block a second time).  k_greedy_extend_labels
+ *     writes the labels: assign[x], or in BEST for a covered new slot the slot its key names.
+ *   dsh_greedy_extend         labels_out: host uint32 [n].
+ *   dsh_greedy_extend_device  d_labels: caller-owned DEVICE uint32 [n]; exactly n labels are written.
+ *   labels_in is a HOST array [first_new] in both forms, NULL if and only if first_new == 0.
+ *   Execution.  Synchronous, on the ctx stream; no host wait between bands, one at the end.  The effects on the context's
+ *     cached state are those of dsh_dist_rect_threshold on [0, m) x [m, n) followed by dsh_dist_threshold on rows [m, n):
+ *     the dense calls before and after give the same bytes.
+ *   Errors, before anything is enqueued: DSH_EINVAL for a NULL context, first_new > n, an assign_mode outside {0, 1},
+ *     labels_in NULL with first_new > 0 (or not NULL with first_new == 0), an x with labels_in[x] > x or
+ *     labels_in[labels_in[x]] != labels_in[x] (the message names x), a NULL output with n > 0 and n > 2^32 - 1; DSH_ESTATE
+ *     without sketches.  n == 0 and n < 2 succeed; a NaN threshold makes every new slot a representative.
+ *   Cost model: the dense path's cost for the old-representative bands of the rectangle and for the
+ *     triangle rows [m, n), one read of each, and in BEST one more read of each diagonal block and one 64-bit atomic per
+ *     hit of a representative row that raises a key.  Not yet measured on the device (tools/bench_greedy_extend.py does it).
+ *   Not built: the old representatives gathered into a compact matrix first (the rows between two representatives of a
+ *     band are computed and not read); a caller-given priority permutation; a rectangle / classify-only form (new slots
+ *     against representatives, no new representatives); CSR or edge-list forms; a multi-GPU form; re-judging old slots
+ *     when a new slot would have been a better representative. */
+#define DSH_GREEDY_FIRST 0
+#define DSH_GREEDY_BEST 1
+int dsh_greedy_extend(dsh_ctx *ctx, int estim, int result_type, int k, float threshold, int assign_mode,
+                      uint64_t first_new, const uint32_t *labels_in, uint32_t *labels_out, uint64_t *n_reps);
+int dsh_greedy_extend_device(dsh_ctx *ctx, int estim, int result_type, int k, float threshold, int assign_mode,
+                             uint64_t first_new, const uint32_t *labels_in, void *d_labels, uint64_t *n_reps);
 
 /* ---- multi-GPU shards of the full triangle ------------------------------------------------
  * Every rank holds all sketches (dsh_upload/attach) and computes one shard; no collective is
