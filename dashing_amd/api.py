@@ -4,6 +4,7 @@ There is deliberately no CPU fallback here: if the shared library is missing, or
 device is visible, construction fails loudly.  (The CPU oracle lives in oracle/ and is test
 infrastructure only -- nothing in this package imports it.)
 """
+import collections
 import ctypes as C
 import os
 
@@ -14,6 +15,9 @@ MASH_DIST, JI, FULL_MASH_DIST = 0, 1, 3  # bns::EmissionType, src/enums.h:13-23
 SIZES, FULL_CONTAINMENT_DIST, CONTAINMENT_INDEX, CONTAINMENT_DIST = 2, 4, 5, 6
 SYMMETRIC_CONTAINMENT_INDEX, SYMMETRIC_CONTAINMENT_DIST = 7, 8
 GREEDY_FIRST, GREEDY_BEST = 0, 1  # assign_mode of dsh_greedy_extend*
+STATS_FRAC_BITS = 30  # DSH_STATS_FRAC_BITS: sums of dsh_group_stats* are in units of 2^-30
+# the measures for which a larger value is better (the others are the *_DIST forms; SIZES has no order)
+SIMILARITY_TYPES = (JI, CONTAINMENT_INDEX, SYMMETRIC_CONTAINMENT_INDEX)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
@@ -33,6 +37,7 @@ SYMBOLS = [
     "dsh_dist_rect", "dsh_knn", "dsh_dist_threshold", "dsh_dist_threshold_device", "dsh_dist_rect_threshold", "dsh_dist_pairs", "dsh_dist_pairs_device", "dsh_dist_pairs_csr",
     "dsh_cluster_threshold", "dsh_cluster_threshold_device", "dsh_cluster_pairs", "dsh_cluster_csr",
     "dsh_greedy_threshold", "dsh_greedy_threshold_device", "dsh_greedy_extend", "dsh_greedy_extend_device",
+    "dsh_group_stats", "dsh_group_stats_device",
     "dsh_fold", "dsh_fold_device", "dsh_upload_sketches_folded", "dsh_upload_sketches_folded_device", "dsh_union_groups", "dsh_union_groups_device", "dsh_shard_plan", "dsh_dist_shard_device", "dsh_unpermute_device", "dsh_unpermute_staged_device", "dsh_unpermute_blocks_device", "dsh_tri_span", "dsh_tri_index", "dsh_partition_rows", "dsh_balance_rows", "dsh_balance_rowsets", "dsh_rowsets_from_bounds", "dsh_rowsets_rank", "dsh_alloc_host", "dsh_free_host",
     "dsh_set_profiling", "dsh_last_kernel_ms", "dsh_last_part_info", "dsh_finalize_phase_cycles", "dsh_set_option", "dsh_get_info", "dsh_stream",
 ]
@@ -170,7 +175,9 @@ def load_library():
                        ("dsh_greedy_threshold", [vp, i32, i32, i32, C.c_float, vp, C.POINTER(u64)]),
                        ("dsh_greedy_threshold_device", [vp, i32, i32, i32, C.c_float, vp, C.POINTER(u64)]),
                        ("dsh_greedy_extend", [vp, i32, i32, i32, C.c_float, i32, u64, vp, vp, C.POINTER(u64)]),
-                       ("dsh_greedy_extend_device", [vp, i32, i32, i32, C.c_float, i32, u64, vp, vp, C.POINTER(u64)])):
+                       ("dsh_greedy_extend_device", [vp, i32, i32, i32, C.c_float, i32, u64, vp, vp, C.POINTER(u64)]),
+                       ("dsh_group_stats", [vp, i32, i32, i32, vp, vp, vp, vp, vp]),
+                       ("dsh_group_stats_device", [vp, i32, i32, i32, vp, vp, vp, vp, vp])):
         fn = getattr(lib, name, None)
         if fn is not None:
             fn.argtypes = args
@@ -343,6 +350,32 @@ def balance_rows(n, nparts):
     if rc:
         raise DshError(rc, "dsh_balance_rows")
     return [int(x) for x in b]
+
+
+class GroupStats(collections.namedtuple("GroupStats", "medoid cnt sum worst")):
+    """what Context.group_stats returns: per slot the medoid of its group (uint32), the included pairs with its group
+    (uint32), the sum of their values in units of 2^-STATS_FRAC_BITS (int64) and the worst of them (float32, NaN where
+    cnt == 0); .mean and .diameter are derived on the host"""
+
+    def __new__(cls, medoid, cnt, sum, worst, labels, descending):
+        self = super().__new__(cls, medoid, cnt, sum, worst)
+        self.labels, self.descending = labels, bool(descending)
+        return self
+
+    @property
+    def mean(self):
+        """float64 [n]: the mean value of each slot to its group, NaN where cnt == 0"""
+        out = np.full(self.cnt.shape, np.nan)
+        ok = self.cnt > 0
+        out[ok] = self.sum[ok] / self.cnt[ok] / float(1 << STATS_FRAC_BITS)
+        return out
+
+    @property
+    def diameter(self):
+        """float32 [n]: per slot the worst value inside its group (the worst `worst` of its members; NaN: none)"""
+        acc = np.full(self.worst.shape, np.nan, np.float32)
+        (np.fmin if self.descending else np.fmax).at(acc, self.labels, self.worst)  # (fmin / fmax pass over NaN)
+        return acc[self.labels]
 
 
 class PinnedArray:
@@ -768,6 +801,41 @@ class Context:
         self._ck(self._derive("dsh_greedy_extend_device")(self._h, estim, result_type, k, threshold, mode, first_new, lip,
                                                           C.c_void_p(labels_ptr), C.byref(nr)))
         return int(nr.value)
+
+    # ---- statistics of a labelling: counts, sums, worst values, medoids (include/dashing_hip.h has the contract)
+    _ROUTES = {"auto": -1, "dense": 0, "pairs": 1}
+
+    def _stats_call(self, name, labels, estim, result_type, k, route, ptrs):
+        if route not in self._ROUTES:
+            raise ValueError("route is 'auto', 'dense' or 'pairs', got %r" % (route,))
+        lab = np.ascontiguousarray(labels, np.uint32).reshape(-1)
+        if lab.size != self.n:
+            raise ValueError("labels holds one label per sketch")
+        # "auto" leaves the context's "stats_route" option as it is; a named route holds for this call alone
+        if route != "auto":
+            self.set_option("stats_route", self._ROUTES[route])
+        try:
+            self._ck(self._derive(name)(self._h, estim, result_type, k, lab.ctypes.data if lab.size else None, *ptrs))
+        finally:
+            if route != "auto":
+                self.set_option("stats_route", -1)
+        return lab
+
+    def group_stats(self, labels, estim=ESTIM_ERTL_MLE, result_type=JI, k=31, route="auto"):
+        """GroupStats(medoid, cnt, sum, worst) of the groups of equal labels (any values < n), with .mean and .diameter.
+        No result depends on route ('auto' | 'dense' | 'pairs')."""
+        n = self.n
+        med, cnt, sm, worst = np.zeros(n, np.uint32), np.zeros(n, np.uint32), np.zeros(n, np.int64), np.zeros(n, np.float32)
+        lab = self._stats_call("dsh_group_stats", labels, estim, result_type, k, route,
+                               [a.ctypes.data if n else None for a in (med, cnt, sm, worst)])
+        return GroupStats(med, cnt, sm, worst, lab, result_type in SIMILARITY_TYPES)
+
+    def group_stats_device(self, labels, medoid_ptr, cnt_ptr, sum_ptr, worst_ptr, estim=ESTIM_ERTL_MLE, result_type=JI, k=31,
+                           route="auto"):
+        """the same into the caller's device buffers (uint32, uint32, int64, float32, [n] each; 0 / None: not wanted);
+        labels stays a host array"""
+        self._stats_call("dsh_group_stats_device", labels, estim, result_type, k, route,
+                         [C.c_void_p(p) if p else None for p in (medoid_ptr, cnt_ptr, sum_ptr, worst_ptr)])
 
     @staticmethod
     def _labels_in(n_nodes, labels_in):

@@ -60,7 +60,8 @@ static void release_ctx(dsh_ctx *c)
                       &c->thr_total, &c->thr_col, &c->thr_val, &c->thr_rowptr, &c->pairs_card, &c->pairs_hist, &c->pairs_lhs,
                       &c->pairs_rhs, &c->pairs_out, &c->pairs_err, &c->derive_err, &c->derive_stage, &c->derive_ptr, &c->derive_mem,
                       &c->derive_dst, &c->derive_part[0], &c->derive_part[1], &c->derive_out, &c->cc_parent, &c->cc_state, &c->cc_lhs,
-                      &c->cc_rhs, &c->cc_rowptr, &c->cc_seed, &c->cc_labels, &c->gr_assign, &c->gr_state, &c->gr_labels, &c->gr_best})
+                      &c->cc_rhs, &c->cc_rowptr, &c->cc_seed, &c->cc_labels, &c->gr_assign, &c->gr_state, &c->gr_labels, &c->gr_best,
+                      &c->gs_labels, &c->gs_acc, &c->gs_grp, &c->gs_out, &c->gs_csr})
         b->release();
     if (c->pin_perm) (void)hipHostFree(c->pin_perm);
     c->pin_perm = nullptr;
@@ -1007,6 +1008,7 @@ int dsh_get_info(dsh_ctx *c, const char *name, int64_t *out)
     else if (!std::strcmp(name, "sketch_kernel_us")) *out = (int64_t)(c->sketch_ms * 1000.0);
     else if (!std::strcmp(name, "fastx_decode_us")) *out = (int64_t)(c->fastx_ms * 1000.0);
     else if (!std::strcmp(name, "xch_recv_gated")) *out = c->xch_recv_gated ? 1 : 0;
+    else if (!std::strcmp(name, "stats_route")) *out = c->stats_route_last;
     else if (!std::strcmp(name, "place_kernel_us")) *out = (int64_t)(c->place_ms * 1000.0);
     else if (!std::strcmp(name, "whatif_mfma")) {
 #ifdef DSH_WHATIF_MFMA
@@ -1077,6 +1079,11 @@ int dsh_set_option(dsh_ctx *c, const char *name, int64_t v)
     if (!std::strcmp(name, "cluster_chunk")) {
         if (v < 1 || v > (1 << 26)) return fail(c, DSH_EINVAL, "cluster_chunk must be in [1, 2^26]");
         c->cluster_chunk = (uint64_t)v;
+        return DSH_OK;
+    }
+    if (!std::strcmp(name, "stats_route")) {
+        if (v < -1 || v > 1) return fail(c, DSH_EINVAL, "stats_route must be -1 (auto), 0 (dense) or 1 (pairs)");
+        c->stats_route = (int)v;
         return DSH_OK;
     }
     if (!std::strcmp(name, "greedy_band_rows")) {

@@ -8,6 +8,7 @@
 //   cluster.hip   dsh_cluster_* (connected components at a threshold, or of a caller's graph)
 //   greedy.hip    dsh_greedy_threshold* (greedy representatives at a threshold, in slot order)
 //   greedy_extend.hip  dsh_greedy_extend* (the same behind a labelling of the first slots; first or best representative)
+//   group_stats.hip    dsh_group_stats* (per-group statistics and medoids of a labelling)
 //   derive.hip    dsh_fold*, dsh_upload_sketches_folded*, dsh_union_groups* (new sketches out of resident ones)
 //   exchange.hip  RCCL: dsh_comm_*, dsh_collect_*, dsh_allgather_device, dsh_dist_collect
 //   plan.cpp      the pure-host planner (layout, tiles, bands, parts, work items, row partitions)
@@ -196,6 +197,11 @@ struct dsh_ctx {
     // dsh_greedy_threshold* (greedy.hip): assign[n], the count of representatives and the labels of the host form
     DevBuf gr_assign, gr_state, gr_labels;
     DevBuf gr_best;                     // dsh_greedy_extend* in BEST mode (greedy_extend.hip): one 64-bit key per new slot
+    // dsh_group_stats* (group_stats.hip): the labels, the per-slot accumulators (cnt, sum, worst key) and per-group medoid
+    // keys, the outputs of the host form, and for the pairs route the member CSR
+    DevBuf gs_labels, gs_acc, gs_grp, gs_out, gs_csr;
+    int stats_route = -1;               // option: -1 auto | 0 dense | 1 pairs
+    int stats_route_last = -1;          // (info) the route the last dsh_group_stats* call took
     uint64_t greedy_band_rows = 4096;   // option: a band holds at most this many rows (k_greedy_diag's LDS; 1..kGreedyMaxRows)
     // dsh_fold*, dsh_upload_sketches_folded*, dsh_union_groups* (derive.hip): the error word, a chunk of source rows or of
     // folded rows on its way through the device, the groups' CSR and the partial unions of groups cut into chunks
@@ -372,6 +378,19 @@ struct PairJob {
 int prepare(dsh_ctx *c, int estim, int want_sorted, bool card_only = false, uint64_t want_rb = 0,
             uint64_t want_re = ~0ull, uint32_t nparts = 1, int rowsorted = 0, const std::vector<uint64_t> *extra = nullptr);
 int run_pairs(dsh_ctx *c, const PairJob &job);
+
+// pairs.hip: the direct pair path over device-resident lists, as dsh_dist_pairs_device runs it
+struct PairsQuery {
+    int estim, k;
+    PairsTypes types;
+    uint32_t n_types;
+};
+int pairs_ensure_cards(dsh_ctx *c, int estim);  // the path's own cardinalities of all n sketches
+int pairs_err_begin(dsh_ctx *c);                // the two error words set to "none"
+// one chunk: cnt pairs at d_lhs / d_rhs (device), values to d_out[t * out_stride + x]; xbase: the chunk's first pair in the call
+int pairs_run_chunk(dsh_ctx *c, const PairsQuery &q, const uint32_t *d_lhs, const uint32_t *d_rhs, uint64_t xbase, uint64_t cnt,
+                    float *d_out, uint64_t out_stride);
+int pairs_err_end(dsh_ctx *c);                  // the one wait: reads the error words, fails the call on either
 
 // exchange.hip: waits for both streams of the communicator's traffic and destroys it (no-op without one)
 int comm_release(dsh_ctx *c);

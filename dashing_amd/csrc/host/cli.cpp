@@ -112,6 +112,12 @@ static void usage(const char *sub)
             "                           --representatives run over the first n_old inputs of this run, in this order; those keep\n"
             "                           their labels and only the inputs behind them are judged, against the old representatives\n"
             "                           and each other.  Outputs keep their formats.\n"
+            "  --stats                  with --cluster or --representatives (also with --assign / --extend): the statistics of the\n"
+            "                           labelling (dsh_group_stats).  Every text line gains three fields: the name of the group's\n"
+            "                           medoid (the member with the best total value to the others), the mean value of the input to\n"
+            "                           the other members of its group ('-' where it has none), and the worst such value; -b appends\n"
+            "                           u32 medoid[n], u32 cnt[n], i64 sum[n] (values in units of 2^-30), f32 worst[n].  Not with\n"
+            "                           --sizes.\n"
             "  --pairs FILE             emit only the pairs FILE lists, one per line as name_a<TAB>name_b (input names as given\n"
             "                           here; record names with dist_by_seq), in FILE's order: name_a<TAB>name_b and one value per\n"
             "                           measure.  --measures LIST: comma-separated from MASH_DIST, JI, SIZES, FULL_MASH_DIST,\n"
@@ -140,6 +146,7 @@ struct Opts {
     float reps_t = 0.f;
     int assign_mode = DSH_GREEDY_FIRST;  // --assign first|best (dsh_greedy_extend)
     bool has_assign = false;
+    bool has_stats = false;  // --stats: medoid, mean and worst value per input of the labelling (dsh_group_stats)
     std::string extend_file;  // --extend FILE: the labels of an earlier --representatives -b run over the first inputs
     std::string groups_file;  // --groups FILE: the unions of named groups are compared instead of the inputs (dsh_union_groups)
     std::string pairs_file, measures;  // --pairs FILE [--measures LIST]: only the listed pairs (dsh_dist_pairs)
@@ -149,7 +156,36 @@ struct Opts {
     std::vector<std::string> inpaths, querypaths;
 };
 
-enum { OPT_PRESKETCHED = 1000, OPT_AVOID_SORT, OPT_DEVICE, OPT_NPERBATCH, OPT_NN, OPT_NGPUS, OPT_DEVICES, OPT_RCCL, OPT_THRESHOLD, OPT_CLUSTER, OPT_REPS, OPT_ASSIGN, OPT_EXTEND, OPT_PAIRS, OPT_MEASURES, OPT_GROUPS, OPT_UNSUPPORTED };
+// --stats: what dsh_group_stats says about the labels of --cluster / --representatives, and its two output forms
+struct GroupStats {
+    std::vector<uint32_t> medoid, cnt;
+    std::vector<int64_t> sum;
+    std::vector<float> worst;
+    void compute(dsh_ctx *ctx, const Opts &o, const std::vector<uint32_t> &labels, size_t n)
+    {
+        medoid.resize(std::max<size_t>(n, 1)), cnt.resize(std::max<size_t>(n, 1)), sum.resize(std::max<size_t>(n, 1)), worst.resize(std::max<size_t>(n, 1));
+        DSH(ctx, dsh_group_stats(ctx, o.estim, o.result_type, o.k, labels.data(), medoid.data(), cnt.data(), sum.data(), worst.data()));
+    }
+    // behind labels[n]: u32 medoid[n], u32 cnt[n], i64 sum[n], f32 worst[n]
+    void write_binary(std::FILE *fp, size_t n) const
+    {
+        if (std::fwrite(medoid.data(), sizeof(uint32_t), n, fp) != n || std::fwrite(cnt.data(), sizeof(uint32_t), n, fp) != n ||
+            std::fwrite(sum.data(), sizeof(int64_t), n, fp) != n || std::fwrite(worst.data(), sizeof(float), n, fp) != n)
+            die("Error writing to binary file");
+    }
+    // <TAB>medoid's name<TAB>mean value to the own group ('-': no pair)<TAB>worst value, in --threshold's number format
+    void append_fields(std::string &s, size_t x, const std::vector<std::string> &names) const
+    {
+        char num[64];
+        s += '\t';
+        s += names[medoid[x]];
+        if (!cnt[x]) s += "\t-";
+        else s.append(num, (size_t)std::snprintf(num, sizeof num, "\t%.6g", (double)sum[x] / (double)cnt[x] / (double)(1ll << DSH_STATS_FRAC_BITS)));
+        s.append(num, (size_t)std::snprintf(num, sizeof num, "\t%.6g", (double)worst[x]));
+    }
+};
+
+enum { OPT_PRESKETCHED = 1000, OPT_AVOID_SORT, OPT_DEVICE, OPT_NPERBATCH, OPT_NN, OPT_NGPUS, OPT_DEVICES, OPT_RCCL, OPT_THRESHOLD, OPT_CLUSTER, OPT_REPS, OPT_ASSIGN, OPT_EXTEND, OPT_STATS, OPT_PAIRS, OPT_MEASURES, OPT_GROUPS, OPT_UNSUPPORTED };
 
 static Opts parse(int argc, char **argv, bool is_dist)
 {
@@ -178,6 +214,7 @@ static Opts parse(int argc, char **argv, bool is_dist)
         {"nearest-neighbors", required_argument, nullptr, OPT_NN}, {"threshold", required_argument, nullptr, OPT_THRESHOLD},
         {"cluster", required_argument, nullptr, OPT_CLUSTER}, {"representatives", required_argument, nullptr, OPT_REPS},
         {"assign", required_argument, nullptr, OPT_ASSIGN}, {"extend", required_argument, nullptr, OPT_EXTEND},
+        {"stats", no_argument, nullptr, OPT_STATS},
         {"pairs", required_argument, nullptr, OPT_PAIRS}, {"groups", required_argument, nullptr, OPT_GROUPS}, {"measures", required_argument, nullptr, OPT_MEASURES},
         // second arm of result_cmp (src/dashing.h:577-588); flag numbers as in DIST_LONG_OPTS
         {"sizes", no_argument, nullptr, 'Z'}, {"containment-index", no_argument, nullptr, 131},
@@ -270,6 +307,7 @@ static Opts parse(int argc, char **argv, bool is_dist)
             o.has_assign = true;
             break;
         case OPT_EXTEND: o.extend_file = optarg; break;
+        case OPT_STATS: o.has_stats = true; break;
         case OPT_PAIRS: o.pairs_file = optarg; break;
         case OPT_MEASURES: o.measures = optarg; break;
         case OPT_GROUPS: o.groups_file = optarg; break;
@@ -1024,6 +1062,8 @@ static int dist_main(int argc, char **argv, bool by_seq = false)
         if (o.devices.size() > 1 || o.rccl) die("--representatives runs on one device: --ngpus / --devices are not supported.");
     }
     if (o.has_assign && !o.has_reps) die("--assign goes with --representatives only.");
+    if (o.has_stats && !o.has_cluster && !o.has_reps) die("--stats goes with --cluster or --representatives only.");
+    if (o.has_stats && o.result_type == DSH_SIZES) die("--stats does not go with --sizes: set sizes have no mean or worst value inside a group.");
     // --extend: u64 n_old, u64 n_reps, u32 labels[n_old], as --representatives -b wrote it for the first n_old inputs
     std::vector<uint32_t> extend_labels;
     if (!o.extend_file.empty()) {
@@ -1259,10 +1299,13 @@ static int dist_main(int argc, char **argv, bool by_seq = false)
         std::vector<uint32_t> labels(std::max<size_t>(n, 1));
         uint64_t n_clusters = 0;
         DSH(ctx, dsh_cluster_threshold(ctx, o.estim, o.result_type, o.k, o.cluster_t, labels.data(), &n_clusters));
+        GroupStats gs;
+        if (o.has_stats) gs.compute(ctx, o, labels, n);
         if (o.fmt == BINARY) {
             const uint64_t hdr[2] = {(uint64_t)n, n_clusters};
             if (std::fwrite(hdr, sizeof(uint64_t), 2, pairofp) != 2 || std::fwrite(labels.data(), sizeof(uint32_t), n, pairofp) != n)
                 die("Error writing to binary file");
+            if (o.has_stats) gs.write_binary(pairofp, n);
         } else {
             const bool dist = o.result_type == 0 || o.result_type == 3 || o.result_type == 4 || o.result_type == 6 || o.result_type == 8;
             std::fprintf(pairofp, "#Cluster\t%s\t%s\t%.6g\n", kMeasureNames[o.result_type], dist ? "<=" : ">=", (double)o.cluster_t);  // --threshold's number format
@@ -1277,6 +1320,7 @@ static int dist_main(int argc, char **argv, bool by_seq = false)
                 s = o.inpaths[x];
                 s.append(num, (size_t)std::snprintf(num, sizeof num, "\t%u\t", index[labels[x]]));
                 s += o.inpaths[labels[x]];
+                if (o.has_stats) gs.append_fields(s, x, o.inpaths);
                 s += '\n';
                 std::fwrite(s.data(), 1, s.size(), pairofp);
             }
@@ -1290,10 +1334,13 @@ static int dist_main(int argc, char **argv, bool by_seq = false)
                                        extend_labels.empty() ? nullptr : extend_labels.data(), labels.data(), &n_reps));
         else
             DSH(ctx, dsh_greedy_threshold(ctx, o.estim, o.result_type, o.k, o.reps_t, labels.data(), &n_reps));
+        GroupStats gs;
+        if (o.has_stats) gs.compute(ctx, o, labels, n);
         if (o.fmt == BINARY) {
             const uint64_t hdr[2] = {(uint64_t)n, n_reps};
             if (std::fwrite(hdr, sizeof(uint64_t), 2, pairofp) != 2 || std::fwrite(labels.data(), sizeof(uint32_t), n, pairofp) != n)
                 die("Error writing to binary file");
+            if (o.has_stats) gs.write_binary(pairofp, n);
         } else {
             const bool dist = o.result_type == 0 || o.result_type == 3 || o.result_type == 4 || o.result_type == 6 || o.result_type == 8;
             std::fprintf(pairofp, "#Representatives\t%s\t%s\t%.6g\n", kMeasureNames[o.result_type], dist ? "<=" : ">=", (double)o.reps_t);  // --threshold's number format
@@ -1316,8 +1363,10 @@ static int dist_main(int argc, char **argv, bool by_seq = false)
                 s = o.inpaths[x];
                 s.append(num, (size_t)std::snprintf(num, sizeof num, "\t%u\t", index[labels[x]]));
                 s += o.inpaths[labels[x]];
-                if (labels[x] == x) s += "\t-\n";
-                else s.append(num, (size_t)std::snprintf(num, sizeof num, "\t%.6g\n", (double)pv[at++]));
+                if (labels[x] == x) s += "\t-";
+                else s.append(num, (size_t)std::snprintf(num, sizeof num, "\t%.6g", (double)pv[at++]));
+                if (o.has_stats) gs.append_fields(s, x, o.inpaths);
+                s += '\n';
                 std::fwrite(s.data(), 1, s.size(), pairofp);
             }
         }

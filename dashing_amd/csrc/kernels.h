@@ -228,6 +228,29 @@ hipError_t launch_greedy_best(hipStream_t st, const float *vals, const ThrRows &
 hipError_t launch_greedy_extend_labels(hipStream_t st, const uint32_t *assign, const uint64_t *best, uint64_t first_new, uint64_t n,
                                        uint32_t *labels, uint64_t *n_reps);
 
+// statistics of a labelling (kernels_group.hip, group_stats.hip): per slot the included pairs inside its group, the sum of
+// their values in 2^-30 units and the key of the worst one (0: none); the caller zeroes all three
+struct GsAccum {
+    uint32_t *cnt;
+    uint64_t *sum;
+    uint32_t *wkey;
+};
+// a band of triangle rows as launch_thr_count takes it, labels[n] on the device: what the band's pairs add to their ROWS ...
+hipError_t launch_gs_rows(hipStream_t st, const float *vals, const ThrRows &g, const uint32_t *labels, int descending, const GsAccum &a);
+// ... and to their COLUMNS
+hipError_t launch_gs_cols(hipStream_t st, const float *vals, const ThrRows &g, const uint32_t *labels, int descending, const GsAccum &a);
+// the intra-group pairs [x0, x0 + cnt) of a member CSR over the groups of at least two members: ppre[ngroups + 1] pairs before
+// each group, moff[ngroups + 1] its first member in mem (slots ascending inside a group); lhs = the larger slot
+hipError_t launch_gs_enum(hipStream_t st, const uint64_t *ppre, const uint32_t *moff, const uint32_t *mem, uint64_t ngroups, uint64_t x0,
+                          uint64_t cnt, uint32_t *lhs, uint32_t *rhs);
+// the values of n_pairs pairs folded into both ends
+hipError_t launch_gs_pairs(hipStream_t st, const uint32_t *lhs, const uint32_t *rhs, const float *vals, uint64_t n_pairs, uint64_t n,
+                           int descending, const GsAccum &a);
+// the medoid of every group (g_cnt, g_sum zeroed, g_slot all ones by the caller, [n] each, indexed by label) and the four
+// outputs, each written only where its pointer is not null
+hipError_t launch_gs_finish(hipStream_t st, const uint32_t *labels, uint64_t n, int descending, const GsAccum &a, uint32_t *g_cnt,
+                            uint64_t *g_sum, uint32_t *g_slot, uint32_t *medoid_out, uint32_t *cnt_out, int64_t *sum_out, float *worst_out);
+
 // explicit pair lists (kernels_pairs.hip, pairs.hip): histograms are [cnt][64] counters, uint16 for p <= kPairsMaxP16
 // (a bin holds at most 2^p), uint32 above
 constexpr int kPairsMaxP16 = 15;

@@ -42,6 +42,7 @@
 #include <algorithm>
 
 #include "kernels.h"
+#include "vkey.h"
 
 namespace dsh {
 
@@ -178,11 +179,7 @@ __device__ __forceinline__ unsigned long long ld_best(const unsigned long long *
 // form of v + 0.0f: equal as float32 must mean equal here), complemented where a smaller value is better; NaN never passes
 __device__ __forceinline__ unsigned long long best_key(float v, int descending, uint32_t r)
 {
-    uint32_t u = __float_as_uint(v);
-    if (u == 0x80000000u) u = 0u;
-    u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-    if (!descending) u = ~u;
-    return ((unsigned long long)u << 32) | (unsigned long long)(0xFFFFFFFFu - r);
+    return ((unsigned long long)value_key32(v, descending) << 32) | (unsigned long long)(0xFFFFFFFFu - r);
 }
 
 // One wave, one chunk [begin, end) of the values of representative row i (row starts at rowoff, its first value belongs to

@@ -10,13 +10,66 @@
 
 using namespace dsh;
 
-namespace {
+namespace dsh {
 
-struct PairsQuery {
-    int estim, k;
-    PairsTypes types;
-    uint32_t n_types;
-};
+// (declared in ctx.h: group_stats.hip computes its pairs with the same machinery)
+static size_t hist_bytes(const dsh_ctx *c, uint64_t cnt) { return cnt * 64 * (c->p <= kPairsMaxP16 ? 2 : 4); }
+
+// the path's own cardinalities of all n sketches under `estim`: k_pairs_hist over the "pairs" (s, s), k_pairs_card.  A
+// sketch with an out-of-range register is not reported here (it may never be named) -- it counts as empty.
+int pairs_ensure_cards(dsh_ctx *c, int estim)
+{
+    if (c->pairs_card_estim == estim) return DSH_OK;
+    c->pairs_card_estim = -1;
+    HIPCHK(c, c->pairs_card.ensure(std::max<uint64_t>(c->n, 1) * sizeof(double)));
+    const uint64_t chunk = c->pairs_chunk;
+    HIPCHK(c, c->pairs_hist.ensure(hist_bytes(c, std::min<uint64_t>(chunk, std::max<uint64_t>(c->n, 1)))));
+    for (uint64_t s0 = 0; s0 < c->n; s0 += chunk) {
+        const uint64_t cnt = std::min<uint64_t>(chunk, c->n - s0);
+        HIPCHK(c, launch_pairs_hist(c->stream, c->regs, c->n, c->p, nullptr, nullptr, s0, 0, cnt, c->pairs_hist.ptr, nullptr));
+        HIPCHK(c, launch_pairs_card(c->stream, c->pairs_hist.ptr, s0, cnt, c->p, estim, (double *)c->pairs_card.ptr));
+    }
+    c->pairs_card_estim = estim;
+    return DSH_OK;
+}
+
+int pairs_err_begin(dsh_ctx *c)
+{
+    HIPCHK(c, c->pairs_err.ensure(2 * sizeof(unsigned long long)));
+    HIPCHK(c, hipMemsetAsync(c->pairs_err.ptr, 0xFF, 2 * sizeof(unsigned long long), c->stream));
+    return DSH_OK;
+}
+
+// one chunk: cnt pairs at d_lhs / d_rhs (device), values to out[t * out_stride + x]
+int pairs_run_chunk(dsh_ctx *c, const PairsQuery &q, const uint32_t *d_lhs, const uint32_t *d_rhs, uint64_t xbase, uint64_t cnt,
+                    float *d_out, uint64_t out_stride)
+{
+    const double ksinv = (double)(float)(1. / (double)q.k);  // the float 1/k of dist_loop (src/sketch_and_cmp.h:797)
+    HIPCHK(c, c->pairs_hist.ensure(hist_bytes(c, cnt)));
+    HIPCHK(c, launch_pairs_hist(c->stream, c->regs, c->n, c->p, d_lhs, d_rhs, 0, xbase, cnt, c->pairs_hist.ptr,
+                                (unsigned long long *)c->pairs_err.ptr));
+    HIPCHK(c, launch_pairs_finish(c->stream, c->pairs_hist.ptr, d_lhs, d_rhs, c->n, cnt, c->p, q.estim,
+                                  (const double *)c->pairs_card.ptr, q.types, q.n_types, ksinv, d_out, out_stride));
+    return DSH_OK;
+}
+
+// the one wait of a call: the error words, then the stream is idle
+int pairs_err_end(dsh_ctx *c)
+{
+    unsigned long long e[2] = {~0ull, ~0ull};
+    HIPCHK(c, hipMemcpyAsync(e, c->pairs_err.ptr, sizeof e, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (e[0] != ~0ull)
+        return fail(c, DSH_EINVAL, "pair %llu names a slot outside [0, %llu)", e[0], (unsigned long long)c->n);
+    if (e[1] != ~0ull)
+        return fail(c, DSH_EINVAL, "sketch %llu holds a register value above %d (= 64 - p + 1): not an HLL of precision %d (corrupt or foreign .hll?)",
+                    e[1], 64 - c->p + 1, c->p);
+    return DSH_OK;
+}
+
+}  // namespace dsh
+
+namespace {
 
 int check_query(dsh_ctx *c, int estim, const int *result_types, uint32_t n_types, int k, PairsQuery &q)
 {
@@ -35,67 +88,13 @@ int check_query(dsh_ctx *c, int estim, const int *result_types, uint32_t n_types
     return DSH_OK;
 }
 
-size_t hist_bytes(const dsh_ctx *c, uint64_t cnt) { return cnt * 64 * (c->p <= kPairsMaxP16 ? 2 : 4); }
-
-// the path's own cardinalities of all n sketches under `estim`: k_pairs_hist over the "pairs" (s, s), k_pairs_card.  A
-// sketch with an out-of-range register is not reported here (it may never be named) -- it counts as empty.
-int ensure_cards(dsh_ctx *c, int estim)
-{
-    if (c->pairs_card_estim == estim) return DSH_OK;
-    c->pairs_card_estim = -1;
-    HIPCHK(c, c->pairs_card.ensure(std::max<uint64_t>(c->n, 1) * sizeof(double)));
-    const uint64_t chunk = c->pairs_chunk;
-    HIPCHK(c, c->pairs_hist.ensure(hist_bytes(c, std::min<uint64_t>(chunk, std::max<uint64_t>(c->n, 1)))));
-    for (uint64_t s0 = 0; s0 < c->n; s0 += chunk) {
-        const uint64_t cnt = std::min<uint64_t>(chunk, c->n - s0);
-        HIPCHK(c, launch_pairs_hist(c->stream, c->regs, c->n, c->p, nullptr, nullptr, s0, 0, cnt, c->pairs_hist.ptr, nullptr));
-        HIPCHK(c, launch_pairs_card(c->stream, c->pairs_hist.ptr, s0, cnt, c->p, estim, (double *)c->pairs_card.ptr));
-    }
-    c->pairs_card_estim = estim;
-    return DSH_OK;
-}
-
-int err_begin(dsh_ctx *c)
-{
-    HIPCHK(c, c->pairs_err.ensure(2 * sizeof(unsigned long long)));
-    HIPCHK(c, hipMemsetAsync(c->pairs_err.ptr, 0xFF, 2 * sizeof(unsigned long long), c->stream));
-    return DSH_OK;
-}
-
-// one chunk: cnt pairs at d_lhs / d_rhs (device), values to out[t * out_stride + x]
-int run_chunk(dsh_ctx *c, const PairsQuery &q, const uint32_t *d_lhs, const uint32_t *d_rhs, uint64_t xbase, uint64_t cnt,
-              float *d_out, uint64_t out_stride)
-{
-    const double ksinv = (double)(float)(1. / (double)q.k);  // the float 1/k of dist_loop (src/sketch_and_cmp.h:797)
-    HIPCHK(c, c->pairs_hist.ensure(hist_bytes(c, cnt)));
-    HIPCHK(c, launch_pairs_hist(c->stream, c->regs, c->n, c->p, d_lhs, d_rhs, 0, xbase, cnt, c->pairs_hist.ptr,
-                                (unsigned long long *)c->pairs_err.ptr));
-    HIPCHK(c, launch_pairs_finish(c->stream, c->pairs_hist.ptr, d_lhs, d_rhs, c->n, cnt, c->p, q.estim,
-                                  (const double *)c->pairs_card.ptr, q.types, q.n_types, ksinv, d_out, out_stride));
-    return DSH_OK;
-}
-
-// the one wait of a call: the error words, then the stream is idle
-int err_end(dsh_ctx *c)
-{
-    unsigned long long e[2] = {~0ull, ~0ull};
-    HIPCHK(c, hipMemcpyAsync(e, c->pairs_err.ptr, sizeof e, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (e[0] != ~0ull)
-        return fail(c, DSH_EINVAL, "pair %llu names a slot outside [0, %llu)", e[0], (unsigned long long)c->n);
-    if (e[1] != ~0ull)
-        return fail(c, DSH_EINVAL, "sketch %llu holds a register value above %d (= 64 - p + 1): not an HLL of precision %d (corrupt or foreign .hll?)",
-                    e[1], 64 - c->p + 1, c->p);
-    return DSH_OK;
-}
-
 // host forms: `fill(x0, cnt, lhs, rhs)` writes the pairs [x0, x0 + cnt) of the (already validated) list
 template <class Fill>
 int run_host(dsh_ctx *c, const PairsQuery &q, uint64_t n_pairs, const Fill &fill, float *out)
 {
     if (!n_pairs || !q.n_types) return DSH_OK;
-    int rc = ensure_cards(c, q.estim);
-    if (rc || (rc = err_begin(c))) return rc;
+    int rc = pairs_ensure_cards(c, q.estim);
+    if (rc || (rc = pairs_err_begin(c))) return rc;
     const uint64_t chunk = std::min<uint64_t>(c->pairs_chunk, n_pairs);
     HIPCHK(c, c->pairs_lhs.ensure(chunk * sizeof(uint32_t)));
     HIPCHK(c, c->pairs_rhs.ensure(chunk * sizeof(uint32_t)));
@@ -118,7 +117,7 @@ int run_host(dsh_ctx *c, const PairsQuery &q, uint64_t n_pairs, const Fill &fill
             rc = fail(c, DSH_EIO, "upload of the pair list failed");
             break;
         }
-        if ((rc = run_chunk(c, q, (const uint32_t *)c->pairs_lhs.ptr, (const uint32_t *)c->pairs_rhs.ptr, x0, cnt,
+        if ((rc = pairs_run_chunk(c, q, (const uint32_t *)c->pairs_lhs.ptr, (const uint32_t *)c->pairs_rhs.ptr, x0, cnt,
                             (float *)c->pairs_out.ptr, chunk)))
             break;
         for (uint32_t t = 0; t < q.n_types; ++t)
@@ -133,7 +132,7 @@ int run_host(dsh_ctx *c, const PairsQuery &q, uint64_t n_pairs, const Fill &fill
         (void)hipGetLastError();
         return rc;
     }
-    return err_end(c);
+    return pairs_err_end(c);
 }
 
 }  // namespace
@@ -165,16 +164,16 @@ int dsh_dist_pairs_device(dsh_ctx *c, int estim, const int *result_types, uint32
     if (rc) return rc;
     if (!n_pairs || !n_types) return DSH_OK;
     if (!d_lhs || !d_rhs || !d_out) return DSH_EINVAL;
-    if ((rc = ensure_cards(c, q.estim)) || (rc = err_begin(c))) return rc;
+    if ((rc = pairs_ensure_cards(c, q.estim)) || (rc = pairs_err_begin(c))) return rc;
     const uint64_t chunk = c->pairs_chunk;
     for (uint64_t x0 = 0; x0 < n_pairs; x0 += chunk) {
         const uint64_t cnt = std::min<uint64_t>(chunk, n_pairs - x0);
-        if ((rc = run_chunk(c, q, (const uint32_t *)d_lhs + x0, (const uint32_t *)d_rhs + x0, x0, cnt, (float *)d_out + x0, n_pairs))) {
+        if ((rc = pairs_run_chunk(c, q, (const uint32_t *)d_lhs + x0, (const uint32_t *)d_rhs + x0, x0, cnt, (float *)d_out + x0, n_pairs))) {
             (void)hipStreamSynchronize(c->stream);
             return rc;
         }
     }
-    return err_end(c);
+    return pairs_err_end(c);
 }
 
 int dsh_dist_pairs_csr(dsh_ctx *c, int estim, const int *result_types, uint32_t n_types, int k, uint64_t row_begin,

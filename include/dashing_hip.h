@@ -62,7 +62,8 @@ typedef struct dsh_ctx dsh_ctx;
  * Entry points that were only ADDED since leave the number alone and are detected by symbol (dlsym):
  * dsh_dist_threshold, dsh_dist_threshold_device, dsh_dist_rect_threshold, dsh_dist_pairs*, dsh_fold*,
  * dsh_upload_sketches_folded*, dsh_union_groups*, dsh_cluster_threshold, dsh_cluster_threshold_device, dsh_cluster_pairs,
- * dsh_cluster_csr, dsh_greedy_threshold, dsh_greedy_threshold_device, dsh_greedy_extend, dsh_greedy_extend_device. */
+ * dsh_cluster_csr, dsh_greedy_threshold, dsh_greedy_threshold_device, dsh_greedy_extend, dsh_greedy_extend_device,
+ * dsh_group_stats, dsh_group_stats_device. */
 #define DSH_ABI_VERSION 7
 int dsh_abi_version(void);
 
@@ -511,6 +512,64 @@ int dsh_greedy_extend(dsh_ctx *ctx, int estim, int result_type, int k, float thr
 int dsh_greedy_extend_device(dsh_ctx *ctx, int estim, int result_type, int k, float threshold, int assign_mode,
                              uint64_t first_new, const uint32_t *labels_in, void *d_labels, uint64_t *n_reps);
 
+/* ---- statistics of a labelling: per-group counts, sums, worst values and medoids, on the device -----------
+ * What a client asks about the labels of dsh_cluster_*, dsh_greedy_* or its own group ids next: how far has a component
+ * chained (its worst intra-group value), how well does each member sit in its group (its mean value to the others), and
+ * which member should represent it (the medoid, not the smallest slot).  Without this call the answer needs the hits of
+ * dsh_dist_threshold at a threshold loose enough to hold every intra-group pair, or the dense matrix, on the host.
+ *   Labels.  labels is a HOST uint32 [n] in both forms; any values < n are legal; a group is the set of slots with equal
+ *     labels.  Nothing else is required of them (labels[labels[x]] need not be labels[x]).
+ *   v(x, y), x != y: the float32 dsh_dist_rows writes at dsh_tri_index(n, min(x, y), max(x, y)) -- for the asymmetric
+ *     measures the ONE orientation of the triangle, as in the cluster and greedy calls.  A pair is INCLUDED iff v is not
+ *     NaN and |v| < 2 (every measure but DSH_SIZES lives there for real sketches; DSH_SIZES is refused with DSH_EINVAL).
+ *     q(v) = llrint((double)v * 2^DSH_STATS_FRAC_BITS), round to nearest even; the product is exact in double.
+ *   cnt[x]    the number of y != x in x's group whose pair with x is included.
+ *   sum[x]    the sum of q(v(x, y)) over those y, int64 (n <= 2^32 - 1 and |q| < 2^31 keep it inside); the mean value of x
+ *             to its group is sum / cnt / 2^DSH_STATS_FRAC_BITS.
+ *   worst[x]  the worst included value: the smallest for the similarity forms, the largest for the *_DIST forms, compared
+ *             as float32 with -0.0 equal to +0.0 (a zero is reported as +0.0); NaN when cnt[x] == 0.  The diameter of a
+ *             group is the worst worst[x] over its members.
+ *   medoid[x] the member m of x's group chosen by three keys in turn: the largest cnt[m]; then the best sum[m] (largest
+ *             for the similarity forms, smallest for the *_DIST forms); then the smallest slot.  A singleton is its own.
+ *   Any output pointer may be NULL: that output is not written; exactly n entries of every other one are.
+ *   This has one answer: all accumulation is in integers (32-bit counts, 64-bit sums, the worst value as an order-preserving
+ *     32-bit key under an integer maximum; no float atomics), so it depends on no band size, route, launch geometry or order
+ *     of arrival of atomics, and the same call gives the same bytes.
+ *   Two routes, one result.  P_in = the intra-group pairs, sum over the groups of s (s - 1) / 2, known on the host.
+ *     dense: the band loop of dsh_cluster_threshold ("threshold_band_bytes", at most 2^20 rows) with two kernels per band:
+ *       k_gs_rows (one wave per 4096-value chunk of a row; at most one set of three atomics per wave, none where no column
+ *       of the chunk is in the row's group) and k_gs_cols (a thread per column walks the band's rows above it in slabs of
+ *       512 rows; at most one set per column and slab).  The number of atomics does not grow with the matching pairs.
+ *     pairs: the member lists of the groups of two or more (4 bytes per slot, 12 per group) go to the device; k_gs_enum
+ *       writes the intra-group pairs chunk by chunk ("pairs_chunk") as lhs = the larger slot, rhs = the smaller -- the
+ *       orientation for which dsh_dist_pairs_device gives the triangle's bits -- the direct pair path computes them and
+ *       k_gs_pairs folds each value into both ends.  Nothing of the size of P_in crosses PCIe or exists at once.
+ *     Option "stats_route": -1 auto | 0 dense | 1 pairs; no result depends on it.  Auto takes the pairs route iff
+ *       20 * P_in <= n (n - 1) / 2: the 5 % break-even of pair lists above, which the measurement of this call
+ *       confirms (below).  dsh_get_info(ctx, "stats_route") is the route the last call took.
+ *   Out-of-range registers: each route fails as its machinery does, DSH_EINVAL with a message that names the sketch, the
+ *     outputs unspecified.  The dense route judges ALL sketches; the pairs route only those inside a group of two or more.
+ *   Cached state.  After the dense route it is as after dsh_dist_threshold on rows [0, n), after the pairs route as after
+ *     dsh_dist_pairs_device: a dense call before and after either gives the same bytes.
+ *   Execution.  Synchronous, on the ctx stream; no host wait between bands or chunks, one at the end.
+ *   Errors, before anything is enqueued: DSH_EINVAL for a NULL context, n > 2^32 - 1, a label >= n (the message names the
+ *     slot), DSH_SIZES, an estimator or result_type out of range; DSH_ESTATE without sketches.  n == 0 and n == 1 succeed.
+ *   Cost model: dense = the dense path's cost for the triangle plus two more reads of each band (values
+ *     and labels for the rows, labels from LDS and the matching values for the columns: at most 8 bytes per pair);
+ *     pairs = 2 * 2^p bytes per intra-group pair.  Measured on one MI355X (tools/bench_group_stats.py, profiles/stats1;
+ *     A = the dense call): at 100 000 x p=10 (A = 282 ms) dense - A = 5.3 ms at P_in = 0.01 % of all pairs to 16.7 ms at
+ *     100 %, pairs = 0.87 ms to 4.8 s; at 10 000 x p=14 (A = 13.0 ms) dense - A stays below 0.5 ms, pairs = 0.26 ms to 288 ms.
+ *     The routes cost the same at P_in = 4.1 % (p = 14) and 5.7 % (p = 10) of all pairs.
+ *   dsh_group_stats         the four outputs in host memory.
+ *   dsh_group_stats_device  the four outputs caller-owned DEVICE arrays [n] (d_sum 8-byte aligned).
+ *   Not built: a multi-GPU form; statistics of a rectangle; relabelling to medoids inside the cluster / greedy calls (the
+ *     client maps labels -> medoid[labels]); weighted members. */
+#define DSH_STATS_FRAC_BITS 30
+int dsh_group_stats(dsh_ctx *ctx, int estim, int result_type, int k, const uint32_t *labels, uint32_t *medoid_out,
+                    uint32_t *cnt_out, int64_t *sum_out, float *worst_out);
+int dsh_group_stats_device(dsh_ctx *ctx, int estim, int result_type, int k, const uint32_t *labels, void *d_medoid,
+                           void *d_cnt, void *d_sum, void *d_worst);
+
 /* ---- multi-GPU shards of the full triangle ------------------------------------------------
  * Every rank holds all sketches (dsh_upload/attach) and computes one shard; no collective is
  * needed inside the compare.  Internally the plane matrix is laid out in (threshold, min value)
@@ -723,6 +782,7 @@ int dsh_finalize_phase_cycles(dsh_ctx *ctx, uint64_t *out16);
  *                 "threshold_band_bytes"    dsh_dist_threshold* computes bands of whole rows of at most this much float32 (1 GiB)
  *                 "cluster_chunk"           dsh_cluster_pairs / dsh_cluster_csr unite at most this many edges per launch (2^20)
  *                 "greedy_band_rows"        a band of dsh_greedy_threshold* holds at most this many rows (4096; 1..8192)
+ *                 "stats_route"             -1 auto | 0 dense | 1 pairs: how dsh_group_stats* computes the intra-group values
  *                 "derive_chunk_bytes"      the host forms of dsh_fold / dsh_upload_sketches_folded move at most this many bytes
  *                                           of source rows per step (256 MiB; at least one row)
  *   layout        "sort"                    -1 auto | 0 | 1: key-ordered plane columns (0 = identity: the slow, simple layout)
@@ -761,7 +821,8 @@ int dsh_set_option(dsh_ctx *ctx, const char *name, int64_t value);
  * "vhi", "pbase", "threshold", "emax", "elow", "kc", "pair_groups" (as the last prepare put them into effect), "pair_round" (work items per round of the last dist call's first launch of the tile kernel: 256 x the items per workgroup it ran with), "tile", "npad", "kpad", "cum_bytes", "sorted", "ncols", "lockstep", "tiles", "bands", "items" (work items of the tile kernel),
  * "words_per_plane", "avg_tile_planes_x100" (of the last dist call), "frag_items", "parts_done", "parts_signalled",
  * "place_kernel_us" (with profiling on: device time of the last dsh_exchange_place_device's placement kernel),
- * "sketch_kernel_us" / "fastx_decode_us" (with profiling on: k_sketch / the FASTA-FASTQ decode kernels of the last sketch call). */
+ * "sketch_kernel_us" / "fastx_decode_us" (with profiling on: k_sketch / the FASTA-FASTQ decode kernels of the last sketch call),
+ * "stats_route" (the route the last dsh_group_stats* call took: 0 dense, 1 pairs; -1 before the first). */
 int dsh_get_info(dsh_ctx *ctx, const char *name, int64_t *out);
 /* HIP stream of the ctx as a void* (hipStream_t) so a host framework can order its own work.
  * Every *_device entry point runs on THIS stream and (except the *_async forms) returns after its work has
