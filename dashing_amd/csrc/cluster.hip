@@ -1,12 +1,11 @@
 // cluster.hip -- dsh_cluster_threshold*, dsh_cluster_pairs, dsh_cluster_csr: connected components on the device
-// (DESIGN.md 4.10).  The threshold forms are the band loop of run_threshold (threshold.hip) -- the same band rule, the
-// same PairJob::triangle + run_pairs into the library-owned band buffer, the dense path unchanged -- with k_cc_band in the
-// place of count / scan / emit: a passing value unites its row and its column in a union-find (kernels_cluster.hip, uf.h)
-// and is never written anywhere.  No host wait between bands; one wait at the end reads the error word and the root
+// (DESIGN.md 4.10).  The threshold forms are the band walk of bands.h -- the band rule and the band buffer of
+// dsh_dist_threshold*, the dense path unchanged -- with k_cc_band in the place of count / scan / emit: a passing value
+// unites its row and its column in a union-find (kernels_cluster.hip, uf.h) and is never written anywhere.  No host wait between bands; one wait at the end reads the error word and the root
 // count.  The pairs and CSR forms run the same union-find over a caller's graph and need no sketches.
 #include <algorithm>
 
-#include "ctx.h"
+#include "bands.h"
 
 using namespace dsh;
 
@@ -57,14 +56,6 @@ int cc_finish(dsh_ctx *c, uint64_t n, uint32_t *d_labels, uint32_t *h_labels, ui
     return DSH_OK;
 }
 
-// a failed enqueue: leave the stream idle, as every entry point does
-int cc_abort(dsh_ctx *c, int rc)
-{
-    (void)hipStreamSynchronize(c->stream);
-    (void)hipGetLastError();
-    return rc;
-}
-
 int run_cluster_threshold(dsh_ctx *c, int estim, int result_type, int k, float t, uint32_t *d_labels, uint32_t *h_labels,
                           uint64_t *n_clusters)
 {
@@ -73,45 +64,17 @@ int run_cluster_threshold(dsh_ctx *c, int estim, int result_type, int k, float t
     if (n_clusters) *n_clusters = 0;
     if (!n) return DSH_OK;
     const int descending = measure_descending(result_type) ? 1 : 0;
-    const uint64_t band_floats = std::max<uint64_t>(c->threshold_band_bytes / sizeof(float), 1);
     int rc = cc_begin(c, n);
     if (rc) return rc;
-    for (uint64_t b0 = 0; b0 + 1 < n && rc == DSH_OK;) {  // (the last row has no values)
-        // a band: whole rows, at most band_floats values (one row at least), at most 2^20 rows (run_threshold's rule)
-        uint64_t b1 = b0, span = 0;
-        const uint64_t longest = n - 1 - b0;
-        do {
-            span += n - 1 - b1;
-            ++b1;
-        } while (b1 < n && b1 - b0 < (1u << 20) && span + (n - 1 - b1) <= band_floats);
-        const uint64_t nchunks64 = std::max<uint64_t>((longest + kThrChunk - 1) / kThrChunk, 1);
-        if ((nchunks64 + 3) / 4 > 65535) return cc_abort(c, fail(c, DSH_EINVAL, "rows of %llu values are not supported", (unsigned long long)longest));
-        ThrRows g;
-        g.rect = 0;
-        g.n = n;
-        g.row0 = b0;
-        g.ncols = 0;
-        g.col0 = 0;
-        g.rows = b1 - b0;
-        g.nchunks = (uint32_t)nchunks64;
-        if (c->thr_vals.ensure(std::max<uint64_t>(span, 1) * sizeof(float)) != hipSuccess) {
-            (void)hipGetLastError();
-            rc = fail(c, DSH_ENOMEM, "device allocation failed");
-            break;
-        }
-        if (span) {
-            if ((rc = run_pairs(c, PairJob::triangle(estim, result_type, k, b0, b1, dsh_tri_span(n, 0, b0), c->thr_vals.ptr)))) break;
-            const hipError_t e = launch_cc_band(c->stream, (const float *)c->thr_vals.ptr, g, t, descending, (uint32_t *)c->cc_parent.ptr,
-                                                cc_cap(n), cc_err(c));
-            if (e != hipSuccess) {
-                rc = fail(c, DSH_EIO, "k_cc_band: %s", hipGetErrorString(e));
-                break;
-            }
-        }
-        b0 = b1;
-    }
-    if (rc) return cc_abort(c, rc);
-    if ((rc = cc_finish(c, n, d_labels, h_labels, n_clusters))) return cc_abort(c, rc);
+    BandQuery bq;
+    bq.estim = estim, bq.result_type = result_type, bq.k = k;
+    bq.re = n;
+    rc = for_each_band(c, bq, [&](const ThrRows &g, const float *vals, uint64_t) -> int {
+        const hipError_t e = launch_cc_band(c->stream, vals, g, t, descending, (uint32_t *)c->cc_parent.ptr, cc_cap(n), cc_err(c));
+        return e == hipSuccess ? DSH_OK : fail(c, DSH_EIO, "k_cc_band: %s", hipGetErrorString(e));
+    });
+    if (rc) return drain(c, rc);
+    if ((rc = cc_finish(c, n, d_labels, h_labels, n_clusters))) return drain(c, rc);
     return DSH_OK;
 }
 
@@ -170,16 +133,16 @@ int dsh_cluster_pairs(dsh_ctx *c, uint64_t n_nodes, const uint32_t *lhs, const u
         HIPCHK(c, c->cc_lhs.ensure(chunk * sizeof(uint32_t)));
         HIPCHK(c, c->cc_rhs.ensure(chunk * sizeof(uint32_t)));
     }
-    if ((rc = cc_begin(c, n_nodes)) || (rc = cc_seed(c, n_nodes, labels_in))) return cc_abort(c, rc);
+    if ((rc = cc_begin(c, n_nodes)) || (rc = cc_seed(c, n_nodes, labels_in))) return drain(c, rc);
     for (uint64_t x0 = 0; x0 < n_pairs; x0 += chunk) {
         const uint64_t cnt = std::min<uint64_t>(chunk, n_pairs - x0);
         if (hipMemcpyAsync(c->cc_lhs.ptr, lhs + x0, cnt * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream) != hipSuccess ||
             hipMemcpyAsync(c->cc_rhs.ptr, rhs + x0, cnt * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream) != hipSuccess ||
             launch_cc_edges(c->stream, (uint32_t *)c->cc_parent.ptr, (const uint32_t *)c->cc_lhs.ptr, (const uint32_t *)c->cc_rhs.ptr, cnt,
                             n_nodes, cc_cap(n_nodes), cc_err(c)) != hipSuccess)
-            return cc_abort(c, fail(c, DSH_EIO, "upload of the edge list / k_cc_edges failed"));
+            return drain(c, fail(c, DSH_EIO, "upload of the edge list / k_cc_edges failed"));
     }
-    if ((rc = cc_finish(c, n_nodes, nullptr, labels_out, n_clusters))) return cc_abort(c, rc);
+    if ((rc = cc_finish(c, n_nodes, nullptr, labels_out, n_clusters))) return drain(c, rc);
     return DSH_OK;
 }
 
@@ -204,20 +167,20 @@ int dsh_cluster_csr(dsh_ctx *c, uint64_t n_nodes, uint64_t row_begin, uint64_t r
         HIPCHK(c, c->cc_rowptr.ensure((rows + 1) * sizeof(uint64_t)));
         HIPCHK(c, c->cc_lhs.ensure(chunk * sizeof(uint32_t)));
     }
-    if ((rc = cc_begin(c, n_nodes)) || (rc = cc_seed(c, n_nodes, labels_in))) return cc_abort(c, rc);
+    if ((rc = cc_begin(c, n_nodes)) || (rc = cc_seed(c, n_nodes, labels_in))) return drain(c, rc);
     if (n_hits) {
         // the row pointer travels whole (8 bytes per row), the columns in chunks; the row of a hit is found on the device
         if (hipMemcpyAsync(c->cc_rowptr.ptr, row_ptr, (rows + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream) != hipSuccess)
-            return cc_abort(c, fail(c, DSH_EIO, "upload of the row pointer failed"));
+            return drain(c, fail(c, DSH_EIO, "upload of the row pointer failed"));
         for (uint64_t x0 = 0; x0 < n_hits; x0 += chunk) {
             const uint64_t cnt = std::min<uint64_t>(chunk, n_hits - x0);
             if (hipMemcpyAsync(c->cc_lhs.ptr, col + h0 + x0, cnt * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream) != hipSuccess ||
                 launch_cc_csr(c->stream, (uint32_t *)c->cc_parent.ptr, (const uint64_t *)c->cc_rowptr.ptr, rows, row_begin,
                               (const uint32_t *)c->cc_lhs.ptr, h0 + x0, cnt, n_nodes, cc_cap(n_nodes), cc_err(c)) != hipSuccess)
-                return cc_abort(c, fail(c, DSH_EIO, "upload of the columns / k_cc_csr failed"));
+                return drain(c, fail(c, DSH_EIO, "upload of the columns / k_cc_csr failed"));
         }
     }
-    if ((rc = cc_finish(c, n_nodes, nullptr, labels_out, n_clusters))) return cc_abort(c, rc);
+    if ((rc = cc_finish(c, n_nodes, nullptr, labels_out, n_clusters))) return drain(c, rc);
     return DSH_OK;
 }
 

@@ -13,6 +13,8 @@ constexpr int kMaxPReg32 = 15;  // up to here k_sketch keeps one 32-bit word per
                                 // (A/B profiles/rd6d, rd6e: p = 10 +11 %, 12-13 +18 %, 14 +4 %; 15 would be -32 %: one workgroup per CU)
 constexpr int kMaxPCompare = 24;  // the compare path takes every p the sketches can have
 constexpr int kMaxP = 24;      // largest p for sketching / cardinalities / up- and download (positions are 24-bit)
+constexpr uint32_t kThrChunk = 4096;  // values of a band row that one wave walks (kernels.h: ThrRows)
+constexpr uint32_t kBandMaxRows = 1u << 20;  // rows of a band of the dense path's consumers (plan.h: tri_band_end, rect_band_rows)
 constexpr uint32_t kSketchSub = 8192;  // bases per sub-chunk (256 threads x 32 start positions)
 
 }  // namespace dsh

@@ -3,6 +3,8 @@
 //   abi.hip       context, resident sketches, sketch waist, cardinalities, compare entry points, tickets, options
 //   engine.hip    prepare() (per-sketch pass, layout, bit-planes, position index) and run_pairs() (tile kernel + k_finalize)
 //   knn.hip       dsh_knn
+//   bands.h       (header) the band walk of the five consumers of dense bands: threshold, cluster, greedy, greedy_extend,
+//                 group_stats -- band rule (plan.cpp), geometry, run_pairs into thr_vals, a callback per band
 //   threshold.hip dsh_dist_threshold*, dsh_dist_rect_threshold (values that pass a threshold, as CSR)
 //   pairs.hip     dsh_dist_pairs* (values of an explicit list of pairs, the direct form)
 //   cluster.hip   dsh_cluster_* (connected components at a threshold, or of a caller's graph)
@@ -178,10 +180,10 @@ struct dsh_ctx {
     uint64_t cum_budget = 8ull << 30;  // scratch for C(v) per pair slot: larger jobs run in bands (2 -> 8 GiB: -1.5 % at 100 000 x p=10)
     int sort_mode = -1;  // -1 auto (key-ordered columns for triangle calls of >= range_sort_min_rows rows), 0 never
     int range_sort_min_rows = 1024;  // smaller row ranges keep the cached identity layout (a rebuild costs more than it saves)
-    // dsh_dist_threshold* (threshold.hip): a band's dense values, its per-chunk counts and offsets, the running total,
-    // and for the host forms the band's hits and the row pointer on their way out
+    // a band's dense values (bands.h: every band consumer); dsh_dist_threshold* (threshold.hip): its per-chunk counts and
+    // offsets, the running total, and for the host forms the band's hits and the row pointer on their way out
     DevBuf thr_vals, thr_cnt, thr_off, thr_total, thr_col, thr_val, thr_rowptr;
-    uint64_t threshold_band_bytes = (uint64_t)1 << 30;  // a band of dsh_dist_threshold* holds at most this much float32
+    uint64_t threshold_band_bytes = (uint64_t)1 << 30;  // a band (bands.h) holds at most this much float32
     uint64_t knn_square_budget = (uint64_t)96 << 30;  // all-vs-all kNN keeps an n x n float matrix in HBM up to this size
     // dsh_dist_pairs* (pairs.hip): the path's OWN cardinalities (nothing of the dense path's derived state is read or
     // written), a chunk's histograms, the host forms' chunk of the list and of the result, the error words
@@ -320,6 +322,14 @@ inline void reset_prof(dsh_ctx *c)
     c->pair_ms = c->fin_ms = c->prep_ms = 0;
     c->pair_launches = 0;
     c->ev_used = 0;
+}
+
+// an entry point that fails after it has enqueued work: leave the stream idle, as every entry point does
+inline int drain(dsh_ctx *c, int rc)
+{
+    (void)hipStreamSynchronize(c->stream);
+    (void)hipGetLastError();
+    return rc;
 }
 
 // what every entry point that reads the resident sketches starts with (reset_prof stays with the entry point: where it

@@ -29,13 +29,6 @@ int err_end(dsh_ctx *c, int src_p)
     return DSH_OK;
 }
 
-int drain(dsh_ctx *c, int rc)
-{
-    (void)hipStreamSynchronize(c->stream);
-    (void)hipGetLastError();
-    return rc;
-}
-
 uint64_t chunk_rows(const dsh_ctx *c, int src_p) { return std::max<uint64_t>(c->derive_chunk_bytes >> src_p, 1); }
 
 int check_fold(dsh_ctx *c, uint64_t first, uint64_t n, int new_p)

@@ -1,30 +1,21 @@
 // greedy.hip -- dsh_greedy_threshold*: greedy representatives at a threshold, in slot order, on the device (DESIGN.md
-// 4.11).  The band loop of run_cluster_threshold (cluster.hip) -- PairJob::triangle + run_pairs into the library-owned band
-// buffer, the dense path unchanged -- with one more cap on a band's rows (plan::greedy_band_end) and, per band,
+// 4.11).  The band walk of bands.h -- the band buffer of dsh_dist_threshold*, the dense path unchanged -- with one more
+// cap on a band's rows (BandQuery::row_cap = the option greedy_band_rows) and, per band,
 // k_greedy_diag (the band's rows among themselves, sequential, in LDS) then k_greedy_band (its representative rows against
 // every later column) in the place of k_cc_band (kernels_greedy.hip).  No host wait between bands; one wait at the end
 // reads the count.  There is no give-up path: no loop of the kernels depends on another thread.
 #include <algorithm>
 
-#include "ctx.h"
+#include "bands.h"
 
 using namespace dsh;
 
 namespace {
 
-// a failed enqueue: leave the stream idle, as every entry point does
-int greedy_abort(dsh_ctx *c, int rc)
-{
-    (void)hipStreamSynchronize(c->stream);
-    (void)hipGetLastError();
-    return rc;
-}
-
 int greedy_bands(dsh_ctx *c, int estim, int result_type, int k, float t, uint32_t *d_labels, uint32_t *h_labels, uint64_t *n_reps)
 {
     const uint64_t n = c->n;
     const int descending = measure_descending(result_type) ? 1 : 0;
-    const uint64_t band_floats = std::max<uint64_t>(c->threshold_band_bytes / sizeof(float), 1);
     HIPCHK(c, c->gr_assign.ensure(n * sizeof(uint32_t)));
     HIPCHK(c, c->gr_state.ensure(sizeof(uint64_t)));
     if (!d_labels) {
@@ -35,30 +26,16 @@ int greedy_bands(dsh_ctx *c, int estim, int result_type, int k, float t, uint32_
     uint64_t *d_reps = (uint64_t *)c->gr_state.ptr;
     HIPCHK(c, hipMemsetAsync(d_reps, 0, sizeof(uint64_t), c->stream));
     HIPCHK(c, launch_cc_init(c->stream, assign, n));  // assign[x] = x
-    for (uint64_t b0 = 0; b0 + 1 < n;) {  // (the last row has no values)
-        const uint64_t b1 = plan::greedy_band_end(n, b0, band_floats, c->greedy_band_rows);
-        const uint64_t span = dsh_tri_span(n, b0, b1), longest = n - 1 - b0;
-        const uint64_t nchunks64 = std::max<uint64_t>((longest + kThrChunk - 1) / kThrChunk, 1);
-        if ((nchunks64 + 3) / 4 > 65535) return fail(c, DSH_EINVAL, "rows of %llu values are not supported", (unsigned long long)longest);
-        ThrRows g;
-        g.rect = 0;
-        g.n = n;
-        g.row0 = b0;
-        g.ncols = 0;
-        g.col0 = 0;
-        g.rows = b1 - b0;
-        g.nchunks = (uint32_t)nchunks64;
-        HIPCHK(c, c->thr_vals.ensure(std::max<uint64_t>(span, 1) * sizeof(float)));
-        if (span) {
-            const int rc = run_pairs(c, PairJob::triangle(estim, result_type, k, b0, b1, dsh_tri_span(n, 0, b0), c->thr_vals.ptr));
-            if (rc) return rc;
-            const float *vals = (const float *)c->thr_vals.ptr;
-            hipError_t e = launch_greedy_diag(c->stream, vals, g, t, descending, assign);
-            if (e == hipSuccess) e = launch_greedy_band(c->stream, vals, g, t, descending, assign);
-            if (e != hipSuccess) return fail(c, DSH_EIO, "k_greedy_diag/k_greedy_band: %s", hipGetErrorString(e));
-        }
-        b0 = b1;
-    }
+    BandQuery bq;
+    bq.estim = estim, bq.result_type = result_type, bq.k = k;
+    bq.re = n;
+    bq.row_cap = c->greedy_band_rows;
+    const int rc = for_each_band(c, bq, [&](const ThrRows &g, const float *vals, uint64_t) -> int {
+        hipError_t e = launch_greedy_diag(c->stream, vals, g, t, descending, assign);
+        if (e == hipSuccess) e = launch_greedy_band(c->stream, vals, g, t, descending, assign);
+        return e == hipSuccess ? DSH_OK : fail(c, DSH_EIO, "k_greedy_diag/k_greedy_band: %s", hipGetErrorString(e));
+    });
+    if (rc) return rc;
     HIPCHK(c, launch_greedy_labels(c->stream, assign, n, d_labels, d_reps));
     uint64_t reps = 0;
     HIPCHK(c, hipMemcpyAsync(&reps, d_reps, sizeof reps, hipMemcpyDeviceToHost, c->stream));
@@ -78,7 +55,7 @@ int run_greedy_threshold(dsh_ctx *c, int estim, int result_type, int k, float t,
     if (c->n > 0xFFFFFFFFull) return fail(c, DSH_EINVAL, "%llu sketches: labels are 32-bit", (unsigned long long)c->n);
     if (n_reps) *n_reps = 0;
     if (!c->n) return DSH_OK;
-    if ((rc = greedy_bands(c, estim, result_type, k, t, d_labels, h_labels, n_reps))) return greedy_abort(c, rc);
+    if ((rc = greedy_bands(c, estim, result_type, k, t, d_labels, h_labels, n_reps))) return drain(c, rc);
     return DSH_OK;
 }
 

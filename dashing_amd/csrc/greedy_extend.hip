@@ -2,25 +2,18 @@
 // the caller brings (slots [0, m) keep their labels, slots [m, n) are judged), with the covered slots given to the FIRST
 // or to the BEST representative that hits them.  Two phases on the ctx stream, the dense path unchanged:
 //   1. the old representatives against the new columns: bands of old rows (plan::greedy_old_band: from a representative to
-//      a representative, stretches without one skipped) computed by PairJob::rectangle into the library-owned band buffer and
-//      walked by k_greedy_rect;
-//   2. the new rows among themselves: the band loop of greedy.hip started at row m -- k_greedy_diag, then k_greedy_band
+//      a representative, stretches without one skipped), each computed into the library-owned band buffer (bands.h:
+//      thr_geometry + compute_band) and walked by k_greedy_rect;
+//   2. the new rows among themselves: the band walk of greedy.hip (bands.h) started at row m -- k_greedy_diag, then k_greedy_band
 //      (FIRST) or k_greedy_best (BEST), kernels_greedy.hip.
 // k_greedy_extend_labels writes the labels.  No host wait between bands; one wait at the end reads the count.
 #include <algorithm>
 
-#include "ctx.h"
+#include "bands.h"
 
 using namespace dsh;
 
 namespace {
-
-int extend_abort(dsh_ctx *c, int rc)
-{
-    (void)hipStreamSynchronize(c->stream);
-    (void)hipGetLastError();
-    return rc;
-}
 
 int extend_bands(dsh_ctx *c, int estim, int result_type, int k, float t, int best_mode, uint64_t m, const uint32_t *labels_in,
                  uint32_t *d_labels, uint32_t *h_labels, uint64_t *n_reps)
@@ -45,52 +38,27 @@ int extend_bands(dsh_ctx *c, int estim, int result_type, int k, float t, int bes
     // phase 1: old representatives x new columns
     if (m && m < n) {
         const uint64_t ncols = n - m;
-        const uint64_t nchunks64 = (ncols + kThrChunk - 1) / kThrChunk;
-        if ((nchunks64 + 3) / 4 > 65535) return fail(c, DSH_EINVAL, "rows of %llu values are not supported", (unsigned long long)ncols);
         uint64_t b0 = 0, b1 = 0;
         for (uint64_t from = 0; plan::greedy_old_band(labels_in, m, ncols, from, band_floats, b0, b1); from = b1) {
             ThrRows g;
-            g.rect = 1;
-            g.n = n;
-            g.row0 = b0;
-            g.ncols = ncols;
-            g.col0 = m;
-            g.rows = b1 - b0;
-            g.nchunks = (uint32_t)nchunks64;
-            HIPCHK(c, c->thr_vals.ensure(g.rows * ncols * sizeof(float)));
-            const int rc = run_pairs(c, PairJob::rectangle(estim, result_type, k, b0, b1, m, n, c->thr_vals.ptr));
-            if (rc) return rc;
+            int rc = thr_geometry(c, 1, n, b0, b1, ncols, m, g);
+            if (rc || (rc = compute_band(c, estim, result_type, k, g, g.rows * ncols))) return rc;
             const hipError_t e = launch_greedy_rect(c->stream, (const float *)c->thr_vals.ptr, g, t, descending, assign, best);
             if (e != hipSuccess) return fail(c, DSH_EIO, "k_greedy_rect: %s", hipGetErrorString(e));
         }
     }
     // phase 2: the new rows among themselves (a column an old representative covered is simply "not itself")
-    for (uint64_t b0 = m; b0 + 1 < n;) {  // (the last row has no values)
-        const uint64_t b1 = plan::greedy_band_end(n, b0, band_floats, c->greedy_band_rows);
-        const uint64_t span = dsh_tri_span(n, b0, b1), longest = n - 1 - b0;
-        const uint64_t nchunks64 = std::max<uint64_t>((longest + kThrChunk - 1) / kThrChunk, 1);
-        if ((nchunks64 + 3) / 4 > 65535) return fail(c, DSH_EINVAL, "rows of %llu values are not supported", (unsigned long long)longest);
-        ThrRows g;
-        g.rect = 0;
-        g.n = n;
-        g.row0 = b0;
-        g.ncols = 0;
-        g.col0 = 0;
-        g.rows = b1 - b0;
-        g.nchunks = (uint32_t)nchunks64;
-        HIPCHK(c, c->thr_vals.ensure(std::max<uint64_t>(span, 1) * sizeof(float)));
-        if (span) {
-            const int rc = run_pairs(c, PairJob::triangle(estim, result_type, k, b0, b1, dsh_tri_span(n, 0, b0), c->thr_vals.ptr));
-            if (rc) return rc;
-            const float *vals = (const float *)c->thr_vals.ptr;
-            hipError_t e = launch_greedy_diag(c->stream, vals, g, t, descending, assign);
-            if (e == hipSuccess)
-                e = best ? launch_greedy_best(c->stream, vals, g, t, descending, assign, best, m)
-                         : launch_greedy_band(c->stream, vals, g, t, descending, assign);
-            if (e != hipSuccess) return fail(c, DSH_EIO, "k_greedy_diag/k_greedy_band/k_greedy_best: %s", hipGetErrorString(e));
-        }
-        b0 = b1;
-    }
+    BandQuery bq;
+    bq.estim = estim, bq.result_type = result_type, bq.k = k;
+    bq.rb = m, bq.re = n;
+    bq.row_cap = c->greedy_band_rows;
+    const int rc = for_each_band(c, bq, [&](const ThrRows &g, const float *vals, uint64_t) -> int {
+        hipError_t e = launch_greedy_diag(c->stream, vals, g, t, descending, assign);
+        if (e == hipSuccess)
+            e = best ? launch_greedy_best(c->stream, vals, g, t, descending, assign, best, m) : launch_greedy_band(c->stream, vals, g, t, descending, assign);
+        return e == hipSuccess ? DSH_OK : fail(c, DSH_EIO, "k_greedy_diag/k_greedy_band/k_greedy_best: %s", hipGetErrorString(e));
+    });
+    if (rc) return rc;
     HIPCHK(c, launch_greedy_extend_labels(c->stream, assign, best, m, n, d_labels, d_reps));
     uint64_t reps = 0;
     HIPCHK(c, hipMemcpyAsync(&reps, d_reps, sizeof reps, hipMemcpyDeviceToHost, c->stream));
@@ -121,7 +89,7 @@ int run_greedy_extend(dsh_ctx *c, int estim, int result_type, int k, float t, in
     if (n_reps) *n_reps = 0;
     if (!n) return DSH_OK;
     if ((rc = extend_bands(c, estim, result_type, k, t, assign_mode == DSH_GREEDY_BEST, m, labels_in, d_labels, h_labels, n_reps)))
-        return extend_abort(c, rc);
+        return drain(c, rc);
     return DSH_OK;
 }
 

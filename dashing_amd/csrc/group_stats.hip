@@ -1,7 +1,7 @@
 // group_stats.hip -- dsh_group_stats*: per-group statistics and medoids of a labelling.  Two routes to the
 // same integer accumulators (kernels_group.hip), so to the same bytes:
-//   dense   the band loop of run_cluster_threshold (cluster.hip) unchanged -- the same band rule, PairJob::triangle +
-//           run_pairs into thr_vals -- with k_gs_rows and k_gs_cols in the place of k_cc_band;
+//   dense   the band walk of bands.h -- the band rule and the band buffer of dsh_dist_threshold* -- with k_gs_rows and
+//           k_gs_cols per band;
 //   pairs   the intra-group pairs enumerated on the device chunk by chunk from the member CSR (k_gs_enum, lhs = the larger
 //           slot: the triangle's bits) and computed by the direct pair path of pairs.hip (pairs_ensure_cards +
 //           pairs_run_chunk), each chunk folded into both ends by k_gs_pairs.  Nothing of the size of P_in exists at once.
@@ -9,7 +9,7 @@
 #include <algorithm>
 #include <vector>
 
-#include "ctx.h"
+#include "bands.h"
 
 using namespace dsh;
 
@@ -25,48 +25,17 @@ struct GsOut {  // device pointers; a null one is not written
     float *worst;
 };
 
-int gs_abort(dsh_ctx *c, int rc)
-{
-    (void)hipStreamSynchronize(c->stream);
-    (void)hipGetLastError();
-    return rc;
-}
-
 int gs_dense(dsh_ctx *c, int estim, int result_type, int k, const uint32_t *d_labels, const GsAccum &acc)
 {
-    const uint64_t n = c->n;
     const int descending = measure_descending(result_type) ? 1 : 0;
-    const uint64_t band_floats = std::max<uint64_t>(c->threshold_band_bytes / sizeof(float), 1);
-    for (uint64_t b0 = 0; b0 + 1 < n;) {  // (the last row has no values)
-        // a band: whole rows, at most band_floats values (one row at least), at most 2^20 rows (run_threshold's rule)
-        uint64_t b1 = b0, span = 0;
-        const uint64_t longest = n - 1 - b0;
-        do {
-            span += n - 1 - b1;
-            ++b1;
-        } while (b1 < n && b1 - b0 < (1u << 20) && span + (n - 1 - b1) <= band_floats);
-        const uint64_t nchunks64 = std::max<uint64_t>((longest + kThrChunk - 1) / kThrChunk, 1);
-        if ((nchunks64 + 3) / 4 > 65535) return fail(c, DSH_EINVAL, "rows of %llu values are not supported", (unsigned long long)longest);
-        ThrRows g;
-        g.rect = 0;
-        g.n = n;
-        g.row0 = b0;
-        g.ncols = 0;
-        g.col0 = 0;
-        g.rows = b1 - b0;
-        g.nchunks = (uint32_t)nchunks64;
-        HIPCHK(c, c->thr_vals.ensure(std::max<uint64_t>(span, 1) * sizeof(float)));
-        if (span) {
-            const int rc = run_pairs(c, PairJob::triangle(estim, result_type, k, b0, b1, dsh_tri_span(n, 0, b0), c->thr_vals.ptr));
-            if (rc) return rc;
-            const float *vals = (const float *)c->thr_vals.ptr;
-            hipError_t e = launch_gs_rows(c->stream, vals, g, d_labels, descending, acc);
-            if (e == hipSuccess) e = launch_gs_cols(c->stream, vals, g, d_labels, descending, acc);
-            if (e != hipSuccess) return fail(c, DSH_EIO, "k_gs_rows/k_gs_cols: %s", hipGetErrorString(e));
-        }
-        b0 = b1;
-    }
-    return DSH_OK;
+    BandQuery bq;
+    bq.estim = estim, bq.result_type = result_type, bq.k = k;
+    bq.re = c->n;
+    return for_each_band(c, bq, [&](const ThrRows &g, const float *vals, uint64_t) -> int {
+        hipError_t e = launch_gs_rows(c->stream, vals, g, d_labels, descending, acc);
+        if (e == hipSuccess) e = launch_gs_cols(c->stream, vals, g, d_labels, descending, acc);
+        return e == hipSuccess ? DSH_OK : fail(c, DSH_EIO, "k_gs_rows/k_gs_cols: %s", hipGetErrorString(e));
+    });
 }
 
 // the groups of at least two members, in label order, their members in slot order (a counting sort)
@@ -176,22 +145,22 @@ int run_group_stats(dsh_ctx *c, int estim, int result_type, int k, const uint32_
     HIPCHK(c, hipMemsetAsync(c->gs_acc.ptr, 0, n * 16, c->stream));
     HIPCHK(c, hipMemsetAsync(c->gs_grp.ptr, 0, n * 12, c->stream));
     HIPCHK(c, hipMemsetAsync(g_slot, 0xFF, n * sizeof(uint32_t), c->stream));
-    if (route == 1 && p_in && (rc = pairs_err_begin(c))) return gs_abort(c, rc);
+    if (route == 1 && p_in && (rc = pairs_err_begin(c))) return drain(c, rc);
     rc = route == 1 ? gs_pairs(c, estim, result_type, k, p_in, csr, acc) : gs_dense(c, estim, result_type, k, d_labels, acc);
-    if (rc) return gs_abort(c, rc);
+    if (rc) return drain(c, rc);
     const int descending = measure_descending(result_type) ? 1 : 0;
     const hipError_t e = launch_gs_finish(c->stream, d_labels, n, descending, acc, g_cnt, g_sum, g_slot, o.medoid, o.cnt, o.sum, o.worst);
-    if (e != hipSuccess) return gs_abort(c, fail(c, DSH_EIO, "k_gs_medoid/k_gs_finish: %s", hipGetErrorString(e)));
+    if (e != hipSuccess) return drain(c, fail(c, DSH_EIO, "k_gs_medoid/k_gs_finish: %s", hipGetErrorString(e)));
     if (!device) {
         hipError_t h = hipSuccess;
         if (medoid_out) h = hipMemcpyAsync(medoid_out, o.medoid, n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream);
         if (h == hipSuccess && cnt_out) h = hipMemcpyAsync(cnt_out, o.cnt, n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream);
         if (h == hipSuccess && sum_out) h = hipMemcpyAsync(sum_out, o.sum, n * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream);
         if (h == hipSuccess && worst_out) h = hipMemcpyAsync(worst_out, o.worst, n * sizeof(float), hipMemcpyDeviceToHost, c->stream);
-        if (h != hipSuccess) return gs_abort(c, fail(c, DSH_EIO, "copy of the statistics failed: %s", hipGetErrorString(h)));
+        if (h != hipSuccess) return drain(c, fail(c, DSH_EIO, "copy of the statistics failed: %s", hipGetErrorString(h)));
     }
     if (route == 1 && p_in) {  // the one wait, with the pair path's error words
-        if ((rc = pairs_err_end(c))) return gs_abort(c, rc);
+        if ((rc = pairs_err_end(c))) return drain(c, rc);
         return DSH_OK;
     }
     HIPCHK(c, hipStreamSynchronize(c->stream));

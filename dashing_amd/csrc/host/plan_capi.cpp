@@ -2,7 +2,7 @@
 // per-sketch keys exactly as engine.hip does and checks the plan against its contract, so the schedule that replaces
 // dist_loop / perform_core_op (src/sketch_and_cmp.h:785-880, :699-710) is unit-tested without a GPU
 // (tests/test_plan.py).  Also the sequential build of the clusters' union-find (dsh_plan_uf_labels, at the end) and the band rule of
-// the greedy representatives (dshh_greedy_bands).  Built into
+// the greedy representatives (dshh_greedy_bands) and the band walk all five band consumers share (dshh_threshold_bands).  Built into
 // libdashing_host.so; not part of the GPU C-ABI.
 #include <algorithm>
 #include <cstdarg>
@@ -398,16 +398,34 @@ int dshh_plan_check_rowset(uint64_t n, const uint32_t *keys, const uint64_t *tab
 // first row of the second run of a row-sorted range (plan::rowsorted_split), re when the range stays one run
 uint64_t dshh_rowsorted_split(uint64_t n, uint64_t rb, uint64_t re) { return rowsorted_split(n, rb, re); }
 
-// the bands of dsh_greedy_threshold* (plan::greedy_band_end, the loop of greedy.hip): bounds[0] = 0, bounds[q + 1] = the end
-// of band q, for the triangle of n sketches.  Returns the number of bands (0 for n < 2), or -1 when they do not fit cap
-// boundaries (tests/test_greedy_plan.py).
+// the band walk of bands.h (plan::tri_band_end, plan::rect_band_rows) over the rows [rb, re): of the triangle of n sketches
+// (ncols == 0; re is cut to n), or of a rectangle of ncols > 0 columns.  bounds[0] = rb, bounds[q + 1] = the end of band q.
+// Returns the number of bands (0 for an empty range), or -1 when they do not fit cap boundaries (tests/test_band_plan.py).
+int64_t dshh_threshold_bands(uint64_t n, uint64_t rb, uint64_t re, uint64_t ncols, uint64_t band_bytes, uint64_t row_cap,
+                             uint64_t *bounds, uint64_t cap)
+{
+    const uint64_t band_floats = std::max<uint64_t>(band_bytes / sizeof(float), 1);
+    if (!ncols && re > n) re = n;
+    uint64_t nb = 0;
+    if (cap) bounds[0] = rb;
+    for (uint64_t b0 = rb; b0 < re;) {
+        b0 = ncols ? std::min<uint64_t>(re, b0 + rect_band_rows(ncols, band_floats)) : tri_band_end(n, b0, re, band_floats, row_cap);
+        if (++nb >= cap) return -1;
+        bounds[nb] = b0;
+    }
+    return (int64_t)nb;
+}
+
+// the bands of dsh_greedy_threshold* (the loop of greedy.hip: plan::tri_band_end up to row n, the empty last row left out):
+// bounds[0] = 0, bounds[q + 1] = the end of band q, for the triangle of n sketches.  Returns the number of bands (0 for
+// n < 2), or -1 when they do not fit cap boundaries (tests/test_greedy_plan.py).
 int64_t dshh_greedy_bands(uint64_t n, uint64_t band_bytes, uint64_t row_cap, uint64_t *bounds, uint64_t cap)
 {
     const uint64_t band_floats = std::max<uint64_t>(band_bytes / sizeof(float), 1);
     uint64_t nb = 0;
     if (cap) bounds[0] = 0;
     for (uint64_t b0 = 0; b0 + 1 < n;) {
-        b0 = greedy_band_end(n, b0, band_floats, row_cap);
+        b0 = tri_band_end(n, b0, n, band_floats, row_cap);
         if (++nb >= cap) return -1;
         bounds[nb] = b0;
     }

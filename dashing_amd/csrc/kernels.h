@@ -172,8 +172,7 @@ hipError_t launch_topk_merge(hipStream_t st, const float *vals, uint64_t ld, int
 
 // thresholded output (kernels_threshold.hip, threshold.hip): the rows of a band buffer -- rows [row0, row0 + rows) of the
 // packed triangle of n sketches back to back (row i: n - 1 - i values, columns i + 1 ...), or rows x ncols of a rectangle
-// (columns col0 ...) -- each cut into nchunks chunks of kThrChunk values (nchunks covers the longest row)
-constexpr uint32_t kThrChunk = 4096;
+// (columns col0 ...) -- each cut into nchunks chunks of kThrChunk values (consts.h; nchunks covers the longest row)
 struct ThrRows {
     int rect;
     uint64_t n, row0;      // triangle
@@ -181,6 +180,8 @@ struct ThrRows {
     uint64_t rows;
     uint32_t nchunks;
 };
+// the grid of the kernels that walk it (thr_walk.h): block (r, y) holds the chunks 4 y .. 4 y + 3 of band row r
+inline dim3 thr_grid(const ThrRows &g) { return dim3((uint32_t)g.rows, (g.nchunks + 3) / 4); }
 // cnt[rows * nchunks]: hits per chunk (similarity measures pass with v >= t, distances with v <= t; NaN never)
 hipError_t launch_thr_count(hipStream_t st, const float *vals, const ThrRows &g, float t, int descending, uint32_t *cnt);
 // off[m + 1] = *total + exclusive scan of cnt[m] (m = rows * nchunks), row_ptr[r] = off[r * nchunks], *total = off[m]

@@ -16,9 +16,9 @@
 //   k_cc_seed    unite(x, labels_in[x]): an earlier labelling to continue from
 //   k_cc_edges   unite(lhs[e], rhs[e]), grid-stride; self loops and repeated edges are legal
 //   k_cc_csr     unite(row_begin + r, col[h]) for the hits of a CSR; the row of a hit by binary search in row_ptr
-//   k_cc_band    the hot one: a band of dense values walked exactly as k_thr_count walks it (kernels_threshold.hip:
-//                ThrRows, one wave per 4096-value chunk of a row, one aligned float4 per lane per step, ragged edges value
-//                by value); a passing value at column j unites j with the chunk's row.  No count, scan or emit pass, and
+//   k_cc_band    the hot one: a band of dense values walked as thr_walk.h lays down (ThrRows, one wave per 4096-value
+//                chunk of a row, one aligned float4 per lane per step, ragged edges value by value, as k_thr_count
+//                does); a passing value at column j unites j with the chunk's row.  No count, scan or emit pass, and
 //                no hit is written
 //   k_cc_labels  a launch of its own, so that all hooks are visible: labels[x] = find(x); roots counted with __ballot +
 //                popcount and one atomicAdd per wave
@@ -27,6 +27,7 @@
 #include <algorithm>
 
 #include "kernels.h"
+#include "thr_walk.h"
 #include "uf.h"
 
 namespace dsh {
@@ -91,11 +92,7 @@ __global__ __launch_bounds__(256) void k_cc_csr(uint32_t *parent, const unsigned
     }
 }
 
-constexpr uint32_t kStep = 256;  // values a wave takes per step: one float4 per lane (kernels_threshold.hip)
-
-__device__ __forceinline__ bool thr_pass(float v, float t, int descending) { return descending ? v >= t : v <= t; }  // NaN: neither
-
-// The geometry of k_thr_count, triangle rows only: block (r, y) holds four waves, wave w the chunk 4 y + w of band row r.
+// The walk of thr_walk.h, triangle rows only (thr_tri_row: launch_cc_band takes no rectangle).
 __global__ __launch_bounds__(256) void k_cc_band(const float *__restrict__ vals, ThrRows g, float t, int descending, uint32_t *parent,
                                                  uint32_t cap, uint32_t *err)
 {
@@ -104,13 +101,9 @@ __global__ __launch_bounds__(256) void k_cc_band(const float *__restrict__ vals,
     const uint32_t ch = blockIdx.y * 4 + wave;
     if (ch >= g.nchunks) return;
     const uint64_t i = g.row0 + r;
-    const uint64_t first = g.n - 1 - g.row0;  // values of the band's first row (row0 < n)
-    const uint64_t len = g.n - 1 - i;
-    const uint64_t rowoff = r * first - r * (r - 1) / 2;  // (thr_row of kernels_threshold.hip)
-    const uint32_t colbase = (uint32_t)(i + 1);
-    const uint64_t cb = (uint64_t)ch * kThrChunk;
-    if (cb >= len) return;
-    const uint64_t begin = rowoff + cb, end = rowoff + (len - cb < kThrChunk ? len : cb + kThrChunk);
+    const ThrRow row = thr_tri_row(g, r);
+    uint64_t begin, end;
+    if (!thr_chunk(row, ch, begin, end)) return;
     // the row is the same for the whole chunk: its root is kept (every lane its own copy: any member of i's set that was
     // a root when read serves) and refreshed after a hook
     uint32_t root_i = uf_find<UfDevice>(parent, (uint32_t)i, cap);
@@ -118,23 +111,13 @@ __global__ __launch_bounds__(256) void k_cc_band(const float *__restrict__ vals,
         __hip_atomic_store(err, kUfErrFind, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         return;
     }
-    for (uint64_t idx = (begin & ~(uint64_t)3) + 4 * lane; idx < end; idx += kStep) {
+    for (uint64_t idx = thr_first(begin, lane); idx < end; idx += kThrStep) {
         float v[4];
-        uint32_t m = 0;
-        if (idx >= begin && idx + 4 <= end) {
-            const float4 q = *reinterpret_cast<const float4 *>(vals + idx);
-            v[0] = q.x, v[1] = q.y, v[2] = q.z, v[3] = q.w;
-#pragma unroll
-            for (int c = 0; c < 4; ++c) m |= (thr_pass(v[c], t, descending) ? 1u : 0u) << c;
-        } else {
-#pragma unroll
-            for (int c = 0; c < 4; ++c)
-                if (idx + c >= begin && idx + c < end) m |= (thr_pass(vals[idx + c], t, descending) ? 1u : 0u) << c;
-        }
+        const uint32_t m = thr_flags(vals, idx, begin, end, t, descending, v);
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
             if (!((m >> c) & 1u)) continue;
-            const uint32_t j = colbase + (uint32_t)(idx + c - rowoff);
+            const uint32_t j = row.colbase + (uint32_t)(idx + c - row.rowoff);
             const uint32_t rj = uf_find<UfDevice>(parent, j, cap);
             if (rj == root_i) continue;  // the common case at loose thresholds: nothing to write
             if (rj == kUfOverrun) {
@@ -209,7 +192,7 @@ hipError_t launch_cc_band(hipStream_t st, const float *vals, const ThrRows &g, f
                           uint32_t *err)
 {
     if (g.rows == 0 || g.rect) return hipSuccess;
-    hipLaunchKernelGGL(k_cc_band, dim3((uint32_t)g.rows, (g.nchunks + 3) / 4), dim3(256), 0, st, vals, g, t, descending, parent, cap, err);
+    hipLaunchKernelGGL(k_cc_band, thr_grid(g), dim3(256), 0, st, vals, g, t, descending, parent, cap, err);
     return hipGetLastError();
 }
 

@@ -12,8 +12,8 @@
 //                    atomics.  A covered row costs a read of LDS and no barrier; a representative row one barrier (and
 //                    every batch of 16 rows two).  The loop visits every row once.  The entries go back to assign at the
 //                    end.
-//   k_greedy_band    the geometry of k_cc_band (kernels_cluster.hip: ThrRows, one wave per 4096-value chunk of a row, one
-//                    aligned float4 per lane per step, ragged edges value by value).  Now assign[b0..b1) is final: a wave
+//   k_greedy_band    the walk of thr_walk.h (ThrRows, one wave per 4096-value chunk of a row, one aligned float4 per lane
+//                    per step, ragged edges value by value).  Now assign[b0..b1) is final: a wave
 //                    whose row is covered returns at once, a representative's wave lowers assign[j] to i for every passing
 //                    column j >= b1 (the in-band columns belong to k_greedy_diag and are skipped, whole chunks of them
 //                    without a load).  atomicMin commutes: the result is the smallest representative whatever the order.
@@ -42,18 +42,16 @@
 #include <algorithm>
 
 #include "kernels.h"
+#include "thr_walk.h"
 #include "vkey.h"
 
 namespace dsh {
 
 namespace {
 
-constexpr uint32_t kStep = 256;  // values a wave takes per step: one float4 per lane (kernels_threshold.hip)
 constexpr uint32_t kDiagThreads = 1024;
 constexpr uint32_t kDiagCols = kGreedyMaxRows / kDiagThreads;  // band columns a thread of k_greedy_diag owns
 constexpr uint32_t kDiagBatch = 16;                            // rows whose values it loads at once
-
-__device__ __forceinline__ bool thr_pass(float v, float t, int descending) { return descending ? v >= t : v <= t; }  // NaN: neither
 
 __device__ __forceinline__ uint32_t ld_assign(const uint32_t *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
@@ -79,7 +77,7 @@ __global__ __launch_bounds__(kDiagThreads) void k_greedy_diag(const float *__res
         __syncthreads();  // nobody writes before everybody has read
         if (!live) continue;
         uint32_t bits[kDiagCols];
-        const uint64_t rowoff0 = (uint64_t)r0 * first - (uint64_t)r0 * (r0 - 1) / 2;  // (thr_row of kernels_threshold.hip)
+        const uint64_t rowoff0 = band_rowoff(first, r0);
 #pragma unroll
         for (uint32_t v = 0; v < kDiagCols; ++v) {
             bits[v] = 0;
@@ -116,7 +114,7 @@ __global__ __launch_bounds__(kDiagThreads) void k_greedy_diag(const float *__res
     for (uint32_t r = threadIdx.x; r < rows; r += kDiagThreads) assign[g.row0 + r] = cur[r];
 }
 
-// block (r, y) holds four waves, wave w the chunk 4 y + w of band row r (k_cc_band)
+// the walk of thr_walk.h, triangle rows only (thr_tri_row: launch_greedy_band takes no rectangle)
 __global__ __launch_bounds__(256) void k_greedy_band(const float *__restrict__ vals, ThrRows g, float t, int descending, uint32_t *assign)
 {
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
@@ -124,31 +122,19 @@ __global__ __launch_bounds__(256) void k_greedy_band(const float *__restrict__ v
     const uint32_t ch = blockIdx.y * 4 + wave;
     if (ch >= g.nchunks) return;
     const uint64_t i = g.row0 + r;
-    const uint64_t first = g.n - 1 - g.row0;
-    const uint64_t len = g.n - 1 - i;
-    const uint64_t inband = g.rows - 1 - r;  // the row's first values: columns inside the band (inband <= len)
-    const uint64_t cb = (uint64_t)ch * kThrChunk;
-    const uint64_t ce = len - cb < kThrChunk ? len : cb + kThrChunk;  // (read only where cb < len)
-    if (cb >= len || ce <= inband) return;  // past the row, or wholly inside the band's own columns
+    const ThrRow row = thr_tri_row(g, r);
+    const uint64_t inband = row.rowoff + (g.rows - 1 - r);  // behind the row's first values: the columns inside the band
+    uint64_t begin, end;
+    if (!thr_chunk(row, ch, begin, end) || end <= inband) return;  // past the row, or wholly inside the band's own columns
     if (ld_assign(assign + i) != (uint32_t)i) return;  // covered: the row has nothing to say
-    const uint64_t rowoff = r * first - r * (r - 1) / 2;
-    const uint32_t colbase = (uint32_t)(i + 1);
-    const uint64_t begin = rowoff + (cb > inband ? cb : inband), end = rowoff + ce;
-    for (uint64_t idx = (begin & ~(uint64_t)3) + 4 * lane; idx < end; idx += kStep) {
-        uint32_t m = 0;
-        if (idx >= begin && idx + 4 <= end) {
-            const float4 q = *reinterpret_cast<const float4 *>(vals + idx);
-            m = (thr_pass(q.x, t, descending) ? 1u : 0u) | (thr_pass(q.y, t, descending) ? 2u : 0u) |
-                (thr_pass(q.z, t, descending) ? 4u : 0u) | (thr_pass(q.w, t, descending) ? 8u : 0u);
-        } else {
-#pragma unroll
-            for (int c = 0; c < 4; ++c)
-                if (idx + c >= begin && idx + c < end) m |= (thr_pass(vals[idx + c], t, descending) ? 1u : 0u) << c;
-        }
+    if (begin < inband) begin = inband;
+    for (uint64_t idx = thr_first(begin, lane); idx < end; idx += kThrStep) {
+        float v[4];
+        const uint32_t m = thr_flags(vals, idx, begin, end, t, descending, v);
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
             if (!((m >> c) & 1u)) continue;
-            uint32_t *a = assign + (colbase + (uint32_t)(idx + c - rowoff));
+            uint32_t *a = assign + (row.colbase + (uint32_t)(idx + c - row.rowoff));
             if (ld_assign(a) > (uint32_t)i) (void)atomicMin(a, (uint32_t)i);
         }
     }
@@ -182,32 +168,18 @@ __device__ __forceinline__ unsigned long long best_key(float v, int descending, 
     return ((unsigned long long)value_key32(v, descending) << 32) | (unsigned long long)(0xFFFFFFFFu - r);
 }
 
-// One wave, one chunk [begin, end) of the values of representative row i (row starts at rowoff, its first value belongs to
-// column colbase): a passing column j is lowered in assign if j >= min_from, and raised in best (if there is one).
-__device__ __forceinline__ void greedy_walk(const float *__restrict__ vals, uint64_t rowoff, uint64_t begin, uint64_t end, uint32_t colbase,
-                                            uint32_t i, uint32_t lane, float t, int descending, uint32_t *assign, uint32_t min_from,
-                                            unsigned long long *best, uint32_t m)
+// One wave, one chunk [begin, end) of the values of representative row i: a passing column j is lowered in assign if
+// j >= min_from, and raised in best (if there is one).
+__device__ __forceinline__ void greedy_walk(const float *__restrict__ vals, const ThrRow row, uint64_t begin, uint64_t end, uint32_t i, uint32_t lane,
+                                            float t, int descending, uint32_t *assign, uint32_t min_from, unsigned long long *best, uint32_t m)
 {
-    for (uint64_t idx = (begin & ~(uint64_t)3) + 4 * lane; idx < end; idx += kStep) {
-        float v[4] = {0.f, 0.f, 0.f, 0.f};
-        uint32_t hit = 0;
-        if (idx >= begin && idx + 4 <= end) {
-            const float4 q = *reinterpret_cast<const float4 *>(vals + idx);
-            v[0] = q.x, v[1] = q.y, v[2] = q.z, v[3] = q.w;
-#pragma unroll
-            for (int c = 0; c < 4; ++c) hit |= (thr_pass(v[c], t, descending) ? 1u : 0u) << c;
-        } else {
-#pragma unroll
-            for (int c = 0; c < 4; ++c)
-                if (idx + c >= begin && idx + c < end) {
-                    v[c] = vals[idx + c];
-                    hit |= (thr_pass(v[c], t, descending) ? 1u : 0u) << c;
-                }
-        }
+    for (uint64_t idx = thr_first(begin, lane); idx < end; idx += kThrStep) {
+        float v[4];
+        const uint32_t hit = thr_flags(vals, idx, begin, end, t, descending, v);
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
             if (!((hit >> c) & 1u)) continue;
-            const uint32_t j = colbase + (uint32_t)(idx + c - rowoff);
+            const uint32_t j = row.colbase + (uint32_t)(idx + c - row.rowoff);
             if (j >= min_from) {
                 uint32_t *a = assign + j;
                 if (ld_assign(a) > i) (void)atomicMin(a, i);
@@ -229,17 +201,16 @@ __global__ __launch_bounds__(256) void k_greedy_rect(const float *__restrict__ v
     const uint64_t r = blockIdx.x;
     const uint32_t ch = blockIdx.y * 4 + wave;
     if (ch >= g.nchunks) return;
-    const uint64_t cb = (uint64_t)ch * kThrChunk;
-    if (cb >= g.ncols) return;
+    const ThrRow row = thr_rect_row(g, r);
+    uint64_t begin, end;
+    if (!thr_chunk(row, ch, begin, end)) return;
     const uint64_t i = g.row0 + r;
     if (ld_assign(assign + i) != (uint32_t)i) return;  // not a representative: the row has nothing to say
-    const uint64_t ce = g.ncols - cb < kThrChunk ? g.ncols : cb + kThrChunk;
-    const uint64_t rowoff = r * g.ncols;
-    greedy_walk(vals, rowoff, rowoff + cb, rowoff + ce, (uint32_t)g.col0, (uint32_t)i, lane, t, descending, assign, 0u, best,
-                (uint32_t)g.col0);
+    greedy_walk(vals, row, begin, end, (uint32_t)i, lane, t, descending, assign, 0u, best, (uint32_t)g.col0);
 }
 
-// a band of triangle rows as k_greedy_band takes it, after k_greedy_diag; m <= g.row0
+// a band of triangle rows as k_greedy_band takes it (thr_tri_row: launch_greedy_best takes no rectangle), after k_greedy_diag;
+// m <= g.row0
 __global__ __launch_bounds__(256) void k_greedy_best(const float *__restrict__ vals, ThrRows g, float t, int descending, uint32_t *assign,
                                                      unsigned long long *best, uint32_t m)
 {
@@ -248,15 +219,12 @@ __global__ __launch_bounds__(256) void k_greedy_best(const float *__restrict__ v
     const uint32_t ch = blockIdx.y * 4 + wave;
     if (ch >= g.nchunks) return;
     const uint64_t i = g.row0 + r;
-    const uint64_t first = g.n - 1 - g.row0;
-    const uint64_t len = g.n - 1 - i;
-    const uint64_t cb = (uint64_t)ch * kThrChunk;
-    if (cb >= len) return;
+    if (!thr_chunk_inside(g.n - 1 - i, ch)) return;  // past the row
     if (ld_assign(assign + i) != (uint32_t)i) return;  // covered
-    const uint64_t ce = len - cb < kThrChunk ? len : cb + kThrChunk;
-    const uint64_t rowoff = r * first - r * (r - 1) / 2;
-    greedy_walk(vals, rowoff, rowoff + cb, rowoff + ce, (uint32_t)(i + 1), (uint32_t)i, lane, t, descending, assign,
-                (uint32_t)(g.row0 + g.rows), best, m);
+    const ThrRow row = thr_tri_row(g, r);  // (behind the load, as the kernel was written: its register count depends on it)
+    uint64_t begin, end;
+    (void)thr_chunk(row, ch, begin, end);
+    greedy_walk(vals, row, begin, end, (uint32_t)i, lane, t, descending, assign, (uint32_t)(g.row0 + g.rows), best, m);
 }
 
 __global__ __launch_bounds__(256) void k_greedy_extend_labels(const uint32_t *__restrict__ assign, const unsigned long long *__restrict__ best,
@@ -290,7 +258,7 @@ hipError_t launch_greedy_diag(hipStream_t st, const float *vals, const ThrRows &
 hipError_t launch_greedy_band(hipStream_t st, const float *vals, const ThrRows &g, float t, int descending, uint32_t *assign)
 {
     if (g.rows == 0 || g.rect) return hipSuccess;
-    hipLaunchKernelGGL(k_greedy_band, dim3((uint32_t)g.rows, (g.nchunks + 3) / 4), dim3(256), 0, st, vals, g, t, descending, assign);
+    hipLaunchKernelGGL(k_greedy_band, thr_grid(g), dim3(256), 0, st, vals, g, t, descending, assign);
     return hipGetLastError();
 }
 
@@ -306,7 +274,7 @@ hipError_t launch_greedy_rect(hipStream_t st, const float *vals, const ThrRows &
 {
     if (g.rows == 0 || g.ncols == 0) return hipSuccess;
     if (!g.rect) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_greedy_rect, dim3((uint32_t)g.rows, (g.nchunks + 3) / 4), dim3(256), 0, st, vals, g, t, descending, assign,
+    hipLaunchKernelGGL(k_greedy_rect, thr_grid(g), dim3(256), 0, st, vals, g, t, descending, assign,
                        reinterpret_cast<unsigned long long *>(best));
     return hipGetLastError();
 }
@@ -316,7 +284,7 @@ hipError_t launch_greedy_best(hipStream_t st, const float *vals, const ThrRows &
 {
     if (g.rows == 0) return hipSuccess;
     if (g.rect || !best || first_new > g.row0) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_greedy_best, dim3((uint32_t)g.rows, (g.nchunks + 3) / 4), dim3(256), 0, st, vals, g, t, descending, assign,
+    hipLaunchKernelGGL(k_greedy_best, thr_grid(g), dim3(256), 0, st, vals, g, t, descending, assign,
                        reinterpret_cast<unsigned long long *>(best), (uint32_t)first_new);
     return hipGetLastError();
 }

@@ -6,7 +6,7 @@
 //   sum[x]   64-bit add   sum of q(v) = llrint(v * 2^30) over them (|q| < 2^31, at most 2^32 - 2 terms: inside int64)
 //   wkey[x]  uint32 max   ~value_key32(v) (vkey.h) of the WORST included value: 0 = none, a larger key is a worse value
 // The number of atomics does not grow with the number of matching pairs:
-//   k_gs_rows    a band of dense values walked as k_cc_band walks it (ThrRows, one wave per 4096-value chunk of a row, one
+//   k_gs_rows    a band of dense values walked as thr_walk.h lays down (ThrRows, one wave per 4096-value chunk of a row, one
 //                aligned float4 per lane per step, ragged edges value by value).  A lane loads the labels of its four columns
 //                next to the values and accumulates row i's (cnt, sum, wkey) over the columns with labels[i]; the wave
 //                reduces across lanes; at most ONE set of atomics per wave, none for a chunk without a matching column
@@ -26,13 +26,13 @@
 #include <algorithm>
 
 #include "kernels.h"
+#include "thr_walk.h"
 #include "vkey.h"
 
 namespace dsh {
 
 namespace {
 
-constexpr uint32_t kStep = 256;    // values a wave takes per step: one float4 per lane (kernels_threshold.hip)
 constexpr uint32_t kGsSlab = 512;  // band rows a thread of k_gs_cols walks
 
 struct GsAcc {
@@ -64,7 +64,7 @@ struct GsAcc {
     }
 };
 
-// The geometry of k_cc_band: block (r, y) holds four waves, wave w the chunk 4 y + w of band row r.
+// The walk of thr_walk.h, triangle rows only (thr_tri_row: launch_gs_rows takes no rectangle).
 __global__ __launch_bounds__(256) void k_gs_rows(const float *__restrict__ vals, ThrRows g, const uint32_t *__restrict__ labels,
                                                  int descending, uint32_t *cnt, unsigned long long *sum, uint32_t *wkey)
 {
@@ -73,22 +73,20 @@ __global__ __launch_bounds__(256) void k_gs_rows(const float *__restrict__ vals,
     const uint32_t ch = blockIdx.y * 4 + wave;
     if (ch >= g.nchunks) return;
     const uint64_t i = g.row0 + r;
-    const uint64_t first = g.n - 1 - g.row0;  // values of the band's first row (row0 < n)
-    const uint64_t len = g.n - 1 - i;
-    const uint64_t rowoff = r * first - r * (r - 1) / 2;  // (thr_row of kernels_threshold.hip)
-    const uint32_t colbase = (uint32_t)(i + 1);
-    const uint64_t cb = (uint64_t)ch * kThrChunk;
-    if (cb >= len) return;
-    const uint64_t begin = rowoff + cb, end = rowoff + (len - cb < kThrChunk ? len : cb + kThrChunk);
+    const ThrRow row = thr_tri_row(g, r);
+    uint64_t begin, end;
+    if (!thr_chunk(row, ch, begin, end)) return;
     const uint32_t li = labels[i];
     GsAcc a;
-    for (uint64_t idx = (begin & ~(uint64_t)3) + 4 * lane; idx < end; idx += kStep) {
+    for (uint64_t idx = thr_first(begin, lane); idx < end; idx += kThrStep) {
+        // the load of thr_flags (thr_walk.h) with the label test in the place of thr_pass, written out: as a predicate handed to a
+        // shared load the kernel came out with other register counts (36 -> 31 VGPRs, 28 -> 34 SGPRs)
         float v[4] = {0.f, 0.f, 0.f, 0.f};
         uint32_t m = 0;
         if (idx >= begin && idx + 4 <= end) {
             const float4 q = *reinterpret_cast<const float4 *>(vals + idx);
             v[0] = q.x, v[1] = q.y, v[2] = q.z, v[3] = q.w;
-            const uint32_t j = colbase + (uint32_t)(idx - rowoff);
+            const uint32_t j = row.colbase + (uint32_t)(idx - row.rowoff);
 #pragma unroll
             for (int c = 0; c < 4; ++c) m |= (labels[j + c] == li ? 1u : 0u) << c;
         } else {
@@ -96,7 +94,7 @@ __global__ __launch_bounds__(256) void k_gs_rows(const float *__restrict__ vals,
             for (int c = 0; c < 4; ++c)
                 if (idx + c >= begin && idx + c < end) {
                     v[c] = vals[idx + c];
-                    m |= (labels[colbase + (uint32_t)(idx + c - rowoff)] == li ? 1u : 0u) << c;
+                    m |= (labels[row.colbase + (uint32_t)(idx + c - row.rowoff)] == li ? 1u : 0u) << c;
                 }
         }
 #pragma unroll
@@ -124,7 +122,7 @@ __global__ __launch_bounds__(256) void k_gs_cols(const float *__restrict__ vals,
     if (j >= g.n) return;
     const uint32_t lj = labels[j];
     const uint64_t first = g.n - 1 - g.row0;
-    uint64_t off = r0 * first - r0 * (r0 - 1) / 2;  // start of band row r0, then of each next one
+    uint64_t off = band_rowoff(first, r0);  // start of band row r0, then of each next one
     const uint64_t rend = j - g.row0 < r1 ? j - g.row0 : r1;  // rows i < j only
     GsAcc a;
     for (uint64_t r = r0; r < rend; ++r) {  // at most kGsSlab steps
@@ -239,7 +237,7 @@ uint32_t gs_grid(uint64_t items)
 hipError_t launch_gs_rows(hipStream_t st, const float *vals, const ThrRows &g, const uint32_t *labels, int descending, const GsAccum &a)
 {
     if (g.rows == 0 || g.rect) return hipSuccess;
-    hipLaunchKernelGGL(k_gs_rows, dim3((uint32_t)g.rows, (g.nchunks + 3) / 4), dim3(256), 0, st, vals, g, labels, descending, a.cnt,
+    hipLaunchKernelGGL(k_gs_rows, thr_grid(g), dim3(256), 0, st, vals, g, labels, descending, a.cnt,
                        reinterpret_cast<unsigned long long *>(a.sum), a.wkey);
     return hipGetLastError();
 }

@@ -1,9 +1,8 @@
 // kernels_threshold.hip -- device-side selection of the values that pass a threshold, as CSR (threshold.hip).
 //
-// The input is what the compare path left in a band buffer: rows of float32, row r either a row of the packed triangle
-// (collection row i = row0 + r, n - 1 - i values, columns i + 1 ..., starting at ANY 4-byte offset of the buffer) or a
-// row of a rectangle (ncols values, columns col0 ...).  A row is cut into chunks of kThrChunk values; a chunk belongs to
-// ONE wave, which walks it front to back, so the order inside a row is the column order by construction:
+// The input is what the compare path left in a band buffer, walked as thr_walk.h lays down: rows of the packed triangle or
+// of a rectangle, a row cut into chunks of kThrChunk values; a chunk belongs to ONE wave, which walks it front to back, so
+// the order inside a row is the column order by construction:
 //   k_thr_count  hits per chunk                                   cnt[r * NC + ch]
 //   k_thr_scan   exclusive scan of cnt over all chunks, row-major  off[...] (absolute: the hits of earlier bands included),
 //                the band's piece of row_ptr and the running total
@@ -14,62 +13,11 @@
 #include <hip/hip_runtime.h>
 
 #include "kernels.h"
+#include "thr_walk.h"
 
 namespace dsh {
 
 namespace {
-
-constexpr uint32_t kStep = 256;  // values a wave takes per step: one float4 per lane
-
-__device__ __forceinline__ bool thr_pass(float v, float t, int descending) { return descending ? v >= t : v <= t; }  // NaN: neither
-
-struct ThrChunk {
-    uint64_t rowoff;  // first value of the row in the band buffer
-    uint64_t len;     // values of the row
-    uint32_t colbase; // column of the row's first value
-};
-
-__device__ __forceinline__ ThrChunk thr_row(const ThrRows &g, uint64_t r)
-{
-    ThrChunk c;
-    if (g.rect) {
-        c.len = g.ncols;
-        c.rowoff = r * g.ncols;
-        c.colbase = (uint32_t)g.col0;
-    } else {
-        const uint64_t i = g.row0 + r;
-        const uint64_t first = g.n - 1 - g.row0;  // values of the band's first row (row0 < n)
-        c.len = g.n - 1 - i;
-        c.rowoff = r * first - r * (r - 1) / 2;  // sum of (first - t) over t < r (r = 0: the product is 0)
-        c.colbase = (uint32_t)(i + 1);
-    }
-    return c;
-}
-
-// The four hit flags of this lane in step s of the chunk [begin, end): the lane owns the values at
-// abase + s * 256 + 4 * lane .. + 3 where abase = begin rounded DOWN to a multiple of 4, so that every full group is one
-// aligned 16-byte load (the buffer's base is 256-byte aligned); a group cut by begin or end is read value by value.
-__device__ __forceinline__ uint32_t thr_flags(const float *__restrict__ vals, uint64_t idx, uint64_t begin, uint64_t end,
-                                              float t, int descending, float v[4])
-{
-    uint32_t m = 0;
-    if (idx >= begin && idx + 4 <= end) {
-        const float4 q = *reinterpret_cast<const float4 *>(vals + idx);
-        v[0] = q.x, v[1] = q.y, v[2] = q.z, v[3] = q.w;
-#pragma unroll
-        for (int c = 0; c < 4; ++c) m |= (thr_pass(v[c], t, descending) ? 1u : 0u) << c;
-    } else {
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            v[c] = 0.f;
-            if (idx + c >= begin && idx + c < end) {
-                v[c] = vals[idx + c];
-                m |= (thr_pass(v[c], t, descending) ? 1u : 0u) << c;
-            }
-        }
-    }
-    return m;
-}
 
 __global__ __launch_bounds__(256) void k_thr_count(const float *__restrict__ vals, ThrRows g, float t, int descending,
                                                    uint32_t *__restrict__ cnt)
@@ -78,13 +26,11 @@ __global__ __launch_bounds__(256) void k_thr_count(const float *__restrict__ val
     const uint64_t r = blockIdx.x;
     const uint32_t ch = blockIdx.y * 4 + wave;
     if (ch >= g.nchunks) return;
-    const ThrChunk row = thr_row(g, r);
-    const uint64_t cb = (uint64_t)ch * kThrChunk;
+    uint64_t begin, end;
     uint32_t mine = 0;
-    if (cb < row.len) {
-        const uint64_t begin = row.rowoff + cb, end = row.rowoff + (row.len - cb < kThrChunk ? row.len : cb + kThrChunk);
+    if (thr_chunk(thr_row(g, r), ch, begin, end)) {
         float v[4];
-        for (uint64_t idx = (begin & ~(uint64_t)3) + 4 * lane; idx < end; idx += kStep)
+        for (uint64_t idx = thr_first(begin, lane); idx < end; idx += kThrStep)
             mine += __popc(thr_flags(vals, idx, begin, end, t, descending, v));
     }
 #pragma unroll
@@ -152,11 +98,10 @@ __global__ __launch_bounds__(256) void k_thr_emit(const float *__restrict__ vals
     uint64_t pos = off[e];  // wave-uniform
     if (off[e + 1] == pos) return;  // (also every chunk beyond the row's end)
     pos -= sub;
-    const ThrChunk row = thr_row(g, r);
-    const uint64_t cb = (uint64_t)ch * kThrChunk;
-    const uint64_t begin = row.rowoff + cb, end = row.rowoff + (row.len - cb < kThrChunk ? row.len : cb + kThrChunk);
-    const uint64_t abase = begin & ~(uint64_t)3;
-    for (uint64_t sb = abase; sb < end; sb += kStep) {  // wave-uniform trip count: every lane takes part in the ballots
+    const ThrRow row = thr_row(g, r);
+    uint64_t begin, end;
+    (void)thr_chunk(row, ch, begin, end);  // (not behind the row's end: the chunk has hits)
+    for (uint64_t sb = thr_first(begin, 0); sb < end; sb += kThrStep) {  // wave-uniform trip count: every lane takes part in the ballots
         const uint64_t idx = sb + 4 * lane;
         float v[4];
         const uint32_t m = idx < end ? thr_flags(vals, idx, begin, end, t, descending, v) : 0u;
@@ -187,7 +132,7 @@ __global__ __launch_bounds__(256) void k_thr_emit(const float *__restrict__ vals
 hipError_t launch_thr_count(hipStream_t st, const float *vals, const ThrRows &g, float t, int descending, uint32_t *cnt)
 {
     if (g.rows == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_thr_count, dim3((uint32_t)g.rows, (g.nchunks + 3) / 4), dim3(256), 0, st, vals, g, t, descending, cnt);
+    hipLaunchKernelGGL(k_thr_count, thr_grid(g), dim3(256), 0, st, vals, g, t, descending, cnt);
     return hipGetLastError();
 }
 
@@ -203,7 +148,7 @@ hipError_t launch_thr_emit(hipStream_t st, const float *vals, const ThrRows &g, 
                            uint64_t sub, uint64_t cap, uint32_t *col, float *val)
 {
     if (g.rows == 0 || cap == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_thr_emit, dim3((uint32_t)g.rows, (g.nchunks + 3) / 4), dim3(256), 0, st, vals, g, t, descending,
+    hipLaunchKernelGGL(k_thr_emit, thr_grid(g), dim3(256), 0, st, vals, g, t, descending,
                        reinterpret_cast<const unsigned long long *>(off), sub, cap, col, val);
     return hipGetLastError();
 }

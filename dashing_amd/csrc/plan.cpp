@@ -19,20 +19,25 @@ uint64_t tri_span(uint64_t n, uint64_t rb, uint64_t re)
     return cnt * (n - 1) - (rb + re - 1) * cnt / 2;
 }
 
-uint64_t greedy_band_end(uint64_t n, uint64_t b0, uint64_t band_floats, uint64_t row_cap)
+uint64_t tri_band_end(uint64_t n, uint64_t b0, uint64_t re, uint64_t band_floats, uint64_t row_cap)
 {
-    const uint64_t max_rows = std::min<uint64_t>(std::max<uint64_t>(row_cap, 1), 1u << 20);
+    const uint64_t max_rows = std::min<uint64_t>(std::max<uint64_t>(row_cap, 1), kBandMaxRows);
     uint64_t b1 = b0, span = 0;
     do {
         span += n - 1 - b1;
         ++b1;
-    } while (b1 < n && b1 - b0 < max_rows && span + (n - 1 - b1) <= band_floats);
+    } while (b1 < re && b1 - b0 < max_rows && span + (n - 1 - b1) <= band_floats);
     return b1;
+}
+
+uint64_t rect_band_rows(uint64_t ncols, uint64_t band_floats)
+{
+    return std::min<uint64_t>(std::max<uint64_t>(band_floats / std::max<uint64_t>(ncols, 1), 1), kBandMaxRows);
 }
 
 bool greedy_old_band(const uint32_t *labels_in, uint64_t m, uint64_t ncols, uint64_t from, uint64_t band_floats, uint64_t &b0, uint64_t &b1)
 {
-    const uint64_t max_rows = std::min<uint64_t>(std::max<uint64_t>(band_floats / std::max<uint64_t>(ncols, 1), 1), 1u << 20);
+    const uint64_t max_rows = rect_band_rows(ncols, band_floats);
     uint64_t x = from;
     while (x < m && labels_in[x] != x) ++x;
     if (x >= m) return false;

@@ -41,12 +41,15 @@ void balance_rows(uint64_t n, uint32_t nparts, uint64_t *bounds);
 // rows [rb, re) cut into nparts consecutive parts of about equal pair counts, every cut a whole number of 128-row
 // tile rows after rb (fewer parts if the range has fewer tile rows); out gets the boundaries
 void range_parts(uint64_t n, uint64_t rb, uint64_t re, uint32_t nparts, std::vector<uint64_t> &out);
-// the band of dsh_greedy_threshold* that starts at triangle row b0 < n: whole rows [b0, b1), at most band_floats values
-// (one row at least), at most 2^20 rows -- the rule of dsh_dist_threshold* -- and at most row_cap rows (>= 1); returns b1
-uint64_t greedy_band_end(uint64_t n, uint64_t b0, uint64_t band_floats, uint64_t row_cap);
+// THE band rule of everything that walks the dense compare path band by band (bands.h).  A band of whole triangle rows
+// [b0, b1) that starts at row b0 < re <= n and ends at or before re: at most band_floats values (one row at least) and at
+// most min(max(row_cap, 1), kBandMaxRows) rows; returns b1
+uint64_t tri_band_end(uint64_t n, uint64_t b0, uint64_t re, uint64_t band_floats, uint64_t row_cap);
+// the same for rows of ncols values each (a rectangle): the rows of a band, max(band_floats / ncols, 1), at most kBandMaxRows
+uint64_t rect_band_rows(uint64_t ncols, uint64_t band_floats);
 // the next band of OLD rows of dsh_greedy_extend* (the rectangle [0, m) x [m, n), ncols = n - m columns): only rows that
 // are representatives (labels_in[x] == x) have something to say, so a band starts at the first representative at or behind
-// `from`, holds at most max(band_floats / ncols, 1) rows and at most 2^20 -- the rectangle rule of dsh_dist_rect_threshold --
+// `from`, holds at most rect_band_rows(ncols, band_floats) rows
 // and ends behind the LAST representative inside that window: a stretch without any is not computed.  Returns false when
 // no representative is left in [from, m); else [b0, b1), b0 < b1 <= m, labels_in[b0] == b0 and labels_in[b1 - 1] == b1 - 1.
 bool greedy_old_band(const uint32_t *labels_in, uint64_t m, uint64_t ncols, uint64_t from, uint64_t band_floats, uint64_t &b0, uint64_t &b1);

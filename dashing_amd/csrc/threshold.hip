@@ -1,11 +1,11 @@
 // threshold.hip -- dsh_dist_threshold*, dsh_dist_rect_threshold: the pairs whose value passes a threshold, as CSR, without
-// the dense result ever reaching the host.  The dense path is the producer and is not changed: a band of
-// whole rows is computed by run_pairs into a library-owned device buffer exactly as dsh_dist_rows_device /
-// dsh_dist_rect compute it, then counted, scanned and emitted on the ctx stream (kernels_threshold.hip).
+// the dense result ever reaching the host.  The dense path is the producer and is not changed: the band walk
+// of bands.h computes a band of whole rows into a library-owned device buffer, which is then counted, scanned and emitted on
+// the ctx stream (kernels_threshold.hip).
 #include <algorithm>
 #include <cstring>
 
-#include "ctx.h"
+#include "bands.h"
 
 using namespace dsh;
 
@@ -65,9 +65,7 @@ int run_threshold(dsh_ctx *c, const ThrQuery &q, uint64_t *n_hits)
 {
     const int descending = measure_descending(q.result_type) ? 1 : 0;
     const uint64_t rows = q.re > q.rb ? q.re - q.rb : 0;
-    const uint64_t ncols = q.rect ? (q.ce > q.cb ? q.ce - q.cb : 0) : 0;
     const bool emit = q.host ? (q.h_col && q.h_val) : (q.d_col && q.d_val);
-    const uint64_t band_floats = std::max<uint64_t>(c->threshold_band_bytes / sizeof(float), 1);
     HIPCHK(c, c->thr_total.ensure(sizeof(uint64_t)));
     uint64_t *d_total = (uint64_t *)c->thr_total.ptr;
     uint64_t *d_row_ptr = q.d_row_ptr;
@@ -76,92 +74,48 @@ int run_threshold(dsh_ctx *c, const ThrQuery &q, uint64_t *n_hits)
         d_row_ptr = (uint64_t *)c->thr_rowptr.ptr;
     }
     HIPCHK(c, hipMemsetAsync(d_total, 0, sizeof(uint64_t), c->stream));
+    // from here on work is queued: every failure goes through the one exit below, which drains the stream and frees hh
     HostHits hh;
     uint64_t done = 0;  // (host form) hits of the bands so far
-    int rc = DSH_OK;
-    for (uint64_t b0 = q.rb; b0 < q.re && rc == DSH_OK;) {
-        // a band: whole rows, at most band_floats values (one row at least), at most 2^20 rows
-        uint64_t b1 = b0, span = 0, longest;
-        if (q.rect) {
-            b1 = std::min<uint64_t>(q.re, b0 + std::min<uint64_t>(std::max<uint64_t>(band_floats / std::max<uint64_t>(ncols, 1), 1), 1u << 20));
-            span = (b1 - b0) * ncols;
-            longest = ncols;
-        } else {
-            longest = c->n - 1 - b0;
-            do {
-                span += c->n - 1 - b1;
-                ++b1;
-            } while (b1 < q.re && b1 - b0 < (1u << 20) && span + (c->n - 1 - b1) <= band_floats);
-        }
-        const uint64_t nchunks64 = std::max<uint64_t>((longest + kThrChunk - 1) / kThrChunk, 1);
-        if ((nchunks64 + 3) / 4 > 65535) return fail(c, DSH_EINVAL, "rows of %llu values are not supported", (unsigned long long)longest);
-        ThrRows g;
-        g.rect = q.rect;
-        g.n = c->n;
-        g.row0 = b0;
-        g.ncols = ncols;
-        g.col0 = q.cb;
-        g.rows = b1 - b0;
-        g.nchunks = (uint32_t)nchunks64;
+    BandQuery bq;
+    bq.estim = q.estim, bq.result_type = q.result_type, bq.k = q.k, bq.rect = q.rect;
+    bq.rb = q.rb, bq.re = q.re, bq.cb = q.cb, bq.ce = q.ce;
+    bq.empty_bands = true;  // a row without values still has its entry of row_ptr
+    int rc = for_each_band(c, bq, [&](const ThrRows &g, const float *vals, uint64_t) -> int {
         const uint64_t m = g.rows * g.nchunks;
-        HIPCHK(c, c->thr_vals.ensure(std::max<uint64_t>(span, 1) * sizeof(float)));
         HIPCHK(c, c->thr_cnt.ensure(m * sizeof(uint32_t)));
         HIPCHK(c, c->thr_off.ensure((m + 1) * sizeof(uint64_t)));
-        if (span) {
-            const PairJob j = q.rect ? PairJob::rectangle(q.estim, q.result_type, q.k, b0, b1, q.cb, q.ce, c->thr_vals.ptr)
-                                     : PairJob::triangle(q.estim, q.result_type, q.k, b0, b1, dsh_tri_span(c->n, 0, b0), c->thr_vals.ptr);
-            if ((rc = run_pairs(c, j))) break;
-        }
-        const float *vals = (const float *)c->thr_vals.ptr;
         hipError_t e = launch_thr_count(c->stream, vals, g, q.t, descending, (uint32_t *)c->thr_cnt.ptr);
         if (e == hipSuccess)
             e = launch_thr_scan(c->stream, (const uint32_t *)c->thr_cnt.ptr, m, g.nchunks, (uint64_t *)c->thr_off.ptr,
-                                d_row_ptr + (b0 - q.rb), d_total);
-        if (e != hipSuccess) {
-            rc = fail(c, DSH_EIO, "k_thr_count/k_thr_scan: %s", hipGetErrorString(e));
-            break;
-        }
-        if (emit && q.host) {
-            // the band's total decides how much room its hits need: the one host wait per band
-            uint64_t tot = 0;
-            if (hipMemcpyAsync(&tot, d_total, sizeof tot, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
-                hipStreamSynchronize(c->stream) != hipSuccess) {
-                rc = fail(c, DSH_EIO, "copy of the band total failed");
-                break;
-            }
-            const uint64_t bh = tot - done;
-            if (bh) {
-                if (c->thr_col.ensure(bh * sizeof(uint32_t)) != hipSuccess || c->thr_val.ensure(bh * sizeof(float)) != hipSuccess) {
-                    (void)hipGetLastError();
-                    rc = fail(c, DSH_ENOMEM, "device allocation failed");
-                    break;
-                }
-                if (!hh.grow(tot, done)) {  // (the stream is idle: earlier bands' copies have arrived)
-                    rc = fail(c, DSH_ENOMEM, "host allocation of %llu hits failed", (unsigned long long)tot);
-                    break;
-                }
-                e = launch_thr_emit(c->stream, vals, g, q.t, descending, (const uint64_t *)c->thr_off.ptr, done, bh,
-                                    (uint32_t *)c->thr_col.ptr, (float *)c->thr_val.ptr);
-                if (e != hipSuccess) {
-                    rc = fail(c, DSH_EIO, "k_thr_emit: %s", hipGetErrorString(e));
-                    break;
-                }
-                if (hipMemcpyAsync(hh.col + done, c->thr_col.ptr, bh * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
-                    hipMemcpyAsync(hh.val + done, c->thr_val.ptr, bh * sizeof(float), hipMemcpyDeviceToHost, c->stream) != hipSuccess) {
-                    rc = fail(c, DSH_EIO, "copy of the hits failed");
-                    break;
-                }
-            }
-            done = tot;
-        } else if (emit) {
+                                d_row_ptr + (g.row0 - q.rb), d_total);
+        if (e != hipSuccess) return fail(c, DSH_EIO, "k_thr_count/k_thr_scan: %s", hipGetErrorString(e));
+        if (!emit) return DSH_OK;
+        if (!q.host) {
             e = launch_thr_emit(c->stream, vals, g, q.t, descending, (const uint64_t *)c->thr_off.ptr, 0, q.cap, q.d_col, q.d_val);
-            if (e != hipSuccess) {
-                rc = fail(c, DSH_EIO, "k_thr_emit: %s", hipGetErrorString(e));
-                break;
-            }
+            return e == hipSuccess ? DSH_OK : fail(c, DSH_EIO, "k_thr_emit: %s", hipGetErrorString(e));
         }
-        b0 = b1;
-    }
+        // the band's total decides how much room its hits need: the one host wait per band
+        uint64_t tot = 0;
+        if (hipMemcpyAsync(&tot, d_total, sizeof tot, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+            hipStreamSynchronize(c->stream) != hipSuccess)
+            return fail(c, DSH_EIO, "copy of the band total failed");
+        const uint64_t bh = tot - done;
+        if (bh) {
+            HIPCHK(c, c->thr_col.ensure(bh * sizeof(uint32_t)));
+            HIPCHK(c, c->thr_val.ensure(bh * sizeof(float)));
+            if (!hh.grow(tot, done))  // (the stream is idle: earlier bands' copies have arrived)
+                return fail(c, DSH_ENOMEM, "host allocation of %llu hits failed", (unsigned long long)tot);
+            e = launch_thr_emit(c->stream, vals, g, q.t, descending, (const uint64_t *)c->thr_off.ptr, done, bh,
+                                (uint32_t *)c->thr_col.ptr, (float *)c->thr_val.ptr);
+            if (e != hipSuccess) return fail(c, DSH_EIO, "k_thr_emit: %s", hipGetErrorString(e));
+            if (hipMemcpyAsync(hh.col + done, c->thr_col.ptr, bh * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+                hipMemcpyAsync(hh.val + done, c->thr_val.ptr, bh * sizeof(float), hipMemcpyDeviceToHost, c->stream) != hipSuccess)
+                return fail(c, DSH_EIO, "copy of the hits failed");
+        }
+        done = tot;
+        return DSH_OK;
+    });
     uint64_t total = 0;
     if (rc == DSH_OK) {
         // row_ptr[rows] = the total (also the whole of an empty range's row pointer)
@@ -171,14 +125,14 @@ int run_threshold(dsh_ctx *c, const ThrQuery &q, uint64_t *n_hits)
             rc = fail(c, DSH_EIO, "copy of the row pointer failed");
     }
     if (hipStreamSynchronize(c->stream) != hipSuccess && rc == DSH_OK) rc = fail(c, DSH_EIO, "hipStreamSynchronize failed");
-    if (rc) {
+    if (rc == DSH_OK && q.host && emit && !hh.col && !hh.grow(1, 0)) rc = fail(c, DSH_ENOMEM, "host allocation failed");  // no hits: still a pointer to free
+    if (rc) {  // (the wait above has drained the stream)
         (void)hipGetLastError();
         hh.release();
         return rc;
     }
     if (n_hits) *n_hits = total;
     if (q.host && emit) {
-        if (!hh.col && !hh.grow(1, 0)) return fail(c, DSH_ENOMEM, "host allocation failed");  // no hits: still a pointer to free
         *q.h_col = hh.col;
         *q.h_val = hh.val;
     }
