@@ -15,9 +15,13 @@ MASH_DIST, JI, FULL_MASH_DIST = 0, 1, 3  # bns::EmissionType, src/enums.h:13-23
 SIZES, FULL_CONTAINMENT_DIST, CONTAINMENT_INDEX, CONTAINMENT_DIST = 2, 4, 5, 6
 SYMMETRIC_CONTAINMENT_INDEX, SYMMETRIC_CONTAINMENT_DIST = 7, 8
 GREEDY_FIRST, GREEDY_BEST = 0, 1  # assign_mode of dsh_greedy_extend*
+HIST_MAX_EDGES = 4096  # DSH_HIST_MAX_EDGES: the edges of one dsh_dist_histogram* call
 STATS_FRAC_BITS = 30  # DSH_STATS_FRAC_BITS: sums of dsh_group_stats* are in units of 2^-30
 # the measures for which a larger value is better (the others are the *_DIST forms; SIZES has no order)
 SIMILARITY_TYPES = (JI, CONTAINMENT_INDEX, SYMMETRIC_CONTAINMENT_INDEX)
+# the *_DIST forms: a smaller value is better and a threshold passes with v <= t; every other measure, SIZES included, ranks
+# descending and passes with v >= t (measure_descending of the library)
+DISTANCE_TYPES = (MASH_DIST, FULL_MASH_DIST, FULL_CONTAINMENT_DIST, CONTAINMENT_DIST, SYMMETRIC_CONTAINMENT_DIST)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
@@ -38,6 +42,7 @@ SYMBOLS = [
     "dsh_cluster_threshold", "dsh_cluster_threshold_device", "dsh_cluster_pairs", "dsh_cluster_csr",
     "dsh_greedy_threshold", "dsh_greedy_threshold_device", "dsh_greedy_extend", "dsh_greedy_extend_device",
     "dsh_group_stats", "dsh_group_stats_device",
+    "dsh_dist_histogram", "dsh_dist_histogram_device", "dsh_dist_rect_histogram",
     "dsh_fold", "dsh_fold_device", "dsh_upload_sketches_folded", "dsh_upload_sketches_folded_device", "dsh_union_groups", "dsh_union_groups_device", "dsh_shard_plan", "dsh_dist_shard_device", "dsh_unpermute_device", "dsh_unpermute_staged_device", "dsh_unpermute_blocks_device", "dsh_tri_span", "dsh_tri_index", "dsh_partition_rows", "dsh_balance_rows", "dsh_balance_rowsets", "dsh_rowsets_from_bounds", "dsh_rowsets_rank", "dsh_alloc_host", "dsh_free_host",
     "dsh_set_profiling", "dsh_last_kernel_ms", "dsh_last_part_info", "dsh_finalize_phase_cycles", "dsh_set_option", "dsh_get_info", "dsh_stream",
 ]
@@ -177,7 +182,10 @@ def load_library():
                        ("dsh_greedy_extend", [vp, i32, i32, i32, C.c_float, i32, u64, vp, vp, C.POINTER(u64)]),
                        ("dsh_greedy_extend_device", [vp, i32, i32, i32, C.c_float, i32, u64, vp, vp, C.POINTER(u64)]),
                        ("dsh_group_stats", [vp, i32, i32, i32, vp, vp, vp, vp, vp]),
-                       ("dsh_group_stats_device", [vp, i32, i32, i32, vp, vp, vp, vp, vp])):
+                       ("dsh_group_stats_device", [vp, i32, i32, i32, vp, vp, vp, vp, vp]),
+                       ("dsh_dist_histogram", [vp, i32, i32, i32, u64, u64, vp, C.c_uint32, vp, vp]),
+                       ("dsh_dist_histogram_device", [vp, i32, i32, i32, u64, u64, vp, C.c_uint32, vp, vp]),
+                       ("dsh_dist_rect_histogram", [vp, i32, i32, i32, u64, u64, u64, u64, vp, C.c_uint32, vp, vp])):
         fn = getattr(lib, name, None)
         if fn is not None:
             fn.argtypes = args
@@ -350,6 +358,23 @@ def balance_rows(n, nparts):
     if rc:
         raise DshError(rc, "dsh_balance_rows")
     return [int(x) for x in b]
+
+
+def histogram_hits(counts, result_type):
+    """Per edge b of a dist_histogram result (counts of shape (planes, n_edges + 2) or (n_edges + 2,)), the n_hits that
+    dist_threshold over the same rows gives at threshold = edges[b]: for the *_DIST forms (DISTANCE_TYPES) the sum of the
+    classes 0 .. b, for every other measure -- the similarities and SIZES, which the library ranks descending -- the sum of
+    the classes b + 1 .. n_edges.  The NaN class (the last) passes no threshold.  uint64 of shape (planes, n_edges), or
+    (n_edges,) for one-dimensional counts."""
+    if isinstance(result_type, bool) or result_type not in range(9):
+        raise ValueError("unsupported result_type %r" % (result_type,))
+    c = np.asarray(counts, np.uint64)
+    if c.ndim not in (1, 2) or c.shape[-1] < 3:
+        raise ValueError("counts holds n_edges + 2 classes per plane")
+    body = c[..., :-1]  # without the NaN class
+    if result_type in DISTANCE_TYPES:
+        return np.cumsum(body, axis=-1, dtype=np.uint64)[..., :-1]
+    return np.cumsum(body[..., ::-1], axis=-1, dtype=np.uint64)[..., ::-1][..., 1:]
 
 
 class GroupStats(collections.namedtuple("GroupStats", "medoid cnt sum worst")):
@@ -836,6 +861,48 @@ class Context:
         labels stays a host array"""
         self._stats_call("dsh_group_stats_device", labels, estim, result_type, k, route,
                          [C.c_void_p(p) if p else None for p in (medoid_ptr, cnt_ptr, sum_ptr, worst_ptr)])
+
+    # ---- value histograms over caller-given edges (include/dashing_hip.h has the contract)
+    _NO_LABELS = np.zeros(1, np.uint32)  # what an empty labelling points at: two planes are asked for, nothing is read
+
+    def _hist_args(self, edges, labels):
+        """(edges float32, their pointer, labels pointer or None, planes)"""
+        e = np.ascontiguousarray(edges, np.float32).reshape(-1)
+        if labels is None:
+            return e, (e.ctypes.data if e.size else None), None, None, 1
+        lab = np.ascontiguousarray(labels, np.uint32).reshape(-1)
+        if lab.size != self.n:
+            raise ValueError("labels holds one label per sketch")
+        keep = lab if lab.size else self._NO_LABELS
+        return e, (e.ctypes.data if e.size else None), keep, keep.ctypes.data, 2
+
+    def dist_histogram(self, edges, row_begin=0, row_end=None, labels=None, estim=ESTIM_ERTL_MLE, result_type=JI, k=31):
+        """uint64 (planes, n_edges + 2): how many values of dist_rows over rows [row_begin, row_end) fall into each class of
+        the strictly increasing float32 `edges` -- class(v) = the number of edges that pass v as a threshold would
+        (similarities e <= v, distances e < v), NaN the last class.  labels (one per slot): plane 0 counts the pairs with
+        equal labels, plane 1 the others; without labels one plane.  histogram_hits() turns it into hit counts per edge."""
+        row_end = self.n if row_end is None else row_end
+        e, ep, _keep, labp, planes = self._hist_args(edges, labels)
+        out = np.zeros((planes, e.size + 2), np.uint64)
+        self._ck(self._derive("dsh_dist_histogram")(self._h, estim, result_type, k, row_begin, row_end, ep, e.size, labp, out.ctypes.data))
+        return out
+
+    def dist_histogram_device(self, counts_ptr, edges, row_begin=0, row_end=None, labels=None, estim=ESTIM_ERTL_MLE, result_type=JI,
+                              k=31):
+        """the same into the caller's device buffer (uint64 [planes][n_edges + 2], 8-byte aligned, overwritten); edges and
+        labels stay host arrays"""
+        row_end = self.n if row_end is None else row_end
+        e, ep, _keep, labp, _ = self._hist_args(edges, labels)
+        self._ck(self._derive("dsh_dist_histogram_device")(self._h, estim, result_type, k, row_begin, row_end, ep, e.size, labp,
+                                                           C.c_void_p(counts_ptr) if counts_ptr else None))
+
+    def dist_rect_histogram(self, edges, q_begin, q_end, r_begin, r_end, labels=None, estim=ESTIM_ERTL_MLE, result_type=JI, k=31):
+        """as dist_histogram for the values of dist_rect (query slots x reference slots, self pairs included)"""
+        e, ep, _keep, labp, planes = self._hist_args(edges, labels)
+        out = np.zeros((planes, e.size + 2), np.uint64)
+        self._ck(self._derive("dsh_dist_rect_histogram")(self._h, estim, result_type, k, q_begin, q_end, r_begin, r_end, ep, e.size,
+                                                         labp, out.ctypes.data))
+        return out
 
     @staticmethod
     def _labels_in(n_nodes, labels_in):

@@ -61,7 +61,7 @@ static void release_ctx(dsh_ctx *c)
                       &c->pairs_rhs, &c->pairs_out, &c->pairs_err, &c->derive_err, &c->derive_stage, &c->derive_ptr, &c->derive_mem,
                       &c->derive_dst, &c->derive_part[0], &c->derive_part[1], &c->derive_out, &c->cc_parent, &c->cc_state, &c->cc_lhs,
                       &c->cc_rhs, &c->cc_rowptr, &c->cc_seed, &c->cc_labels, &c->gr_assign, &c->gr_state, &c->gr_labels, &c->gr_best,
-                      &c->gs_labels, &c->gs_acc, &c->gs_grp, &c->gs_out, &c->gs_csr})
+                      &c->gs_labels, &c->gs_acc, &c->gs_grp, &c->gs_out, &c->gs_csr, &c->hs_edges, &c->hs_labels, &c->hs_counts})
         b->release();
     if (c->pin_perm) (void)hipHostFree(c->pin_perm);
     c->pin_perm = nullptr;
@@ -138,6 +138,7 @@ int dsh_preload(int device, unsigned what)
     if ((what & DSH_PRELOAD_SKETCH) && e == hipSuccess) e = preload_sketch_kernels();
     if ((what & DSH_PRELOAD_SKETCH) && e == hipSuccess) e = preload_fastx_kernels();
     if ((what & DSH_PRELOAD_COMPARE) && e == hipSuccess) e = preload_compare_kernels();
+    if ((what & DSH_PRELOAD_COMPARE) && e == hipSuccess) e = preload_hist_kernels();
     if (e != hipSuccess) (void)hipGetLastError();
     return e == hipSuccess ? DSH_OK : DSH_EIO;
 }

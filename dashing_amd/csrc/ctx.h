@@ -11,6 +11,7 @@
 //   greedy.hip    dsh_greedy_threshold* (greedy representatives at a threshold, in slot order)
 //   greedy_extend.hip  dsh_greedy_extend* (the same behind a labelling of the first slots; first or best representative)
 //   group_stats.hip    dsh_group_stats* (per-group statistics and medoids of a labelling)
+//   hist.hip      dsh_dist_histogram*, dsh_dist_rect_histogram (the distribution of the values over caller-given edges)
 //   derive.hip    dsh_fold*, dsh_upload_sketches_folded*, dsh_union_groups* (new sketches out of resident ones)
 //   exchange.hip  RCCL: dsh_comm_*, dsh_collect_*, dsh_allgather_device, dsh_dist_collect
 //   plan.cpp      the pure-host planner (layout, tiles, bands, parts, work items, row partitions)
@@ -202,6 +203,9 @@ struct dsh_ctx {
     // dsh_group_stats* (group_stats.hip): the labels, the per-slot accumulators (cnt, sum, worst key) and per-group medoid
     // keys, the outputs of the host form, and for the pairs route the member CSR
     DevBuf gs_labels, gs_acc, gs_grp, gs_out, gs_csr;
+    // dsh_dist_histogram* (hist.hip): the edges, the labels and the call's uint64 counters (the host forms' on their way out)
+    DevBuf hs_edges, hs_labels, hs_counts;
+    int hs_cus = 0;                     // compute units of the device (hipDeviceAttributeMultiprocessorCount), queried once
     int stats_route = -1;               // option: -1 auto | 0 dense | 1 pairs
     int stats_route_last = -1;          // (info) the route the last dsh_group_stats* call took
     uint64_t greedy_band_rows = 4096;   // option: a band holds at most this many rows (k_greedy_diag's LDS; 1..kGreedyMaxRows)

@@ -9,6 +9,7 @@
 
 #include <atomic>
 #include <fstream>
+#include <limits>
 #include <sys/stat.h>
 #include <unistd.h>
 #include <zlib.h>
@@ -118,6 +119,20 @@ static void usage(const char *sub)
             "                           the other members of its group ('-' where it has none), and the worst such value; -b appends\n"
             "                           u32 medoid[n], u32 cnt[n], i64 sum[n] (values in units of 2^-30), f32 worst[n].  Not with\n"
             "                           --sizes.\n"
+            "  --histogram SPEC         emit the distribution of the values instead of the values: how many pairs fall between\n"
+            "                           the edges SPEC names, counted on the device in one pass (dsh_dist_histogram).  SPEC is\n"
+            "                           lo:hi:nbins (the nbins + 1 edges lo + (hi - lo) * i / nbins), a comma list of numbers, or\n"
+            "                           @FILE with one number per line; at most 4096 edges, strictly increasing as float32.  An\n"
+            "                           edge is closed on the side that passes --threshold: bins [lo, hi) for the similarity\n"
+            "                           measures, (lo, hi] for the distances.  Text: '#Histogram<TAB>measure<TAB>\">=\" or \"<=\"',\n"
+            "                           then per class lower<TAB>upper<TAB>count ('-inf' / 'inf' for the outer classes, 'nan' for\n"
+            "                           the values that are NaN); -b: u64 n_edges, u64 planes, f32 edges[n_edges] padded to 8\n"
+            "                           bytes, u64 counts[planes][n_edges + 2].  With -Q the queries x references rectangle is\n"
+            "                           counted, else every pair once (also for the asymmetric measures).  Not with --threshold,\n"
+            "                           --cluster, --representatives, --nearest-neighbors, --pairs, -U, -T or several devices.\n"
+            "  --histogram-labels FILE  with --histogram: FILE is the -b output of --cluster or --representatives over the same\n"
+            "                           inputs in the same order; every line gets two counts, the pairs inside a group and the\n"
+            "                           pairs between groups (-b: two planes).\n"
             "  --pairs FILE             emit only the pairs FILE lists, one per line as name_a<TAB>name_b (input names as given\n"
             "                           here; record names with dist_by_seq), in FILE's order: name_a<TAB>name_b and one value per\n"
             "                           measure.  --measures LIST: comma-separated from MASH_DIST, JI, SIZES, FULL_MASH_DIST,\n"
@@ -147,6 +162,9 @@ struct Opts {
     int assign_mode = DSH_GREEDY_FIRST;  // --assign first|best (dsh_greedy_extend)
     bool has_assign = false;
     bool has_stats = false;  // --stats: medoid, mean and worst value per input of the labelling (dsh_group_stats)
+    bool has_hist = false;  // --histogram SPEC: the distribution of the values over the edges of SPEC (dsh_dist_histogram)
+    std::vector<float> hist_edges;
+    std::string hist_labels_file;  // --histogram-labels FILE: counts split into intra-group and inter-group pairs
     std::string extend_file;  // --extend FILE: the labels of an earlier --representatives -b run over the first inputs
     std::string groups_file;  // --groups FILE: the unions of named groups are compared instead of the inputs (dsh_union_groups)
     std::string pairs_file, measures;  // --pairs FILE [--measures LIST]: only the listed pairs (dsh_dist_pairs)
@@ -185,7 +203,75 @@ struct GroupStats {
     }
 };
 
-enum { OPT_PRESKETCHED = 1000, OPT_AVOID_SORT, OPT_DEVICE, OPT_NPERBATCH, OPT_NN, OPT_NGPUS, OPT_DEVICES, OPT_RCCL, OPT_THRESHOLD, OPT_CLUSTER, OPT_REPS, OPT_ASSIGN, OPT_EXTEND, OPT_STATS, OPT_PAIRS, OPT_MEASURES, OPT_GROUPS, OPT_UNSUPPORTED };
+// one number of a --histogram SPEC (strtod's syntax: inf and -inf included), whole token; NaN is no edge
+static double histogram_number(const std::string &tok, const char *spec)
+{
+    char *end = nullptr;
+    const double v = std::strtod(tok.c_str(), &end);
+    if (tok.empty() || end == tok.c_str() || *end || v != v) die("--histogram: '%s' in '%s' is not a number", tok.c_str(), spec);
+    return v;
+}
+
+// --histogram SPEC: lo:hi:nbins | a comma list of numbers | @FILE with one number per line -> the float32 edges
+static std::vector<float> parse_histogram_spec(const char *spec)
+{
+    const std::string sp(spec);
+    std::vector<float> e;
+    if (!sp.empty() && sp[0] == '@') {
+        std::ifstream f(sp.substr(1));
+        if (!f) die("--histogram: could not open %s", sp.c_str() + 1);
+        std::string line;
+        while (std::getline(f, line)) {
+            while (!line.empty() && (line.back() == '\r' || line.back() == ' ' || line.back() == '\t')) line.pop_back();
+            if (line.empty()) continue;
+            e.push_back((float)histogram_number(line, spec));
+        }
+    } else if (sp.find(':') != std::string::npos) {
+        const size_t c1 = sp.find(':'), c2 = sp.find(':', c1 + 1);
+        if (c2 == std::string::npos || sp.find(':', c2 + 1) != std::string::npos) die("--histogram: '%s' is not lo:hi:nbins", spec);
+        const double lo = histogram_number(sp.substr(0, c1), spec), hi = histogram_number(sp.substr(c1 + 1, c2 - c1 - 1), spec);
+        const std::string nb = sp.substr(c2 + 1);
+        char *end = nullptr;
+        const long nbins = std::strtol(nb.c_str(), &end, 10);
+        if (nb.empty() || *end || nbins < 1 || nbins + 1 > DSH_HIST_MAX_EDGES)
+            die("--histogram: '%s' needs between 1 and %d bins", spec, DSH_HIST_MAX_EDGES - 1);
+        if (!(lo < hi) || lo - lo != 0 || hi - hi != 0) die("--histogram: '%s' needs finite lo < hi", spec);
+        for (long i = 0; i <= nbins; ++i) e.push_back((float)(lo + (hi - lo) * (double)i / (double)nbins));
+    } else {
+        for (size_t b = 0; b <= sp.size();) {
+            const size_t c = std::min(sp.find(',', b), sp.size());
+            e.push_back((float)histogram_number(sp.substr(b, c - b), spec));
+            b = c + 1;
+        }
+    }
+    if (e.empty() || e.size() > (size_t)DSH_HIST_MAX_EDGES) die("--histogram: '%s' gives %zu edges: between 1 and %d", spec, e.size(), DSH_HIST_MAX_EDGES);
+    for (size_t b = 1; b < e.size(); ++b)
+        if (!(e[b - 1] < e[b]))
+            die("--histogram: '%s': edge %zu (%.9g) is not above edge %zu (%.9g) as float32: the edges must increase strictly", spec, b,
+                (double)e[b], b - 1, (double)e[b - 1]);
+    return e;
+}
+
+// the labels of a --cluster -b / --representatives -b file: u64 n, u64 count, u32 labels[n] (what --extend and
+// --histogram-labels read)
+static std::vector<uint32_t> read_labels_binary(const char *flag, const std::string &path)
+{
+    std::FILE *ef = std::fopen(path.c_str(), "rb");
+    if (!ef) die("%s: could not open %s", flag, path.c_str());
+    uint64_t hdr[2] = {0, 0};
+    if (std::fread(hdr, sizeof(uint64_t), 2, ef) != 2) die("%s: %s is too short for the header of a --cluster -b or --representatives -b file", flag, path.c_str());
+    if (std::fseek(ef, 0, SEEK_END) != 0) die("%s: could not read %s", flag, path.c_str());
+    const long fsize = std::ftell(ef);
+    if (hdr[0] > 0xFFFFFFFFull || fsize < 0 || (uint64_t)fsize != 16 + 4 * hdr[0])
+        die("%s: %s has the wrong length for the %llu labels its header announces", flag, path.c_str(), (unsigned long long)hdr[0]);
+    std::vector<uint32_t> labels((size_t)hdr[0]);
+    if (std::fseek(ef, 16, SEEK_SET) != 0 || std::fread(labels.data(), sizeof(uint32_t), labels.size(), ef) != labels.size())
+        die("%s: could not read %s", flag, path.c_str());
+    std::fclose(ef);
+    return labels;
+}
+
+enum { OPT_PRESKETCHED = 1000, OPT_AVOID_SORT, OPT_DEVICE, OPT_NPERBATCH, OPT_NN, OPT_NGPUS, OPT_DEVICES, OPT_RCCL, OPT_THRESHOLD, OPT_CLUSTER, OPT_REPS, OPT_ASSIGN, OPT_EXTEND, OPT_STATS, OPT_HISTOGRAM, OPT_HISTOGRAM_LABELS, OPT_PAIRS, OPT_MEASURES, OPT_GROUPS, OPT_UNSUPPORTED };
 
 static Opts parse(int argc, char **argv, bool is_dist)
 {
@@ -215,6 +301,7 @@ static Opts parse(int argc, char **argv, bool is_dist)
         {"cluster", required_argument, nullptr, OPT_CLUSTER}, {"representatives", required_argument, nullptr, OPT_REPS},
         {"assign", required_argument, nullptr, OPT_ASSIGN}, {"extend", required_argument, nullptr, OPT_EXTEND},
         {"stats", no_argument, nullptr, OPT_STATS},
+        {"histogram", required_argument, nullptr, OPT_HISTOGRAM}, {"histogram-labels", required_argument, nullptr, OPT_HISTOGRAM_LABELS},
         {"pairs", required_argument, nullptr, OPT_PAIRS}, {"groups", required_argument, nullptr, OPT_GROUPS}, {"measures", required_argument, nullptr, OPT_MEASURES},
         // second arm of result_cmp (src/dashing.h:577-588); flag numbers as in DIST_LONG_OPTS
         {"sizes", no_argument, nullptr, 'Z'}, {"containment-index", no_argument, nullptr, 131},
@@ -308,6 +395,11 @@ static Opts parse(int argc, char **argv, bool is_dist)
             break;
         case OPT_EXTEND: o.extend_file = optarg; break;
         case OPT_STATS: o.has_stats = true; break;
+        case OPT_HISTOGRAM:
+            o.hist_edges = parse_histogram_spec(optarg);
+            o.has_hist = true;
+            break;
+        case OPT_HISTOGRAM_LABELS: o.hist_labels_file = optarg; break;
         case OPT_PAIRS: o.pairs_file = optarg; break;
         case OPT_MEASURES: o.measures = optarg; break;
         case OPT_GROUPS: o.groups_file = optarg; break;
@@ -1061,6 +1153,19 @@ static int dist_main(int argc, char **argv, bool by_seq = false)
         if (o.fmt == FULL_TSV) die("--representatives does not go with -T: the output is one line per input.");
         if (o.devices.size() > 1 || o.rccl) die("--representatives runs on one device: --ngpus / --devices are not supported.");
     }
+    if (o.has_hist) {
+        if (o.has_threshold) die("--histogram does not go with --threshold: choose the distribution or the pairs.");
+        if (o.has_cluster) die("--histogram does not go with --cluster: choose the distribution or the clusters.");
+        if (o.has_reps) die("--histogram does not go with --representatives: choose the distribution or the representatives.");
+        if (o.nneighbors) die("--histogram does not go with --nearest-neighbors: choose one selection.");
+        if (!o.pairs_file.empty()) die("--histogram does not go with --pairs: the distribution is that of all pairs.");
+        if (o.fmt == UPPER_TRIANGULAR) die("--histogram does not go with -U: the output is one line per class.");
+        if (o.fmt == FULL_TSV) die("--histogram does not go with -T: the output is one line per class.");
+        if (o.devices.size() > 1 || o.rccl) die("--histogram runs on one device: --ngpus / --devices are not supported.");
+    }
+    if (!o.hist_labels_file.empty() && !o.has_hist) die("--histogram-labels goes with --histogram only.");
+    std::vector<uint32_t> hist_labels;
+    if (!o.hist_labels_file.empty()) hist_labels = read_labels_binary("--histogram-labels", o.hist_labels_file);
     if (o.has_assign && !o.has_reps) die("--assign goes with --representatives only.");
     if (o.has_stats && !o.has_cluster && !o.has_reps) die("--stats goes with --cluster or --representatives only.");
     if (o.has_stats && o.result_type == DSH_SIZES) die("--stats does not go with --sizes: set sizes have no mean or worst value inside a group.");
@@ -1069,18 +1174,7 @@ static int dist_main(int argc, char **argv, bool by_seq = false)
     if (!o.extend_file.empty()) {
         if (!o.has_reps) die("--extend goes with --representatives only.");
         if (!o.avoid_sorting) die("--extend needs --avoid-sorting: sorting by size would interleave the old inputs and the new.");
-        std::FILE *ef = std::fopen(o.extend_file.c_str(), "rb");
-        if (!ef) die("--extend: could not open %s", o.extend_file.c_str());
-        uint64_t hdr[2] = {0, 0};
-        if (std::fread(hdr, sizeof(uint64_t), 2, ef) != 2) die("--extend: %s is too short for the header of a --representatives -b file", o.extend_file.c_str());
-        if (std::fseek(ef, 0, SEEK_END) != 0) die("--extend: could not read %s", o.extend_file.c_str());
-        const long fsize = std::ftell(ef);
-        if (hdr[0] > 0xFFFFFFFFull || fsize < 0 || (uint64_t)fsize != 16 + 4 * hdr[0])
-            die("--extend: %s has the wrong length for the %llu labels its header announces", o.extend_file.c_str(), (unsigned long long)hdr[0]);
-        extend_labels.resize((size_t)hdr[0]);
-        if (std::fseek(ef, 16, SEEK_SET) != 0 || std::fread(extend_labels.data(), sizeof(uint32_t), extend_labels.size(), ef) != extend_labels.size())
-            die("--extend: could not read %s", o.extend_file.c_str());
-        std::fclose(ef);
+        extend_labels = read_labels_binary("--extend", o.extend_file);
         if (o.groups_file.empty() && extend_labels.size() > o.inpaths.size())
             die("--extend: %s labels %zu inputs but this run has only %zu", o.extend_file.c_str(), extend_labels.size(), o.inpaths.size());
     }
@@ -1121,8 +1215,9 @@ static int dist_main(int argc, char **argv, bool by_seq = false)
     if (!o.out_sizes.empty() && !(ofp = std::fopen(o.out_sizes.c_str(), "w"))) die("Could not open file at %s for writing.", o.out_sizes.c_str());
     if (!o.out_dists.empty() && !(pairofp = std::fopen(o.out_dists.c_str(), "wb"))) die("Could not open file at %s for writing.", o.out_dists.c_str());
     // asymmetric measure without -Q: all references are also the queries (src/distmain.cpp:120-125)
-    // (--cluster and --representatives test every pair once, in the triangle's orientation: no query/reference format for them)
-    const bool symmetric = o.has_cluster || o.has_reps || !(o.result_type == 4 || o.result_type == 5 || o.result_type == 6);  // src/dashing.h:389-399
+    // (--cluster, --representatives and --histogram take every pair once, in the triangle's orientation: no query/reference format
+    // of their own making for them)
+    const bool symmetric = o.has_cluster || o.has_reps || o.has_hist || !(o.result_type == 4 || o.result_type == 5 || o.result_type == 6);  // src/dashing.h:389-399
     if (o.querypaths.empty() && !symmetric && !with_pairs && !with_groups) {  // (a pair list names its own pairs, each in one orientation; the groups take their turn below)
         o.querypaths = o.inpaths;
         std::fprintf(stderr, "Note: No query files provided, but an asymmetric distance was requested. Switching to a query/reference format with all references as queries.\n");
@@ -1368,6 +1463,35 @@ static int dist_main(int argc, char **argv, bool by_seq = false)
                 if (o.has_stats) gs.append_fields(s, x, o.inpaths);
                 s += '\n';
                 std::fwrite(s.data(), 1, s.size(), pairofp);
+            }
+        }
+    } else if (o.has_hist) {  // the distribution of the values (dsh_dist_histogram / dsh_dist_rect_histogram): only counts leave the device
+        if (nq >= n && nq) die("Wrong number of query/references. (ip size: %zu, nq: %zu", n, nq);
+        const bool split = !o.hist_labels_file.empty();
+        if (split && hist_labels.size() != n)
+            die("--histogram-labels: %s labels %zu inputs but this run has %zu", o.hist_labels_file.c_str(), hist_labels.size(), n);
+        const size_t ne = o.hist_edges.size(), nclass = ne + 2, planes = split ? 2 : 1;
+        const uint32_t *lab = split ? hist_labels.data() : nullptr;
+        std::vector<uint64_t> counts(planes * nclass);
+        if (nq) DSH(ctx, dsh_dist_rect_histogram(ctx, o.estim, o.result_type, o.k, n - nq, n, 0, n - nq, o.hist_edges.data(), (uint32_t)ne, lab, counts.data()));
+        else DSH(ctx, dsh_dist_histogram(ctx, o.estim, o.result_type, o.k, 0, n, o.hist_edges.data(), (uint32_t)ne, lab, counts.data()));
+        if (o.fmt == BINARY) {
+            const uint64_t hdr[2] = {(uint64_t)ne, (uint64_t)planes};
+            const float pad = 0.f;
+            if (std::fwrite(hdr, sizeof(uint64_t), 2, pairofp) != 2 || std::fwrite(o.hist_edges.data(), sizeof(float), ne, pairofp) != ne ||
+                ((ne & 1) && std::fwrite(&pad, sizeof(float), 1, pairofp) != 1) ||
+                std::fwrite(counts.data(), sizeof(uint64_t), counts.size(), pairofp) != counts.size())
+                die("Error writing to binary file");
+        } else {
+            const bool dist = o.result_type == 0 || o.result_type == 3 || o.result_type == 4 || o.result_type == 6 || o.result_type == 8;
+            std::fprintf(pairofp, "#Histogram\t%s\t%s\n", kMeasureNames[o.result_type], dist ? "<=" : ">=");
+            const double inf = std::numeric_limits<double>::infinity(), nan = std::numeric_limits<double>::quiet_NaN();
+            for (size_t b = 0; b < nclass; ++b) {  // --threshold's number format
+                const double lo = b == ne + 1 ? nan : (b == 0 ? -inf : (double)o.hist_edges[b - 1]);
+                const double hi = b == ne + 1 ? nan : (b == ne ? inf : (double)o.hist_edges[b]);
+                std::fprintf(pairofp, "%.6g\t%.6g\t%llu", lo, hi, (unsigned long long)counts[b]);
+                if (split) std::fprintf(pairofp, "\t%llu", (unsigned long long)counts[nclass + b]);
+                std::fputc('\n', pairofp);
             }
         }
     } else if (o.has_threshold) {  // only the pairs that pass (dsh_dist_threshold / dsh_dist_rect_threshold): no dense matrix

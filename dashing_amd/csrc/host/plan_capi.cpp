@@ -416,6 +416,14 @@ int64_t dshh_threshold_bands(uint64_t n, uint64_t rb, uint64_t re, uint64_t ncol
     return (int64_t)nb;
 }
 
+// the grid of k_hist (plan::hist_grid) and the trips of a workgroup's waves it implies (tests/test_hist_ref.py)
+uint64_t dshh_hist_grid(uint64_t units, uint64_t lds_bytes, uint32_t cus, uint64_t *iters)
+{
+    const uint64_t grid = hist_grid(units, lds_bytes, cus);
+    if (iters) *iters = units / (4 * grid) + (units % (4 * grid) ? 1 : 0);
+    return grid;
+}
+
 // the bands of dsh_greedy_threshold* (the loop of greedy.hip: plan::tri_band_end up to row n, the empty last row left out):
 // bounds[0] = 0, bounds[q + 1] = the end of band q, for the triangle of n sketches.  Returns the number of bands (0 for
 // n < 2), or -1 when they do not fit cap boundaries (tests/test_greedy_plan.py).

@@ -252,6 +252,15 @@ hipError_t launch_gs_pairs(hipStream_t st, const uint32_t *lhs, const uint32_t *
 hipError_t launch_gs_finish(hipStream_t st, const uint32_t *labels, uint64_t n, int descending, const GsAccum &a, uint32_t *g_cnt,
                             uint64_t *g_sum, uint32_t *g_slot, uint32_t *medoid_out, uint32_t *cnt_out, int64_t *sum_out, float *worst_out);
 
+// value histograms (kernels_hist.hip, hist.hip): a band of triangle or rectangle rows as launch_thr_count takes it, counted
+// into counts[planes][n_edges + 2] (device, 64-bit adds: the caller zeroes it) over the n_edges strictly increasing edges at
+// d_edges (device); class(v) = the edges that pass v as a threshold would, NaN = n_edges + 1.  labels == nullptr: one plane;
+// else labels[n] on the device and plane = (label of the row's slot != label of the column's slot)
+// cus: the compute units of the device (the residency bound of plan::hist_grid)
+hipError_t launch_hist(hipStream_t st, const float *vals, const ThrRows &g, const float *d_edges, uint32_t n_edges, const uint32_t *labels,
+                       int descending, uint32_t cus, uint64_t *counts);
+size_t hist_lds_bytes(uint32_t n_edges, int planes);  // LDS of a workgroup of k_hist
+
 // explicit pair lists (kernels_pairs.hip, pairs.hip): histograms are [cnt][64] counters, uint16 for p <= kPairsMaxP16
 // (a bin holds at most 2^p), uint32 above
 constexpr int kPairsMaxP16 = 15;
@@ -340,6 +349,7 @@ hipError_t launch_fastx_decode(hipStream_t st, const uint8_t *raw, const FastxCh
 
 // dsh_preload: load the code objects of the kernel translation units now (else: at the first launch from each)
 hipError_t preload_compare_kernels();
+hipError_t preload_hist_kernels();  // (part of the compare set)
 hipError_t preload_fastx_kernels();
 hipError_t preload_sketch_kernels();
 

@@ -49,6 +49,15 @@ bool greedy_old_band(const uint32_t *labels_in, uint64_t m, uint64_t ncols, uint
     return true;
 }
 
+uint64_t hist_grid(uint64_t units, uint64_t lds_bytes, uint32_t cus)
+{
+    const uint64_t per_cu = std::min<uint64_t>(std::max<uint64_t>(kHistLdsPerCu / std::max<uint64_t>(lds_bytes, 1), 1), kHistMaxPerCu);
+    const uint64_t resident = std::max<uint64_t>(cus, 1) * per_cu;
+    const uint64_t need = units / 4 + (units % 4 ? 1 : 0);                                    // a unit per wave
+    const uint64_t least = units / (4 * kHistMaxIters) + (units % (4 * kHistMaxIters) ? 1 : 0);  // at most kHistMaxIters trips
+    return std::max<uint64_t>(std::max<uint64_t>(std::min<uint64_t>(need, resident), least), 1);
+}
+
 void partition_rows(uint64_t n, uint32_t nparts, uint32_t align, uint64_t *bounds)
 {
     if (align == 0) align = 1;

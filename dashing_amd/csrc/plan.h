@@ -53,6 +53,18 @@ uint64_t rect_band_rows(uint64_t ncols, uint64_t band_floats);
 // and ends behind the LAST representative inside that window: a stretch without any is not computed.  Returns false when
 // no representative is left in [from, m); else [b0, b1), b0 < b1 <= m, labels_in[b0] == b0 and labels_in[b1 - 1] == b1 - 1.
 bool greedy_old_band(const uint32_t *labels_in, uint64_t m, uint64_t ncols, uint64_t from, uint64_t band_floats, uint64_t &b0, uint64_t &b1);
+// The grid of k_hist (kernels_hist.hip) over a band of `units` (row, chunk) units, four to a workgroup per trip.  A
+// workgroup zeroes and flushes lds_bytes of counters once per launch, so the grid is bounded by what the device holds at
+// once -- cus x min(max(kHistLdsPerCu / lds_bytes, 1), kHistMaxPerCu) workgroups, cus = the compute units of the device the
+// caller runs on -- and never larger than the units need.
+// It is RAISED above that bound where a workgroup would otherwise make more than kHistMaxIters trips: four waves x
+// kHistMaxIters units x kThrChunk values stay below 2^32, which is what keeps the 32-bit LDS counters from wrapping
+// whatever threshold_band_bytes makes of a band.  At least 1.
+constexpr uint64_t kHistMaxIters = (1u << 18) - 1;
+constexpr uint64_t kHistLdsPerCu = 160u << 10;  // LDS of a gfx950 compute unit
+constexpr uint64_t kHistMaxPerCu = 8;           // workgroups of 256 lanes a compute unit holds
+static_assert(4 * kHistMaxIters * kThrChunk < (1ull << 32), "a workgroup's share of a band must fit its 32-bit counters");
+uint64_t hist_grid(uint64_t units, uint64_t lds_bytes, uint32_t cus);
 
 // ---- row sets: a rank's rows as a range plus top-up tile rows --------------------------------------------------------
 // Contiguous row ranges on 128-row boundaries cannot give every rank the same number of tiles when the ranges are a

@@ -63,7 +63,7 @@ typedef struct dsh_ctx dsh_ctx;
  * dsh_dist_threshold, dsh_dist_threshold_device, dsh_dist_rect_threshold, dsh_dist_pairs*, dsh_fold*,
  * dsh_upload_sketches_folded*, dsh_union_groups*, dsh_cluster_threshold, dsh_cluster_threshold_device, dsh_cluster_pairs,
  * dsh_cluster_csr, dsh_greedy_threshold, dsh_greedy_threshold_device, dsh_greedy_extend, dsh_greedy_extend_device,
- * dsh_group_stats, dsh_group_stats_device. */
+ * dsh_group_stats, dsh_group_stats_device, dsh_dist_histogram, dsh_dist_histogram_device, dsh_dist_rect_histogram. */
 #define DSH_ABI_VERSION 7
 int dsh_abi_version(void);
 
@@ -569,6 +569,69 @@ int dsh_group_stats(dsh_ctx *ctx, int estim, int result_type, int k, const uint3
                     uint32_t *cnt_out, int64_t *sum_out, float *worst_out);
 int dsh_group_stats_device(dsh_ctx *ctx, int estim, int result_type, int k, const uint32_t *labels, void *d_medoid,
                            void *d_cnt, void *d_sum, void *d_worst);
+
+/* ---- value histograms of the triangle and of a rectangle: the distribution of the values, on the device -----
+ * Every selection above is driven by one number the caller must already know: the threshold.  This call is how to choose
+ * it: the values of a triangle or rectangle call are counted over up to DSH_HIST_MAX_EDGES caller-given bin edges in ONE
+ * dense pass, optionally split into the intra-group and inter-group pairs of a labelling, and only the counts --
+ * planes * (n_edges + 2) 64-bit integers -- leave the device.
+ *   Values counted.  Triangle forms: exactly the float32 values dsh_dist_rows writes for rows [row_begin, row_end),
+ *     columns j > i (row_end is cut at n); for the asymmetric measures the ONE orientation of the triangle.  Rectangle
+ *     form: exactly the values dsh_dist_rect writes, self pairs included where the ranges overlap.  Any result_type the
+ *     dense path takes.
+ *   Edges.  edges is a HOST float32 [n_edges] in all forms, 1 <= n_edges <= DSH_HIST_MAX_EDGES, strictly increasing under
+ *     float32 comparison, no NaN; -inf and +inf are legal; -0.0 followed by +0.0 is NOT increasing.
+ *   Classes.  There are n_edges + 2 of them, and the closed side of an edge is the side that passes as a threshold:
+ *     similarity forms: class(v) = the number of edges e with e <= v; the bins are [e_{b-1}, e_b)  (every measure that
+ *                       is no *_DIST form, DSH_SIZES included: what dsh_dist_threshold passes with v >= t);
+ *     *_DIST forms:     class(v) = the number of edges e with e <  v; the bins are (e_{b-1}, e_b];
+ *     NaN is class n_edges + 1 (which nothing else reaches); -0.0 and +0.0 are one value.
+ *     Consequence: for every b, the n_hits of dsh_dist_threshold over the same rows at threshold = edges[b] is, for the
+ *     similarity forms, the sum of the classes b + 1 .. n_edges, and for the *_DIST forms the sum of the classes 0 .. b.
+ *     One call therefore gives the exact hit counts at up to 4096 thresholds (e.g. the cap of dsh_dist_threshold_device).
+ *     The sum of all classes is the number of pairs of the call.
+ *   Labels.  labels is NULL, or a HOST uint32 [n] indexed by slot; any values are legal, only equality matters.
+ *     NULL: counts is [1][n_edges + 2].  Not NULL: counts is [2][n_edges + 2]; plane 0 holds the pairs whose two slots carry
+ *     equal labels (intra), plane 1 the others (inter).  In the rectangle the row is the query slot, the column the
+ *     reference slot; a self pair is intra.
+ *   Counts.  uint64, OVERWRITTEN (not added to); exactly planes * (n_edges + 2) entries are written.  d_counts is a
+ *     caller-owned DEVICE buffer, 8-byte aligned.  All accumulation is in integers: the result depends on no band size,
+ *     launch geometry or order of arrival of atomics, and the same call gives the same bytes.
+ *   Execution.  Synchronous, on the ctx stream: the band loop of dsh_dist_threshold ("threshold_band_bytes", at most 2^20
+ *     rows) with one launch of k_hist per band; no host wait between bands, one at the end.  k_hist keeps the edges and
+ *     32-bit counters in LDS (sized from n_edges), runs as a bounded grid whose waves stride over the band's 4096-value
+ *     chunks, finds a value's class by a binary search of at most 13 steps (none while a lane's values stay in one class),
+ *     counts the lanes of a wave that share a class with ONE LDS add, and flushes its non-zero counters once per launch with
+ *     64-bit atomic adds.  A workgroup's share of a band is kept below 2^32 values by the grid rule, whatever the band size.
+ *   Cached state.  Exactly the effects of dsh_dist_threshold / dsh_dist_rect_threshold over the same rows: a dense call
+ *     before and after gives the same bytes.
+ *   Errors, before anything is enqueued: DSH_EINVAL for a NULL context, n_edges == 0 or > DSH_HIST_MAX_EDGES, NULL edges or
+ *     a NULL output, edges not strictly increasing or NaN (the message names the index), rectangle slots beyond n, an
+ *     estimator or result_type out of range; DSH_ESTATE without sketches.  An empty range (row_begin >= row_end after the
+ *     cut, as the threshold forms judge it) or n < 2 succeeds with all-zero counts.  Out-of-range registers fail as the
+ *     dense path does, the counts unspecified.
+ *   Cost model: the dense path's cost for the same rows plus one read of each band, 4 bytes per pair, plus
+ *     4 more with labels: about 5 ms at 100 000 x p=10.  Measured on one MI355X (tools/bench_hist.py, profiles/hist1;
+ *     H = dsh_dist_histogram_device, A = dsh_dist_rows_device of the full triangle, MASH_DIST): at 100 000 x p=10
+ *     (A = 281 ms) H - A = 4.6 ms at 2 edges and 4.9 ms at 101 edges where ONE class holds every value (5.8 / 5.7 ms with
+ *     labels), 8.4 ms at 4096 (15 ms with labels); where half of the values are spread over the classes 12.6 ms at 2 edges,
+ *     22 ms at 101 (23 ms with labels), 46 ms at 4096 (60 ms with labels).  The one-class case is the cheapest; with
+ *     spread values the cost grows with the steps of the search, about 3 ms each.  At 20 000 x p=12 with continuous values
+ *     (A = 45.6 ms) H - A = 0.2 ms in one class, 0.9 ms evenly spread over 101 edges, 1.6 ms over 4096.  At 10 000 x p=14
+ *     (A = 12.7 ms) H - A is below 0.25 ms up to 101 edges, 0.4 ms (1.0 ms with labels) at 4096.
+ *   dsh_dist_histogram         triangle rows, counts in host memory.
+ *   dsh_dist_histogram_device  triangle rows, counts in the caller's device buffer.
+ *   dsh_dist_rect_histogram    query slots [q_begin, q_end) x reference slots [r_begin, r_end), counts in host memory.
+ *   Not built: a multi-GPU form (the caller adds the counts of row ranges); per-slot histograms; weighted members;
+ *     quantiles computed by the library (the cumulative sums of the counts give them to the resolution of the edges). */
+#define DSH_HIST_MAX_EDGES 4096
+int dsh_dist_histogram(dsh_ctx *ctx, int estim, int result_type, int k, uint64_t row_begin, uint64_t row_end,
+                       const float *edges, uint32_t n_edges, const uint32_t *labels, uint64_t *counts_out);
+int dsh_dist_histogram_device(dsh_ctx *ctx, int estim, int result_type, int k, uint64_t row_begin, uint64_t row_end,
+                              const float *edges, uint32_t n_edges, const uint32_t *labels, void *d_counts);
+int dsh_dist_rect_histogram(dsh_ctx *ctx, int estim, int result_type, int k, uint64_t q_begin, uint64_t q_end,
+                            uint64_t r_begin, uint64_t r_end, const float *edges, uint32_t n_edges,
+                            const uint32_t *labels, uint64_t *counts_out);
 
 /* ---- multi-GPU shards of the full triangle ------------------------------------------------
  * Every rank holds all sketches (dsh_upload/attach) and computes one shard; no collective is
