@@ -271,6 +271,15 @@ static std::vector<uint32_t> read_labels_binary(const char *flag, const std::str
     return labels;
 }
 
+// the FLOAT of --threshold / --cluster / --representatives: a whole token, no NaN
+static float float_option(const char *flag, const char *arg)
+{
+    char *end = nullptr;
+    const float v = std::strtof(arg, &end);
+    if (end == arg || *end || v != v) die("%s needs a number, got '%s'", flag, arg);
+    return v;
+}
+
 enum { OPT_PRESKETCHED = 1000, OPT_AVOID_SORT, OPT_DEVICE, OPT_NPERBATCH, OPT_NN, OPT_NGPUS, OPT_DEVICES, OPT_RCCL, OPT_THRESHOLD, OPT_CLUSTER, OPT_REPS, OPT_ASSIGN, OPT_EXTEND, OPT_STATS, OPT_HISTOGRAM, OPT_HISTOGRAM_LABELS, OPT_PAIRS, OPT_MEASURES, OPT_GROUPS, OPT_UNSUPPORTED };
 
 static Opts parse(int argc, char **argv, bool is_dist)
@@ -366,27 +375,9 @@ static Opts parse(int argc, char **argv, bool is_dist)
             if (std::atoi(optarg) <= 0) die("--nearest-neighbors needs a positive count");
             o.nneighbors = (unsigned)std::atoi(optarg);
             break;
-        case OPT_THRESHOLD: {
-            char *end = nullptr;
-            o.threshold = std::strtof(optarg, &end);
-            if (end == optarg || *end || o.threshold != o.threshold) die("--threshold needs a number, got '%s'", optarg);
-            o.has_threshold = true;
-            break;
-        }
-        case OPT_CLUSTER: {
-            char *end = nullptr;
-            o.cluster_t = std::strtof(optarg, &end);
-            if (end == optarg || *end || o.cluster_t != o.cluster_t) die("--cluster needs a number, got '%s'", optarg);
-            o.has_cluster = true;
-            break;
-        }
-        case OPT_REPS: {
-            char *end = nullptr;
-            o.reps_t = std::strtof(optarg, &end);
-            if (end == optarg || *end || o.reps_t != o.reps_t) die("--representatives needs a number, got '%s'", optarg);
-            o.has_reps = true;
-            break;
-        }
+        case OPT_THRESHOLD: o.threshold = float_option("--threshold", optarg), o.has_threshold = true; break;
+        case OPT_CLUSTER: o.cluster_t = float_option("--cluster", optarg), o.has_cluster = true; break;
+        case OPT_REPS: o.reps_t = float_option("--representatives", optarg), o.has_reps = true; break;
         case OPT_ASSIGN:
             if (!std::strcmp(optarg, "first")) o.assign_mode = DSH_GREEDY_FIRST;
             else if (!std::strcmp(optarg, "best")) o.assign_mode = DSH_GREEDY_BEST;
@@ -1103,30 +1094,74 @@ static int sketch_by_seq_main(int argc, char **argv)
     return EXIT_SUCCESS;
 }
 
-static int dist_main(int argc, char **argv, bool by_seq = false)
+// ---- dist / dist_by_seq: dist_main (at the end) is the sequence of the phases below -------------------------------
+static const char *const kMeasureNames[9] = {"MASH_DIST", "JI", "SIZES", "FULL_MASH_DIST", "FULL_CONTAINMENT_DIST", "CONTAINMENT_INDEX",
+                                             "CONTAINMENT_DIST", "SYMMETRIC_CONTAINMENT_INDEX", "SYMMETRIC_CONTAINMENT_DIST"};
+
+// the measures whose smaller value is the closer pair, so that --threshold's test is <=: !measure_descending of ctx.h
+static bool is_distance(int result_type)
 {
-    Opts o = parse(argc, argv, true);
+    return result_type == 0 || result_type == 3 || result_type == 4 || result_type == 6 || result_type == 8;
+}
+
+// DSH_BLOCK_VALS=N: the row blocks of the streamed triangle hold at most N values, not 256 Mi (no output depends on the cut:
+// the tests cross block edges with few inputs this way); anything but a positive integer is ignored
+static uint64_t block_vals_from_env()
+{
+    const char *s = std::getenv("DSH_BLOCK_VALS");
+    char *end = nullptr;
+    const unsigned long long v = (s && *s >= '0' && *s <= '9') ? std::strtoull(s, &end, 10) : 0;
+    return (v && !*end) ? (uint64_t)v : (uint64_t)256 << 20;
+}
+
+// what a run of `dist` / `dist_by_seq` carries from phase to phase
+struct DistRun {
+    Opts o;  // inpaths: the names of the collection in output order -- paths, record names, at last the group names
+    bool symmetric = true;
+    uint64_t block_vals = 0;    // cap of a row block (for_row_blocks)
+    Records R;                  // dist_by_seq: the records ...
+    std::vector<uint8_t> pre;   // ... or, with --presketched, the sketch_by_seq stream
+    std::vector<uint32_t> hist_labels, extend_labels;  // --histogram-labels, --extend
+    std::vector<std::pair<std::string, std::string>> pair_names;  // --pairs: the listed names, their slots, the measures
+    std::vector<uint32_t> lhs, rhs;
+    std::vector<int> pair_types;
+    std::vector<std::string> group_names;  // --groups: in order of first appearance, and the members of each as input slots
+    std::vector<uint64_t> group_ptr;
+    std::vector<uint32_t> group_members;
+    size_t n = 0, nq = 0;  // sketches in all; the last nq are the queries
+    dsh_ctx *ctx = nullptr;
+};
+
+// --measures LIST, or the one measure the other flags select
+static std::vector<int> parse_measures(const Opts &o)
+{
+    std::vector<int> types;
+    if (o.measures.empty()) types.push_back(o.result_type);
+    for (size_t b = 0; b <= o.measures.size() && !o.measures.empty();) {  // (an empty element, a trailing comma included, is no measure)
+        const size_t e = std::min(o.measures.find(',', b), o.measures.size());
+        const std::string name = o.measures.substr(b, e - b);
+        int t = 0;
+        while (t < 9 && name != kMeasureNames[t]) ++t;
+        if (t == 9) die("--measures: unknown measure '%s'", name.c_str());
+        types.push_back(t);
+        b = e + 1;
+    }
+    if (types.empty() || types.size() > 9) die("--measures takes one to nine names.");
+    return types;
+}
+
+// Phase 1, behind parse: every refusal the options alone decide, before a record, label, pair or group file is opened.  In this
+// order: a command line with several conflicts names the first of them.  (What needs a file's content is refused where the
+// file is read: label counts against n, p against -S, names that are no inputs.)
+static void refuse_conflicts(const Opts &o, bool by_seq)
+{
+    const bool with_pairs = !o.pairs_file.empty();
     if (by_seq && !o.groups_file.empty()) die("--groups does not go with dist_by_seq: the groups name input files.");
-    // dist_by_seq: the records (or a sketch_by_seq file) take the place of the genomes, their names that of the paths
-    Records R;
-    std::vector<uint8_t> pre;  // --presketched: the sketch_by_seq stream
     if (by_seq) {
         if (!o.querypaths.empty()) die("dist_by_seq does not take -Q: every record is compared with every other.");
         if (o.devices.size() > 1) die("dist_by_seq runs on one device: --ngpus / --devices are not supported.");
         if (o.cache) die("dist_by_seq does not take -W: records have no per-genome sketch files to cache.");
-        if (o.presketched) {
-            if (o.inpaths.size() != 1) die("dist_by_seq --presketched takes ONE sketch_by_seq file.");
-            int p = 0;
-            size_t cnt = 0;
-            if (read_hll_multi(o.inpaths[0], pre, p, cnt)) die("Could not read sketches from %s", o.inpaths[0].c_str());
-            if (p != o.S) die("Sketches in %s have p=%d but -S is %d", o.inpaths[0].c_str(), p, o.S);
-            R.names = read_labels_gz(o.inpaths[0] + ".labels.gz");
-            if (R.names.size() != cnt) die("%s holds %zu sketches but its labels %zu names", o.inpaths[0].c_str(), cnt, R.names.size());
-        } else {
-            read_records(o, R);
-        }
-        o.inpaths = R.names;
-        o.avoid_sorting = 1;
+        if (o.presketched && o.inpaths.size() != 1) die("dist_by_seq --presketched takes ONE sketch_by_seq file.");
     }
     if (o.has_threshold) {
         if (o.nneighbors) die("--threshold does not go with --nearest-neighbors: choose one selection.");
@@ -1137,7 +1172,7 @@ static int dist_main(int argc, char **argv, bool by_seq = false)
     if (o.has_cluster) {
         if (o.has_threshold) die("--cluster does not go with --threshold: choose the clusters or the pairs.");
         if (o.nneighbors) die("--cluster does not go with --nearest-neighbors: choose one selection.");
-        if (!o.pairs_file.empty()) die("--cluster does not go with --pairs: the clusters are those of all pairs.");
+        if (with_pairs) die("--cluster does not go with --pairs: the clusters are those of all pairs.");
         if (!o.querypaths.empty()) die("--cluster does not go with -Q: every input is clustered with every other.");
         if (o.fmt == UPPER_TRIANGULAR) die("--cluster does not go with -U: the output is one line per input.");
         if (o.fmt == FULL_TSV) die("--cluster does not go with -T: the output is one line per input.");
@@ -1147,7 +1182,7 @@ static int dist_main(int argc, char **argv, bool by_seq = false)
         if (o.has_cluster) die("--representatives does not go with --cluster: choose the representatives or the components.");
         if (o.has_threshold) die("--representatives does not go with --threshold: choose the representatives or the pairs.");
         if (o.nneighbors) die("--representatives does not go with --nearest-neighbors: choose one selection.");
-        if (!o.pairs_file.empty()) die("--representatives does not go with --pairs: the representatives are those of all pairs.");
+        if (with_pairs) die("--representatives does not go with --pairs: the representatives are those of all pairs.");
         if (!o.querypaths.empty()) die("--representatives does not go with -Q: every input is tested against every earlier one.");
         if (o.fmt == UPPER_TRIANGULAR) die("--representatives does not go with -U: the output is one line per input.");
         if (o.fmt == FULL_TSV) die("--representatives does not go with -T: the output is one line per input.");
@@ -1158,31 +1193,19 @@ static int dist_main(int argc, char **argv, bool by_seq = false)
         if (o.has_cluster) die("--histogram does not go with --cluster: choose the distribution or the clusters.");
         if (o.has_reps) die("--histogram does not go with --representatives: choose the distribution or the representatives.");
         if (o.nneighbors) die("--histogram does not go with --nearest-neighbors: choose one selection.");
-        if (!o.pairs_file.empty()) die("--histogram does not go with --pairs: the distribution is that of all pairs.");
+        if (with_pairs) die("--histogram does not go with --pairs: the distribution is that of all pairs.");
         if (o.fmt == UPPER_TRIANGULAR) die("--histogram does not go with -U: the output is one line per class.");
         if (o.fmt == FULL_TSV) die("--histogram does not go with -T: the output is one line per class.");
         if (o.devices.size() > 1 || o.rccl) die("--histogram runs on one device: --ngpus / --devices are not supported.");
     }
     if (!o.hist_labels_file.empty() && !o.has_hist) die("--histogram-labels goes with --histogram only.");
-    std::vector<uint32_t> hist_labels;
-    if (!o.hist_labels_file.empty()) hist_labels = read_labels_binary("--histogram-labels", o.hist_labels_file);
     if (o.has_assign && !o.has_reps) die("--assign goes with --representatives only.");
     if (o.has_stats && !o.has_cluster && !o.has_reps) die("--stats goes with --cluster or --representatives only.");
     if (o.has_stats && o.result_type == DSH_SIZES) die("--stats does not go with --sizes: set sizes have no mean or worst value inside a group.");
-    // --extend: u64 n_old, u64 n_reps, u32 labels[n_old], as --representatives -b wrote it for the first n_old inputs
-    std::vector<uint32_t> extend_labels;
     if (!o.extend_file.empty()) {
         if (!o.has_reps) die("--extend goes with --representatives only.");
         if (!o.avoid_sorting) die("--extend needs --avoid-sorting: sorting by size would interleave the old inputs and the new.");
-        extend_labels = read_labels_binary("--extend", o.extend_file);
-        if (o.groups_file.empty() && extend_labels.size() > o.inpaths.size())
-            die("--extend: %s labels %zu inputs but this run has only %zu", o.extend_file.c_str(), extend_labels.size(), o.inpaths.size());
     }
-    static const char *const kMeasureNames[9] = {"MASH_DIST", "JI", "SIZES", "FULL_MASH_DIST", "FULL_CONTAINMENT_DIST", "CONTAINMENT_INDEX",
-                                                 "CONTAINMENT_DIST", "SYMMETRIC_CONTAINMENT_INDEX", "SYMMETRIC_CONTAINMENT_DIST"};
-    const bool with_pairs = !o.pairs_file.empty();
-    std::vector<std::pair<std::string, std::string>> pair_names;
-    std::vector<int> pair_types;
     if (!o.measures.empty() && !with_pairs) die("--measures goes with --pairs only.");
     if (with_pairs) {
         if (!o.querypaths.empty()) die("--pairs does not go with -Q: the list names the pairs, from all inputs.");
@@ -1190,567 +1213,666 @@ static int dist_main(int argc, char **argv, bool by_seq = false)
         if (o.has_threshold) die("--pairs does not go with --threshold: choose one selection.");
         if (o.fmt == BINARY) die("--pairs does not go with -b: the output is one text line per pair.");
         if (o.devices.size() > 1) die("--pairs runs on one device: --ngpus / --devices are not supported.");
-        const long bad = read_pairs_file(o.pairs_file, pair_names);
-        if (bad < 0) die("Could not open %s", o.pairs_file.c_str());
-        if (bad > 0) die("%s, line %ld: a pair is two names separated by one tab.", o.pairs_file.c_str(), bad);
-        if (o.measures.empty()) pair_types.push_back(o.result_type);
-        for (size_t b = 0; b <= o.measures.size() && !o.measures.empty();) {  // (an empty element, a trailing comma included, is no measure)
-            const size_t e = std::min(o.measures.find(',', b), o.measures.size());
-            const std::string name = o.measures.substr(b, e - b);
-            int t = 0;
-            while (t < 9 && name != kMeasureNames[t]) ++t;
-            if (t == 9) die("--measures: unknown measure '%s'", name.c_str());
-            pair_types.push_back(t);
-            b = e + 1;
-        }
-        if (pair_types.empty() || pair_types.size() > 9) die("--measures takes one to nine names.");
     }
-    const bool with_groups = !o.groups_file.empty();
-    if (with_groups) {
+    if (!o.groups_file.empty()) {
         if (with_pairs) die("--groups does not go with --pairs: a pair list names inputs, not groups.");
         if (!o.querypaths.empty()) die("--groups does not go with -Q: every group is compared with every other.");
         if (o.devices.size() > 1 || o.rccl) die("--groups runs on one device: --ngpus / --devices are not supported.");
     }
-    std::FILE *ofp = stdout, *pairofp = stdout;
-    if (!o.out_sizes.empty() && !(ofp = std::fopen(o.out_sizes.c_str(), "w"))) die("Could not open file at %s for writing.", o.out_sizes.c_str());
-    if (!o.out_dists.empty() && !(pairofp = std::fopen(o.out_dists.c_str(), "wb"))) die("Could not open file at %s for writing.", o.out_dists.c_str());
-    // asymmetric measure without -Q: all references are also the queries (src/distmain.cpp:120-125)
+}
+
+// Phase 2 of dist_by_seq: the records, or a sketch_by_seq file, take the place of the genomes and their names that of the paths
+static void read_records_or_presketched(DistRun &r)
+{
+    Opts &o = r.o;
+    if (o.presketched) {
+        int p = 0;
+        size_t cnt = 0;
+        if (read_hll_multi(o.inpaths[0], r.pre, p, cnt)) die("Could not read sketches from %s", o.inpaths[0].c_str());
+        if (p != o.S) die("Sketches in %s have p=%d but -S is %d", o.inpaths[0].c_str(), p, o.S);
+        r.R.names = read_labels_gz(o.inpaths[0] + ".labels.gz");
+        if (r.R.names.size() != cnt) die("%s holds %zu sketches but its labels %zu names", o.inpaths[0].c_str(), cnt, r.R.names.size());
+    } else {
+        read_records(o, r.R);
+    }
+    o.inpaths = r.R.names;
+}
+
+// Phase 3: the files that options name, but for --groups' (parse_groups_file: its lines are checked against the inputs)
+static void read_option_files(DistRun &r)
+{
+    const Opts &o = r.o;
+    if (!o.hist_labels_file.empty()) r.hist_labels = read_labels_binary("--histogram-labels", o.hist_labels_file);
+    // --extend: u64 n_old, u64 n_reps, u32 labels[n_old], as --representatives -b wrote it for the first n_old inputs
+    if (!o.extend_file.empty()) {
+        r.extend_labels = read_labels_binary("--extend", o.extend_file);
+        if (o.groups_file.empty() && r.extend_labels.size() > o.inpaths.size())
+            die("--extend: %s labels %zu inputs but this run has only %zu", o.extend_file.c_str(), r.extend_labels.size(), o.inpaths.size());
+    }
+    if (!o.pairs_file.empty()) {
+        const long bad = read_pairs_file(o.pairs_file, r.pair_names);
+        if (bad < 0) die("Could not open %s", o.pairs_file.c_str());
+        if (bad > 0) die("%s, line %ld: a pair is two names separated by one tab.", o.pairs_file.c_str(), bad);
+    }
+}
+
+// Phase 4: output order, the queries behind the references (src/distmain.cpp:120-133)
+static void order_paths(DistRun &r)
+{
+    Opts &o = r.o;
+    // asymmetric measure without -Q: all references are also the queries
     // (--cluster, --representatives and --histogram take every pair once, in the triangle's orientation: no query/reference format
     // of their own making for them)
-    const bool symmetric = o.has_cluster || o.has_reps || o.has_hist || !(o.result_type == 4 || o.result_type == 5 || o.result_type == 6);  // src/dashing.h:389-399
-    if (o.querypaths.empty() && !symmetric && !with_pairs && !with_groups) {  // (a pair list names its own pairs, each in one orientation; the groups take their turn below)
+    r.symmetric = o.has_cluster || o.has_reps || o.has_hist || !(o.result_type == 4 || o.result_type == 5 || o.result_type == 6);  // src/dashing.h:389-399
+    if (o.querypaths.empty() && !r.symmetric && o.pairs_file.empty() && o.groups_file.empty()) {  // (a pair list names its own pairs, each in one orientation; the groups take their turn in union_groups)
         o.querypaths = o.inpaths;
         std::fprintf(stderr, "Note: No query files provided, but an asymmetric distance was requested. Switching to a query/reference format with all references as queries.\n");
     }
-    if (!o.presketched && !o.avoid_sorting) {  // src/distmain.cpp:126-129
+    if (!o.presketched && !o.avoid_sorting) {
         sort_paths_by_fsize(o.inpaths);
         sort_paths_by_fsize(o.querypaths);
     }
-    size_t nq = o.querypaths.size();
-    for (auto &q : o.querypaths) o.inpaths.push_back(q);  // queries follow the references (src/distmain.cpp:130-133)
-    size_t n = o.inpaths.size();
-    // --groups: group names in order of first appearance, and the members of each as input slots
-    std::vector<std::string> group_names;
-    std::vector<uint64_t> group_ptr;
-    std::vector<uint32_t> group_members;
-    if (with_groups) {
-        std::unordered_map<std::string, uint32_t> slot_of, group_of;
-        for (size_t i = n; i-- > 0;) slot_of[o.inpaths[i]] = (uint32_t)i;
-        if (slot_of.size() != n) die("--groups: an input is given twice.");
-        std::vector<uint32_t> gid(n, ~0u);
-        std::ifstream gf(o.groups_file);
-        if (!gf) die("Could not open %s", o.groups_file.c_str());
-        std::string line;
-        for (long ln = 1; std::getline(gf, line); ++ln) {
-            if (!line.empty() && line.back() == '\r') line.pop_back();
-            if (line.empty()) continue;
-            const size_t tab = line.find('\t');
-            if (tab == std::string::npos || tab == 0 || tab + 1 == line.size() || line.find('\t', tab + 1) != std::string::npos)
-                die("%s, line %ld: a line is a name and a group separated by one tab.", o.groups_file.c_str(), ln);
-            const std::string name = line.substr(0, tab), grp = line.substr(tab + 1);
-            const auto it = slot_of.find(name);
-            if (it == slot_of.end()) die("%s: '%s' is not one of the inputs.", o.groups_file.c_str(), name.c_str());
-            if (gid[it->second] != ~0u) die("%s: '%s' is named twice.", o.groups_file.c_str(), name.c_str());
-            const auto g = group_of.emplace(grp, (uint32_t)group_names.size());
-            if (g.second) group_names.push_back(grp);
-            gid[it->second] = g.first->second;
-        }
-        for (size_t i = 0; i < n; ++i)
-            if (gid[i] == ~0u) die("%s: the input '%s' has no group.", o.groups_file.c_str(), o.inpaths[i].c_str());
-        const size_t ng = group_names.size();
-        group_ptr.assign(ng + 1, 0);
-        for (size_t i = 0; i < n; ++i) ++group_ptr[gid[i] + 1];
-        for (size_t g = 0; g < ng; ++g) group_ptr[g + 1] += group_ptr[g];
-        group_members.resize(n);
-        std::vector<uint64_t> fill(group_ptr.begin(), group_ptr.end() - 1);
-        for (size_t i = 0; i < n; ++i) group_members[fill[gid[i]]++] = (uint32_t)i;
+    r.nq = o.querypaths.size();
+    for (auto &q : o.querypaths) o.inpaths.push_back(q);
+    r.n = o.inpaths.size();
+}
+
+// Phase 5: names to slots, before anything is sketched (a name given twice: its first slot)
+static std::unordered_map<std::string, uint32_t> slots_by_name(const std::vector<std::string> &names)
+{
+    std::unordered_map<std::string, uint32_t> slot_of;
+    for (size_t i = names.size(); i-- > 0;) slot_of[names[i]] = (uint32_t)i;
+    return slot_of;
+}
+
+// --groups FILE: name<TAB>group per line, every input exactly once
+static void parse_groups_file(DistRun &r)
+{
+    const Opts &o = r.o;
+    const size_t n = r.n;
+    const auto slot_of = slots_by_name(o.inpaths);
+    std::unordered_map<std::string, uint32_t> group_of;
+    if (slot_of.size() != n) die("--groups: an input is given twice.");
+    std::vector<uint32_t> gid(n, ~0u);
+    std::ifstream gf(o.groups_file);
+    if (!gf) die("Could not open %s", o.groups_file.c_str());
+    std::string line;
+    for (long ln = 1; std::getline(gf, line); ++ln) {
+        if (!line.empty() && line.back() == '\r') line.pop_back();
+        if (line.empty()) continue;
+        const size_t tab = line.find('\t');
+        if (tab == std::string::npos || tab == 0 || tab + 1 == line.size() || line.find('\t', tab + 1) != std::string::npos)
+            die("%s, line %ld: a line is a name and a group separated by one tab.", o.groups_file.c_str(), ln);
+        const std::string name = line.substr(0, tab), grp = line.substr(tab + 1);
+        const auto it = slot_of.find(name);
+        if (it == slot_of.end()) die("%s: '%s' is not one of the inputs.", o.groups_file.c_str(), name.c_str());
+        if (gid[it->second] != ~0u) die("%s: '%s' is named twice.", o.groups_file.c_str(), name.c_str());
+        const auto g = group_of.emplace(grp, (uint32_t)r.group_names.size());
+        if (g.second) r.group_names.push_back(grp);
+        gid[it->second] = g.first->second;
     }
-    std::vector<uint32_t> lhs, rhs;  // --pairs: the slots of the listed names, looked up before anything is sketched
-    if (with_pairs) {
-        std::unordered_map<std::string, uint32_t> slot_of;
-        for (size_t i = n; i-- > 0;) slot_of[o.inpaths[i]] = (uint32_t)i;  // (a name given twice: its first slot)
-        lhs.resize(pair_names.size());
-        rhs.resize(pair_names.size());
-        for (size_t x = 0; x < pair_names.size(); ++x) {
-            const auto a = slot_of.find(pair_names[x].first), b = slot_of.find(pair_names[x].second);
-            if (a == slot_of.end()) die("%s: '%s' is not one of the inputs.", o.pairs_file.c_str(), pair_names[x].first.c_str());
-            if (b == slot_of.end()) die("%s: '%s' is not one of the inputs.", o.pairs_file.c_str(), pair_names[x].second.c_str());
-            lhs[x] = a->second, rhs[x] = b->second;
-        }
+    for (size_t i = 0; i < n; ++i)
+        if (gid[i] == ~0u) die("%s: the input '%s' has no group.", o.groups_file.c_str(), o.inpaths[i].c_str());
+    const size_t ng = r.group_names.size();
+    r.group_ptr.assign(ng + 1, 0);
+    for (size_t i = 0; i < n; ++i) ++r.group_ptr[gid[i] + 1];
+    for (size_t g = 0; g < ng; ++g) r.group_ptr[g + 1] += r.group_ptr[g];
+    r.group_members.resize(n);
+    std::vector<uint64_t> fill(r.group_ptr.begin(), r.group_ptr.end() - 1);
+    for (size_t i = 0; i < n; ++i) r.group_members[fill[gid[i]]++] = (uint32_t)i;
+}
+
+// --pairs: the slots of the listed names
+static void look_up_pairs(DistRun &r)
+{
+    const Opts &o = r.o;
+    const auto slot_of = slots_by_name(o.inpaths);
+    r.lhs.resize(r.pair_names.size());
+    r.rhs.resize(r.pair_names.size());
+    for (size_t x = 0; x < r.pair_names.size(); ++x) {
+        const auto a = slot_of.find(r.pair_names[x].first), b = slot_of.find(r.pair_names[x].second);
+        if (a == slot_of.end()) die("%s: '%s' is not one of the inputs.", o.pairs_file.c_str(), r.pair_names[x].first.c_str());
+        if (b == slot_of.end()) die("%s: '%s' is not one of the inputs.", o.pairs_file.c_str(), r.pair_names[x].second.c_str());
+        r.lhs[x] = a->second, r.rhs[x] = b->second;
     }
-    const double t_start = now_s();
-    since_launch("dist: options parsed, context thread about to start");
-    CtxFuture cf(o.device, n, o.S, (o.presketched || by_seq) ? 0 : staging_bytes_for(o.inpaths));  // the HIP runtime comes up while the first batch is read
-    dsh_ctx *ctx = nullptr;
-    const double t_fill0 = now_s();
-    if (by_seq) {  // the records into [0, nr) and, as queries of an asymmetric measure, once more into [nr, n)
-        ctx = cf.get();
-        const size_t nrec = R.names.size();
-        for (size_t s0 = 0; s0 < n; s0 += nrec) {
-            if (o.presketched) DSH(ctx, dsh_upload_sketches(ctx, pre.data(), s0, nrec));
-            else sketch_records_batched(ctx, R, s0, o.k, o.canon);
-        }
-    } else if (o.presketched) {  // sketch.read(path), src/sketch_and_cmp.h:318-324
-        ctx = cf.get();
-        // read on all host threads into a staging matrix, upload in batches
-        const size_t m = (size_t)1 << o.S, batch = std::max<size_t>(1, ((size_t)256 << 20) / m);
-        std::vector<uint8_t> stage(std::min(n, batch) * m);
-        // a file sketched at a higher precision than -S is folded on the device (dsh_upload_sketches_folded): its
-        // registers wait here until the batch is read, then go run by run of equal p.  At most 256 MiB of them are held: a
-        // batch ends before the file that would exceed that
-        std::vector<std::vector<uint8_t>> hi(std::min(n, batch));
-        std::vector<int> hi_p(std::min(n, batch));
-        std::vector<uint8_t> run;
-        for (size_t b0 = 0, b1; b0 < n; b0 = b1) {
-            b1 = std::min(n, b0 + batch);
-            std::atomic<size_t> held{0};
-            std::atomic<int64_t> cut{(int64_t)b1};
+}
+
+// Phase 6, loader 1 of 3 (the third is fill_sketches): the records into [0, nr) and, as queries of an asymmetric measure,
+// once more into [nr, n)
+static void load_records(dsh_ctx *ctx, const DistRun &r)
+{
+    const Opts &o = r.o;
+    const size_t nrec = r.R.names.size();
+    for (size_t s0 = 0; s0 < r.n; s0 += nrec) {
+        if (o.presketched) DSH(ctx, dsh_upload_sketches(ctx, r.pre.data(), s0, nrec));
+        else sketch_records_batched(ctx, r.R, s0, o.k, o.canon);
+    }
+}
+
+// Loader 2: .hll files (sketch.read(path), src/sketch_and_cmp.h:318-324), read on all host threads into a staging matrix,
+// uploaded in batches
+static void load_hll_files(dsh_ctx *ctx, const Opts &o, size_t n)
+{
+    const size_t m = (size_t)1 << o.S, batch = std::max<size_t>(1, ((size_t)256 << 20) / m);
+    std::vector<uint8_t> stage(std::min(n, batch) * m);
+    // a file sketched at a higher precision than -S is folded on the device (dsh_upload_sketches_folded): its
+    // registers wait here until the batch is read, then go run by run of equal p.  At most 256 MiB of them are held: a
+    // batch ends before the file that would exceed that
+    std::vector<std::vector<uint8_t>> hi(std::min(n, batch));
+    std::vector<int> hi_p(std::min(n, batch));
+    std::vector<uint8_t> run;
+    for (size_t b0 = 0, b1; b0 < n; b0 = b1) {
+        b1 = std::min(n, b0 + batch);
+        std::atomic<size_t> held{0};
+        std::atomic<int64_t> cut{(int64_t)b1};
 #pragma omp parallel for schedule(dynamic, 16) num_threads(o.nthreads)
-            for (int64_t i = (int64_t)b0; i < (int64_t)b1; ++i) {
-                if (i >= cut.load()) continue;  // behind a file that did not fit: the next batch
-                int p = 0;
-                std::vector<uint8_t> r;
-                if (read_hll(o.inpaths[i], r, p)) die("Could not read sketch %s", o.inpaths[i].c_str());
-                if (p < o.S) die("Sketch %s has p=%d but -S is %d", o.inpaths[i].c_str(), p, o.S);
-                hi_p[i - b0] = p;
-                if (p == o.S) {
-                    std::memcpy(stage.data() + (size_t)(i - (int64_t)b0) * m, r.data(), m);
-                } else if (held.fetch_add(r.size()) + r.size() > ((size_t)256 << 20) && i > (int64_t)b0) {
-                    for (int64_t c = cut.load(); i < c && !cut.compare_exchange_weak(c, i);) {}
-                } else {
-                    hi[i - b0].swap(r);
-                }
+        for (int64_t i = (int64_t)b0; i < (int64_t)b1; ++i) {
+            if (i >= cut.load()) continue;  // behind a file that did not fit: the next batch
+            int p = 0;
+            std::vector<uint8_t> r;
+            if (read_hll(o.inpaths[i], r, p)) die("Could not read sketch %s", o.inpaths[i].c_str());
+            if (p < o.S) die("Sketch %s has p=%d but -S is %d", o.inpaths[i].c_str(), p, o.S);
+            hi_p[i - b0] = p;
+            if (p == o.S) {
+                std::memcpy(stage.data() + (size_t)(i - (int64_t)b0) * m, r.data(), m);
+            } else if (held.fetch_add(r.size()) + r.size() > ((size_t)256 << 20) && i > (int64_t)b0) {
+                for (int64_t c = cut.load(); i < c && !cut.compare_exchange_weak(c, i);) {}
+            } else {
+                hi[i - b0].swap(r);
             }
-            b1 = (size_t)cut.load();
-            for (size_t i = b0; i < b1;) {
-                const int p = hi_p[i - b0];
-                const size_t mp = (size_t)1 << p, cap = std::max<size_t>(1, ((size_t)256 << 20) / mp);
-                size_t j = i + 1;
-                while (j < b1 && hi_p[j - b0] == p && j - i < cap) ++j;
-                if (p == o.S) {
-                    DSH(ctx, dsh_upload_sketches(ctx, stage.data() + (i - b0) * m, i, j - i));
-                } else {
-                    run.resize((j - i) * mp);
-                    for (size_t x = i; x < j; ++x) std::memcpy(run.data() + (x - i) * mp, hi[x - b0].data(), mp);
-                    DSH(ctx, dsh_upload_sketches_folded(ctx, run.data(), p, i, j - i));
-                }
-                i = j;
-            }
-            for (auto &h : hi) std::vector<uint8_t>().swap(h);
         }
-    } else {
-        fill_sketches(cf, o, /*write_files=*/o.cache != 0, false);
-        ctx = cf.get();
-    }
-    if (g_timing) std::fprintf(stderr, "[timing] all sketches resident after %.3f s\n", now_s() - t_fill0);
-    if (with_groups) {
-        // the unions go into a device buffer that a second context takes as its sketch matrix; from here on the groups
-        // are the collection.  An asymmetric measure wants every reference once more as a query: the groups twice
-        const size_t ng = group_names.size(), copies = symmetric ? 1 : 2;
-        if (!symmetric) {
-            std::fprintf(stderr, "Note: No query files provided, but an asymmetric distance was requested. Switching to a query/reference format with all references as queries.\n");
-            const std::vector<uint32_t> once(group_members);
-            for (size_t g = 0; g < ng; ++g) {
-                group_names.push_back(group_names[g]);
-                group_ptr.push_back(group_ptr.back() + (group_ptr[g + 1] - group_ptr[g]));
-                group_members.insert(group_members.end(), once.begin() + (long)group_ptr[g], once.begin() + (long)group_ptr[g + 1]);
+        b1 = (size_t)cut.load();
+        for (size_t i = b0; i < b1;) {
+            const int p = hi_p[i - b0];
+            const size_t mp = (size_t)1 << p, cap = std::max<size_t>(1, ((size_t)256 << 20) / mp);
+            size_t j = i + 1;
+            while (j < b1 && hi_p[j - b0] == p && j - i < cap) ++j;
+            if (p == o.S) {
+                DSH(ctx, dsh_upload_sketches(ctx, stage.data() + (i - b0) * m, i, j - i));
+            } else {
+                run.resize((j - i) * mp);
+                for (size_t x = i; x < j; ++x) std::memcpy(run.data() + (x - i) * mp, hi[x - b0].data(), mp);
+                DSH(ctx, dsh_upload_sketches_folded(ctx, run.data(), p, i, j - i));
             }
-            nq = ng;
+            i = j;
         }
-        void *d_union = nullptr;
-        if (hipSetDevice(o.device) != hipSuccess || hipMalloc(&d_union, std::max<size_t>((copies * ng) << o.S, 256)) != hipSuccess)
-            die("[dashing-amd] no device memory for the unions of %zu groups", ng);
-        DSH(ctx, dsh_union_groups_device(ctx, group_ptr.data(), group_members.data(), copies * ng, d_union));
-        dsh_ctx *gctx = nullptr;
-        if (int rc = dsh_create(o.device, &gctx)) die("[dashing-amd] dsh_create(device %d) = %d", o.device, rc);
-        DSH(gctx, dsh_attach_device_sketches(gctx, d_union, copies * ng, o.S));
-        dsh_destroy(ctx);
-        ctx = gctx;  // (the buffer lives as long as the process)
-        o.inpaths = group_names;
-        n = copies * ng;
+        for (auto &h : hi) std::vector<uint8_t>().swap(h);
     }
-    // sizes (src/sketch_and_cmp.h:372-385)
-    std::vector<double> card(std::max<size_t>(n, 1));
-    DSH(ctx, dsh_cardinalities(ctx, o.estim, card.data()));
-    emit_sizes(ofp, o.inpaths, card.data());
+}
+
+// Phase 7, --groups: the unions go into a device buffer that a second context takes as its sketch matrix; from here on the
+// groups are the collection.  An asymmetric measure wants every reference once more as a query: the groups twice
+static void union_groups(DistRun &r)
+{
+    Opts &o = r.o;
+    const size_t ng = r.group_names.size(), copies = r.symmetric ? 1 : 2;
+    if (!r.symmetric) {
+        std::fprintf(stderr, "Note: No query files provided, but an asymmetric distance was requested. Switching to a query/reference format with all references as queries.\n");
+        const std::vector<uint32_t> once(r.group_members);
+        for (size_t g = 0; g < ng; ++g) {
+            r.group_names.push_back(r.group_names[g]);
+            r.group_ptr.push_back(r.group_ptr.back() + (r.group_ptr[g + 1] - r.group_ptr[g]));
+            r.group_members.insert(r.group_members.end(), once.begin() + (long)r.group_ptr[g], once.begin() + (long)r.group_ptr[g + 1]);
+        }
+        r.nq = ng;
+    }
+    void *d_union = nullptr;
+    if (hipSetDevice(o.device) != hipSuccess || hipMalloc(&d_union, std::max<size_t>((copies * ng) << o.S, 256)) != hipSuccess)
+        die("[dashing-amd] no device memory for the unions of %zu groups", ng);
+    DSH(r.ctx, dsh_union_groups_device(r.ctx, r.group_ptr.data(), r.group_members.data(), copies * ng, d_union));
+    dsh_ctx *gctx = nullptr;
+    if (int rc = dsh_create(o.device, &gctx)) die("[dashing-amd] dsh_create(device %d) = %d", o.device, rc);
+    DSH(gctx, dsh_attach_device_sketches(gctx, d_union, copies * ng, o.S));
+    dsh_destroy(r.ctx);
+    r.ctx = gctx;  // (the buffer lives as long as the process)
+    o.inpaths = r.group_names;
+    r.n = copies * ng;
+}
+
+// Phase 8: sizes (src/sketch_and_cmp.h:372-385)
+static void write_sizes(const DistRun &r, std::FILE *ofp)
+{
+    std::vector<double> card(std::max<size_t>(r.n, 1));
+    DSH(r.ctx, dsh_cardinalities(r.ctx, r.o.estim, card.data()));
+    emit_sizes(ofp, r.o.inpaths, card.data());
     if (ofp != stdout) std::fclose(ofp);
-    // distances (dist_loop, src/sketch_and_cmp.h:785-880)
-    const uint64_t total = n ? (uint64_t)n * (n - 1) / 2 : 0;
-    if (with_pairs) {  // only the listed pairs (dsh_dist_pairs): the first name is lhs, the second rhs of result_cmp
-        const size_t np = pair_names.size(), nt = pair_types.size();
-        std::vector<float> vals(std::max<size_t>(np * nt, 1));
-        DSH(ctx, dsh_dist_pairs(ctx, o.estim, pair_types.data(), (uint32_t)nt, o.k, lhs.data(), rhs.data(), np, vals.data()));
+}
+
+// ---- Phase 9: one emitter per selection, each given the run (context, options, names = o.inpaths, n, nq) and the output file
+static void check_query_count(size_t n, size_t nq)
+{
+    if (nq >= n && nq) die("Wrong number of query/references. (ip size: %zu, nq: %zu", n, nq);
+}
+
+static uint64_t tri_total(size_t n)
+{
+    return n ? (uint64_t)n * (n - 1) / 2 : 0;
+}
+
+// The rows [r0, r1) of the n-sketch triangle in blocks of at most block_vals values (a block is at least one row), each handed
+// to sink(first row, end row, values, span) in order.  Two page-locked ping-pong buffers, asynchronous C-ABI calls: block b+1 is
+// enqueued (compute + copy into its buffer, which the sink left in the previous iteration) and its ticket recorded before block b
+// is awaited, so the GPU works while the sink formats / writes -- dist_loop's dps[i & 1] scheme (src/sketch_and_cmp.h:804-816)
+// without the writer thread.  Blocks are large by default (256 Mi values) so that each one is a row range the library lays its
+// plane matrix out for (few planes per tile, values at their final positions).
+template <class Sink>
+static void for_row_blocks(dsh_ctx *ctx, const Opts &o, uint64_t n, uint64_t r0, uint64_t r1, uint64_t block_vals, Sink sink)
+{
+    std::vector<uint64_t> cuts{r0};
+    while (cuts.back() < r1) {
+        const uint64_t rb = cuts.back();
+        uint64_t re = rb + 1;
+        while (re < r1 && dsh_tri_span(n, rb, re + 1) <= block_vals) ++re;
+        cuts.push_back(re);
+    }
+    uint64_t cap = 1;
+    for (size_t b = 0; b + 1 < cuts.size(); ++b) cap = std::max<uint64_t>(cap, dsh_tri_span(n, cuts[b], cuts[b + 1]));
+    float *bufs[2] = {nullptr, nullptr};
+    for (int w = 0; w < (cuts.size() > 2 ? 2 : 1); ++w)
+        if (!(bufs[w] = (float *)dsh_alloc_host(cap * sizeof(float)))) die("could not allocate %llu bytes of pinned host memory", (unsigned long long)(cap * sizeof(float)));
+    const size_t nblocks = cuts.size() - 1;
+    if (g_timing)
+        std::fprintf(stderr, "[timing] rows [%llu, %llu): %zu blocks of at most %llu values, %d buffers\n", (unsigned long long)r0, (unsigned long long)r1, nblocks,
+                     (unsigned long long)block_vals, bufs[1] ? 2 : 1);
+    std::vector<uint64_t> ticket(nblocks + 1, 0);
+    auto enqueue = [&](size_t b) {
+        DSH(ctx, dsh_dist_rows_async(ctx, o.estim, o.result_type, o.k, cuts[b], cuts[b + 1], bufs[b & 1]));
+        DSH(ctx, dsh_event_record(ctx, &ticket[b]));
+    };
+    if (nblocks) enqueue(0);
+    for (size_t b = 0; b < nblocks; ++b) {
+        if (b + 1 < nblocks) enqueue(b + 1);  // its kernels fill the library's other device buffer while block b is still copied out
+        DSH(ctx, dsh_event_wait(ctx, ticket[b]));  // block b has arrived in bufs[b & 1]
+        sink(cuts[b], cuts[b + 1], (const float *)bufs[b & 1], dsh_tri_span(n, cuts[b], cuts[b + 1]));
+    }
+    for (auto &b : bufs) dsh_free_host(b);
+}
+
+// a context on device `device` that holds the n sketches `all` was downloaded as: what a further device of a multi-device run
+// computes its rows from
+static dsh_ctx *secondary_context(int device, const std::vector<uint8_t> &all, size_t n, int S)
+{
+    dsh_ctx *c = nullptr;
+    if (int rc = dsh_create(device, &c)) die("[dashing-amd] dsh_create(device %d) = %d", device, rc);
+    DSH(c, dsh_sketches_alloc(c, n, S));
+    DSH(c, dsh_upload_sketches(c, all.data(), 0, n));
+    return c;
+}
+
+// --pairs: only the listed pairs (dsh_dist_pairs): the first name is lhs, the second rhs of result_cmp
+static void emit_pairs(const DistRun &r, std::FILE *fp)
+{
+    const Opts &o = r.o;
+    const size_t np = r.pair_names.size(), nt = r.pair_types.size();
+    std::vector<float> vals(std::max<size_t>(np * nt, 1));
+    DSH(r.ctx, dsh_dist_pairs(r.ctx, o.estim, r.pair_types.data(), (uint32_t)nt, o.k, r.lhs.data(), r.rhs.data(), np, vals.data()));
+    std::string s;
+    char num[64];
+    for (size_t x = 0; x < np; ++x) {
+        s = r.pair_names[x].first;
+        s += '\t';
+        s += r.pair_names[x].second;
+        for (size_t t = 0; t < nt; ++t) s.append(num, (size_t)std::snprintf(num, sizeof num, "\t%.6g", (double)vals[t * np + x]));  // --threshold's number format
+        s += '\n';
+        std::fwrite(s.data(), 1, s.size(), fp);
+    }
+}
+
+// --cluster: the connected components of the pairs that pass (dsh_cluster_threshold); --representatives: the greedy pass in
+// output order (dsh_greedy_threshold / dsh_greedy_extend).  No pair leaves the device.  One layout for both: the header word and
+// the count differ, and --representatives' text has the value column
+static void emit_labelling(const DistRun &r, std::FILE *fp)
+{
+    const Opts &o = r.o;
+    const size_t n = r.n;
+    const std::vector<std::string> &names = o.inpaths;
+    const bool reps = o.has_reps;
+    const float t = reps ? o.reps_t : o.cluster_t;
+    std::vector<uint32_t> labels(std::max<size_t>(n, 1));
+    uint64_t count = 0;
+    if (!reps) {
+        DSH(r.ctx, dsh_cluster_threshold(r.ctx, o.estim, o.result_type, o.k, t, labels.data(), &count));
+    } else {
+        if (r.extend_labels.size() > n) die("--extend: %s labels %zu inputs but this run has only %zu", o.extend_file.c_str(), r.extend_labels.size(), n);
+        if (o.has_assign || !o.extend_file.empty())
+            DSH(r.ctx, dsh_greedy_extend(r.ctx, o.estim, o.result_type, o.k, t, o.assign_mode, r.extend_labels.size(),
+                                         r.extend_labels.empty() ? nullptr : r.extend_labels.data(), labels.data(), &count));
+        else
+            DSH(r.ctx, dsh_greedy_threshold(r.ctx, o.estim, o.result_type, o.k, t, labels.data(), &count));
+    }
+    GroupStats gs;
+    if (o.has_stats) gs.compute(r.ctx, o, labels, n);
+    if (o.fmt == BINARY) {
+        const uint64_t hdr[2] = {(uint64_t)n, count};
+        if (std::fwrite(hdr, sizeof(uint64_t), 2, fp) != 2 || std::fwrite(labels.data(), sizeof(uint32_t), n, fp) != n) die("Error writing to binary file");
+        if (o.has_stats) gs.write_binary(fp, n);
+        return;
+    }
+    std::fprintf(fp, "#%s\t%s\t%s\t%.6g\n", reps ? "Representatives" : "Cluster", kMeasureNames[o.result_type], is_distance(o.result_type) ? "<=" : ">=",
+                 (double)t);  // --threshold's number format
+    // --representatives: the value of every non-representative against its label: ONE list of pairs (lhs = the input, rhs =
+    // its representative), by dsh_dist_pairs' contract bit for bit the triangle's value
+    std::vector<uint32_t> plhs, prhs;
+    for (size_t x = 0; reps && x < n; ++x)
+        if (labels[x] != x) plhs.push_back((uint32_t)x), prhs.push_back(labels[x]);
+    std::vector<float> pv(std::max<size_t>(plhs.size(), 1));
+    const int type = o.result_type;
+    if (!plhs.empty()) DSH(r.ctx, dsh_dist_pairs(r.ctx, o.estim, &type, 1, o.k, plhs.data(), prhs.data(), plhs.size(), pv.data()));
+    // clusters are numbered by ascending representative: a label is its cluster's first member (a representative comes
+    // before its members), so the numbers are handed out in one pass
+    std::vector<uint32_t> index(std::max<size_t>(n, 1));
+    uint32_t next = 0;
+    size_t at = 0;
+    std::string s;
+    char num[64];
+    for (size_t x = 0; x < n; ++x) {
+        if (labels[x] == x) index[x] = next++;
+        s = names[x];
+        s.append(num, (size_t)std::snprintf(num, sizeof num, "\t%u\t", index[labels[x]]));
+        s += names[labels[x]];
+        if (reps && labels[x] == x) s += "\t-";
+        else if (reps) s.append(num, (size_t)std::snprintf(num, sizeof num, "\t%.6g", (double)pv[at++]));
+        if (o.has_stats) gs.append_fields(s, x, names);
+        s += '\n';
+        std::fwrite(s.data(), 1, s.size(), fp);
+    }
+}
+
+// --histogram: the distribution of the values (dsh_dist_histogram / dsh_dist_rect_histogram): only counts leave the device
+static void emit_histogram(const DistRun &r, std::FILE *fp)
+{
+    const Opts &o = r.o;
+    const size_t n = r.n, nq = r.nq;
+    check_query_count(n, nq);
+    const bool split = !o.hist_labels_file.empty();
+    if (split && r.hist_labels.size() != n)
+        die("--histogram-labels: %s labels %zu inputs but this run has %zu", o.hist_labels_file.c_str(), r.hist_labels.size(), n);
+    const size_t ne = o.hist_edges.size(), nclass = ne + 2, planes = split ? 2 : 1;
+    const uint32_t *lab = split ? r.hist_labels.data() : nullptr;
+    std::vector<uint64_t> counts(planes * nclass);
+    if (nq) DSH(r.ctx, dsh_dist_rect_histogram(r.ctx, o.estim, o.result_type, o.k, n - nq, n, 0, n - nq, o.hist_edges.data(), (uint32_t)ne, lab, counts.data()));
+    else DSH(r.ctx, dsh_dist_histogram(r.ctx, o.estim, o.result_type, o.k, 0, n, o.hist_edges.data(), (uint32_t)ne, lab, counts.data()));
+    if (o.fmt == BINARY) {
+        const uint64_t hdr[2] = {(uint64_t)ne, (uint64_t)planes};
+        const float pad = 0.f;
+        if (std::fwrite(hdr, sizeof(uint64_t), 2, fp) != 2 || std::fwrite(o.hist_edges.data(), sizeof(float), ne, fp) != ne ||
+            ((ne & 1) && std::fwrite(&pad, sizeof(float), 1, fp) != 1) ||
+            std::fwrite(counts.data(), sizeof(uint64_t), counts.size(), fp) != counts.size())
+            die("Error writing to binary file");
+        return;
+    }
+    std::fprintf(fp, "#Histogram\t%s\t%s\n", kMeasureNames[o.result_type], is_distance(o.result_type) ? "<=" : ">=");
+    const double inf = std::numeric_limits<double>::infinity(), nan = std::numeric_limits<double>::quiet_NaN();
+    for (size_t b = 0; b < nclass; ++b) {  // --threshold's number format
+        const double lo = b == ne + 1 ? nan : (b == 0 ? -inf : (double)o.hist_edges[b - 1]);
+        const double hi = b == ne + 1 ? nan : (b == ne ? inf : (double)o.hist_edges[b]);
+        std::fprintf(fp, "%.6g\t%.6g\t%llu", lo, hi, (unsigned long long)counts[b]);
+        if (split) std::fprintf(fp, "\t%llu", (unsigned long long)counts[nclass + b]);
+        std::fputc('\n', fp);
+    }
+}
+
+// --threshold: only the pairs that pass (dsh_dist_threshold / dsh_dist_rect_threshold): no dense matrix
+static void emit_threshold(const DistRun &r, std::FILE *fp)
+{
+    const Opts &o = r.o;
+    const size_t n = r.n, nq = r.nq;
+    const std::vector<std::string> &names = o.inpaths;
+    check_query_count(n, nq);
+    const size_t nr = n - nq, rows = nq ? nq : n;
+    std::vector<uint64_t> row_ptr(rows + 1);
+    uint32_t *col = nullptr;
+    float *val = nullptr;
+    uint64_t nnz = 0;
+    if (nq) DSH(r.ctx, dsh_dist_rect_threshold(r.ctx, o.estim, o.result_type, o.k, nr, n, 0, nr, o.threshold, row_ptr.data(), &col, &val, &nnz));
+    else DSH(r.ctx, dsh_dist_threshold(r.ctx, o.estim, o.result_type, o.k, 0, n, o.threshold, row_ptr.data(), &col, &val, &nnz));
+    if (o.fmt == BINARY) {
+        const uint64_t hdr[2] = {(uint64_t)rows, nnz};
+        if (std::fwrite(hdr, sizeof(uint64_t), 2, fp) != 2 || std::fwrite(row_ptr.data(), sizeof(uint64_t), rows + 1, fp) != rows + 1 ||
+            std::fwrite(col, sizeof(uint32_t), nnz, fp) != nnz || std::fwrite(val, sizeof(float), nnz, fp) != nnz)
+            die("Error writing to binary file");
+    } else {
+        std::fprintf(fp, "#Threshold\t%s\t%s\t%.6g\n", kMeasureNames[o.result_type], is_distance(o.result_type) ? "<=" : ">=", (double)o.threshold);
         std::string s;
         char num[64];
-        for (size_t x = 0; x < np; ++x) {
-            s = pair_names[x].first;
-            s += '\t';
-            s += pair_names[x].second;
-            for (size_t t = 0; t < nt; ++t) s.append(num, (size_t)std::snprintf(num, sizeof num, "\t%.6g", (double)vals[t * np + x]));  // --threshold's number format
-            s += '\n';
-            std::fwrite(s.data(), 1, s.size(), pairofp);
-        }
-    } else if (o.has_cluster) {  // the connected components of the pairs that pass (dsh_cluster_threshold): no pair leaves the device
-        std::vector<uint32_t> labels(std::max<size_t>(n, 1));
-        uint64_t n_clusters = 0;
-        DSH(ctx, dsh_cluster_threshold(ctx, o.estim, o.result_type, o.k, o.cluster_t, labels.data(), &n_clusters));
-        GroupStats gs;
-        if (o.has_stats) gs.compute(ctx, o, labels, n);
-        if (o.fmt == BINARY) {
-            const uint64_t hdr[2] = {(uint64_t)n, n_clusters};
-            if (std::fwrite(hdr, sizeof(uint64_t), 2, pairofp) != 2 || std::fwrite(labels.data(), sizeof(uint32_t), n, pairofp) != n)
-                die("Error writing to binary file");
-            if (o.has_stats) gs.write_binary(pairofp, n);
-        } else {
-            const bool dist = o.result_type == 0 || o.result_type == 3 || o.result_type == 4 || o.result_type == 6 || o.result_type == 8;
-            std::fprintf(pairofp, "#Cluster\t%s\t%s\t%.6g\n", kMeasureNames[o.result_type], dist ? "<=" : ">=", (double)o.cluster_t);  // --threshold's number format
-            // clusters are numbered by ascending representative: a label is its cluster's first member, so the numbers
-            // are handed out in one pass
-            std::vector<uint32_t> index(std::max<size_t>(n, 1));
-            uint32_t next = 0;
-            std::string s;
-            char num[32];
-            for (size_t x = 0; x < n; ++x) {
-                if (labels[x] == x) index[x] = next++;
-                s = o.inpaths[x];
-                s.append(num, (size_t)std::snprintf(num, sizeof num, "\t%u\t", index[labels[x]]));
-                s += o.inpaths[labels[x]];
-                if (o.has_stats) gs.append_fields(s, x, o.inpaths);
-                s += '\n';
-                std::fwrite(s.data(), 1, s.size(), pairofp);
+        for (size_t q = 0; q < rows; ++q) {
+            s.clear();
+            const std::string &name = names[nq ? nr + q : q];
+            for (uint64_t h = row_ptr[q]; h < row_ptr[q + 1]; ++h) {
+                s += name;
+                s += '\t';
+                s += names[col[h]];
+                s.append(num, (size_t)std::snprintf(num, sizeof num, "\t%.6g\n", (double)val[h]));  // format_ut_row's number format
             }
+            std::fwrite(s.data(), 1, s.size(), fp);
         }
-    } else if (o.has_reps) {  // the greedy pass in output order (dsh_greedy_threshold / dsh_greedy_extend): no pair leaves the device
-        std::vector<uint32_t> labels(std::max<size_t>(n, 1));
-        uint64_t n_reps = 0;
-        if (extend_labels.size() > n) die("--extend: %s labels %zu inputs but this run has only %zu", o.extend_file.c_str(), extend_labels.size(), n);
-        if (o.has_assign || !o.extend_file.empty())
-            DSH(ctx, dsh_greedy_extend(ctx, o.estim, o.result_type, o.k, o.reps_t, o.assign_mode, extend_labels.size(),
-                                       extend_labels.empty() ? nullptr : extend_labels.data(), labels.data(), &n_reps));
-        else
-            DSH(ctx, dsh_greedy_threshold(ctx, o.estim, o.result_type, o.k, o.reps_t, labels.data(), &n_reps));
-        GroupStats gs;
-        if (o.has_stats) gs.compute(ctx, o, labels, n);
-        if (o.fmt == BINARY) {
-            const uint64_t hdr[2] = {(uint64_t)n, n_reps};
-            if (std::fwrite(hdr, sizeof(uint64_t), 2, pairofp) != 2 || std::fwrite(labels.data(), sizeof(uint32_t), n, pairofp) != n)
-                die("Error writing to binary file");
-            if (o.has_stats) gs.write_binary(pairofp, n);
-        } else {
-            const bool dist = o.result_type == 0 || o.result_type == 3 || o.result_type == 4 || o.result_type == 6 || o.result_type == 8;
-            std::fprintf(pairofp, "#Representatives\t%s\t%s\t%.6g\n", kMeasureNames[o.result_type], dist ? "<=" : ">=", (double)o.reps_t);  // --threshold's number format
-            // the value of every non-representative against its label: ONE list of pairs (lhs = the input, rhs = its
-            // representative), by dsh_dist_pairs' contract bit for bit the triangle's value
-            std::vector<uint32_t> plhs, prhs;
-            for (size_t x = 0; x < n; ++x)
-                if (labels[x] != x) plhs.push_back((uint32_t)x), prhs.push_back(labels[x]);
-            std::vector<float> pv(std::max<size_t>(plhs.size(), 1));
-            const int type = o.result_type;
-            if (!plhs.empty()) DSH(ctx, dsh_dist_pairs(ctx, o.estim, &type, 1, o.k, plhs.data(), prhs.data(), plhs.size(), pv.data()));
-            // clusters are numbered by ascending representative; a representative comes before its members
-            std::vector<uint32_t> index(std::max<size_t>(n, 1));
-            uint32_t next = 0;
-            size_t at = 0;
-            std::string s;
-            char num[64];
-            for (size_t x = 0; x < n; ++x) {
-                if (labels[x] == x) index[x] = next++;
-                s = o.inpaths[x];
-                s.append(num, (size_t)std::snprintf(num, sizeof num, "\t%u\t", index[labels[x]]));
-                s += o.inpaths[labels[x]];
-                if (labels[x] == x) s += "\t-";
-                else s.append(num, (size_t)std::snprintf(num, sizeof num, "\t%.6g", (double)pv[at++]));
-                if (o.has_stats) gs.append_fields(s, x, o.inpaths);
-                s += '\n';
-                std::fwrite(s.data(), 1, s.size(), pairofp);
-            }
-        }
-    } else if (o.has_hist) {  // the distribution of the values (dsh_dist_histogram / dsh_dist_rect_histogram): only counts leave the device
-        if (nq >= n && nq) die("Wrong number of query/references. (ip size: %zu, nq: %zu", n, nq);
-        const bool split = !o.hist_labels_file.empty();
-        if (split && hist_labels.size() != n)
-            die("--histogram-labels: %s labels %zu inputs but this run has %zu", o.hist_labels_file.c_str(), hist_labels.size(), n);
-        const size_t ne = o.hist_edges.size(), nclass = ne + 2, planes = split ? 2 : 1;
-        const uint32_t *lab = split ? hist_labels.data() : nullptr;
-        std::vector<uint64_t> counts(planes * nclass);
-        if (nq) DSH(ctx, dsh_dist_rect_histogram(ctx, o.estim, o.result_type, o.k, n - nq, n, 0, n - nq, o.hist_edges.data(), (uint32_t)ne, lab, counts.data()));
-        else DSH(ctx, dsh_dist_histogram(ctx, o.estim, o.result_type, o.k, 0, n, o.hist_edges.data(), (uint32_t)ne, lab, counts.data()));
-        if (o.fmt == BINARY) {
-            const uint64_t hdr[2] = {(uint64_t)ne, (uint64_t)planes};
-            const float pad = 0.f;
-            if (std::fwrite(hdr, sizeof(uint64_t), 2, pairofp) != 2 || std::fwrite(o.hist_edges.data(), sizeof(float), ne, pairofp) != ne ||
-                ((ne & 1) && std::fwrite(&pad, sizeof(float), 1, pairofp) != 1) ||
-                std::fwrite(counts.data(), sizeof(uint64_t), counts.size(), pairofp) != counts.size())
-                die("Error writing to binary file");
-        } else {
-            const bool dist = o.result_type == 0 || o.result_type == 3 || o.result_type == 4 || o.result_type == 6 || o.result_type == 8;
-            std::fprintf(pairofp, "#Histogram\t%s\t%s\n", kMeasureNames[o.result_type], dist ? "<=" : ">=");
-            const double inf = std::numeric_limits<double>::infinity(), nan = std::numeric_limits<double>::quiet_NaN();
-            for (size_t b = 0; b < nclass; ++b) {  // --threshold's number format
-                const double lo = b == ne + 1 ? nan : (b == 0 ? -inf : (double)o.hist_edges[b - 1]);
-                const double hi = b == ne + 1 ? nan : (b == ne ? inf : (double)o.hist_edges[b]);
-                std::fprintf(pairofp, "%.6g\t%.6g\t%llu", lo, hi, (unsigned long long)counts[b]);
-                if (split) std::fprintf(pairofp, "\t%llu", (unsigned long long)counts[nclass + b]);
-                std::fputc('\n', pairofp);
-            }
-        }
-    } else if (o.has_threshold) {  // only the pairs that pass (dsh_dist_threshold / dsh_dist_rect_threshold): no dense matrix
-        if (nq >= n && nq) die("Wrong number of query/references. (ip size: %zu, nq: %zu", n, nq);
-        const size_t nr = n - nq, rows = nq ? nq : n;
-        std::vector<uint64_t> row_ptr(rows + 1);
-        uint32_t *col = nullptr;
-        float *val = nullptr;
-        uint64_t nnz = 0;
-        if (nq) DSH(ctx, dsh_dist_rect_threshold(ctx, o.estim, o.result_type, o.k, nr, n, 0, nr, o.threshold, row_ptr.data(), &col, &val, &nnz));
-        else DSH(ctx, dsh_dist_threshold(ctx, o.estim, o.result_type, o.k, 0, n, o.threshold, row_ptr.data(), &col, &val, &nnz));
-        if (o.fmt == BINARY) {
-            const uint64_t hdr[2] = {(uint64_t)rows, nnz};
-            if (std::fwrite(hdr, sizeof(uint64_t), 2, pairofp) != 2 || std::fwrite(row_ptr.data(), sizeof(uint64_t), rows + 1, pairofp) != rows + 1 ||
-                std::fwrite(col, sizeof(uint32_t), nnz, pairofp) != nnz || std::fwrite(val, sizeof(float), nnz, pairofp) != nnz)
-                die("Error writing to binary file");
-        } else {
-            static const char *const kMeasure[9] = {"MASH_DIST", "JI", "SIZES", "FULL_MASH_DIST", "FULL_CONTAINMENT_DIST", "CONTAINMENT_INDEX",
-                                                    "CONTAINMENT_DIST", "SYMMETRIC_CONTAINMENT_INDEX", "SYMMETRIC_CONTAINMENT_DIST"};
-            const bool dist = o.result_type == 0 || o.result_type == 3 || o.result_type == 4 || o.result_type == 6 || o.result_type == 8;
-            std::fprintf(pairofp, "#Threshold\t%s\t%s\t%.6g\n", kMeasure[o.result_type], dist ? "<=" : ">=", (double)o.threshold);
-            std::string s;
-            char num[64];
-            for (size_t r = 0; r < rows; ++r) {
-                s.clear();
-                const std::string &name = o.inpaths[nq ? nr + r : r];
-                for (uint64_t h = row_ptr[r]; h < row_ptr[r + 1]; ++h) {
-                    s += name;
-                    s += '\t';
-                    s += o.inpaths[col[h]];
-                    s.append(num, (size_t)std::snprintf(num, sizeof num, "\t%.6g\n", (double)val[h]));  // format_ut_row's number format
-                }
-                std::fwrite(s.data(), 1, s.size(), pairofp);
-            }
-        }
-        dsh_free_host(col);
-        dsh_free_host(val);
-    } else if (o.nneighbors) {  // nndist_loop (src/sketch_and_cmp.h:712-783)
-        const size_t nr = nq ? n - nq : n, npairs = nq ? nq : n;
-        unsigned nn = o.nneighbors;
-        const size_t possible = nq ? nr : (n ? n - 1 : 0);
-        if (nn > possible) {
-            std::fprintf(stderr, "Only reporting %zu rather than %u neighbors due to their being only that many sets.\n", possible, nn);
-            nn = (unsigned)possible;
-        }
-        std::vector<uint32_t> idx(std::max<size_t>(npairs * nn, 1));
-        std::vector<float> val(std::max<size_t>(npairs * nn, 1));
-        if (nn) DSH(ctx, dsh_knn(ctx, o.estim, o.result_type, o.k, nq ? nr : 0, n, 0, nr, nn, idx.data(), val.data()));
-        if (o.fmt == BINARY) {  // u32 n, u32 nn, then {float value, u32 id} pairs (validx_t, :605)
-            uint32_t hdr[2] = {(uint32_t)n, nn};
-            std::fwrite(hdr, sizeof(uint32_t), 2, pairofp);
-            for (size_t t = 0; t < npairs * nn; ++t) {
-                std::fwrite(&val[t], sizeof(float), 1, pairofp);
-                std::fwrite(&idx[t], sizeof(uint32_t), 1, pairofp);
-            }
-        } else {  // rows in input order (the reference's row order depends on its thread schedule)
-            std::fputs("#File\tNeighbor ID:distance\t...\n", pairofp);
-            for (size_t i = 0; i < npairs; ++i) {
-                std::string s(o.inpaths[i + (nq ? nr : 0)]);
-                char num[64];
-                for (unsigned j = 0; j < nn; ++j)
-                    s.append(num, (size_t)std::snprintf(num, sizeof num, "\t%u:%g", idx[i * nn + j], (double)val[i * nn + j]));
-                s += '\n';
-                std::fwrite(s.data(), 1, s.size(), pairofp);
-            }
-        }
-    } else if (nq) {  // partdist_loop (src/dashing.h:660-712): one row per query over all references
-        if (nq >= n) die("Wrong number of query/references. (ip size: %zu, nq: %zu", n, nq);
-        const size_t nr = n - nq;
-        if (o.fmt == UPPER_TRIANGULAR) std::fprintf(pairofp, "%zu\n", n);  // src/sketch_and_cmp.h:394-396
-        const size_t qblock = std::max<size_t>(1, ((size_t)64 << 20) / nr);
-        std::vector<float> buf;
-        for (size_t q0 = nr; q0 < n; q0 += qblock) {
-            const size_t q1 = std::min(n, q0 + qblock);
-            buf.resize((q1 - q0) * nr);
-            DSH(ctx, dsh_dist_rect(ctx, o.estim, o.result_type, o.k, q0, q1, 0, nr, buf.data()));
-            for (size_t qi = q0; qi < q1; ++qi) {
-                const float *row = buf.data() + (qi - q0) * nr;
-                if (o.fmt == BINARY) {
-                    if (std::fwrite(row, sizeof(float), nr, pairofp) != nr) die("Error writing to binary file");
-                } else {
-                    std::string s(o.inpaths[qi]);
-                    char num[64];
-                    for (size_t j = 0; j < nr; ++j) s.append(num, (size_t)std::snprintf(num, sizeof num, "\t%g", (double)row[j]));
-                    s += '\n';
-                    std::fwrite(s.data(), 1, s.size(), pairofp);
-                }
-            }
-        }
-    } else if (o.fmt == BINARY && o.devices.size() > 1 && !o.out_dists.empty()) {
-        // Several GPUs of one node: every device holds all sketches, device d computes the row range
-        // dsh_balance_rows gives it (tile-aligned, equal tile counts) and writes its
-        // contiguous span of the packed matrix straight into the output file.
-        if (write_binary_header(pairofp, n)) die("Failure");
-        std::fflush(pairofp);
-        const int fd = ::fileno(pairofp);
-        if (::ftruncate(fd, (off_t)(9 + total * sizeof(float)))) die("could not size %s", o.out_dists.c_str());
-        const size_t G = o.devices.size(), m = (size_t)1 << o.S;
-        std::vector<uint8_t> all(n * m);
-        DSH(ctx, dsh_download_sketches(ctx, 0, n, all.data()));
-        std::vector<uint64_t> bounds(G + 1);
-        if (dsh_balance_rows(n, (uint32_t)G, bounds.data())) die("dsh_balance_rows failed");
-        std::vector<std::thread> workers;
-        for (size_t d = 0; d < G; ++d)
-            workers.emplace_back([&, d]() {
-                dsh_ctx *c = ctx;
-                if (d > 0) {
-                    if (int rc = dsh_create(o.devices[d], &c)) die("[dashing-amd] dsh_create(device %d) = %d", o.devices[d], rc);
-                    DSH(c, dsh_sketches_alloc(c, n, o.S));
-                    DSH(c, dsh_upload_sketches(c, all.data(), 0, n));
-                }
-                // as below: large row blocks (each one a range the library lays its planes out for), two
-                // page-locked buffers, block b+1 enqueued before block b is written at its file offset
-                const uint64_t block_vals = (uint64_t)256 << 20;
-                std::vector<uint64_t> cuts{bounds[d]};
-                while (cuts.back() < bounds[d + 1]) {
-                    const uint64_t rb = cuts.back();
-                    uint64_t re = rb + 1;
-                    while (re < bounds[d + 1] && dsh_tri_span(n, rb, re + 1) <= block_vals) ++re;
-                    cuts.push_back(re);
-                }
-                uint64_t cap = 1;
-                for (size_t b = 0; b + 1 < cuts.size(); ++b) cap = std::max<uint64_t>(cap, dsh_tri_span(n, cuts[b], cuts[b + 1]));
-                float *bufs[2] = {nullptr, nullptr};
-                for (int w = 0; w < (cuts.size() > 2 ? 2 : 1); ++w)
-                    if (!(bufs[w] = (float *)dsh_alloc_host(cap * sizeof(float)))) die("could not allocate pinned host memory");
-                const size_t nblocks = cuts.size() - 1;
-                std::vector<uint64_t> ticket(nblocks + 1, 0);
-                if (nblocks) {
-                    DSH(c, dsh_dist_rows_async(c, o.estim, o.result_type, o.k, cuts[0], cuts[1], bufs[0]));
-                    DSH(c, dsh_event_record(c, &ticket[0]));
-                }
-                for (size_t b = 0; b < nblocks; ++b) {
-                    if (b + 1 < nblocks) {
-                        DSH(c, dsh_dist_rows_async(c, o.estim, o.result_type, o.k, cuts[b + 1], cuts[b + 2], bufs[(b + 1) & 1]));
-                        DSH(c, dsh_event_record(c, &ticket[b + 1]));
-                    }
-                    DSH(c, dsh_event_wait(c, ticket[b]));
-                    const uint64_t span = dsh_tri_span(n, cuts[b], cuts[b + 1]);
-                    const off_t pos = (off_t)(9 + dsh_tri_span(n, 0, cuts[b]) * sizeof(float));
-                    size_t done = 0;
-                    while (done < span * sizeof(float)) {
-                        const ssize_t w = ::pwrite(fd, (const char *)bufs[b & 1] + done, span * sizeof(float) - done, pos + (off_t)done);
-                        if (w <= 0) die("Failed to write rows to disk");
-                        done += (size_t)w;
-                    }
-                }
-                for (auto &bf : bufs) dsh_free_host(bf);
-                if (d > 0) dsh_destroy(c);
-            });
-        for (auto &w : workers) w.join();
-    } else if (o.devices.size() > 1 || o.rccl) {
-        // Several GPUs, output that one writer has to emit in order (text formats, or -b to a pipe): every device
-        // computes its rows -- the library partitions them itself (dsh_dist_collect with bounds = NULL: a row range per
-        // device plus top-up tile rows from the bottom of the triangle, dsh_balance_rowsets) -- and the rows are delivered
-        // to the first device over RCCL / xGMI inside the library (pipelined grouped ncclSend/ncclRecv, part by part),
-        // which hands the whole matrix to this process -- dashing's single writer (src/sketch_and_cmp.h:804-849) fed by
-        // G GPUs.  One thread per device, as RCCL wants for one process.
-        const size_t G = std::max<size_t>(o.devices.size(), 1), m = (size_t)1 << o.S;
-        uint8_t uid[DSH_UNIQUE_ID_BYTES];
-        if (int rc = dsh_comm_unique_id(uid)) die("[dashing-amd] RCCL is not available (dsh_comm_unique_id = %d)", rc);
-        std::vector<uint8_t> all;
-        if (G > 1) {
-            all.resize(n * m);
-            DSH(ctx, dsh_download_sketches(ctx, 0, n, all.data()));
-        }
-        std::vector<float> tri(std::max<uint64_t>(total, 1));
-        std::vector<std::thread> workers;
-        for (size_t d = 0; d < G; ++d)
-            workers.emplace_back([&, d]() {
-                dsh_ctx *c = ctx;
-                if (d > 0) {
-                    if (int rc = dsh_create(o.devices[d], &c)) die("[dashing-amd] dsh_create(device %d) = %d", o.devices[d], rc);
-                    DSH(c, dsh_sketches_alloc(c, n, o.S));
-                    DSH(c, dsh_upload_sketches(c, all.data(), 0, n));
-                }
-                DSH(c, dsh_comm_init(c, uid, (int)d, (int)G));
-                DSH(c, dsh_dist_collect(c, o.estim, o.result_type, o.k, /*bounds=*/nullptr, 0, d == 0 ? tri.data() : nullptr));
-                DSH(c, dsh_comm_destroy(c));
-                if (d > 0) dsh_destroy(c);
-            });
-        for (auto &w : workers) w.join();
-        if (o.fmt == BINARY) {
-            if (write_binary_header(pairofp, n)) die("Failure");
-            if (total && std::fwrite(tri.data(), sizeof(float), total, pairofp) != total) die("Failed to write rows to disk");
-        } else if (o.fmt == FULL_TSV) {
-            emit_full_header(pairofp, o.inpaths);
-            for (size_t i = 0; i < n; ++i) emit_full_row(pairofp, o.inpaths, i, tri.data());
-        } else {
-            emit_header(pairofp, o.fmt, o.inpaths);
-            for (size_t i = 0; i < n; ++i) emit_ut_row(pairofp, o.fmt, o.inpaths, i, tri.data() + dsh_tri_span(n, 0, i));
-        }
-    } else if (o.fmt == FULL_TSV) {
-        std::vector<float> tri(std::max<uint64_t>(total, 1));
-        DSH(ctx, dsh_dist_rows(ctx, o.estim, o.result_type, o.k, 0, n, tri.data()));
-        emit_full_header(pairofp, o.inpaths);
-        for (size_t i = 0; i < n; ++i) emit_full_row(pairofp, o.inpaths, i, tri.data());
-    } else {
-        if (o.fmt == BINARY) {
-            if (write_binary_header(pairofp, n)) die("Failure");
-        } else {
-            emit_header(pairofp, o.fmt, o.inpaths);
-        }
-        // Row blocks, two page-locked ping-pong buffers, asynchronous C-ABI calls: block b+1 is enqueued
-        // (compute + copy into its buffer) before block b is emitted, so the GPU works while this thread
-        // formats / writes -- dist_loop's dps[i & 1] scheme (src/sketch_and_cmp.h:804-816) without the
-        // writer thread.  Blocks are large (<= 256 Mi values) so that each one is a row range the library
-        // lays its plane matrix out for (few planes per tile, values at their final positions).
-        const uint64_t block_vals = (uint64_t)256 << 20;
-        std::vector<uint64_t> cuts{0};
-        while (cuts.back() < n) {
-            const uint64_t rb = cuts.back();
-            uint64_t re = rb + 1;
-            while (re < n && dsh_tri_span(n, rb, re + 1) <= block_vals) ++re;
-            cuts.push_back(re);
-        }
-        uint64_t cap = 1;
-        for (size_t b = 0; b + 1 < cuts.size(); ++b) cap = std::max<uint64_t>(cap, dsh_tri_span(n, cuts[b], cuts[b + 1]));
-        float *bufs[2] = {nullptr, nullptr};
-        for (int w = 0; w < (cuts.size() > 2 ? 2 : 1); ++w)
-            if (!(bufs[w] = (float *)dsh_alloc_host(cap * sizeof(float)))) die("could not allocate %llu bytes of pinned host memory", (unsigned long long)(cap * sizeof(float)));
-        auto enqueue = [&](size_t b) {
-            DSH(ctx, dsh_dist_rows_async(ctx, o.estim, o.result_type, o.k, cuts[b], cuts[b + 1], bufs[b & 1]));
-        };
-        const size_t nblocks = cuts.size() - 1;
-        std::vector<uint64_t> ticket(nblocks + 1, 0);
-        if (nblocks) {
-            enqueue(0);
-            DSH(ctx, dsh_event_record(ctx, &ticket[0]));
-        }
-        for (size_t b = 0; b < nblocks; ++b) {
-            // block b+1 goes in first (its host buffer was emitted in the previous iteration): its kernels fill the
-            // library's other device buffer while block b is still being copied out, and only block b is awaited
-            if (b + 1 < nblocks) {
-                enqueue(b + 1);
-                DSH(ctx, dsh_event_record(ctx, &ticket[b + 1]));
-            }
-            DSH(ctx, dsh_event_wait(ctx, ticket[b]));  // block b has arrived in bufs[b & 1]
-            const uint64_t rb = cuts[b], re = cuts[b + 1], span = dsh_tri_span(n, rb, re);
-            const float *buf = bufs[b & 1];
-            if (o.fmt == BINARY) {
-                if (span && std::fwrite(buf, sizeof(float), span, pairofp) != span) die("Failed to write rows to disk");
-                continue;
-            }
-            // format rows on all host threads (snprintf dominates text output), write in order
-            std::vector<uint64_t> off(re - rb + 1, 0);
-            for (uint64_t i = rb; i < re; ++i) off[i - rb + 1] = off[i - rb] + (n - i - 1);
-            const uint64_t group = 64;
-            for (uint64_t g0 = rb; g0 < re; g0 += group * (uint64_t)o.nthreads) {
-                const uint64_t g1 = std::min<uint64_t>(re, g0 + group * (uint64_t)o.nthreads);
-                std::vector<std::string> rows(g1 - g0);
-#pragma omp parallel for schedule(dynamic, 4) num_threads(o.nthreads)
-                for (int64_t i = (int64_t)g0; i < (int64_t)g1; ++i)
-                    format_ut_row(rows[i - g0], o.fmt, o.inpaths, (size_t)i, buf + off[i - rb]);
-                for (auto &r : rows) std::fwrite(r.data(), 1, r.size(), pairofp);
-            }
-        }
-        for (auto &b : bufs) dsh_free_host(b);
     }
+    dsh_free_host(col);
+    dsh_free_host(val);
+}
+
+// --nearest-neighbors: nndist_loop (src/sketch_and_cmp.h:712-783)
+static void emit_nearest_neighbors(const DistRun &r, std::FILE *fp)
+{
+    const Opts &o = r.o;
+    const size_t n = r.n, nq = r.nq;
+    const size_t nr = nq ? n - nq : n, npairs = nq ? nq : n;
+    unsigned nn = o.nneighbors;
+    const size_t possible = nq ? nr : (n ? n - 1 : 0);
+    if (nn > possible) {
+        std::fprintf(stderr, "Only reporting %zu rather than %u neighbors due to their being only that many sets.\n", possible, nn);
+        nn = (unsigned)possible;
+    }
+    std::vector<uint32_t> idx(std::max<size_t>(npairs * nn, 1));
+    std::vector<float> val(std::max<size_t>(npairs * nn, 1));
+    if (nn) DSH(r.ctx, dsh_knn(r.ctx, o.estim, o.result_type, o.k, nq ? nr : 0, n, 0, nr, nn, idx.data(), val.data()));
+    if (o.fmt == BINARY) {  // u32 n, u32 nn, then {float value, u32 id} pairs (validx_t, :605)
+        uint32_t hdr[2] = {(uint32_t)n, nn};
+        std::fwrite(hdr, sizeof(uint32_t), 2, fp);
+        for (size_t t = 0; t < npairs * nn; ++t) {
+            std::fwrite(&val[t], sizeof(float), 1, fp);
+            std::fwrite(&idx[t], sizeof(uint32_t), 1, fp);
+        }
+    } else {  // rows in input order (the reference's row order depends on its thread schedule)
+        std::fputs("#File\tNeighbor ID:distance\t...\n", fp);
+        for (size_t i = 0; i < npairs; ++i) {
+            std::string s(o.inpaths[i + (nq ? nr : 0)]);
+            char num[64];
+            for (unsigned j = 0; j < nn; ++j)
+                s.append(num, (size_t)std::snprintf(num, sizeof num, "\t%u:%g", idx[i * nn + j], (double)val[i * nn + j]));
+            s += '\n';
+            std::fwrite(s.data(), 1, s.size(), fp);
+        }
+    }
+}
+
+// -Q, or an asymmetric measure: partdist_loop (src/dashing.h:660-712): one row per query over all references
+static void emit_rectangle(const DistRun &r, std::FILE *fp)
+{
+    const Opts &o = r.o;
+    const size_t n = r.n, nq = r.nq;
+    check_query_count(n, nq);
+    const size_t nr = n - nq;
+    if (o.fmt == UPPER_TRIANGULAR) std::fprintf(fp, "%zu\n", n);  // src/sketch_and_cmp.h:394-396
+    const size_t qblock = std::max<size_t>(1, ((size_t)64 << 20) / nr);
+    std::vector<float> buf;
+    for (size_t q0 = nr; q0 < n; q0 += qblock) {
+        const size_t q1 = std::min(n, q0 + qblock);
+        buf.resize((q1 - q0) * nr);
+        DSH(r.ctx, dsh_dist_rect(r.ctx, o.estim, o.result_type, o.k, q0, q1, 0, nr, buf.data()));
+        for (size_t qi = q0; qi < q1; ++qi) {
+            const float *row = buf.data() + (qi - q0) * nr;
+            if (o.fmt == BINARY) {
+                if (std::fwrite(row, sizeof(float), nr, fp) != nr) die("Error writing to binary file");
+            } else {
+                std::string s(o.inpaths[qi]);
+                char num[64];
+                for (size_t j = 0; j < nr; ++j) s.append(num, (size_t)std::snprintf(num, sizeof num, "\t%g", (double)row[j]));
+                s += '\n';
+                std::fwrite(s.data(), 1, s.size(), fp);
+            }
+        }
+    }
+}
+
+// -b to a file on several GPUs of one node: every device holds all sketches, device d computes the row range dsh_balance_rows
+// gives it (tile-aligned, equal tile counts) and writes its contiguous span of the packed matrix straight into the output
+// file, block by block at the block's offset
+static void emit_multi_device_file(const DistRun &r, std::FILE *fp)
+{
+    const Opts &o = r.o;
+    const size_t n = r.n;
+    if (write_binary_header(fp, n)) die("Failure");
+    std::fflush(fp);
+    const int fd = ::fileno(fp);
+    if (::ftruncate(fd, (off_t)(9 + tri_total(n) * sizeof(float)))) die("could not size %s", o.out_dists.c_str());
+    const size_t G = o.devices.size();
+    std::vector<uint8_t> all(n << o.S);
+    DSH(r.ctx, dsh_download_sketches(r.ctx, 0, n, all.data()));
+    std::vector<uint64_t> bounds(G + 1);
+    if (dsh_balance_rows(n, (uint32_t)G, bounds.data())) die("dsh_balance_rows failed");
+    std::vector<std::thread> workers;
+    for (size_t d = 0; d < G; ++d)
+        workers.emplace_back([&, d]() {
+            dsh_ctx *c = d ? secondary_context(o.devices[d], all, n, o.S) : r.ctx;
+            for_row_blocks(c, o, n, bounds[d], bounds[d + 1], r.block_vals, [&](uint64_t rb, uint64_t, const float *vals, uint64_t span) {
+                const off_t pos = (off_t)(9 + dsh_tri_span(n, 0, rb) * sizeof(float));
+                size_t done = 0;
+                while (done < span * sizeof(float)) {
+                    const ssize_t w = ::pwrite(fd, (const char *)vals + done, span * sizeof(float) - done, pos + (off_t)done);
+                    if (w <= 0) die("Failed to write rows to disk");
+                    done += (size_t)w;
+                }
+            });
+            if (d > 0) dsh_destroy(c);
+        });
+    for (auto &w : workers) w.join();
+}
+
+// Several GPUs (or --rccl), output that one writer has to emit in order (text formats, or -b to a pipe): every device
+// computes its rows -- the library partitions them itself (dsh_dist_collect with bounds = NULL: a row range per
+// device plus top-up tile rows from the bottom of the triangle, dsh_balance_rowsets) -- and the rows are delivered
+// to the first device over RCCL / xGMI inside the library (pipelined grouped ncclSend/ncclRecv, part by part),
+// which hands the whole matrix to this process -- dashing's single writer (src/sketch_and_cmp.h:804-849) fed by
+// G GPUs.  One thread per device, as RCCL wants for one process.
+static void emit_rccl_collect(const DistRun &r, std::FILE *fp)
+{
+    const Opts &o = r.o;
+    const size_t n = r.n;
+    const uint64_t total = tri_total(n);
+    const size_t G = std::max<size_t>(o.devices.size(), 1);
+    uint8_t uid[DSH_UNIQUE_ID_BYTES];
+    if (int rc = dsh_comm_unique_id(uid)) die("[dashing-amd] RCCL is not available (dsh_comm_unique_id = %d)", rc);
+    std::vector<uint8_t> all;
+    if (G > 1) {
+        all.resize(n << o.S);
+        DSH(r.ctx, dsh_download_sketches(r.ctx, 0, n, all.data()));
+    }
+    std::vector<float> tri(std::max<uint64_t>(total, 1));
+    std::vector<std::thread> workers;
+    for (size_t d = 0; d < G; ++d)
+        workers.emplace_back([&, d]() {
+            dsh_ctx *c = d ? secondary_context(o.devices[d], all, n, o.S) : r.ctx;
+            DSH(c, dsh_comm_init(c, uid, (int)d, (int)G));
+            DSH(c, dsh_dist_collect(c, o.estim, o.result_type, o.k, /*bounds=*/nullptr, 0, d == 0 ? tri.data() : nullptr));
+            DSH(c, dsh_comm_destroy(c));
+            if (d > 0) dsh_destroy(c);
+        });
+    for (auto &w : workers) w.join();
+    if (o.fmt == BINARY) {
+        if (write_binary_header(fp, n)) die("Failure");
+        if (total && std::fwrite(tri.data(), sizeof(float), total, fp) != total) die("Failed to write rows to disk");
+    } else if (o.fmt == FULL_TSV) {
+        emit_full_header(fp, o.inpaths);
+        for (size_t i = 0; i < n; ++i) emit_full_row(fp, o.inpaths, i, tri.data());
+    } else {
+        emit_header(fp, o.fmt, o.inpaths);
+        for (size_t i = 0; i < n; ++i) emit_ut_row(fp, o.fmt, o.inpaths, i, tri.data() + dsh_tri_span(n, 0, i));
+    }
+}
+
+// -T: the full table needs the whole triangle at once
+static void emit_full_tsv(const DistRun &r, std::FILE *fp)
+{
+    const Opts &o = r.o;
+    std::vector<float> tri(std::max<uint64_t>(tri_total(r.n), 1));
+    DSH(r.ctx, dsh_dist_rows(r.ctx, o.estim, o.result_type, o.k, 0, r.n, tri.data()));
+    emit_full_header(fp, o.inpaths);
+    for (size_t i = 0; i < r.n; ++i) emit_full_row(fp, o.inpaths, i, tri.data());
+}
+
+// The streamed triangle (dist_loop, src/sketch_and_cmp.h:785-880), -b or one text line per row: a block is written, or its rows
+// formatted on all host threads, while the device computes the next one
+static void emit_triangle(const DistRun &r, std::FILE *fp)
+{
+    const Opts &o = r.o;
+    const uint64_t n = r.n;
+    if (o.fmt == BINARY) {
+        if (write_binary_header(fp, n)) die("Failure");
+    } else {
+        emit_header(fp, o.fmt, o.inpaths);
+    }
+    for_row_blocks(r.ctx, o, n, 0, n, r.block_vals, [&](uint64_t rb, uint64_t re, const float *buf, uint64_t span) {
+        if (o.fmt == BINARY) {
+            if (span && std::fwrite(buf, sizeof(float), span, fp) != span) die("Failed to write rows to disk");
+            return;
+        }
+        // format rows on all host threads (snprintf dominates text output), write in order
+        std::vector<uint64_t> off(re - rb + 1, 0);
+        for (uint64_t i = rb; i < re; ++i) off[i - rb + 1] = off[i - rb] + (n - i - 1);
+        const uint64_t group = 64;
+        for (uint64_t g0 = rb; g0 < re; g0 += group * (uint64_t)o.nthreads) {
+            const uint64_t g1 = std::min<uint64_t>(re, g0 + group * (uint64_t)o.nthreads);
+            std::vector<std::string> rows(g1 - g0);
+#pragma omp parallel for schedule(dynamic, 4) num_threads(o.nthreads)
+            for (int64_t i = (int64_t)g0; i < (int64_t)g1; ++i)
+                format_ut_row(rows[i - g0], o.fmt, o.inpaths, (size_t)i, buf + off[i - rb]);
+            for (auto &row : rows) std::fwrite(row.data(), 1, row.size(), fp);
+        }
+    });
+}
+
+static int dist_main(int argc, char **argv, bool by_seq = false)
+{
+    DistRun r;
+    Opts &o = r.o;
+    o = parse(argc, argv, true);
+    r.block_vals = block_vals_from_env();
+    if (by_seq) o.avoid_sorting = 1;  // records keep their order
+    refuse_conflicts(o, by_seq);
+    if (!o.pairs_file.empty()) r.pair_types = parse_measures(o);
+    if (by_seq) read_records_or_presketched(r);
+    read_option_files(r);
+    std::FILE *ofp = stdout, *pairofp = stdout;
+    if (!o.out_sizes.empty() && !(ofp = std::fopen(o.out_sizes.c_str(), "w"))) die("Could not open file at %s for writing.", o.out_sizes.c_str());
+    if (!o.out_dists.empty() && !(pairofp = std::fopen(o.out_dists.c_str(), "wb"))) die("Could not open file at %s for writing.", o.out_dists.c_str());
+    order_paths(r);
+    if (!o.groups_file.empty()) parse_groups_file(r);
+    if (!o.pairs_file.empty()) look_up_pairs(r);
+
+    const double t_start = now_s();
+    since_launch("dist: options parsed, context thread about to start");
+    CtxFuture cf(o.device, r.n, o.S, (o.presketched || by_seq) ? 0 : staging_bytes_for(o.inpaths));  // the HIP runtime comes up while the first batch is read
+    const double t_fill0 = now_s();
+    if (by_seq) load_records(cf.get(), r);
+    else if (o.presketched) load_hll_files(cf.get(), o, r.n);
+    else fill_sketches(cf, o, /*write_files=*/o.cache != 0, false);
+    r.ctx = cf.get();
+    if (g_timing) std::fprintf(stderr, "[timing] all sketches resident after %.3f s\n", now_s() - t_fill0);
+    if (!o.groups_file.empty()) union_groups(r);
+    write_sizes(r, ofp);
+
+    if (!o.pairs_file.empty()) emit_pairs(r, pairofp);
+    else if (o.has_cluster || o.has_reps) emit_labelling(r, pairofp);
+    else if (o.has_hist) emit_histogram(r, pairofp);
+    else if (o.has_threshold) emit_threshold(r, pairofp);
+    else if (o.nneighbors) emit_nearest_neighbors(r, pairofp);
+    else if (r.nq) emit_rectangle(r, pairofp);
+    else if (o.fmt == BINARY && o.devices.size() > 1 && !o.out_dists.empty()) emit_multi_device_file(r, pairofp);
+    else if (o.devices.size() > 1 || o.rccl) emit_rccl_collect(r, pairofp);
+    else if (o.fmt == FULL_TSV) emit_full_tsv(r, pairofp);
+    else emit_triangle(r, pairofp);
+
     std::fflush(pairofp);
     if (pairofp != stdout) std::fclose(pairofp);
     if (g_timing) std::fprintf(stderr, "[timing] total since dsh_create %.3f s\n", now_s() - t_start);
@@ -1758,7 +1880,7 @@ static int dist_main(int argc, char **argv, bool by_seq = false)
         const std::string labels = o.out_dists.empty() ? "unspecified" : o.out_dists + ".labels";
         if (write_labels(labels, o.inpaths)) die("Could not open file at '%s' for writing", labels.c_str());
     }
-    leave(ctx);
+    leave(r.ctx);
     return EXIT_SUCCESS;
 }
 
