@@ -16,6 +16,7 @@ SIZES, FULL_CONTAINMENT_DIST, CONTAINMENT_INDEX, CONTAINMENT_DIST = 2, 4, 5, 6
 SYMMETRIC_CONTAINMENT_INDEX, SYMMETRIC_CONTAINMENT_DIST = 7, 8
 GREEDY_FIRST, GREEDY_BEST = 0, 1  # assign_mode of dsh_greedy_extend*
 HIST_MAX_EDGES = 4096  # DSH_HIST_MAX_EDGES: the edges of one dsh_dist_histogram* call
+LINKAGE_SINGLE, LINKAGE_COMPLETE, LINKAGE_AVERAGE = 0, 1, 2  # DSH_LINKAGE_*
 STATS_FRAC_BITS = 30  # DSH_STATS_FRAC_BITS: sums of dsh_group_stats* are in units of 2^-30
 # the measures for which a larger value is better (the others are the *_DIST forms; SIZES has no order)
 SIMILARITY_TYPES = (JI, CONTAINMENT_INDEX, SYMMETRIC_CONTAINMENT_INDEX)
@@ -43,6 +44,7 @@ SYMBOLS = [
     "dsh_greedy_threshold", "dsh_greedy_threshold_device", "dsh_greedy_extend", "dsh_greedy_extend_device",
     "dsh_group_stats", "dsh_group_stats_device",
     "dsh_dist_histogram", "dsh_dist_histogram_device", "dsh_dist_rect_histogram",
+    "dsh_linkage_threshold", "dsh_linkage_threshold_device", "dsh_linkage_tri",
     "dsh_fold", "dsh_fold_device", "dsh_upload_sketches_folded", "dsh_upload_sketches_folded_device", "dsh_union_groups", "dsh_union_groups_device", "dsh_shard_plan", "dsh_dist_shard_device", "dsh_unpermute_device", "dsh_unpermute_staged_device", "dsh_unpermute_blocks_device", "dsh_tri_span", "dsh_tri_index", "dsh_partition_rows", "dsh_balance_rows", "dsh_balance_rowsets", "dsh_rowsets_from_bounds", "dsh_rowsets_rank", "dsh_alloc_host", "dsh_free_host",
     "dsh_set_profiling", "dsh_last_kernel_ms", "dsh_last_part_info", "dsh_finalize_phase_cycles", "dsh_set_option", "dsh_get_info", "dsh_stream",
 ]
@@ -185,7 +187,10 @@ def load_library():
                        ("dsh_group_stats_device", [vp, i32, i32, i32, vp, vp, vp, vp, vp]),
                        ("dsh_dist_histogram", [vp, i32, i32, i32, u64, u64, vp, C.c_uint32, vp, vp]),
                        ("dsh_dist_histogram_device", [vp, i32, i32, i32, u64, u64, vp, C.c_uint32, vp, vp]),
-                       ("dsh_dist_rect_histogram", [vp, i32, i32, i32, u64, u64, u64, u64, vp, C.c_uint32, vp, vp])):
+                       ("dsh_dist_rect_histogram", [vp, i32, i32, i32, u64, u64, u64, u64, vp, C.c_uint32, vp, vp]),
+                       ("dsh_linkage_threshold", [vp, i32, i32, i32, C.c_float, i32, vp, C.POINTER(u64)]),
+                       ("dsh_linkage_threshold_device", [vp, i32, i32, i32, C.c_float, i32, vp, C.POINTER(u64)]),
+                       ("dsh_linkage_tri", [vp, u64, vp, i32, C.c_float, i32, vp, C.POINTER(u64)])):
         fn = getattr(lib, name, None)
         if fn is not None:
             fn.argtypes = args
@@ -775,6 +780,48 @@ class Context:
         nc = C.c_uint64()
         self._ck(self._derive("dsh_cluster_threshold_device")(self._h, estim, result_type, k, threshold, C.c_void_p(labels_ptr), C.byref(nc)))
         return int(nc.value)
+
+    # ---- single-, complete- and average-linkage clusters at a threshold (include/dashing_hip.h has the contract)
+    _LINKAGES = {"single": LINKAGE_SINGLE, "complete": LINKAGE_COMPLETE, "average": LINKAGE_AVERAGE}
+
+    @classmethod
+    def _linkage(cls, linkage):
+        """a name, or the number as it is (the library refuses an unknown one)"""
+        if isinstance(linkage, str):
+            if linkage not in cls._LINKAGES:
+                raise ValueError("linkage is 'single', 'complete' or 'average', got %r" % (linkage,))
+            return cls._LINKAGES[linkage]
+        return int(linkage)
+
+    def linkage_threshold(self, threshold, linkage="complete", estim=ESTIM_ERTL_MLE, result_type=JI, k=31):
+        """(labels uint32 [n], n_clusters): labels[x] = the smallest slot of x's cluster after agglomerating, best pair
+        first, while a pair of clusters passes the threshold under the linkage"""
+        labels = np.zeros(self.n, np.uint32)
+        nc = C.c_uint64()
+        self._ck(self._derive("dsh_linkage_threshold")(self._h, estim, result_type, k, threshold, self._linkage(linkage),
+                                                       labels.ctypes.data if labels.size else None, C.byref(nc)))
+        return labels, int(nc.value)
+
+    def linkage_threshold_device(self, labels_ptr, threshold, linkage="complete", estim=ESTIM_ERTL_MLE, result_type=JI, k=31):
+        """labels into the caller's device buffer (uint32 [n]); returns n_clusters"""
+        nc = C.c_uint64()
+        self._ck(self._derive("dsh_linkage_threshold_device")(self._h, estim, result_type, k, threshold, self._linkage(linkage),
+                                                              C.c_void_p(labels_ptr), C.byref(nc)))
+        return int(nc.value)
+
+    def linkage_tri(self, n_nodes, tri, threshold, linkage, descending=False):
+        """(labels, n_clusters) for a caller's values: tri holds n_nodes (n_nodes - 1) / 2 float32 in dsh_tri_index order
+        (np.triu_indices(n_nodes, 1)).  Needs no sketches."""
+        tri = np.ascontiguousarray(tri, np.float32).reshape(-1)
+        n_nodes = int(n_nodes)
+        if n_nodes >= 0 and tri.size != n_nodes * (n_nodes - 1) // 2:
+            raise ValueError("tri holds n_nodes (n_nodes - 1) / 2 values")
+        labels = np.zeros(max(n_nodes, 0), np.uint32)
+        nc = C.c_uint64()
+        self._ck(self._derive("dsh_linkage_tri")(self._h, n_nodes, tri.ctypes.data if tri.size else None, 1 if descending else 0,
+                                                 threshold, self._linkage(linkage), labels.ctypes.data if labels.size else None,
+                                                 C.byref(nc)))
+        return labels, int(nc.value)
 
     # ---- greedy representatives in slot order (include/dashing_hip.h has the contract)
     def greedy_threshold(self, threshold, estim=ESTIM_ERTL_MLE, result_type=JI, k=31):

@@ -61,7 +61,8 @@ static void release_ctx(dsh_ctx *c)
                       &c->pairs_rhs, &c->pairs_out, &c->pairs_err, &c->derive_err, &c->derive_stage, &c->derive_ptr, &c->derive_mem,
                       &c->derive_dst, &c->derive_part[0], &c->derive_part[1], &c->derive_out, &c->cc_parent, &c->cc_state, &c->cc_lhs,
                       &c->cc_rhs, &c->cc_rowptr, &c->cc_seed, &c->cc_labels, &c->gr_assign, &c->gr_state, &c->gr_labels, &c->gr_best,
-                      &c->gs_labels, &c->gs_acc, &c->gs_grp, &c->gs_out, &c->gs_csr, &c->hs_edges, &c->hs_labels, &c->hs_counts})
+                      &c->gs_labels, &c->gs_acc, &c->gs_grp, &c->gs_out, &c->gs_csr, &c->hs_edges, &c->hs_labels, &c->hs_counts,
+                      &c->lk_tab, &c->lk_cells, &c->lk_nodes, &c->lk_labels, &c->lk_state})
         b->release();
     if (c->pin_perm) (void)hipHostFree(c->pin_perm);
     c->pin_perm = nullptr;
@@ -1010,6 +1011,7 @@ int dsh_get_info(dsh_ctx *c, const char *name, int64_t *out)
     else if (!std::strcmp(name, "fastx_decode_us")) *out = (int64_t)(c->fastx_ms * 1000.0);
     else if (!std::strcmp(name, "xch_recv_gated")) *out = c->xch_recv_gated ? 1 : 0;
     else if (!std::strcmp(name, "stats_route")) *out = c->stats_route_last;
+    else if (!std::strcmp(name, "linkage_route")) *out = c->linkage_route_last;
     else if (!std::strcmp(name, "place_kernel_us")) *out = (int64_t)(c->place_ms * 1000.0);
     else if (!std::strcmp(name, "whatif_mfma")) {
 #ifdef DSH_WHATIF_MFMA
@@ -1085,6 +1087,26 @@ int dsh_set_option(dsh_ctx *c, const char *name, int64_t v)
     if (!std::strcmp(name, "stats_route")) {
         if (v < -1 || v > 1) return fail(c, DSH_EINVAL, "stats_route must be -1 (auto), 0 (dense) or 1 (pairs)");
         c->stats_route = (int)v;
+        return DSH_OK;
+    }
+    if (!std::strcmp(name, "linkage_route")) {
+        if (v < -1 || v > 1) return fail(c, DSH_EINVAL, "linkage_route must be -1 (auto), 0 (dense) or 1 (pairs)");
+        c->linkage_route = (int)v;
+        return DSH_OK;
+    }
+    if (!std::strcmp(name, "linkage_partition")) {
+        if (v < 0 || v > 1) return fail(c, DSH_EINVAL, "linkage_partition must be 0 or 1");
+        c->linkage_partition = (int)v;
+        return DSH_OK;
+    }
+    if (!std::strcmp(name, "linkage_budget_bytes")) {
+        if (v < 64) return fail(c, DSH_EINVAL, "linkage_budget_bytes must be at least 64");
+        c->linkage_budget = (uint64_t)v;
+        return DSH_OK;
+    }
+    if (!std::strcmp(name, "linkage_lds_max")) {  // 6144 members x 24 bytes + the reduction's 6 KiB = 150 KiB of the 160 KiB of LDS
+        if (v < 0 || v > 6144) return fail(c, DSH_EINVAL, "linkage_lds_max must be in [0, 6144]");
+        c->linkage_lds_max = (uint32_t)v;
         return DSH_OK;
     }
     if (!std::strcmp(name, "greedy_band_rows")) {

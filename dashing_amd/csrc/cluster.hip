@@ -16,6 +16,10 @@ struct CcState {  // cc_state on the device
     uint32_t err, pad_;
 };
 
+}  // namespace
+
+namespace dsh {  // (ctx.h: dsh_linkage_* partitions by the same components)
+
 int cc_begin(dsh_ctx *c, uint64_t n)
 {
     HIPCHK(c, c->cc_parent.ensure(std::max<uint64_t>(n, 1) * sizeof(uint32_t)));
@@ -27,16 +31,6 @@ int cc_begin(dsh_ctx *c, uint64_t n)
 
 uint32_t *cc_err(dsh_ctx *c) { return &((CcState *)c->cc_state.ptr)->err; }
 uint32_t cc_cap(uint64_t n) { return (uint32_t)std::min<uint64_t>(n + 1, 0xFFFFFFFFull); }
-
-// an earlier labelling (host [n], validated) to continue from
-int cc_seed(dsh_ctx *c, uint64_t n, const uint32_t *labels_in)
-{
-    if (!labels_in || !n) return DSH_OK;
-    HIPCHK(c, c->cc_seed.ensure(n * sizeof(uint32_t)));
-    HIPCHK(c, hipMemcpyAsync(c->cc_seed.ptr, labels_in, n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, launch_cc_seed(c->stream, (uint32_t *)c->cc_parent.ptr, (const uint32_t *)c->cc_seed.ptr, n, cc_cap(n), cc_err(c)));
-    return DSH_OK;
-}
 
 // labels and the root count; the one wait of a call.  d_labels: the caller's device buffer, or nullptr for h_labels (host)
 int cc_finish(dsh_ctx *c, uint64_t n, uint32_t *d_labels, uint32_t *h_labels, uint64_t *n_clusters)
@@ -53,6 +47,20 @@ int cc_finish(dsh_ctx *c, uint64_t n, uint32_t *d_labels, uint32_t *h_labels, ui
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (h.err) return fail(c, DSH_EIO, "internal: union-find step bound exceeded (code %u)", h.err);
     if (n_clusters) *n_clusters = h.n_roots;
+    return DSH_OK;
+}
+
+}  // namespace dsh
+
+namespace {
+
+// an earlier labelling (host [n], validated) to continue from
+int cc_seed(dsh_ctx *c, uint64_t n, const uint32_t *labels_in)
+{
+    if (!labels_in || !n) return DSH_OK;
+    HIPCHK(c, c->cc_seed.ensure(n * sizeof(uint32_t)));
+    HIPCHK(c, hipMemcpyAsync(c->cc_seed.ptr, labels_in, n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, launch_cc_seed(c->stream, (uint32_t *)c->cc_parent.ptr, (const uint32_t *)c->cc_seed.ptr, n, cc_cap(n), cc_err(c)));
     return DSH_OK;
 }
 

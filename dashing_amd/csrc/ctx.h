@@ -208,6 +208,14 @@ struct dsh_ctx {
     int hs_cus = 0;                     // compute units of the device (hipDeviceAttributeMultiprocessorCount), queried once
     int stats_route = -1;               // option: -1 auto | 0 dense | 1 pairs
     int stats_route_last = -1;          // (info) the route the last dsh_group_stats* call took
+    // dsh_linkage_* (linkage.hip): the components' tables (comp | rank | moff | coff | mem), the cell matrices of a batch, the
+    // state of its members, the labels before they go out, and the count of clusters + the error word
+    DevBuf lk_tab, lk_cells, lk_nodes, lk_labels, lk_state;
+    uint64_t linkage_budget = 8ull << 30;  // option linkage_budget_bytes: the matrices of a batch of components
+    uint32_t linkage_lds_max = 4096;    // option: components of at most this many members keep their per-row state in LDS
+    int linkage_partition = 1;          // option: 0 = the whole collection as one component
+    int linkage_route = -1;             // option: -1 auto | 0 dense | 1 pairs
+    int linkage_route_last = -1;        // (info) the route the last dsh_linkage_threshold* call took
     uint64_t greedy_band_rows = 4096;   // option: a band holds at most this many rows (k_greedy_diag's LDS; 1..kGreedyMaxRows)
     // dsh_fold*, dsh_upload_sketches_folded*, dsh_union_groups* (derive.hip): the error word, a chunk of source rows or of
     // folded rows on its way through the device, the groups' CSR and the partial unions of groups cut into chunks
@@ -405,6 +413,13 @@ int pairs_err_begin(dsh_ctx *c);                // the two error words set to "n
 int pairs_run_chunk(dsh_ctx *c, const PairsQuery &q, const uint32_t *d_lhs, const uint32_t *d_rhs, uint64_t xbase, uint64_t cnt,
                     float *d_out, uint64_t out_stride);
 int pairs_err_end(dsh_ctx *c);                  // the one wait: reads the error words, fails the call on either
+
+// cluster.hip: the union-find of a call on the ctx stream -- parent[n] and the state word set up; the labels and the root count,
+// which is the one wait (d_labels: a device buffer, or nullptr for h_labels on the host)
+int cc_begin(dsh_ctx *c, uint64_t n);
+uint32_t *cc_err(dsh_ctx *c);
+uint32_t cc_cap(uint64_t n);
+int cc_finish(dsh_ctx *c, uint64_t n, uint32_t *d_labels, uint32_t *h_labels, uint64_t *n_clusters);
 
 // exchange.hip: waits for both streams of the communicator's traffic and destroys it (no-op without one)
 int comm_release(dsh_ctx *c);

@@ -99,6 +99,11 @@ static void usage(const char *sub)
             "                           output order, clusters numbered from 0 by their first member, which represents them;\n"
             "                           -b: u64 n, u64 n_clusters, u32 labels[n] (label = slot of the representative).  Not with\n"
             "                           --threshold, --nearest-neighbors, --pairs, -Q, -U, -T or several devices.\n"
+            "  --linkage NAME           with --cluster: single [default: the components above], complete or average -- agglomerate,\n"
+            "                           best pair of clusters first, while a pair passes FLOAT under the linkage (worst member\n"
+            "                           pair; exact mean of the member pairs in units of 2^-30), on the device (dsh_linkage_threshold).\n"
+            "                           With complete or average the '#Cluster' line gains a fifth field, the linkage; -b is the same.\n"
+            "                           average not with --sizes.\n"
             "  --representatives FLOAT  emit greedy representatives at FLOAT instead of distances: walk the inputs in output order\n"
             "                           (largest file first by default, the order given with --avoid-sorting); an input that no\n"
             "                           earlier representative passes --threshold FLOAT's test with becomes a representative, every\n"
@@ -155,6 +160,7 @@ struct Opts {
     unsigned nneighbors = 0;  // --nearest-neighbors
     bool has_threshold = false;  // --threshold: only the pairs that pass, as (name, name, value) lines or CSR (-b)
     float threshold = 0.f;
+    int linkage = -1;          // --linkage: -1 not given, else DSH_LINKAGE_* (complete / average: dsh_linkage_threshold)
     bool has_cluster = false;  // --cluster: the connected components of --threshold's graph (dsh_cluster_threshold)
     float cluster_t = 0.f;
     bool has_reps = false;  // --representatives: the greedy pass in output order over --threshold's graph (dsh_greedy_threshold)
@@ -280,7 +286,7 @@ static float float_option(const char *flag, const char *arg)
     return v;
 }
 
-enum { OPT_PRESKETCHED = 1000, OPT_AVOID_SORT, OPT_DEVICE, OPT_NPERBATCH, OPT_NN, OPT_NGPUS, OPT_DEVICES, OPT_RCCL, OPT_THRESHOLD, OPT_CLUSTER, OPT_REPS, OPT_ASSIGN, OPT_EXTEND, OPT_STATS, OPT_HISTOGRAM, OPT_HISTOGRAM_LABELS, OPT_PAIRS, OPT_MEASURES, OPT_GROUPS, OPT_UNSUPPORTED };
+enum { OPT_PRESKETCHED = 1000, OPT_AVOID_SORT, OPT_DEVICE, OPT_NPERBATCH, OPT_NN, OPT_NGPUS, OPT_DEVICES, OPT_RCCL, OPT_THRESHOLD, OPT_CLUSTER, OPT_LINKAGE, OPT_REPS, OPT_ASSIGN, OPT_EXTEND, OPT_STATS, OPT_HISTOGRAM, OPT_HISTOGRAM_LABELS, OPT_PAIRS, OPT_MEASURES, OPT_GROUPS, OPT_UNSUPPORTED };
 
 static Opts parse(int argc, char **argv, bool is_dist)
 {
@@ -307,7 +313,7 @@ static Opts parse(int argc, char **argv, bool is_dist)
         {"use-bloom-filter", no_argument, nullptr, OPT_UNSUPPORTED}, {"use-nthash", no_argument, nullptr, OPT_UNSUPPORTED},
         {"use-cyclic-hash", no_argument, nullptr, OPT_UNSUPPORTED}, {"countmin", no_argument, nullptr, OPT_UNSUPPORTED},
         {"nearest-neighbors", required_argument, nullptr, OPT_NN}, {"threshold", required_argument, nullptr, OPT_THRESHOLD},
-        {"cluster", required_argument, nullptr, OPT_CLUSTER}, {"representatives", required_argument, nullptr, OPT_REPS},
+        {"cluster", required_argument, nullptr, OPT_CLUSTER}, {"linkage", required_argument, nullptr, OPT_LINKAGE}, {"representatives", required_argument, nullptr, OPT_REPS},
         {"assign", required_argument, nullptr, OPT_ASSIGN}, {"extend", required_argument, nullptr, OPT_EXTEND},
         {"stats", no_argument, nullptr, OPT_STATS},
         {"histogram", required_argument, nullptr, OPT_HISTOGRAM}, {"histogram-labels", required_argument, nullptr, OPT_HISTOGRAM_LABELS},
@@ -377,6 +383,11 @@ static Opts parse(int argc, char **argv, bool is_dist)
             break;
         case OPT_THRESHOLD: o.threshold = float_option("--threshold", optarg), o.has_threshold = true; break;
         case OPT_CLUSTER: o.cluster_t = float_option("--cluster", optarg), o.has_cluster = true; break;
+        case OPT_LINKAGE:
+            o.linkage = !std::strcmp(optarg, "single") ? DSH_LINKAGE_SINGLE : !std::strcmp(optarg, "complete") ? DSH_LINKAGE_COMPLETE
+                        : !std::strcmp(optarg, "average") ? DSH_LINKAGE_AVERAGE : -1;
+            if (o.linkage < 0) die("--linkage takes single, complete or average, not '%s'.", optarg);
+            break;
         case OPT_REPS: o.reps_t = float_option("--representatives", optarg), o.has_reps = true; break;
         case OPT_ASSIGN:
             if (!std::strcmp(optarg, "first")) o.assign_mode = DSH_GREEDY_FIRST;
@@ -1178,6 +1189,8 @@ static void refuse_conflicts(const Opts &o, bool by_seq)
         if (o.fmt == FULL_TSV) die("--cluster does not go with -T: the output is one line per input.");
         if (o.devices.size() > 1 || o.rccl) die("--cluster runs on one device: --ngpus / --devices are not supported.");
     }
+    if (o.linkage >= 0 && !o.has_cluster) die("--linkage goes with --cluster only.");
+    if (o.linkage == DSH_LINKAGE_AVERAGE && o.result_type == DSH_SIZES) die("--linkage average does not go with --sizes: it judges values in (-2, 2).");
     if (o.has_reps) {  // (what --cluster refuses, and --cluster)
         if (o.has_cluster) die("--representatives does not go with --cluster: choose the representatives or the components.");
         if (o.has_threshold) die("--representatives does not go with --threshold: choose the representatives or the pairs.");
@@ -1530,7 +1543,10 @@ static void emit_labelling(const DistRun &r, std::FILE *fp)
     const float t = reps ? o.reps_t : o.cluster_t;
     std::vector<uint32_t> labels(std::max<size_t>(n, 1));
     uint64_t count = 0;
-    if (!reps) {
+    const bool linked = !reps && o.linkage > DSH_LINKAGE_SINGLE;  // (single, given or not: the components, every byte as before)
+    if (linked) {
+        DSH(r.ctx, dsh_linkage_threshold(r.ctx, o.estim, o.result_type, o.k, t, o.linkage, labels.data(), &count));
+    } else if (!reps) {
         DSH(r.ctx, dsh_cluster_threshold(r.ctx, o.estim, o.result_type, o.k, t, labels.data(), &count));
     } else {
         if (r.extend_labels.size() > n) die("--extend: %s labels %zu inputs but this run has only %zu", o.extend_file.c_str(), r.extend_labels.size(), n);
@@ -1548,8 +1564,8 @@ static void emit_labelling(const DistRun &r, std::FILE *fp)
         if (o.has_stats) gs.write_binary(fp, n);
         return;
     }
-    std::fprintf(fp, "#%s\t%s\t%s\t%.6g\n", reps ? "Representatives" : "Cluster", kMeasureNames[o.result_type], is_distance(o.result_type) ? "<=" : ">=",
-                 (double)t);  // --threshold's number format
+    std::fprintf(fp, "#%s\t%s\t%s\t%.6g%s\n", reps ? "Representatives" : "Cluster", kMeasureNames[o.result_type], is_distance(o.result_type) ? "<=" : ">=",
+                 (double)t, !linked ? "" : o.linkage == DSH_LINKAGE_COMPLETE ? "\tcomplete" : "\taverage");  // --threshold's number format
     // --representatives: the value of every non-representative against its label: ONE list of pairs (lhs = the input, rhs =
     // its representative), by dsh_dist_pairs' contract bit for bit the triangle's value
     std::vector<uint32_t> plhs, prhs;

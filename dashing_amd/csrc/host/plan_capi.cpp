@@ -2,7 +2,8 @@
 // per-sketch keys exactly as engine.hip does and checks the plan against its contract, so the schedule that replaces
 // dist_loop / perform_core_op (src/sketch_and_cmp.h:785-880, :699-710) is unit-tested without a GPU
 // (tests/test_plan.py).  Also the sequential build of the clusters' union-find (dsh_plan_uf_labels, at the end) and the band rule of
-// the greedy representatives (dshh_greedy_bands) and the band walk all five band consumers share (dshh_threshold_bands).  Built into
+// the greedy representatives (dshh_greedy_bands) and the band walk all five band consumers share (dshh_threshold_bands), and the
+// sequential build of the linkage clusters (dsh_plan_linkage_labels, dsh_plan_linkage_loose: ../linkage.h).  Built into
 // libdashing_host.so; not part of the GPU C-ABI.
 #include <algorithm>
 #include <cstdarg>
@@ -10,6 +11,7 @@
 #include <cstring>
 #include <vector>
 
+#include "../linkage.h"
 #include "../plan.h"
 #include "../uf.h"
 
@@ -478,5 +480,58 @@ int dsh_plan_uf_labels(uint64_t n, const uint32_t *lhs, const uint32_t *rhs, uin
     }
     return 0;
 }
+
+}  // extern "C"
+
+namespace {
+
+template <int L>
+int linkage_labels(uint64_t n, const float *tri, const LkThr &thr, uint32_t *labels, uint32_t step_cap)
+{
+    typedef typename LkCell<L>::T T;
+    const uint32_t m = (uint32_t)n;
+    std::vector<T> cells((size_t)m * m, T(0)), nnv(m);
+    std::vector<uint32_t> alive(m), size(m), nn(m), root(m);
+    for (uint32_t i = 0; i < m; ++i)
+        for (uint32_t j = i + 1; j < m; ++j)
+            cells[(size_t)i * m + j] = cells[(size_t)j * m + i] = lk_cell<L>(tri[tri_index(n, i, j)], thr.descending);
+    const uint32_t rc = lk_run_seq<L>(m, cells.data(), alive.data(), size.data(), nn.data(), nnv.data(), root.data(), thr, step_cap, m + 1);
+    for (uint32_t i = 0; i < m; ++i) labels[i] = root[i];
+    return (int)rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+// the linkage clusters at a threshold (../linkage.h, the step logic the device kernel compiles) run sequentially with the
+// whole collection as ONE component: labels[x] = the smallest slot of x's final cluster for the n (n - 1) / 2 values of tri
+// (dsh_tri_index order).  Returns 0, -1 for a bad argument (an unknown linkage, n above 2^16, AVERAGE with |t| >= 2), and the
+// give-up code (1) when the merges overran step_cap -- the path the device kernel must never reach
+// (tests/test_linkage_host.py).  A NaN threshold gives n singletons.
+int dsh_plan_linkage_labels(uint64_t n, const float *tri, int descending, float threshold, int linkage, uint32_t *labels,
+                            uint64_t *n_clusters, uint32_t step_cap)
+{
+    if (n > 65536 || linkage < kLkSingle || linkage > kLkAverage || (n && !labels) || (n > 1 && !tri)) return -1;
+    if (linkage == kLkAverage && threshold == threshold && !(fabsf(threshold) < 2.f)) return -1;
+    int rc = 0;
+    if (threshold != threshold) {
+        for (uint64_t x = 0; x < n; ++x) labels[x] = (uint32_t)x;
+    } else {
+        const LkThr thr = lk_threshold(threshold, descending ? 1 : 0);
+        rc = linkage == kLkSingle     ? linkage_labels<kLkSingle>(n, tri, thr, labels, step_cap)
+             : linkage == kLkComplete ? linkage_labels<kLkComplete>(n, tri, thr, labels, step_cap)
+                                      : linkage_labels<kLkAverage>(n, tri, thr, labels, step_cap);
+    }
+    if (n_clusters) {
+        *n_clusters = 0;
+        for (uint64_t x = 0; x < n; ++x) *n_clusters += labels[x] == x;
+    }
+    return rc;
+}
+
+// the loose float threshold of the AVERAGE partition (lk_loose_threshold) and q(v), for the CPU tests
+float dsh_plan_linkage_loose(float threshold, int descending) { return lk_loose_threshold(threshold, descending ? 1 : 0); }
+int64_t dsh_plan_linkage_q(float v) { return lk_q(v); }
 
 }  // extern "C"

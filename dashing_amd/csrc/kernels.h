@@ -252,6 +252,34 @@ hipError_t launch_gs_pairs(hipStream_t st, const uint32_t *lhs, const uint32_t *
 hipError_t launch_gs_finish(hipStream_t st, const uint32_t *labels, uint64_t n, int descending, const GsAccum &a, uint32_t *g_cnt,
                             uint64_t *g_sum, uint32_t *g_slot, uint32_t *medoid_out, uint32_t *cnt_out, int64_t *sum_out, float *worst_out);
 
+// linkage clusters at a threshold (kernels_linkage.hip, linkage.hip, linkage.h): the components of at least two members as a
+// member CSR on the device, and the batch of them whose m x m cell matrices (uint32 keys, int64 sums for AVERAGE) are resident
+struct LkComps {
+    const uint32_t *comp;  // [n] the component of a slot, 0xFFFFFFFF: none (a singleton)
+    const uint32_t *rank;  // [n] its index inside the component (its rank in slot order)
+    const uint32_t *moff;  // [components + 1] the component's first member in mem
+    const uint64_t *coff;  // [components] the first cell of its matrix in the scratch of its batch
+    const uint32_t *mem;   // the members, slots ascending inside a component
+};
+struct LkBatch {
+    uint32_t c0, c1;   // the components of the batch
+    void *cells;       // their matrices
+    uint64_t ncells;   // cells the scratch holds: no store goes beyond
+    void *state;       // nnv | size | nn | root | alive for the batch's members (the components above lds_max use theirs)
+    uint32_t mbase;    // moff[c0]
+    uint32_t members;  // moff[c1] - moff[c0]
+};
+// a band of triangle rows as launch_thr_count takes it: the values inside a component of the batch become cells
+hipError_t launch_lk_fill_band(hipStream_t st, int linkage, const float *vals, const ThrRows &g, const LkComps &C, const LkBatch &B, int descending);
+// the same for the values of cnt pairs of slots below n
+hipError_t launch_lk_fill_pairs(hipStream_t st, int linkage, const uint32_t *lhs, const uint32_t *rhs, const float *vals, uint64_t cnt,
+                                uint64_t n, const LkComps &C, const LkBatch &B, int descending);
+// one workgroup per component of the batch: labels[member] = the smallest slot of its final cluster.  lds_members: the largest
+// component of the batch that is at most lds_max; cap bounds every loop (the largest m + 1); err: one device word, starts at 0
+hipError_t launch_linkage(hipStream_t st, int linkage, const LkComps &C, const LkBatch &B, float threshold, int descending, uint32_t lds_max,
+                          uint32_t lds_members, uint32_t cap, uint32_t *labels, uint32_t *err);
+size_t linkage_lds_bytes(int linkage, uint32_t m);  // LDS of a workgroup of k_linkage whose state holds m members
+
 // value histograms (kernels_hist.hip, hist.hip): a band of triangle or rectangle rows as launch_thr_count takes it, counted
 // into counts[planes][n_edges + 2] (device, 64-bit adds: the caller zeroes it) over the n_edges strictly increasing edges at
 // d_edges (device); class(v) = the edges that pass v as a threshold would, NaN = n_edges + 1.  labels == nullptr: one plane;

@@ -63,7 +63,8 @@ typedef struct dsh_ctx dsh_ctx;
  * dsh_dist_threshold, dsh_dist_threshold_device, dsh_dist_rect_threshold, dsh_dist_pairs*, dsh_fold*,
  * dsh_upload_sketches_folded*, dsh_union_groups*, dsh_cluster_threshold, dsh_cluster_threshold_device, dsh_cluster_pairs,
  * dsh_cluster_csr, dsh_greedy_threshold, dsh_greedy_threshold_device, dsh_greedy_extend, dsh_greedy_extend_device,
- * dsh_group_stats, dsh_group_stats_device, dsh_dist_histogram, dsh_dist_histogram_device, dsh_dist_rect_histogram. */
+ * dsh_group_stats, dsh_group_stats_device, dsh_dist_histogram, dsh_dist_histogram_device, dsh_dist_rect_histogram,
+ * dsh_linkage_threshold, dsh_linkage_threshold_device, dsh_linkage_tri. */
 #define DSH_ABI_VERSION 7
 int dsh_abi_version(void);
 
@@ -394,8 +395,8 @@ int dsh_union_groups_device(dsh_ctx *ctx, const uint64_t *group_ptr, const uint3
  *   Synchronous, on the ctx stream.  Cost model: the dense path's cost for the triangle plus ONE read of
  *     each band (4 bytes per pair) and two small reads of parent[] per hit; dsh_dist_threshold_device + dsh_cluster_csr
  *     reads each band twice and writes 8 bytes per hit.  Not yet measured on the device (tools/bench_cluster.py does it).
- *   Not built: a multi-GPU form (merge per-rank labels with dsh_cluster_pairs' labels_in), clusters of a rectangle, and
- *     linkages other than single. */
+ *   Not built: a multi-GPU form (merge per-rank labels with dsh_cluster_pairs' labels_in) and clusters of a rectangle.
+ *     Complete and average linkage: dsh_linkage_* below. */
 int dsh_cluster_threshold(dsh_ctx *ctx, int estim, int result_type, int k, float threshold, uint32_t *labels_out,
                           uint64_t *n_clusters);
 int dsh_cluster_threshold_device(dsh_ctx *ctx, int estim, int result_type, int k, float threshold, void *d_labels,
@@ -404,6 +405,77 @@ int dsh_cluster_pairs(dsh_ctx *ctx, uint64_t n_nodes, const uint32_t *lhs, const
                       const uint32_t *labels_in, uint32_t *labels_out, uint64_t *n_clusters);
 int dsh_cluster_csr(dsh_ctx *ctx, uint64_t n_nodes, uint64_t row_begin, uint64_t rows, const uint64_t *row_ptr, const uint32_t *col,
                     const uint32_t *labels_in, uint32_t *labels_out, uint64_t *n_clusters);
+
+/* ---- single-, complete- and average-linkage clusters at a threshold --------------------------------------
+ * Replaces what a clustering client (dRep's primary step, ANI / Mash pipelines) does when it cuts an average- or
+ * complete-linkage tree at a threshold: pull the dense matrix to the host and run a host `linkage` on it.  Here the
+ * agglomeration runs on the device, component by component, and `n` labels leave it.
+ *   Values.  v(x, y), x != y, is the float32 that dsh_dist_rows leaves at dsh_tri_index(n, min, max): the ONE orientation
+ *     of the triangle (dsh_linkage_tri: the caller's tri[dsh_tri_index(n, min, max)]).  desc = the measure is a similarity
+ *     (better = larger; the *_DIST forms: better = smaller; dsh_linkage_tri: the caller's `descending`).  Floats compare as
+ *     integer keys of the same order compare them: -0.0 equals +0.0, +-inf are ordinary values, NaN is special (below).
+ *     q(v) = llrint((double)v * 2^DSH_STATS_FRAC_BITS), exactly as dsh_group_stats defines it.
+ *   Clusters.  A cluster is a set of slots, its label its smallest slot; at the start every slot is a cluster.  For two
+ *     clusters A != B the pair is either BLOCKED or has a value D(A, B):
+ *       DSH_LINKAGE_SINGLE    the best v over the member pairs that are not NaN; blocked iff all of them are NaN
+ *       DSH_LINKAGE_COMPLETE  the worst v over the member pairs; blocked iff any is NaN
+ *       DSH_LINKAGE_AVERAGE   the exact rational S / c, S = the sum of q(v) over the member pairs (int64), c = |A| |B|;
+ *                             blocked iff any member pair is NaN or has |v| >= 2 (the rule dsh_group_stats includes a pair by)
+ *     D passes the threshold t iff, SINGLE and COMPLETE: the float predicate of dsh_dist_threshold (>= for similarities, <=
+ *     for distances, NaN never); AVERAGE: S >= Q c (similarity) or S <= Q c (distance) with Q = q(t), compared exactly in
+ *     128-bit integers.  AVERAGE therefore judges QUANTISED values: a value within 2^-31 of t may be judged equal to t.
+ *   The procedure (the definition, not the implementation).  While some unblocked pair of current clusters passes, take the
+ *     one with the best D -- AVERAGE: the rationals compared exactly by cross-multiplication -- ties to the
+ *     lexicographically smallest (label(A), label(B)) with label(A) < label(B); replace A and B by their union.
+ *     labels[x] is the label of x's final cluster, *n_clusters the number of x with labels[x] == x.  This has one answer:
+ *     it depends on no band size, route, partition, launch geometry or order of arrival, and the same call gives the same
+ *     bytes.
+ *   Consequences.  SINGLE equals dsh_cluster_threshold byte for byte (it exists as the check of the machinery: it agglomerates
+ *     every component pair by pair, so call dsh_cluster_threshold for single linkage).  Every COMPLETE or AVERAGE cluster lies
+ *     inside one SINGLE cluster at the same t (AVERAGE: at the loose threshold below).  In a COMPLETE cluster every member's
+ *     `worst` of dsh_group_stats passes t.  The Lance-Williams updates are exact in this arithmetic: the best or worst of two
+ *     keys, S(A u B, C) = S(A, C) + S(B, C), and blocked is absorbing for COMPLETE and AVERAGE.
+ *   How.  Every merge needs a passing member pair, so the connected components of the graph of passing pairs
+ *     split the problem: they come from the union-find of dsh_cluster_threshold at t -- for AVERAGE at the loose float
+ *     threshold t' whose graph is the quantised one (distance: the largest float32 with q(t') <= Q; similarity: the smallest
+ *     with q(t') >= Q).  Components of one slot are done.  Each of the others gets an m x m matrix of cells (uint32 keys;
+ *     int64 sums for AVERAGE) in device scratch and ONE workgroup (k_linkage), which agglomerates it to the end with a
+ *     nearest-neighbour entry per row; components run side by side in batches whose matrices fit "linkage_budget_bytes"
+ *     (default 8 GiB).  The matrices are filled by one of two routes, as in dsh_group_stats: dense (the band walk again, a
+ *     kernel that stores the pairs inside a component) or pairs (the intra-component pairs enumerated on the device and
+ *     computed by the direct pair path).  Option "linkage_route": -1 auto | 0 dense | 1 pairs; auto takes pairs iff
+ *     20 P_in <= n (n - 1) / 2, P_in the pairs inside components; dsh_get_info(ctx, "linkage_route") is the route the last
+ *     dsh_linkage_threshold* call took.  With several batches the dense route walks the triangle once per batch.
+ *     "linkage_partition" 0 treats the whole collection as one component; "linkage_lds_max" (default 4096, at most 6144) is
+ *     the largest component whose per-row state lives in LDS rather than in global scratch.  No result depends on an option.
+ *     Every loop of the kernel counts against the component's size + 1; an overrun -- unreachable in a correct kernel --
+ *     fails the call with DSH_EIO and the message "internal: linkage step bound exceeded".
+ *   dsh_linkage_threshold         labels_out: host uint32 [n].
+ *   dsh_linkage_threshold_device  d_labels: caller-owned DEVICE uint32 [n]; exactly n labels are written.
+ *   dsh_linkage_tri               the same for a caller's values (ANI, say): tri holds n_nodes (n_nodes - 1) / 2 float32 in host
+ *                                 memory in dsh_tri_index order; no sketches are needed, only the stream and scratch.  The
+ *                                 triangle travels through the band buffer ("threshold_band_bytes") band by band, once for the
+ *                                 components and once per batch.
+ *   Synchronous, on the ctx stream; the only host wait beyond the final one is the one the component labels need.  The effects
+ *     on cached state are those of dsh_cluster_threshold, plus those of dsh_dist_pairs_device on the pairs route: a dense call
+ *     before and a dense call after give the same bytes.
+ *   Errors, before anything is enqueued: as dsh_cluster_threshold (DSH_ESTATE without sketches, n > 2^32 - 1); DSH_EINVAL for
+ *     an unknown linkage, AVERAGE with DSH_SIZES, AVERAGE with |threshold| >= 2, n_nodes > 2^32 - 1 and a NULL tri with
+ *     n_nodes >= 2.  After the component labels: DSH_ENOMEM, with a message that names m and the bytes, for one component whose
+ *     matrix exceeds "linkage_budget_bytes" (or, AVERAGE, of more than 65536 members: its sums are 64-bit); the context stays
+ *     usable.  A NaN threshold gives n singletons; n == 0 and n == 1 succeed.
+ *   Not built: the merge list (a dendrogram), a component larger than one workgroup's budget spread over several workgroups,
+ *     Ward / centroid linkages, a multi-GPU form.  Cost: about 1-2 ms per merge step of a component of ~3000 members on an MI355X
+ *     (DESIGN.md 4.15); tools/bench_linkage.py is the benchmark, which has not been run to its end. */
+#define DSH_LINKAGE_SINGLE 0
+#define DSH_LINKAGE_COMPLETE 1
+#define DSH_LINKAGE_AVERAGE 2
+int dsh_linkage_threshold(dsh_ctx *ctx, int estim, int result_type, int k, float threshold, int linkage, uint32_t *labels_out,
+                          uint64_t *n_clusters);
+int dsh_linkage_threshold_device(dsh_ctx *ctx, int estim, int result_type, int k, float threshold, int linkage, void *d_labels,
+                                 uint64_t *n_clusters);
+int dsh_linkage_tri(dsh_ctx *ctx, uint64_t n_nodes, const float *tri, int descending, float threshold, int linkage,
+                    uint32_t *labels_out, uint64_t *n_clusters);
 
 /* ---- greedy representatives at a threshold: the greedy pass in slot order, on the device ---------------
  * Replaces what a dereplication client does with the hits of dsh_dist_threshold* when it wants REPRESENTATIVES rather than
@@ -846,6 +918,11 @@ int dsh_finalize_phase_cycles(dsh_ctx *ctx, uint64_t *out16);
  *                 "cluster_chunk"           dsh_cluster_pairs / dsh_cluster_csr unite at most this many edges per launch (2^20)
  *                 "greedy_band_rows"        a band of dsh_greedy_threshold* holds at most this many rows (4096; 1..8192)
  *                 "stats_route"             -1 auto | 0 dense | 1 pairs: how dsh_group_stats* computes the intra-group values
+ *                 "linkage_budget_bytes"    the cell matrices of a batch of components of dsh_linkage_* (8 GiB)
+ *                 "linkage_route"           -1 auto | 0 dense | 1 pairs: how dsh_linkage_threshold* fills them
+ *                 "linkage_partition"       1 | 0: 0 = the whole collection as ONE component of dsh_linkage_*
+ *                 "linkage_lds_max"         0..6144 (default 4096): components of dsh_linkage_* up to this size keep their
+ *                                           per-row state in LDS, larger ones in global scratch
  *                 "derive_chunk_bytes"      the host forms of dsh_fold / dsh_upload_sketches_folded move at most this many bytes
  *                                           of source rows per step (256 MiB; at least one row)
  *   layout        "sort"                    -1 auto | 0 | 1: key-ordered plane columns (0 = identity: the slow, simple layout)
@@ -885,7 +962,8 @@ int dsh_set_option(dsh_ctx *ctx, const char *name, int64_t value);
  * "words_per_plane", "avg_tile_planes_x100" (of the last dist call), "frag_items", "parts_done", "parts_signalled",
  * "place_kernel_us" (with profiling on: device time of the last dsh_exchange_place_device's placement kernel),
  * "sketch_kernel_us" / "fastx_decode_us" (with profiling on: k_sketch / the FASTA-FASTQ decode kernels of the last sketch call),
- * "stats_route" (the route the last dsh_group_stats* call took: 0 dense, 1 pairs; -1 before the first). */
+ * "stats_route" (the route the last dsh_group_stats* call took: 0 dense, 1 pairs; -1 before the first), "linkage_route" (the same
+ * for the last dsh_linkage_threshold* call). */
 int dsh_get_info(dsh_ctx *ctx, const char *name, int64_t *out);
 /* HIP stream of the ctx as a void* (hipStream_t) so a host framework can order its own work.
  * Every *_device entry point runs on THIS stream and (except the *_async forms) returns after its work has
