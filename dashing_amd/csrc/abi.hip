@@ -12,17 +12,6 @@
 
 using namespace dsh;
 
-// The copy-out stream gets the highest priority the device offers: on this runtime a device-to-host copy that has to
-// wait for an event of another stream runs as a small blit kernel, which would otherwise queue behind the millions
-// of workgroups of the compare kernels it is meant to overlap with (profiles/r3d).
-static hipError_t create_copy_stream(hipStream_t *s)
-{
-    int least = 0, greatest = 0;
-    if (hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess) greatest = 0;
-    if (const char *e = std::getenv("DSH_COPY_STREAM_PRIORITY")) greatest = std::atoi(e);
-    return hipStreamCreateWithPriority(s, hipStreamNonBlocking, greatest);
-}
-
 extern "C" {
 
 const char *dsh_backend_name(void) { return "hip:gfx950"; }
@@ -36,62 +25,19 @@ int dsh_device_count(void)
     return n;
 }
 
-// One teardown for dsh_destroy and the failure path of dsh_create: wait for all three streams first (nothing of ours is
-// then in flight), then the communicator, the events and buffers, and the streams last.
+// The explicit part of a teardown, for dsh_destroy and the failure path of dsh_create: the device is made current and
+// every stream waited for (nothing of ours is then in flight), the spin kernel let go, the communicator destroyed while
+// its library is loaded.  `delete` then frees the buffers, staging blocks and events, and the streams last (ctx.h: the
+// order of the members).
 static void release_ctx(dsh_ctx *c)
 {
     (void)hipSetDevice(c->device);
-    for (hipStream_t s : {c->stream, c->copy_stream, c->aux_stream, c->place_stream})
-        if (s) (void)hipStreamSynchronize(s);
-    if (c->spin_running && c->spin_flag) *(volatile uint32_t *)c->spin_flag = 1;
-    if (c->spin_stream) {
-        (void)hipStreamSynchronize(c->spin_stream);
-        (void)hipStreamDestroy(c->spin_stream);
-        c->spin_stream = nullptr;
-    }
-    c->spin_running = false;
-    if (c->spin_flag) (void)hipHostFree(c->spin_flag);
-    c->spin_flag = nullptr;
+    for (const Stream *s : {&c->stream, &c->copy_stream, &c->aux_stream, &c->place_stream})
+        if (*s) (void)hipStreamSynchronize(*s);
+    if (c->xch.spin_running && c->xch.spin_flag.ptr) *(volatile uint32_t *)c->xch.spin_flag.ptr = 1;
+    if (c->spin_stream) (void)hipStreamSynchronize(c->spin_stream);
+    c->xch.spin_running = false;
     (void)comm_release(c);
-    for (DevBuf *b : {&c->gather_full, &c->gather_local, &c->regs_own, &c->card, &c->planes, &c->exc, &c->exc_n, &c->excv,
-                      &c->keys, &c->tailhist, &c->hist, &c->cidx_rec, &c->cidx_ent, &c->colS_n, &c->colS_key, &c->colS_card, &c->colS_th, &c->colS_rl, &c->rowoff, &c->xch_stage, &c->xch_tab, &c->place_tab, &c->sig, &c->perm, &c->items, &c->cum, &c->tiles,
-                      &c->outbuf, &c->outbuf2[0], &c->outbuf2[1], &c->seqbuf, &c->workbuf, &c->phase_cyc, &c->rawbuf, &c->fx_tab,
-                      &c->fx_summ, &c->fx_state, &c->fx_declen, &c->fx_status, &c->recbuf, &c->thr_vals, &c->thr_cnt, &c->thr_off,
-                      &c->thr_total, &c->thr_col, &c->thr_val, &c->thr_rowptr, &c->pairs_card, &c->pairs_hist, &c->pairs_lhs,
-                      &c->pairs_rhs, &c->pairs_out, &c->pairs_err, &c->derive_err, &c->derive_stage, &c->derive_ptr, &c->derive_mem,
-                      &c->derive_dst, &c->derive_part[0], &c->derive_part[1], &c->derive_out, &c->cc_parent, &c->cc_state, &c->cc_lhs,
-                      &c->cc_rhs, &c->cc_rowptr, &c->cc_seed, &c->cc_labels, &c->gr_assign, &c->gr_state, &c->gr_labels, &c->gr_best,
-                      &c->gs_labels, &c->gs_acc, &c->gs_grp, &c->gs_out, &c->gs_csr, &c->hs_edges, &c->hs_labels, &c->hs_counts,
-                      &c->lk_tab, &c->lk_cells, &c->lk_nodes, &c->lk_labels, &c->lk_state})
-        b->release();
-    if (c->pin_perm) (void)hipHostFree(c->pin_perm);
-    c->pin_perm = nullptr;
-    c->pin_lists.release();
-    c->pin_work.release();
-    c->pin_keys.release();
-    c->pin_rowoff.release();
-    c->pin_xch.release();
-    c->pin_sig.release();
-    c->pin_fx.release();
-    c->pin_rec.release();
-    c->pin_pairs.release();
-    for (hipEvent_t *e : {&c->ev_fx, &c->ev_work, &c->ev_rec, &c->ev_lists, &c->ev_perm, &c->ev_keys, &c->ev_filled[0], &c->ev_filled[1],
-                          &c->ev_drained[0], &c->ev_drained[1], &c->ev_aux_fork, &c->ev_aux_join, &c->ev_xch_tab, &c->ev_place_done, &c->ev_first_tiles, &c->ev_sig, &c->ev_pairs}) {
-        if (*e) (void)hipEventDestroy(*e);
-        *e = nullptr;
-    }
-    for (auto e : c->ev_pool) (void)hipEventDestroy(e);
-    for (auto e : c->tickets) (void)hipEventDestroy(e);
-    for (auto e : c->ev_part) (void)hipEventDestroy(e);
-    for (auto e : c->ev_round) (void)hipEventDestroy(e);
-    c->ev_round.clear();
-    c->ev_pool.clear();
-    c->tickets.clear();
-    c->ev_part.clear();
-    for (hipStream_t *s : {&c->stream, &c->copy_stream, &c->aux_stream, &c->place_stream}) {
-        if (*s) (void)hipStreamDestroy(*s);
-        *s = nullptr;
-    }
 }
 
 int dsh_create(int device, dsh_ctx **out)
@@ -108,12 +54,9 @@ int dsh_create(int device, dsh_ctx **out)
     if (!c) return DSH_ENOMEM;
     c->device = device;
     if (hipSetDevice(device) != hipSuccess ||
-        hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess ||
-        create_copy_stream(&c->copy_stream) != hipSuccess ||
-        hipStreamCreateWithFlags(&c->aux_stream, hipStreamNonBlocking) != hipSuccess ||
-        create_copy_stream(&c->place_stream) != hipSuccess ||
-        hipEventCreateWithFlags(&c->ev_aux_fork, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&c->ev_aux_join, hipEventDisableTiming) != hipSuccess) {
+        c->stream.create() != hipSuccess || c->copy_stream.create_copy() != hipSuccess ||
+        c->aux_stream.create() != hipSuccess || c->place_stream.create_copy() != hipSuccess ||
+        c->ev_aux_fork.ensure() != hipSuccess || c->ev_aux_join.ensure() != hipSuccess) {
         release_ctx(c);
         delete c;
         return DSH_EIO;
@@ -296,33 +239,16 @@ static int run_sketch_work(dsh_ctx *c, const uint8_t *d_seq, const std::vector<S
     if (work.empty()) return DSH_OK;
     // the work list travels through page-locked staging (rewritten only after its previous upload has run),
     // so nothing here waits: the blocking entry points synchronise, dsh_sketch_batch_async returns
-    if (c->work_in_flight) {
-        HIPCHK(c, hipEventSynchronize(c->ev_work));
-        c->work_in_flight = false;
-    }
-    HIPCHK(c, c->pin_work.ensure(work.size() * sizeof(SketchWork)));
-    std::memcpy(c->pin_work.ptr, work.data(), work.size() * sizeof(SketchWork));
-    HIPCHK(c, c->workbuf.ensure(work.size() * sizeof(SketchWork)));
-    HIPCHK(c, launch_upload(c->stream, c->workbuf.ptr, c->pin_work.ptr, work.size() * sizeof(SketchWork)));
-    if (!c->ev_work) HIPCHK(c, hipEventCreateWithFlags(&c->ev_work, hipEventDisableTiming));
-    HIPCHK(c, hipEventRecord(c->ev_work, c->stream));
-    c->work_in_flight = true;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (c->profiling) {  // k_sketch alone, on the stream it runs on
-        c->ev_used = 0;
-        e0 = next_event(c);
-        e1 = next_event(c);
-        if (e0) (void)hipEventRecord(e0, c->stream);
-    }
-    HIPCHK(c, launch_sketch(c->stream, d_seq, (const SketchWork *)c->workbuf.ptr,
+    HIPCHK(c, c->sketch.work.room(work.size() * sizeof(SketchWork)));
+    std::memcpy(c->sketch.work.ptr(), work.data(), work.size() * sizeof(SketchWork));
+    HIPCHK(c, c->sketch.workbuf.ensure(work.size() * sizeof(SketchWork)));
+    HIPCHK(c, launch_upload(c->stream, c->sketch.workbuf.ptr, c->sketch.work.ptr(), work.size() * sizeof(SketchWork)));
+    HIPCHK(c, c->sketch.work.sent(c->stream));
+    if (c->profiling) c->ev_used = 0;
+    DeviceTimer t(c, c->stream);  // k_sketch alone, on the stream it runs on
+    HIPCHK(c, launch_sketch(c->stream, d_seq, (const SketchWork *)c->sketch.workbuf.ptr,
                             (uint32_t)work.size(), k, c->p, canon, (uint8_t *)c->regs_own.ptr));
-    if (e0 && e1) {
-        (void)hipEventRecord(e1, c->stream);
-        (void)hipEventSynchronize(e1);
-        float ms = 0;
-        (void)hipEventElapsedTime(&ms, e0, e1);
-        c->sketch_ms = ms;
-    }
+    t.stop(c->sketch_ms);
     return DSH_OK;
 }
 
@@ -349,15 +275,15 @@ int dsh_sketch_batch_async(dsh_ctx *c, const uint8_t *seq, const uint64_t *genom
     // ship only [lo,hi), 32-aligned on the device side; pad so every lane's 64-byte read is in bounds
     const uint64_t shift = lo & 31;
     const size_t bytes = (size_t)(hi - lo) + shift;
-    HIPCHK(c, c->seqbuf.ensure(bytes + 256));
+    HIPCHK(c, c->sketch.seqbuf.ensure(bytes + 256));
     if (hi > lo) {
         if (!seq) return DSH_EINVAL;
-        HIPCHK(c, hipMemcpyAsync((uint8_t *)c->seqbuf.ptr + shift, seq + lo, (size_t)(hi - lo),
+        HIPCHK(c, hipMemcpyAsync((uint8_t *)c->sketch.seqbuf.ptr + shift, seq + lo, (size_t)(hi - lo),
                                  hipMemcpyHostToDevice, c->stream));
     }
     std::vector<uint64_t> off(n_genomes + 1);
     for (uint32_t g = 0; g <= n_genomes; ++g) off[g] = genome_off[g] - lo + shift;
-    rc = sketch_common(c, (const uint8_t *)c->seqbuf.ptr, off.data(), n_genomes, first_slot, k, canon);
+    rc = sketch_common(c, (const uint8_t *)c->sketch.seqbuf.ptr, off.data(), n_genomes, first_slot, k, canon);
     if (rc) return rc;
     invalidate(c);
     return DSH_OK;
@@ -448,22 +374,16 @@ static int records_common(dsh_ctx *c, const uint8_t *d_seq, const uint64_t *rec_
     const size_t rb = runs.size() * sizeof(RecRun), sb = segs.size() * sizeof(uint2), zb = zero.size() * sizeof(uint32_t);
     const size_t so = (rb + 15) & ~(size_t)15, zo = so + ((sb + 15) & ~(size_t)15), tot = zo + zb;
     if (tot) {
-        if (c->rec_in_flight) {
-            HIPCHK(c, hipEventSynchronize(c->ev_rec));
-            c->rec_in_flight = false;
-        }
-        HIPCHK(c, c->pin_rec.ensure(tot));
-        HIPCHK(c, c->recbuf.ensure(tot));
-        uint8_t *h = (uint8_t *)c->pin_rec.ptr;
+        HIPCHK(c, c->sketch.rec.room(tot));
+        HIPCHK(c, c->sketch.recbuf.ensure(tot));
+        uint8_t *h = (uint8_t *)c->sketch.rec.ptr();
         if (rb) std::memcpy(h, runs.data(), rb);
         if (sb) std::memcpy(h + so, segs.data(), sb);
         if (zb) std::memcpy(h + zo, zero.data(), zb);
-        HIPCHK(c, launch_upload(c->stream, c->recbuf.ptr, c->pin_rec.ptr, tot));
-        if (!c->ev_rec) HIPCHK(c, hipEventCreateWithFlags(&c->ev_rec, hipEventDisableTiming));
-        HIPCHK(c, hipEventRecord(c->ev_rec, c->stream));
-        c->rec_in_flight = true;
+        HIPCHK(c, launch_upload(c->stream, c->sketch.recbuf.ptr, c->sketch.rec.ptr(), tot));
+        HIPCHK(c, c->sketch.rec.sent(c->stream));
     }
-    const uint8_t *d = (const uint8_t *)c->recbuf.ptr;
+    const uint8_t *d = (const uint8_t *)c->sketch.recbuf.ptr;
     HIPCHK(c, launch_zero_rows(c->stream, (const uint32_t *)(d + zo), (uint32_t)zero.size(), p, regs));
     HIPCHK(c, launch_sketch_records(c->stream, d_seq, (const RecRun *)d, (uint32_t)runs.size(), (const uint2 *)(d + so), k, p,
                                     canon, regs));
@@ -491,12 +411,12 @@ int dsh_sketch_records_async(dsh_ctx *c, const uint8_t *seq, const uint64_t *rec
     const uint64_t lo = rec_off[0], hi = rec_off[n_records];
     if (hi > lo && !seq) return fail(c, DSH_EINVAL, "seq is NULL");
     const uint64_t shift = lo & 31;
-    HIPCHK(c, c->seqbuf.ensure((size_t)(hi - lo) + shift + 256));
+    HIPCHK(c, c->sketch.seqbuf.ensure((size_t)(hi - lo) + shift + 256));
     if (hi > lo)
-        HIPCHK(c, hipMemcpyAsync((uint8_t *)c->seqbuf.ptr + shift, seq + lo, (size_t)(hi - lo), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync((uint8_t *)c->sketch.seqbuf.ptr + shift, seq + lo, (size_t)(hi - lo), hipMemcpyHostToDevice, c->stream));
     std::vector<uint64_t> off(n_records + 1);
     for (uint32_t r = 0; r <= n_records; ++r) off[r] = rec_off[r] - lo + shift;
-    rc = records_common(c, (const uint8_t *)c->seqbuf.ptr, off.data(), n_records, first_slot, k, canon);
+    rc = records_common(c, (const uint8_t *)c->sketch.seqbuf.ptr, off.data(), n_records, first_slot, k, canon);
     if (rc) return rc;
     invalidate(c);
     return DSH_OK;
@@ -557,55 +477,39 @@ int dsh_sketch_fastx_batch_async(dsh_ctx *c, const uint8_t *raw, const uint64_t 
         if (chunks.size() > 0x7FFFFFFFull) return fail(c, DSH_EINVAL, "batch too large");
     }
     const size_t bytes = (size_t)(hi - lo);
-    HIPCHK(c, c->rawbuf.ensure(bytes + 256));
-    HIPCHK(c, c->seqbuf.ensure(bytes + 256));
+    HIPCHK(c, c->sketch.rawbuf.ensure(bytes + 256));
+    HIPCHK(c, c->sketch.seqbuf.ensure(bytes + 256));
     if (bytes) {
         if (!raw) return DSH_EINVAL;
-        HIPCHK(c, hipMemcpyAsync(c->rawbuf.ptr, raw + lo, bytes, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(c->sketch.rawbuf.ptr, raw + lo, bytes, hipMemcpyHostToDevice, c->stream));
     }
     const size_t gbytes = gen.size() * sizeof(FastxGenome), cbytes = chunks.size() * sizeof(FastxChunk);
-    if (c->fx_in_flight) {  // (the previous batch's tables have long been uploaded unless calls come back to back)
-        HIPCHK(c, hipEventSynchronize(c->ev_fx));
-        c->fx_in_flight = false;
-    }
-    HIPCHK(c, c->pin_fx.ensure(gbytes + cbytes));
-    std::memcpy(c->pin_fx.ptr, gen.data(), gbytes);
-    if (cbytes) std::memcpy((uint8_t *)c->pin_fx.ptr + gbytes, chunks.data(), cbytes);
-    HIPCHK(c, c->fx_tab.ensure(gbytes + cbytes));
-    HIPCHK(c, launch_upload(c->stream, c->fx_tab.ptr, c->pin_fx.ptr, gbytes + cbytes));
-    if (!c->ev_fx) HIPCHK(c, hipEventCreateWithFlags(&c->ev_fx, hipEventDisableTiming));
-    HIPCHK(c, hipEventRecord(c->ev_fx, c->stream));
-    c->fx_in_flight = true;
-    HIPCHK(c, c->fx_summ.ensure(std::max<size_t>(chunks.size(), 1) * sizeof(FastxSumm)));
-    HIPCHK(c, c->fx_state.ensure(std::max<size_t>(chunks.size(), 1) * sizeof(uint4)));
-    HIPCHK(c, c->fx_declen.ensure(gen.size() * sizeof(uint64_t)));
+    // (the previous batch's tables have long been uploaded unless calls come back to back)
+    HIPCHK(c, c->sketch.fx.room(gbytes + cbytes));
+    std::memcpy(c->sketch.fx.ptr(), gen.data(), gbytes);
+    if (cbytes) std::memcpy((uint8_t *)c->sketch.fx.ptr() + gbytes, chunks.data(), cbytes);
+    HIPCHK(c, c->sketch.fx_tab.ensure(gbytes + cbytes));
+    HIPCHK(c, launch_upload(c->stream, c->sketch.fx_tab.ptr, c->sketch.fx.ptr(), gbytes + cbytes));
+    HIPCHK(c, c->sketch.fx.sent(c->stream));
+    HIPCHK(c, c->sketch.fx_summ.ensure(std::max<size_t>(chunks.size(), 1) * sizeof(FastxSumm)));
+    HIPCHK(c, c->sketch.fx_state.ensure(std::max<size_t>(chunks.size(), 1) * sizeof(uint4)));
+    HIPCHK(c, c->sketch.fx_declen.ensure(gen.size() * sizeof(uint64_t)));
     // [status words | length fingerprints]: one buffer, cleared by one memset
     const size_t st_bytes = (gen.size() * sizeof(uint32_t) + 7) & ~(size_t)7;
-    HIPCHK(c, c->fx_status.ensure(st_bytes + gen.size() * sizeof(unsigned long long)));
-    HIPCHK(c, hipMemsetAsync(c->fx_status.ptr, 0, st_bytes + gen.size() * sizeof(unsigned long long), c->stream));
-    hipEvent_t fe0 = nullptr, fe1 = nullptr;  // (profiling: the decode kernels alone, dsh_get_info "fastx_decode_us")
-    if (c->profiling) {
-        c->ev_used = 0;
-        fe0 = next_event(c);
-        fe1 = next_event(c);
-        if (fe0) (void)hipEventRecord(fe0, c->stream);
-    }
-    HIPCHK(c, launch_fastx_decode(c->stream, (const uint8_t *)c->rawbuf.ptr, (const FastxChunk *)((const uint8_t *)c->fx_tab.ptr + gbytes),
-                                  (uint32_t)chunks.size(), (const FastxGenome *)c->fx_tab.ptr, n_genomes, (FastxSumm *)c->fx_summ.ptr,
-                                  (uint4 *)c->fx_state.ptr, (uint64_t *)c->fx_declen.ptr, (uint32_t *)c->fx_status.ptr,
-                                  (unsigned long long *)((uint8_t *)c->fx_status.ptr + st_bytes), (uint8_t *)c->seqbuf.ptr));
-    if (fe0 && fe1) {
-        (void)hipEventRecord(fe1, c->stream);
-        (void)hipEventSynchronize(fe1);
-        float ms = 0;
-        (void)hipEventElapsedTime(&ms, fe0, fe1);
-        c->fastx_ms = ms;
-    }
+    HIPCHK(c, c->sketch.fx_status.ensure(st_bytes + gen.size() * sizeof(unsigned long long)));
+    HIPCHK(c, hipMemsetAsync(c->sketch.fx_status.ptr, 0, st_bytes + gen.size() * sizeof(unsigned long long), c->stream));
+    if (c->profiling) c->ev_used = 0;
+    DeviceTimer ft(c, c->stream);  // (profiling: the decode kernels alone, dsh_get_info "fastx_decode_us")
+    HIPCHK(c, launch_fastx_decode(c->stream, (const uint8_t *)c->sketch.rawbuf.ptr, (const FastxChunk *)((const uint8_t *)c->sketch.fx_tab.ptr + gbytes),
+                                  (uint32_t)chunks.size(), (const FastxGenome *)c->sketch.fx_tab.ptr, n_genomes, (FastxSumm *)c->sketch.fx_summ.ptr,
+                                  (uint4 *)c->sketch.fx_state.ptr, (uint64_t *)c->sketch.fx_declen.ptr, (uint32_t *)c->sketch.fx_status.ptr,
+                                  (unsigned long long *)((uint8_t *)c->sketch.fx_status.ptr + st_bytes), (uint8_t *)c->sketch.seqbuf.ptr));
+    ft.stop(c->fastx_ms);
     if (status_out)
-        HIPCHK(c, hipMemcpyAsync(status_out, c->fx_status.ptr, gen.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(status_out, c->sketch.fx_status.ptr, gen.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
     std::vector<uint64_t> off(n_genomes + 1);
     for (uint32_t g = 0; g <= n_genomes; ++g) off[g] = genome_off[g] - lo;
-    rc = sketch_common(c, (const uint8_t *)c->seqbuf.ptr, off.data(), n_genomes, first_slot, k, canon);
+    rc = sketch_common(c, (const uint8_t *)c->sketch.seqbuf.ptr, off.data(), n_genomes, first_slot, k, canon);
     if (rc) return rc;
     invalidate(c);
     return DSH_OK;
@@ -678,8 +582,8 @@ int dsh_dist_rows_async(dsh_ctx *c, int estim, int result_type, int k, uint64_t 
     // (src/sketch_and_cmp.h:804-816, distmat/distmat.h:475-479,504-508).
     const unsigned b = c->out_turn++ & 1u;
     for (int t = 0; t < 2; ++t) {
-        if (!c->ev_filled[t]) HIPCHK(c, hipEventCreateWithFlags(&c->ev_filled[t], hipEventDisableTiming));
-        if (!c->ev_drained[t]) HIPCHK(c, hipEventCreateWithFlags(&c->ev_drained[t], hipEventDisableTiming));
+        HIPCHK(c, c->ev_filled[t].ensure());
+        HIPCHK(c, c->ev_drained[t].ensure());
     }
     if (c->outbuf2[b].cap < span * sizeof(float)) {  // growing frees the old buffer: let its last copy finish first
         if (c->drained_pending[b]) HIPCHK(c, hipEventSynchronize(c->ev_drained[b]));
@@ -720,11 +624,8 @@ int dsh_event_record(dsh_ctx *c, uint64_t *ticket)
     int rc = bind(c);
     if (rc) return rc;
     if (c->tickets.size() < 2 * kTicketRing) {
-        hipEvent_t e = nullptr, j = nullptr;
-        HIPCHK(c, hipEventCreateWithFlags(&j, hipEventDisableTiming));
-        c->tickets.push_back(j);
-        HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        c->tickets.push_back(e);
+        HIPCHK(c, add_event(c->tickets));
+        HIPCHK(c, add_event(c->tickets));
     }
     const uint64_t t = c->ticket_next;
     hipEvent_t es = c->tickets[2 * (t % kTicketRing)], ec = c->tickets[2 * (t % kTicketRing) + 1];
@@ -909,10 +810,10 @@ int dsh_unpermute_blocks_device(dsh_ctx *c, const void *d_stage, const uint64_t 
         const uint64_t off = dsh_tri_span(c->n, 0, std::min<uint64_t>(c->n, (uint64_t)tb[r] * kTile));
         for (uint32_t t = tb[r]; t < tb[r + 1]; ++t) delta[t] = (int64_t)block_off[r] - (int64_t)off;
     }
-    HIPCHK(c, c->workbuf.ensure(NT * sizeof(int64_t)));
-    HIPCHK(c, hipMemcpyAsync(c->workbuf.ptr, delta.data(), NT * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, c->sketch.workbuf.ensure(NT * sizeof(int64_t)));
+    HIPCHK(c, hipMemcpyAsync(c->sketch.workbuf.ptr, delta.data(), NT * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, launch_unpermute_staged(c->stream, (const float *)d_stage, (const uint32_t *)c->perm.ptr + c->n,
-                                      (const int64_t *)c->workbuf.ptr, c->n, (float *)d_out_tri));
+                                      (const int64_t *)c->sketch.workbuf.ptr, c->n, (float *)d_out_tri));
     HIPCHK(c, hipStreamSynchronize(c->stream));  // `delta` (pageable source) must outlive the copy
     return DSH_OK;
 }
@@ -1009,10 +910,10 @@ int dsh_get_info(dsh_ctx *c, const char *name, int64_t *out)
     else if (!std::strcmp(name, "parts_signalled")) *out = c->parts_signalled ? 1 : 0;
     else if (!std::strcmp(name, "sketch_kernel_us")) *out = (int64_t)(c->sketch_ms * 1000.0);
     else if (!std::strcmp(name, "fastx_decode_us")) *out = (int64_t)(c->fastx_ms * 1000.0);
-    else if (!std::strcmp(name, "xch_recv_gated")) *out = c->xch_recv_gated ? 1 : 0;
-    else if (!std::strcmp(name, "stats_route")) *out = c->stats_route_last;
-    else if (!std::strcmp(name, "linkage_route")) *out = c->linkage_route_last;
-    else if (!std::strcmp(name, "place_kernel_us")) *out = (int64_t)(c->place_ms * 1000.0);
+    else if (!std::strcmp(name, "xch_recv_gated")) *out = c->xch.recv_gated ? 1 : 0;
+    else if (!std::strcmp(name, "stats_route")) *out = c->gs.route_last;
+    else if (!std::strcmp(name, "linkage_route")) *out = c->lk.route_last;
+    else if (!std::strcmp(name, "place_kernel_us")) *out = (int64_t)(c->xch.place_ms * 1000.0);
     else if (!std::strcmp(name, "whatif_mfma")) {
 #ifdef DSH_WHATIF_MFMA
         *out = 1;
@@ -1076,47 +977,47 @@ int dsh_set_option(dsh_ctx *c, const char *name, int64_t v)
     }
     if (!std::strcmp(name, "pairs_chunk")) {
         if (v < 1 || v > (1 << 24)) return fail(c, DSH_EINVAL, "pairs_chunk must be in [1, 2^24]");
-        c->pairs_chunk = (uint64_t)v;
+        c->pairs.chunk = (uint64_t)v;
         return DSH_OK;
     }
     if (!std::strcmp(name, "cluster_chunk")) {
         if (v < 1 || v > (1 << 26)) return fail(c, DSH_EINVAL, "cluster_chunk must be in [1, 2^26]");
-        c->cluster_chunk = (uint64_t)v;
+        c->cc.chunk = (uint64_t)v;
         return DSH_OK;
     }
     if (!std::strcmp(name, "stats_route")) {
         if (v < -1 || v > 1) return fail(c, DSH_EINVAL, "stats_route must be -1 (auto), 0 (dense) or 1 (pairs)");
-        c->stats_route = (int)v;
+        c->gs.route = (int)v;
         return DSH_OK;
     }
     if (!std::strcmp(name, "linkage_route")) {
         if (v < -1 || v > 1) return fail(c, DSH_EINVAL, "linkage_route must be -1 (auto), 0 (dense) or 1 (pairs)");
-        c->linkage_route = (int)v;
+        c->lk.route = (int)v;
         return DSH_OK;
     }
     if (!std::strcmp(name, "linkage_partition")) {
         if (v < 0 || v > 1) return fail(c, DSH_EINVAL, "linkage_partition must be 0 or 1");
-        c->linkage_partition = (int)v;
+        c->lk.partition = (int)v;
         return DSH_OK;
     }
     if (!std::strcmp(name, "linkage_budget_bytes")) {
         if (v < 64) return fail(c, DSH_EINVAL, "linkage_budget_bytes must be at least 64");
-        c->linkage_budget = (uint64_t)v;
+        c->lk.budget = (uint64_t)v;
         return DSH_OK;
     }
     if (!std::strcmp(name, "linkage_lds_max")) {  // 6144 members x 24 bytes + the reduction's 6 KiB = 150 KiB of the 160 KiB of LDS
         if (v < 0 || v > 6144) return fail(c, DSH_EINVAL, "linkage_lds_max must be in [0, 6144]");
-        c->linkage_lds_max = (uint32_t)v;
+        c->lk.lds_max = (uint32_t)v;
         return DSH_OK;
     }
     if (!std::strcmp(name, "greedy_band_rows")) {
         if (v < 1 || v > (long long)kGreedyMaxRows) return fail(c, DSH_EINVAL, "greedy_band_rows must be in [1, %u]", kGreedyMaxRows);
-        c->greedy_band_rows = (uint64_t)v;
+        c->gr.band_rows = (uint64_t)v;
         return DSH_OK;
     }
     if (!std::strcmp(name, "derive_chunk_bytes")) {
         if (v < 1) return fail(c, DSH_EINVAL, "derive_chunk_bytes must be at least 1");
-        c->derive_chunk_bytes = (uint64_t)v;
+        c->derive.chunk_bytes = (uint64_t)v;
         return DSH_OK;
     }
     if (!std::strcmp(name, "sort")) {
@@ -1173,7 +1074,7 @@ int dsh_set_option(dsh_ctx *c, const char *name, int64_t v)
     }
     if (!std::strcmp(name, "xch_recv_gate")) {
         if (v < -1 || v > 1) return fail(c, DSH_EINVAL, "xch_recv_gate is -1 (auto), 0 or 1");
-        c->xch_recv_gate = (int)v;
+        c->xch.recv_gate = (int)v;
         return DSH_OK;
     }
     if (!std::strcmp(name, "finalize_signal")) {

@@ -22,25 +22,25 @@ namespace dsh {  // (ctx.h: dsh_linkage_* partitions by the same components)
 
 int cc_begin(dsh_ctx *c, uint64_t n)
 {
-    HIPCHK(c, c->cc_parent.ensure(std::max<uint64_t>(n, 1) * sizeof(uint32_t)));
-    HIPCHK(c, c->cc_state.ensure(sizeof(CcState)));
-    HIPCHK(c, hipMemsetAsync(c->cc_state.ptr, 0, sizeof(CcState), c->stream));
-    HIPCHK(c, launch_cc_init(c->stream, (uint32_t *)c->cc_parent.ptr, n));
+    HIPCHK(c, c->cc.parent.ensure(std::max<uint64_t>(n, 1) * sizeof(uint32_t)));
+    HIPCHK(c, c->cc.state.ensure(sizeof(CcState)));
+    HIPCHK(c, hipMemsetAsync(c->cc.state.ptr, 0, sizeof(CcState), c->stream));
+    HIPCHK(c, launch_cc_init(c->stream, (uint32_t *)c->cc.parent.ptr, n));
     return DSH_OK;
 }
 
-uint32_t *cc_err(dsh_ctx *c) { return &((CcState *)c->cc_state.ptr)->err; }
+uint32_t *cc_err(dsh_ctx *c) { return &((CcState *)c->cc.state.ptr)->err; }
 uint32_t cc_cap(uint64_t n) { return (uint32_t)std::min<uint64_t>(n + 1, 0xFFFFFFFFull); }
 
 // labels and the root count; the one wait of a call.  d_labels: the caller's device buffer, or nullptr for h_labels (host)
 int cc_finish(dsh_ctx *c, uint64_t n, uint32_t *d_labels, uint32_t *h_labels, uint64_t *n_clusters)
 {
     if (!d_labels) {
-        HIPCHK(c, c->cc_labels.ensure(std::max<uint64_t>(n, 1) * sizeof(uint32_t)));
-        d_labels = (uint32_t *)c->cc_labels.ptr;
+        HIPCHK(c, c->cc.labels.ensure(std::max<uint64_t>(n, 1) * sizeof(uint32_t)));
+        d_labels = (uint32_t *)c->cc.labels.ptr;
     }
-    CcState *st = (CcState *)c->cc_state.ptr;
-    HIPCHK(c, launch_cc_labels(c->stream, (uint32_t *)c->cc_parent.ptr, n, cc_cap(n), d_labels, (uint64_t *)&st->n_roots, &st->err));
+    CcState *st = (CcState *)c->cc.state.ptr;
+    HIPCHK(c, launch_cc_labels(c->stream, (uint32_t *)c->cc.parent.ptr, n, cc_cap(n), d_labels, (uint64_t *)&st->n_roots, &st->err));
     CcState h = {0, 0, 0};
     HIPCHK(c, hipMemcpyAsync(&h, st, sizeof h, hipMemcpyDeviceToHost, c->stream));
     if (h_labels && n) HIPCHK(c, hipMemcpyAsync(h_labels, d_labels, n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
@@ -58,9 +58,9 @@ namespace {
 int cc_seed(dsh_ctx *c, uint64_t n, const uint32_t *labels_in)
 {
     if (!labels_in || !n) return DSH_OK;
-    HIPCHK(c, c->cc_seed.ensure(n * sizeof(uint32_t)));
-    HIPCHK(c, hipMemcpyAsync(c->cc_seed.ptr, labels_in, n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, launch_cc_seed(c->stream, (uint32_t *)c->cc_parent.ptr, (const uint32_t *)c->cc_seed.ptr, n, cc_cap(n), cc_err(c)));
+    HIPCHK(c, c->cc.seed.ensure(n * sizeof(uint32_t)));
+    HIPCHK(c, hipMemcpyAsync(c->cc.seed.ptr, labels_in, n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, launch_cc_seed(c->stream, (uint32_t *)c->cc.parent.ptr, (const uint32_t *)c->cc.seed.ptr, n, cc_cap(n), cc_err(c)));
     return DSH_OK;
 }
 
@@ -78,7 +78,7 @@ int run_cluster_threshold(dsh_ctx *c, int estim, int result_type, int k, float t
     bq.estim = estim, bq.result_type = result_type, bq.k = k;
     bq.re = n;
     rc = for_each_band(c, bq, [&](const ThrRows &g, const float *vals, uint64_t) -> int {
-        const hipError_t e = launch_cc_band(c->stream, vals, g, t, descending, (uint32_t *)c->cc_parent.ptr, cc_cap(n), cc_err(c));
+        const hipError_t e = launch_cc_band(c->stream, vals, g, t, descending, (uint32_t *)c->cc.parent.ptr, cc_cap(n), cc_err(c));
         return e == hipSuccess ? DSH_OK : fail(c, DSH_EIO, "k_cc_band: %s", hipGetErrorString(e));
     });
     if (rc) return drain(c, rc);
@@ -136,17 +136,17 @@ int dsh_cluster_pairs(dsh_ctx *c, uint64_t n_nodes, const uint32_t *lhs, const u
     if (!n_nodes) return DSH_OK;
     // the list goes through bounded scratch: 8 bytes per edge of ONE chunk (the caller's arrays outlive the call, which
     // ends with a wait, so they are uploaded as they stand)
-    const uint64_t chunk = std::min<uint64_t>(c->cluster_chunk, std::max<uint64_t>(n_pairs, 1));
+    const uint64_t chunk = std::min<uint64_t>(c->cc.chunk, std::max<uint64_t>(n_pairs, 1));
     if (n_pairs) {
-        HIPCHK(c, c->cc_lhs.ensure(chunk * sizeof(uint32_t)));
-        HIPCHK(c, c->cc_rhs.ensure(chunk * sizeof(uint32_t)));
+        HIPCHK(c, c->cc.lhs.ensure(chunk * sizeof(uint32_t)));
+        HIPCHK(c, c->cc.rhs.ensure(chunk * sizeof(uint32_t)));
     }
     if ((rc = cc_begin(c, n_nodes)) || (rc = cc_seed(c, n_nodes, labels_in))) return drain(c, rc);
     for (uint64_t x0 = 0; x0 < n_pairs; x0 += chunk) {
         const uint64_t cnt = std::min<uint64_t>(chunk, n_pairs - x0);
-        if (hipMemcpyAsync(c->cc_lhs.ptr, lhs + x0, cnt * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream) != hipSuccess ||
-            hipMemcpyAsync(c->cc_rhs.ptr, rhs + x0, cnt * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream) != hipSuccess ||
-            launch_cc_edges(c->stream, (uint32_t *)c->cc_parent.ptr, (const uint32_t *)c->cc_lhs.ptr, (const uint32_t *)c->cc_rhs.ptr, cnt,
+        if (hipMemcpyAsync(c->cc.lhs.ptr, lhs + x0, cnt * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+            hipMemcpyAsync(c->cc.rhs.ptr, rhs + x0, cnt * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+            launch_cc_edges(c->stream, (uint32_t *)c->cc.parent.ptr, (const uint32_t *)c->cc.lhs.ptr, (const uint32_t *)c->cc.rhs.ptr, cnt,
                             n_nodes, cc_cap(n_nodes), cc_err(c)) != hipSuccess)
             return drain(c, fail(c, DSH_EIO, "upload of the edge list / k_cc_edges failed"));
     }
@@ -170,21 +170,21 @@ int dsh_cluster_csr(dsh_ctx *c, uint64_t n_nodes, uint64_t row_begin, uint64_t r
             return fail(c, DSH_EINVAL, "col[%llu] = %u outside [0, %llu)", (unsigned long long)(h0 + h), col[h0 + h], (unsigned long long)n_nodes);
     if (n_clusters) *n_clusters = 0;
     if (!n_nodes) return DSH_OK;
-    const uint64_t chunk = std::min<uint64_t>(c->cluster_chunk, std::max<uint64_t>(n_hits, 1));
+    const uint64_t chunk = std::min<uint64_t>(c->cc.chunk, std::max<uint64_t>(n_hits, 1));
     if (n_hits) {
-        HIPCHK(c, c->cc_rowptr.ensure((rows + 1) * sizeof(uint64_t)));
-        HIPCHK(c, c->cc_lhs.ensure(chunk * sizeof(uint32_t)));
+        HIPCHK(c, c->cc.rowptr.ensure((rows + 1) * sizeof(uint64_t)));
+        HIPCHK(c, c->cc.lhs.ensure(chunk * sizeof(uint32_t)));
     }
     if ((rc = cc_begin(c, n_nodes)) || (rc = cc_seed(c, n_nodes, labels_in))) return drain(c, rc);
     if (n_hits) {
         // the row pointer travels whole (8 bytes per row), the columns in chunks; the row of a hit is found on the device
-        if (hipMemcpyAsync(c->cc_rowptr.ptr, row_ptr, (rows + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream) != hipSuccess)
+        if (hipMemcpyAsync(c->cc.rowptr.ptr, row_ptr, (rows + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream) != hipSuccess)
             return drain(c, fail(c, DSH_EIO, "upload of the row pointer failed"));
         for (uint64_t x0 = 0; x0 < n_hits; x0 += chunk) {
             const uint64_t cnt = std::min<uint64_t>(chunk, n_hits - x0);
-            if (hipMemcpyAsync(c->cc_lhs.ptr, col + h0 + x0, cnt * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream) != hipSuccess ||
-                launch_cc_csr(c->stream, (uint32_t *)c->cc_parent.ptr, (const uint64_t *)c->cc_rowptr.ptr, rows, row_begin,
-                              (const uint32_t *)c->cc_lhs.ptr, h0 + x0, cnt, n_nodes, cc_cap(n_nodes), cc_err(c)) != hipSuccess)
+            if (hipMemcpyAsync(c->cc.lhs.ptr, col + h0 + x0, cnt * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+                launch_cc_csr(c->stream, (uint32_t *)c->cc.parent.ptr, (const uint64_t *)c->cc.rowptr.ptr, rows, row_begin,
+                              (const uint32_t *)c->cc.lhs.ptr, h0 + x0, cnt, n_nodes, cc_cap(n_nodes), cc_err(c)) != hipSuccess)
                 return drain(c, fail(c, DSH_EIO, "upload of the columns / k_cc_csr failed"));
         }
     }

@@ -1,5 +1,6 @@
-// ctx.h -- the per-GPU context behind the opaque dsh_ctx of include/dashing_hip.h, and the internal entry points the
-// translation units of libdashing_hip.so share:
+// ctx.h -- the per-GPU context behind the opaque dsh_ctx of include/dashing_hip.h, the owners of what it holds on the
+// device and in page-locked memory (DevBuf, PinBuf, Event, Stream, Staging: each releases itself, so `delete` of a
+// context is its whole release list), and the internal entry points the translation units of libdashing_hip.so share:
 //   abi.hip       context, resident sketches, sketch waist, cardinalities, compare entry points, tickets, options
 //   engine.hip    prepare() (per-sketch pass, layout, bit-planes, position index) and run_pairs() (tile kernel + k_finalize)
 //   knn.hip       dsh_knn
@@ -15,12 +16,16 @@
 //   derive.hip    dsh_fold*, dsh_upload_sketches_folded*, dsh_union_groups* (new sketches out of resident ones)
 //   exchange.hip  RCCL: dsh_comm_*, dsh_collect_*, dsh_allgather_device, dsh_dist_collect
 //   plan.cpp      the pure-host planner (layout, tiles, bands, parts, work items, row partitions)
+// State that one of these modules uses alone is a named member struct of dsh_ctx (c->cc.parent, c->xch.comm); what the
+// compare path shares with every module stays flat.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>  // types only: the library is dlopen'ed at dsh_comm_init (single-GPU users never load it)
 
 #include <cstdarg>
 #include <cstdio>
+#include <cstdlib>
+#include <deque>
 #include <string>
 #include <vector>
 
@@ -28,15 +33,22 @@
 #include "kernels.h"
 #include "plan.h"
 
-struct DevBuf {
+// The owners below free in their destructors and are neither copied nor moved (a pool of them is a std::deque, which
+// never relocates).  Scratch stays grow-only: nothing is freed before its owner goes, except by ensure() making room.
+struct NoCopy {
+    NoCopy() = default;
+    NoCopy(const NoCopy &) = delete;
+    NoCopy &operator=(const NoCopy &) = delete;
+};
+
+struct DevBuf : NoCopy {
     void *ptr = nullptr;
     size_t cap = 0;
+    ~DevBuf() { release(); }
     hipError_t ensure(size_t bytes)
     {
         if (bytes <= cap) return hipSuccess;
-        if (ptr) (void)hipFree(ptr);
-        ptr = nullptr;
-        cap = 0;
+        release();
         hipError_t e = hipMalloc(&ptr, bytes);
         if (e == hipSuccess) cap = bytes;
         return e;
@@ -49,17 +61,16 @@ struct DevBuf {
     }
 };
 
-// page-locked host staging: a hipMemcpyAsync from it is a true asynchronous DMA, so the call that filled it
-// may return before the copy has run (the event says when it may be rewritten)
-struct PinBuf {
+// page-locked host memory: a hipMemcpyAsync from or to it is a true asynchronous DMA, so the call that enqueued it may
+// return before the copy has run
+struct PinBuf : NoCopy {
     void *ptr = nullptr;
     size_t cap = 0;
+    ~PinBuf() { release(); }
     hipError_t ensure(size_t bytes)
     {
         if (bytes <= cap) return hipSuccess;
-        if (ptr) (void)hipHostFree(ptr);
-        ptr = nullptr;
-        cap = 0;
+        release();
         const size_t want = bytes + bytes / 2;
         hipError_t e = hipHostMalloc(&ptr, want, hipHostMallocDefault);
         if (e == hipSuccess) cap = want;
@@ -73,9 +84,92 @@ struct PinBuf {
     }
 };
 
+// one word of page-locked memory the device reads through a mapping (dsh_diag_spin_*)
+struct MappedWord : NoCopy {
+    uint32_t *ptr = nullptr;
+    ~MappedWord() { if (ptr) (void)hipHostFree(ptr); }
+    hipError_t ensure() { return ptr ? hipSuccess : hipHostMalloc((void **)&ptr, 64, hipHostMallocMapped); }
+};
+
+// an event made on first use: ensure() returns the creation's error (its caller's HIPCHK reports it)
+struct Event : NoCopy {
+    hipEvent_t ev = nullptr;
+    ~Event() { if (ev) (void)hipEventDestroy(ev); }
+    hipError_t ensure(unsigned flags = hipEventDisableTiming) { return ev ? hipSuccess : hipEventCreateWithFlags(&ev, flags); }
+    operator hipEvent_t() const { return ev; }
+};
+
+// one more event at the end of a pool; a pool never holds an event that could not be made
+inline hipError_t add_event(std::deque<Event> &pool, unsigned flags = hipEventDisableTiming)
+{
+    pool.emplace_back();
+    const hipError_t e = pool.back().ensure(flags);
+    if (e != hipSuccess) pool.pop_back();
+    return e;
+}
+
+struct Stream : NoCopy {
+    hipStream_t st = nullptr;
+    ~Stream() { if (st) (void)hipStreamDestroy(st); }
+    hipError_t create() { return st ? hipSuccess : hipStreamCreateWithFlags(&st, hipStreamNonBlocking); }
+    // The copy-out stream gets the highest priority the device offers: on this runtime a device-to-host copy that has to
+    // wait for an event of another stream runs as a small blit kernel, which would otherwise queue behind the millions
+    // of workgroups of the compare kernels it is meant to overlap with (profiles/r3d).
+    hipError_t create_copy()
+    {
+        int least = 0, greatest = 0;
+        if (hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess) greatest = 0;
+        if (const char *e = std::getenv("DSH_COPY_STREAM_PRIORITY")) greatest = std::atoi(e);
+        return hipStreamCreateWithPriority(&st, hipStreamNonBlocking, greatest);
+    }
+    operator hipStream_t() const { return st; }
+};
+
+// Page-locked staging of an upload: filled by the host, read by a copy or an upload kernel when the stream gets there, so
+// the call that filled it may return first.  The block may be rewritten -- and may MOVE, since growing frees the old
+// block under a DMA that still reads it -- only once the previous upload has run: room() waits first and grows second.
+struct Staging : NoCopy {
+    PinBuf buf;
+    Event sent_ev;
+    bool in_flight = false;
+    // the previous upload has run (for a caller whose size is only known later: room() waits anyway)
+    hipError_t wait()
+    {
+        if (!in_flight) return hipSuccess;
+        const hipError_t e = hipEventSynchronize(sent_ev);
+        if (e == hipSuccess) in_flight = false;
+        return e;
+    }
+    // room for `bytes` to write: waits for the previous upload if one is in flight
+    hipError_t room(size_t bytes)
+    {
+        const hipError_t e = wait();
+        return e == hipSuccess ? buf.ensure(bytes) : e;
+    }
+    // the upload has been enqueued on `st`
+    hipError_t sent(hipStream_t st)
+    {
+        hipError_t e = sent_ev.ensure();
+        if (e == hipSuccess) e = hipEventRecord(sent_ev, st);
+        if (e == hipSuccess) in_flight = true;
+        return e;
+    }
+    void *ptr() const { return buf.ptr; }
+};
+
+// DESTRUCTION ORDER: members go in reverse order of declaration, and `delete` of a context is what frees its buffers and
+// events (abi.hip: release_ctx has made the device current, waited for every stream and released the communicator just
+// before).  The streams are therefore declared FIRST, so that they go last, behind every buffer, staging block and event
+// that was used on them; a new member goes below them.
 struct dsh_ctx {
     int device = 0;
-    hipStream_t stream = nullptr;
+    Stream stream;
+    // copy-out pipeline of dsh_dist_rows_async: results alternate between two device buffers; the copy of call b to the
+    // host runs on its own stream while the kernels of call b+1 fill the other buffer
+    Stream copy_stream;
+    Stream aux_stream;    // prepare(): the column index is built next to the bit-plane transform
+    Stream place_stream;  // destination of an exchange: received rows are put into place beside the next round's transfer
+    Stream spin_stream;   // diagnostics (dsh_diag_spin_*): the waiting kernel's own
     std::string err;
     // resident sketch matrix
     DevBuf regs_own;
@@ -88,39 +182,20 @@ struct dsh_ctx {
     int card_estim = -1;
     uint64_t card_from = 0;             // the per-sketch pass (cardinalities, lists, keys) covers the sketches [card_from, n)
     uint64_t pass_gen = 0, lay_gen = 0; // per-sketch passes so far; the one the layout's per-column data was built from
-    DevBuf card, planes, cum, tiles, items, outbuf, seqbuf, workbuf, exc, excv, exc_n, keys, perm, tailhist;
-    // copy-out pipeline of dsh_dist_rows_async: results alternate between two device buffers; the copy of call b to the
-    // host runs on its own stream while the kernels of call b+1 fill the other buffer
-    hipStream_t copy_stream = nullptr;
-    hipStream_t aux_stream = nullptr;   // prepare(): the column index is built next to the bit-plane transform
-    hipStream_t place_stream = nullptr; // destination of an exchange: received rows are put into place beside the next round's transfer
-    hipEvent_t ev_aux_fork = nullptr, ev_aux_join = nullptr;
+    DevBuf card, planes, cum, tiles, items, outbuf, exc, excv, exc_n, keys, perm, tailhist;
+    Event ev_aux_fork, ev_aux_join;
     bool aux_join_pending = false;
     DevBuf outbuf2[2];
-    hipEvent_t ev_filled[2] = {nullptr, nullptr};  // kernels of the call that filled outbuf2[b] done (recorded on stream)
-    hipEvent_t ev_drained[2] = {nullptr, nullptr}; // copy out of outbuf2[b] done (recorded on copy_stream)
+    Event ev_filled[2];                 // kernels of the call that filled outbuf2[b] done (recorded on stream)
+    Event ev_drained[2];                // copy out of outbuf2[b] done (recorded on copy_stream)
     bool drained_pending[2] = {false, false};
     unsigned out_turn = 0;
-    std::vector<hipEvent_t> tickets;    // dsh_event_record ring: slot t % 64 holds {mark on the ctx stream, mark on the copy stream}
+    std::deque<Event> tickets;          // dsh_event_record ring: slot t % 64 holds {mark on the ctx stream, mark on the copy stream}
     uint64_t ticket_next = 0;
-    // multi-GPU exchange (dsh_comm_*): an RCCL communicator over the ranks' contexts
-    ncclComm_t comm = nullptr;
-    int comm_rank = 0, comm_world = 1;
-    DevBuf gather_full, gather_local;   // dsh_dist_collect: the assembled matrix on the destination rank / this rank's span
-    // dsh_exchange_*: on the destination, the row-sorted spans as they arrive and the sources' key order + row offsets
-    DevBuf xch_stage, xch_tab;
-    DevBuf place_tab;                   // dsh_exchange_place_device's own tables (ctx stream; xch_tab belongs to the copy stream)
-    PinBuf pin_xch;
-    hipEvent_t ev_xch_tab = nullptr;
-    hipEvent_t ev_first_tiles = nullptr;       // the tile kernel of the last call's first band has run
-    bool xch_recv_gated = false;               // (info) the last collect of a destination waited for its tile kernel
-    int xch_recv_gate = -1;                    // option: -1 auto | 0 | 1 (exchange.hip, the destination's receives)
-    hipEvent_t ev_place_done = nullptr;        // the last placement of a collect (the copy stream joins it)
-    std::vector<hipEvent_t> ev_round;          // round q of a collect has arrived (place_stream waits for it)
-    bool xch_tab_in_flight = false;
+    Event ev_first_tiles;               // the tile kernel of the last call's first band has run
     bool pass_from_zero = false;        // the next per-sketch pass covers every sketch (the destination of an exchange)
     DevBuf hist;                        // [n][64] per-sketch register histograms (k_selfhist_card -> k_card_from_hist)
-    hipEvent_t ev_keys = nullptr;       // the keys have reached the host
+    Event ev_keys;                      // the keys have reached the host
     DevBuf cidx_rec, cidx_ent;          // position index of the column blocks of the current layout (k_build_colindex)
     uint32_t nbuckets = 0, ent_stride = 0;
     DevBuf colS_n, colS_key, colS_card, colS_th, colS_rl;  // per column of the layout, in layout order (k_finalize's inputs)
@@ -129,14 +204,12 @@ struct dsh_ctx {
     dsh::plan::Layout lay;
     bool lay_built = false;             // `lay` holds a layout (whatever happened to the planes since)
     dsh::plan::PairPlan pp;
-    std::vector<hipEvent_t> ev_part;    // part q complete (recorded on the ctx stream by the last call with parts)
+    std::deque<Event> ev_part;          // part q complete (recorded on the ctx stream by the last call with parts)
     uint32_t parts_done = 0;            // parts of the last dsh_dist_rows_parts_device_async call
     // part signalling (kernels.h kSig*): k_finalize announces the parts from inside ONE launch per band; the copy stream
     // waits for a part's flag with hipStreamWaitValue32 instead of an event between launches
     DevBuf sig;
-    PinBuf pin_sig;                     // the parts' tile totals on their way to the device
-    hipEvent_t ev_sig = nullptr;        // their upload has run (the staging is rewritten by the next call)
-    bool sig_in_flight = false;
+    Staging st_sig;                     // the parts' tile totals on their way to the device
     uint32_t sig_gen = 0;               // generation of the last call with parts: the value its flags take
     bool parts_signalled = false;       // the last call with parts used flags (else events)
     int finalize_signal = -1;           // option: -1 auto (on where the device supports stream wait-value), 0 events, 1 flags
@@ -145,23 +218,10 @@ struct dsh_ctx {
     PinBuf pin_keys;                    // host copy of the per-sketch keys (valid while the per-sketch pass is), page-locked:
     const uint32_t *hk32 = nullptr;     // the copy is a direct DMA and the host only waits for ev_keys
     bool hk32_valid = false;
-    hipEvent_t ev_perm = nullptr;       // upload of pin_perm done (it is rewritten by the next layout)
-    bool perm_in_flight = false;
     double host_layout_us = 0, host_lists_us = 0, host_keys_wait_us = 0;  // host time of the last call (dsh_get_info)
-    uint32_t *pin_perm = nullptr;       // page-locked copy of lay.perm: its upload is then truly asynchronous
-    size_t pin_perm_cap = 0;
+    Staging st_perm;                    // lay.perm, then (row-sorted parts) lay.rowoff from the next 16-byte boundary on
     DevBuf rowoff;                      // (row-sorted parts) offset of the row at layout position s in the rank's buffer
-    PinBuf pin_rowoff;
-    PinBuf pin_work;                    // sketch work list of the call in flight
-    hipEvent_t ev_work = nullptr;
-    bool work_in_flight = false;
-    PinBuf pin_rec;                     // dsh_sketch_records: runs, segments and rows to clear of the call in flight
-    DevBuf recbuf;
-    hipEvent_t ev_rec = nullptr;
-    bool rec_in_flight = false;
-    PinBuf pin_lists;                   // tiles then items of the call in flight
-    hipEvent_t ev_lists = nullptr;      // recorded after their upload; waited on before they are rewritten
-    bool lists_in_flight = false;
+    Staging st_lists;                   // tiles then items of the call in flight
     uint32_t W = 0, Kpad = 0;           // words per plane; plane rows padded to whole LDS stages
     int emax = 0, elow = 0, cum_bytes = 4;
     // options
@@ -181,67 +241,104 @@ struct dsh_ctx {
     uint64_t cum_budget = 8ull << 30;  // scratch for C(v) per pair slot: larger jobs run in bands (2 -> 8 GiB: -1.5 % at 100 000 x p=10)
     int sort_mode = -1;  // -1 auto (key-ordered columns for triangle calls of >= range_sort_min_rows rows), 0 never
     int range_sort_min_rows = 1024;  // smaller row ranges keep the cached identity layout (a rebuild costs more than it saves)
-    // a band's dense values (bands.h: every band consumer); dsh_dist_threshold* (threshold.hip): its per-chunk counts and
-    // offsets, the running total, and for the host forms the band's hits and the row pointer on their way out
-    DevBuf thr_vals, thr_cnt, thr_off, thr_total, thr_col, thr_val, thr_rowptr;
+    DevBuf thr_vals;                  // a band's dense values (bands.h: every band consumer)
     uint64_t threshold_band_bytes = (uint64_t)1 << 30;  // a band (bands.h) holds at most this much float32
     uint64_t knn_square_budget = (uint64_t)96 << 30;  // all-vs-all kNN keeps an n x n float matrix in HBM up to this size
-    // dsh_dist_pairs* (pairs.hip): the path's OWN cardinalities (nothing of the dense path's derived state is read or
-    // written), a chunk's histograms, the host forms' chunk of the list and of the result, the error words
-    DevBuf pairs_card, pairs_hist, pairs_lhs, pairs_rhs, pairs_out, pairs_err;
-    PinBuf pin_pairs;                   // host forms: a chunk of the list on its way to the device
-    hipEvent_t ev_pairs = nullptr;      // its upload has run
-    int pairs_card_estim = -1;          // estimator pairs_card was computed under (-1: none), dropped by invalidate()
-    uint64_t pairs_chunk = 1u << 18;    // option: pairs per launch (scratch is 64 counters per pair of a chunk)
-    // dsh_cluster_* (cluster.hip): parent[n], the root count + error word, a chunk of the caller's edges (or the CSR's row
-    // pointer and a chunk of its columns), a seed labelling and the labels of the host forms
-    DevBuf cc_parent, cc_state, cc_lhs, cc_rhs, cc_rowptr, cc_seed, cc_labels;
-    uint64_t cluster_chunk = 1u << 20;  // option: edges per launch of dsh_cluster_pairs / dsh_cluster_csr
-    // dsh_greedy_threshold* (greedy.hip): assign[n], the count of representatives and the labels of the host form
-    DevBuf gr_assign, gr_state, gr_labels;
-    DevBuf gr_best;                     // dsh_greedy_extend* in BEST mode (greedy_extend.hip): one 64-bit key per new slot
-    // dsh_group_stats* (group_stats.hip): the labels, the per-slot accumulators (cnt, sum, worst key) and per-group medoid
-    // keys, the outputs of the host form, and for the pairs route the member CSR
-    DevBuf gs_labels, gs_acc, gs_grp, gs_out, gs_csr;
-    // dsh_dist_histogram* (hist.hip): the edges, the labels and the call's uint64 counters (the host forms' on their way out)
-    DevBuf hs_edges, hs_labels, hs_counts;
-    int hs_cus = 0;                     // compute units of the device (hipDeviceAttributeMultiprocessorCount), queried once
-    int stats_route = -1;               // option: -1 auto | 0 dense | 1 pairs
-    int stats_route_last = -1;          // (info) the route the last dsh_group_stats* call took
-    // dsh_linkage_* (linkage.hip): the components' tables (comp | rank | moff | coff | mem), the cell matrices of a batch, the
-    // state of its members, the labels before they go out, and the count of clusters + the error word
-    DevBuf lk_tab, lk_cells, lk_nodes, lk_labels, lk_state;
-    uint64_t linkage_budget = 8ull << 30;  // option linkage_budget_bytes: the matrices of a batch of components
-    uint32_t linkage_lds_max = 4096;    // option: components of at most this many members keep their per-row state in LDS
-    int linkage_partition = 1;          // option: 0 = the whole collection as one component
-    int linkage_route = -1;             // option: -1 auto | 0 dense | 1 pairs
-    int linkage_route_last = -1;        // (info) the route the last dsh_linkage_threshold* call took
-    uint64_t greedy_band_rows = 4096;   // option: a band holds at most this many rows (k_greedy_diag's LDS; 1..kGreedyMaxRows)
-    // dsh_fold*, dsh_upload_sketches_folded*, dsh_union_groups* (derive.hip): the error word, a chunk of source rows or of
-    // folded rows on its way through the device, the groups' CSR and the partial unions of groups cut into chunks
-    DevBuf derive_err, derive_stage, derive_ptr, derive_mem, derive_dst, derive_part[2], derive_out;
-    uint64_t derive_chunk_bytes = (uint64_t)256 << 20;  // option: source rows staged per step of the host forms
     int pair_mfma = 0;  // WHAT-IF only (built with `make WHATIF=1`): 1 = the AND+popcount tile kernel on the matrix cores
     int finalize_stop = 0;  // profiling only: k_finalize leaves after phase 1..4 (results are then meaningless)
     int finalize_timing = 0;  // profiling only: the s_memtime-stamped instance of k_finalize (same results, per-phase cycles)
     DevBuf phase_cyc;       // 8 x u64 of the last call with finalize_timing
     int nsplit = 0;  // plane-range splits per tile; 0 = auto (aim at >= 16 items per workgroup slot)
-    // dsh_sketch_fastx_batch_async: raw FASTA bytes of a batch, the decoder's tables and scratch (kernels_fastx.hip)
-    DevBuf rawbuf, fx_tab, fx_summ, fx_state, fx_declen, fx_status;
-    PinBuf pin_fx;
-    hipEvent_t ev_fx = nullptr;         // the upload of pin_fx has run
-    bool fx_in_flight = false;
-    // diagnostics (dsh_diag_spin_*): a kernel that waits like an RCCL receive kernel, on a stream of its own
-    uint32_t *spin_flag = nullptr;      // page-locked, mapped
-    hipStream_t spin_stream = nullptr;
-    bool spin_running = false;
     // profiling
     bool profiling = false;
-    double place_ms = 0;  // (profiling) device time of the last dsh_exchange_place_device's placement kernel
     double pair_ms = 0, fin_ms = 0, prep_ms = 0, sketch_ms = 0, fastx_ms = 0;
     uint32_t pair_launches = 0;
-    std::vector<hipEvent_t> ev_pool;
+    std::deque<Event> ev_pool;          // timing events, handed out by next_event
     size_t ev_used = 0;
+
+    // ---- state of ONE module each ----
+    // sketch waist (abi.hip): the sequence of a batch, the k_sketch work list of the call in flight, the runs, segments
+    // and rows to clear of dsh_sketch_records; dsh_sketch_fastx_batch_async: raw FASTA bytes of a batch, the decoder's
+    // tables and scratch (kernels_fastx.hip)
+    struct {
+        DevBuf seqbuf, workbuf, recbuf;
+        Staging work, rec;
+        DevBuf rawbuf, fx_tab, fx_summ, fx_state, fx_declen, fx_status;
+        Staging fx;
+    } sketch;
+    // dsh_dist_threshold* (threshold.hip): a band's per-chunk counts and offsets, the running total, and for the host forms
+    // the band's hits and the row pointer on their way out
+    struct {
+        DevBuf cnt, off, total, col, val, rowptr;
+    } thr;
+    // dsh_dist_pairs* (pairs.hip): the path's OWN cardinalities (nothing of the dense path's derived state is read or
+    // written), a chunk's histograms, the host forms' chunk of the list and of the result, the error words
+    // (group_stats.hip and linkage.hip run their pairs through lhs / rhs / out)
+    struct {
+        DevBuf card, hist, lhs, rhs, out, err;
+        Staging list;                 // host forms: a chunk of the list on its way to the device
+        int card_estim = -1;          // estimator `card` was computed under (-1: none), dropped by invalidate()
+        uint64_t chunk = 1u << 18;    // option pairs_chunk: pairs per launch (scratch is 64 counters per pair of a chunk)
+    } pairs;
+    // dsh_cluster_* (cluster.hip): parent[n], the root count + error word, a chunk of the caller's edges (or the CSR's row
+    // pointer and a chunk of its columns), a seed labelling and the labels of the host forms
+    struct {
+        DevBuf parent, state, lhs, rhs, rowptr, seed, labels;
+        uint64_t chunk = 1u << 20;    // option cluster_chunk: edges per launch of dsh_cluster_pairs / dsh_cluster_csr
+    } cc;
+    // dsh_greedy_threshold* (greedy.hip): assign[n], the count of representatives and the labels of the host form
+    struct {
+        DevBuf assign, state, labels;
+        DevBuf best;                  // dsh_greedy_extend* in BEST mode (greedy_extend.hip): one 64-bit key per new slot
+        uint64_t band_rows = 4096;    // option greedy_band_rows: a band holds at most this many rows (k_greedy_diag's LDS; 1..kGreedyMaxRows)
+    } gr;
+    // dsh_group_stats* (group_stats.hip): the labels, the per-slot accumulators (cnt, sum, worst key) and per-group medoid
+    // keys, the outputs of the host form, and for the pairs route the member CSR
+    struct {
+        DevBuf labels, acc, grp, out, csr;
+        int route = -1;               // option stats_route: -1 auto | 0 dense | 1 pairs
+        int route_last = -1;          // (info) the route the last dsh_group_stats* call took
+    } gs;
+    // dsh_dist_histogram* (hist.hip): the edges, the labels and the call's uint64 counters (the host forms' on their way out)
+    struct {
+        DevBuf edges, labels, counts;
+        int cus = 0;                  // compute units of the device (hipDeviceAttributeMultiprocessorCount), queried once
+    } hs;
+    // dsh_linkage_* (linkage.hip): the components' tables (comp | rank | moff | coff | mem), the cell matrices of a batch, the
+    // state of its members, the labels before they go out, and the count of clusters + the error word
+    struct {
+        DevBuf tab, cells, nodes, labels, state;
+        uint64_t budget = 8ull << 30; // option linkage_budget_bytes: the matrices of a batch of components
+        uint32_t lds_max = 4096;      // option linkage_lds_max: components of at most this many members keep their per-row state in LDS
+        int partition = 1;            // option linkage_partition: 0 = the whole collection as one component
+        int route = -1;               // option linkage_route: -1 auto | 0 dense | 1 pairs
+        int route_last = -1;          // (info) the route the last dsh_linkage_threshold* call took
+    } lk;
+    // dsh_fold*, dsh_upload_sketches_folded*, dsh_union_groups* (derive.hip): the error word, a chunk of source rows or of
+    // folded rows on its way through the device, the groups' CSR and the partial unions of groups cut into chunks
+    struct {
+        DevBuf err, stage, ptr, mem, dst, part[2], out;
+        uint64_t chunk_bytes = (uint64_t)256 << 20;  // option derive_chunk_bytes: source rows staged per step of the host forms
+    } derive;
+    // multi-GPU exchange (exchange.hip, dsh_comm_*): an RCCL communicator over the ranks' contexts (not owned here:
+    // comm_release destroys it while the library is loaded)
+    struct {
+        ncclComm_t comm = nullptr;
+        int rank = 0, world = 1;
+        DevBuf gather_full, gather_local;  // dsh_dist_collect: the assembled matrix on the destination rank / this rank's span
+        // dsh_exchange_*: on the destination, the row-sorted spans as they arrive and the sources' key order + row offsets
+        DevBuf stage, tab;
+        Staging tabs;                 // the tables on their way to `tab` (sent on the COPY stream)
+        DevBuf place_tab;             // dsh_exchange_place_device's own tables (ctx stream; `tab` belongs to the copy stream)
+        bool recv_gated = false;      // (info) the last collect of a destination waited for its tile kernel
+        int recv_gate = -1;           // option xch_recv_gate: -1 auto | 0 | 1 (the destination's receives)
+        Event ev_place_done;          // the last placement of a collect (the copy stream joins it)
+        std::deque<Event> ev_round;   // round q of a collect has arrived (place_stream waits for it)
+        double place_ms = 0;          // (profiling) device time of the last dsh_exchange_place_device's placement kernel
+        // diagnostics (dsh_diag_spin_*): a kernel that waits like an RCCL receive kernel, on spin_stream
+        MappedWord spin_flag;
+        bool spin_running = false;
+    } xch;
 };
 
 namespace dsh {
@@ -277,13 +374,33 @@ inline int bind(dsh_ctx *c)
 
 inline hipEvent_t next_event(dsh_ctx *c)
 {
-    if (c->ev_used == c->ev_pool.size()) {
-        hipEvent_t e;
-        if (hipEventCreate(&e) != hipSuccess) return nullptr;
-        c->ev_pool.push_back(e);
-    }
+    if (c->ev_used == c->ev_pool.size() && add_event(c->ev_pool, hipEventDefault) != hipSuccess) return nullptr;
     return c->ev_pool[c->ev_used++];
 }
+
+// (profiling) the device time of what is enqueued on `st` between the constructor and stop(): two events of the pool.
+// Inert -- stop() waits for nothing and leaves `ms` alone -- while profiling is off or where an event could not be made.
+struct DeviceTimer {
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    hipStream_t st;
+    DeviceTimer(dsh_ctx *c, hipStream_t st_) : st(st_)
+    {
+        if (!c->profiling) return;
+        e0 = next_event(c);
+        e1 = next_event(c);
+        if (e0 && e1) (void)hipEventRecord(e0, st);
+    }
+    // waits for the interval's end; its milliseconds replace `ms` or, with `add`, are added to it
+    void stop(double &ms, bool add = false)
+    {
+        if (!e0 || !e1) return;
+        (void)hipEventRecord(e1, st);
+        (void)hipEventSynchronize(e1);
+        float t = 0;
+        (void)hipEventElapsedTime(&t, e0, e1);
+        ms = add ? ms + t : t;
+    }
+};
 
 // slots [first, first + cnt) inside [0, total) -- written so that first + cnt cannot wrap
 inline bool slots_ok(uint64_t first, uint64_t cnt, uint64_t total) { return first <= total && cnt <= total - first; }
@@ -310,7 +427,7 @@ inline void invalidate(dsh_ctx *c)
     c->planes_valid = false;
     c->card_estim = -1;
     c->hk32_valid = false;
-    c->pairs_card_estim = -1;
+    c->pairs.card_estim = -1;
 }
 
 // hipStreamWaitValue32 on this device (asked once): what lets the parts of a call announce themselves from inside k_finalize

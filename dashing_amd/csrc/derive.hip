@@ -12,8 +12,8 @@ namespace {
 
 int err_begin(dsh_ctx *c)
 {
-    HIPCHK(c, c->derive_err.ensure(sizeof(unsigned long long)));
-    HIPCHK(c, hipMemsetAsync(c->derive_err.ptr, 0xFF, sizeof(unsigned long long), c->stream));
+    HIPCHK(c, c->derive.err.ensure(sizeof(unsigned long long)));
+    HIPCHK(c, hipMemsetAsync(c->derive.err.ptr, 0xFF, sizeof(unsigned long long), c->stream));
     return DSH_OK;
 }
 
@@ -21,7 +21,7 @@ int err_begin(dsh_ctx *c)
 int err_end(dsh_ctx *c, int src_p)
 {
     unsigned long long e = ~0ull;
-    HIPCHK(c, hipMemcpyAsync(&e, c->derive_err.ptr, sizeof e, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(&e, c->derive.err.ptr, sizeof e, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (e != ~0ull)
         return fail(c, DSH_EINVAL, "sketch %llu holds a register value above %d (= 64 - p + 1): not an HLL of precision %d (corrupt or foreign .hll?)",
@@ -29,7 +29,7 @@ int err_end(dsh_ctx *c, int src_p)
     return DSH_OK;
 }
 
-uint64_t chunk_rows(const dsh_ctx *c, int src_p) { return std::max<uint64_t>(c->derive_chunk_bytes >> src_p, 1); }
+uint64_t chunk_rows(const dsh_ctx *c, int src_p) { return std::max<uint64_t>(c->derive.chunk_bytes >> src_p, 1); }
 
 int check_fold(dsh_ctx *c, uint64_t first, uint64_t n, int new_p)
 {
@@ -61,15 +61,15 @@ int run_union(dsh_ctx *c, const uint64_t *gp, const uint32_t *members, uint64_t 
     const int p = c->p;
     const uint64_t blocks_per_row = std::max<uint64_t>(((uint64_t)1 << p) >> 12, 1);
     const uint64_t base = gp[0], total = gp[ng] - base;
-    HIPCHK(c, c->derive_mem.ensure(std::max<uint64_t>(total, 1) * sizeof(uint32_t)));
-    if (total) HIPCHK(c, hipMemcpyAsync(c->derive_mem.ptr, members + base, total * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, c->derive.mem.ensure(std::max<uint64_t>(total, 1) * sizeof(uint32_t)));
+    if (total) HIPCHK(c, hipMemcpyAsync(c->derive.mem.ptr, members + base, total * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
     std::vector<uint64_t> cptr(ng + 1);
     std::vector<uint32_t> cdst(ng);
     for (uint64_t g = 0; g <= ng; ++g) cptr[g] = gp[g] - base;
     for (uint64_t g = 0; g < ng; ++g) cdst[g] = (uint32_t)g;
     std::vector<UnionLevel> keep;  // what the uploads of the levels read: alive until the stream is idle
     const uint8_t *src = c->regs;
-    const uint32_t *mem = (const uint32_t *)c->derive_mem.ptr;
+    const uint32_t *mem = (const uint32_t *)c->derive.mem.ptr;
     for (int lvl = 0; !cdst.empty(); ++lvl) {
         // a workgroup streams its group's members one after the other: no group may hold more than a small share of the
         // launch's work (about 2048 workgroups run at a time), and none is cut below 64 members (a chunk costs a row of
@@ -98,13 +98,13 @@ int run_union(dsh_ctx *c, const uint64_t *gp, const uint32_t *members, uint64_t 
         v.ptr.push_back(cptr[cnt]);
         if (srow >= 0x80000000ull) return fail(c, DSH_EINVAL, "too many members");
         const uint64_t nv = v.dst.size();
-        DevBuf &part = c->derive_part[lvl & 1];
-        HIPCHK(c, c->derive_ptr.ensure((nv + 1) * sizeof(uint64_t)));
-        HIPCHK(c, c->derive_dst.ensure(nv * sizeof(uint32_t)));
+        DevBuf &part = c->derive.part[lvl & 1];
+        HIPCHK(c, c->derive.ptr.ensure((nv + 1) * sizeof(uint64_t)));
+        HIPCHK(c, c->derive.dst.ensure(nv * sizeof(uint32_t)));
         if (srow) HIPCHK(c, part.ensure(srow << p));
-        HIPCHK(c, hipMemcpyAsync(c->derive_ptr.ptr, v.ptr.data(), (nv + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(c->derive_dst.ptr, v.dst.data(), nv * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, launch_union_groups(c->stream, src, p, (const uint64_t *)c->derive_ptr.ptr, mem, (const uint32_t *)c->derive_dst.ptr,
+        HIPCHK(c, hipMemcpyAsync(c->derive.ptr.ptr, v.ptr.data(), (nv + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(c->derive.dst.ptr, v.dst.data(), nv * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, launch_union_groups(c->stream, src, p, (const uint64_t *)c->derive.ptr.ptr, mem, (const uint32_t *)c->derive.dst.ptr,
                                       nv, d_out, (uint8_t *)part.ptr));
         src = (const uint8_t *)part.ptr;
         mem = nullptr;
@@ -142,7 +142,7 @@ int dsh_fold_device(dsh_ctx *c, uint64_t first, uint64_t n, int new_p, void *d_o
     if (!d_out) return DSH_EINVAL;
     if ((rc = err_begin(c))) return rc;
     HIPCHK(c, launch_fold(c->stream, c->regs + (first << c->p), n, c->p, new_p, first, (uint8_t *)d_out,
-                          (unsigned long long *)c->derive_err.ptr));
+                          (unsigned long long *)c->derive.err.ptr));
     return err_end(c, c->p);
 }
 
@@ -153,12 +153,12 @@ int dsh_fold(dsh_ctx *c, uint64_t first, uint64_t n, int new_p, uint8_t *out)
     if (!out) return DSH_EINVAL;
     if ((rc = err_begin(c))) return rc;
     const uint64_t rows = std::min(chunk_rows(c, c->p), n);
-    HIPCHK(c, c->derive_out.ensure(rows << new_p));
+    HIPCHK(c, c->derive.out.ensure(rows << new_p));
     for (uint64_t r0 = 0; r0 < n; r0 += rows) {
         const uint64_t cnt = std::min(rows, n - r0);
-        if (launch_fold(c->stream, c->regs + ((first + r0) << c->p), cnt, c->p, new_p, first + r0, (uint8_t *)c->derive_out.ptr,
-                        (unsigned long long *)c->derive_err.ptr) != hipSuccess ||
-            hipMemcpyAsync(out + (r0 << new_p), c->derive_out.ptr, cnt << new_p, hipMemcpyDeviceToHost, c->stream) != hipSuccess)
+        if (launch_fold(c->stream, c->regs + ((first + r0) << c->p), cnt, c->p, new_p, first + r0, (uint8_t *)c->derive.out.ptr,
+                        (unsigned long long *)c->derive.err.ptr) != hipSuccess ||
+            hipMemcpyAsync(out + (r0 << new_p), c->derive.out.ptr, cnt << new_p, hipMemcpyDeviceToHost, c->stream) != hipSuccess)
             return drain(c, fail(c, DSH_EIO, "fold of rows %llu.. failed", (unsigned long long)(first + r0)));
     }
     return err_end(c, c->p);
@@ -172,7 +172,7 @@ int dsh_upload_sketches_folded_device(dsh_ctx *c, const void *d_regs, int src_p,
     if ((rc = err_begin(c))) return rc;
     invalidate(c);
     HIPCHK(c, launch_fold(c->stream, (const uint8_t *)d_regs, n, src_p, c->p, first, (uint8_t *)c->regs_own.ptr + (first << c->p),
-                          (unsigned long long *)c->derive_err.ptr));
+                          (unsigned long long *)c->derive.err.ptr));
     return err_end(c, src_p);
 }
 
@@ -184,13 +184,13 @@ int dsh_upload_sketches_folded(dsh_ctx *c, const uint8_t *regs, int src_p, uint6
     if ((rc = err_begin(c))) return rc;
     invalidate(c);
     const uint64_t rows = std::min(chunk_rows(c, src_p), n);
-    HIPCHK(c, c->derive_stage.ensure(rows << src_p));
+    HIPCHK(c, c->derive.stage.ensure(rows << src_p));
     for (uint64_t r0 = 0; r0 < n; r0 += rows) {
         // (the stream orders a chunk's fold before the next chunk's copy into the same scratch)
         const uint64_t cnt = std::min(rows, n - r0);
-        if (hipMemcpyAsync(c->derive_stage.ptr, regs + (r0 << src_p), cnt << src_p, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
-            launch_fold(c->stream, (const uint8_t *)c->derive_stage.ptr, cnt, src_p, c->p, first + r0,
-                        (uint8_t *)c->regs_own.ptr + ((first + r0) << c->p), (unsigned long long *)c->derive_err.ptr) != hipSuccess)
+        if (hipMemcpyAsync(c->derive.stage.ptr, regs + (r0 << src_p), cnt << src_p, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+            launch_fold(c->stream, (const uint8_t *)c->derive.stage.ptr, cnt, src_p, c->p, first + r0,
+                        (uint8_t *)c->regs_own.ptr + ((first + r0) << c->p), (unsigned long long *)c->derive.err.ptr) != hipSuccess)
             return drain(c, fail(c, DSH_EIO, "folded upload of rows %llu.. failed", (unsigned long long)(first + r0)));
     }
     return err_end(c, src_p);
@@ -210,9 +210,9 @@ int dsh_union_groups(dsh_ctx *c, const uint64_t *group_ptr, const uint32_t *memb
     int rc = check_union(c, group_ptr, members, n_groups);
     if (rc || !n_groups) return rc;
     if (!out) return DSH_EINVAL;
-    HIPCHK(c, c->derive_out.ensure(n_groups << c->p));
-    if ((rc = run_union(c, group_ptr, members, n_groups, (uint8_t *)c->derive_out.ptr))) return drain(c, rc);
-    HIPCHK(c, hipMemcpyAsync(out, c->derive_out.ptr, n_groups << c->p, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, c->derive.out.ensure(n_groups << c->p));
+    if ((rc = run_union(c, group_ptr, members, n_groups, (uint8_t *)c->derive.out.ptr))) return drain(c, rc);
+    HIPCHK(c, hipMemcpyAsync(out, c->derive.out.ptr, n_groups << c->p, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return DSH_OK;
 }

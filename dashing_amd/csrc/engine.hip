@@ -56,12 +56,7 @@ int prepare(dsh_ctx *c, int estim, int want_sorted, bool card_only, uint64_t wan
     const bool have_pass = c->card_estim == estim && c->card_from <= need_from;
     if (have_pass && (card_only || same_layout)) return DSH_OK;
     const bool keep_layout = same_layout && have_pass;  // (a new pass below also outdates the layout's per-column data)
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (c->profiling) {
-        e0 = next_event(c);
-        e1 = next_event(c);
-        if (e0) (void)hipEventRecord(e0, c->stream);
-    }
+    DeviceTimer timer(c, c->stream);
     // the per-sketch pass depends on (registers, estimator, emax) only: a new column layout reuses it
     if (!have_pass) {
         HIPCHK(c, c->card.ensure(std::max<uint64_t>(n, 1) * sizeof(double)));
@@ -82,7 +77,7 @@ int prepare(dsh_ctx *c, int estim, int want_sorted, bool card_only, uint64_t wan
         if (n > need_from)
             HIPCHK(c, hipMemcpyAsync((uint32_t *)c->pin_keys.ptr + need_from, (const uint32_t *)c->keys.ptr + need_from,
                                      (n - need_from) * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-        if (!c->ev_keys) HIPCHK(c, hipEventCreateWithFlags(&c->ev_keys, hipEventDisableTiming));
+        HIPCHK(c, c->ev_keys.ensure());
         HIPCHK(c, hipEventRecord(c->ev_keys, c->stream));
         HIPCHK(c, launch_card_from_hist(c->stream, (const uint32_t *)c->hist.ptr, (const uint32_t *)c->keys.ptr, need_from, n,
                                         c->p, estim, (double *)c->card.ptr));
@@ -92,13 +87,7 @@ int prepare(dsh_ctx *c, int estim, int want_sorted, bool card_only, uint64_t wan
         ++c->pass_gen;
     }
     if (card_only) {  // a cardinality query never builds planes (and leaves stale ones marked so)
-        if (e0 && e1) {
-            (void)hipEventRecord(e1, c->stream);
-            (void)hipEventSynchronize(e1);
-            float ms = 0;
-            (void)hipEventElapsedTime(&ms, e0, e1);
-            c->prep_ms += ms;
-        }
+        timer.stop(c->prep_ms, /*add=*/true);
         return DSH_OK;
     }
 #ifdef DSH_EXPERIMENT_REUSE_LAYOUT
@@ -151,29 +140,20 @@ int prepare(dsh_ctx *c, int estim, int want_sorted, bool card_only, uint64_t wan
             const uint64_t nperm = L.perm.size();
             HIPCHK(c, c->perm.ensure(std::max<uint64_t>(nperm, 1) * sizeof(uint32_t)));
             if (nperm) {
-                if (c->perm_in_flight) {  // the previous layout's upload from pin_perm
-                    HIPCHK(c, hipEventSynchronize(c->ev_perm));
-                    c->perm_in_flight = false;
-                }
-                if (nperm > c->pin_perm_cap) {
-                    if (c->pin_perm) (void)hipHostFree(c->pin_perm);
-                    c->pin_perm = nullptr;
-                    c->pin_perm_cap = 0;
-                    HIPCHK(c, hipHostMalloc((void **)&c->pin_perm, nperm * sizeof(uint32_t), hipHostMallocDefault));
-                    c->pin_perm_cap = nperm;
-                }
-                std::memcpy(c->pin_perm, L.perm.data(), nperm * sizeof(uint32_t));
-                HIPCHK(c, launch_upload(c->stream, c->perm.ptr, c->pin_perm, nperm * sizeof(uint32_t)));
-                if (L.rowsorted) {  // where the rows of the rank's buffer start
-                    const size_t rb_ = L.rowoff.size() * sizeof(uint64_t);
-                    HIPCHK(c, c->pin_rowoff.ensure(rb_));
+                // one staging block (the previous layout's upload from it has run): perm, then where the rows of a
+                // row-sorted rank's buffer start
+                const size_t pb_ = (nperm * sizeof(uint32_t) + 15) & ~(size_t)15;
+                const size_t rb_ = L.rowsorted ? L.rowoff.size() * sizeof(uint64_t) : 0;
+                HIPCHK(c, c->st_perm.room(pb_ + rb_));
+                uint8_t *h = (uint8_t *)c->st_perm.ptr();
+                std::memcpy(h, L.perm.data(), nperm * sizeof(uint32_t));
+                HIPCHK(c, launch_upload(c->stream, c->perm.ptr, h, nperm * sizeof(uint32_t)));
+                if (L.rowsorted) {
                     HIPCHK(c, c->rowoff.ensure(rb_));
-                    std::memcpy(c->pin_rowoff.ptr, L.rowoff.data(), rb_);
-                    HIPCHK(c, launch_upload(c->stream, c->rowoff.ptr, c->pin_rowoff.ptr, rb_));
+                    std::memcpy(h + pb_, L.rowoff.data(), rb_);
+                    HIPCHK(c, launch_upload(c->stream, c->rowoff.ptr, h + pb_, rb_));
                 }
-                if (!c->ev_perm) HIPCHK(c, hipEventCreateWithFlags(&c->ev_perm, hipEventDisableTiming));
-                HIPCHK(c, hipEventRecord(c->ev_perm, c->stream));
-                c->perm_in_flight = true;
+                HIPCHK(c, c->st_perm.sent(c->stream));
             }
         }
         const uint32_t NT = L.Npad / kTile;
@@ -236,13 +216,7 @@ int prepare(dsh_ctx *c, int estim, int want_sorted, bool card_only, uint64_t wan
         c->lay_gen = c->pass_gen;
         c->planes_valid = true;
     }
-    if (e0 && e1) {
-        (void)hipEventRecord(e1, c->stream);
-        (void)hipEventSynchronize(e1);
-        float ms = 0;
-        (void)hipEventElapsedTime(&ms, e0, e1);
-        c->prep_ms += ms;
-    }
+    timer.stop(c->prep_ms, /*add=*/true);
     return DSH_OK;
 }
 
@@ -322,16 +296,12 @@ int reserve_lists(dsh_ctx *c, PairRun &r)
     const uint64_t nitems_total = r.item_off.back();
     pp.items.reserve(nitems_total);
     // tile and item lists travel through page-locked staging, so nothing in the band loop needs the host to wait
-    if (c->lists_in_flight) {  // the previous call's upload (long done unless calls are issued back to back)
-        HIPCHK(c, hipEventSynchronize(c->ev_lists));
-        c->lists_in_flight = false;
-    }
+    // (the previous call's upload is long done unless calls are issued back to back)
     static_assert(sizeof(plan::U4) == sizeof(uint4), "plan::U4 must have the layout of uint4");
-    HIPCHK(c, c->pin_lists.ensure((2 * T.size() + std::max<uint64_t>(nitems_total, 1)) * sizeof(uint4)));
-    r.pinT = (plan::U4 *)c->pin_lists.ptr, r.pinF = r.pinT + T.size(), r.pinI = r.pinF + T.size();
+    HIPCHK(c, c->st_lists.room((2 * T.size() + std::max<uint64_t>(nitems_total, 1)) * sizeof(uint4)));
+    r.pinT = (plan::U4 *)c->st_lists.ptr(), r.pinF = r.pinT + T.size(), r.pinI = r.pinF + T.size();
     HIPCHK(c, c->tiles.ensure(2 * T.size() * sizeof(uint4)));  // [tile kernel's list | k_finalize's list]
     HIPCHK(c, c->items.ensure(std::max<uint64_t>(nitems_total, 1) * sizeof(uint4)));
-    if (!c->ev_lists) HIPCHK(c, hipEventCreateWithFlags(&c->ev_lists, hipEventDisableTiming));
     HIPCHK(c, c->cum.ensure(std::max<uint64_t>(pp.per_tile_bytes * pp.max_band, 256)));
     return DSH_OK;
 }
@@ -342,16 +312,12 @@ int stage_signal_block(dsh_ctx *c, PairRun &r)
     ++c->sig_gen;
     if (c->sig_gen == 0) c->sig_gen = 1;
     // the parts' tile totals (host -> device through page-locked staging), their counters cleared
-    if (c->sig_in_flight) {
-        HIPCHK(c, hipEventSynchronize(c->ev_sig));
-        c->sig_in_flight = false;
-    }
+    HIPCHK(c, c->st_sig.room((2 * kSigMaxParts + 2) * sizeof(uint32_t)));
     // the words kSigPartCnt .. kSigStamp of the block lie one behind the other: the parts' counters (zero), their totals,
     // the call's generation, the stamp switch -- uploaded with the first band's lists, in one launch (the tile counters
     // clear themselves: k_finalize_signal)
     static_assert(kSigPartTotal == kSigPartCnt + kSigMaxParts && kSigGen == kSigPartTotal + kSigMaxParts && kSigStamp == kSigGen + 1, "signal block layout");
-    HIPCHK(c, c->pin_sig.ensure((2 * kSigMaxParts + 2) * sizeof(uint32_t)));
-    uint32_t *blk = (uint32_t *)c->pin_sig.ptr, *tot = blk + kSigMaxParts;
+    uint32_t *blk = (uint32_t *)c->st_sig.ptr(), *tot = blk + kSigMaxParts;
     for (uint32_t qd = 0; qd < kSigMaxParts; ++qd) blk[qd] = 0u;
     for (uint32_t qd = 0; qd < kSigMaxParts; ++qd) tot[qd] = qd < c->pp.part_tiles.size() ? c->pp.part_tiles[qd] : 0u;
     tot[kSigMaxParts] = c->sig_gen;                   // kSigGen
@@ -408,7 +374,7 @@ FinalizeLaunch finalize_invariants(const dsh_ctx *c, const PairJob &job, bool wi
 }
 
 // this band's items and list entries: planned, staged, uploaded (the uploads read the staging when they run: it is
-// not touched again before ev_lists of this call has passed)
+// not touched again before st_lists' event of this call has passed)
 int upload_band(dsh_ctx *c, PairRun &r, size_t bi)
 {
     plan::PairPlan &pp = c->pp;
@@ -426,19 +392,16 @@ int upload_band(dsh_ctx *c, PairRun &r, size_t bi)
     c->host_lists_us += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_b0).count();
     UploadSegs up;
     uint32_t nseg = 0;
-    if (r.sig_upload) up.add(nseg, (uint32_t *)c->sig.ptr + kSigPartCnt, c->pin_sig.ptr, (2 * kSigMaxParts + 2) * sizeof(uint32_t));
+    if (r.sig_upload) up.add(nseg, (uint32_t *)c->sig.ptr + kSigPartCnt, c->st_sig.ptr(), (2 * kSigMaxParts + 2) * sizeof(uint32_t));
     up.add(nseg, (uint4 *)c->tiles.ptr + bd.first, r.pinT + bd.first, (size_t)nt * sizeof(uint4));
     up.add(nseg, (uint4 *)c->tiles.ptr + nT + bd.first, r.pinF + bd.first, (size_t)nt * sizeof(uint4));
     up.add(nseg, (uint4 *)c->items.ptr + r.item_off[bi], r.pinI + r.item_off[bi], (size_t)ni * sizeof(uint4));
     HIPCHK(c, launch_upload_segs(c->stream, up, nseg));
     if (r.sig_upload) {
-        if (!c->ev_sig) HIPCHK(c, hipEventCreateWithFlags(&c->ev_sig, hipEventDisableTiming));
-        HIPCHK(c, hipEventRecord(c->ev_sig, c->stream));
-        c->sig_in_flight = true;
+        HIPCHK(c, c->st_sig.sent(c->stream));
         r.sig_upload = false;
     }
-    HIPCHK(c, hipEventRecord(c->ev_lists, c->stream));
-    c->lists_in_flight = true;
+    HIPCHK(c, c->st_lists.sent(c->stream));
     return DSH_OK;
 }
 
@@ -489,11 +452,7 @@ int finalize_band(dsh_ctx *c, PairRun &r, size_t bi)
         HIPCHK(c, launch_finalize(fst, f));
         if (sg.part >= 0) {  // this segment completes a part: its span of the matrix is final
             const size_t qp = (size_t)sg.part;
-            while (c->ev_part.size() <= qp) {
-                hipEvent_t e = nullptr;
-                HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-                c->ev_part.push_back(e);
-            }
+            while (c->ev_part.size() <= qp) HIPCHK(c, add_event(c->ev_part));
             HIPCHK(c, hipEventRecord(c->ev_part[qp], fst));
             c->parts_done = (uint32_t)qp + 1;
             if (r.e_call0) {
@@ -633,7 +592,7 @@ int run_pairs(dsh_ctx *c, const PairJob &job)
         if ((rc = launch_tile_kernel(c, r, bi, nslots))) return rc;
         if (b) (void)hipEventRecord(b, c->stream);
         if (bi == 0) {  // (the destination of an exchange may post its receives behind its first tile kernel, exchange.hip)
-            if (!c->ev_first_tiles) HIPCHK(c, hipEventCreateWithFlags(&c->ev_first_tiles, hipEventDisableTiming));
+            HIPCHK(c, c->ev_first_tiles.ensure());
             HIPCHK(c, hipEventRecord(c->ev_first_tiles, c->stream));
         }
         r.fin.a.nslots = nslots;  // (the band's stride: the distance between two planes of its C(v))

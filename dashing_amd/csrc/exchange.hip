@@ -99,7 +99,7 @@ double env_seconds(const char *name, double dflt)
 // stream) and the call fails with a message; DSH_COMM_TIMEOUT_S (default 120) sets the deadline.
 int sync_guarded(dsh_ctx *c, hipStream_t st, const char *what)
 {
-    if (!c->comm || c->comm_world == 1) {
+    if (!c->xch.comm || c->xch.world == 1) {
         HIPCHK(c, hipStreamSynchronize(st));
         return DSH_OK;
     }
@@ -113,10 +113,10 @@ int sync_guarded(dsh_ctx *c, hipStream_t st, const char *what)
         if (++spins > 2000) std::this_thread::sleep_for(std::chrono::microseconds(50));
         if ((spins & 1023u) == 0 &&
             std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > limit) {
-            (void)rccl()->CommAbort(c->comm);
-            c->comm = nullptr;
-            c->comm_rank = 0;
-            c->comm_world = 1;
+            (void)rccl()->CommAbort(c->xch.comm);
+            c->xch.comm = nullptr;
+            c->xch.rank = 0;
+            c->xch.world = 1;
             return fail(c, DSH_EIO, "%s: the RCCL exchange did not complete within %.0f s (DSH_COMM_TIMEOUT_S): a peer "
                                     "is missing or stuck; the communicator was aborted", what, limit);
         }
@@ -155,13 +155,13 @@ namespace dsh {
 
 int comm_release(dsh_ctx *c)
 {
-    if (!c->comm) return DSH_OK;
+    if (!c->xch.comm) return DSH_OK;
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     if (c->copy_stream) (void)hipStreamSynchronize(c->copy_stream);  // dsh_collect_parts_async sends there
-    const ncclResult_t e = rccl()->CommDestroy(c->comm);
-    c->comm = nullptr;
-    c->comm_rank = 0;
-    c->comm_world = 1;
+    const ncclResult_t e = rccl()->CommDestroy(c->xch.comm);
+    c->xch.comm = nullptr;
+    c->xch.rank = 0;
+    c->xch.world = 1;
     return e == ncclSuccess ? DSH_OK : fail(c, DSH_EIO, "ncclCommDestroy: %s", rccl()->GetErrorString(e));
 }
 
@@ -249,10 +249,10 @@ int dsh_comm_init(dsh_ctx *c, const void *unique_id, int rank, int world)
                                     "not every rank joined", rank, world, limit);
         }
         if (sh->res != ncclSuccess) return fail(c, DSH_EIO, "ncclCommInitRank: %s", r->GetErrorString(sh->res));
-        c->comm = sh->comm;
+        c->xch.comm = sh->comm;
     }
-    c->comm_rank = rank;
-    c->comm_world = world;
+    c->xch.rank = rank;
+    c->xch.world = world;
     return DSH_OK;
 }
 
@@ -267,9 +267,9 @@ int dsh_comm_destroy(dsh_ctx *c)
 int dsh_comm_rank(const dsh_ctx *c, int *rank, int *world)
 {
     if (!c) return DSH_EINVAL;
-    if (rank) *rank = c->comm_rank;
-    if (world) *world = c->comm ? c->comm_world : 1;
-    return c->comm ? DSH_OK : DSH_ESTATE;
+    if (rank) *rank = c->xch.rank;
+    if (world) *world = c->xch.comm ? c->xch.world : 1;
+    return c->xch.comm ? DSH_OK : DSH_ESTATE;
 }
 
 int dsh_comm_wait(dsh_ctx *c)
@@ -283,7 +283,7 @@ int dsh_comm_wait(dsh_ctx *c)
 
 static int collect_spans(dsh_ctx *c, uint64_t n, const uint64_t *bounds, const void *d_local, void *d_final, int dst)
 {
-    const int world = c->comm ? c->comm_world : 1, rank = c->comm ? c->comm_rank : 0;
+    const int world = c->xch.comm ? c->xch.world : 1, rank = c->xch.comm ? c->xch.rank : 0;
     int rc = validate_bounds(c, n, bounds, world, dst);
     if (rc) return rc;
     const uint64_t mine = dsh_tri_span(n, bounds[rank], bounds[rank + 1]);
@@ -304,14 +304,14 @@ static int collect_spans(dsh_ctx *c, uint64_t n, const uint64_t *bounds, const v
         for (int src = 0; src < world; ++src) {
             const uint64_t cnt = dsh_tri_span(n, bounds[src], bounds[src + 1]);
             if (src == dst || cnt == 0) continue;
-            ncclResult_t e = r->Recv((float *)d_final + dsh_tri_span(n, 0, bounds[src]), cnt, ncclFloat32, src, c->comm, c->stream);
+            ncclResult_t e = r->Recv((float *)d_final + dsh_tri_span(n, 0, bounds[src]), cnt, ncclFloat32, src, c->xch.comm, c->stream);
             if (e != ncclSuccess) {
                 (void)r->GroupEnd();
                 return fail(c, DSH_EIO, "ncclRecv: %s", r->GetErrorString(e));
             }
         }
     } else if (mine) {
-        ncclResult_t e = r->Send(d_local, mine, ncclFloat32, dst, c->comm, c->stream);
+        ncclResult_t e = r->Send(d_local, mine, ncclFloat32, dst, c->xch.comm, c->stream);
         if (e != ncclSuccess) {
             (void)r->GroupEnd();
             return fail(c, DSH_EIO, "ncclSend: %s", r->GetErrorString(e));
@@ -326,7 +326,7 @@ int dsh_collect_spans_async(dsh_ctx *c, uint64_t n, const uint64_t *bounds, cons
     if (!c) return DSH_EINVAL;
     int rc = bind(c);
     if (rc) return rc;
-    if (!c->comm && !(bounds && bounds[0] == 0 && bounds[1] == n)) return fail(c, DSH_ESTATE, "dsh_comm_init first");
+    if (!c->xch.comm && !(bounds && bounds[0] == 0 && bounds[1] == n)) return fail(c, DSH_ESTATE, "dsh_comm_init first");
     return collect_spans(c, n, bounds, d_local, d_final, dst);
 }
 
@@ -343,8 +343,8 @@ int dsh_collect_parts_async(dsh_ctx *c, uint64_t n, const uint64_t *bounds, uint
     if (!c || !bounds || nparts == 0) return DSH_EINVAL;
     int rc = bind(c);
     if (rc) return rc;
-    const int world = c->comm ? c->comm_world : 1, rank = c->comm ? c->comm_rank : 0;
-    if (!c->comm && !(bounds[0] == 0 && bounds[1] == n)) return fail(c, DSH_ESTATE, "dsh_comm_init first");
+    const int world = c->xch.comm ? c->xch.world : 1, rank = c->xch.comm ? c->xch.rank : 0;
+    if (!c->xch.comm && !(bounds[0] == 0 && bounds[1] == n)) return fail(c, DSH_ESTATE, "dsh_comm_init first");
     if ((rc = validate_bounds(c, n, bounds, world, dst))) return rc;
     if (rank == dst && !d_final) return DSH_EINVAL;
     // every rank's parts, from the same function the compute used (dsh_range_parts): both sides of a message agree.
@@ -379,13 +379,13 @@ int dsh_collect_parts_async(dsh_ctx *c, uint64_t n, const uint64_t *bounds, uint
             for (int src = 0; src < world && e == ncclSuccess; ++src) {
                 if (src == dst || q >= parts[src].size() - 1) continue;
                 const uint64_t cnt = dsh_tri_span(n, parts[src][q], parts[src][q + 1]);
-                if (cnt) e = rc_->Recv((float *)d_final + dsh_tri_span(n, 0, parts[src][q]), cnt, ncclFloat32, src, c->comm, c->copy_stream);
+                if (cnt) e = rc_->Recv((float *)d_final + dsh_tri_span(n, 0, parts[src][q]), cnt, ncclFloat32, src, c->xch.comm, c->copy_stream);
             }
         } else if (q < myparts) {
             const uint64_t o0 = dsh_tri_span(n, 0, parts[rank][q]) - my_off, cnt = dsh_tri_span(n, parts[rank][q], parts[rank][q + 1]);
             if (cnt) {
                 if (!d_local) e = ncclInvalidArgument;
-                else e = rc_->Send((const float *)d_local + o0, cnt, ncclFloat32, dst, c->comm, c->copy_stream);
+                else e = rc_->Send((const float *)d_local + o0, cnt, ncclFloat32, dst, c->xch.comm, c->copy_stream);
             }
         }
         if (e != ncclSuccess) {
@@ -576,8 +576,8 @@ int dsh_exchange_collect_async(dsh_ctx *c, uint64_t n, const uint64_t *rowsets, 
     if (rc) return rc;
     plan::RowSets rs;
     if ((rc = parse_table(c, n, rowsets, dst, rs))) return rc;
-    const int world = c->comm ? c->comm_world : 1, rank = c->comm ? c->comm_rank : 0;
-    if (!c->comm && rs.world != 1) return fail(c, DSH_ESTATE, "dsh_comm_init first");
+    const int world = c->xch.comm ? c->xch.world : 1, rank = c->xch.comm ? c->xch.rank : 0;
+    if (!c->xch.comm && rs.world != 1) return fail(c, DSH_ESTATE, "dsh_comm_init first");
     if ((int)rs.world != world) return fail(c, DSH_EINVAL, "the row-set table is for %u ranks, the communicator has %d", rs.world, world);
     if (rank == dst && !d_final) return DSH_EINVAL;
     const std::vector<XMode> modes = xmodes(n, rs, nparts, dst, c->parts_signalled ? rank : -1);  // (as this rank's compute call cut them)
@@ -621,11 +621,8 @@ int dsh_exchange_collect_async(dsh_ctx *c, uint64_t n, const uint64_t *rowsets, 
             tab_bytes += (rowoff[r].size() * sizeof(uint64_t) + order[r].size() * sizeof(uint32_t) + 15) & ~(uint64_t)15;
         }
         if (stage_total) {
-            HIPCHK(c, c->xch_stage.ensure(stage_total * sizeof(float)));
-            if (c->xch_tab_in_flight) {  // the previous call's upload from the pinned tables
-                HIPCHK(c, hipEventSynchronize(c->ev_xch_tab));
-                c->xch_tab_in_flight = false;
-            }
+            HIPCHK(c, c->xch.stage.ensure(stage_total * sizeof(float)));
+            HIPCHK(c, c->xch.tabs.wait());  // the previous call's upload from the pinned tables
             // behind the sources' tables: the entries of every round's placement launch (k_rows_place) -- the rows of a
             // source that lie completely inside its first q + 1 messages and did not inside its first q
             ent_off = tab_bytes;
@@ -655,31 +652,25 @@ int dsh_exchange_collect_async(dsh_ctx *c, uint64_t n, const uint64_t *rowsets, 
             }
             round_ent[M] = (uint32_t)ents.size();
             tab_bytes += ents.size() * sizeof(PlaceEnt);
-            HIPCHK(c, c->pin_xch.ensure(tab_bytes));
-            HIPCHK(c, c->xch_tab.ensure(tab_bytes));
+            HIPCHK(c, c->xch.tabs.room(tab_bytes));
+            HIPCHK(c, c->xch.tab.ensure(tab_bytes));
             for (int r = 0; r < world; ++r) {
                 if (r == dst || !modes[r].rowsorted) continue;
-                uint8_t *h = (uint8_t *)c->pin_xch.ptr + tab_off[r];
+                uint8_t *h = (uint8_t *)c->xch.tabs.ptr() + tab_off[r];
                 std::memcpy(h, rowoff[r].data(), rowoff[r].size() * sizeof(uint64_t));
                 std::memcpy(h + rowoff[r].size() * sizeof(uint64_t), order[r].data(), order[r].size() * sizeof(uint32_t));
             }
             for (size_t x = 0; x < ents.size(); ++x) {
                 const int src = ent_src[x];
-                const uint8_t *t = (const uint8_t *)c->xch_tab.ptr + tab_off[src];
-                ents[x].src = (const float *)c->xch_stage.ptr + stage_off[src];
+                const uint8_t *t = (const uint8_t *)c->xch.tab.ptr + tab_off[src];
+                ents[x].src = (const float *)c->xch.stage.ptr + stage_off[src];
                 ents[x].rowoff = (const uint64_t *)t;
                 ents[x].order = (const uint32_t *)(t + rowoff[src].size() * sizeof(uint64_t));
             }
-            if (!ents.empty()) std::memcpy((uint8_t *)c->pin_xch.ptr + ent_off, ents.data(), ents.size() * sizeof(PlaceEnt));
-            HIPCHK(c, hipMemcpyAsync(c->xch_tab.ptr, c->pin_xch.ptr, tab_bytes, hipMemcpyHostToDevice, c->copy_stream));
-            if (!c->ev_xch_tab) HIPCHK(c, hipEventCreateWithFlags(&c->ev_xch_tab, hipEventDisableTiming));
-            HIPCHK(c, hipEventRecord(c->ev_xch_tab, c->copy_stream));
-            c->xch_tab_in_flight = true;
-            while (c->ev_round.size() < M) {
-                hipEvent_t e = nullptr;
-                HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-                c->ev_round.push_back(e);
-            }
+            if (!ents.empty()) std::memcpy((uint8_t *)c->xch.tabs.ptr() + ent_off, ents.data(), ents.size() * sizeof(PlaceEnt));
+            HIPCHK(c, hipMemcpyAsync(c->xch.tab.ptr, c->xch.tabs.ptr(), tab_bytes, hipMemcpyHostToDevice, c->copy_stream));
+            HIPCHK(c, c->xch.tabs.sent(c->copy_stream));
+            while (c->xch.ev_round.size() < M) HIPCHK(c, add_event(c->xch.ev_round));
         }
     }
     // (source) where this rank's parts end in its buffer: message q waits for the part that holds its last value
@@ -694,9 +685,9 @@ int dsh_exchange_collect_async(dsh_ctx *c, uint64_t n, const uint64_t *rowsets, 
     // xch_recv_gate: -1 auto | 0 at once | 1 behind the first tile kernel).
     if (rank == dst && world > 1 && mine.nparts() && c->ev_first_tiles) {
         const uint64_t rounds = (c->pp.items.size() + 511) / 512;
-        const bool gate = c->xch_recv_gate == 1 || (c->xch_recv_gate < 0 && c->last_bands == 1 && rounds <= 8);
+        const bool gate = c->xch.recv_gate == 1 || (c->xch.recv_gate < 0 && c->last_bands == 1 && rounds <= 8);
         if (gate) HIPCHK(c, hipStreamWaitEvent(c->copy_stream, c->ev_first_tiles, 0));
-        c->xch_recv_gated = gate;
+        c->xch.recv_gated = gate;
     }
     bool placed = false;
     size_t next_wait = 0;  // (source) the first part the copy stream has not joined yet
@@ -731,13 +722,13 @@ int dsh_exchange_collect_async(dsh_ctx *c, uint64_t n, const uint64_t *rowsets, 
                 uint64_t first, cnt;
                 message_span(total[src], q, M, first, cnt);
                 if (!cnt) continue;
-                float *to = modes[src].rowsorted ? (float *)c->xch_stage.ptr + stage_off[src] + first
+                float *to = modes[src].rowsorted ? (float *)c->xch.stage.ptr + stage_off[src] + first
                                                  : (float *)d_final + dsh_tri_span(n, 0, modes[src].rb) + first;
-                e = rc_->Recv(to, cnt, ncclFloat32, src, c->comm, c->copy_stream);
+                e = rc_->Recv(to, cnt, ncclFloat32, src, c->xch.comm, c->copy_stream);
             }
         } else {
             if (!d_local) e = ncclInvalidArgument;
-            else e = rc_->Send((const float *)d_local + my_first, my_cnt, ncclFloat32, dst, c->comm, c->copy_stream);
+            else e = rc_->Send((const float *)d_local + my_first, my_cnt, ncclFloat32, dst, c->xch.comm, c->copy_stream);
         }
         if (e != ncclSuccess) {
             (void)rc_->GroupEnd();
@@ -747,9 +738,9 @@ int dsh_exchange_collect_async(dsh_ctx *c, uint64_t n, const uint64_t *rowsets, 
         // the rows that are now complete go to their places: ONE launch per round, on a stream of its own behind the
         // round's event, so that the next round's transfer does not wait for it
         if (rank == dst && stage_total && round_rows[q]) {
-            HIPCHK(c, hipEventRecord(c->ev_round[q], c->copy_stream));
-            HIPCHK(c, hipStreamWaitEvent(c->place_stream, c->ev_round[q], 0));
-            HIPCHK(c, launch_rows_place(c->place_stream, (const PlaceEnt *)((const uint8_t *)c->xch_tab.ptr + ent_off) + round_ent[q],
+            HIPCHK(c, hipEventRecord(c->xch.ev_round[q], c->copy_stream));
+            HIPCHK(c, hipStreamWaitEvent(c->place_stream, c->xch.ev_round[q], 0));
+            HIPCHK(c, launch_rows_place(c->place_stream, (const PlaceEnt *)((const uint8_t *)c->xch.tab.ptr + ent_off) + round_ent[q],
                                         round_ent[q + 1] - round_ent[q], round_rows[q], (float *)d_final, n));
             placed = true;
         }
@@ -763,9 +754,9 @@ int dsh_exchange_collect_async(dsh_ctx *c, uint64_t n, const uint64_t *rowsets, 
             if ((rc = place_own_rows(c, n, mine, d_local, d_final, c->copy_stream))) return rc;
         }
         if (placed) {
-            if (!c->ev_place_done) HIPCHK(c, hipEventCreateWithFlags(&c->ev_place_done, hipEventDisableTiming));
-            HIPCHK(c, hipEventRecord(c->ev_place_done, c->place_stream));
-            HIPCHK(c, hipStreamWaitEvent(c->copy_stream, c->ev_place_done, 0));
+            HIPCHK(c, c->xch.ev_place_done.ensure());
+            HIPCHK(c, hipEventRecord(c->xch.ev_place_done, c->place_stream));
+            HIPCHK(c, hipStreamWaitEvent(c->copy_stream, c->xch.ev_place_done, 0));
         }
     }
     return DSH_OK;
@@ -794,26 +785,16 @@ int dsh_exchange_place_device(dsh_ctx *c, const uint64_t *rowsets, int src, uint
     std::vector<uint64_t> rowoff;
     if ((rc = rowsorted_tables(c, n, m, order, rowoff, c->lay.sort_a))) return rc;
     const size_t ro_bytes = rowoff.size() * sizeof(uint64_t), bytes = ro_bytes + order.size() * sizeof(uint32_t);
-    HIPCHK(c, c->place_tab.ensure(bytes));
-    HIPCHK(c, hipMemcpyAsync(c->place_tab.ptr, rowoff.data(), ro_bytes, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync((uint8_t *)c->place_tab.ptr + ro_bytes, order.data(), order.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-    hipEvent_t e0 = nullptr, e1 = nullptr;  // (profiling: the device time of the placement itself, dsh_get_info "place_kernel_us")
-    if (c->profiling) {
-        HIPCHK(c, hipEventCreate(&e0));
-        HIPCHK(c, hipEventCreate(&e1));
-        HIPCHK(c, hipEventRecord(e0, c->stream));
-    }
+    HIPCHK(c, c->xch.place_tab.ensure(bytes));
+    HIPCHK(c, hipMemcpyAsync(c->xch.place_tab.ptr, rowoff.data(), ro_bytes, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync((uint8_t *)c->xch.place_tab.ptr + ro_bytes, order.data(), order.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    if (c->profiling) c->ev_used = 0;  // (no other timer of this call holds an event of the pool)
+    DeviceTimer t(c, c->stream);  // (profiling: the device time of the placement itself, dsh_get_info "place_kernel_us")
     HIPCHK(c, launch_row_place(c->stream, (const float *)d_src_local, (float *)d_final,
-                               (const uint32_t *)((const uint8_t *)c->place_tab.ptr + ro_bytes), (const uint64_t *)c->place_tab.ptr,
+                               (const uint32_t *)((const uint8_t *)c->xch.place_tab.ptr + ro_bytes), (const uint64_t *)c->xch.place_tab.ptr,
                                0, order.size(), n));
-    if (e1) HIPCHK(c, hipEventRecord(e1, c->stream));
+    t.stop(c->xch.place_ms);
     HIPCHK(c, hipStreamSynchronize(c->stream));  // (the pageable tables must outlive their copies)
-    if (e1) {
-        float ms = 0;
-        if (hipEventElapsedTime(&ms, e0, e1) == hipSuccess) c->place_ms = ms;
-        (void)hipEventDestroy(e0);
-        (void)hipEventDestroy(e1);
-    }
     return DSH_OK;
 }
 
@@ -871,7 +852,7 @@ int dsh_exchange_probe_parts_async(dsh_ctx *c, uint64_t n, const uint64_t *rowse
         else end = dsh_tri_span(n, mine.rb, mine.cut[i + 1]);
         part_end.push_back(std::max(end, part_end.empty() ? 0 : part_end.back()));
     }
-    if (c->comm && c->comm_world == 1) {
+    if (c->xch.comm && c->xch.world == 1) {
         // The reader is librccl itself: the rank's step as dsh_exchange_collect_async runs it for a source -- M = nparts
         // rounds, message q of the buffer behind the gate of the part that holds its last value, one grouped call per round
         // -- with the one peer a communicator of one rank has: ncclSend to itself paired with the ncclRecv into d_probe.
@@ -887,8 +868,8 @@ int dsh_exchange_probe_parts_async(dsh_ctx *c, uint64_t n, const uint64_t *rowse
             for (; next_wait <= i; ++next_wait)
                 if ((rc = wait_part(c, next_wait))) return rc;
             NCCLCHK(c, rc_->GroupStart());
-            ncclResult_t e = rc_->Send((const float *)d_local + first, cnt, ncclFloat32, 0, c->comm, c->copy_stream);
-            if (e == ncclSuccess) e = rc_->Recv((float *)d_probe + first, cnt, ncclFloat32, 0, c->comm, c->copy_stream);
+            ncclResult_t e = rc_->Send((const float *)d_local + first, cnt, ncclFloat32, 0, c->xch.comm, c->copy_stream);
+            if (e == ncclSuccess) e = rc_->Recv((float *)d_probe + first, cnt, ncclFloat32, 0, c->xch.comm, c->copy_stream);
             if (e != ncclSuccess) {
                 (void)rc_->GroupEnd();
                 return fail(c, DSH_EIO, "ncclSend/ncclRecv to this rank itself: %s", rc_->GetErrorString(e));
@@ -920,19 +901,19 @@ int dsh_diag_spin_start(dsh_ctx *c, uint32_t nblocks, uint32_t threads, uint32_t
         return DSH_EINVAL;
     int rc = bind(c);
     if (rc) return rc;
-    if (c->spin_running) return fail(c, DSH_ESTATE, "dsh_diag_spin_stop first");
+    if (c->xch.spin_running) return fail(c, DSH_ESTATE, "dsh_diag_spin_stop first");
     (void)device_can_wait_value(c);  // (also asks for the wall clock's rate)
     if (c->wall_clock_khz <= 0) return fail(c, DSH_ENODEV, "the device reports no wall clock rate");
-    if (!c->spin_flag) HIPCHK(c, hipHostMalloc((void **)&c->spin_flag, 64, hipHostMallocMapped));
-    if (!c->spin_stream) HIPCHK(c, hipStreamCreateWithFlags(&c->spin_stream, hipStreamNonBlocking));
-    *(volatile uint32_t *)c->spin_flag = 0;
+    HIPCHK(c, c->xch.spin_flag.ensure());
+    HIPCHK(c, c->spin_stream.create());
+    *(volatile uint32_t *)c->xch.spin_flag.ptr = 0;
     uint32_t *dflag = nullptr;
-    HIPCHK(c, hipHostGetDevicePointer((void **)&dflag, c->spin_flag, 0));
+    HIPCHK(c, hipHostGetDevicePointer((void **)&dflag, c->xch.spin_flag.ptr, 0));
     if (lds_bytes > 64 * 1024) HIPCHK(c, ensure_dynamic_lds((const void *)k_diag_spin, lds_bytes));
     hipLaunchKernelGGL(k_diag_spin, dim3(nblocks), dim3(threads), std::max<uint32_t>(lds_bytes, 16), c->spin_stream, dflag,
                        (unsigned long long)max_ms * (unsigned long long)c->wall_clock_khz, (uint32_t *)nullptr);
     HIPCHK(c, hipGetLastError());
-    c->spin_running = true;
+    c->xch.spin_running = true;
     return DSH_OK;
 }
 
@@ -941,9 +922,9 @@ int dsh_diag_spin_stop(dsh_ctx *c)
     if (!c) return DSH_EINVAL;
     int rc = bind(c);
     if (rc) return rc;
-    if (!c->spin_running) return DSH_OK;
-    *(volatile uint32_t *)c->spin_flag = 1;
-    c->spin_running = false;
+    if (!c->xch.spin_running) return DSH_OK;
+    *(volatile uint32_t *)c->xch.spin_flag.ptr = 1;
+    c->xch.spin_running = false;
     HIPCHK(c, hipStreamSynchronize(c->spin_stream));
     return DSH_OK;
 }
@@ -953,8 +934,8 @@ int dsh_allgather_device(dsh_ctx *c, const void *d_send, uint64_t bytes_per_rank
     if (!c || (bytes_per_rank && (!d_send || !d_recv))) return DSH_EINVAL;
     int rc = bind(c);
     if (rc) return rc;
-    if (!c->comm) return fail(c, DSH_ESTATE, "dsh_comm_init first");
-    if (bytes_per_rank) NCCLCHK(c, rccl()->AllGather(d_send, d_recv, bytes_per_rank, ncclUint8, c->comm, c->stream));
+    if (!c->xch.comm) return fail(c, DSH_ESTATE, "dsh_comm_init first");
+    if (bytes_per_rank) NCCLCHK(c, rccl()->AllGather(d_send, d_recv, bytes_per_rank, ncclUint8, c->xch.comm, c->stream));
     return sync_guarded(c, c->stream, "dsh_allgather_device");
 }
 
@@ -962,7 +943,7 @@ int dsh_dist_collect(dsh_ctx *c, int estim, int result_type, int k, const uint64
 {
     int rc = enter(c);
     if (rc) return rc;
-    const int world = c->comm ? c->comm_world : 1, rank = c->comm ? c->comm_rank : 0;
+    const int world = c->xch.comm ? c->xch.world : 1, rank = c->xch.comm ? c->xch.rank : 0;
     const uint64_t n = c->n, total = dsh_tri_span(n, 0, n);
     if (!bounds) {
         // the library's own partition: balanced row sets (range + top-up tile rows, dsh_balance_rowsets) through the
@@ -979,22 +960,22 @@ int dsh_dist_collect(dsh_ctx *c, int estim, int result_type, int k, const uint64
         void *d_loc = nullptr;
         if (rank == dst) {
             if (total && !out) return DSH_EINVAL;
-            HIPCHK(c, c->gather_full.ensure(std::max<uint64_t>(total, 1) * sizeof(float)));
+            HIPCHK(c, c->xch.gather_full.ensure(std::max<uint64_t>(total, 1) * sizeof(float)));
             uint64_t rb = 0, re = 0;
             std::vector<uint64_t> ex;
             rs.rank_rows((uint32_t)rank, rb, re, ex);
-            d_loc = (float *)c->gather_full.ptr + dsh_tri_span(n, 0, rb);  // computed in place
+            d_loc = (float *)c->xch.gather_full.ptr + dsh_tri_span(n, 0, rb);  // computed in place
         } else {
-            HIPCHK(c, c->gather_local.ensure(std::max<uint64_t>(local_floats, 1) * sizeof(float)));
-            d_loc = c->gather_local.ptr;
+            HIPCHK(c, c->xch.gather_local.ensure(std::max<uint64_t>(local_floats, 1) * sizeof(float)));
+            d_loc = c->xch.gather_local.ptr;
         }
         if ((rc = dsh_exchange_rows_device_async(c, estim, result_type, k, tab.data(), rank, kParts, dst, d_loc))) return rc;
-        if ((rc = dsh_exchange_collect_async(c, n, tab.data(), kParts, rank == dst ? nullptr : d_loc, rank == dst ? c->gather_full.ptr : nullptr, dst)))
+        if ((rc = dsh_exchange_collect_async(c, n, tab.data(), kParts, rank == dst ? nullptr : d_loc, rank == dst ? c->xch.gather_full.ptr : nullptr, dst)))
             return rc;
         if ((rc = sync_guarded(c, c->stream, "dsh_dist_collect (ctx stream)"))) return rc;
         if ((rc = sync_guarded(c, c->copy_stream, "dsh_dist_collect (copy stream)"))) return rc;
         if (rank == dst && total)
-            HIPCHK(c, hipMemcpyAsync(out, c->gather_full.ptr, total * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipMemcpyAsync(out, c->xch.gather_full.ptr, total * sizeof(float), hipMemcpyDeviceToHost, c->stream));
         return sync_guarded(c, c->stream, "dsh_dist_collect");
     }
     if ((rc = validate_bounds(c, n, bounds, world, dst))) return rc;  // before anything is sized by them
@@ -1002,16 +983,16 @@ int dsh_dist_collect(dsh_ctx *c, int estim, int result_type, int k, const uint64
     void *d_local = nullptr;
     if (rank == dst) {
         if (total && !out) return DSH_EINVAL;
-        HIPCHK(c, c->gather_full.ensure(std::max<uint64_t>(total, 1) * sizeof(float)));
-        d_local = (float *)c->gather_full.ptr + dsh_tri_span(n, 0, bounds[rank]);  // computed in place
+        HIPCHK(c, c->xch.gather_full.ensure(std::max<uint64_t>(total, 1) * sizeof(float)));
+        d_local = (float *)c->xch.gather_full.ptr + dsh_tri_span(n, 0, bounds[rank]);  // computed in place
     } else {
-        HIPCHK(c, c->gather_local.ensure(std::max<uint64_t>(mine, 1) * sizeof(float)));
-        d_local = c->gather_local.ptr;
+        HIPCHK(c, c->xch.gather_local.ensure(std::max<uint64_t>(mine, 1) * sizeof(float)));
+        d_local = c->xch.gather_local.ptr;
     }
     if (mine && (rc = dsh_dist_rows_device_async(c, estim, result_type, k, bounds[rank], bounds[rank + 1], d_local))) return rc;
-    if ((rc = collect_spans(c, n, bounds, d_local, rank == dst ? c->gather_full.ptr : nullptr, dst))) return rc;
+    if ((rc = collect_spans(c, n, bounds, d_local, rank == dst ? c->xch.gather_full.ptr : nullptr, dst))) return rc;
     if (rank == dst && total)
-        HIPCHK(c, hipMemcpyAsync(out, c->gather_full.ptr, total * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(out, c->xch.gather_full.ptr, total * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     return sync_guarded(c, c->stream, "dsh_dist_collect");
 }
 

@@ -16,20 +16,20 @@ int greedy_bands(dsh_ctx *c, int estim, int result_type, int k, float t, uint32_
 {
     const uint64_t n = c->n;
     const int descending = measure_descending(result_type) ? 1 : 0;
-    HIPCHK(c, c->gr_assign.ensure(n * sizeof(uint32_t)));
-    HIPCHK(c, c->gr_state.ensure(sizeof(uint64_t)));
+    HIPCHK(c, c->gr.assign.ensure(n * sizeof(uint32_t)));
+    HIPCHK(c, c->gr.state.ensure(sizeof(uint64_t)));
     if (!d_labels) {
-        HIPCHK(c, c->gr_labels.ensure(n * sizeof(uint32_t)));
-        d_labels = (uint32_t *)c->gr_labels.ptr;
+        HIPCHK(c, c->gr.labels.ensure(n * sizeof(uint32_t)));
+        d_labels = (uint32_t *)c->gr.labels.ptr;
     }
-    uint32_t *assign = (uint32_t *)c->gr_assign.ptr;
-    uint64_t *d_reps = (uint64_t *)c->gr_state.ptr;
+    uint32_t *assign = (uint32_t *)c->gr.assign.ptr;
+    uint64_t *d_reps = (uint64_t *)c->gr.state.ptr;
     HIPCHK(c, hipMemsetAsync(d_reps, 0, sizeof(uint64_t), c->stream));
     HIPCHK(c, launch_cc_init(c->stream, assign, n));  // assign[x] = x
     BandQuery bq;
     bq.estim = estim, bq.result_type = result_type, bq.k = k;
     bq.re = n;
-    bq.row_cap = c->greedy_band_rows;
+    bq.row_cap = c->gr.band_rows;
     const int rc = for_each_band(c, bq, [&](const ThrRows &g, const float *vals, uint64_t) -> int {
         hipError_t e = launch_greedy_diag(c->stream, vals, g, t, descending, assign);
         if (e == hipSuccess) e = launch_greedy_band(c->stream, vals, g, t, descending, assign);

@@ -21,16 +21,16 @@ int extend_bands(dsh_ctx *c, int estim, int result_type, int k, float t, int bes
     const uint64_t n = c->n;
     const int descending = measure_descending(result_type) ? 1 : 0;
     const uint64_t band_floats = std::max<uint64_t>(c->threshold_band_bytes / sizeof(float), 1);
-    HIPCHK(c, c->gr_assign.ensure(n * sizeof(uint32_t)));
-    HIPCHK(c, c->gr_state.ensure(sizeof(uint64_t)));
-    if (best_mode) HIPCHK(c, c->gr_best.ensure(std::max<uint64_t>(n - m, 1) * sizeof(uint64_t)));
+    HIPCHK(c, c->gr.assign.ensure(n * sizeof(uint32_t)));
+    HIPCHK(c, c->gr.state.ensure(sizeof(uint64_t)));
+    if (best_mode) HIPCHK(c, c->gr.best.ensure(std::max<uint64_t>(n - m, 1) * sizeof(uint64_t)));
     if (!d_labels) {
-        HIPCHK(c, c->gr_labels.ensure(n * sizeof(uint32_t)));
-        d_labels = (uint32_t *)c->gr_labels.ptr;
+        HIPCHK(c, c->gr.labels.ensure(n * sizeof(uint32_t)));
+        d_labels = (uint32_t *)c->gr.labels.ptr;
     }
-    uint32_t *assign = (uint32_t *)c->gr_assign.ptr;
-    uint64_t *best = best_mode ? (uint64_t *)c->gr_best.ptr : nullptr;
-    uint64_t *d_reps = (uint64_t *)c->gr_state.ptr;
+    uint32_t *assign = (uint32_t *)c->gr.assign.ptr;
+    uint64_t *best = best_mode ? (uint64_t *)c->gr.best.ptr : nullptr;
+    uint64_t *d_reps = (uint64_t *)c->gr.state.ptr;
     HIPCHK(c, hipMemsetAsync(d_reps, 0, sizeof(uint64_t), c->stream));
     HIPCHK(c, launch_cc_init(c->stream, assign, n));  // assign[x] = x
     if (m) HIPCHK(c, hipMemcpyAsync(assign, labels_in, m * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
@@ -51,7 +51,7 @@ int extend_bands(dsh_ctx *c, int estim, int result_type, int k, float t, int bes
     BandQuery bq;
     bq.estim = estim, bq.result_type = result_type, bq.k = k;
     bq.rb = m, bq.re = n;
-    bq.row_cap = c->greedy_band_rows;
+    bq.row_cap = c->gr.band_rows;
     const int rc = for_each_band(c, bq, [&](const ThrRows &g, const float *vals, uint64_t) -> int {
         hipError_t e = launch_greedy_diag(c->stream, vals, g, t, descending, assign);
         if (e == hipSuccess)

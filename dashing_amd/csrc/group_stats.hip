@@ -71,19 +71,19 @@ int gs_pairs(dsh_ctx *c, int estim, int result_type, int k, uint64_t p_in, const
     const int descending = measure_descending(result_type) ? 1 : 0;
     const uint64_t ng = s.ppre.size() - 1;
     const size_t pb = (ng + 1) * sizeof(uint64_t), ob = (ng + 1) * sizeof(uint32_t), mb = s.mem.size() * sizeof(uint32_t);
-    HIPCHK(c, c->gs_csr.ensure(pb + ob + mb));
-    char *base = (char *)c->gs_csr.ptr;
+    HIPCHK(c, c->gs.csr.ensure(pb + ob + mb));
+    char *base = (char *)c->gs.csr.ptr;
     HIPCHK(c, hipMemcpyAsync(base, s.ppre.data(), pb, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(base + pb, s.moff.data(), ob, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(base + pb + ob, s.mem.data(), mb, hipMemcpyHostToDevice, c->stream));
-    const uint64_t chunk = std::min<uint64_t>(c->pairs_chunk, p_in);
-    HIPCHK(c, c->pairs_lhs.ensure(chunk * sizeof(uint32_t)));
-    HIPCHK(c, c->pairs_rhs.ensure(chunk * sizeof(uint32_t)));
-    HIPCHK(c, c->pairs_out.ensure(chunk * sizeof(float)));
+    const uint64_t chunk = std::min<uint64_t>(c->pairs.chunk, p_in);
+    HIPCHK(c, c->pairs.lhs.ensure(chunk * sizeof(uint32_t)));
+    HIPCHK(c, c->pairs.rhs.ensure(chunk * sizeof(uint32_t)));
+    HIPCHK(c, c->pairs.out.ensure(chunk * sizeof(float)));
     int rc = pairs_ensure_cards(c, estim);
     if (rc) return rc;
-    uint32_t *lhs = (uint32_t *)c->pairs_lhs.ptr, *rhs = (uint32_t *)c->pairs_rhs.ptr;
-    float *vals = (float *)c->pairs_out.ptr;
+    uint32_t *lhs = (uint32_t *)c->pairs.lhs.ptr, *rhs = (uint32_t *)c->pairs.rhs.ptr;
+    float *vals = (float *)c->pairs.out.ptr;
     for (uint64_t x0 = 0; x0 < p_in; x0 += chunk) {
         const uint64_t cnt = std::min<uint64_t>(chunk, p_in - x0);
         HIPCHK(c, launch_gs_enum(c->stream, (const uint64_t *)base, (const uint32_t *)(base + pb), (const uint32_t *)(base + pb + ob), ng, x0,
@@ -116,34 +116,34 @@ int run_group_stats(dsh_ctx *c, int estim, int result_type, int k, const uint32_
     uint64_t p_in = 0;
     for (uint64_t l = 0; l < n; ++l) p_in += (uint64_t)size[l] * (size[l] ? size[l] - 1 : 0) / 2;
     const uint64_t tri = n * (n - 1) / 2;
-    const int route = c->stats_route >= 0 ? c->stats_route : (p_in <= tri / kGsPairsDivisor ? 1 : 0);  // 20 P_in <= n (n - 1) / 2
+    const int route = c->gs.route >= 0 ? c->gs.route : (p_in <= tri / kGsPairsDivisor ? 1 : 0);  // 20 P_in <= n (n - 1) / 2
     if (route == 1 && p_in && k < 1) return fail(c, DSH_EINVAL, "bad k %d", k);
-    c->stats_route_last = route;
+    c->gs.route_last = route;
     GsCsr csr;  // (uploaded from where it stands: it lives until the call's wait)
     if (route == 1 && p_in) gs_build_csr(labels, n, size, csr);
 
     // accumulators: sum[n] | cnt[n] | wkey[n], zero; groups: g_sum[n] | g_cnt[n] zero, g_slot[n] all ones
-    HIPCHK(c, c->gs_labels.ensure(n * sizeof(uint32_t)));
-    HIPCHK(c, c->gs_acc.ensure(n * 16));
-    HIPCHK(c, c->gs_grp.ensure(n * 16));
+    HIPCHK(c, c->gs.labels.ensure(n * sizeof(uint32_t)));
+    HIPCHK(c, c->gs.acc.ensure(n * 16));
+    HIPCHK(c, c->gs.grp.ensure(n * 16));
     GsAccum acc;
-    acc.sum = (uint64_t *)c->gs_acc.ptr;
+    acc.sum = (uint64_t *)c->gs.acc.ptr;
     acc.cnt = (uint32_t *)(acc.sum + n);
     acc.wkey = acc.cnt + n;
-    uint64_t *g_sum = (uint64_t *)c->gs_grp.ptr;
+    uint64_t *g_sum = (uint64_t *)c->gs.grp.ptr;
     uint32_t *g_cnt = (uint32_t *)(g_sum + n), *g_slot = g_cnt + n;
-    uint32_t *d_labels = (uint32_t *)c->gs_labels.ptr;
+    uint32_t *d_labels = (uint32_t *)c->gs.labels.ptr;
     GsOut o = {medoid_out, cnt_out, sum_out, worst_out};
     if (!device) {  // the host form's outputs pass through the library's own buffer: sum[n] | medoid[n] | cnt[n] | worst[n]
-        HIPCHK(c, c->gs_out.ensure(n * 20));
-        o.sum = sum_out ? (int64_t *)c->gs_out.ptr : nullptr;
-        o.medoid = medoid_out ? (uint32_t *)((int64_t *)c->gs_out.ptr + n) : nullptr;
-        o.cnt = cnt_out ? (uint32_t *)((int64_t *)c->gs_out.ptr + n) + n : nullptr;
-        o.worst = worst_out ? (float *)((int64_t *)c->gs_out.ptr + n) + 2 * n : nullptr;
+        HIPCHK(c, c->gs.out.ensure(n * 20));
+        o.sum = sum_out ? (int64_t *)c->gs.out.ptr : nullptr;
+        o.medoid = medoid_out ? (uint32_t *)((int64_t *)c->gs.out.ptr + n) : nullptr;
+        o.cnt = cnt_out ? (uint32_t *)((int64_t *)c->gs.out.ptr + n) + n : nullptr;
+        o.worst = worst_out ? (float *)((int64_t *)c->gs.out.ptr + n) + 2 * n : nullptr;
     }
     HIPCHK(c, hipMemcpyAsync(d_labels, labels, n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemsetAsync(c->gs_acc.ptr, 0, n * 16, c->stream));
-    HIPCHK(c, hipMemsetAsync(c->gs_grp.ptr, 0, n * 12, c->stream));
+    HIPCHK(c, hipMemsetAsync(c->gs.acc.ptr, 0, n * 16, c->stream));
+    HIPCHK(c, hipMemsetAsync(c->gs.grp.ptr, 0, n * 12, c->stream));
     HIPCHK(c, hipMemsetAsync(g_slot, 0xFF, n * sizeof(uint32_t), c->stream));
     if (route == 1 && p_in && (rc = pairs_err_begin(c))) return drain(c, rc);
     rc = route == 1 ? gs_pairs(c, estim, result_type, k, p_in, csr, acc) : gs_dense(c, estim, result_type, k, d_labels, acc);

@@ -53,30 +53,30 @@ int run_hist(dsh_ctx *c, const HistQuery &q)
     const int descending = measure_descending(q.result_type) ? 1 : 0;
     uint64_t *d_counts = q.d_counts;
     if (!d_counts) {
-        HIPCHK(c, c->hs_counts.ensure(ncnt * sizeof(uint64_t)));
-        d_counts = (uint64_t *)c->hs_counts.ptr;
+        HIPCHK(c, c->hs.counts.ensure(ncnt * sizeof(uint64_t)));
+        d_counts = (uint64_t *)c->hs.counts.ptr;
     }
-    if (c->hs_cus <= 0) {  // the residency bound of k_hist's grid (plan::hist_grid)
+    if (c->hs.cus <= 0) {  // the residency bound of k_hist's grid (plan::hist_grid)
         int cus = 0;
         HIPCHK(c, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device));
-        c->hs_cus = std::max(cus, 1);
+        c->hs.cus = std::max(cus, 1);
     }
-    HIPCHK(c, c->hs_edges.ensure(q.n_edges * sizeof(float)));
-    if (q.labels && c->n) HIPCHK(c, c->hs_labels.ensure(c->n * sizeof(uint32_t)));
+    HIPCHK(c, c->hs.edges.ensure(q.n_edges * sizeof(float)));
+    if (q.labels && c->n) HIPCHK(c, c->hs.labels.ensure(c->n * sizeof(uint32_t)));
     // from here on work is queued: a failure drains the stream
     if (hipMemsetAsync(d_counts, 0, ncnt * sizeof(uint64_t), c->stream) != hipSuccess) return drain(c, fail(c, DSH_EIO, "clearing the counts failed"));
     if (pairs) {
-        const float *d_edges = (const float *)c->hs_edges.ptr;
-        const uint32_t *d_labels = q.labels ? (const uint32_t *)c->hs_labels.ptr : nullptr;
+        const float *d_edges = (const float *)c->hs.edges.ptr;
+        const uint32_t *d_labels = q.labels ? (const uint32_t *)c->hs.labels.ptr : nullptr;
         // (pageable sources: the runtime has taken its copy of them when the call returns)
-        if (hipMemcpyAsync(c->hs_edges.ptr, q.edges, q.n_edges * sizeof(float), hipMemcpyHostToDevice, c->stream) != hipSuccess ||
-            (q.labels && hipMemcpyAsync(c->hs_labels.ptr, q.labels, c->n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream) != hipSuccess))
+        if (hipMemcpyAsync(c->hs.edges.ptr, q.edges, q.n_edges * sizeof(float), hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+            (q.labels && hipMemcpyAsync(c->hs.labels.ptr, q.labels, c->n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream) != hipSuccess))
             return drain(c, fail(c, DSH_EIO, "upload of the edges or labels failed"));
         BandQuery bq;
         bq.estim = q.estim, bq.result_type = q.result_type, bq.k = q.k, bq.rect = q.rect;
         bq.rb = q.rb, bq.re = q.re, bq.cb = q.cb, bq.ce = q.ce;
         rc = for_each_band(c, bq, [&](const ThrRows &g, const float *vals, uint64_t) -> int {
-            const hipError_t e = launch_hist(c->stream, vals, g, d_edges, q.n_edges, d_labels, descending, (uint32_t)c->hs_cus, d_counts);
+            const hipError_t e = launch_hist(c->stream, vals, g, d_edges, q.n_edges, d_labels, descending, (uint32_t)c->hs.cus, d_counts);
             return e == hipSuccess ? DSH_OK : fail(c, DSH_EIO, "k_hist: %s", hipGetErrorString(e));
         });
         if (rc) return drain(c, rc);

@@ -10,15 +10,6 @@ using namespace dsh;
 
 namespace {
 
-// device buffers of one call, freed when it leaves (DevBuf itself has no destructor: as a member of dsh_ctx it is
-// released in the order release_ctx chooses)
-struct Scratch : DevBuf {
-    Scratch() = default;
-    Scratch(const Scratch &) = delete;
-    Scratch &operator=(const Scratch &) = delete;
-    ~Scratch() { release(); }
-};
-
 // the selected neighbours of `rows` queries to the host; returns when they have arrived
 int copy_out(dsh_ctx *c, const DevBuf &didx, const DevBuf &dval, uint64_t rows, uint32_t nn, uint32_t *idx_out, float *val_out)
 {
@@ -34,7 +25,7 @@ int copy_out(dsh_ctx *c, const DevBuf &didx, const DevBuf &dval, uint64_t rows, 
 int knn_square(dsh_ctx *c, int estim, int result_type, int k, int descending, uint32_t nn, uint32_t *idx_out, float *val_out)
 {
     const uint64_t n = c->n;
-    Scratch sq, didx, dval;
+    DevBuf sq, didx, dval;  // (the call's own: freed when it leaves)
     if (sq.ensure(n * n * sizeof(float)) != hipSuccess || didx.ensure(n * nn * sizeof(uint32_t)) != hipSuccess ||
         dval.ensure(n * nn * sizeof(float)) != hipSuccess)
         return fail(c, DSH_ENOMEM, "device allocation failed");
@@ -67,7 +58,7 @@ int knn_bands(dsh_ctx *c, int estim, int result_type, int k, int descending, uin
         hipStream_t st;
         ~Drain() { (void)hipStreamSynchronize(st); }
     };
-    Scratch V, Vt, didx, dval;
+    DevBuf V, Vt, didx, dval;  // (the call's own: freed when it leaves)
     const Drain drain{c->stream};  // (declared last: it runs first)
     if (V.ensure(band * npad * sizeof(float)) != hipSuccess || Vt.ensure(npad * band * sizeof(float)) != hipSuccess ||
         didx.ensure(n * nn * sizeof(uint32_t)) != hipSuccess || dval.ensure(n * nn * sizeof(float)) != hipSuccess)
@@ -104,7 +95,7 @@ int knn_rect(dsh_ctx *c, int estim, int result_type, int k, int descending, uint
     DevBuf &rect = c->outbuf;
     const uint64_t qblock = std::max<uint64_t>(1, std::min<uint64_t>(nq, ((uint64_t)256 << 20) / std::max<uint64_t>(nr, 1)));
     HIPCHK(c, rect.ensure(std::max<uint64_t>(qblock * nr, 1) * sizeof(float)));
-    Scratch didx, dval;
+    DevBuf didx, dval;  // (the call's own: freed when it leaves)
     if (didx.ensure(nq * nn * sizeof(uint32_t)) != hipSuccess || dval.ensure(nq * nn * sizeof(float)) != hipSuccess)
         return fail(c, DSH_ENOMEM, "device allocation failed");
     for (uint64_t q0 = qb; q0 < qe; q0 += qblock) {

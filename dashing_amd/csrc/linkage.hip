@@ -66,13 +66,13 @@ int lk_walk(dsh_ctx *c, uint64_t n, const LkSource &s, const PerBand &per_band)
 // n singletons, or whatever labels the device holds: out to the caller, counted; the call's last wait
 int lk_finish(dsh_ctx *c, uint64_t n, bool pairs_route, uint32_t *d_labels, uint32_t *h_labels, uint64_t *n_clusters)
 {
-    LkState *st = (LkState *)c->lk_state.ptr;
+    LkState *st = (LkState *)c->lk.state.ptr;
     uint32_t *out = d_labels;
     if (!out) {
-        HIPCHK(c, c->cc_labels.ensure(std::max<uint64_t>(n, 1) * sizeof(uint32_t)));
-        out = (uint32_t *)c->cc_labels.ptr;
+        HIPCHK(c, c->cc.labels.ensure(std::max<uint64_t>(n, 1) * sizeof(uint32_t)));
+        out = (uint32_t *)c->cc.labels.ptr;
     }
-    HIPCHK(c, launch_greedy_labels(c->stream, (const uint32_t *)c->lk_labels.ptr, n, out, (uint64_t *)&st->n_roots));
+    HIPCHK(c, launch_greedy_labels(c->stream, (const uint32_t *)c->lk.labels.ptr, n, out, (uint64_t *)&st->n_roots));
     LkState h = {0, 0, 0};
     HIPCHK(c, hipMemcpyAsync(&h, st, sizeof h, hipMemcpyDeviceToHost, c->stream));
     if (h_labels) HIPCHK(c, hipMemcpyAsync(h_labels, out, n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
@@ -89,10 +89,10 @@ int lk_finish(dsh_ctx *c, uint64_t n, bool pairs_route, uint32_t *d_labels, uint
 
 int lk_begin(dsh_ctx *c, uint64_t n)
 {
-    HIPCHK(c, c->lk_labels.ensure(std::max<uint64_t>(n, 1) * sizeof(uint32_t)));
-    HIPCHK(c, c->lk_state.ensure(sizeof(LkState)));
-    HIPCHK(c, hipMemsetAsync(c->lk_state.ptr, 0, sizeof(LkState), c->stream));
-    HIPCHK(c, launch_cc_init(c->stream, (uint32_t *)c->lk_labels.ptr, n));
+    HIPCHK(c, c->lk.labels.ensure(std::max<uint64_t>(n, 1) * sizeof(uint32_t)));
+    HIPCHK(c, c->lk.state.ensure(sizeof(LkState)));
+    HIPCHK(c, hipMemsetAsync(c->lk.state.ptr, 0, sizeof(LkState), c->stream));
+    HIPCHK(c, launch_cc_init(c->stream, (uint32_t *)c->lk.labels.ptr, n));
     return DSH_OK;
 }
 
@@ -115,11 +115,11 @@ int run_linkage(dsh_ctx *c, uint64_t n, const LkSource &src, int descending, flo
     }
     // 1. the components of the graph of passing pairs
     std::vector<uint32_t> lab(n, 0);
-    if (c->linkage_partition) {
+    if (c->lk.partition) {
         const float loose = linkage == kLkAverage ? lk_loose_threshold(t, descending) : t;
         if ((rc = cc_begin(c, n))) return drain(c, rc);
         rc = lk_walk(c, n, src, [&](const ThrRows &g, const float *vals, uint64_t) -> int {
-            const hipError_t e = launch_cc_band(c->stream, vals, g, loose, descending, (uint32_t *)c->cc_parent.ptr, cc_cap(n), cc_err(c));
+            const hipError_t e = launch_cc_band(c->stream, vals, g, loose, descending, (uint32_t *)c->cc.parent.ptr, cc_cap(n), cc_err(c));
             return e == hipSuccess ? DSH_OK : fail(c, DSH_EIO, "k_cc_band: %s", hipGetErrorString(e));
         });
         if (rc || (rc = cc_finish(c, n, nullptr, lab.data(), nullptr))) return drain(c, rc);
@@ -160,10 +160,10 @@ int run_linkage(dsh_ctx *c, uint64_t n, const LkSource &src, int descending, flo
             if (linkage == kLkAverage && m > kLkAvgMaxMembers)
                 return fail(c, DSH_ENOMEM, "a component of m = %llu members: average linkage takes at most %u (64-bit sums), and its matrix would need %llu bytes",
                             (unsigned long long)m, kLkAvgMaxMembers, (unsigned long long)need);
-            if (m > (1ull << 30) || need > c->linkage_budget)  // (m <= 2^30: need did not wrap)
+            if (m > (1ull << 30) || need > c->lk.budget)  // (m <= 2^30: need did not wrap)
                 return fail(c, DSH_ENOMEM, "a component of m = %llu members needs a matrix of %llu bytes, linkage_budget_bytes is %llu",
-                            (unsigned long long)m, (unsigned long long)need, (unsigned long long)c->linkage_budget);
-            if (cells && (cells + m * m) * cellsz > c->linkage_budget) {
+                            (unsigned long long)m, (unsigned long long)need, (unsigned long long)c->lk.budget);
+            if (cells && (cells + m * m) * cellsz > c->lk.budget) {
                 batch.push_back((uint32_t)ci);
                 cells = 0;
             }
@@ -176,8 +176,8 @@ int run_linkage(dsh_ctx *c, uint64_t n, const LkSource &src, int descending, flo
         batch.push_back((uint32_t)ncomp);
     }
     const uint64_t p_in = ppre[ncomp], tri_pairs = n * (n - 1) / 2;
-    const int route = src.tri ? 0 : (c->linkage_route >= 0 ? c->linkage_route : (p_in <= tri_pairs / kLkPairsDivisor ? 1 : 0));
-    if (!src.tri) c->linkage_route_last = route;
+    const int route = src.tri ? 0 : (c->lk.route >= 0 ? c->lk.route : (p_in <= tri_pairs / kLkPairsDivisor ? 1 : 0));
+    if (!src.tri) c->lk.route_last = route;
     const bool pairs = route == 1 && p_in;
     if (pairs && src.k < 1) return fail(c, DSH_EINVAL, "bad k %d", src.k);
     if ((rc = lk_begin(c, n))) return drain(c, rc);
@@ -187,8 +187,8 @@ int run_linkage(dsh_ctx *c, uint64_t n, const LkSource &src, int descending, flo
     }
     // the tables on the device: ppre | coff | comp | rank | moff | mem (8-byte entries first)
     const size_t b_ppre = (ncomp + 1) * 8, b_coff = ncomp * 8, b_n = n * 4, b_moff = (ncomp + 1) * 4, b_mem = mem.size() * 4;
-    HIPCHK(c, c->lk_tab.ensure(b_ppre + b_coff + 2 * b_n + b_moff + b_mem));
-    char *tab = (char *)c->lk_tab.ptr;
+    HIPCHK(c, c->lk.tab.ensure(b_ppre + b_coff + 2 * b_n + b_moff + b_mem));
+    char *tab = (char *)c->lk.tab.ptr;
     const uint64_t *d_ppre = (const uint64_t *)tab;
     LkComps C;
     C.coff = (const uint64_t *)(tab + b_ppre);
@@ -204,7 +204,7 @@ int run_linkage(dsh_ctx *c, uint64_t n, const LkSource &src, int descending, flo
         hipMemcpyAsync((void *)C.mem, mem.data(), b_mem, hipMemcpyHostToDevice, c->stream) != hipSuccess)
         return drain(c, fail(c, DSH_EIO, "upload of the components' tables failed"));
     {
-        const hipError_t e1 = c->lk_cells.ensure(max_cells * cellsz), e2 = c->lk_nodes.ensure(max_members * (cellsz + 16));
+        const hipError_t e1 = c->lk.cells.ensure(max_cells * cellsz), e2 = c->lk.nodes.ensure(max_members * (cellsz + 16));
         if (e1 != hipSuccess || e2 != hipSuccess) {
             (void)hipGetLastError();
             return drain(c, fail(c, DSH_ENOMEM, "no device memory for the matrices of a batch (%llu bytes)", (unsigned long long)(max_cells * cellsz)));
@@ -216,31 +216,31 @@ int run_linkage(dsh_ctx *c, uint64_t n, const LkSource &src, int descending, flo
         pq.estim = src.estim, pq.k = src.k, pq.n_types = 1;
         for (uint32_t x = 0; x < 9; ++x) pq.types.t[x] = 0;
         pq.types.t[0] = src.result_type;
-        chunk = std::min<uint64_t>(c->pairs_chunk, p_in);
-        HIPCHK(c, c->pairs_lhs.ensure(chunk * sizeof(uint32_t)));
-        HIPCHK(c, c->pairs_rhs.ensure(chunk * sizeof(uint32_t)));
-        HIPCHK(c, c->pairs_out.ensure(chunk * sizeof(float)));
+        chunk = std::min<uint64_t>(c->pairs.chunk, p_in);
+        HIPCHK(c, c->pairs.lhs.ensure(chunk * sizeof(uint32_t)));
+        HIPCHK(c, c->pairs.rhs.ensure(chunk * sizeof(uint32_t)));
+        HIPCHK(c, c->pairs.out.ensure(chunk * sizeof(float)));
         if ((rc = pairs_ensure_cards(c, src.estim)) || (rc = pairs_err_begin(c))) return drain(c, rc);
     }
     // 3. batch by batch
     const uint32_t cap = (uint32_t)std::min<uint64_t>(max_m + 1, 0xFFFFFFFFull);
-    uint32_t *err = &((LkState *)c->lk_state.ptr)->err;
+    uint32_t *err = &((LkState *)c->lk.state.ptr)->err;
     for (size_t q = 0; q + 1 < batch.size(); ++q) {
         LkBatch B;
         B.c0 = batch[q], B.c1 = batch[q + 1];
-        B.cells = c->lk_cells.ptr;
-        B.ncells = c->lk_cells.cap / cellsz;
-        B.state = c->lk_nodes.ptr;
+        B.cells = c->lk.cells.ptr;
+        B.ncells = c->lk.cells.cap / cellsz;
+        B.state = c->lk.nodes.ptr;
         B.mbase = moff[B.c0];
         B.members = moff[B.c1] - moff[B.c0];
         uint32_t lds_members = 0;
         for (uint32_t ci = B.c0; ci < B.c1; ++ci) {
             const uint32_t m = moff[ci + 1] - moff[ci];
-            if (m <= c->linkage_lds_max) lds_members = std::max(lds_members, m);
+            if (m <= c->lk.lds_max) lds_members = std::max(lds_members, m);
         }
         if (pairs) {
-            uint32_t *lhs = (uint32_t *)c->pairs_lhs.ptr, *rhs = (uint32_t *)c->pairs_rhs.ptr;
-            float *vals = (float *)c->pairs_out.ptr;
+            uint32_t *lhs = (uint32_t *)c->pairs.lhs.ptr, *rhs = (uint32_t *)c->pairs.rhs.ptr;
+            float *vals = (float *)c->pairs.out.ptr;
             for (uint64_t x0 = ppre[B.c0]; x0 < ppre[B.c1]; x0 += chunk) {
                 const uint64_t cnt = std::min<uint64_t>(chunk, ppre[B.c1] - x0);
                 if (launch_gs_enum(c->stream, d_ppre, C.moff, C.mem, ncomp, x0, cnt, lhs, rhs) != hipSuccess)
@@ -256,8 +256,8 @@ int run_linkage(dsh_ctx *c, uint64_t n, const LkSource &src, int descending, flo
             });
             if (rc) return drain(c, rc);
         }
-        const hipError_t e = launch_linkage(c->stream, linkage, C, B, t, descending, c->linkage_lds_max, lds_members, cap,
-                                            (uint32_t *)c->lk_labels.ptr, err);
+        const hipError_t e = launch_linkage(c->stream, linkage, C, B, t, descending, c->lk.lds_max, lds_members, cap,
+                                            (uint32_t *)c->lk.labels.ptr, err);
         if (e != hipSuccess) return drain(c, fail(c, DSH_EIO, "k_linkage: %s", hipGetErrorString(e)));
     }
     // 4. out

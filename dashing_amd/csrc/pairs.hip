@@ -19,24 +19,24 @@ static size_t hist_bytes(const dsh_ctx *c, uint64_t cnt) { return cnt * 64 * (c-
 // sketch with an out-of-range register is not reported here (it may never be named) -- it counts as empty.
 int pairs_ensure_cards(dsh_ctx *c, int estim)
 {
-    if (c->pairs_card_estim == estim) return DSH_OK;
-    c->pairs_card_estim = -1;
-    HIPCHK(c, c->pairs_card.ensure(std::max<uint64_t>(c->n, 1) * sizeof(double)));
-    const uint64_t chunk = c->pairs_chunk;
-    HIPCHK(c, c->pairs_hist.ensure(hist_bytes(c, std::min<uint64_t>(chunk, std::max<uint64_t>(c->n, 1)))));
+    if (c->pairs.card_estim == estim) return DSH_OK;
+    c->pairs.card_estim = -1;
+    HIPCHK(c, c->pairs.card.ensure(std::max<uint64_t>(c->n, 1) * sizeof(double)));
+    const uint64_t chunk = c->pairs.chunk;
+    HIPCHK(c, c->pairs.hist.ensure(hist_bytes(c, std::min<uint64_t>(chunk, std::max<uint64_t>(c->n, 1)))));
     for (uint64_t s0 = 0; s0 < c->n; s0 += chunk) {
         const uint64_t cnt = std::min<uint64_t>(chunk, c->n - s0);
-        HIPCHK(c, launch_pairs_hist(c->stream, c->regs, c->n, c->p, nullptr, nullptr, s0, 0, cnt, c->pairs_hist.ptr, nullptr));
-        HIPCHK(c, launch_pairs_card(c->stream, c->pairs_hist.ptr, s0, cnt, c->p, estim, (double *)c->pairs_card.ptr));
+        HIPCHK(c, launch_pairs_hist(c->stream, c->regs, c->n, c->p, nullptr, nullptr, s0, 0, cnt, c->pairs.hist.ptr, nullptr));
+        HIPCHK(c, launch_pairs_card(c->stream, c->pairs.hist.ptr, s0, cnt, c->p, estim, (double *)c->pairs.card.ptr));
     }
-    c->pairs_card_estim = estim;
+    c->pairs.card_estim = estim;
     return DSH_OK;
 }
 
 int pairs_err_begin(dsh_ctx *c)
 {
-    HIPCHK(c, c->pairs_err.ensure(2 * sizeof(unsigned long long)));
-    HIPCHK(c, hipMemsetAsync(c->pairs_err.ptr, 0xFF, 2 * sizeof(unsigned long long), c->stream));
+    HIPCHK(c, c->pairs.err.ensure(2 * sizeof(unsigned long long)));
+    HIPCHK(c, hipMemsetAsync(c->pairs.err.ptr, 0xFF, 2 * sizeof(unsigned long long), c->stream));
     return DSH_OK;
 }
 
@@ -45,11 +45,11 @@ int pairs_run_chunk(dsh_ctx *c, const PairsQuery &q, const uint32_t *d_lhs, cons
                     float *d_out, uint64_t out_stride)
 {
     const double ksinv = (double)(float)(1. / (double)q.k);  // the float 1/k of dist_loop (src/sketch_and_cmp.h:797)
-    HIPCHK(c, c->pairs_hist.ensure(hist_bytes(c, cnt)));
-    HIPCHK(c, launch_pairs_hist(c->stream, c->regs, c->n, c->p, d_lhs, d_rhs, 0, xbase, cnt, c->pairs_hist.ptr,
-                                (unsigned long long *)c->pairs_err.ptr));
-    HIPCHK(c, launch_pairs_finish(c->stream, c->pairs_hist.ptr, d_lhs, d_rhs, c->n, cnt, c->p, q.estim,
-                                  (const double *)c->pairs_card.ptr, q.types, q.n_types, ksinv, d_out, out_stride));
+    HIPCHK(c, c->pairs.hist.ensure(hist_bytes(c, cnt)));
+    HIPCHK(c, launch_pairs_hist(c->stream, c->regs, c->n, c->p, d_lhs, d_rhs, 0, xbase, cnt, c->pairs.hist.ptr,
+                                (unsigned long long *)c->pairs.err.ptr));
+    HIPCHK(c, launch_pairs_finish(c->stream, c->pairs.hist.ptr, d_lhs, d_rhs, c->n, cnt, c->p, q.estim,
+                                  (const double *)c->pairs.card.ptr, q.types, q.n_types, ksinv, d_out, out_stride));
     return DSH_OK;
 }
 
@@ -57,7 +57,7 @@ int pairs_run_chunk(dsh_ctx *c, const PairsQuery &q, const uint32_t *d_lhs, cons
 int pairs_err_end(dsh_ctx *c)
 {
     unsigned long long e[2] = {~0ull, ~0ull};
-    HIPCHK(c, hipMemcpyAsync(e, c->pairs_err.ptr, sizeof e, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(e, c->pairs.err.ptr, sizeof e, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (e[0] != ~0ull)
         return fail(c, DSH_EINVAL, "pair %llu names a slot outside [0, %llu)", e[0], (unsigned long long)c->n);
@@ -95,33 +95,32 @@ int run_host(dsh_ctx *c, const PairsQuery &q, uint64_t n_pairs, const Fill &fill
     if (!n_pairs || !q.n_types) return DSH_OK;
     int rc = pairs_ensure_cards(c, q.estim);
     if (rc || (rc = pairs_err_begin(c))) return rc;
-    const uint64_t chunk = std::min<uint64_t>(c->pairs_chunk, n_pairs);
-    HIPCHK(c, c->pairs_lhs.ensure(chunk * sizeof(uint32_t)));
-    HIPCHK(c, c->pairs_rhs.ensure(chunk * sizeof(uint32_t)));
-    HIPCHK(c, c->pairs_out.ensure(chunk * q.n_types * sizeof(float)));
+    const uint64_t chunk = std::min<uint64_t>(c->pairs.chunk, n_pairs);
+    HIPCHK(c, c->pairs.lhs.ensure(chunk * sizeof(uint32_t)));
+    HIPCHK(c, c->pairs.rhs.ensure(chunk * sizeof(uint32_t)));
+    HIPCHK(c, c->pairs.out.ensure(chunk * q.n_types * sizeof(float)));
     // the list travels through one page-locked slot (lhs then rhs of a chunk): it is rewritten once its upload has run
     // (the copy of a chunk's values into the caller's pageable `out` holds the host until the chunk is done anyway)
-    HIPCHK(c, c->pin_pairs.ensure(2 * chunk * sizeof(uint32_t)));
-    if (!c->ev_pairs) HIPCHK(c, hipEventCreateWithFlags(&c->ev_pairs, hipEventDisableTiming));
-    uint32_t *hl = (uint32_t *)c->pin_pairs.ptr, *hr = hl + chunk;
+    HIPCHK(c, c->pairs.list.room(2 * chunk * sizeof(uint32_t)));
+    uint32_t *hl = (uint32_t *)c->pairs.list.ptr(), *hr = hl + chunk;
     for (uint64_t x0 = 0; x0 < n_pairs && rc == DSH_OK; x0 += chunk) {
         const uint64_t cnt = std::min<uint64_t>(chunk, n_pairs - x0);
-        if (x0 && hipEventSynchronize(c->ev_pairs) != hipSuccess) {
+        if (c->pairs.list.wait() != hipSuccess) {  // (from the second chunk on: room() has waited for an earlier call's)
             rc = fail(c, DSH_EIO, "hipEventSynchronize failed");
             break;
         }
         fill(x0, cnt, hl, hr);
-        if (hipMemcpyAsync(c->pairs_lhs.ptr, hl, cnt * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream) != hipSuccess ||
-            hipMemcpyAsync(c->pairs_rhs.ptr, hr, cnt * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream) != hipSuccess ||
-            hipEventRecord(c->ev_pairs, c->stream) != hipSuccess) {
+        if (hipMemcpyAsync(c->pairs.lhs.ptr, hl, cnt * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+            hipMemcpyAsync(c->pairs.rhs.ptr, hr, cnt * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+            c->pairs.list.sent(c->stream) != hipSuccess) {
             rc = fail(c, DSH_EIO, "upload of the pair list failed");
             break;
         }
-        if ((rc = pairs_run_chunk(c, q, (const uint32_t *)c->pairs_lhs.ptr, (const uint32_t *)c->pairs_rhs.ptr, x0, cnt,
-                            (float *)c->pairs_out.ptr, chunk)))
+        if ((rc = pairs_run_chunk(c, q, (const uint32_t *)c->pairs.lhs.ptr, (const uint32_t *)c->pairs.rhs.ptr, x0, cnt,
+                            (float *)c->pairs.out.ptr, chunk)))
             break;
         for (uint32_t t = 0; t < q.n_types; ++t)
-            if (hipMemcpyAsync(out + (uint64_t)t * n_pairs + x0, (const float *)c->pairs_out.ptr + (uint64_t)t * chunk,
+            if (hipMemcpyAsync(out + (uint64_t)t * n_pairs + x0, (const float *)c->pairs.out.ptr + (uint64_t)t * chunk,
                                cnt * sizeof(float), hipMemcpyDeviceToHost, c->stream) != hipSuccess) {
                 rc = fail(c, DSH_EIO, "copy of the values failed");
                 break;
@@ -165,7 +164,7 @@ int dsh_dist_pairs_device(dsh_ctx *c, int estim, const int *result_types, uint32
     if (!n_pairs || !n_types) return DSH_OK;
     if (!d_lhs || !d_rhs || !d_out) return DSH_EINVAL;
     if ((rc = pairs_ensure_cards(c, q.estim)) || (rc = pairs_err_begin(c))) return rc;
-    const uint64_t chunk = c->pairs_chunk;
+    const uint64_t chunk = c->pairs.chunk;
     for (uint64_t x0 = 0; x0 < n_pairs; x0 += chunk) {
         const uint64_t cnt = std::min<uint64_t>(chunk, n_pairs - x0);
         if ((rc = pairs_run_chunk(c, q, (const uint32_t *)d_lhs + x0, (const uint32_t *)d_rhs + x0, x0, cnt, (float *)d_out + x0, n_pairs))) {

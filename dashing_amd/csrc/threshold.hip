@@ -66,12 +66,12 @@ int run_threshold(dsh_ctx *c, const ThrQuery &q, uint64_t *n_hits)
     const int descending = measure_descending(q.result_type) ? 1 : 0;
     const uint64_t rows = q.re > q.rb ? q.re - q.rb : 0;
     const bool emit = q.host ? (q.h_col && q.h_val) : (q.d_col && q.d_val);
-    HIPCHK(c, c->thr_total.ensure(sizeof(uint64_t)));
-    uint64_t *d_total = (uint64_t *)c->thr_total.ptr;
+    HIPCHK(c, c->thr.total.ensure(sizeof(uint64_t)));
+    uint64_t *d_total = (uint64_t *)c->thr.total.ptr;
     uint64_t *d_row_ptr = q.d_row_ptr;
     if (q.host) {
-        HIPCHK(c, c->thr_rowptr.ensure((rows + 1) * sizeof(uint64_t)));
-        d_row_ptr = (uint64_t *)c->thr_rowptr.ptr;
+        HIPCHK(c, c->thr.rowptr.ensure((rows + 1) * sizeof(uint64_t)));
+        d_row_ptr = (uint64_t *)c->thr.rowptr.ptr;
     }
     HIPCHK(c, hipMemsetAsync(d_total, 0, sizeof(uint64_t), c->stream));
     // from here on work is queued: every failure goes through the one exit below, which drains the stream and frees hh
@@ -83,16 +83,16 @@ int run_threshold(dsh_ctx *c, const ThrQuery &q, uint64_t *n_hits)
     bq.empty_bands = true;  // a row without values still has its entry of row_ptr
     int rc = for_each_band(c, bq, [&](const ThrRows &g, const float *vals, uint64_t) -> int {
         const uint64_t m = g.rows * g.nchunks;
-        HIPCHK(c, c->thr_cnt.ensure(m * sizeof(uint32_t)));
-        HIPCHK(c, c->thr_off.ensure((m + 1) * sizeof(uint64_t)));
-        hipError_t e = launch_thr_count(c->stream, vals, g, q.t, descending, (uint32_t *)c->thr_cnt.ptr);
+        HIPCHK(c, c->thr.cnt.ensure(m * sizeof(uint32_t)));
+        HIPCHK(c, c->thr.off.ensure((m + 1) * sizeof(uint64_t)));
+        hipError_t e = launch_thr_count(c->stream, vals, g, q.t, descending, (uint32_t *)c->thr.cnt.ptr);
         if (e == hipSuccess)
-            e = launch_thr_scan(c->stream, (const uint32_t *)c->thr_cnt.ptr, m, g.nchunks, (uint64_t *)c->thr_off.ptr,
+            e = launch_thr_scan(c->stream, (const uint32_t *)c->thr.cnt.ptr, m, g.nchunks, (uint64_t *)c->thr.off.ptr,
                                 d_row_ptr + (g.row0 - q.rb), d_total);
         if (e != hipSuccess) return fail(c, DSH_EIO, "k_thr_count/k_thr_scan: %s", hipGetErrorString(e));
         if (!emit) return DSH_OK;
         if (!q.host) {
-            e = launch_thr_emit(c->stream, vals, g, q.t, descending, (const uint64_t *)c->thr_off.ptr, 0, q.cap, q.d_col, q.d_val);
+            e = launch_thr_emit(c->stream, vals, g, q.t, descending, (const uint64_t *)c->thr.off.ptr, 0, q.cap, q.d_col, q.d_val);
             return e == hipSuccess ? DSH_OK : fail(c, DSH_EIO, "k_thr_emit: %s", hipGetErrorString(e));
         }
         // the band's total decides how much room its hits need: the one host wait per band
@@ -102,15 +102,15 @@ int run_threshold(dsh_ctx *c, const ThrQuery &q, uint64_t *n_hits)
             return fail(c, DSH_EIO, "copy of the band total failed");
         const uint64_t bh = tot - done;
         if (bh) {
-            HIPCHK(c, c->thr_col.ensure(bh * sizeof(uint32_t)));
-            HIPCHK(c, c->thr_val.ensure(bh * sizeof(float)));
+            HIPCHK(c, c->thr.col.ensure(bh * sizeof(uint32_t)));
+            HIPCHK(c, c->thr.val.ensure(bh * sizeof(float)));
             if (!hh.grow(tot, done))  // (the stream is idle: earlier bands' copies have arrived)
                 return fail(c, DSH_ENOMEM, "host allocation of %llu hits failed", (unsigned long long)tot);
-            e = launch_thr_emit(c->stream, vals, g, q.t, descending, (const uint64_t *)c->thr_off.ptr, done, bh,
-                                (uint32_t *)c->thr_col.ptr, (float *)c->thr_val.ptr);
+            e = launch_thr_emit(c->stream, vals, g, q.t, descending, (const uint64_t *)c->thr.off.ptr, done, bh,
+                                (uint32_t *)c->thr.col.ptr, (float *)c->thr.val.ptr);
             if (e != hipSuccess) return fail(c, DSH_EIO, "k_thr_emit: %s", hipGetErrorString(e));
-            if (hipMemcpyAsync(hh.col + done, c->thr_col.ptr, bh * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
-                hipMemcpyAsync(hh.val + done, c->thr_val.ptr, bh * sizeof(float), hipMemcpyDeviceToHost, c->stream) != hipSuccess)
+            if (hipMemcpyAsync(hh.col + done, c->thr.col.ptr, bh * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+                hipMemcpyAsync(hh.val + done, c->thr.val.ptr, bh * sizeof(float), hipMemcpyDeviceToHost, c->stream) != hipSuccess)
                 return fail(c, DSH_EIO, "copy of the hits failed");
         }
         done = tot;

@@ -72,7 +72,7 @@ int dsh_abi_version(void);
 const char *dsh_backend_name(void);       /* "hip:gfx950" */
 int dsh_device_count(void);               /* number of visible HIP devices (0 if none) */
 int dsh_create(int device, dsh_ctx **out);
-void dsh_destroy(dsh_ctx *ctx);
+void dsh_destroy(dsh_ctx *ctx);            /* waits for everything the context has enqueued before it releases anything */
 const char *dsh_last_error(const dsh_ctx *ctx);
 /* Load the kernels' code objects NOW (the HIP runtime otherwise loads each when one of its kernels is first launched:
  * 10-40 ms in the middle of the first sketch batch / the first dist call).  No context needed and safe to call from any
