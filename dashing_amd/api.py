@@ -6,6 +6,7 @@ infrastructure only -- nothing in this package imports it.)
 """
 import collections
 import ctypes as C
+import math
 import os
 
 import numpy as np
@@ -45,6 +46,7 @@ SYMBOLS = [
     "dsh_group_stats", "dsh_group_stats_device",
     "dsh_dist_histogram", "dsh_dist_histogram_device", "dsh_dist_rect_histogram",
     "dsh_linkage_threshold", "dsh_linkage_threshold_device", "dsh_linkage_tri",
+    "dsh_mst", "dsh_mst_tri", "dsh_mst_linkage",
     "dsh_fold", "dsh_fold_device", "dsh_upload_sketches_folded", "dsh_upload_sketches_folded_device", "dsh_union_groups", "dsh_union_groups_device", "dsh_shard_plan", "dsh_dist_shard_device", "dsh_unpermute_device", "dsh_unpermute_staged_device", "dsh_unpermute_blocks_device", "dsh_tri_span", "dsh_tri_index", "dsh_partition_rows", "dsh_balance_rows", "dsh_balance_rowsets", "dsh_rowsets_from_bounds", "dsh_rowsets_rank", "dsh_alloc_host", "dsh_free_host",
     "dsh_set_profiling", "dsh_last_kernel_ms", "dsh_last_part_info", "dsh_finalize_phase_cycles", "dsh_set_option", "dsh_get_info", "dsh_stream",
 ]
@@ -190,7 +192,10 @@ def load_library():
                        ("dsh_dist_rect_histogram", [vp, i32, i32, i32, u64, u64, u64, u64, vp, C.c_uint32, vp, vp]),
                        ("dsh_linkage_threshold", [vp, i32, i32, i32, C.c_float, i32, vp, C.POINTER(u64)]),
                        ("dsh_linkage_threshold_device", [vp, i32, i32, i32, C.c_float, i32, vp, C.POINTER(u64)]),
-                       ("dsh_linkage_tri", [vp, u64, vp, i32, C.c_float, i32, vp, C.POINTER(u64)])):
+                       ("dsh_linkage_tri", [vp, u64, vp, i32, C.c_float, i32, vp, C.POINTER(u64)]),
+                       ("dsh_mst", [vp, i32, i32, i32, C.c_float, vp, vp, vp, C.POINTER(u64), vp]),
+                       ("dsh_mst_tri", [vp, u64, vp, i32, C.c_float, vp, vp, vp, C.POINTER(u64), vp]),
+                       ("dsh_mst_linkage", [u64, vp, vp, vp, u64, vp, vp, vp, vp])):
         fn = getattr(lib, name, None)
         if fn is not None:
             fn.argtypes = args
@@ -380,6 +385,22 @@ def histogram_hits(counts, result_type):
     if result_type in DISTANCE_TYPES:
         return np.cumsum(body, axis=-1, dtype=np.uint64)[..., :-1]
     return np.cumsum(body[..., ::-1], axis=-1, dtype=np.uint64)[..., ::-1][..., 1:]
+
+
+def mst_linkage(n, lhs, rhs, val):
+    """(za, zb, zv, zsize): the sorted edge list of Context.mst / mst_tri as a merge table in scipy's Z convention -- leaves
+    0 .. n - 1, step s joins the current clusters of lhs[s] and rhs[s] into cluster n + s; za < zb.  Pure host."""
+    lhs, rhs = np.ascontiguousarray(lhs, np.uint32).reshape(-1), np.ascontiguousarray(rhs, np.uint32).reshape(-1)
+    val = np.ascontiguousarray(val, np.float32).reshape(-1)
+    if not lhs.size == rhs.size == val.size:
+        raise ValueError("lhs, rhs and val hold one entry per edge")
+    m = lhs.size
+    za, zb, zv, zsize = np.zeros(m, np.uint32), np.zeros(m, np.uint32), np.zeros(m, np.float32), np.zeros(m, np.uint32)
+    ptr = [a.ctypes.data if m else None for a in (lhs, rhs, val, za, zb, zv, zsize)]
+    rc = load_library().dsh_mst_linkage(int(n), ptr[0], ptr[1], ptr[2], m, *ptr[3:])
+    if rc:
+        raise DshError(rc, "dsh_mst_linkage: an edge names a node outside [0, n) or the list is not a forest")
+    return za, zb, zv, zsize
 
 
 class GroupStats(collections.namedtuple("GroupStats", "medoid cnt sum worst")):
@@ -822,6 +843,36 @@ class Context:
                                                  threshold, self._linkage(linkage), labels.ctypes.data if labels.size else None,
                                                  C.byref(nc)))
         return labels, int(nc.value)
+
+    # ---- the minimum spanning tree of the pair values: the single-linkage dendrogram (include/dashing_hip.h has the contract)
+    def _mst(self, name, n, head, descending, cutoff, labels):
+        if cutoff is None:  # no cutoff: every value that is not NaN is an edge
+            cutoff = -np.inf if descending else np.inf
+        m = max(n - 1, 0)
+        lhs, rhs, val = np.zeros(m, np.uint32), np.zeros(m, np.uint32), np.zeros(m, np.float32)
+        lab = np.zeros(n, np.uint32) if labels else None
+        ne = C.c_uint64()
+        self._ck(self._derive(name)(self._h, *head, cutoff, lhs.ctypes.data if m else None, rhs.ctypes.data if m else None,
+                                    val.ctypes.data if m else None, C.byref(ne), lab.ctypes.data if labels and n else None))
+        e = int(ne.value)
+        return (lhs[:e], rhs[:e], val[:e]) + ((lab,) if labels else ())
+
+    def mst(self, cutoff=None, estim=ESTIM_ERTL_MLE, result_type=JI, k=31, labels=False):
+        """(lhs, rhs, val[, labels]): the best spanning forest of the pairs whose value passes `cutoff` (None: all that are not
+        NaN), edges lhs < rhs sorted best first -- better value, then smaller lhs, then smaller rhs; labels = what
+        cluster_threshold(cutoff) gives"""
+        return self._mst("dsh_mst", self.n, (estim, result_type, k), result_type not in DISTANCE_TYPES, cutoff, labels)
+
+    def mst_tri(self, tri, descending, cutoff=None, labels=False, n_nodes=None):
+        """the same for a caller's values: tri holds n (n - 1) / 2 float32 in dsh_tri_index order (np.triu_indices(n, 1)); n is
+        taken from its size (n_nodes tells one node from none: both have an empty triangle).  Needs no sketches."""
+        tri = np.ascontiguousarray(tri, np.float32).reshape(-1)
+        n = (1 + math.isqrt(1 + 8 * tri.size)) // 2 if tri.size else 0
+        if n_nodes is not None:
+            n = int(n_nodes)
+        if n < 0 or n * (n - 1) // 2 != tri.size:
+            raise ValueError("tri holds n (n - 1) / 2 values")
+        return self._mst("dsh_mst_tri", n, (n, tri.ctypes.data if tri.size else None, 1 if descending else 0), descending, cutoff, labels)
 
     # ---- greedy representatives in slot order (include/dashing_hip.h has the contract)
     def greedy_threshold(self, threshold, estim=ESTIM_ERTL_MLE, result_type=JI, k=31):

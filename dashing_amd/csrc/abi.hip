@@ -913,6 +913,8 @@ int dsh_get_info(dsh_ctx *c, const char *name, int64_t *out)
     else if (!std::strcmp(name, "xch_recv_gated")) *out = c->xch.recv_gated ? 1 : 0;
     else if (!std::strcmp(name, "stats_route")) *out = c->gs.route_last;
     else if (!std::strcmp(name, "linkage_route")) *out = c->lk.route_last;
+    else if (!std::strcmp(name, "mst_rounds")) *out = c->mst.rounds_last;
+    else if (!std::strcmp(name, "mst_band_us")) *out = (int64_t)(c->mst.band_ms * 1000.0);
     else if (!std::strcmp(name, "place_kernel_us")) *out = (int64_t)(c->xch.place_ms * 1000.0);
     else if (!std::strcmp(name, "whatif_mfma")) {
 #ifdef DSH_WHATIF_MFMA

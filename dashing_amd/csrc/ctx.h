@@ -9,6 +9,7 @@
 //   threshold.hip dsh_dist_threshold*, dsh_dist_rect_threshold (values that pass a threshold, as CSR)
 //   pairs.hip     dsh_dist_pairs* (values of an explicit list of pairs, the direct form)
 //   cluster.hip   dsh_cluster_* (connected components at a threshold, or of a caller's graph)
+//   mst.hip       dsh_mst* (the minimum spanning tree of the pair values: the single-linkage dendrogram)
 //   greedy.hip    dsh_greedy_threshold* (greedy representatives at a threshold, in slot order)
 //   greedy_extend.hip  dsh_greedy_extend* (the same behind a labelling of the first slots; first or best representative)
 //   group_stats.hip    dsh_group_stats* (per-group statistics and medoids of a labelling)
@@ -314,6 +315,13 @@ struct dsh_ctx {
         int route = -1;               // option linkage_route: -1 auto | 0 dense | 1 pairs
         int route_last = -1;          // (info) the route the last dsh_linkage_threshold* call took
     } lk;
+    // dsh_mst* (mst.hip): per slot the best offer of a round, per component root its best key and edge, the edges of the call
+    // (lhs | rhs | key, n - 1 each) and their count + the scratch root count of the rounds' labels
+    struct {
+        DevBuf best, ckey, cedge, elhs, erhs, ekey, state;
+        int rounds_last = 0;          // (info) mst_rounds: the rounds of the last call that emitted an edge
+        double band_ms = 0;           // (profiling) device time of the last call's k_mst_band launches
+    } mst;
     // dsh_fold*, dsh_upload_sketches_folded*, dsh_union_groups* (derive.hip): the error word, a chunk of source rows or of
     // folded rows on its way through the device, the groups' CSR and the partial unions of groups cut into chunks
     struct {

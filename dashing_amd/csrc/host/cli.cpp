@@ -138,6 +138,18 @@ static void usage(const char *sub)
             "  --histogram-labels FILE  with --histogram: FILE is the -b output of --cluster or --representatives over the same\n"
             "                           inputs in the same order; every line gets two counts, the pairs inside a group and the\n"
             "                           pairs between groups (-b: two planes).\n"
+            "  --mst                    emit the minimum spanning tree of the pair values instead of the values: the\n"
+            "                           single-linkage dendrogram, n - 1 edges that give the --cluster components at EVERY\n"
+            "                           threshold (dsh_mst).  Text: '#MST<TAB>measure<TAB>n<TAB>n_edges', then\n"
+            "                           name_a<TAB>name_b<TAB>value per edge, best value first (ties: inputs in output order);\n"
+            "                           -b: u64 n, u64 n_edges, u32 lhs[n_edges], u32 rhs[n_edges], f32 val[n_edges].\n"
+            "                           --mst-cutoff FLOAT: only pairs that pass FLOAT as --threshold would are edges (a forest)\n"
+            "                           [every pair whose value is not NaN].  Not with what --cluster refuses, nor with --cluster,\n"
+            "                           --representatives, --histogram or --stats.\n"
+            "  --dendrogram             with --mst: emit the merge table instead of the edges (dsh_mst_linkage).  Inputs are the\n"
+            "                           clusters 0 .. n - 1 in output order, merge s makes cluster n + s.  Text:\n"
+            "                           '#Dendrogram<TAB>measure<TAB>n<TAB>n_merges', then a<TAB>b<TAB>value<TAB>size per merge\n"
+            "                           (a < b the cluster ids); -b: u64 n, u64 n_merges, u32 a[], u32 b[], f32 value[], u32 size[].\n"
             "  --pairs FILE             emit only the pairs FILE lists, one per line as name_a<TAB>name_b (input names as given\n"
             "                           here; record names with dist_by_seq), in FILE's order: name_a<TAB>name_b and one value per\n"
             "                           measure.  --measures LIST: comma-separated from MASH_DIST, JI, SIZES, FULL_MASH_DIST,\n"
@@ -168,6 +180,9 @@ struct Opts {
     int assign_mode = DSH_GREEDY_FIRST;  // --assign first|best (dsh_greedy_extend)
     bool has_assign = false;
     bool has_stats = false;  // --stats: medoid, mean and worst value per input of the labelling (dsh_group_stats)
+    bool has_mst = false;  // --mst [--mst-cutoff FLOAT] [--dendrogram]: the minimum spanning tree of the pair values (dsh_mst)
+    bool has_mst_cutoff = false, dendrogram = false;
+    float mst_cutoff = 0.f;
     bool has_hist = false;  // --histogram SPEC: the distribution of the values over the edges of SPEC (dsh_dist_histogram)
     std::vector<float> hist_edges;
     std::string hist_labels_file;  // --histogram-labels FILE: counts split into intra-group and inter-group pairs
@@ -286,7 +301,7 @@ static float float_option(const char *flag, const char *arg)
     return v;
 }
 
-enum { OPT_PRESKETCHED = 1000, OPT_AVOID_SORT, OPT_DEVICE, OPT_NPERBATCH, OPT_NN, OPT_NGPUS, OPT_DEVICES, OPT_RCCL, OPT_THRESHOLD, OPT_CLUSTER, OPT_LINKAGE, OPT_REPS, OPT_ASSIGN, OPT_EXTEND, OPT_STATS, OPT_HISTOGRAM, OPT_HISTOGRAM_LABELS, OPT_PAIRS, OPT_MEASURES, OPT_GROUPS, OPT_UNSUPPORTED };
+enum { OPT_PRESKETCHED = 1000, OPT_AVOID_SORT, OPT_DEVICE, OPT_NPERBATCH, OPT_NN, OPT_NGPUS, OPT_DEVICES, OPT_RCCL, OPT_THRESHOLD, OPT_CLUSTER, OPT_LINKAGE, OPT_REPS, OPT_ASSIGN, OPT_EXTEND, OPT_STATS, OPT_HISTOGRAM, OPT_HISTOGRAM_LABELS, OPT_MST, OPT_MST_CUTOFF, OPT_DENDROGRAM, OPT_PAIRS, OPT_MEASURES, OPT_GROUPS, OPT_UNSUPPORTED };
 
 static Opts parse(int argc, char **argv, bool is_dist)
 {
@@ -317,6 +332,7 @@ static Opts parse(int argc, char **argv, bool is_dist)
         {"assign", required_argument, nullptr, OPT_ASSIGN}, {"extend", required_argument, nullptr, OPT_EXTEND},
         {"stats", no_argument, nullptr, OPT_STATS},
         {"histogram", required_argument, nullptr, OPT_HISTOGRAM}, {"histogram-labels", required_argument, nullptr, OPT_HISTOGRAM_LABELS},
+        {"mst", no_argument, nullptr, OPT_MST}, {"mst-cutoff", required_argument, nullptr, OPT_MST_CUTOFF}, {"dendrogram", no_argument, nullptr, OPT_DENDROGRAM},
         {"pairs", required_argument, nullptr, OPT_PAIRS}, {"groups", required_argument, nullptr, OPT_GROUPS}, {"measures", required_argument, nullptr, OPT_MEASURES},
         // second arm of result_cmp (src/dashing.h:577-588); flag numbers as in DIST_LONG_OPTS
         {"sizes", no_argument, nullptr, 'Z'}, {"containment-index", no_argument, nullptr, 131},
@@ -397,6 +413,9 @@ static Opts parse(int argc, char **argv, bool is_dist)
             break;
         case OPT_EXTEND: o.extend_file = optarg; break;
         case OPT_STATS: o.has_stats = true; break;
+        case OPT_MST: o.has_mst = true; break;
+        case OPT_MST_CUTOFF: o.mst_cutoff = float_option("--mst-cutoff", optarg), o.has_mst_cutoff = true; break;
+        case OPT_DENDROGRAM: o.dendrogram = true; break;
         case OPT_HISTOGRAM:
             o.hist_edges = parse_histogram_spec(optarg);
             o.has_hist = true;
@@ -1211,6 +1230,21 @@ static void refuse_conflicts(const Opts &o, bool by_seq)
         if (o.fmt == FULL_TSV) die("--histogram does not go with -T: the output is one line per class.");
         if (o.devices.size() > 1 || o.rccl) die("--histogram runs on one device: --ngpus / --devices are not supported.");
     }
+    if (o.has_mst) {  // (what --cluster refuses, and the other selections)
+        if (o.has_cluster) die("--mst does not go with --cluster: the tree gives the clusters at every threshold.");
+        if (o.has_reps) die("--mst does not go with --representatives: choose the tree or the representatives.");
+        if (o.has_hist) die("--mst does not go with --histogram: choose the tree or the distribution.");
+        if (o.has_stats) die("--mst does not go with --stats: the tree is no labelling.");
+        if (o.has_threshold) die("--mst does not go with --threshold: choose the tree or the pairs (--mst-cutoff bounds the tree's edges).");
+        if (o.nneighbors) die("--mst does not go with --nearest-neighbors: choose one selection.");
+        if (with_pairs) die("--mst does not go with --pairs: the tree is that of all pairs.");
+        if (!o.querypaths.empty()) die("--mst does not go with -Q: every input is joined with every other.");
+        if (o.fmt == UPPER_TRIANGULAR) die("--mst does not go with -U: the output is one line per edge.");
+        if (o.fmt == FULL_TSV) die("--mst does not go with -T: the output is one line per edge.");
+        if (o.devices.size() > 1 || o.rccl) die("--mst runs on one device: --ngpus / --devices are not supported.");
+    }
+    if (o.has_mst_cutoff && !o.has_mst) die("--mst-cutoff goes with --mst only.");
+    if (o.dendrogram && !o.has_mst) die("--dendrogram goes with --mst only.");
     if (!o.hist_labels_file.empty() && !o.has_hist) die("--histogram-labels goes with --histogram only.");
     if (o.has_assign && !o.has_reps) die("--assign goes with --representatives only.");
     if (o.has_stats && !o.has_cluster && !o.has_reps) die("--stats goes with --cluster or --representatives only.");
@@ -1276,7 +1310,7 @@ static void order_paths(DistRun &r)
     // asymmetric measure without -Q: all references are also the queries
     // (--cluster, --representatives and --histogram take every pair once, in the triangle's orientation: no query/reference format
     // of their own making for them)
-    r.symmetric = o.has_cluster || o.has_reps || o.has_hist || !(o.result_type == 4 || o.result_type == 5 || o.result_type == 6);  // src/dashing.h:389-399
+    r.symmetric = o.has_cluster || o.has_reps || o.has_hist || o.has_mst || !(o.result_type == 4 || o.result_type == 5 || o.result_type == 6);  // src/dashing.h:389-399
     if (o.querypaths.empty() && !r.symmetric && o.pairs_file.empty() && o.groups_file.empty()) {  // (a pair list names its own pairs, each in one orientation; the groups take their turn in union_groups)
         o.querypaths = o.inpaths;
         std::fprintf(stderr, "Note: No query files provided, but an asymmetric distance was requested. Switching to a query/reference format with all references as queries.\n");
@@ -1594,6 +1628,41 @@ static void emit_labelling(const DistRun &r, std::FILE *fp)
     }
 }
 
+// --mst: the minimum spanning tree of the pair values (dsh_mst), or with --dendrogram its merge table (dsh_mst_linkage).  No
+// pair leaves the device: n - 1 edges do
+static void emit_mst(const DistRun &r, std::FILE *fp)
+{
+    const Opts &o = r.o;
+    const size_t n = r.n;
+    const std::vector<std::string> &names = o.inpaths;
+    const float inf = std::numeric_limits<float>::infinity();
+    const float cutoff = o.has_mst_cutoff ? o.mst_cutoff : (is_distance(o.result_type) ? inf : -inf);
+    const size_t room = std::max<size_t>(n, 2) - 1;
+    std::vector<uint32_t> lhs(room), rhs(room), size(room);
+    std::vector<float> val(room);
+    uint64_t m = 0;
+    DSH(r.ctx, dsh_mst(r.ctx, o.estim, o.result_type, o.k, cutoff, lhs.data(), rhs.data(), val.data(), &m, nullptr));
+    if (o.dendrogram) {  // (the values stay where they are: row s takes the value of edge s)
+        std::vector<uint32_t> za(room), zb(room);
+        if (dsh_mst_linkage(n, lhs.data(), rhs.data(), val.data(), m, za.data(), zb.data(), val.data(), size.data()) != DSH_OK)
+            die("internal: the edges of dsh_mst are not a forest");
+        lhs.swap(za), rhs.swap(zb);
+    }
+    if (o.fmt == BINARY) {
+        const uint64_t hdr[2] = {(uint64_t)n, m};
+        if (std::fwrite(hdr, sizeof(uint64_t), 2, fp) != 2 || std::fwrite(lhs.data(), sizeof(uint32_t), m, fp) != m ||
+            std::fwrite(rhs.data(), sizeof(uint32_t), m, fp) != m || std::fwrite(val.data(), sizeof(float), m, fp) != m ||
+            (o.dendrogram && std::fwrite(size.data(), sizeof(uint32_t), m, fp) != m))
+            die("Error writing to binary file");
+        return;
+    }
+    std::fprintf(fp, "#%s\t%s\t%zu\t%llu\n", o.dendrogram ? "Dendrogram" : "MST", kMeasureNames[o.result_type], n, (unsigned long long)m);
+    for (size_t e = 0; e < m; ++e) {  // --representatives' number format
+        if (o.dendrogram) std::fprintf(fp, "%u\t%u\t%.6g\t%u\n", lhs[e], rhs[e], (double)val[e], size[e]);
+        else std::fprintf(fp, "%s\t%s\t%.6g\n", names[lhs[e]].c_str(), names[rhs[e]].c_str(), (double)val[e]);
+    }
+}
+
 // --histogram: the distribution of the values (dsh_dist_histogram / dsh_dist_rect_histogram): only counts leave the device
 static void emit_histogram(const DistRun &r, std::FILE *fp)
 {
@@ -1881,6 +1950,7 @@ static int dist_main(int argc, char **argv, bool by_seq = false)
     if (!o.pairs_file.empty()) emit_pairs(r, pairofp);
     else if (o.has_cluster || o.has_reps) emit_labelling(r, pairofp);
     else if (o.has_hist) emit_histogram(r, pairofp);
+    else if (o.has_mst) emit_mst(r, pairofp);
     else if (o.has_threshold) emit_threshold(r, pairofp);
     else if (o.nneighbors) emit_nearest_neighbors(r, pairofp);
     else if (r.nq) emit_rectangle(r, pairofp);

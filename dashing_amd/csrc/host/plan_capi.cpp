@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../linkage.h"
+#include "../mst.h"
 #include "../plan.h"
 #include "../uf.h"
 
@@ -533,5 +534,25 @@ int dsh_plan_linkage_labels(uint64_t n, const float *tri, int descending, float 
 // the loose float threshold of the AVERAGE partition (lk_loose_threshold) and q(v), for the CPU tests
 float dsh_plan_linkage_loose(float threshold, int descending) { return lk_loose_threshold(threshold, descending ? 1 : 0); }
 int64_t dsh_plan_linkage_q(float v) { return lk_q(v); }
+
+// the minimum spanning tree of the pair values (../mst.h, the step logic the device kernels compile) run sequentially over the
+// n (n - 1) / 2 values of tri (dsh_tri_index order): the edges sorted best first as dsh_mst_tri returns them, labels (or NULL) =
+// the smallest node of x's component, *rounds = the rounds that emitted.  Returns 0, -1 for a bad argument, and the give-up code
+// (3) when more than round_cap rounds emitted -- the path the device build must never reach (tests/test_mst_host.py).
+int dsh_plan_mst(uint64_t n, const float *tri, int descending, float cutoff, uint32_t round_cap, uint32_t *lhs, uint32_t *rhs, float *val,
+                 uint64_t *n_edges, uint32_t *labels, uint32_t *rounds)
+{
+    if (n > 65536 || !n_edges || !rounds || (n > 1 && (!tri || !lhs || !rhs || !val))) return -1;
+    std::vector<uint32_t> parent;
+    std::vector<MstEdge> e;
+    *n_edges = 0;
+    const uint32_t rc = mst_run_seq(n, tri, descending ? 1 : 0, cutoff, round_cap, parent, e, rounds);
+    if (rc) return (int)rc;
+    if (!e.empty()) mst_sorted_out(e, descending ? 1 : 0, lhs, rhs, val);
+    *n_edges = e.size();
+    if (labels)
+        for (uint64_t x = 0; x < n; ++x) labels[x] = uf_find<UfPlain>(parent.data(), (uint32_t)x, (uint32_t)n + 1);
+    return 0;
+}
 
 }  // extern "C"

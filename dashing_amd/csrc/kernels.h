@@ -280,6 +280,23 @@ hipError_t launch_linkage(hipStream_t st, int linkage, const LkComps &C, const L
                           uint32_t lds_members, uint32_t cap, uint32_t *labels, uint32_t *err);
 size_t linkage_lds_bytes(int linkage, uint32_t m);  // LDS of a workgroup of k_linkage whose state holds m members
 
+// minimum spanning tree of the pair values (kernels_mst.hip, mst.hip, mst.h): one Borůvka round over labels[n] (launch_cc_labels),
+// best_v[n] and ckey[n] zeroed and cedge[n] all ones by the caller
+struct MstEdges {
+    uint32_t *lhs, *rhs, *key;  // [room] the edges of the call so far, in arbitrary order
+    unsigned long long *count;  // how many
+    uint64_t room;              // n - 1: no store goes beyond
+};
+// a band of triangle rows as launch_thr_count takes it: every value that passes the cutoff between two components offers
+// itself to best_v of both ends
+hipError_t launch_mst_band(hipStream_t st, const float *vals, const ThrRows &g, float cutoff, int descending, const uint32_t *labels,
+                           uint64_t *best_v);
+// per component root: ckey = the best key among its members' offers, cedge = the smallest (i << 32 | j) that holds it
+hipError_t launch_mst_pick(hipStream_t st, const uint64_t *best_v, const uint32_t *labels, uint32_t *ckey, uint64_t *cedge, uint64_t n);
+// the roots' edges appended to e (a mutual choice once) and their ends united in parent (cap, err: as launch_cc_edges)
+hipError_t launch_mst_emit(hipStream_t st, const uint32_t *labels, const uint32_t *ckey, const uint64_t *cedge, uint64_t n, uint32_t *parent,
+                           uint32_t cap, uint32_t *err, const MstEdges &e);
+
 // value histograms (kernels_hist.hip, hist.hip): a band of triangle or rectangle rows as launch_thr_count takes it, counted
 // into counts[planes][n_edges + 2] (device, 64-bit adds: the caller zeroes it) over the n_edges strictly increasing edges at
 // d_edges (device); class(v) = the edges that pass v as a threshold would, NaN = n_edges + 1.  labels == nullptr: one plane;

@@ -64,7 +64,7 @@ typedef struct dsh_ctx dsh_ctx;
  * dsh_upload_sketches_folded*, dsh_union_groups*, dsh_cluster_threshold, dsh_cluster_threshold_device, dsh_cluster_pairs,
  * dsh_cluster_csr, dsh_greedy_threshold, dsh_greedy_threshold_device, dsh_greedy_extend, dsh_greedy_extend_device,
  * dsh_group_stats, dsh_group_stats_device, dsh_dist_histogram, dsh_dist_histogram_device, dsh_dist_rect_histogram,
- * dsh_linkage_threshold, dsh_linkage_threshold_device, dsh_linkage_tri. */
+ * dsh_linkage_threshold, dsh_linkage_threshold_device, dsh_linkage_tri, dsh_mst, dsh_mst_tri, dsh_mst_linkage. */
 #define DSH_ABI_VERSION 7
 int dsh_abi_version(void);
 
@@ -464,7 +464,8 @@ int dsh_cluster_csr(dsh_ctx *ctx, uint64_t n_nodes, uint64_t row_begin, uint64_t
  *     n_nodes >= 2.  After the component labels: DSH_ENOMEM, with a message that names m and the bytes, for one component whose
  *     matrix exceeds "linkage_budget_bytes" (or, AVERAGE, of more than 65536 members: its sums are 64-bit); the context stays
  *     usable.  A NaN threshold gives n singletons; n == 0 and n == 1 succeed.
- *   Not built: the merge list (a dendrogram), a component larger than one workgroup's budget spread over several workgroups,
+ *   Not built: the merge list (a dendrogram) of complete or average linkage (the single-linkage dendrogram is dsh_mst below), a
+ *     component larger than one workgroup's budget spread over several workgroups,
  *     Ward / centroid linkages, a multi-GPU form.  Cost: about 1-2 ms per merge step of a component of ~3000 members on an MI355X
  *     (DESIGN.md 4.15); tools/bench_linkage.py is the benchmark, which has not been run to its end. */
 #define DSH_LINKAGE_SINGLE 0
@@ -476,6 +477,62 @@ int dsh_linkage_threshold_device(dsh_ctx *ctx, int estim, int result_type, int k
                                  uint64_t *n_clusters);
 int dsh_linkage_tri(dsh_ctx *ctx, uint64_t n_nodes, const float *tri, int descending, float threshold, int linkage,
                     uint32_t *labels_out, uint64_t *n_clusters);
+
+/* ---- minimum spanning tree of the pair values: the single-linkage dendrogram, on the device ------------------
+ * Replaces what a client does today for the single-linkage tree (a guide tree, or the clusters at EVERY threshold): pull the
+ * n (n - 1) / 2 matrix to the host and run a host `linkage` on it, or call dsh_cluster_threshold once per candidate threshold.
+ * The single-linkage dendrogram is the minimum spanning tree of the pair values: n - 1 edges.
+ *   Values: for slots x != y, v(x, y) is the float32 dsh_dist_rows leaves at dsh_tri_index(n, min, max) -- the ONE orientation of
+ *     the triangle, as in dsh_cluster_threshold (dsh_mst_tri: the caller's tri[dsh_tri_index(n, min, max)]).  desc = the measure
+ *     is a similarity (better = larger; the *_DIST forms: better = smaller; dsh_mst_tri: the caller's `descending`).  Values
+ *     compare as floats do with -0.0 equal to +0.0; +-inf are ordinary values.
+ *   The graph G: the pair {x, y} is an edge iff v is not NaN and passes `cutoff` by the float predicate of dsh_dist_threshold
+ *     (v >= cutoff for similarities, v <= cutoff for distances).  A NaN cutoff passes nothing (dsh_cluster_threshold's rule); for
+ *     "no cutoff" pass -INFINITY (similarity) or +INFINITY (distance).
+ *   Edge order: the edge (i, j), i < j, is better than another iff it comes first lexicographically by (the better value, the
+ *     smaller i, the smaller j).  This is a strict total order, so G has exactly ONE best spanning forest: the one Kruskal's
+ *     algorithm builds when it takes the edges in this order.  It is the result.
+ *   Output: *n_edges = n - (components of G); lhs_out[e] < rhs_out[e] (uint32) and val_out[e] (float32: the pair's dense value,
+ *     a zero as +0.0), sorted best first in the order above; the caller sizes the three arrays for n - 1 entries.  labels_out
+ *     (host uint32 [n], or NULL): the smallest slot of x's component of G, byte for byte what dsh_cluster_threshold gives at
+ *     `cutoff`.  The result depends on no band size, launch geometry or order of arrival of atomics: the same call gives the
+ *     same bytes.
+ *   Consequence: for any t at least as tight as `cutoff`, the edges whose value passes t are a prefix of the list, and
+ *     dsh_cluster_pairs over that prefix equals dsh_cluster_threshold at t byte for byte -- one call stands in for a cluster call
+ *     at every threshold.
+ *   dsh_mst          over the resident sketches.
+ *   dsh_mst_tri      the same for a caller's values (ANI, say): tri holds n_nodes (n_nodes - 1) / 2 float32 in host memory in
+ *                    dsh_tri_index order; no sketches are needed, only the stream and scratch.
+ *   dsh_mst_linkage  pure host, no context: the sorted edge list as a merge table in scipy's Z convention.  Leaves are
+ *                    0 .. n - 1; step s joins the current clusters of lhs[s] and rhs[s] into cluster n + s; za[s] < zb[s] are the
+ *                    two cluster ids, zv[s] = val[s], zsize[s] the member count.  A forest of fewer than n - 1 edges is legal and
+ *                    gives n_edges rows.  DSH_EINVAL if an edge names a node >= n_nodes or joins two nodes that are already
+ *                    united (the list is not a forest), or a NULL array with n_edges > 0.
+ *   How: Boruvka rounds over the band walk of dsh_cluster_threshold ("threshold_band_bytes").  Per round the component labels of
+ *     the union-find, one pass of k_mst_band over every band -- a passing value between two components offers (value, partner)
+ *     to both ends under a 64-bit maximum --, per component the best offer of its members, and the chosen edges appended and
+ *     united; one 8-byte read of the edge count is the round's only host wait.  The components with an outgoing edge at least
+ *     halve per round, so at most floor(log2 n) + 1 rounds emit; dsh_get_info(ctx, "mst_rounds") is the number of the last call.
+ *     The loop is bounded at 34 rounds: an overrun is unreachable in a correct build and fails the call with DSH_EIO and the
+ *     message "internal: mst round bound exceeded".  The edges (12 bytes each) come to the host once and are sorted there.
+ *   Cost: rounds x one dense pass.  Where the whole triangle is ONE band (10 000 sketches at the default 1 GiB) it is computed,
+ *     or uploaded, once and walked again by every round; else every round recomputes (dsh_mst) or uploads again (dsh_mst_tri)
+ *     its bands.  Per pair and round the walk reads up to 16 bytes (value, label, best offer) where k_cc_band reads 4
+ *     (tools/bench_mst.py is the benchmark: on an MI355X 15.0 ms at 10 000 x p=14, where one cluster call takes
+ *     14.0, and 2.07 s at 100 000 x p=10, seven dense passes).  Scratch: 32 bytes per slot beside the cluster call's.
+ *   Synchronous, on the ctx stream.  The effects on cached state are exactly those of dsh_cluster_threshold: a dense call before
+ *     and a dense call after give the same bytes.
+ *   Errors, before anything is enqueued, as dsh_cluster_threshold / dsh_linkage_tri: DSH_ESTATE without sketches (dsh_mst);
+ *     DSH_EINVAL for n > 2^32 - 1, for a NULL lhs_out, rhs_out, val_out or n_edges with n >= 2, and for a NULL tri with
+ *     n_nodes >= 2.  n == 0 and n == 1 succeed with 0 edges.
+ *   Not built: a device-resident output form (the result is at most 12 (n - 1) bytes and is sorted on the host), a rectangle, a
+ *     multi-GPU form, merge lists for complete or average linkage. */
+int dsh_mst(dsh_ctx *ctx, int estim, int result_type, int k, float cutoff, uint32_t *lhs_out, uint32_t *rhs_out, float *val_out,
+            uint64_t *n_edges, uint32_t *labels_out);
+int dsh_mst_tri(dsh_ctx *ctx, uint64_t n_nodes, const float *tri, int descending, float cutoff, uint32_t *lhs_out, uint32_t *rhs_out,
+                float *val_out, uint64_t *n_edges, uint32_t *labels_out);
+int dsh_mst_linkage(uint64_t n_nodes, const uint32_t *lhs, const uint32_t *rhs, const float *val, uint64_t n_edges, uint32_t *za,
+                    uint32_t *zb, float *zv, uint32_t *zsize);
 
 /* ---- greedy representatives at a threshold: the greedy pass in slot order, on the device ---------------
  * Replaces what a dereplication client does with the hits of dsh_dist_threshold* when it wants REPRESENTATIVES rather than
@@ -963,7 +1020,8 @@ int dsh_set_option(dsh_ctx *ctx, const char *name, int64_t value);
  * "place_kernel_us" (with profiling on: device time of the last dsh_exchange_place_device's placement kernel),
  * "sketch_kernel_us" / "fastx_decode_us" (with profiling on: k_sketch / the FASTA-FASTQ decode kernels of the last sketch call),
  * "stats_route" (the route the last dsh_group_stats* call took: 0 dense, 1 pairs; -1 before the first), "linkage_route" (the same
- * for the last dsh_linkage_threshold* call). */
+ * for the last dsh_linkage_threshold* call), "mst_rounds" (the rounds of the last dsh_mst* call that emitted an edge),
+ * "mst_band_us" (with profiling on: the device time of its k_mst_band launches). */
 int dsh_get_info(dsh_ctx *ctx, const char *name, int64_t *out);
 /* HIP stream of the ctx as a void* (hipStream_t) so a host framework can order its own work.
  * Every *_device entry point runs on THIS stream and (except the *_async forms) returns after its work has
