@@ -15,7 +15,8 @@ ESTIM_ORIGINAL, ESTIM_ERTL_IMPROVED, ESTIM_ERTL_MLE = 0, 1, 2
 MASH_DIST, JI, FULL_MASH_DIST = 0, 1, 3  # bns::EmissionType, src/enums.h:13-23
 SIZES, FULL_CONTAINMENT_DIST, CONTAINMENT_INDEX, CONTAINMENT_DIST = 2, 4, 5, 6
 SYMMETRIC_CONTAINMENT_INDEX, SYMMETRIC_CONTAINMENT_DIST = 7, 8
-GREEDY_FIRST, GREEDY_BEST = 0, 1  # assign_mode of dsh_greedy_extend*
+GREEDY_FIRST, GREEDY_BEST = 0, 1  # assign_mode of dsh_greedy_extend* and dsh_dbscan_*
+DBSCAN_NOISE, DBSCAN_BORDER, DBSCAN_CORE = 0, 1, 2  # DSH_DBSCAN_*: kind[] of dsh_dbscan_*
 HIST_MAX_EDGES = 4096  # DSH_HIST_MAX_EDGES: the edges of one dsh_dist_histogram* call
 LINKAGE_SINGLE, LINKAGE_COMPLETE, LINKAGE_AVERAGE = 0, 1, 2  # DSH_LINKAGE_*
 STATS_FRAC_BITS = 30  # DSH_STATS_FRAC_BITS: sums of dsh_group_stats* are in units of 2^-30
@@ -47,6 +48,7 @@ SYMBOLS = [
     "dsh_dist_histogram", "dsh_dist_histogram_device", "dsh_dist_rect_histogram",
     "dsh_linkage_threshold", "dsh_linkage_threshold_device", "dsh_linkage_tri",
     "dsh_mst", "dsh_mst_tri", "dsh_mst_linkage",
+    "dsh_dbscan_threshold", "dsh_dbscan_threshold_device", "dsh_dbscan_tri", "dsh_degree_threshold", "dsh_degree_threshold_device",
     "dsh_fold", "dsh_fold_device", "dsh_upload_sketches_folded", "dsh_upload_sketches_folded_device", "dsh_union_groups", "dsh_union_groups_device", "dsh_shard_plan", "dsh_dist_shard_device", "dsh_unpermute_device", "dsh_unpermute_staged_device", "dsh_unpermute_blocks_device", "dsh_tri_span", "dsh_tri_index", "dsh_partition_rows", "dsh_balance_rows", "dsh_balance_rowsets", "dsh_rowsets_from_bounds", "dsh_rowsets_rank", "dsh_alloc_host", "dsh_free_host",
     "dsh_set_profiling", "dsh_last_kernel_ms", "dsh_last_part_info", "dsh_finalize_phase_cycles", "dsh_set_option", "dsh_get_info", "dsh_stream",
 ]
@@ -195,7 +197,12 @@ def load_library():
                        ("dsh_linkage_tri", [vp, u64, vp, i32, C.c_float, i32, vp, C.POINTER(u64)]),
                        ("dsh_mst", [vp, i32, i32, i32, C.c_float, vp, vp, vp, C.POINTER(u64), vp]),
                        ("dsh_mst_tri", [vp, u64, vp, i32, C.c_float, vp, vp, vp, C.POINTER(u64), vp]),
-                       ("dsh_mst_linkage", [u64, vp, vp, vp, u64, vp, vp, vp, vp])):
+                       ("dsh_mst_linkage", [u64, vp, vp, vp, u64, vp, vp, vp, vp]),
+                       ("dsh_dbscan_threshold", [vp, i32, i32, i32, C.c_float, C.c_uint32, i32, vp, vp, vp, C.POINTER(u64), C.POINTER(u64)]),
+                       ("dsh_dbscan_threshold_device", [vp, i32, i32, i32, C.c_float, C.c_uint32, i32, vp, vp, vp, C.POINTER(u64), C.POINTER(u64)]),
+                       ("dsh_dbscan_tri", [vp, u64, vp, i32, C.c_float, C.c_uint32, i32, vp, vp, vp, C.POINTER(u64), C.POINTER(u64)]),
+                       ("dsh_degree_threshold", [vp, i32, i32, i32, C.c_float, vp]),
+                       ("dsh_degree_threshold_device", [vp, i32, i32, i32, C.c_float, vp])):
         fn = getattr(lib, name, None)
         if fn is not None:
             fn.argtypes = args
@@ -873,6 +880,63 @@ class Context:
         if n < 0 or n * (n - 1) // 2 != tri.size:
             raise ValueError("tri holds n (n - 1) / 2 values")
         return self._mst("dsh_mst_tri", n, (n, tri.ctypes.data if tri.size else None, 1 if descending else 0), descending, cutoff, labels)
+
+    # ---- density clusters at a threshold and the degrees of the threshold graph (include/dashing_hip.h has the contract)
+    @staticmethod
+    def _dbscan_args(min_pts, assign):
+        mode = {"first": GREEDY_FIRST, "best": GREEDY_BEST}.get(assign, assign)
+        if mode not in (GREEDY_FIRST, GREEDY_BEST) or isinstance(mode, bool):
+            raise ValueError("assign is 'first' or 'best', got %r" % (assign,))
+        min_pts = int(min_pts)
+        if not 0 <= min_pts <= 0xFFFFFFFF:  # (0 is the library's to refuse)
+            raise ValueError("min_pts is a uint32")
+        return min_pts, mode
+
+    def _dbscan(self, name, n, head, threshold, min_pts, assign):
+        min_pts, mode = self._dbscan_args(min_pts, assign)
+        labels, kind, degree = np.zeros(n, np.uint32), np.zeros(n, np.uint8), np.zeros(n, np.uint32)
+        nc, nn = C.c_uint64(), C.c_uint64()
+        self._ck(self._derive(name)(self._h, *head, threshold, min_pts, mode, labels.ctypes.data if n else None,
+                                    kind.ctypes.data if n else None, degree.ctypes.data if n else None, C.byref(nc), C.byref(nn)))
+        return labels, kind, degree, int(nc.value), int(nn.value)
+
+    def dbscan_threshold(self, threshold, min_pts, assign="first", estim=ESTIM_ERTL_MLE, result_type=JI, k=31):
+        """(labels uint32 [n], kind uint8 [n], degree uint32 [n], n_clusters, n_noise): DBSCAN over the graph of the hits of
+        dist_threshold(threshold, ...).  x is a core (DBSCAN_CORE) iff degree[x] + 1 >= min_pts; the clusters are the components
+        of the core-core edges, labelled with their smallest core; a non-core with a core neighbour is a border and goes to the
+        smallest ("first") or the best-valued ("best"; ties to the smallest) of them; the rest is noise, labelled with itself"""
+        return self._dbscan("dsh_dbscan_threshold", self.n, (estim, result_type, k), threshold, min_pts, assign)
+
+    def dbscan_threshold_device(self, labels_ptr, threshold, min_pts, assign="first", kind_ptr=None, degree_ptr=None,
+                                estim=ESTIM_ERTL_MLE, result_type=JI, k=31):
+        """labels (uint32 [n]) and, where given, kind (uint8 [n]) and degree (uint32 [n]) into the caller's device buffers;
+        returns (n_clusters, n_noise)"""
+        min_pts, mode = self._dbscan_args(min_pts, assign)
+        nc, nn = C.c_uint64(), C.c_uint64()
+        self._ck(self._derive("dsh_dbscan_threshold_device")(self._h, estim, result_type, k, threshold, min_pts, mode, C.c_void_p(labels_ptr),
+                                                             C.c_void_p(kind_ptr), C.c_void_p(degree_ptr), C.byref(nc), C.byref(nn)))
+        return int(nc.value), int(nn.value)
+
+    def dbscan_tri(self, tri, descending, threshold, min_pts, assign="first", n_nodes=None):
+        """the same for a caller's values: tri holds n (n - 1) / 2 float32 in dsh_tri_index order (np.triu_indices(n, 1)); n is
+        taken from its size (n_nodes tells one node from none: both have an empty triangle).  Needs no sketches."""
+        tri = np.ascontiguousarray(tri, np.float32).reshape(-1)
+        n = (1 + math.isqrt(1 + 8 * tri.size)) // 2 if tri.size else 0
+        if n_nodes is not None:
+            n = int(n_nodes)
+        if n < 0 or n * (n - 1) // 2 != tri.size:
+            raise ValueError("tri holds n (n - 1) / 2 values")
+        return self._dbscan("dsh_dbscan_tri", n, (n, tri.ctypes.data if tri.size else None, 1 if descending else 0), threshold, min_pts, assign)
+
+    def degree_threshold(self, threshold, estim=ESTIM_ERTL_MLE, result_type=JI, k=31):
+        """degree uint32 [n]: how many hits of dist_threshold(threshold, ...) each slot is an end of"""
+        degree = np.zeros(self.n, np.uint32)
+        self._ck(self._derive("dsh_degree_threshold")(self._h, estim, result_type, k, threshold, degree.ctypes.data if degree.size else None))
+        return degree
+
+    def degree_threshold_device(self, degree_ptr, threshold, estim=ESTIM_ERTL_MLE, result_type=JI, k=31):
+        """the degrees into the caller's device buffer (uint32 [n])"""
+        self._ck(self._derive("dsh_degree_threshold_device")(self._h, estim, result_type, k, threshold, C.c_void_p(degree_ptr)))
 
     # ---- greedy representatives in slot order (include/dashing_hip.h has the contract)
     def greedy_threshold(self, threshold, estim=ESTIM_ERTL_MLE, result_type=JI, k=31):

@@ -3,7 +3,8 @@
 // bands of whole rows by the planner's rule (plan.h: tri_band_end, rect_band_rows); a band is computed by run_pairs into
 // the library-owned c->thr_vals exactly as dsh_dist_rows_device / dsh_dist_rect compute it -- the dense path is the
 // producer and is not changed -- and handed to the caller's kernels as a ThrRows (kernels.h, thr_walk.h).  Everything is
-// enqueued on the ctx stream; no host wait of its own.
+// enqueued on the ctx stream; no host wait of its own.  dsh_mst* and dsh_dbscan_* walk the whole triangle through
+// for_each_source_band, which also takes a caller's own triangle on the host in the place of the sketches.
 #pragma once
 #include <algorithm>
 
@@ -62,6 +63,38 @@ int for_each_band(dsh_ctx *c, const BandQuery &q, F &&per_band)
         int rc = thr_geometry(c, q.rect, c->n, b0, b1, ncols, q.cb, g);
         if (rc || (rc = compute_band(c, q.estim, q.result_type, q.k, g, span)) || (rc = per_band(g, (const float *)c->thr_vals.ptr, span)))
             return rc;
+    }
+    return DSH_OK;
+}
+
+// where the values of a walk over the whole triangle come from: the resident sketches, or a caller's packed triangle of n
+// nodes on the host (dsh_mst_tri, dsh_dbscan_tri)
+struct BandSource {
+    const float *tri = nullptr;
+    int estim = 0, result_type = 0, k = 0;
+};
+
+// the band walk over either source: the caller's triangle is cut by the same rule and uploaded band by band into c->thr_vals
+template <class F>
+int for_each_source_band(dsh_ctx *c, uint64_t n, const BandSource &s, F &&per_band)
+{
+    if (!s.tri) {
+        BandQuery bq;
+        bq.estim = s.estim, bq.result_type = s.result_type, bq.k = s.k;
+        bq.re = n;
+        return for_each_band(c, bq, per_band);
+    }
+    const uint64_t band_floats = std::max<uint64_t>(c->threshold_band_bytes / sizeof(float), 1);
+    for (uint64_t b0 = 0, b1; b0 < n; b0 = b1) {
+        b1 = plan::tri_band_end(n, b0, n, band_floats, kBandMaxRows);
+        const uint64_t span = dsh_tri_span(n, b0, b1);
+        if (!span) continue;
+        ThrRows g;
+        int rc = thr_geometry(c, 0, n, b0, b1, 0, 0, g);
+        if (rc) return rc;
+        HIPCHK(c, c->thr_vals.ensure(span * sizeof(float)));
+        HIPCHK(c, hipMemcpyAsync(c->thr_vals.ptr, s.tri + dsh_tri_span(n, 0, b0), span * sizeof(float), hipMemcpyHostToDevice, c->stream));
+        if ((rc = per_band(g, (const float *)c->thr_vals.ptr, span))) return rc;
     }
     return DSH_OK;
 }

@@ -10,6 +10,7 @@
 //   pairs.hip     dsh_dist_pairs* (values of an explicit list of pairs, the direct form)
 //   cluster.hip   dsh_cluster_* (connected components at a threshold, or of a caller's graph)
 //   mst.hip       dsh_mst* (the minimum spanning tree of the pair values: the single-linkage dendrogram)
+//   dbscan.hip    dsh_dbscan_*, dsh_degree_threshold* (density clusters at a threshold; the degrees of the threshold graph)
 //   greedy.hip    dsh_greedy_threshold* (greedy representatives at a threshold, in slot order)
 //   greedy_extend.hip  dsh_greedy_extend* (the same behind a labelling of the first slots; first or best representative)
 //   group_stats.hip    dsh_group_stats* (per-group statistics and medoids of a labelling)
@@ -322,6 +323,11 @@ struct dsh_ctx {
         int rounds_last = 0;          // (info) mst_rounds: the rounds of the last call that emitted an edge
         double band_ms = 0;           // (profiling) device time of the last call's k_mst_band launches
     } mst;
+    // dsh_dbscan_*, dsh_degree_threshold* (dbscan.hip): per slot its degree and the best offer of a core neighbour, the kinds
+    // of the host form, and the counts of clusters and noise + the error word (parent and labels are those of cc)
+    struct {
+        DevBuf degree, best, kind, state;
+    } db;
     // dsh_fold*, dsh_upload_sketches_folded*, dsh_union_groups* (derive.hip): the error word, a chunk of source rows or of
     // folded rows on its way through the device, the groups' CSR and the partial unions of groups cut into chunks
     struct {

@@ -104,6 +104,17 @@ static void usage(const char *sub)
             "                           pair; exact mean of the member pairs in units of 2^-30), on the device (dsh_linkage_threshold).\n"
             "                           With complete or average the '#Cluster' line gains a fifth field, the linkage; -b is the same.\n"
             "                           average not with --sizes.\n"
+            "  --min-pts N              with --cluster: density clusters (DBSCAN) instead of the components, on the device\n"
+            "                           (dsh_dbscan_threshold).  An input with at least N - 1 others passing FLOAT with it is a core\n"
+            "                           (it counts itself); the clusters are the components of the core-core pairs; an input that\n"
+            "                           is no core joins the cluster of one core that passes with it (--assign first [default]: the\n"
+            "                           first in output order; best: the one with the best value) as a border, else it is noise.\n"
+            "                           Text: '#Cluster<TAB>measure<TAB>op<TAB>FLOAT<TAB>dbscan<TAB>N<TAB>first|best', then\n"
+            "                           name<TAB>cluster<TAB>representative<TAB>core|border|noise<TAB>degree per input, clusters\n"
+            "                           numbered from 0 by their first core, which represents them; noise has '-' for both;\n"
+            "                           -b: u64 n, u64 n_clusters, u32 labels[n], u32 degree[n], u8 kind[n] (0 noise, 1 border,\n"
+            "                           2 core): no input for --extend or --histogram-labels.  --stats composes.  Not with\n"
+            "                           --linkage complete|average.\n"
             "  --representatives FLOAT  emit greedy representatives at FLOAT instead of distances: walk the inputs in output order\n"
             "                           (largest file first by default, the order given with --avoid-sorting); an input that no\n"
             "                           earlier representative passes --threshold FLOAT's test with becomes a representative, every\n"
@@ -175,6 +186,8 @@ struct Opts {
     int linkage = -1;          // --linkage: -1 not given, else DSH_LINKAGE_* (complete / average: dsh_linkage_threshold)
     bool has_cluster = false;  // --cluster: the connected components of --threshold's graph (dsh_cluster_threshold)
     float cluster_t = 0.f;
+    bool has_min_pts = false;  // --min-pts N with --cluster: density clusters (dsh_dbscan_threshold)
+    uint32_t min_pts = 0;
     bool has_reps = false;  // --representatives: the greedy pass in output order over --threshold's graph (dsh_greedy_threshold)
     float reps_t = 0.f;
     int assign_mode = DSH_GREEDY_FIRST;  // --assign first|best (dsh_greedy_extend)
@@ -301,7 +314,7 @@ static float float_option(const char *flag, const char *arg)
     return v;
 }
 
-enum { OPT_PRESKETCHED = 1000, OPT_AVOID_SORT, OPT_DEVICE, OPT_NPERBATCH, OPT_NN, OPT_NGPUS, OPT_DEVICES, OPT_RCCL, OPT_THRESHOLD, OPT_CLUSTER, OPT_LINKAGE, OPT_REPS, OPT_ASSIGN, OPT_EXTEND, OPT_STATS, OPT_HISTOGRAM, OPT_HISTOGRAM_LABELS, OPT_MST, OPT_MST_CUTOFF, OPT_DENDROGRAM, OPT_PAIRS, OPT_MEASURES, OPT_GROUPS, OPT_UNSUPPORTED };
+enum { OPT_PRESKETCHED = 1000, OPT_AVOID_SORT, OPT_DEVICE, OPT_NPERBATCH, OPT_NN, OPT_NGPUS, OPT_DEVICES, OPT_RCCL, OPT_THRESHOLD, OPT_CLUSTER, OPT_LINKAGE, OPT_MIN_PTS, OPT_REPS, OPT_ASSIGN, OPT_EXTEND, OPT_STATS, OPT_HISTOGRAM, OPT_HISTOGRAM_LABELS, OPT_MST, OPT_MST_CUTOFF, OPT_DENDROGRAM, OPT_PAIRS, OPT_MEASURES, OPT_GROUPS, OPT_UNSUPPORTED };
 
 static Opts parse(int argc, char **argv, bool is_dist)
 {
@@ -328,7 +341,7 @@ static Opts parse(int argc, char **argv, bool is_dist)
         {"use-bloom-filter", no_argument, nullptr, OPT_UNSUPPORTED}, {"use-nthash", no_argument, nullptr, OPT_UNSUPPORTED},
         {"use-cyclic-hash", no_argument, nullptr, OPT_UNSUPPORTED}, {"countmin", no_argument, nullptr, OPT_UNSUPPORTED},
         {"nearest-neighbors", required_argument, nullptr, OPT_NN}, {"threshold", required_argument, nullptr, OPT_THRESHOLD},
-        {"cluster", required_argument, nullptr, OPT_CLUSTER}, {"linkage", required_argument, nullptr, OPT_LINKAGE}, {"representatives", required_argument, nullptr, OPT_REPS},
+        {"cluster", required_argument, nullptr, OPT_CLUSTER}, {"linkage", required_argument, nullptr, OPT_LINKAGE}, {"min-pts", required_argument, nullptr, OPT_MIN_PTS}, {"representatives", required_argument, nullptr, OPT_REPS},
         {"assign", required_argument, nullptr, OPT_ASSIGN}, {"extend", required_argument, nullptr, OPT_EXTEND},
         {"stats", no_argument, nullptr, OPT_STATS},
         {"histogram", required_argument, nullptr, OPT_HISTOGRAM}, {"histogram-labels", required_argument, nullptr, OPT_HISTOGRAM_LABELS},
@@ -404,6 +417,13 @@ static Opts parse(int argc, char **argv, bool is_dist)
                         : !std::strcmp(optarg, "average") ? DSH_LINKAGE_AVERAGE : -1;
             if (o.linkage < 0) die("--linkage takes single, complete or average, not '%s'.", optarg);
             break;
+        case OPT_MIN_PTS: {
+            char *end = nullptr;
+            const unsigned long long v = std::strtoull(optarg, &end, 10);
+            if (end == optarg || *end || *optarg == '-' || v < 1 || v > 0xFFFFFFFFull) die("--min-pts needs a count of at least 1, got '%s'", optarg);
+            o.min_pts = (uint32_t)v, o.has_min_pts = true;
+            break;
+        }
         case OPT_REPS: o.reps_t = float_option("--representatives", optarg), o.has_reps = true; break;
         case OPT_ASSIGN:
             if (!std::strcmp(optarg, "first")) o.assign_mode = DSH_GREEDY_FIRST;
@@ -1210,6 +1230,8 @@ static void refuse_conflicts(const Opts &o, bool by_seq)
     }
     if (o.linkage >= 0 && !o.has_cluster) die("--linkage goes with --cluster only.");
     if (o.linkage == DSH_LINKAGE_AVERAGE && o.result_type == DSH_SIZES) die("--linkage average does not go with --sizes: it judges values in (-2, 2).");
+    if (o.has_min_pts && !o.has_cluster) die("--min-pts goes with --cluster only.");
+    if (o.has_min_pts && o.linkage > DSH_LINKAGE_SINGLE) die("--min-pts does not go with --linkage complete or average: density clusters are components of cores.");
     if (o.has_reps) {  // (what --cluster refuses, and --cluster)
         if (o.has_cluster) die("--representatives does not go with --cluster: choose the representatives or the components.");
         if (o.has_threshold) die("--representatives does not go with --threshold: choose the representatives or the pairs.");
@@ -1246,7 +1268,7 @@ static void refuse_conflicts(const Opts &o, bool by_seq)
     if (o.has_mst_cutoff && !o.has_mst) die("--mst-cutoff goes with --mst only.");
     if (o.dendrogram && !o.has_mst) die("--dendrogram goes with --mst only.");
     if (!o.hist_labels_file.empty() && !o.has_hist) die("--histogram-labels goes with --histogram only.");
-    if (o.has_assign && !o.has_reps) die("--assign goes with --representatives only.");
+    if (o.has_assign && !o.has_reps && !o.has_min_pts) die("--assign goes with --representatives only.");
     if (o.has_stats && !o.has_cluster && !o.has_reps) die("--stats goes with --cluster or --representatives only.");
     if (o.has_stats && o.result_type == DSH_SIZES) die("--stats does not go with --sizes: set sizes have no mean or worst value inside a group.");
     if (!o.extend_file.empty()) {
@@ -1628,6 +1650,52 @@ static void emit_labelling(const DistRun &r, std::FILE *fp)
     }
 }
 
+// --cluster FLOAT --min-pts N: the density clusters of the pairs that pass (dsh_dbscan_threshold).  No pair leaves the device.
+// A label is its cluster's smallest CORE, which may come behind a border it labels: the clusters are numbered in a pass of
+// their own, by ascending label
+static void emit_dbscan(const DistRun &r, std::FILE *fp)
+{
+    const Opts &o = r.o;
+    const size_t n = r.n;
+    const std::vector<std::string> &names = o.inpaths;
+    std::vector<uint32_t> labels(std::max<size_t>(n, 1)), degree(std::max<size_t>(n, 1));
+    std::vector<uint8_t> kind(std::max<size_t>(n, 1));
+    uint64_t count = 0, noise = 0;
+    DSH(r.ctx, dsh_dbscan_threshold(r.ctx, o.estim, o.result_type, o.k, o.cluster_t, o.min_pts, o.assign_mode, labels.data(), kind.data(),
+                                    degree.data(), &count, &noise));
+    GroupStats gs;
+    if (o.has_stats) gs.compute(r.ctx, o, labels, n);
+    if (o.fmt == BINARY) {
+        const uint64_t hdr[2] = {(uint64_t)n, count};
+        if (std::fwrite(hdr, sizeof(uint64_t), 2, fp) != 2 || std::fwrite(labels.data(), sizeof(uint32_t), n, fp) != n ||
+            std::fwrite(degree.data(), sizeof(uint32_t), n, fp) != n || std::fwrite(kind.data(), sizeof(uint8_t), n, fp) != n)
+            die("Error writing to binary file");
+        if (o.has_stats) gs.write_binary(fp, n);
+        return;
+    }
+    std::fprintf(fp, "#Cluster\t%s\t%s\t%.6g\tdbscan\t%u\t%s\n", kMeasureNames[o.result_type], is_distance(o.result_type) ? "<=" : ">=",
+                 (double)o.cluster_t, o.min_pts, o.assign_mode == DSH_GREEDY_BEST ? "best" : "first");  // --threshold's number format
+    std::vector<uint32_t> index(std::max<size_t>(n, 1));
+    uint32_t next = 0;
+    for (size_t x = 0; x < n; ++x)
+        if (kind[x] == DSH_DBSCAN_CORE && labels[x] == x) index[x] = next++;
+    static const char *const kKinds[3] = {"noise", "border", "core"};
+    std::string s;
+    char num[64];
+    for (size_t x = 0; x < n; ++x) {
+        s = names[x];
+        if (kind[x] == DSH_DBSCAN_NOISE) s += "\t-\t-";
+        else {
+            s.append(num, (size_t)std::snprintf(num, sizeof num, "\t%u\t", index[labels[x]]));
+            s += names[labels[x]];
+        }
+        s.append(num, (size_t)std::snprintf(num, sizeof num, "\t%s\t%u", kKinds[kind[x] <= DSH_DBSCAN_CORE ? kind[x] : 0], degree[x]));
+        if (o.has_stats) gs.append_fields(s, x, names);
+        s += '\n';
+        std::fwrite(s.data(), 1, s.size(), fp);
+    }
+}
+
 // --mst: the minimum spanning tree of the pair values (dsh_mst), or with --dendrogram its merge table (dsh_mst_linkage).  No
 // pair leaves the device: n - 1 edges do
 static void emit_mst(const DistRun &r, std::FILE *fp)
@@ -1948,6 +2016,7 @@ static int dist_main(int argc, char **argv, bool by_seq = false)
     write_sizes(r, ofp);
 
     if (!o.pairs_file.empty()) emit_pairs(r, pairofp);
+    else if (o.has_cluster && o.has_min_pts) emit_dbscan(r, pairofp);
     else if (o.has_cluster || o.has_reps) emit_labelling(r, pairofp);
     else if (o.has_hist) emit_histogram(r, pairofp);
     else if (o.has_mst) emit_mst(r, pairofp);

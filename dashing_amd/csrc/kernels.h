@@ -297,6 +297,21 @@ hipError_t launch_mst_pick(hipStream_t st, const uint64_t *best_v, const uint32_
 hipError_t launch_mst_emit(hipStream_t st, const uint32_t *labels, const uint32_t *ckey, const uint64_t *cedge, uint64_t n, uint32_t *parent,
                            uint32_t cap, uint32_t *err, const MstEdges &e);
 
+// density clusters at a threshold (kernels_dbscan.hip, dbscan.hip): a band of triangle rows as launch_thr_count takes it
+constexpr uint32_t kDbSlab = 512;  // band rows a thread of k_db_deg_cols walks
+// walk 1: every passing value adds one to degree[] of its row and of its column (degree zeroed by the caller)
+hipError_t launch_db_degree(hipStream_t st, const float *vals, const ThrRows &g, float t, int descending, uint32_t *degree);
+// walk 2, degree[n] final: a passing value between two cores (degree + 1 >= min_pts) unites them in parent (cap, err: as
+// launch_cc_band); between a core c and a non-core b it offers (hi << 32 | ~c) to best[b] (zeroed by the caller) under a
+// maximum, hi = the value's key (assign_best) or 1
+hipError_t launch_db_band(hipStream_t st, const float *vals, const ThrRows &g, float t, int descending, const uint32_t *degree,
+                          uint32_t min_pts, int assign_best, uint32_t *parent, uint32_t cap, uint32_t *err, uint64_t *best);
+// labels[x]: a core's root, a border's core's root, a noise point itself; kind_out / degree_out where not null; *n_clusters +=
+// the cores that are their own label, *n_noise += the noise points (the caller zeroes both)
+hipError_t launch_db_labels(hipStream_t st, uint32_t *parent, uint64_t n, uint32_t cap, const uint32_t *degree, const uint64_t *best,
+                            uint32_t min_pts, uint32_t *labels, uint8_t *kind_out, uint32_t *degree_out, uint64_t *n_clusters,
+                            uint64_t *n_noise, uint32_t *err);
+
 // value histograms (kernels_hist.hip, hist.hip): a band of triangle or rectangle rows as launch_thr_count takes it, counted
 // into counts[planes][n_edges + 2] (device, 64-bit adds: the caller zeroes it) over the n_edges strictly increasing edges at
 // d_edges (device); class(v) = the edges that pass v as a threshold would, NaN = n_edges + 1.  labels == nullptr: one plane;

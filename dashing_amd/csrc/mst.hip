@@ -18,35 +18,12 @@ struct MstState {  // mst.state on the device
     unsigned long long roots;  // what the rounds' k_cc_labels count: not read
 };
 
-// where the values come from: the resident sketches, or a caller's triangle on the host
-struct MstSource {
-    const float *tri = nullptr;
-    int estim = 0, result_type = 0, k = 0;
-};
-
-// the band walk of bands.h over either source
+// where the values come from and the band walk over either source: bands.h
+using MstSource = BandSource;
 template <class F>
 int mst_walk(dsh_ctx *c, uint64_t n, const MstSource &s, F &&per_band)
 {
-    if (!s.tri) {
-        BandQuery bq;
-        bq.estim = s.estim, bq.result_type = s.result_type, bq.k = s.k;
-        bq.re = n;
-        return for_each_band(c, bq, per_band);
-    }
-    const uint64_t band_floats = std::max<uint64_t>(c->threshold_band_bytes / sizeof(float), 1);
-    for (uint64_t b0 = 0, b1; b0 < n; b0 = b1) {
-        b1 = plan::tri_band_end(n, b0, n, band_floats, kBandMaxRows);
-        const uint64_t span = dsh_tri_span(n, b0, b1);
-        if (!span) continue;
-        ThrRows g;
-        int rc = thr_geometry(c, 0, n, b0, b1, 0, 0, g);
-        if (rc) return rc;
-        HIPCHK(c, c->thr_vals.ensure(span * sizeof(float)));
-        HIPCHK(c, hipMemcpyAsync(c->thr_vals.ptr, s.tri + dsh_tri_span(n, 0, b0), span * sizeof(float), hipMemcpyHostToDevice, c->stream));
-        if ((rc = per_band(g, (const float *)c->thr_vals.ptr, span))) return rc;
-    }
-    return DSH_OK;
+    return for_each_source_band(c, n, s, per_band);
 }
 
 int mst_rounds(dsh_ctx *c, uint64_t n, const MstSource &s, int descending, float cutoff, uint64_t *count_out)

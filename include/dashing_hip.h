@@ -64,7 +64,8 @@ typedef struct dsh_ctx dsh_ctx;
  * dsh_upload_sketches_folded*, dsh_union_groups*, dsh_cluster_threshold, dsh_cluster_threshold_device, dsh_cluster_pairs,
  * dsh_cluster_csr, dsh_greedy_threshold, dsh_greedy_threshold_device, dsh_greedy_extend, dsh_greedy_extend_device,
  * dsh_group_stats, dsh_group_stats_device, dsh_dist_histogram, dsh_dist_histogram_device, dsh_dist_rect_histogram,
- * dsh_linkage_threshold, dsh_linkage_threshold_device, dsh_linkage_tri, dsh_mst, dsh_mst_tri, dsh_mst_linkage. */
+ * dsh_linkage_threshold, dsh_linkage_threshold_device, dsh_linkage_tri, dsh_mst, dsh_mst_tri, dsh_mst_linkage,
+ * dsh_dbscan_threshold, dsh_dbscan_threshold_device, dsh_dbscan_tri, dsh_degree_threshold, dsh_degree_threshold_device. */
 #define DSH_ABI_VERSION 7
 int dsh_abi_version(void);
 
@@ -533,6 +534,66 @@ int dsh_mst_tri(dsh_ctx *ctx, uint64_t n_nodes, const float *tri, int descending
                 float *val_out, uint64_t *n_edges, uint32_t *labels_out);
 int dsh_mst_linkage(uint64_t n_nodes, const uint32_t *lhs, const uint32_t *rhs, const float *val, uint64_t n_edges, uint32_t *za,
                     uint32_t *zb, float *zv, uint32_t *zsize);
+
+/* ---- density clusters at a threshold (DBSCAN) and the degrees of the threshold graph, on the device ---------
+ * Single linkage (dsh_cluster_threshold) chains: at a loose threshold one bridge input welds two groups into one component.
+ * DBSCAN keeps the components' cost and cuts the bridges: only inputs with enough neighbours carry a cluster.  What a client
+ * does today is bring the CSR of dsh_dist_threshold to the host (10^8 to 10^9 hits at 100 000 sketches) to count neighbours.
+ *   The graph G on the slots 0 .. n - 1: its edges are exactly the hits of dsh_dist_threshold(ctx, estim, result_type, k, 0, n,
+ *     threshold, ...) -- the same float32 values, the same predicate (v >= threshold for the similarity forms, v <= threshold for
+ *     the *_DIST forms, NaN never) and, for the asymmetric measures, the ONE orientation of the triangle, as in
+ *     dsh_cluster_threshold (dsh_dbscan_tri: the caller's tri[dsh_tri_index(n, min, max)] and `descending`).
+ *   degree[x] (uint32): the edges at x, whether x is their row or their column.
+ *   x is a CORE iff degree[x] + 1 >= min_pts, compared in 64 bits: the point counts itself, as in the DBSCAN paper and in
+ *     scikit-learn.  min_pts is at least 1.
+ *   Clusters: the connected components of G restricted to the edges between two cores; the label of a cluster is its smallest
+ *     core slot.
+ *   A non-core x with at least one core neighbour is a BORDER and takes the label of ONE core neighbour c:
+ *       DSH_GREEDY_FIRST: the smallest such c;
+ *       DSH_GREEDY_BEST:  the c with the best value v(c, x); values that are equal as float32 (-0.0 equal to +0.0) go to the
+ *                         smaller c.
+ *     A border is never a bridge: nothing is united through it.  Every other non-core is NOISE and labelled with itself.
+ *   Output: labels[x] (uint32) as above, with labels[labels[x]] == labels[x].  NOTE that a border's label may be LARGER than
+ *     its own slot (the label is the cluster's smallest CORE): the labels are group ids as dsh_group_stats accepts them, not
+ *     "the smallest member".  kind[x] (uint8, optional): DSH_DBSCAN_NOISE, DSH_DBSCAN_BORDER or DSH_DBSCAN_CORE.  degree[x]
+ *     (uint32, optional).  *n_clusters = the cores with labels[x] == x; *n_noise (optional) = the noise points.  A NULL optional
+ *     output is not written.  The result depends on no band size, launch geometry or order of arrival of atomics.
+ *   Consequences.  min_pts == 1: every slot is a core and labels, n_clusters equal dsh_cluster_threshold's byte for byte.
+ *     min_pts == 2: the labels still equal them (the singletons are noise, labelled with themselves) and n_clusters is the
+ *     components' count minus n_noise.  min_pts > n: everything is noise.  A non-core has at most min_pts - 2 edges.
+ *   dsh_dbscan_threshold          over the resident sketches; host outputs, [n] each.
+ *   dsh_dbscan_threshold_device   the three arrays are caller-owned DEVICE buffers; exactly n items of each are written.
+ *   dsh_dbscan_tri                the same for a caller's values (ANI, say): tri holds n_nodes (n_nodes - 1) / 2 float32 in host
+ *                                 memory in dsh_tri_index order; no sketches are needed, only the stream and scratch.
+ *   dsh_degree_threshold(_device) the degrees alone: how many inputs lie within the threshold of each input.
+ *   How: two walks over the band walk of dsh_cluster_threshold ("threshold_band_bytes").  Walk 1 counts the degrees with a number
+ *     of atomics that does not grow with the hits (one per 4096-value chunk of a row and one per column and slab of 512 rows that
+ *     saw a hit).  Walk 2 unites the two ends of a passing value in the union-find of dsh_cluster_threshold where both are
+ *     cores, and where exactly one is, offers it to the other end under a 64-bit maximum (value key, then the smaller core); a
+ *     non-core has at most min_pts - 2 edges, so these offers are bounded by n (min_pts - 2) whatever the threshold.  One more
+ *     launch writes labels, kinds and counts.  No hit is written, no host wait between bands, one wait at the end.
+ *   Cost: where the whole triangle is ONE band (10 000 sketches at the default 1 GiB) its values stay on the device between the
+ *     walks: one dense pass and two reads of the span.  Else walk 2 recomputes (dsh_dbscan_tri: uploads again) its bands and the
+ *     call costs about two dense passes; dsh_degree_threshold* always costs one.  Scratch: 13 bytes per slot beside the cluster
+ *     call's.  tools/bench_dbscan.py is the benchmark.
+ *   Synchronous, on the ctx stream.  The effects on cached state are exactly those of dsh_dist_threshold: a dense call before
+ *     and a dense call after give the same bytes.
+ *   Errors, before anything is enqueued, as dsh_cluster_threshold / dsh_greedy_extend: DSH_ESTATE without sketches (not
+ *     dsh_dbscan_tri); DSH_EINVAL for n > 2^32 - 1, for min_pts == 0, for an unknown assign_mode, for a NULL labels (or degrees, for
+ *     dsh_degree_threshold*) output with n > 0, and for a NULL tri with n_nodes >= 2.  n == 0 succeeds with zero counts.
+ *   Not built: a CSR / edge-list form, a rectangle, a multi-GPU form, a weighted degree, OPTICS / HDBSCAN, and keeping the hits
+ *     as a bit mask between the walks instead of recomputing the bands of a triangle of several bands. */
+#define DSH_DBSCAN_NOISE 0
+#define DSH_DBSCAN_BORDER 1
+#define DSH_DBSCAN_CORE 2
+int dsh_dbscan_threshold(dsh_ctx *ctx, int estim, int result_type, int k, float threshold, uint32_t min_pts, int assign_mode,
+                         uint32_t *labels_out, uint8_t *kind_out, uint32_t *degree_out, uint64_t *n_clusters, uint64_t *n_noise);
+int dsh_dbscan_threshold_device(dsh_ctx *ctx, int estim, int result_type, int k, float threshold, uint32_t min_pts, int assign_mode,
+                                void *d_labels, void *d_kind, void *d_degree, uint64_t *n_clusters, uint64_t *n_noise);
+int dsh_dbscan_tri(dsh_ctx *ctx, uint64_t n_nodes, const float *tri, int descending, float threshold, uint32_t min_pts, int assign_mode,
+                   uint32_t *labels_out, uint8_t *kind_out, uint32_t *degree_out, uint64_t *n_clusters, uint64_t *n_noise);
+int dsh_degree_threshold(dsh_ctx *ctx, int estim, int result_type, int k, float threshold, uint32_t *degree_out);
+int dsh_degree_threshold_device(dsh_ctx *ctx, int estim, int result_type, int k, float threshold, void *d_degree);
 
 /* ---- greedy representatives at a threshold: the greedy pass in slot order, on the device ---------------
  * Replaces what a dereplication client does with the hits of dsh_dist_threshold* when it wants REPRESENTATIVES rather than
