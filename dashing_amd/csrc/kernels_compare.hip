@@ -242,9 +242,11 @@ __global__ __launch_bounds__(64) void k_card_from_hist(const uint32_t *__restric
 // |list_i| x |list_j| / 2^p times per tail -- a sparse join instead of every pair walking a whole list.
 //   rec[b]  one RECORD per bucket, RK + 1 words (16 bytes with RK = 3 for p >= 13, 32 bytes with RK = 7 below, where a
 //           bucket holds ~4 entries): word 0 = entries in the bucket | first slot in ent[] << 16, then its first RK
-//           entries (0xFFFFFFFF = none).  A look-up is ONE gather; only a bucket with more than RK entries (14 % at C3,
-//           5 % at p = 10) sends the reader on to ent[] (round 3 read two bounds and then the entries: three dependent
-//           levels, 6x read amplification -- VERDICT r3 item 1b).
+//           entries (0xFFFFFFFF = none).  A look-up is ONE gather; only a bucket with more than RK entries sends the
+//           reader on to ent[] (round 3 read two bounds and then the entries: three dependent levels, 6x read
+//           amplification -- VERDICT r3 item 1b).  Few BUCKETS are that full -- 6.5 % of the looked-up ones at C3, 5 % at
+//           p = 10 -- but a wave looks 64 up at a time: 81 % of k_finalize's wave-rounds at C3 and 68 % at p = 10 hold
+//           one (tools/join_model.py, profiles/join1), so the wave reads the rest of such a bucket together.
 //   ent[]   all entries in bucket order (uint16 slots: a block holds at most 128 x 510 entries); an entry is
 //           (pos & (2^sh - 1)) << 13 | column within the block << 6 | value.
 // The kernel also leaves everything k_finalize needs per COLUMN in layout order, so that nothing there waits for the
@@ -1047,8 +1049,9 @@ hipError_t launch_pair_counts_mfma(hipStream_t st, int kc, int cum_bytes, const 
 //     (if Lp comes from the value minima instead, no register pair lies below it and the join finds nothing).
 // The shared positions are found through the column block's position index (k_build_colindex): lane e takes the row
 // sketch's e-th listed register and reads the RECORD of its position's bucket (one gather: count + the first RK
-// entries) -- |list_i| lookups per tile row instead of 128 list walks -- and applies what it finds to the owning lane's
-// histogram column with LDS atomics.  Exact and order-independent.  C(Lp) = number of low joins, so c[Lp] = C(Lp+1) -
+// entries) -- |list_i| lookups per tile row instead of 128 list walks; what the look-ups of a wave find is gathered in
+// the wave's queue and applied from there, one entry per lane, to the owning lanes' histogram columns with LDS atomics.
+// Exact and order-independent.  C(Lp) = number of low joins, so c[Lp] = C(Lp+1) -
 // C(Lp) and c[T] = m - |union above T| - C(T).
 // Loads (round 4, profiles/r4b: the join and the prologue were 54 % of a wave's life at p = 10, all of it dependent
 // global loads): every input of a block is addressed by the TILE alone -- the per-column side arrays are in layout
@@ -1062,6 +1065,8 @@ hipError_t launch_pair_counts_mfma(hipStream_t st, int kc, int cum_bytes, const 
 // parts): it never reads the arguments of the rectangle / square / sorted-output / nearest-neighbour forms, which
 // relieves the scalar registers (~70 dwords of arguments: the compiler parked the overflow in VGPR lanes -- 67
 // v_writelane + 105 v_readlane VALU instructions in the p <= 12 instance, profiles/r4f).
+constexpr uint32_t kJoinQ = 128;  // items of a wave's join queue (1 KiB per block: what 16 blocks per CU leave at C3)
+constexpr uint32_t kFinalizeLdsHead = (64 + 128 + 8 + 2 * kJoinQ) * 4;  // bytes in front of the histogram columns
 template <typename CT, int RK, bool TIMED, bool GENERAL>
 __device__ __forceinline__ void finalize_block(const FinalizeArgs &a)
 {
@@ -1073,7 +1078,8 @@ __device__ __forceinline__ void finalize_block(const FinalizeArgs &a)
     uint32_t *histA = reinterpret_cast<uint32_t *>(hs_raw);  // [64] row sketch's tail histogram above T
     uint32_t *corr = histA + 64;                              // [128] per column: upper-tail positions shared with the row sketch
     uint32_t *actm = corr + 128;                              // [4] lanes whose column is live (bit per lane) + naLive
-    CT *hs = reinterpret_cast<CT *>(hs_raw + (64 + 128 + 8) * 4);
+    uint32_t *joinq = actm + 8;                               // [2][kJoinQ] the join's work queue of either wave
+    CT *hs = reinterpret_cast<CT *>(hs_raw + kFinalizeLdsHead);
     constexpr uint32_t RW = (uint32_t)RK + 1u;  // words of a bucket record
     constexpr uint32_t kNone = 0xFFFFFFFFu;
     const int tid = threadIdx.x;
@@ -1283,12 +1289,22 @@ __device__ __forceinline__ void finalize_block(const FinalizeArgs &a)
         uint32_t *hw = reinterpret_cast<uint32_t *>(hs);
         // every lane of the block owns a pair (any tile off the diagonal of a full range): no per-entry ownership test
         const bool all_own = (actm[0] & actm[1] & actm[2] & actm[3]) == 0xFFFFFFFFu;
-        auto apply = [&](uint32_t x, int var, bool upr, uint32_t plow) {
-            const uint32_t jl = (x >> 6) & 127u;
-            const int vb = (int)(x & 63u);
-            // same position (groups of positions share a bucket only for p > 14), a live value on the column's side too,
-            // and a lane that owns a pair (diagonal tile, row range, padding)
-            if (x == kNone || (sh && (x >> 13) != plow) || !(upr ? vb > T : vb < Lp)) return;
+        // Gather, then apply.  A lane's own record is a poor unit of work for a wave: most buckets hold 0-2 entries, yet
+        // nearly every wave-round holds a lane whose bucket overflows its record, and the wave pays its longest lane
+        // (profiles/join1: 36 wave-level applications per tile row for 250 entries, a tenth of the lane slots busy).  So
+        // what the records hold goes into a queue of the WAVE first -- one 32-bit item per entry: column << 6 | value
+        // (the entry's low 13 bits), the row value << 13, upper tail << 21; an entry of another position of the group
+        // (p > 14) is dropped here -- with slots from a ballot, not from an LDS atomic per item, and the lanes then walk
+        // the queue one item each.  Filled and drained by the wave alone: no barrier, the LDS serves a wave in order.
+        uint32_t *jq = joinq + (uint32_t)(tid >> 6) * kJoinQ;
+        const uint32_t lane = (uint32_t)tid & 63u;
+        uint32_t qn = 0;  // items queued (uniform)
+        auto apply = [&](uint32_t it) {
+            const uint32_t jl = (it >> 6) & 127u;
+            const int vb = (int)(it & 63u), var = (int)((it >> 13) & 0xFFu);
+            const bool upr = (it >> 21) & 1u;
+            // a live value on the column's side too, and a lane that owns a pair (diagonal tile, row range, padding)
+            if (!(upr ? vb > T : vb < Lp)) return;
             if (!all_own && !((actm[jl >> 5] >> (jl & 31u)) & 1u)) return;
             // upper tail: the position was counted in both tail histograms, take the smaller value out again;
             // lower tail: both registers are below the dense range, max(a_t, b_t) is the larger one
@@ -1303,25 +1319,65 @@ __device__ __forceinline__ void finalize_block(const FinalizeArgs &a)
                 atomicAdd(w, one);
             }
         };
+        auto drain = [&]() {
+            for (uint32_t b = 0; b < qn; b += 64u)
+                if (b + lane < qn) apply(jq[b + lane]);
+            qn = 0;
+        };
+        // entry x of a bucket that a row entry with header h (row value << 13 | upper << 21 | position's low bits << 22)
+        // looked up: queued if it is an entry of the same position.  At most 64 items per call, so after a drain they fit.
+        auto push = [&](uint32_t x, uint32_t h) {
+            const bool ok = x != kNone && (!sh || (x >> 13) == (h >> 22));
+            const unsigned long long mk = __ballot(ok);
+            const uint32_t n = (uint32_t)__popcll(mk);
+            if (qn + n > kJoinQ) drain();  // (uniform)
+            if (ok) jq[qn + __builtin_amdgcn_mbcnt_hi((uint32_t)(mk >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mk, 0u))] = (x & 0x1FFFu) | (h & 0x3FFFFFu);
+            qn += n;
+        };
 #pragma unroll
         for (int r = 0; r < kR; ++r) {
             if (r >= nr) break;
             if (__ballot(rc[r].y != kNone) == 0) continue;  // no lane of this wave found anything (a short list: wave 1)
-            const int va = (int)(le[r] & 0xFFu);
-            const bool up = va > T;
-            const uint32_t plow = (le[r] >> 8) & ((1u << sh) - 1u);
-            apply(rc[r].y, va, up, plow);
-            apply(rc[r].z, va, up, plow);
-            apply(rc[r].w, va, up, plow);
+            const uint32_t va = le[r] & 0xFFu;
+            const uint32_t hdr = (va << 13) | ((int)va > T ? 1u << 21 : 0u) | (((le[r] >> 8) & ((1u << sh) - 1u)) << 22);
+            push(rc[r].y, hdr);
+            push(rc[r].z, hdr);
+            push(rc[r].w, hdr);
             if constexpr (RK > 3) {
-                apply(rc2[r].x, va, up, plow);
-                apply(rc2[r].y, va, up, plow);
-                apply(rc2[r].z, va, up, plow);
-                apply(rc2[r].w, va, up, plow);
+                push(rc2[r].x, hdr);
+                push(rc2[r].y, hdr);
+                push(rc2[r].z, hdr);
+                push(rc2[r].w, hdr);
             }
-            const uint32_t cnt = rc[r].x & 0xFFFFu, q0 = rc[r].x >> 16;
-            for (uint32_t q = (uint32_t)RK; q < cnt; ++q) apply(bent[q0 + q], va, up, plow);  // a crowded bucket (rare)
+            // buckets with more than RK entries (few per lane, but nearly every wave-round has some): the wave takes them
+            // one at a time and reads the rest of the bucket from ent[] together, lane q its q-th further entry -- the
+            // next bucket's read is in flight while this one's entries are queued
+            unsigned long long ov = __ballot((rc[r].x & 0xFFFFu) > (uint32_t)RK);
+            if (ov == 0) continue;
+            auto rest = [&](uint32_t w0, uint32_t b) -> uint32_t {  // entry RK + b + lane of the bucket with record word w0
+                return b + lane < (w0 & 0xFFFFu) - (uint32_t)RK ? bent[(w0 >> 16) + (uint32_t)RK + b + lane] : kNone;
+            };
+            int l = __ffsll((long long)ov) - 1;
+            uint32_t w0 = (uint32_t)__builtin_amdgcn_readlane((int)rc[r].x, l), h = (uint32_t)__builtin_amdgcn_readlane((int)hdr, l);
+            uint32_t x = rest(w0, 0u);
+            for (;;) {
+                ov &= ov - 1ull;
+                uint32_t w0n = 0u, hn = 0u, xn = kNone;
+                if (ov) {
+                    l = __ffsll((long long)ov) - 1;
+                    w0n = (uint32_t)__builtin_amdgcn_readlane((int)rc[r].x, l);
+                    hn = (uint32_t)__builtin_amdgcn_readlane((int)hdr, l);
+                    xn = rest(w0n, 0u);
+                }
+                push(x, h);
+                for (uint32_t b = 64u; b < (w0 & 0xFFFFu) - (uint32_t)RK; b += 64u) push(rest(w0, b), h);  // (> 64 + RK entries)
+                if (ov == 0) break;
+                w0 = w0n;
+                h = hn;
+                x = xn;
+            }
         }
+        drain();
     }
     __syncthreads();
     if constexpr (TIMED) tph[3] = __builtin_readcyclecounter();
@@ -2004,7 +2060,7 @@ hipError_t launch_finalize(hipStream_t st, const FinalizeLaunch &f)
     if (f.nslots == 0) return hipSuccess;
     FinalizeArgs a = f.a;
     a.ntiles = (uint32_t)(f.nslots / ((uint64_t)kTile * kTile));
-    const size_t lds = (64 + 128 + 8) * sizeof(uint32_t) + (size_t)a.hist_bins * 128 * (f.cum_bytes == 2 ? 2 : 4);
+    const size_t lds = kFinalizeLdsHead + (size_t)a.hist_bins * 128 * (f.cum_bytes == 2 ? 2 : 4);
     const uint32_t blocks = (a.ntiles + 7u) / 8u * 8u * 128u;  // (whole groups of 8 tiles: a tile's 128 rows on one XCD)
     const bool timed = a.phase_cyc != nullptr;  // profiling only
     const bool general = a.rect || a.square || a.sorted_out || a.knn;
