@@ -83,6 +83,8 @@ int dsh_preload(int device, unsigned what)
     if ((what & DSH_PRELOAD_SKETCH) && e == hipSuccess) e = preload_fastx_kernels();
     if ((what & DSH_PRELOAD_COMPARE) && e == hipSuccess) e = preload_compare_kernels();
     if ((what & DSH_PRELOAD_COMPARE) && e == hipSuccess) e = preload_hist_kernels();
+    if ((what & DSH_PRELOAD_COMPARE) && e == hipSuccess) e = preload_knn_kernels();
+    if ((what & DSH_PRELOAD_COMPARE) && e == hipSuccess) e = preload_exchange_kernels();
     if (e != hipSuccess) (void)hipGetLastError();
     return e == hipSuccess ? DSH_OK : DSH_EIO;
 }

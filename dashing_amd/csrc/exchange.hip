@@ -15,6 +15,117 @@
 
 #include "ctx.h"
 
+// ---- the kernels of the destination side: row placement of row-sorted parts, the older shard scheme's un-permute
+namespace dsh {
+
+// row-sorted parts (plan.h): the rows at the positions [pos0, pos1) of a source rank's key order, lying at rowoff[s] of its
+// buffer, go to their places in dashing's packed triangle (row r starts at r (2n - r - 1) / 2 and holds n - 1 - r values).
+// A row is contiguous on both sides; a block copies kPlaceChunk values of it (blockIdx.y = the chunk: the longest rows
+// of a part -- 40 KB at n = 10 000 -- would otherwise keep 128 blocks busy while 128 CUs idle).
+constexpr uint32_t kPlaceChunk = 4096;
+__device__ __forceinline__ void place_row_chunk(const float *__restrict__ src, float *__restrict__ out, const uint32_t *__restrict__ order,
+                                                const uint64_t *__restrict__ rowoff, uint64_t s, uint64_t n)
+{
+    const uint64_t r = order[s], len = n - 1 - r;
+    const uint64_t x0 = (uint64_t)blockIdx.y * kPlaceChunk;
+    if (x0 >= len) return;
+    const uint64_t x1 = x0 + kPlaceChunk < len ? x0 + kPlaceChunk : len;
+    const float *from = src + rowoff[s];
+    float *to = out + r * (2 * n - r - 1) / 2;
+    for (uint64_t x = x0 + threadIdx.x; x < x1; x += 256) to[x] = from[x];
+}
+
+__global__ __launch_bounds__(256) void k_row_place(const float *__restrict__ src, float *__restrict__ out,
+                                                    const uint32_t *__restrict__ order, const uint64_t *__restrict__ rowoff,
+                                                    uint64_t pos0, uint64_t n)
+{
+    place_row_chunk(src, out, order, rowoff, pos0 + blockIdx.x, n);
+}
+
+hipError_t launch_row_place(hipStream_t st, const float *src, float *out, const uint32_t *order, const uint64_t *rowoff,
+                            uint64_t pos0, uint64_t pos1, uint64_t n)
+{
+    if (pos1 <= pos0 || n < 2) return hipSuccess;
+    hipLaunchKernelGGL(k_row_place, dim3((uint32_t)(pos1 - pos0), (uint32_t)((n - 1 + kPlaceChunk - 1) / kPlaceChunk)), dim3(256), 0, st,
+                       src, out, order, rowoff, pos0, n);
+    return hipGetLastError();
+}
+
+// one round of the exchange at the destination: the parts of ALL row-sorted sources that arrived in it, in ONE launch
+// (a launch per source left seven small kernels in a row behind the last transfer of an 8-rank step).  Entry e covers
+// the blocks [row0, row0 + nrows) of the grid's x.
+__global__ __launch_bounds__(256) void k_rows_place(const PlaceEnt *__restrict__ ent, uint32_t nent, float *__restrict__ out, uint64_t n)
+{
+    uint32_t e = 0;
+    while (e + 1 < nent && ent[e + 1].row0 <= blockIdx.x) ++e;
+    const PlaceEnt E = ent[e];
+    place_row_chunk(E.src, out, E.order, E.rowoff, E.pos0 + (blockIdx.x - E.row0), n);
+}
+
+hipError_t launch_rows_place(hipStream_t st, const PlaceEnt *ent, uint32_t nent, uint32_t total_rows, float *out, uint64_t n)
+{
+    if (!nent || !total_rows || n < 2) return hipSuccess;
+    hipLaunchKernelGGL(k_rows_place, dim3(total_rows, (uint32_t)((n - 1 + kPlaceChunk - 1) / kPlaceChunk)), dim3(256), 0, st, ent, nent, out, n);
+    return hipGetLastError();
+}
+
+
+// same mapping driven from the destination: one block per ORIGINAL row a, coalesced writes of
+// row a of the output, gathered reads (inv = inverse of perm)
+__global__ __launch_bounds__(256) void k_unpermute_gather(const float *__restrict__ in,
+                                                           const uint32_t *__restrict__ inv, uint64_t n,
+                                                           float *__restrict__ out)
+{
+    const uint64_t a = blockIdx.x;
+    const uint64_t sa = inv[a];
+    float *row = out + a * (2 * n - a - 1) / 2 - (a + 1);
+    for (uint64_t b = a + 1 + threadIdx.x; b < n; b += 256) {
+        const uint64_t sb = inv[b];
+        const uint64_t lo = sa < sb ? sa : sb, hi = sa < sb ? sb : sa;
+        row[b] = in[lo * (2 * n - lo - 1) / 2 + hi - (lo + 1)];
+    }
+}
+
+// as k_unpermute_gather, but the spans of the shards sit at a fixed stride in `in` (the padded blocks an
+// RCCL gather delivers): rowdelta[sorted row / 128] = shard * stride - span_off[shard]
+__global__ __launch_bounds__(256) void k_unpermute_staged(const float *__restrict__ in,
+                                                           const uint32_t *__restrict__ inv,
+                                                           const int64_t *__restrict__ rowdelta,
+                                                           uint64_t n, float *__restrict__ out)
+{
+    const uint64_t a = blockIdx.x;
+    const uint64_t sa = inv[a];
+    float *row = out + a * (2 * n - a - 1) / 2 - (a + 1);
+    for (uint64_t b = a + 1 + threadIdx.x; b < n; b += 256) {
+        const uint64_t sb = inv[b];
+        const uint64_t lo = sa < sb ? sa : sb, hi = sa < sb ? sb : sa;
+        row[b] = in[(int64_t)(lo * (2 * n - lo - 1) / 2 + hi - (lo + 1)) + rowdelta[lo / kTile]];
+    }
+}
+
+hipError_t launch_unpermute_staged(hipStream_t st, const float *in, const uint32_t *inv,
+                                   const int64_t *rowdelta, uint64_t n, float *out)
+{
+    if (n < 2) return hipSuccess;
+    hipLaunchKernelGGL(k_unpermute_staged, dim3((uint32_t)(n - 1)), dim3(256), 0, st, in, inv, rowdelta, n, out);
+    return hipGetLastError();
+}
+
+hipError_t launch_unpermute(hipStream_t st, const float *in, const uint32_t *inv, uint64_t n, float *out)
+{
+    if (n < 2) return hipSuccess;
+    hipLaunchKernelGGL(k_unpermute_gather, dim3((uint32_t)(n - 1)), dim3(256), 0, st, in, inv, n, out);
+    return hipGetLastError();
+}
+
+hipError_t preload_exchange_kernels()
+{
+    hipFuncAttributes fa;
+    return hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(k_row_place));
+}
+
+}  // namespace dsh
+
 using namespace dsh;
 
 namespace {

@@ -143,6 +143,7 @@ struct UploadSegs {
 };
 hipError_t launch_upload_segs(hipStream_t st, const UploadSegs &u, uint32_t nseg);
 hipError_t launch_wall_stamp(hipStream_t st, unsigned long long *out);
+// ---- exchange.hip: row placement at the destination of an exchange, the older shard scheme's un-permute
 // (k_rows_place) the rows of one source's part in a round of the exchange: positions [pos0, pos0 + nrows) of its key order
 struct PlaceEnt {
     const float *src;         // the source's staged buffer
@@ -160,11 +161,12 @@ hipError_t launch_unpermute_staged(hipStream_t st, const float *in, const uint32
 // destination-driven (coalesced writes, gathered reads through inv, the inverse of perm)
 hipError_t launch_unpermute(hipStream_t st, const float *in, const uint32_t *inv, uint64_t n, float *out);
 
+// ---- knn.hip: nearest-neighbour selection (k_topk: one pass over a matrix of values)
 hipError_t launch_topk(hipStream_t st, const float *vals, uint64_t rows, uint64_t ncols,
                        uint64_t row0, uint64_t col0, int descending, uint32_t nn,
                        int exclude_self, uint32_t *idx_out, float *val_out);
 
-// band-wise nearest neighbours (no n x n matrix): running lists idx/val[n][nn] by sketch index
+// band-wise nearest neighbours (no n x n matrix; k_topk_merge, k_fill_knn_state): running lists idx/val[n][nn] by sketch index
 hipError_t launch_knn_state_init(hipStream_t st, uint32_t *idx, float *val, uint64_t cnt, int descending);
 hipError_t launch_topk_merge(hipStream_t st, const float *vals, uint64_t ld, int mode, uint64_t b0, uint64_t rows,
                              uint64_t ncols, const uint32_t *perm, int descending, uint32_t nn, uint32_t *st_idx,
@@ -409,7 +411,9 @@ hipError_t launch_fastx_decode(hipStream_t st, const uint8_t *raw, const FastxCh
 
 // dsh_preload: load the code objects of the kernel translation units now (else: at the first launch from each)
 hipError_t preload_compare_kernels();
-hipError_t preload_hist_kernels();  // (part of the compare set)
+hipError_t preload_hist_kernels();      // (part of the compare set)
+hipError_t preload_knn_kernels();       // (part of the compare set: knn.hip)
+hipError_t preload_exchange_kernels();  // (part of the compare set: exchange.hip)
 hipError_t preload_fastx_kernels();
 hipError_t preload_sketch_kernels();
 

@@ -29,7 +29,10 @@
 //                     lane owns an 8x8 block of pairs; writes C(v) per pair.  (k_pair_counts: the free-running form, p < 9)
 //   k_finalize        one lane per pair: C(v) differences + the two tail joins -> histogram (LDS column) -> estimator -> J
 //                     -> Mash transform -> float at the packed index
-//   k_topk(_merge)    nearest neighbours;  k_unpermute*  the older shard scheme;  k_upload  in-order list uploads
+//   k_finalize_signal the plain triangle's instance that announces the parts of a call from inside the launch
+//   k_upload(_segs)   in-order list uploads;  k_wall_stamp  the device's wall clock
+// (the nearest-neighbour selection kernels live in knn.hip, the exchange's row placement and the older shard scheme's
+// un-permute in exchange.hip)
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -1065,35 +1068,191 @@ hipError_t launch_pair_counts_mfma(hipStream_t st, int kc, int cum_bytes, const 
 // parts): it never reads the arguments of the rectangle / square / sorted-output / nearest-neighbour forms, which
 // relieves the scalar registers (~70 dwords of arguments: the compiler parked the overflow in VGPR lanes -- 67
 // v_writelane + 105 v_readlane VALU instructions in the p <= 12 instance, profiles/r4f).
+// Structure: the LDS head (FinalizeLds), the block -> (tile, row) rule, the join's bit layout (JoinWord), the stop
+// exits' store and the join are described once, below; finalize_block holds the other phases in the order above.  They
+// stay in its body on purpose (profiles/fin_phases): the compiler optimises a callee on its own -- unrolled loops and
+// all -- before it inlines it, and each of them tried as a function of its own (row list, lane inputs, ownership,
+// dense bins, records, tail bins, closing, estimator and stores, report; results by reference and by value) left
+// instances with other instruction counts or code length than the parent's.  The pieces below compile to the
+// parent's machine code, instruction for instruction.
 constexpr uint32_t kJoinQ = 128;  // items of a wave's join queue (1 KiB per block: what 16 blocks per CU leave at C3)
-constexpr uint32_t kFinalizeLdsHead = (64 + 128 + 8 + 2 * kJoinQ) * 4;  // bytes in front of the histogram columns
+constexpr uint32_t kNone = 0xFFFFFFFFu;  // an unused slot: of a row of rl, of a bucket record, of a read past a bucket's end
+constexpr int kCvBatch = 16;             // planes whose C(v) travel with the first round trip
+// rounds of 128 row entries a block can meet (the wide records are only used with lists of <= 256 entries)
+template <int RK>
+constexpr int kListRounds = RK > 3 ? 2 : (int)(kListCap / 128);
+
+// The head of a block's dynamic LDS; the histogram columns follow it (CT[hist_bins][128]: bin x of lane t's column at
+// (x - vlo) * 128 + t).  The kernel takes its pointers from here, launch_finalize the head's size.
+struct FinalizeLds {
+    uint32_t histA[64];         // row sketch's tail histogram above T
+    uint32_t corr[128];         // per column: upper-tail positions shared with the row sketch
+    uint32_t actm[8];           // [0..3] lanes whose column is live (bit per lane); [4], [5] the waves' shares of naLive
+    uint32_t joinq[2][kJoinQ];  // the join's work queue of either wave
+};
+
+// block -> (tile, row of the tile): consecutive blocks go to consecutive XCDs (block b runs on XCD b % 8: observed
+// dispatch behaviour, speed only), so block b takes row (b / 8) % 128 of tile (b / 1024) * 8 + b % 8: the 128 rows of a
+// tile run on ONE XCD and its column block's position index, tail histograms and keys are fetched into that XCD's L2
+// once instead of into all eight.  (The grid is rounded up to whole groups of 8 tiles: tidx may be >= a.ntiles.)
+struct FinalizeRow {
+    uint32_t tidx, trow;
+};
+__device__ __forceinline__ FinalizeRow finalize_row_of_block()
+{
+    const uint32_t kq = blockIdx.x >> 3;
+    return {((kq >> 7) << 3) + (blockIdx.x & 7u), kq & 127u};
+}
+
+// The join's 32-bit words.  An ENTRY of the position index: the column's value | column << 6 | (p > 14) the position's
+// low bits << 13.  The HEADER of a row entry's look-up: row value << 13 | upper tail << 21 | the position's low bits
+// << 22.  A queue ITEM: the entry's low 13 bits | the header's low 22 -- column value, column, row value, tail.
+struct JoinWord {
+    enum : uint32_t { kColShift = 6, kRowValShift = 13, kUpperShift = 21, kGroupShift = 22 };
+    // of a row entry (position << 8 | value) in a tile with the threshold T, 1 << sh positions to a bucket
+    static __device__ __forceinline__ uint32_t header(uint32_t row_entry, int T, uint32_t sh)
+    {
+        const uint32_t va = row_entry & 0xFFu;
+        return (va << kRowValShift) | ((int)va > T ? 1u << kUpperShift : 0u) | (((row_entry >> 8) & ((1u << sh) - 1u)) << kGroupShift);
+    }
+    static __device__ __forceinline__ bool same_position(uint32_t entry, uint32_t hdr) { return (entry >> kRowValShift) == (hdr >> kGroupShift); }
+    static __device__ __forceinline__ uint32_t item(uint32_t entry, uint32_t hdr)
+    {
+        return (entry & ((1u << kRowValShift) - 1u)) | (hdr & ((1u << kGroupShift) - 1u));
+    }
+    static __device__ __forceinline__ int col_val(uint32_t it) { return (int)(it & ((1u << kColShift) - 1u)); }
+    static __device__ __forceinline__ uint32_t col(uint32_t it) { return (it >> kColShift) & 127u; }
+    static __device__ __forceinline__ int row_val(uint32_t it) { return (int)((it >> kRowValShift) & 0xFFu); }
+    static __device__ __forceinline__ bool upper(uint32_t it) { return (it >> kUpperShift) & 1u; }
+};
+
+// profiling only (option "finalize_stop" = 1..4): the store with which the kernel leaves after a phase -- the owning
+// lanes write a value that depends on what the phase computed.  out_index: where the pair's value goes.
+template <typename Index>
+__device__ __forceinline__ void stop_store(const FinalizeArgs &a, bool active, const Index &out_index, float v)
+{
+    const FinalizeArgs *L = &a;
+    if (active) L->out[out_index(L)] = v;
+}
+
+// ---- the join: what the records hold is applied to the owning lanes' histogram columns (le: the row entries, rc / rc2:
+// their buckets' records, bent: the column block's entries in bucket order, 1 << sh positions to a bucket)
+template <typename CT, int RK, int kR>
+__device__ __forceinline__ void join_tails(FinalizeLds &lds, CT *hs, int tid, int T, int Lp, int vlo, uint32_t sh, const uint32_t *bent, int nr,
+                                           const uint32_t (&le)[kR], const uint4 (&rc)[kR], const uint4 (&rc2)[RK > 3 ? kR : 1])
+{
+    uint32_t *corr = lds.corr, *actm = lds.actm;
+    uint32_t *hw = reinterpret_cast<uint32_t *>(hs);
+    // every lane of the block owns a pair (any tile off the diagonal of a full range): no per-entry ownership test
+    const bool all_own = (actm[0] & actm[1] & actm[2] & actm[3]) == 0xFFFFFFFFu;
+    // Gather, then apply.  A lane's own record is a poor unit of work for a wave: most buckets hold 0-2 entries, yet
+    // nearly every wave-round holds a lane whose bucket overflows its record, and the wave pays its longest lane
+    // (profiles/join1: 36 wave-level applications per tile row for 250 entries, a tenth of the lane slots busy).  So
+    // what the records hold goes into a queue of the WAVE first -- one 32-bit item per entry (JoinWord); an entry of
+    // another position of the group (p > 14) is dropped here -- with slots from a ballot, not from an LDS atomic per item, and the lanes then walk
+    // the queue one item each.  Filled and drained by the wave alone: no barrier, the LDS serves a wave in order.
+    uint32_t *jq = lds.joinq[0] + (uint32_t)(tid >> 6) * kJoinQ;
+    const uint32_t lane = (uint32_t)tid & 63u;
+    uint32_t qn = 0;  // items queued (uniform)
+    auto apply = [&](uint32_t it) {
+        const uint32_t jl = JoinWord::col(it);
+        const int vb = JoinWord::col_val(it), var = JoinWord::row_val(it);
+        const bool upr = JoinWord::upper(it);
+        // a live value on the column's side too, and a lane that owns a pair (diagonal tile, row range, padding)
+        if (!(upr ? vb > T : vb < Lp)) return;
+        if (!all_own && !((actm[jl >> 5] >> (jl & 31u)) & 1u)) return;
+        // upper tail: the position was counted in both tail histograms, take the smaller value out again;
+        // lower tail: both registers are below the dense range, max(a_t, b_t) is the larger one
+        const int bin = upr ? (var < vb ? var : vb) : (var > vb ? var : vb);
+        const uint32_t cell = (uint32_t)(bin - vlo) * 128u + jl;
+        const uint32_t one = sizeof(CT) == 2 ? 1u << (16u * (cell & 1u)) : 1u;
+        uint32_t *w = &hw[sizeof(CT) == 2 ? cell >> 1 : cell];
+        if (upr) {
+            atomicAdd(&corr[jl], 1u);
+            atomicSub(w, one);  // (the 16-bit half holds >= 1: no borrow into its neighbour)
+        } else {
+            atomicAdd(w, one);
+        }
+    };
+    auto drain = [&]() {
+        for (uint32_t b = 0; b < qn; b += 64u)
+            if (b + lane < qn) apply(jq[b + lane]);
+        qn = 0;
+    };
+    // entry x of a bucket that a row entry with header h looked up: queued if it is an entry of the same position.  At most 64 items per call, so after a drain they fit.
+    auto push = [&](uint32_t x, uint32_t h) {
+        const bool ok = x != kNone && (!sh || JoinWord::same_position(x, h));
+        const unsigned long long mk = __ballot(ok);
+        const uint32_t n = (uint32_t)__popcll(mk);
+        if (qn + n > kJoinQ) drain();  // (uniform)
+        if (ok) jq[qn + __builtin_amdgcn_mbcnt_hi((uint32_t)(mk >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mk, 0u))] = JoinWord::item(x, h);
+        qn += n;
+    };
+#pragma unroll
+    for (int r = 0; r < kR; ++r) {
+        if (r >= nr) break;
+        if (__ballot(rc[r].y != kNone) == 0) continue;  // no lane of this wave found anything (a short list: wave 1)
+        const uint32_t hdr = JoinWord::header(le[r], T, sh);
+        push(rc[r].y, hdr);
+        push(rc[r].z, hdr);
+        push(rc[r].w, hdr);
+        if constexpr (RK > 3) {
+            push(rc2[r].x, hdr);
+            push(rc2[r].y, hdr);
+            push(rc2[r].z, hdr);
+            push(rc2[r].w, hdr);
+        }
+        // buckets with more than RK entries (few per lane, but nearly every wave-round has some): the wave takes them
+        // one at a time and reads the rest of the bucket from ent[] together, lane q its q-th further entry -- the
+        // next bucket's read is in flight while this one's entries are queued
+        unsigned long long ov = __ballot((rc[r].x & 0xFFFFu) > (uint32_t)RK);
+        if (ov == 0) continue;
+        auto rest = [&](uint32_t w0, uint32_t b) -> uint32_t {  // entry RK + b + lane of the bucket with record word w0
+            return b + lane < (w0 & 0xFFFFu) - (uint32_t)RK ? bent[(w0 >> 16) + (uint32_t)RK + b + lane] : kNone;
+        };
+        int l = __ffsll((long long)ov) - 1;
+        uint32_t w0 = (uint32_t)__builtin_amdgcn_readlane((int)rc[r].x, l), h = (uint32_t)__builtin_amdgcn_readlane((int)hdr, l);
+        uint32_t x = rest(w0, 0u);
+        for (;;) {
+            ov &= ov - 1ull;
+            uint32_t w0n = 0u, hn = 0u, xn = kNone;
+            if (ov) {
+                l = __ffsll((long long)ov) - 1;
+                w0n = (uint32_t)__builtin_amdgcn_readlane((int)rc[r].x, l);
+                hn = (uint32_t)__builtin_amdgcn_readlane((int)hdr, l);
+                xn = rest(w0n, 0u);
+            }
+            push(x, h);
+            for (uint32_t b = 64u; b < (w0 & 0xFFFFu) - (uint32_t)RK; b += 64u) push(rest(w0, b), h);  // (> 64 + RK entries)
+            if (ov == 0) break;
+            w0 = w0n;
+            h = hn;
+            x = xn;
+        }
+    }
+    drain();
+}
+
 template <typename CT, int RK, bool TIMED, bool GENERAL>
 __device__ __forceinline__ void finalize_block(const FinalizeArgs &a)
 {
     unsigned long long tph[7] = {0, 0, 0, 0, 0, 0, 0};
     if constexpr (TIMED) tph[0] = __builtin_readcyclecounter();
+    extern __shared__ __attribute__((aligned(16))) unsigned char hs_raw[];
+    FinalizeLds &lds = *reinterpret_cast<FinalizeLds *>(hs_raw);
+    uint32_t *histA = lds.histA, *corr = lds.corr, *actm = lds.actm;
     // histogram columns hold counts <= 2^p: CT (uint16 when p <= 15) halves the LDS footprint and
     // doubles the resident waves of this latency-sensitive kernel
-    extern __shared__ __attribute__((aligned(16))) unsigned char hs_raw[];
-    uint32_t *histA = reinterpret_cast<uint32_t *>(hs_raw);  // [64] row sketch's tail histogram above T
-    uint32_t *corr = histA + 64;                              // [128] per column: upper-tail positions shared with the row sketch
-    uint32_t *actm = corr + 128;                              // [4] lanes whose column is live (bit per lane) + naLive
-    uint32_t *joinq = actm + 8;                               // [2][kJoinQ] the join's work queue of either wave
-    CT *hs = reinterpret_cast<CT *>(hs_raw + kFinalizeLdsHead);
+    CT *hs = reinterpret_cast<CT *>(hs_raw + sizeof(FinalizeLds));
     constexpr uint32_t RW = (uint32_t)RK + 1u;  // words of a bucket record
-    constexpr uint32_t kNone = 0xFFFFFFFFu;
     const int tid = threadIdx.x;
     // one block = one row of a 128 x 128 tile: everything derived from the tile is block-uniform and is
     // written so that the compiler sees it (scalar loads, SGPR compares, scalar branches)
     // k_finalize's tile descriptor (its own list, row-major per segment -- run_pairs): {row block, column block, plane
     // begin | plane end << 8 | smallest << 16 | largest << 24 register value of the two blocks' sketches, index of the
     // tile's C(v) block in the band}: the histogram columns of a block only span the values its own sketches can hold
-    // block -> (tile, row of the tile): consecutive blocks go to consecutive XCDs (block b runs on XCD b % 8: observed
-    // dispatch behaviour, speed only), so block b takes row (b / 8) % 128 of tile (b / 1024) * 8 + b % 8: the 128 rows of a
-    // tile run on ONE XCD and its column block's position index, tail histograms and keys are fetched into that XCD's L2
-    // once instead of into all eight.
-    const uint32_t kq = blockIdx.x >> 3;
-    const uint32_t tidx = ((kq >> 7) << 3) + (blockIdx.x & 7u), trow = kq & 127u;
+    const FinalizeRow row = finalize_row_of_block();
+    const uint32_t tidx = row.tidx, trow = row.trow;
     if (tidx >= a.ntiles) return;  // (the grid is rounded up to whole groups of 8 tiles)
     uint4 tile = a.tiles[tidx];
     const int vlo = (int)((tile.z >> 16) & 0xFFu), vhi = (int)(tile.z >> 24);
@@ -1110,7 +1269,7 @@ __device__ __forceinline__ void finalize_block(const FinalizeArgs &a)
     const int Lp = a.pbase + (int)tile.z, T = a.pbase + (int)tile.w;
     // ---- requests that only need the tile, oldest first.  (1) the row sketch's listed registers: lane e takes entry e
     // (+128 per round); the bucket records below depend on them
-    constexpr int kR = RK > 3 ? 2 : (int)(kListCap / 128);  // (the wide records are only used with lists of <= 256 entries)
+    constexpr int kR = kListRounds<RK>;
     // (every row of rl holds E slots, the unused ones 0xFFFFFFFF: no look at the list's length first -- one dependent
     // scalar load less in front of the records)
     const int nr = (int)((a.E + 127u) >> 7);  // rounds (uniform): 1 at p <= 11, 4 at p = 14
@@ -1132,9 +1291,8 @@ __device__ __forceinline__ void finalize_block(const FinalizeArgs &a)
     // (3) this lane's inputs: the C(v) of up to 16 planes, 48 bins of column j's tail histogram, the keys -- one round
     // trip for all of them.  (Uniform base + 32-bit lane offset: the plane stride is added on the scalar side.)
     const CT *cum0 = reinterpret_cast<const CT *>(a.cum);
-    constexpr int kBatch = 16;
     const int npl = (int)(tile.w - tile.z);  // dense planes of this tile (uniform)
-    uint32_t cvv[kBatch];
+    uint32_t cvv[kCvBatch];
     const int w0 = (T + 1) >> 4;  // first 16-byte word of the tail histogram that holds a bin > T (uniform)
     uint4 tq[3];
     {
@@ -1142,7 +1300,7 @@ __device__ __forceinline__ void finalize_block(const FinalizeArgs &a)
         // bases do not fit the scalar registers and were parked in VGPR lanes
         const CT *cp = cum0 + (uint64_t)tile.z * a.nslots;
 #pragma unroll
-        for (int t = 0; t < kBatch; ++t) {
+        for (int t = 0; t < kCvBatch; ++t) {
             cvv[t] = 0u;
             if (t < npl) {  // uniform (a scalar compare with an immediate: nothing to keep for the second loop below)
                 cvv[t] = (uint32_t)cp[slot];
@@ -1209,11 +1367,7 @@ __device__ __forceinline__ void finalize_block(const FinalizeArgs &a)
                : L->rowoff ? L->rowoff[i < j ? si : sj] + (oj - oi - 1)  // (the pair's row is the smaller sketch index)
                            : (uint64_t)oi * (2 * L->n - oi - 1) / 2 + oj - (oi + 1) - L->base_index;
     };
-    if (a.stop == 1) {
-        const FinalizeArgs *L = &a;
-        if (active) L->out[out_index(L)] = (float)T;
-        return;
-    }
+    if (a.stop == 1) return stop_store(a, active, out_index, (float)T);
     const uint32_t m = 1u << a.p;
     CT *col = hs + tid;
     uint32_t prev = 0, nb = 0;
@@ -1226,13 +1380,13 @@ __device__ __forceinline__ void finalize_block(const FinalizeArgs &a)
         CT *dcol = col + (a.pbase - vlo) * 128;  // bin pbase + pl lives at dcol + pl * 128
         CT *dcz = dcol + tile.z * 128;
 #pragma unroll
-        for (int t = 0; t < kBatch; ++t) {
+        for (int t = 0; t < kCvBatch; ++t) {
             if (t < npl) {  // uniform
                 dcz[t * 128] = (CT)(cvv[t] - prev);
                 prev = cvv[t];
             }
         }
-        for (uint32_t pl = tile.z + kBatch; pl < tile.w; ++pl) {  // wide plane ranges (heterogeneous tiles)
+        for (uint32_t pl = tile.z + kCvBatch; pl < tile.w; ++pl) {  // wide plane ranges (heterogeneous tiles)
             const uint32_t cv = (cum0 + (uint64_t)pl * a.nslots)[slot];
             dcol[pl * 128] = (CT)(cv - prev);
             prev = cv;
@@ -1279,106 +1433,8 @@ __device__ __forceinline__ void finalize_block(const FinalizeArgs &a)
     }
     __syncthreads();
     if constexpr (TIMED) tph[2] = __builtin_readcyclecounter();
-    if (a.stop == 2) {
-        const FinalizeArgs *L = &a;
-        if (active) L->out[out_index(L)] = (float)(nb + prev + keyj);
-        return;
-    }
-    // ---- the join: what the records hold is applied to the owning lanes' histogram columns
-    {
-        uint32_t *hw = reinterpret_cast<uint32_t *>(hs);
-        // every lane of the block owns a pair (any tile off the diagonal of a full range): no per-entry ownership test
-        const bool all_own = (actm[0] & actm[1] & actm[2] & actm[3]) == 0xFFFFFFFFu;
-        // Gather, then apply.  A lane's own record is a poor unit of work for a wave: most buckets hold 0-2 entries, yet
-        // nearly every wave-round holds a lane whose bucket overflows its record, and the wave pays its longest lane
-        // (profiles/join1: 36 wave-level applications per tile row for 250 entries, a tenth of the lane slots busy).  So
-        // what the records hold goes into a queue of the WAVE first -- one 32-bit item per entry: column << 6 | value
-        // (the entry's low 13 bits), the row value << 13, upper tail << 21; an entry of another position of the group
-        // (p > 14) is dropped here -- with slots from a ballot, not from an LDS atomic per item, and the lanes then walk
-        // the queue one item each.  Filled and drained by the wave alone: no barrier, the LDS serves a wave in order.
-        uint32_t *jq = joinq + (uint32_t)(tid >> 6) * kJoinQ;
-        const uint32_t lane = (uint32_t)tid & 63u;
-        uint32_t qn = 0;  // items queued (uniform)
-        auto apply = [&](uint32_t it) {
-            const uint32_t jl = (it >> 6) & 127u;
-            const int vb = (int)(it & 63u), var = (int)((it >> 13) & 0xFFu);
-            const bool upr = (it >> 21) & 1u;
-            // a live value on the column's side too, and a lane that owns a pair (diagonal tile, row range, padding)
-            if (!(upr ? vb > T : vb < Lp)) return;
-            if (!all_own && !((actm[jl >> 5] >> (jl & 31u)) & 1u)) return;
-            // upper tail: the position was counted in both tail histograms, take the smaller value out again;
-            // lower tail: both registers are below the dense range, max(a_t, b_t) is the larger one
-            const int bin = upr ? (var < vb ? var : vb) : (var > vb ? var : vb);
-            const uint32_t cell = (uint32_t)(bin - vlo) * 128u + jl;
-            const uint32_t one = sizeof(CT) == 2 ? 1u << (16u * (cell & 1u)) : 1u;
-            uint32_t *w = &hw[sizeof(CT) == 2 ? cell >> 1 : cell];
-            if (upr) {
-                atomicAdd(&corr[jl], 1u);
-                atomicSub(w, one);  // (the 16-bit half holds >= 1: no borrow into its neighbour)
-            } else {
-                atomicAdd(w, one);
-            }
-        };
-        auto drain = [&]() {
-            for (uint32_t b = 0; b < qn; b += 64u)
-                if (b + lane < qn) apply(jq[b + lane]);
-            qn = 0;
-        };
-        // entry x of a bucket that a row entry with header h (row value << 13 | upper << 21 | position's low bits << 22)
-        // looked up: queued if it is an entry of the same position.  At most 64 items per call, so after a drain they fit.
-        auto push = [&](uint32_t x, uint32_t h) {
-            const bool ok = x != kNone && (!sh || (x >> 13) == (h >> 22));
-            const unsigned long long mk = __ballot(ok);
-            const uint32_t n = (uint32_t)__popcll(mk);
-            if (qn + n > kJoinQ) drain();  // (uniform)
-            if (ok) jq[qn + __builtin_amdgcn_mbcnt_hi((uint32_t)(mk >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mk, 0u))] = (x & 0x1FFFu) | (h & 0x3FFFFFu);
-            qn += n;
-        };
-#pragma unroll
-        for (int r = 0; r < kR; ++r) {
-            if (r >= nr) break;
-            if (__ballot(rc[r].y != kNone) == 0) continue;  // no lane of this wave found anything (a short list: wave 1)
-            const uint32_t va = le[r] & 0xFFu;
-            const uint32_t hdr = (va << 13) | ((int)va > T ? 1u << 21 : 0u) | (((le[r] >> 8) & ((1u << sh) - 1u)) << 22);
-            push(rc[r].y, hdr);
-            push(rc[r].z, hdr);
-            push(rc[r].w, hdr);
-            if constexpr (RK > 3) {
-                push(rc2[r].x, hdr);
-                push(rc2[r].y, hdr);
-                push(rc2[r].z, hdr);
-                push(rc2[r].w, hdr);
-            }
-            // buckets with more than RK entries (few per lane, but nearly every wave-round has some): the wave takes them
-            // one at a time and reads the rest of the bucket from ent[] together, lane q its q-th further entry -- the
-            // next bucket's read is in flight while this one's entries are queued
-            unsigned long long ov = __ballot((rc[r].x & 0xFFFFu) > (uint32_t)RK);
-            if (ov == 0) continue;
-            auto rest = [&](uint32_t w0, uint32_t b) -> uint32_t {  // entry RK + b + lane of the bucket with record word w0
-                return b + lane < (w0 & 0xFFFFu) - (uint32_t)RK ? bent[(w0 >> 16) + (uint32_t)RK + b + lane] : kNone;
-            };
-            int l = __ffsll((long long)ov) - 1;
-            uint32_t w0 = (uint32_t)__builtin_amdgcn_readlane((int)rc[r].x, l), h = (uint32_t)__builtin_amdgcn_readlane((int)hdr, l);
-            uint32_t x = rest(w0, 0u);
-            for (;;) {
-                ov &= ov - 1ull;
-                uint32_t w0n = 0u, hn = 0u, xn = kNone;
-                if (ov) {
-                    l = __ffsll((long long)ov) - 1;
-                    w0n = (uint32_t)__builtin_amdgcn_readlane((int)rc[r].x, l);
-                    hn = (uint32_t)__builtin_amdgcn_readlane((int)hdr, l);
-                    xn = rest(w0n, 0u);
-                }
-                push(x, h);
-                for (uint32_t b = 64u; b < (w0 & 0xFFFFu) - (uint32_t)RK; b += 64u) push(rest(w0, b), h);  // (> 64 + RK entries)
-                if (ov == 0) break;
-                w0 = w0n;
-                h = hn;
-                x = xn;
-            }
-        }
-        drain();
-    }
+    if (a.stop == 2) return stop_store(a, active, out_index, (float)(nb + prev + keyj));
+    join_tails<CT, RK, kR>(lds, hs, tid, T, Lp, vlo, sh, bent, nr, le, rc, rc2);
     __syncthreads();
     if constexpr (TIMED) tph[3] = __builtin_readcyclecounter();
     if (!active) return;
@@ -1388,11 +1444,7 @@ __device__ __forceinline__ void finalize_block(const FinalizeArgs &a)
     if (tile.w > tile.z) col[(Lp - vlo) * 128] -= (CT)clow;  // c[Lp] = C(Lp+1) - C(Lp)
     else prev = clow;                                         // no dense plane: C(T) = C(Lp)
     col[(T - vlo) * 128] = (CT)(m - ucnt - prev);  // c[T] = C(T+1) - C(T), C(T+1) = m - |union above T|
-    if (a.stop == 3) {
-        const FinalizeArgs *L = &a;
-        L->out[out_index(L)] = (float)(ucnt + clow);
-        return;
-    }
+    if (a.stop == 3) return stop_store(a, true, out_index, (float)(ucnt + clow));
     // scan bounds for the estimator: no bin below the larger of the two minima, none above the larger of the maxima
     const int loj = (int)(keyj & 63u), loi = (int)(keyi & 63u);
     const int minv = loi > loj ? loi : loj;
@@ -1424,10 +1476,7 @@ __device__ __forceinline__ void finalize_block(const FinalizeArgs &a)
     int mle_it = 0;
     const double us = estimate(c, raw, a.p, a.estim, minv < T ? minv : T, maxv, TIMED ? &mle_it : nullptr);
     if constexpr (TIMED) tph[5] = __builtin_readcyclecounter();
-    if (a.stop == 4) {
-        outp[oidx] = (float)us;
-        return;
-    }
+    if (a.stop == 4) return stop_store(a, true, [oidx](const FinalizeArgs *) { return oidx; }, (float)us);  // (the index is there already)
     const float res = result_cmp_from(cardj, cardi, us, rtype, ksinv);  // lhs = j, rhs = i
     if (m_square || m_knn) {  // row i sees j as lhs, row j sees i as lhs (only the containment measures differ)
         const bool asym = rtype == 4 || rtype == 5 || rtype == 6;
@@ -1509,7 +1558,7 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(8, 8), amdg
 {
     finalize_block<CT, RK, false, false>(a);
     if (a.sig == nullptr) return;  // (a call without parts: nothing to announce)
-    const uint32_t tidx = (((blockIdx.x >> 3) >> 7) << 3) + (blockIdx.x & 7u);
+    const uint32_t tidx = finalize_row_of_block().tidx;
     if (tidx >= a.ntiles) return;  // (the grid is rounded up to whole groups of 8 tiles: no tile, nothing to count)
     // every WAVE waits for its own write-through stores (gfx9 counts stores in vmcnt; a workgroup-scope release fence
     // compiles to lgkmcnt(0) only, which would let wave 1's stores still be in flight when wave 0 counts the block:
@@ -1538,315 +1587,11 @@ hipError_t launch_wall_stamp(hipStream_t st, unsigned long long *out)
     return hipGetLastError();
 }
 
-// row-sorted parts (plan.h): the rows at the positions [pos0, pos1) of a source rank's key order, lying at rowoff[s] of its
-// buffer, go to their places in dashing's packed triangle (row r starts at r (2n - r - 1) / 2 and holds n - 1 - r values).
-// A row is contiguous on both sides; a block copies kPlaceChunk values of it (blockIdx.y = the chunk: the longest rows
-// of a part -- 40 KB at n = 10 000 -- would otherwise keep 128 blocks busy while 128 CUs idle).
-constexpr uint32_t kPlaceChunk = 4096;
-__device__ __forceinline__ void place_row_chunk(const float *__restrict__ src, float *__restrict__ out, const uint32_t *__restrict__ order,
-                                                const uint64_t *__restrict__ rowoff, uint64_t s, uint64_t n)
-{
-    const uint64_t r = order[s], len = n - 1 - r;
-    const uint64_t x0 = (uint64_t)blockIdx.y * kPlaceChunk;
-    if (x0 >= len) return;
-    const uint64_t x1 = x0 + kPlaceChunk < len ? x0 + kPlaceChunk : len;
-    const float *from = src + rowoff[s];
-    float *to = out + r * (2 * n - r - 1) / 2;
-    for (uint64_t x = x0 + threadIdx.x; x < x1; x += 256) to[x] = from[x];
-}
-
-__global__ __launch_bounds__(256) void k_row_place(const float *__restrict__ src, float *__restrict__ out,
-                                                    const uint32_t *__restrict__ order, const uint64_t *__restrict__ rowoff,
-                                                    uint64_t pos0, uint64_t n)
-{
-    place_row_chunk(src, out, order, rowoff, pos0 + blockIdx.x, n);
-}
-
-hipError_t launch_row_place(hipStream_t st, const float *src, float *out, const uint32_t *order, const uint64_t *rowoff,
-                            uint64_t pos0, uint64_t pos1, uint64_t n)
-{
-    if (pos1 <= pos0 || n < 2) return hipSuccess;
-    hipLaunchKernelGGL(k_row_place, dim3((uint32_t)(pos1 - pos0), (uint32_t)((n - 1 + kPlaceChunk - 1) / kPlaceChunk)), dim3(256), 0, st,
-                       src, out, order, rowoff, pos0, n);
-    return hipGetLastError();
-}
-
-// one round of the exchange at the destination: the parts of ALL row-sorted sources that arrived in it, in ONE launch
-// (a launch per source left seven small kernels in a row behind the last transfer of an 8-rank step).  Entry e covers
-// the blocks [row0, row0 + nrows) of the grid's x.
-__global__ __launch_bounds__(256) void k_rows_place(const PlaceEnt *__restrict__ ent, uint32_t nent, float *__restrict__ out, uint64_t n)
-{
-    uint32_t e = 0;
-    while (e + 1 < nent && ent[e + 1].row0 <= blockIdx.x) ++e;
-    const PlaceEnt E = ent[e];
-    place_row_chunk(E.src, out, E.order, E.rowoff, E.pos0 + (blockIdx.x - E.row0), n);
-}
-
-hipError_t launch_rows_place(hipStream_t st, const PlaceEnt *ent, uint32_t nent, uint32_t total_rows, float *out, uint64_t n)
-{
-    if (!nent || !total_rows || n < 2) return hipSuccess;
-    hipLaunchKernelGGL(k_rows_place, dim3(total_rows, (uint32_t)((n - 1 + kPlaceChunk - 1) / kPlaceChunk)), dim3(256), 0, st, ent, nent, out, n);
-    return hipGetLastError();
-}
-
-
-// same mapping driven from the destination: one block per ORIGINAL row a, coalesced writes of
-// row a of the output, gathered reads (inv = inverse of perm)
-__global__ __launch_bounds__(256) void k_unpermute_gather(const float *__restrict__ in,
-                                                           const uint32_t *__restrict__ inv, uint64_t n,
-                                                           float *__restrict__ out)
-{
-    const uint64_t a = blockIdx.x;
-    const uint64_t sa = inv[a];
-    float *row = out + a * (2 * n - a - 1) / 2 - (a + 1);
-    for (uint64_t b = a + 1 + threadIdx.x; b < n; b += 256) {
-        const uint64_t sb = inv[b];
-        const uint64_t lo = sa < sb ? sa : sb, hi = sa < sb ? sb : sa;
-        row[b] = in[lo * (2 * n - lo - 1) / 2 + hi - (lo + 1)];
-    }
-}
-
-// as k_unpermute_gather, but the spans of the shards sit at a fixed stride in `in` (the padded blocks an
-// RCCL gather delivers): rowdelta[sorted row / 128] = shard * stride - span_off[shard]
-__global__ __launch_bounds__(256) void k_unpermute_staged(const float *__restrict__ in,
-                                                           const uint32_t *__restrict__ inv,
-                                                           const int64_t *__restrict__ rowdelta,
-                                                           uint64_t n, float *__restrict__ out)
-{
-    const uint64_t a = blockIdx.x;
-    const uint64_t sa = inv[a];
-    float *row = out + a * (2 * n - a - 1) / 2 - (a + 1);
-    for (uint64_t b = a + 1 + threadIdx.x; b < n; b += 256) {
-        const uint64_t sb = inv[b];
-        const uint64_t lo = sa < sb ? sa : sb, hi = sa < sb ? sb : sa;
-        row[b] = in[(int64_t)(lo * (2 * n - lo - 1) / 2 + hi - (lo + 1)) + rowdelta[lo / kTile]];
-    }
-}
-
-hipError_t launch_unpermute_staged(hipStream_t st, const float *in, const uint32_t *inv,
-                                   const int64_t *rowdelta, uint64_t n, float *out)
-{
-    if (n < 2) return hipSuccess;
-    hipLaunchKernelGGL(k_unpermute_staged, dim3((uint32_t)(n - 1)), dim3(256), 0, st, in, inv, rowdelta, n, out);
-    return hipGetLastError();
-}
-
-hipError_t launch_unpermute(hipStream_t st, const float *in, const uint32_t *inv, uint64_t n, float *out)
-{
-    if (n < 2) return hipSuccess;
-    hipLaunchKernelGGL(k_unpermute_gather, dim3((uint32_t)(n - 1)), dim3(256), 0, st, in, inv, n, out);
-    return hipGetLastError();
-}
-
-// ------------------------------------------------------------------------------------------
-// k best columns of every row of a row-major [rows][ncols] block (perform_nns,
-// src/sketch_and_cmp.h:642-697, without its heaps and mutexes): one wave per row, nn selection
-// passes; pass t takes the best element that comes strictly after pass t-1's pick in the total
-// order (value best-first, then column index ascending), so nothing is mutated and ties are
-// deterministic.  NaN ranks last.  self_col (or ~0) is skipped.
-__global__ __launch_bounds__(256) void k_topk(const float *__restrict__ vals, uint64_t rows,
-                                               uint64_t ncols, uint64_t row0, uint64_t col0,
-                                               int descending, uint32_t nn, int exclude_self,
-                                               uint32_t *__restrict__ idx_out,
-                                               float *__restrict__ val_out)
-{
-    const int lane = threadIdx.x & 63;
-    const uint64_t r = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (r >= rows) return;
-    const float *v = vals + r * ncols;
-    const float worst = descending ? -__builtin_huge_valf() : __builtin_huge_valf();
-    const uint64_t self = exclude_self ? row0 + r - col0 : ~0ull;  // column of the row's own sketch
-    // order: a before b  <=>  a.val better than b.val, or equal and a.idx < b.idx
-    auto before = [descending](float av, uint32_t ai, float bv, uint32_t bi) {
-        if (av != bv) return descending ? av > bv : av < bv;
-        return ai < bi;
-    };
-    float pv = descending ? __builtin_huge_valf() : -__builtin_huge_valf();  // "before everything"
-    uint32_t pi = 0;
-    bool first = true;
-    for (uint32_t t = 0; t < nn; ++t) {
-        float bv = worst;
-        uint32_t bi = 0xFFFFFFFFu;
-        for (uint64_t j = lane; j < ncols; j += 64) {
-            if (j == self) continue;
-            float x = v[j];
-            if (x != x) x = worst;
-            const uint32_t ji = (uint32_t)j;
-            if (!first && !before(pv, pi, x, ji)) continue;  // not after the previous pick
-            if (bi == 0xFFFFFFFFu || before(x, ji, bv, bi)) {
-                bv = x;
-                bi = ji;
-            }
-        }
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) {
-            const float ov = __shfl_xor(bv, d, 64);
-            const uint32_t oi = __shfl_xor(bi, d, 64);
-            if (oi != 0xFFFFFFFFu && (bi == 0xFFFFFFFFu || before(ov, oi, bv, bi))) {
-                bv = ov;
-                bi = oi;
-            }
-        }
-        if (lane == 0) {
-            idx_out[r * nn + t] = bi == 0xFFFFFFFFu ? 0xFFFFFFFFu : (uint32_t)(bi + col0);
-            val_out[r * nn + t] = bi == 0xFFFFFFFFu ? worst : v[bi];
-        }
-        pv = bv;
-        pi = bi;
-        first = false;
-        if (bi == 0xFFFFFFFFu) {  // fewer candidates than nn: fill the rest
-            for (uint32_t u = t + 1; u < nn; ++u)
-                if (lane == 0) {
-                    idx_out[r * nn + u] = 0xFFFFFFFFu;
-                    val_out[r * nn + u] = worst;
-                }
-            break;
-        }
-    }
-}
-
 // (dsh_preload) the runtime loads a translation unit's code object at the first use of one of its kernels: ask for one
 hipError_t preload_compare_kernels()
 {
     hipFuncAttributes fa;
     return hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(k_wall_stamp));
-}
-
-hipError_t launch_topk(hipStream_t st, const float *vals, uint64_t rows, uint64_t ncols,
-                       uint64_t row0, uint64_t col0, int descending, uint32_t nn,
-                       int exclude_self, uint32_t *idx_out, float *val_out)
-{
-    if (rows == 0 || nn == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_topk, dim3((uint32_t)((rows + 3) / 4)), dim3(256), 0, st, vals, rows,
-                       ncols, row0, col0, descending, nn, exclude_self, idx_out, val_out);
-    return hipGetLastError();
-}
-
-// ------------------------------------------------------------------------------------------
-// Nearest neighbours without the n x n matrix (perform_nns, src/sketch_and_cmp.h:642-697, whose heaps take every pair
-// as it is computed): the triangle is computed in bands of tile rows of the key-ordered layout; k_finalize leaves a
-// band's values twice -- V[r][t] (row = band row r, column = plane column t > b0 + r) and Vt[t][r] (row = plane column
-// t, column = band row r with b0 + r < t) -- and this kernel folds each row's new candidates into the running list of
-// that row's sketch: one wave per row, nn selection passes over (running list) U (candidates) in the total order of
-// k_topk (value best-first, then sketch index ascending; NaN last), every candidate carrying its ORIGINAL sketch index.
-//   mode 0: rows r in [0, rows) of V (leading dimension ld): sketch perm[b0 + r], candidates t in (b0 + r, ncols)
-//   mode 1: rows t in (b0, ncols) of Vt (leading dimension = band rows): sketch perm[t], candidates r in [0, min(rows, t - b0))
-// state: idx[n][nn] / val[n][nn] by original sketch index, initialised to (0xFFFFFFFF, worst).
-__global__ __launch_bounds__(256) void k_topk_merge(const float *__restrict__ vals, uint64_t ld, int mode, uint64_t b0,
-                                                     uint64_t rows, uint64_t ncols, const uint32_t *__restrict__ perm,
-                                                     int descending, uint32_t nn, uint32_t *__restrict__ st_idx,
-                                                     float *__restrict__ st_val)
-{
-    extern __shared__ __attribute__((aligned(8))) unsigned char tk_raw[];  // per wave: nn x (idx, val) of the running list
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint32_t *ri = reinterpret_cast<uint32_t *>(tk_raw) + (size_t)wave * 2 * nn;
-    float *rv = reinterpret_cast<float *>(ri + nn);
-    const uint64_t w = (uint64_t)blockIdx.x * 4 + wave;
-    uint64_t srow, c_begin, c_end;  // plane column of the row's sketch; candidate columns of this row
-    const float *v;
-    if (mode == 0) {
-        if (w >= rows) return;
-        srow = b0 + w;
-        c_begin = srow + 1;
-        c_end = ncols;
-        v = vals + w * ld;
-    } else {
-        srow = b0 + 1 + w;
-        if (srow >= ncols) return;
-        c_begin = 0;
-        c_end = srow - b0 < rows ? srow - b0 : rows;
-        v = vals + srow * ld;
-    }
-    const uint32_t self = perm ? perm[srow] : (uint32_t)srow;
-    const float worst = descending ? -__builtin_huge_valf() : __builtin_huge_valf();
-    for (uint32_t t = lane; t < nn; t += 64) {
-        ri[t] = st_idx[(uint64_t)self * nn + t];
-        rv[t] = st_val[(uint64_t)self * nn + t];
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    auto before = [descending](float av, uint32_t ai, float bv, uint32_t bi) {
-        if (av != bv) return descending ? av > bv : av < bv;
-        return ai < bi;
-    };
-    float pv = descending ? __builtin_huge_valf() : -__builtin_huge_valf();
-    uint32_t pi = 0;
-    bool first = true;
-    for (uint32_t t = 0; t < nn; ++t) {
-        float bv = worst, braw = worst;  // bv: the value the order uses (NaN ranks as the worst), braw: what is reported
-        uint32_t bi = 0xFFFFFFFFu;
-        auto offer = [&](float raw, uint32_t id) {
-            const float x = raw != raw ? worst : raw;
-            if (!first && !before(pv, pi, x, id)) return;  // not after the previous pick
-            if (bi == 0xFFFFFFFFu || before(x, id, bv, bi)) {
-                bv = x;
-                braw = raw;
-                bi = id;
-            }
-        };
-        for (uint32_t u = lane; u < nn; u += 64)
-            if (ri[u] != 0xFFFFFFFFu) offer(rv[u], ri[u]);
-        for (uint64_t c = c_begin + lane; c < c_end; c += 64) {
-            const uint64_t sc = mode == 0 ? c : b0 + c;  // plane column of the candidate
-            offer(v[c], perm ? perm[sc] : (uint32_t)sc);
-        }
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) {
-            const float ov = __shfl_xor(bv, d, 64), oraw = __shfl_xor(braw, d, 64);
-            const uint32_t oi = __shfl_xor(bi, d, 64);
-            if (oi != 0xFFFFFFFFu && (bi == 0xFFFFFFFFu || before(ov, oi, bv, bi))) {
-                bv = ov;
-                braw = oraw;
-                bi = oi;
-            }
-        }
-        if (lane == 0) {
-            st_idx[(uint64_t)self * nn + t] = bi;
-            st_val[(uint64_t)self * nn + t] = bi == 0xFFFFFFFFu ? worst : braw;  // (a NaN stays a NaN, as k_topk reports it)
-        }
-        pv = bv;
-        pi = bi;
-        first = false;
-        if (bi == 0xFFFFFFFFu) {  // fewer candidates than nn: the rest stays empty
-            for (uint32_t u = t + 1 + lane; u < nn; u += 64) {
-                st_idx[(uint64_t)self * nn + u] = 0xFFFFFFFFu;
-                st_val[(uint64_t)self * nn + u] = worst;
-            }
-            break;
-        }
-    }
-}
-
-__global__ __launch_bounds__(256) void k_fill_knn_state(uint32_t *__restrict__ idx, float *__restrict__ val, uint64_t cnt, float worst)
-{
-    const uint64_t t = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    if (t < cnt) {
-        idx[t] = 0xFFFFFFFFu;
-        val[t] = worst;
-    }
-}
-
-hipError_t launch_knn_state_init(hipStream_t st, uint32_t *idx, float *val, uint64_t cnt, int descending)
-{
-    if (cnt == 0) return hipSuccess;
-    const float worst = descending ? -__builtin_huge_valf() : __builtin_huge_valf();
-    hipLaunchKernelGGL(k_fill_knn_state, dim3((uint32_t)((cnt + 255) / 256)), dim3(256), 0, st, idx, val, cnt, worst);
-    return hipGetLastError();
-}
-
-hipError_t launch_topk_merge(hipStream_t st, const float *vals, uint64_t ld, int mode, uint64_t b0, uint64_t rows,
-                             uint64_t ncols, const uint32_t *perm, int descending, uint32_t nn, uint32_t *st_idx,
-                             float *st_val)
-{
-    const uint64_t nrows = mode == 0 ? rows : (ncols > b0 + 1 ? ncols - b0 - 1 : 0);
-    if (nrows == 0 || nn == 0) return hipSuccess;
-    const size_t lds = (size_t)4 * 2 * nn * sizeof(uint32_t);
-    hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void *>(k_topk_merge), lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_topk_merge, dim3((uint32_t)((nrows + 3) / 4)), dim3(256), lds, st, vals, ld, mode, b0, rows, ncols,
-                       perm, descending, nn, st_idx, st_val);
-    return hipGetLastError();
 }
 
 // ------------------------------------------------------------------------------------------
@@ -2060,7 +1805,7 @@ hipError_t launch_finalize(hipStream_t st, const FinalizeLaunch &f)
     if (f.nslots == 0) return hipSuccess;
     FinalizeArgs a = f.a;
     a.ntiles = (uint32_t)(f.nslots / ((uint64_t)kTile * kTile));
-    const size_t lds = kFinalizeLdsHead + (size_t)a.hist_bins * 128 * (f.cum_bytes == 2 ? 2 : 4);
+    const size_t lds = sizeof(FinalizeLds) + (size_t)a.hist_bins * 128 * (f.cum_bytes == 2 ? 2 : 4);
     const uint32_t blocks = (a.ntiles + 7u) / 8u * 8u * 128u;  // (whole groups of 8 tiles: a tile's 128 rows on one XCD)
     const bool timed = a.phase_cyc != nullptr;  // profiling only
     const bool general = a.rect || a.square || a.sorted_out || a.knn;

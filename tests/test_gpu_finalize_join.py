@@ -1,4 +1,4 @@
-"""k_finalize's tail join through the wave's work queue (kernels_compare.hip, finalize_block): crowded buckets -- more
+"""k_finalize's tail join through the wave's work queue (kernels_compare.hip, join_tails of finalize_block): crowded buckets -- more
 entries than a record holds inline, more than one wave-wide read of ent[], more items than the queue holds -- both
 tails, empty lists, and every call form, against the oracle (|d| <= 1e-6 * max(|ref|, 1e-9)) and byte for byte against
 the full call of the same context.  The conditions a collection is chosen for are asserted on the host first, with
@@ -184,6 +184,28 @@ def test_call_forms_agree_byte_for_byte(ctx, oracle, p):
                 assert out.cpu().numpy().tobytes() == full[a : a + span].tobytes(), (sort_min, rb, re, nparts)
         finally:
             ctx.set_option("range_sort_min_rows", 1024)
+
+
+@pytest.mark.parametrize("p", [10, 14])  # bucket records with 7 inline entries; with 3
+def test_timed_instance_returns_the_same_bytes(ctx, oracle, p):
+    """the stamped instance (option finalize_timing under profiling, as tools/finalize_probe.py sets it) at a crowded
+    collection with a diagonal tile, off-diagonal tiles and a padded last block: the same bytes as the plain instance,
+    and some wave reported its phases"""
+    n = 300
+    regs, load, _ = crowded(n, p)
+    assert load["RK"] == (7 if p == 10 else 3), load
+    ctx.set_sketches(regs)
+    plain = ctx.dist_rows()
+    ctx.set_profiling(True)
+    try:
+        ctx.set_option("finalize_timing", 1)
+        timed = ctx.dist_rows()
+        cycles = ctx.finalize_phase_cycles()
+    finally:
+        ctx.set_option("finalize_timing", 0)
+        ctx.set_profiling(False)
+    assert timed.tobytes() == plain.tobytes()
+    assert cycles[6] > 0, cycles  # waves counted
 
 
 def fuzz_case(k):
