@@ -53,6 +53,8 @@ _FIRST = int(os.environ.get("DSH_FUZZ_FIRST", "0"))  # e.g. DSH_FUZZ_FIRST=2500 
 
 @pytest.mark.parametrize("case", range(_FIRST, _FIRST + int(os.environ.get("DSH_FUZZ_CASES", "100"))))
 def test_random_case(ctx, oracle, case):
+    # (tools/path_census.py::fuzz_random_case repeats the draws below -- p, n, kind, estim, rt, k, _regs, the two planted
+    # sketches, emax, elow, in this order -- to replay the collections without a device: change both together)
     rng = np.random.default_rng(1000 + case)
     p = int(rng.choice([4, 6, 8, 9, 10, 11, 12, 13, 14, 15, 16, 18, 20]))
     n = int(rng.integers(2, 420 if p <= 12 else (180 if p <= 16 else 24)))

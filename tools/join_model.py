@@ -9,6 +9,8 @@ It rebuilds, from the registers and the two list caps alone,
   * the buckets of k_build_colindex ((position >> sh) * 2 + lower tail, the tail by the COLUMN's own thresholds),
   * the tile's dense range (plan::tile_planes) and, for sampled (row, column block) pairs, the look-ups of the row:
     lane e of round r holds entry 128 r + e of the row's list.
+The rules are stated once, as functions (list_thresholds, key_order, listed, ColumnBlock, lookup_matches, row_lookups);
+tools/path_census.py builds the census of the compare path's data-dependent branches on them.
 Two things the device does not fix are assumptions here: the ORDER of a row's list (k_selfhist_card writes it lane by
 lane, this model takes it in position order) and therefore which entries share a wave-round; the order inside a bucket
 plays no part (a bucket is a set).
@@ -45,13 +47,11 @@ def record_inline(p, E):
     return 7 if p <= 12 and E <= 256 else 3
 
 
-def thresholds(regs, emax, elow):
-    """per sketch: lo, hi, T, L as k_selfhist_card finds them (regs: [n, 2^p] uint8)"""
+def list_thresholds(regs, emax, elow):
+    """per sketch: lo, hi, T, L as k_selfhist_card finds them, and the registers it lists above T and below L
+    (regs: [n, 2^p] uint8)"""
     n = regs.shape[0]
-    lo = np.zeros(n, np.int64)
-    hi = np.zeros(n, np.int64)
-    T = np.zeros(n, np.int64)
-    L = np.zeros(n, np.int64)
+    out = np.zeros((6, n), np.int64)
     for s in range(n):
         h = np.bincount(regs[s], minlength=64)[:64]
         nz = np.flatnonzero(h)
@@ -64,8 +64,13 @@ def thresholds(regs, emax, elow):
         while l < t and cntl + h[l] <= elow:
             cntl += h[l]
             l += 1
-        lo[s], hi[s], T[s], L[s] = a, b, t, l
-    return lo, hi, T, L
+        out[:, s] = a, b, t, l, cnt, cntl
+    return tuple(out)
+
+
+def thresholds(regs, emax, elow):
+    """per sketch: lo, hi, T, L as k_selfhist_card finds them (regs: [n, 2^p] uint8)"""
+    return list_thresholds(regs, emax, elow)[:4]
 
 
 def key_order(hi, T, L):
@@ -104,32 +109,35 @@ class ColumnBlock:
         self.L = int(L[cols].min())
 
 
+def lookup_matches(ps, vs, cb, Tt, Lp, p):
+    """list entries (positions ps, values vs: of one row or of many) looked up in column block cb by a tile with the
+    thresholds Tt and Lp.  Per entry: the bucket's entry count (-1: the entry is not looked up -- Tt itself and the dense
+    range are never joined) and whether it is one of the upper tail; per (entry, entry of its bucket): e, the index into
+    ps, and k, the index into cb's arrays"""
+    sh = max(p - 14, 0)
+    up = vs > Tt
+    look = up | (vs < Lp)
+    b = ((ps >> sh) << 1) | (~up).astype(np.int64)
+    cnt = np.where(look, cb.count[b], -1).astype(np.int64)
+    c = np.maximum(cnt, 0)
+    e = np.repeat(np.arange(len(ps)), c)
+    k = cb.first[b][e] + (np.arange(e.size) - np.repeat(np.cumsum(c) - c, c))
+    return cnt, up, e, k.astype(np.int64)
+
+
 def row_lookups(regs, s, T, L, lo, blk_row, blk_col, cb, p):
     """the look-ups of row sketch s in column block cb: per list entry (in list order) the bucket's entry count (-1: the
     entry is not looked up), the entries of its own position (the queue's items), those that pass the value filter, and
     whether the look-up is one of the upper tail"""
-    sh = max(p - 14, 0)
     Tt = max(blk_row["T"], blk_col["T"])
     Lp = max(max(blk_row["lo"], blk_col["lo"]), min(blk_row["L"], blk_col["L"]))
     ps, vs = listed(regs[s], T[s], L[s])
-    cnt = np.full(len(ps), -1, np.int64)
-    items = np.zeros(len(ps), np.int64)
-    applied = np.zeros(len(ps), np.int64)
-    upper = vs > Tt
-    for e in range(len(ps)):
-        va = int(vs[e])
-        up = va > Tt
-        if not (up or va < Lp):
-            continue
-        b = ((int(ps[e]) >> sh) << 1) | (0 if up else 1)
-        c = int(cb.count[b])
-        cnt[e] = c
-        q = slice(int(cb.first[b]), int(cb.first[b]) + c)
-        same = cb.pos[q] == ps[e]
-        items[e] = int(same.sum())
-        vb = cb.vb[q][same]
-        applied[e] = int((vb > Tt).sum() if up else (vb < Lp).sum())
-    return cnt, items, applied, upper
+    cnt, up, e, k = lookup_matches(ps, vs, cb, Tt, Lp, p)
+    same = cb.pos[k] == ps[e]
+    live = same & np.where(up[e], cb.vb[k] > Tt, cb.vb[k] < Lp)
+    items = np.bincount(e[same], minlength=len(ps)).astype(np.int64)
+    applied = np.bincount(e[live], minlength=len(ps)).astype(np.int64)
+    return cnt, items, applied, up
 
 
 def model(regs, p, emax=None, elow=None, rows=320, seed=1, sort=True):
