@@ -83,6 +83,7 @@ int dsh_preload(int device, unsigned what)
     if ((what & DSH_PRELOAD_SKETCH) && e == hipSuccess) e = preload_fastx_kernels();
     if ((what & DSH_PRELOAD_COMPARE) && e == hipSuccess) e = preload_compare_kernels();
     if ((what & DSH_PRELOAD_COMPARE) && e == hipSuccess) e = preload_hist_kernels();
+    if ((what & DSH_PRELOAD_COMPARE) && e == hipSuccess) e = preload_sparseplane_kernels();
     if ((what & DSH_PRELOAD_COMPARE) && e == hipSuccess) e = preload_knn_kernels();
     if ((what & DSH_PRELOAD_COMPARE) && e == hipSuccess) e = preload_exchange_kernels();
     if (e != hipSuccess) (void)hipGetLastError();
@@ -939,6 +940,10 @@ int dsh_get_info(dsh_ctx *c, const char *name, int64_t *out)
         for (uint32_t x : c->pp.band_frags) f += x;
         *out = (int64_t)f;
     }
+    else if (!std::strcmp(name, "sparse_items")) *out = (int64_t)c->pp.sp_items.size();  // (tile, plane) items counted from position lists (plan.h)
+    else if (!std::strcmp(name, "sparse_plane_us")) *out = (int64_t)(c->sparse_ms * 1000.0);  // (profiling) their counting kernel, of the last call
+    else if (!std::strcmp(name, "sparse_planes")) *out = c->sparse_planes;
+    else if (!std::strcmp(name, "sparse_cap")) *out = c->sparse_cap;
     else if (!std::strcmp(name, "words_per_plane")) *out = c->W;
     else if (!std::strcmp(name, "avg_tile_planes_x100")) {
         uint64_t tot = 0;
@@ -1074,6 +1079,21 @@ int dsh_set_option(dsh_ctx *c, const char *name, int64_t v)
     if (!std::strcmp(name, "overflow_frag_permille")) {
         if (v < 0 || v > 1000) return fail(c, DSH_EINVAL, "overflow_frag_permille out of range");
         c->overflow_frag_permille = (int)v;
+        return DSH_OK;
+    }
+    if (!std::strcmp(name, "sparse_planes")) {  // sparse outer planes (plan.h, Tuning)
+        if (v < -1 || v > 2) return fail(c, DSH_EINVAL, "sparse_planes is -1 (auto), 0 (off), 1 or 2");
+        c->sparse_planes = (int)v;
+        return DSH_OK;
+    }
+    if (!std::strcmp(name, "sparse_lds")) {
+        if (v < 0 || v > 1) return fail(c, DSH_EINVAL, "sparse_lds must be 0 or 1");
+        c->sparse_lds = (int)v;
+        return DSH_OK;
+    }
+    if (!std::strcmp(name, "sparse_cap")) {
+        if (v < 0 || v > (int64_t)plan::kSparseCapMax) return fail(c, DSH_EINVAL, "sparse_cap must be in [0, %u]", plan::kSparseCapMax);
+        c->sparse_cap = (int)v;
         return DSH_OK;
     }
     if (!std::strcmp(name, "xch_recv_gate")) {

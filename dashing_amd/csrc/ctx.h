@@ -219,6 +219,7 @@ struct dsh_ctx {
     int wall_clock_khz = 0;
     PinBuf pin_keys;                    // host copy of the per-sketch keys (valid while the per-sketch pass is), page-locked:
     const uint32_t *hk32 = nullptr;     // the copy is a direct DMA and the host only waits for ev_keys
+    const uint32_t *hg32 = nullptr;     // the per-sketch counts g0 | g1 << 16 behind the keys, same transfer (plan.h, build_layout)
     bool hk32_valid = false;
     double host_layout_us = 0, host_lists_us = 0, host_keys_wait_us = 0;  // host time of the last call (dsh_get_info)
     Staging st_perm;                    // lay.perm, then (row-sorted parts) lay.rowoff from the next 16-byte boundary on
@@ -236,6 +237,16 @@ struct dsh_ctx {
     int elow_opt = -1;  // cap of the listed lower tail; -1: auto_list_cap(p, false)
     int part_band_tiles = 2048;       // a part of at least this many tiles gets its own launch of the tile kernel (plan.cpp)
     int overflow_frag_permille = 500;  // overflow fragments of the tile kernel (plan.h, Tuning): 0 = never
+    int sparse_planes = -1;  // sparse outer planes (plan.h, Tuning): -1 auto, 0 off, 1 | 2 forced
+    int sparse_cap = (int)dsh::plan::kSparseCapDefault;  // the longest set a routed plane may have
+    int sparse_lds = 1;      // the table of the counting kernel staged in LDS where a word of it fits (p <= 15); 0: gathered
+    DevBuf sp_tab, sp_lists, sp_len, sp_slabs, sp_items;  // the slabs of the last call that routed planes (kernels_sparseplane.hip) and its items
+    Staging st_sparse;               // slabs then sparse items on their way to the device
+    std::vector<dsh::plan::U2> sp_have;  // the slabs sp_tab / sp_lists / sp_len hold ...
+    uint64_t sp_serial = 0, lay_serial = 0;  // ... of which layout (lay_serial counts the layouts built)
+    uint32_t sp_cap_have = 0;
+    double sparse_ms = 0;            // (profiling) the counting kernel of the last call
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_sparse;  // (profiling) around its launches
     int tail_bands = 2;  // option xch_tail_bands: small jobs with parts have their tile kernel cut at whole rounds (plan.h, Tuning)
     std::vector<double> part_ready_ms;  // (profiling) when each part of the last call with parts was final, from the call's start
     std::vector<uint64_t> part_floats;  // and the floats of the rank's buffer it holds

@@ -63,20 +63,22 @@ int prepare(dsh_ctx *c, int estim, int want_sorted, bool card_only, uint64_t wan
         HIPCHK(c, c->exc.ensure(std::max<uint64_t>(n, 1) * kListCap * (c->p <= 15 ? 2 : 4)));
         HIPCHK(c, c->excv.ensure(std::max<uint64_t>(n, 1) * kListCap));
         HIPCHK(c, c->exc_n.ensure(std::max<uint64_t>(n, 1) * sizeof(uint32_t)));
-        HIPCHK(c, c->keys.ensure(std::max<uint64_t>(n, 1) * sizeof(uint32_t)));
+        // (keys [n], then the counts of the sparse-plane planner [n]: one buffer, one transfer)
+        HIPCHK(c, c->keys.ensure(std::max<uint64_t>(n, 1) * 2 * sizeof(uint32_t)));
         HIPCHK(c, c->tailhist.ensure(std::max<uint64_t>(n, 1) * 64));
         HIPCHK(c, c->hist.ensure(std::max<uint64_t>(n, 1) * 64 * sizeof(uint32_t)));
         HIPCHK(c, launch_selfhist_card(c->stream, c->regs, need_from, n, c->p, estim, c->emax, c->elow,
                                        (uint32_t *)c->hist.ptr, c->exc.ptr, (uint8_t *)c->excv.ptr,
                                        (uint32_t *)c->exc_n.ptr, (uint32_t *)c->keys.ptr,
-                                       (uint8_t *)c->tailhist.ptr));
+                                       (uint8_t *)c->tailhist.ptr, (uint32_t *)c->keys.ptr + n));
         // the keys travel to the host right behind the per-sketch pass (the column order is made there); the
         // cardinalities follow on the stream while the host sorts
-        HIPCHK(c, c->pin_keys.ensure(std::max<uint64_t>(n, 1) * sizeof(uint32_t)));
+        HIPCHK(c, c->pin_keys.ensure(std::max<uint64_t>(n, 1) * 2 * sizeof(uint32_t)));
         c->hk32 = (const uint32_t *)c->pin_keys.ptr;
-        if (n > need_from)
+        c->hg32 = c->hk32 + n;
+        if (n > need_from)  // (the keys from need_from on and every count: the counts in front of need_from are never read)
             HIPCHK(c, hipMemcpyAsync((uint32_t *)c->pin_keys.ptr + need_from, (const uint32_t *)c->keys.ptr + need_from,
-                                     (n - need_from) * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+                                     (2 * n - need_from) * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, c->ev_keys.ensure());
         HIPCHK(c, hipEventRecord(c->ev_keys, c->stream));
         HIPCHK(c, launch_card_from_hist(c->stream, (const uint32_t *)c->hist.ptr, (const uint32_t *)c->keys.ptr, need_from, n,
@@ -126,7 +128,8 @@ int prepare(dsh_ctx *c, int estim, int want_sorted, bool card_only, uint64_t wan
         plan::Layout &L = c->lay;
         if (!reuse_host_layout)
             plan::build_layout(k32, n, want_sorted, want_rb, want_re, parts, L, rowsorted ? std::max<uint32_t>(nparts, 1) : 0,
-                               extra->empty() ? nullptr : extra);
+                               extra->empty() ? nullptr : extra, c->hg32);
+        ++c->lay_serial;
         c->lay_built = true;
         c->cum_bytes = c->p <= 15 ? 2 : 4;
         const uint64_t m = 1ull << c->p;
@@ -269,6 +272,21 @@ JobLayout choose_layout(const dsh_ctx *c, const PairJob &job)
     return jl;
 }
 
+// sparse outer planes (kernels_sparseplane.hip): the stride of a list row, and what a slab (table, lists, lengths) takes of
+// the kSparseSlabBudget a call's slabs may fill (C3: 237 slabs of 576 KiB)
+constexpr uint64_t kSparseSlabBudget = 2ull << 30;
+uint32_t sparse_list_stride(const dsh_ctx *c)
+{
+    return std::max<uint32_t>(8, (std::min<uint32_t>((uint32_t)c->sparse_cap, plan::kSparseCapMax) + 7) / 8 * 8);
+}
+// the table's placement: a word of it staged in LDS up to p = 15 (option sparse_lds = 0: gathered from global memory, the
+// arm the measurements compare against); at p = 16 a word is 256 KiB and the table is always gathered
+int sparse_wordmajor(const dsh_ctx *c) { return c->sparse_lds && c->p <= 15 ? 1 : 0; }
+uint64_t sparse_slab_bytes(const dsh_ctx *c)
+{
+    return ((uint64_t)16 << c->p) + (uint64_t)kTile * sparse_list_stride(c) * sizeof(uint16_t) + kTile * sizeof(uint32_t);
+}
+
 plan::Tuning tuning_of(const dsh_ctx *c)
 {
     plan::Tuning tu;
@@ -283,6 +301,10 @@ plan::Tuning tuning_of(const dsh_ctx *c)
     tu.part_band_tiles = (uint32_t)c->part_band_tiles;
     tu.overflow_frag_max_permille = (uint32_t)c->overflow_frag_permille;
     tu.tail_bands = (uint32_t)c->tail_bands;
+    tu.p = c->p;
+    tu.sparse_planes = c->sparse_planes;
+    tu.sparse_cap = (uint32_t)c->sparse_cap;
+    tu.sparse_max_slabs = (uint32_t)std::min<uint64_t>(1u << 16, kSparseSlabBudget / sparse_slab_bytes(c));
     return tu;
 }
 
@@ -405,6 +427,63 @@ int upload_band(dsh_ctx *c, PairRun &r, size_t bi)
     return DSH_OK;
 }
 
+// The slabs of the call's sparse items (built unless the buffers hold exactly them, of this layout) and the items
+// themselves on the device.  Behind prepare() on the same stream: the bit-plane matrix the slabs are made from is there.
+int prepare_sparse(dsh_ctx *c)
+{
+    const plan::PairPlan &pp = c->pp;
+    const plan::Layout &L = c->lay;
+    const size_t ns = pp.slabs.size(), ni = pp.sp_items.size();
+    const uint32_t cap = sparse_list_stride(c);
+    const uint64_t m = 1ull << c->p;
+    static_assert(sizeof(plan::U2) == sizeof(uint2), "plan::U2 must have the layout of uint2");
+    HIPCHK(c, c->sp_items.ensure(ni * sizeof(uint4)));
+    HIPCHK(c, c->sp_slabs.ensure(ns * sizeof(uint2)));
+    const size_t ib = ni * sizeof(uint4), sb = ns * sizeof(uint2);
+    HIPCHK(c, c->st_sparse.room(ib + sb));
+    uint8_t *h = (uint8_t *)c->st_sparse.ptr();
+    std::memcpy(h, pp.sp_items.data(), ib);
+    std::memcpy(h + ib, pp.slabs.data(), sb);
+    HIPCHK(c, launch_upload(c->stream, c->sp_items.ptr, h, ib));
+    const bool have = c->sp_serial == c->lay_serial && c->sp_cap_have == (cap | (uint32_t)sparse_wordmajor(c) << 31) && c->sp_have.size() == ns &&
+                      std::memcmp(c->sp_have.data(), pp.slabs.data(), sb) == 0;
+    if (!have) {
+        DeviceTimer timer(c, c->stream);
+        c->sp_have.clear();
+        HIPCHK(c, launch_upload(c->stream, c->sp_slabs.ptr, h + ib, sb));
+        HIPCHK(c, c->sp_tab.ensure(ns * m * 16));
+        HIPCHK(c, c->sp_lists.ensure(ns * kTile * (size_t)cap * sizeof(uint16_t)));
+        HIPCHK(c, c->sp_len.ensure(ns * kTile * sizeof(uint32_t)));
+        HIPCHK(c, launch_sparse_build(c->stream, (const uint32_t *)c->planes.ptr, L.Npad, c->W, L.ncols, (const uint2 *)c->sp_slabs.ptr,
+                                      (uint32_t)ns, cap, sparse_wordmajor(c), (uint32_t *)c->sp_tab.ptr, (uint16_t *)c->sp_lists.ptr, (uint32_t *)c->sp_len.ptr));
+        c->sp_have = pp.slabs;
+        c->sp_serial = c->lay_serial;
+        c->sp_cap_have = cap | (uint32_t)sparse_wordmajor(c) << 31;
+        timer.stop(c->prep_ms, /*add=*/true);
+    }
+    HIPCHK(c, c->st_sparse.sent(c->stream));
+    return DSH_OK;
+}
+
+// the band's sparse items, in front of its tile kernel: both fill the band's C(v), k_finalize needs both
+int launch_sparse_items(dsh_ctx *c, size_t bi, uint64_t nslots)
+{
+    const plan::PairPlan &pp = c->pp;
+    if (bi >= pp.band_sp_items.size()) return DSH_OK;
+    const auto &rg = pp.band_sp_items[bi];
+    if (rg.first == rg.second) return DSH_OK;
+    hipEvent_t a = c->profiling ? next_event(c) : nullptr, b = c->profiling ? next_event(c) : nullptr;
+    if (a && b) (void)hipEventRecord(a, c->stream);
+    HIPCHK(c, launch_sparse_count(c->stream, c->cum_bytes, (const uint4 *)c->sp_items.ptr + rg.first, (uint32_t)(rg.second - rg.first),
+                                  sparse_wordmajor(c), (const uint32_t *)c->sp_tab.ptr, (const uint16_t *)c->sp_lists.ptr, (const uint32_t *)c->sp_len.ptr,
+                                  sparse_list_stride(c), 1u << c->p, c->cum.ptr, nslots));
+    if (a && b) {
+        (void)hipEventRecord(b, c->stream);
+        c->ev_sparse.emplace_back(a, b);
+    }
+    return DSH_OK;
+}
+
 int launch_tile_kernel(dsh_ctx *c, const PairRun &r, size_t bi, uint64_t nslots)
 {
     const plan::Layout &L = c->lay;
@@ -483,6 +562,13 @@ int read_profile(dsh_ctx *c, const PairRun &r)
         (void)hipEventElapsedTime(&ms, e.first, e.second);
         c->fin_ms += ms;
     }
+    c->sparse_ms = 0;
+    for (auto &e : c->ev_sparse) {  // (inside the tile kernels' intervals above: pair_ms holds them too)
+        float ms = 0;
+        (void)hipEventElapsedTime(&ms, e.first, e.second);
+        c->sparse_ms += ms;
+    }
+    c->ev_sparse.clear();
     // when every part of the call was final (from the start of the call, prepare included) and how many floats of the
     // rank's buffer it holds: what a model of the pipelined exchange needs (dsh_last_part_info)
     auto fill_part_floats = [&] {  // how many floats of the rank's buffer every part holds
@@ -579,6 +665,8 @@ int run_pairs(dsh_ctx *c, const PairJob &job)
         HIPCHK(c, hipMemsetAsync(c->phase_cyc.ptr, 0, 16 * sizeof(unsigned long long), c->stream));
     }
     r.fin = finalize_invariants(c, job, jl.with_extra);
+    c->ev_sparse.clear();
+    if (!pp.sp_items.empty() && (rc = prepare_sparse(c))) return rc;
     for (size_t bi = 0; bi < pp.bands.size(); ++bi) {
         const uint64_t nslots = (uint64_t)(pp.bands[bi].second - pp.bands[bi].first) * kTile * kTile;
         if ((rc = upload_band(c, r, bi))) return rc;
@@ -589,6 +677,7 @@ int run_pairs(dsh_ctx *c, const PairJob &job)
             d = next_event(c);
             if (a) (void)hipEventRecord(a, c->stream);
         }
+        if ((rc = launch_sparse_items(c, bi, nslots))) return rc;
         if ((rc = launch_tile_kernel(c, r, bi, nslots))) return rc;
         if (b) (void)hipEventRecord(b, c->stream);
         if (bi == 0) {  // (the destination of an exchange may post its receives behind its first tile kernel, exchange.hip)

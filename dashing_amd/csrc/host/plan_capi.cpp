@@ -21,6 +21,16 @@ using namespace dsh::plan;
 
 namespace {
 
+// sparse outer planes (plan.h, Tuning): what dshh_plan_check_sparse adds to a check -- the per-sketch counts, the two
+// options, and where the routes go (5 words per tile: row block, column block, plane begin, plane end, planes routed sparse)
+struct SparseCheck {
+    const uint32_t *gcnt = nullptr;
+    int planes = 0;
+    uint32_t cap = 0;
+    uint32_t *routes = nullptr;
+    uint64_t routes_cap = 0;  // tiles `routes` has room for
+};
+
 struct Err {
     char *buf;
     size_t cap;
@@ -49,7 +59,7 @@ struct Err {
 static int plan_check(uint64_t n, const uint32_t *keys, int mode, int want_sorted, uint64_t rb, uint64_t re, uint64_t cb,
                       uint64_t ce, uint32_t nparts, int want_parts, int p, uint64_t cum_budget, int lockstep, int nsplit,
                       int ls_item_chunks, const std::vector<uint64_t> &extra, uint64_t *stats, char *err, size_t cap,
-                      uint32_t round_items = 0)
+                      uint32_t round_items = 0, const SparseCheck *sc = nullptr)
 {
     Err E{err, cap};
     if (re > n) re = n;
@@ -63,7 +73,8 @@ static int plan_check(uint64_t n, const uint32_t *keys, int mode, int want_sorte
     if (want_sorted && !rowsorted) range_parts(n, lrb, lre, std::max<uint32_t>(want_parts ? nparts : 1, 1), parts);
     if (!extra.empty() && !(want_sorted && mode == 0)) return E.fail("extra segments need a sorted triangle layout");
     Layout L;
-    build_layout(keys, n, want_sorted, lrb, lre, parts, L, rowsorted ? std::max<uint32_t>(nparts, 1) : 0, extra.empty() ? nullptr : &extra);
+    build_layout(keys, n, want_sorted, lrb, lre, parts, L, rowsorted ? std::max<uint32_t>(nparts, 1) : 0, extra.empty() ? nullptr : &extra,
+                 sc ? sc->gcnt : nullptr);
     // the wanted segments, main range first
     std::vector<std::pair<uint64_t, uint64_t>> wsegs;  // (the wanted order: extra segments first, then the main range)
     wanted_order(n, lrb, lre, &extra, wsegs, rowsorted);
@@ -149,6 +160,8 @@ static int plan_check(uint64_t n, const uint32_t *keys, int mode, int want_sorte
     tu.ls_item_chunks = ls_item_chunks;
     if (round_items) tu.round_items = round_items;
     if (round_items > 512) tu.small_round_items = 512;  // (as engine.hip under pair_groups = auto)
+    tu.p = p;
+    if (sc) tu.sparse_planes = sc->planes, tu.sparse_cap = sc->cap;
     PairQuery q;
     q.rect = mode == 1;
     q.sorted_rows = mode == 2;
@@ -298,6 +311,60 @@ static int plan_check(uint64_t n, const uint32_t *keys, int mode, int want_sorte
         }
     }
     if (at != T.size()) return E.fail("bands end at %zu of %zu tiles", at, T.size());
+    // ---- sparse outer planes: every plane of a tile's range is in the tile's chunk range (checked above against
+    // pp.chunks) or has exactly one sparse item, never both; a routed plane's sets are inside the cap
+    if (pp.sp.size() != T.size() || pp.band_sp_items.size() != pp.bands.size()) return E.fail("sparse bookkeeping sizes differ");
+    {
+        const uint32_t cpp_ = tu.W >= (uint32_t)tu.kc ? tu.W / tu.kc : 1;
+        std::vector<uint8_t> seen_pl;
+        size_t sat = 0;
+        for (size_t bi = 0; bi < pp.bands.size(); ++bi) {
+            const auto &bd = pp.bands[bi];
+            const auto &rg = pp.band_sp_items[bi];
+            if (rg.first != sat || rg.second < rg.first || rg.second > pp.sp_items.size()) return E.fail("sparse items of band %zu do not follow %zu", bi, sat);
+            sat = rg.second;
+            seen_pl.assign((bd.second - bd.first) * 2, 0);
+            for (size_t k = rg.first; k < rg.second; ++k) {
+                const U4 &I = pp.sp_items[k];
+                if (I.x >= bd.second - bd.first) return E.fail("sparse item %zu names tile %u of band %zu", k, I.x, bi);
+                const size_t t = bd.first + I.x;
+                const uint32_t sp = pp.sp[t];
+                if (I.y >= T[t].w || I.y + sp < T[t].w) return E.fail("sparse item %zu: plane %u is not one of the top %u of tile %zu", k, I.y, sp, t);
+                if (seen_pl[I.x * 2 + (T[t].w - 1 - I.y)]++) return E.fail("plane %u of tile %zu has two sparse items", I.y, t);
+                if (I.z >= pp.slabs.size() || I.w >= pp.slabs.size() || pp.slabs[I.z].x != T[t].x || pp.slabs[I.z].y != I.y ||
+                    pp.slabs[I.w].x != T[t].y || pp.slabs[I.w].y != I.y)
+                    return E.fail("sparse item %zu names the wrong slabs", k);
+                const int v = L.pbase + 1 + (int)I.y;
+                if (sparse_bound(L, T[t].x, v) > tu.sparse_cap || sparse_bound(L, T[t].y, v) > tu.sparse_cap) return E.fail("sparse item %zu: a set may exceed the cap", k);
+                // the bound holds for every sketch of the two blocks (what the lists and counters are sized by)
+                if (sc && sc->gcnt)
+                    for (int side = 0; side < 2; ++side)
+                        for (uint32_t a = 0; a < kTile; ++a) {
+                            const uint64_t sx = (uint64_t)(side ? T[t].y : T[t].x) * kTile + a;
+                            if (sx >= L.ncols) continue;
+                            const uint32_t key = keys[orig(sx)], g = sc->gcnt[orig(sx)];
+                            const uint32_t own = v >= key_T(key) ? (g & 0xFFFFu) : v == key_T(key) - 1 ? g >> 16 : 65535u;
+                            if (own > tu.sparse_cap) return E.fail("sparse item %zu: sketch %llu may hold %u positions", k, (unsigned long long)orig(sx), own);
+                        }
+            }
+            for (size_t t = bd.first; t < bd.second; ++t) {
+                const uint32_t sp = pp.sp[t];
+                if (sp > 2 || sp > T[t].w - T[t].z) return E.fail("tile %zu routes %u planes of %u", t, sp, T[t].w - T[t].z);
+                for (uint32_t x = 0; x < sp; ++x)
+                    if (!seen_pl[(t - bd.first) * 2 + x]) return E.fail("routed plane %u of tile %zu has no sparse item", T[t].w - 1 - x, t);
+                if (tu.W >= (uint32_t)tu.kc && (pp.chunks[t].x != T[t].z * cpp_ || pp.chunks[t].y != (T[t].w - sp) * cpp_))
+                    return E.fail("tile %zu: the dense chunk range is not the planes left over", t);
+            }
+        }
+        if (sat != pp.sp_items.size()) return E.fail("sparse items end at %zu of %zu", sat, pp.sp_items.size());
+        if (sc && sc->routes) {
+            if (T.size() > sc->routes_cap) return E.fail("%zu tiles, room for %llu routes", T.size(), (unsigned long long)sc->routes_cap);
+            for (size_t t = 0; t < T.size(); ++t) {
+                uint32_t *o = sc->routes + 5 * t;
+                o[0] = T[t].x, o[1] = T[t].y, o[2] = T[t].z, o[3] = T[t].w, o[4] = pp.sp[t];
+            }
+        }
+    }
     for (uint32_t qd = 0; qd < pp.nparts; ++qd)
         if (part_done[qd] != 1) return E.fail("part %u never completes", qd);
     if (pp.nparts) {  // the tile counts the signalling k_finalize waits for
@@ -351,6 +418,7 @@ static int plan_check(uint64_t n, const uint32_t *keys, int mode, int want_sorte
     stats[3] = pp.nparts;
     stats[4] = T.empty() ? 0 : planes_sum * 100 / T.size();
     // rounds of the lockstep tile kernel over all bands (a band of k items takes ceil(k / round_items) rounds)
+    if (sc) stats[10] = pp.sp_items.size(), stats[11] = pp.slabs.size();
     stats[7] = 0;
     for (size_t b = 0; b < pp.band_items.size(); ++b) {
         const uint32_t nfr = b < pp.band_frags.size() ? pp.band_frags[b] : 0u;
@@ -379,6 +447,26 @@ int dshh_plan_check_ri(uint64_t n, const uint32_t *keys, int mode, int want_sort
     if (round_items == 0 || round_items % 256) return E.fail("round_items %u is not a positive multiple of 256", round_items);
     return plan_check(n, keys, mode, want_sorted, rb, re, cb, ce, nparts, want_parts, p, cum_budget, lockstep, nsplit, ls_item_chunks,
                       std::vector<uint64_t>(), stats, err, cap, round_items);
+}
+
+// the same with the sparse outer planes planned (plan.h, Tuning::sparse_planes): gcnt = the per-sketch counts g0 | g1 << 16
+// next to the keys (NULL: none), sparse_planes / sparse_cap the two options.  stats gets twelve slots: [10] sparse items,
+// [11] slabs.  routes (or NULL): 5 words per tile -- row block, column block, plane begin, plane end, planes routed sparse.
+int dshh_plan_check_sparse(uint64_t n, const uint32_t *keys, const uint32_t *gcnt, int mode, int want_sorted, uint64_t rb, uint64_t re,
+                           uint32_t nparts, int want_parts, int p, uint64_t cum_budget, uint32_t round_items, int sparse_planes,
+                           uint32_t sparse_cap, uint64_t *stats, uint32_t *routes, uint64_t routes_cap, char *err, size_t cap)
+{
+    Err E{err, cap};
+    if (round_items == 0 || round_items % 256) return E.fail("round_items %u is not a positive multiple of 256", round_items);
+    SparseCheck sc;
+    sc.gcnt = gcnt;
+    sc.planes = sparse_planes;
+    sc.cap = sparse_cap;
+    sc.routes = routes;
+    sc.routes_cap = routes_cap;
+    stats[10] = stats[11] = 0;
+    return plan_check(n, keys, mode, want_sorted, rb, re, 0, 0, nparts, want_parts, p, cum_budget, 1, 0, 64, std::vector<uint64_t>(), stats, err,
+                      cap, round_items, &sc);
 }
 
 // the rows of ONE rank of a row-set table (plan.h): main range + extra segments, row-sorted parts (rowsorted != 0: what a

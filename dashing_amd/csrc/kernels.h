@@ -9,7 +9,7 @@ namespace dsh {
 
 hipError_t launch_selfhist_card(hipStream_t st, const uint8_t *regs, uint64_t first, uint64_t n, int p, int estim,
                                 int emax, int elow, uint32_t *hist, void *exc, uint8_t *excv, uint32_t *exc_n,
-                                uint32_t *keys, uint8_t *tailhist);
+                                uint32_t *keys, uint8_t *tailhist, uint32_t *gcnt);
 hipError_t launch_card_from_hist(hipStream_t st, const uint32_t *hist, const uint32_t *keys, uint64_t first, uint64_t n, int p,
                                  int estim, double *card);
 // position index of every 128-column block of the plane layout (perm == nullptr: identity) and the per-column side
@@ -41,6 +41,19 @@ hipError_t launch_pair_counts(hipStream_t st, int kc, int cum_bytes, const uint3
                               uint32_t Npad, uint32_t Kpad, uint32_t W, uint32_t P,
                               const uint4 *tiles, const uint4 *items, uint32_t nitems, void *cum,
                               uint64_t nslots);
+
+// sparse outer planes (kernels_sparseplane.hip; plan.h, Tuning::sparse_planes).  launch_sparse_build: for each of the nslabs
+// {block, plane} of `slabs`, from that plane's words of the bit-plane matrix, tab[slab][2^p][4] (bit j of a position's 128:
+// column j of the block has a register >= the plane's threshold there), lists[slab][128][cap] (every column's such
+// positions, 16-bit) and len[slab][128] (their number; cleared here first).  cap: a multiple of 8.  wordmajor: the table as
+// tab[slab][4][2^p], which the LDS placement of the counting kernel stages a word of (2^p <= 2^15); the two launchers of
+// a call take the same value.
+hipError_t launch_sparse_build(hipStream_t st, const uint32_t *planes, uint32_t Npad, uint32_t W, uint64_t ncols, const uint2 *slabs,
+                               uint32_t nslabs, uint32_t cap, int wordmajor, uint32_t *tab, uint16_t *lists, uint32_t *len);
+// one workgroup per item {tile index in band, plane, slab of the row block, slab of the column block}: the plane's C(v) of
+// the tile's 128 x 128 pairs, stored where the tile kernel stores it; m = 2^p
+hipError_t launch_sparse_count(hipStream_t st, int cum_bytes, const uint4 *items, uint32_t nitems, int wordmajor, const uint32_t *tab,
+                               const uint16_t *lists, const uint32_t *len, uint32_t cap, uint32_t m, void *cum, uint64_t nslots);
 
 // what-if variant on the matrix cores (option "pair_mfma"; never the default: the north star excludes MFMA)
 // the same arithmetic with the waves of a SIMD kept in one instruction class: workgroups of 256 * groups threads with
@@ -412,6 +425,7 @@ hipError_t launch_fastx_decode(hipStream_t st, const uint8_t *raw, const FastxCh
 // dsh_preload: load the code objects of the kernel translation units now (else: at the first launch from each)
 hipError_t preload_compare_kernels();
 hipError_t preload_hist_kernels();      // (part of the compare set)
+hipError_t preload_sparseplane_kernels();  // (part of the compare set: kernels_sparseplane.hip)
 hipError_t preload_knn_kernels();       // (part of the compare set: knn.hip)
 hipError_t preload_exchange_kernels();  // (part of the compare set: exchange.hip)
 hipError_t preload_fastx_kernels();

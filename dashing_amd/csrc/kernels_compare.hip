@@ -61,7 +61,8 @@ __global__ __launch_bounds__(256, 4) void k_selfhist_card(const uint8_t *__restr
                                                         uint8_t *__restrict__ excv,
                                                         uint32_t *__restrict__ exc_n,
                                                         uint32_t *__restrict__ keys,
-                                                        uint8_t *__restrict__ tailhist)
+                                                        uint8_t *__restrict__ tailhist,
+                                                        uint32_t *__restrict__ gcnt)
 {
     __shared__ uint32_t hist[4][64];
     __shared__ uint32_t sub[4][8][72];  // 8 privatised copies per wave: the register values pile up in ~8 bins, so
@@ -149,6 +150,10 @@ __global__ __launch_bounds__(256, 4) void k_selfhist_card(const uint8_t *__restr
         // the host derives the global ranges from the keys (no same-address global atomics: 3 x N of them cost
         // ~12 ns each) and orders the columns by them
         keys[s] = ((uint32_t)hi << 18) | ((uint32_t)T << 12) | ((uint32_t)L << 6) | (uint32_t)lo;
+        // for the planner of the sparse outer planes (plan.h, kernels_sparseplane.hip): how many registers are >= T and
+        // >= T - 1, the sizes of the sets the two top planes' complements are, saturating 16-bit each
+        const uint32_t g0 = cnt + h[T], g1 = g0 + (T > 0 ? h[T - 1] : 0u);
+        gcnt[s] = (g0 < 65535u ? g0 : 65535u) | ((g1 < 65535u ? g1 : 65535u) << 16);
     }
     if (s < n && __any(bad != 0) && lane == 0) atomicOr(&keys[s], 0x80000000u);  // (after lane 0's plain store above)
     __syncthreads();
@@ -1638,16 +1643,16 @@ hipError_t launch_upload(hipStream_t st, void *dst, const void *src_pinned, size
 // launch wrappers (host)
 hipError_t launch_selfhist_card(hipStream_t st, const uint8_t *regs, uint64_t first, uint64_t n, int p, int estim,
                                 int emax, int elow, uint32_t *hist, void *exc, uint8_t *excv, uint32_t *exc_n,
-                                uint32_t *keys, uint8_t *tailhist)
+                                uint32_t *keys, uint8_t *tailhist, uint32_t *gcnt)
 {
     if (n <= first) return hipSuccess;
     const uint32_t blocks = (uint32_t)((n - first + 3) / 4);
     if (p <= 15)
         hipLaunchKernelGGL(k_selfhist_card<uint16_t>, dim3(blocks), dim3(256), 0, st, regs, first, n, p, estim, emax, elow,
-                           hist, (uint16_t *)exc, excv, exc_n, keys, tailhist);
+                           hist, (uint16_t *)exc, excv, exc_n, keys, tailhist, gcnt);
     else
         hipLaunchKernelGGL(k_selfhist_card<uint32_t>, dim3(blocks), dim3(256), 0, st, regs, first, n, p, estim, emax, elow,
-                           hist, (uint32_t *)exc, excv, exc_n, keys, tailhist);
+                           hist, (uint32_t *)exc, excv, exc_n, keys, tailhist, gcnt);
     return hipGetLastError();
 }
 

@@ -490,7 +490,8 @@ void tile_planes(const Layout &L, uint32_t ti, uint32_t tj, int &pb, int &pe)
 }
 
 void build_layout(const uint32_t *k32, uint64_t n, int want_sorted, uint64_t rb, uint64_t re,
-                  const std::vector<uint64_t> &parts, Layout &L, uint32_t rowsorted_nparts, const std::vector<uint64_t> *extra_in)
+                  const std::vector<uint64_t> &parts, Layout &L, uint32_t rowsorted_nparts, const std::vector<uint64_t> *extra_in,
+                  const uint32_t *gcnt)
 {
     if (re > n) re = n;
     if (!want_sorted) rb = 0, re = n;
@@ -598,6 +599,8 @@ void build_layout(const uint32_t *k32, uint64_t n, int want_sorted, uint64_t rb,
     L.blk_lo.assign(NT, 255);
     L.blk_L.assign(NT, 255);
     L.blk_hi.assign(NT, 0);
+    L.blk_g0.assign(gcnt ? NT : 0, 0);
+    L.blk_g1.assign(gcnt ? NT : 0, 0);
     int pbase = vr[2];
     const uint32_t *perm = L.perm.data();
     for (uint32_t b = 0; b < NT; ++b) {  // (a block at a time, its four statistics in registers)
@@ -615,6 +618,18 @@ void build_layout(const uint32_t *k32, uint64_t n, int want_sorted, uint64_t rb,
         L.blk_L[b] = (uint8_t)bl;
         L.blk_hi[b] = (uint8_t)bhi;
         pbase = std::min(pbase, bl);
+        if (gcnt) {
+            // A sketch has g0 registers >= its own T_i <= bt, so at most g0 registers >= v for every v >= bt; and >= bt - 1:
+            // g1 of them where T_i = bt, at most g0 where T_i < bt
+            uint32_t g0 = 0, g1 = 0;
+            for (uint64_t s = s0; s < s1; ++s) {
+                const uint32_t g = gcnt[perm[s]];
+                g0 = std::max(g0, g & 0xFFFFu);
+                g1 = std::max(g1, key_T(k32[perm[s]]) == bt ? g >> 16 : g & 0xFFFFu);
+            }
+            L.blk_g0[b] = (uint16_t)g0;
+            L.blk_g1[b] = (uint16_t)g1;
+        }
     }
     // dense planes cover v in (pbase, Tmax]: below the smallest low threshold every C(v) comes from the list join
     L.pbase = pbase;
@@ -647,6 +662,24 @@ static void xcd_order(std::vector<U4> &t, std::vector<uint32_t> &rank, size_t b,
     std::copy(rtmp.begin(), rtmp.begin() + q, rank.begin() + b);
 }
 
+uint32_t sparse_bound(const Layout &L, uint32_t b, int v)
+{
+    if (b >= L.blk_g0.size()) return 65535u;
+    const int Tb = L.blk_T[b];
+    return v >= Tb ? L.blk_g0[b] : v == Tb - 1 ? L.blk_g1[b] : 65535u;
+}
+
+// how many planes of the tile {ti, tj, pb, pe} leave the tile kernel, from the top of its range (plan.h, Tuning)
+static uint32_t sparse_route(const Layout &L, uint32_t cap, int nplanes, const U4 &t)
+{
+    uint32_t k = 0;
+    for (; (int)k < nplanes && t.w - k > t.z; ++k) {
+        const int v = L.pbase + (int)(t.w - k);  // plane pl is the threshold pbase + 1 + pl; pl = t.w - 1 - k
+        if (std::max(sparse_bound(L, t.x, v), sparse_bound(L, t.y, v)) > cap) break;
+    }
+    return k;
+}
+
 static void tile_vrange(const Layout &L, const U4 &t, int &lo, int &hi)
 {
     lo = std::min<int>(L.blk_lo[t.x], L.blk_lo[t.y]);
@@ -664,6 +697,10 @@ bool build_tiles(const Layout &L, const PairQuery &job, const Tuning &tu, PairPl
     pp.items.clear();
     pp.band_frags.clear();
     pp.band_round.clear();
+    pp.sp.clear();
+    pp.sp_items.clear();
+    pp.band_sp_items.clear();
+    pp.slabs.clear();
     pp.nparts = 0;
     pp.max_band = 0;
     const uint32_t NT = L.Npad / kTile;
@@ -713,6 +750,15 @@ bool build_tiles(const Layout &L, const PairQuery &job, const Tuning &tu, PairPl
         }
     }
     if (T.empty()) return false;
+    // sparse outer planes (plan.h, Tuning): which calls may route at all, and how many planes of a tile at most
+    const uint32_t sp_cap = std::min(tu.sparse_cap, kSparseCapMax);
+    const bool sp_can = tu.sparse_planes != 0 && !job.rect && !job.sorted_rows && L.sorted && !L.blk_g0.empty() && tu.lockstep &&
+                        tu.nsplit == 0 && tu.W >= (uint32_t)tu.kc && tu.p >= 9 && tu.p <= 16 && (tu.sparse_planes > 0 || tu.p >= 13);
+    const int sp_planes = !sp_can ? 0 : tu.sparse_planes < 0 ? kSparseAutoPlanes : std::min(tu.sparse_planes, 2);
+    const uint64_t sp_min_planes = tu.sparse_planes < 0 ? std::max<uint64_t>(tu.small_round_items, 512) : 0;  // a band with more than this
+    uint64_t job_planes = 0;
+    for (const U4 &t : T) job_planes += t.w - t.z;
+    const int sp_planes_job = job_planes > sp_min_planes ? sp_planes : 0;  // (what the cuts below are estimated with)
     // bands bounded by the cum scratch budget
     pp.per_tile_bytes = (uint64_t)kTile * kTile * tu.cum_bytes * std::max<uint32_t>(L.P, 1);
     // (at most 2^16 tiles per band: k_finalize addresses a pair slot of the band with 32 bits)
@@ -755,8 +801,9 @@ bool build_tiles(const Layout &L, const PairQuery &job, const Tuning &tu, PairPl
         // a longer launch takes pieces of 2-4 planes, i.e. longer rounds.  Jobs of up to 64 rounds are therefore cut into
         // bands of at most 16: the head as well as the tails (2 ranks of BASELINE configs[2]: 27 rounds = 15 + 9 + 3
         // instead of ONE launch of 15 two-plane rounds whose first part is final after 6 ms).
+        auto dense_planes = [&](const U4 &t) -> uint64_t { return t.w - t.z - (sp_planes_job ? sparse_route(L, sp_cap, sp_planes_job, t) : 0u); };
         uint64_t items = 0;
-        for (const U4 &t : T) items += t.w - t.z;
+        for (const U4 &t : T) items += dense_planes(t);
         const uint64_t R = (items + RI - 1) / RI;
         constexpr uint64_t kBandRounds = 16;
         for (uint32_t ntails = tu.tail_bands; ntails >= 1 && cuts.empty() && items <= 4 * kBandRounds * RI && R >= 3; --ntails) {
@@ -787,9 +834,9 @@ bool build_tiles(const Layout &L, const PairQuery &job, const Tuning &tu, PairPl
             uint64_t acc = 0, rounds = 0, band_items = 0;
             size_t t = 0;
             for (size_t b = 0; b + 1 < quota.size(); ++b) {
-                while (t < T.size() && band_items + (T[t].w - T[t].z) <= quota[b] * RI) {
-                    acc += T[t].w - T[t].z;
-                    band_items += T[t].w - T[t].z;
+                while (t < T.size() && band_items + dense_planes(T[t]) <= quota[b] * RI) {
+                    acc += dense_planes(T[t]);
+                    band_items += dense_planes(T[t]);
                     ++t;
                 }
                 if (t == 0 || t >= T.size() || (!cuts.empty() && cuts.back() == t)) continue;
@@ -840,13 +887,79 @@ bool build_tiles(const Layout &L, const PairQuery &job, const Tuning &tu, PairPl
             for (size_t t = sg.b; t < sg.e; ++t) rank[t] = (uint32_t)(t - sg.b);
     for (auto &sv : pp.segs)
         for (auto &sg : sv) xcd_order(T, rank, sg.b, sg.e, tu.lockstep ? 2 : 1);
-    // chunk range of every tile (the work items of a band are cut from these: build_band_items)
+    // sparse outer planes: band by band (the automatic rule looks at the band), the routed planes of every tile, one sparse
+    // item each -- ordered by column block, whose table the items of a column share in L2 -- and the slabs they read
+    pp.sp.assign(T.size(), 0);
+    pp.band_sp_items.assign(pp.bands.size(), std::make_pair((size_t)0, (size_t)0));
+    if (sp_planes) {
+        pp.slab_of.assign((size_t)NT * std::max<uint32_t>(L.P, 1), -1);
+        auto slab = [&](uint32_t b, uint32_t pl) -> uint32_t {
+            int32_t &s = pp.slab_of[(size_t)b * L.P + pl];
+            if (s < 0) {
+                s = (int32_t)pp.slabs.size();
+                pp.slabs.push_back(U2{b, pl});
+            }
+            return (uint32_t)s;
+        };
+        for (size_t bi = 0; bi < pp.bands.size(); ++bi) {
+            const auto &bd = pp.bands[bi];
+            const size_t i0 = pp.sp_items.size();
+            uint64_t band_planes = 0;
+            for (size_t t = bd.first; t < bd.second; ++t) band_planes += T[t].w - T[t].z;
+            if (band_planes > sp_min_planes)
+                for (size_t t = bd.first; t < bd.second; ++t) {
+                    const uint32_t k = sparse_route(L, sp_cap, sp_planes, T[t]);
+                    if (!k || pp.slabs.size() + 2 * k > tu.sparse_max_slabs) continue;
+                    pp.sp[t] = (uint8_t)k;
+                    for (uint32_t x = 0; x < k; ++x) {
+                        const uint32_t pl = T[t].w - 1 - x;
+                        pp.sp_items.push_back(U4{(uint32_t)(t - bd.first), pl, slab(T[t].x, pl), slab(T[t].y, pl)});
+                    }
+                }
+            // Launch order.  An item gathers from its column block's table (16 bytes per position: 256 KiB at p = 14), which
+            // only pays while the table stays in L2; workgroup w runs on XCD w % 8 (xcd_order above).  So every column
+            // block is given to ONE XCD -- the blocks with the most items first, each to the XCD with the fewest so far --
+            // its items follow each other there, and the eight lists are interleaved one item at a time.
+            const size_t cnt = pp.sp_items.size() - i0;
+            if (cnt > 1) {
+                constexpr size_t nx = 8;
+                std::vector<uint32_t> per_col(NT, 0), cols;
+                for (size_t k = i0; k < pp.sp_items.size(); ++k) per_col[T[bd.first + pp.sp_items[k].x].y]++;
+                for (uint32_t b = 0; b < NT; ++b)
+                    if (per_col[b]) cols.push_back(b);
+                std::stable_sort(cols.begin(), cols.end(), [&](uint32_t a, uint32_t b) { return per_col[a] > per_col[b]; });
+                std::vector<uint32_t> xcd_of(NT, 0);
+                size_t load[nx] = {0};
+                for (uint32_t b : cols) {
+                    size_t x = 0;
+                    for (size_t y = 1; y < nx; ++y)
+                        if (load[y] < load[x]) x = y;
+                    xcd_of[b] = (uint32_t)x;
+                    load[x] += per_col[b];
+                }
+                std::vector<U4> lists[nx];
+                for (size_t k = i0; k < pp.sp_items.size(); ++k) lists[xcd_of[T[bd.first + pp.sp_items[k].x].y]].push_back(pp.sp_items[k]);
+                for (auto &l : lists)
+                    std::stable_sort(l.begin(), l.end(), [&](const U4 &a, const U4 &b) {
+                        const U4 &ta = T[bd.first + a.x], &tb = T[bd.first + b.x];
+                        return ta.y != tb.y ? ta.y < tb.y : a.y != b.y ? a.y > b.y : ta.x < tb.x;
+                    });
+                size_t q = i0;
+                for (size_t r = 0; q < pp.sp_items.size(); ++r)
+                    for (size_t x = 0; x < nx; ++x)
+                        if (r < lists[x].size()) pp.sp_items[q++] = lists[x][r];
+            }
+            pp.band_sp_items[bi] = std::make_pair(i0, pp.sp_items.size());
+        }
+    }
+    // chunk range of every tile (the work items of a band are cut from these: build_band_items); the planes routed sparse
+    // are the top of the tile's range and simply left out
     const uint32_t KC = (uint32_t)tu.kc;
     const uint32_t cpp = tu.W >= KC ? tu.W / KC : 1;  // chunks per plane when a plane spans chunks
     std::vector<U2> &CR = pp.chunks;
     CR.resize(T.size());
     if (tu.W >= KC) {  // whole chunks per plane (both powers of two)
-        for (size_t t = 0; t < T.size(); ++t) CR[t] = U2{T[t].z * cpp, T[t].w * cpp};
+        for (size_t t = 0; t < T.size(); ++t) CR[t] = U2{T[t].z * cpp, (T[t].w - pp.sp[t]) * cpp};
     } else {
         for (size_t t = 0; t < T.size(); ++t)
             CR[t] = U2{(uint32_t)(((uint64_t)T[t].z * tu.W) / KC), (uint32_t)(((uint64_t)T[t].w * tu.W + KC - 1) / KC)};

@@ -158,6 +158,9 @@ struct Layout {
     bool whole = false;           // sorted over the whole collection: perm also holds its inverse at [n, 2n)
     std::vector<uint32_t> perm;   // plane-matrix column -> sketch
     std::vector<uint8_t> blk_T, blk_lo, blk_L, blk_hi;  // per block: max high threshold, min value, min low threshold, max value
+    // (sparse outer planes, below) per block, with T = blk_T: no sketch of it has more than blk_g0 registers >= v for any
+    // v >= T, nor more than blk_g1 registers >= T - 1 (saturating at 65535); empty when the layout was built without counts
+    std::vector<uint16_t> blk_g0, blk_g1;
     int vlo = 0, vhi = 0;         // register value range of the columns
     int pbase = 0;                // plane pl is the threshold pbase + 1 + pl
     uint32_t P = 0;               // dense planes
@@ -168,9 +171,11 @@ struct Layout {
 // (ignored for the identity layout).
 // rowsorted_nparts > 0 (sorted layouts only): row-sorted parts, `parts` is ignored.
 // extra (sorted layouts only): further wanted segments; the wanted range is then ONE part (`parts` is ignored).
+// gcnt (or nullptr: no plane is ever routed sparse): per sketch, next to its key, g0 | g1 << 16 of k_selfhist_card -- how
+// many of its registers are >= its T and >= T - 1
 void build_layout(const uint32_t *keys, uint64_t n, int want_sorted, uint64_t rb, uint64_t re,
                   const std::vector<uint64_t> &parts, Layout &L, uint32_t rowsorted_nparts = 0,
-                  const std::vector<uint64_t> *extra = nullptr);
+                  const std::vector<uint64_t> *extra = nullptr, const uint32_t *gcnt = nullptr);
 
 // dense plane range of the tile (ti, tj): C(v) is needed for v in (max(larger of the two minima, smaller of the two
 // low thresholds), larger of the two high thresholds] -- below that every C(v) is 0 or comes from the low-list join
@@ -183,6 +188,9 @@ struct PairQuery {
     int want_parts = 0;    // an event per part of the layout (dsh_dist_rows_parts_device_async)
     uint64_t row_begin = 0, row_end = 0, col_begin = 0, col_end = 0;
 };
+
+constexpr uint32_t kSparseCapDefault = 1280, kSparseCapMax = 2040;  // sparse outer planes (Tuning): 11 counter words hold sets up to 2047
+constexpr int kSparseAutoPlanes = 2;
 
 struct Tuning {
     uint32_t W = 0;        // 32-bit words per plane
@@ -220,6 +228,18 @@ struct Tuning {
     uint32_t tail_permille = 100;   // the last tail: one round of the tile kernel of a rank of BASELINE configs[2] over 8
     uint32_t tail_permille2 = 350;  // share of the rounds left for the tails in front of the last one
     uint32_t tail_head_min_rounds = 7;  // a tail in front of the last one must leave the head at least this many rounds
+    // Sparse outer planes.  The top plane of a tile, C(T) = #{a < T and b < T}, ANDs planes that are 97-98 % ones: the
+    // complement sets U = {t : a_t >= T} hold a few hundred of the 2^p positions, and C(v) = m - |U_i| - |U_j| + |U_i & U_j|.
+    // A (tile, plane) whose sets are all at most sparse_cap long (the bound of Layout::blk_g0 / blk_g1 over both blocks)
+    // leaves the tile kernel and is counted from position lists instead (kernels_sparseplane.hip), into the same C(v)
+    // block; the plane below it follows the same rule, only if the top one went.  sparse_planes: -1 automatic (kSparseAutoPlanes
+    // planes where p >= 13 and the band holds more than max(small_round_items, 512) planes: a second launch does not pay
+    // on a small band), 0 off, 1 | 2 forced (the cap still holds).  Triangle calls on a key-ordered layout only, whole-plane
+    // items only (lockstep, nsplit = 0), 9 <= p <= 16 (positions are 16-bit).
+    int sparse_planes = 0;
+    uint32_t sparse_cap = kSparseCapDefault;
+    uint32_t sparse_max_slabs = 1u << 16;  // (block, plane) tables the caller has room for
+    int p = 0;                              // precision (the automatic rule, and the 16-bit positions)
 };
 
 struct Seg {
@@ -245,7 +265,15 @@ struct PairPlan {
     std::vector<size_t> part_first;                      // first tile of every part in T (+ the end): the part of a tile
     std::vector<uint32_t> sort_first;                    // scratch of the item sort
     std::vector<U4> sort_tmp;
+    // sparse outer planes (Tuning): the tile's top sp[t] planes are not in its chunk range; each is one sparse item
+    std::vector<uint8_t> sp;                             // per tile: 0, 1 or 2
+    std::vector<U4> sp_items;                            // {tile index in band, plane, slab of the row block, slab of the column block}
+    std::vector<std::pair<size_t, size_t>> band_sp_items;  // sparse item ranges of the bands
+    std::vector<U2> slabs;                               // {block, plane}: the (table, row lists) the call's sparse items read
+    std::vector<int32_t> slab_of;                        // scratch: block * P + plane -> slab, or -1
 };
+// the bound on |{t : a_t >= v}| over the sketches of block b (v at most one below the block's T), else 65535
+uint32_t sparse_bound(const Layout &L, uint32_t b, int v);
 
 // returns false when there is nothing to compute
 bool build_pairs(const Layout &L, const PairQuery &q, const Tuning &t, PairPlan &pp);

@@ -1059,6 +1059,15 @@ int dsh_finalize_phase_cycles(dsh_ctx *ctx, uint64_t *out16);
  *                 "overflow_frag_permille"  0..1000 (default 500): a band whose one-plane work items number at most that
  *                                           share of a round above a multiple of a round has the items left over cut into
  *                                           fragments that ADD their counts; 0 = never
+ *                 "sparse_planes"           -1 auto | 0 off | 1 | 2: a tile's top one or two bit-planes are counted from
+ *                                           the positions of the few registers at or above the plane's threshold instead
+ *                                           of by the tile kernel (kernels_sparseplane.hip), wherever no sketch of the
+ *                                           tile's two blocks has more than "sparse_cap" of them; auto = at p >= 13 in
+ *                                           launches of more than 512 planes.  Triangle calls on key-ordered columns only.
+ *                                           Results do not depend on it.
+ *                 "sparse_cap"              0..2040 (default 1280): the longest such set a routed plane may have
+ *                 "sparse_lds"              1 (default) | 0: up to p = 15 the counting kernel stages a word of the block's
+ *                                           position table in LDS; 0 = it gathers from global memory, as at p = 16
  *   exchange      "part_band_tiles"         a part of at least this many tiles also ends a launch of the tile kernel (2048)
  *                 "xch_tail_bands"          0..8 (default 2): a job with parts of at most 64 rounds has its tile kernel cut
  *                                           at whole rounds into a head and this many tails, so that the head's parts
@@ -1076,7 +1085,7 @@ int dsh_finalize_phase_cycles(dsh_ctx *ctx, uint64_t *out16);
  * ("pair_mfma" exists only in a library built with `make WHATIF=1`: the matrix-core what-if the north star excludes.) */
 int dsh_set_option(dsh_ctx *ctx, const char *name, int64_t value);
 /* Derived state of the last prepared sketch matrix: "planes" (dense bit-planes used), "vlo",
- * "vhi", "pbase", "threshold", "emax", "elow", "kc", "pair_groups" (as the last prepare put them into effect), "pair_round" (work items per round of the last dist call's first launch of the tile kernel: 256 x the items per workgroup it ran with), "tile", "npad", "kpad", "cum_bytes", "sorted", "ncols", "lockstep", "tiles", "bands", "items" (work items of the tile kernel),
+ * "vhi", "pbase", "threshold", "emax", "elow", "kc", "pair_groups" (as the last prepare put them into effect), "pair_round" (work items per round of the last dist call's first launch of the tile kernel: 256 x the items per workgroup it ran with), "tile", "npad", "kpad", "cum_bytes", "sorted", "ncols", "lockstep", "tiles", "bands", "items" (work items of the tile kernel), "sparse_items" ((tile, plane) items counted from position lists instead: option "sparse_planes"), "sparse_plane_us" (with profiling on: the device time of their counting kernel in the last dist call; it is part of the pair phase of dsh_last_kernel_ms), "sparse_planes", "sparse_cap",
  * "words_per_plane", "avg_tile_planes_x100" (of the last dist call), "frag_items", "parts_done", "parts_signalled",
  * "place_kernel_us" (with profiling on: device time of the last dsh_exchange_place_device's placement kernel),
  * "sketch_kernel_us" / "fastx_decode_us" (with profiling on: k_sketch / the FASTA-FASTQ decode kernels of the last sketch call),

@@ -37,6 +37,11 @@ TILE = jm.TILE
 CV_BATCH = 16    # kCvBatch of kernels_compare.hip: planes whose C(v) travel with the first round trip
 TAIL_BINS = 48   # bins of a column's tail histogram that travel as three 16-byte words (tq[3])
 PAIR_KC = 16     # k-rows of an LDS stage of the tile kernel with three items per workgroup (the default; engine.hip)
+# sparse outer planes (plan.h, Tuning::sparse_planes): the defaults of the library
+SPARSE_CAP = 1280        # kSparseCapDefault
+SPARSE_CAP_MAX = 2040    # kSparseCapMax
+SPARSE_AUTO_PLANES = 2   # kSparseAutoPlanes
+SPARSE_MIN_BAND = 512    # the automatic rule: a band of more planes than this (Tuning::small_round_items under pair_groups = auto)
 
 # name -> what it stands for in the code.  The order is the order of the report.
 CONDITIONS = {
@@ -92,9 +97,36 @@ class Census:
         return self.counts[name] > 0
 
 
-def census(regs, p, emax=None, elow=None, sort=True, kc=PAIR_KC):
+def sparse_sets(regs, v):
+    """the complement sets of the plane (register < v): per sketch the positions whose register is >= v"""
+    return [np.flatnonzero(r >= v) for r in np.asarray(regs)]
+
+
+def sparse_plane_counts(rows, cols, v):
+    """C(v) = #{t : a_t < v and b_t < v} of every (row sketch, column sketch) as the sparse route counts it
+    (kernels_sparseplane.hip): the column block's table M[t] (bit j: column j has b_t >= v), every row's position list,
+    and m - |U_i| - |U_j| + |U_i & U_j|"""
+    rows, cols = np.asarray(rows), np.asarray(cols)
+    m = rows.shape[1]
+    table = cols.T >= v                      # [m positions][columns]
+    len_j = table.sum(axis=0).astype(np.int64)
+    out = np.empty((rows.shape[0], cols.shape[0]), np.int64)
+    for i, u in enumerate(sparse_sets(rows, v)):
+        out[i] = m - u.size - len_j + table[u].sum(axis=0)
+    return out
+
+
+def sparse_counts(regs, T):
+    """k_selfhist_card's g0, g1: registers >= T_i and >= T_i - 1 per sketch, saturating 16-bit"""
+    g0 = (regs >= T[:, None]).sum(axis=1)
+    g1 = (regs.astype(np.int64) >= (T.astype(np.int64) - 1)[:, None]).sum(axis=1)
+    return np.minimum(g0, 65535), np.minimum(g1, 65535)
+
+
+def census(regs, p, emax=None, elow=None, sort=True, kc=PAIR_KC, sparse_planes=-1, sparse_cap=SPARSE_CAP):
     """regs: [n, 2^p] uint8 (legal registers, <= 64 - p + 1); emax / elow: the list caps (None: plan::auto_list_cap);
-    sort: the key-ordered column layout (True) or the identity (False); the whole triangle"""
+    sort: the key-ordered column layout (True) or the identity (False); the whole triangle; sparse_planes / sparse_cap:
+    the two options of the sparse outer planes (-1: the automatic rule)"""
     regs = np.ascontiguousarray(regs, np.uint8)
     n = regs.shape[0]
     assert n >= 1 and regs.shape[1] == 1 << p and int(regs.max()) <= 64 - p + 1
@@ -116,6 +148,18 @@ def census(regs, p, emax=None, elow=None, sort=True, kc=PAIR_KC):
     for b in range(nblk):
         cols = order[b * TILE : (b + 1) * TILE]
         blk.append({"cols": cols, "T": int(T[cols].max()), "L": int(L[cols].min()), "lo": int(lo[cols].min()), "hi": int(hi[cols].max())})
+    # sparse outer planes: the blocks' bounds (plan::build_layout) and which calls route at all (plan::build_tiles)
+    g0, g1 = sparse_counts(regs, T)
+    for b in blk:
+        b["g0"] = int(g0[b["cols"]].max())
+        b["g1"] = int(np.where(T[b["cols"]] == b["T"], g1[b["cols"]], g0[b["cols"]]).max())
+
+    def sparse_bound(b, v):
+        return b["g0"] if v >= b["T"] else b["g1"] if v == b["T"] - 1 else 65535
+
+    sp_can = (sparse_planes != 0 and sort and inst["tile_kernel"] == "lockstep" and 9 <= p <= 16 and (sparse_planes > 0 or p >= 13))
+    sp_planes = 0 if not sp_can else SPARSE_AUTO_PLANES if sparse_planes < 0 else min(sparse_planes, 2)
+    sp_cap = min(sparse_cap, SPARSE_CAP_MAX)
     pbase = min(int(T.max()), min(b["L"] for b in blk))
     P = int(T.max()) - pbase
     index = [jm.ColumnBlock(regs, b["cols"], T, L, p) for b in blk]  # a block's listed registers: as columns and as rows
@@ -131,6 +175,9 @@ def census(regs, p, emax=None, elow=None, sort=True, kc=PAIR_KC):
             Lp, Tt = pbase + pb, pbase + pe
             vlo, vhi = min(blk[bi]["lo"], blk[bj]["lo"]), max(blk[bi]["hi"], blk[bj]["hi"])
             planes.append(pe - pb)
+            sp = 0  # planes routed sparse, from the top of the range (plan.cpp, sparse_route)
+            while sp < sp_planes and pe - sp > pb and max(sparse_bound(blk[bi], Tt - sp), sparse_bound(blk[bj], Tt - sp)) <= sp_cap:
+                sp += 1
             w0 = (Tt + 1) >> 4
             rows, cb = index[bi], index[bj]
             tile = {
@@ -160,7 +207,7 @@ def census(regs, p, emax=None, elow=None, sort=True, kc=PAIR_KC):
                 "join.bucket_beyond_wave_read": bool((c > 64 + RK).any()),
                 "join.queue_drained_early": bool((items > 2 * jm.QUEUE_ITEMS).any()),
             })
-            tiles.append({"bi": bi, "bj": bj, "Lp": Lp, "T": Tt, "vlo": vlo, "vhi": vhi, "planes": pe - pb, "items": int(same.sum()),
+            tiles.append({"bi": bi, "bj": bj, "Lp": Lp, "T": Tt, "vlo": vlo, "vhi": vhi, "planes": pe - pb, "sparse": sp, "items": int(same.sum()),
                           "live": int(live.sum()), "fullest": int(c.max()) if c.size else -1})
             joins["upper"] += int((applied & up[e]).sum())
             joins["lower"] += int((applied & ~up[e]).sum())
@@ -169,9 +216,14 @@ def census(regs, p, emax=None, elow=None, sort=True, kc=PAIR_KC):
     counts["collection.no_planes"] = int(P == 0)
     counts["collection.band_mixed_planes"] = int(min(planes) == 0 < max(planes))
     W = max(1, (1 << p) // 32)
+    if sparse_planes < 0 and sum(planes) <= SPARSE_MIN_BAND:  # (the automatic rule: one band here)
+        for t in tiles:
+            t["sparse"] = 0
+    sparse_items = sum(t["sparse"] for t in tiles)
     plan = {"planes": P, "pbase": pbase, "kpad": (P * W + kc - 1) // kc * kc, "tiles": len(planes), "sum_tile_planes": int(sum(planes)),
             "avg_tile_planes_x100": int(sum(planes)) * 100 // len(planes), "cum_bytes": inst["CT"],
-            "lockstep": int(inst["tile_kernel"] == "lockstep"), "sorted": int(bool(sort))}
+            "lockstep": int(inst["tile_kernel"] == "lockstep"), "sorted": int(bool(sort)),
+            "sparse_items": sparse_items, "dense_planes": int(sum(planes)) - sparse_items}
     return Census(inst, counts, plan, joins, tiles, blk)
 
 
