@@ -942,7 +942,12 @@ int dsh_get_info(dsh_ctx *c, const char *name, int64_t *out)
     }
     else if (!std::strcmp(name, "sparse_items")) *out = (int64_t)c->pp.sp_items.size();  // (tile, plane) items counted from position lists (plan.h)
     else if (!std::strcmp(name, "sparse_plane_us")) *out = (int64_t)(c->sparse_ms * 1000.0);  // (profiling) their counting kernel, of the last call
+    else if (!std::strcmp(name, "sparse_sided_items")) *out = (int64_t)c->pp.sided_items;  // those of them the sided route planned (plan.h, Tuning::sparse_sided) ...
+    else if (!std::strcmp(name, "sparse_transposed_items")) *out = (int64_t)c->pp.transposed_items;  // ... with the lists on the column block ...
+    else if (!std::strcmp(name, "sparse_slabs")) *out = (int64_t)c->pp.slabs.size();  // (block, plane) tables and lists the last dist call's items read
+    else if (!std::strcmp(name, "sparse_table_slabs")) *out = (int64_t)c->pp.table_slabs;  // ... and the slabs of the last call built without lists
     else if (!std::strcmp(name, "sparse_planes")) *out = c->sparse_planes;
+    else if (!std::strcmp(name, "sparse_sided")) *out = c->sparse_sided;
     else if (!std::strcmp(name, "sparse_cap")) *out = c->sparse_cap;
     else if (!std::strcmp(name, "words_per_plane")) *out = c->W;
     else if (!std::strcmp(name, "avg_tile_planes_x100")) {
@@ -1084,6 +1089,11 @@ int dsh_set_option(dsh_ctx *c, const char *name, int64_t v)
     if (!std::strcmp(name, "sparse_planes")) {  // sparse outer planes (plan.h, Tuning)
         if (v < -1 || v > 2) return fail(c, DSH_EINVAL, "sparse_planes is -1 (auto), 0 (off), 1 or 2");
         c->sparse_planes = (int)v;
+        return DSH_OK;
+    }
+    if (!std::strcmp(name, "sparse_sided")) {  // the sided route (plan.h, Tuning)
+        if (v < -1 || v > 1) return fail(c, DSH_EINVAL, "sparse_sided is -1 (auto), 0 (off) or 1 (forced)");
+        c->sparse_sided = (int)v;
         return DSH_OK;
     }
     if (!std::strcmp(name, "sparse_lds")) {

@@ -220,6 +220,8 @@ struct dsh_ctx {
     PinBuf pin_keys;                    // host copy of the per-sketch keys (valid while the per-sketch pass is), page-locked:
     const uint32_t *hk32 = nullptr;     // the copy is a direct DMA and the host only waits for ev_keys
     const uint32_t *hg32 = nullptr;     // the per-sketch counts g0 | g1 << 16 behind the keys, same transfer (plan.h, build_layout)
+    const uint32_t *hv32 = nullptr;     // and behind those the thresholds vU | vA << 8 of the sided route, computed at the cap ...
+    uint32_t pass_sparse_cap = 0;       // ... sparse_cap had when the per-sketch pass ran (plan.h, Layout::thr_cap)
     bool hk32_valid = false;
     double host_layout_us = 0, host_lists_us = 0, host_keys_wait_us = 0;  // host time of the last call (dsh_get_info)
     Staging st_perm;                    // lay.perm, then (row-sorted parts) lay.rowoff from the next 16-byte boundary on
@@ -239,6 +241,7 @@ struct dsh_ctx {
     int overflow_frag_permille = 500;  // overflow fragments of the tile kernel (plan.h, Tuning): 0 = never
     int sparse_planes = -1;  // sparse outer planes (plan.h, Tuning): -1 auto, 0 off, 1 | 2 forced
     int sparse_cap = (int)dsh::plan::kSparseCapDefault;  // the longest set a routed plane may have
+    int sparse_sided = -1;   // the sided route (plan.h, Tuning::sparse_sided): -1 auto, 0 off, 1 forced
     int sparse_lds = 1;      // the table of the counting kernel staged in LDS where a word of it fits (p <= 15); 0: gathered
     DevBuf sp_tab, sp_lists, sp_len, sp_slabs, sp_items;  // the slabs of the last call that routed planes (kernels_sparseplane.hip) and its items
     Staging st_sparse;               // slabs then sparse items on their way to the device

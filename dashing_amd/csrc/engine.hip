@@ -63,22 +63,25 @@ int prepare(dsh_ctx *c, int estim, int want_sorted, bool card_only, uint64_t wan
         HIPCHK(c, c->exc.ensure(std::max<uint64_t>(n, 1) * kListCap * (c->p <= 15 ? 2 : 4)));
         HIPCHK(c, c->excv.ensure(std::max<uint64_t>(n, 1) * kListCap));
         HIPCHK(c, c->exc_n.ensure(std::max<uint64_t>(n, 1) * sizeof(uint32_t)));
-        // (keys [n], then the counts of the sparse-plane planner [n]: one buffer, one transfer)
-        HIPCHK(c, c->keys.ensure(std::max<uint64_t>(n, 1) * 2 * sizeof(uint32_t)));
+        // (keys [n], then the counts [n] and the thresholds [n] of the sparse-plane planner: one buffer, one transfer)
+        HIPCHK(c, c->keys.ensure(std::max<uint64_t>(n, 1) * 3 * sizeof(uint32_t)));
         HIPCHK(c, c->tailhist.ensure(std::max<uint64_t>(n, 1) * 64));
         HIPCHK(c, c->hist.ensure(std::max<uint64_t>(n, 1) * 64 * sizeof(uint32_t)));
         HIPCHK(c, launch_selfhist_card(c->stream, c->regs, need_from, n, c->p, estim, c->emax, c->elow,
                                        (uint32_t *)c->hist.ptr, c->exc.ptr, (uint8_t *)c->excv.ptr,
                                        (uint32_t *)c->exc_n.ptr, (uint32_t *)c->keys.ptr,
-                                       (uint8_t *)c->tailhist.ptr, (uint32_t *)c->keys.ptr + n));
+                                       (uint8_t *)c->tailhist.ptr, (uint32_t *)c->keys.ptr + n, (uint32_t *)c->keys.ptr + 2 * n,
+                                       std::min<uint32_t>((uint32_t)c->sparse_cap, plan::kSparseCapMax)));
+        c->pass_sparse_cap = std::min<uint32_t>((uint32_t)c->sparse_cap, plan::kSparseCapMax);
         // the keys travel to the host right behind the per-sketch pass (the column order is made there); the
         // cardinalities follow on the stream while the host sorts
-        HIPCHK(c, c->pin_keys.ensure(std::max<uint64_t>(n, 1) * 2 * sizeof(uint32_t)));
+        HIPCHK(c, c->pin_keys.ensure(std::max<uint64_t>(n, 1) * 3 * sizeof(uint32_t)));
         c->hk32 = (const uint32_t *)c->pin_keys.ptr;
         c->hg32 = c->hk32 + n;
+        c->hv32 = c->hk32 + 2 * n;
         if (n > need_from)  // (the keys from need_from on and every count: the counts in front of need_from are never read)
             HIPCHK(c, hipMemcpyAsync((uint32_t *)c->pin_keys.ptr + need_from, (const uint32_t *)c->keys.ptr + need_from,
-                                     (2 * n - need_from) * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+                                     (3 * n - need_from) * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, c->ev_keys.ensure());
         HIPCHK(c, hipEventRecord(c->ev_keys, c->stream));
         HIPCHK(c, launch_card_from_hist(c->stream, (const uint32_t *)c->hist.ptr, (const uint32_t *)c->keys.ptr, need_from, n,
@@ -128,7 +131,7 @@ int prepare(dsh_ctx *c, int estim, int want_sorted, bool card_only, uint64_t wan
         plan::Layout &L = c->lay;
         if (!reuse_host_layout)
             plan::build_layout(k32, n, want_sorted, want_rb, want_re, parts, L, rowsorted ? std::max<uint32_t>(nparts, 1) : 0,
-                               extra->empty() ? nullptr : extra, c->hg32);
+                               extra->empty() ? nullptr : extra, c->hg32, c->hv32, c->pass_sparse_cap);
         ++c->lay_serial;
         c->lay_built = true;
         c->cum_bytes = c->p <= 15 ? 2 : 4;
@@ -304,6 +307,7 @@ plan::Tuning tuning_of(const dsh_ctx *c)
     tu.p = c->p;
     tu.sparse_planes = c->sparse_planes;
     tu.sparse_cap = (uint32_t)c->sparse_cap;
+    tu.sparse_sided = c->sparse_sided;
     tu.sparse_max_slabs = (uint32_t)std::min<uint64_t>(1u << 16, kSparseSlabBudget / sparse_slab_bytes(c));
     return tu;
 }

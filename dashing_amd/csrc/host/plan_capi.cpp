@@ -29,6 +29,15 @@ struct SparseCheck {
     uint32_t cap = 0;
     uint32_t *routes = nullptr;
     uint64_t routes_cap = 0;  // tiles `routes` has room for
+    // the sided route (dshh_plan_check_sparse_sided): the per-sketch thresholds vU | vA << 8 and their cap, the option, and
+    // where the routes, items and slabs go -- 6 words per tile (row block, column block, plane begin, plane end, planes
+    // routed below, planes routed above), 5 per item (tile, plane, list A | table A << 1 | transposed << 2, slab of the row
+    // block, slab of the column block), 3 per slab (block, plane, A | table-only << 1)
+    const uint32_t *thr = nullptr;
+    uint32_t thr_cap = 0;
+    int sided = 0;
+    uint32_t *routes6 = nullptr, *items5 = nullptr, *slabs3 = nullptr;
+    uint64_t items_cap = 0, slabs_cap = 0;
 };
 
 struct Err {
@@ -74,7 +83,7 @@ static int plan_check(uint64_t n, const uint32_t *keys, int mode, int want_sorte
     if (!extra.empty() && !(want_sorted && mode == 0)) return E.fail("extra segments need a sorted triangle layout");
     Layout L;
     build_layout(keys, n, want_sorted, lrb, lre, parts, L, rowsorted ? std::max<uint32_t>(nparts, 1) : 0, extra.empty() ? nullptr : &extra,
-                 sc ? sc->gcnt : nullptr);
+                 sc ? sc->gcnt : nullptr, sc ? sc->thr : nullptr, sc ? sc->thr_cap : 0);
     // the wanted segments, main range first
     std::vector<std::pair<uint64_t, uint64_t>> wsegs;  // (the wanted order: extra segments first, then the main range)
     wanted_order(n, lrb, lre, &extra, wsegs, rowsorted);
@@ -161,7 +170,7 @@ static int plan_check(uint64_t n, const uint32_t *keys, int mode, int want_sorte
     if (round_items) tu.round_items = round_items;
     if (round_items > 512) tu.small_round_items = 512;  // (as engine.hip under pair_groups = auto)
     tu.p = p;
-    if (sc) tu.sparse_planes = sc->planes, tu.sparse_cap = sc->cap;
+    if (sc) tu.sparse_planes = sc->planes, tu.sparse_cap = sc->cap, tu.sparse_sided = sc->sided;
     PairQuery q;
     q.rect = mode == 1;
     q.sorted_rows = mode == 2;
@@ -313,7 +322,10 @@ static int plan_check(uint64_t n, const uint32_t *keys, int mode, int want_sorte
     if (at != T.size()) return E.fail("bands end at %zu of %zu tiles", at, T.size());
     // ---- sparse outer planes: every plane of a tile's range is in the tile's chunk range (checked above against
     // pp.chunks) or has exactly one sparse item, never both; a routed plane's sets are inside the cap
-    if (pp.sp.size() != T.size() || pp.band_sp_items.size() != pp.bands.size()) return E.fail("sparse bookkeeping sizes differ");
+    // With the sided route every plane of a tile's range is in exactly one route: the dense remainder [pb + below, pe - above)
+    // -- one range -- or one sparse item; an item's list block is within its bound, in the item's polarity, for every sketch.
+    if (pp.sp.size() != T.size() || pp.spb.size() != T.size() || pp.band_sp_items.size() != pp.bands.size()) return E.fail("sparse bookkeeping sizes differ");
+    const bool sided_chk = sc && sc->thr && sc->sided != 0 && pp.sided_items > 0;
     {
         const uint32_t cpp_ = tu.W >= (uint32_t)tu.kc ? tu.W / tu.kc : 1;
         std::vector<uint8_t> seen_pl;
@@ -323,18 +335,37 @@ static int plan_check(uint64_t n, const uint32_t *keys, int mode, int want_sorte
             const auto &rg = pp.band_sp_items[bi];
             if (rg.first != sat || rg.second < rg.first || rg.second > pp.sp_items.size()) return E.fail("sparse items of band %zu do not follow %zu", bi, sat);
             sat = rg.second;
-            seen_pl.assign((bd.second - bd.first) * 2, 0);
+            seen_pl.assign((bd.second - bd.first) * 64, 0);
             for (size_t k = rg.first; k < rg.second; ++k) {
                 const U4 &I = pp.sp_items[k];
                 if (I.x >= bd.second - bd.first) return E.fail("sparse item %zu names tile %u of band %zu", k, I.x, bi);
                 const size_t t = bd.first + I.x;
-                const uint32_t sp = pp.sp[t];
-                if (I.y >= T[t].w || I.y + sp < T[t].w) return E.fail("sparse item %zu: plane %u is not one of the top %u of tile %zu", k, I.y, sp, t);
-                if (seen_pl[I.x * 2 + (T[t].w - 1 - I.y)]++) return E.fail("plane %u of tile %zu has two sparse items", I.y, t);
-                if (I.z >= pp.slabs.size() || I.w >= pp.slabs.size() || pp.slabs[I.z].x != T[t].x || pp.slabs[I.z].y != I.y ||
-                    pp.slabs[I.w].x != T[t].y || pp.slabs[I.w].y != I.y)
+                const uint32_t sp = pp.sp[t], spb = pp.spb[t], Ipl = I.y & kSpPlaneMask;
+                if (Ipl >= T[t].w || Ipl < T[t].z || (Ipl + sp < T[t].w && Ipl >= T[t].z + spb))
+                    return E.fail("sparse item %zu: plane %u is not one of the top %u or bottom %u of tile %zu", k, Ipl, sp, spb, t);
+                if (T[t].w - T[t].z > 64) return E.fail("tile %zu has %u planes: register values are below 64", t, T[t].w - T[t].z);
+                if (seen_pl[I.x * 64 + (Ipl - T[t].z)]++) return E.fail("plane %u of tile %zu has two sparse items", Ipl, t);
+                if (I.z >= pp.slabs.size() || I.w >= pp.slabs.size() || pp.slabs[I.z].x != T[t].x || (pp.slabs[I.z].y & kSpPlaneMask) != Ipl ||
+                    pp.slabs[I.w].x != T[t].y || (pp.slabs[I.w].y & kSpPlaneMask) != Ipl)
                     return E.fail("sparse item %zu names the wrong slabs", k);
-                const int v = L.pbase + 1 + (int)I.y;
+                const int v = L.pbase + 1 + (int)Ipl;
+                if (sided_chk) {
+                    const bool tr = (I.y & kSpItemTransposed) != 0, la = (I.y & kSpItemListA) != 0, ta = (I.y & kSpItemTabA) != 0;
+                    if (tr && T[t].x == T[t].y) return E.fail("sparse item %zu: a diagonal tile is transposed", k);
+                    const U2 &lsl = pp.slabs[tr ? I.w : I.z], &tsl = pp.slabs[tr ? I.z : I.w];
+                    if (((lsl.y & kSpSlabA) != 0) != la || ((tsl.y & kSpSlabA) != 0) != ta) return E.fail("sparse item %zu: polarities differ from its slabs'", k);
+                    if (lsl.y & kSpSlabTableOnly) return E.fail("sparse item %zu reads lists from a table-only slab", k);
+                    if (L.thr_cap != tu.sparse_cap) return E.fail("sparse item %zu planned on thresholds of cap %u at cap %u", k, L.thr_cap, tu.sparse_cap);
+                    for (uint32_t a = 0; a < kTile; ++a) {
+                        const uint64_t sx = (uint64_t)lsl.x * kTile + a;
+                        if (sx >= L.ncols) continue;
+                        const uint32_t th = sc->thr[orig(sx)];
+                        if (la ? v > (int)((th >> 8) & 0xFFu) : v < (int)(th & 0xFFu))
+                            return E.fail("sparse item %zu: sketch %llu of the list block is outside its bound at v = %d", k, (unsigned long long)orig(sx), v);
+                    }
+                    continue;
+                }
+                if (I.y != Ipl || pp.slabs[I.z].y != Ipl || pp.slabs[I.w].y != Ipl) return E.fail("sparse item %zu carries flags without the sided route", k);
                 if (sparse_bound(L, T[t].x, v) > tu.sparse_cap || sparse_bound(L, T[t].y, v) > tu.sparse_cap) return E.fail("sparse item %zu: a set may exceed the cap", k);
                 // the bound holds for every sketch of the two blocks (what the lists and counters are sized by)
                 if (sc && sc->gcnt)
@@ -348,11 +379,13 @@ static int plan_check(uint64_t n, const uint32_t *keys, int mode, int want_sorte
                         }
             }
             for (size_t t = bd.first; t < bd.second; ++t) {
-                const uint32_t sp = pp.sp[t];
-                if (sp > 2 || sp > T[t].w - T[t].z) return E.fail("tile %zu routes %u planes of %u", t, sp, T[t].w - T[t].z);
-                for (uint32_t x = 0; x < sp; ++x)
-                    if (!seen_pl[(t - bd.first) * 2 + x]) return E.fail("routed plane %u of tile %zu has no sparse item", T[t].w - 1 - x, t);
-                if (tu.W >= (uint32_t)tu.kc && (pp.chunks[t].x != T[t].z * cpp_ || pp.chunks[t].y != (T[t].w - sp) * cpp_))
+                const uint32_t sp = pp.sp[t], spb = pp.spb[t], np = T[t].w - T[t].z;
+                if ((!sided_chk && (sp > 2 || spb)) || sp + spb > np) return E.fail("tile %zu routes %u + %u planes of %u", t, spb, sp, np);
+                if (np > 64) return E.fail("tile %zu has %u planes: register values are below 64", t, np);
+                for (uint32_t x = 0; x < np; ++x)
+                    if ((seen_pl[(t - bd.first) * 64 + x] != 0) != (x < spb || x + sp >= np))
+                        return E.fail("plane %u of tile %zu: routed and sparse item disagree", T[t].z + x, t);
+                if (tu.W >= (uint32_t)tu.kc && (pp.chunks[t].x != (T[t].z + spb) * cpp_ || pp.chunks[t].y != (T[t].w - sp) * cpp_))
                     return E.fail("tile %zu: the dense chunk range is not the planes left over", t);
             }
         }
@@ -362,6 +395,24 @@ static int plan_check(uint64_t n, const uint32_t *keys, int mode, int want_sorte
             for (size_t t = 0; t < T.size(); ++t) {
                 uint32_t *o = sc->routes + 5 * t;
                 o[0] = T[t].x, o[1] = T[t].y, o[2] = T[t].z, o[3] = T[t].w, o[4] = pp.sp[t];
+            }
+        }
+        if (sc && sc->routes6) {
+            if (T.size() > sc->routes_cap || pp.sp_items.size() > sc->items_cap || pp.slabs.size() > sc->slabs_cap)
+                return E.fail("%zu tiles, %zu items, %zu slabs: no room", T.size(), pp.sp_items.size(), pp.slabs.size());
+            for (size_t t = 0; t < T.size(); ++t) {
+                uint32_t *o = sc->routes6 + 6 * t;
+                o[0] = T[t].x, o[1] = T[t].y, o[2] = T[t].z, o[3] = T[t].w, o[4] = pp.spb[t], o[5] = pp.sp[t];
+            }
+            for (size_t bi = 0; bi < pp.bands.size(); ++bi)
+                for (size_t k = pp.band_sp_items[bi].first; k < pp.band_sp_items[bi].second; ++k) {
+                    const U4 &I = pp.sp_items[k];
+                    uint32_t *o = sc->items5 + 5 * k;
+                    o[0] = (uint32_t)(pp.bands[bi].first + I.x), o[1] = I.y & kSpPlaneMask, o[2] = I.y >> 8, o[3] = I.z, o[4] = I.w;
+                }
+            for (size_t k = 0; k < pp.slabs.size(); ++k) {
+                uint32_t *o = sc->slabs3 + 3 * k;
+                o[0] = pp.slabs[k].x, o[1] = pp.slabs[k].y & kSpPlaneMask, o[2] = pp.slabs[k].y >> 8;
             }
         }
     }
@@ -419,6 +470,7 @@ static int plan_check(uint64_t n, const uint32_t *keys, int mode, int want_sorte
     stats[4] = T.empty() ? 0 : planes_sum * 100 / T.size();
     // rounds of the lockstep tile kernel over all bands (a band of k items takes ceil(k / round_items) rounds)
     if (sc) stats[10] = pp.sp_items.size(), stats[11] = pp.slabs.size();
+    if (sc && sc->routes6) stats[12] = pp.sided_items, stats[13] = pp.transposed_items, stats[14] = pp.table_slabs;
     stats[7] = 0;
     for (size_t b = 0; b < pp.band_items.size(); ++b) {
         const uint32_t nfr = b < pp.band_frags.size() ? pp.band_frags[b] : 0u;
@@ -465,6 +517,34 @@ int dshh_plan_check_sparse(uint64_t n, const uint32_t *keys, const uint32_t *gcn
     sc.routes = routes;
     sc.routes_cap = routes_cap;
     stats[10] = stats[11] = 0;
+    return plan_check(n, keys, mode, want_sorted, rb, re, 0, 0, nparts, want_parts, p, cum_budget, 1, 0, 64, std::vector<uint64_t>(), stats, err,
+                      cap, round_items, &sc);
+}
+
+// the same with the sided route planned (plan.h, Tuning::sparse_sided): thr = the per-sketch thresholds vU | vA << 8 at the cap
+// thr_cap, sparse_sided the option.  Checks the contract -- every (tile, plane) in exactly one route, the dense remainder one
+// range, every item's list block within its bound in the item's polarity -- and returns the plan: stats gets fifteen slots
+// ([12] items of the sided route, [13] transposed items, [14] table-only slabs); routes 6 words per tile, items 5 per item
+// (tile index, plane, flags, slab of the row block, slab of the column block), slabs 3 per slab (SparseCheck above).
+int dshh_plan_check_sparse_sided(uint64_t n, const uint32_t *keys, const uint32_t *gcnt, const uint32_t *thr, uint32_t thr_cap, int mode,
+                                 int want_sorted, uint64_t rb, uint64_t re, uint32_t nparts, int want_parts, int p, uint64_t cum_budget,
+                                 uint32_t round_items, int sparse_planes, int sparse_sided, uint32_t sparse_cap, uint64_t *stats, uint32_t *routes,
+                                 uint64_t routes_cap, uint32_t *items, uint64_t items_cap, uint32_t *slabs, uint64_t slabs_cap, char *err, size_t cap)
+{
+    Err E{err, cap};
+    if (round_items == 0 || round_items % 256) return E.fail("round_items %u is not a positive multiple of 256", round_items);
+    if (!routes || !items || !slabs) return E.fail("routes, items and slabs are wanted");
+    SparseCheck sc;
+    sc.gcnt = gcnt;
+    sc.planes = sparse_planes;
+    sc.cap = sparse_cap;
+    sc.thr = thr;
+    sc.thr_cap = thr_cap;
+    sc.sided = sparse_sided;
+    sc.routes6 = routes, sc.routes_cap = routes_cap;
+    sc.items5 = items, sc.items_cap = items_cap;
+    sc.slabs3 = slabs, sc.slabs_cap = slabs_cap;
+    for (int i = 10; i < 15; ++i) stats[i] = 0;
     return plan_check(n, keys, mode, want_sorted, rb, re, 0, 0, nparts, want_parts, p, cum_budget, 1, 0, 64, std::vector<uint64_t>(), stats, err,
                       cap, round_items, &sc);
 }

@@ -9,7 +9,7 @@ namespace dsh {
 
 hipError_t launch_selfhist_card(hipStream_t st, const uint8_t *regs, uint64_t first, uint64_t n, int p, int estim,
                                 int emax, int elow, uint32_t *hist, void *exc, uint8_t *excv, uint32_t *exc_n,
-                                uint32_t *keys, uint8_t *tailhist, uint32_t *gcnt);
+                                uint32_t *keys, uint8_t *tailhist, uint32_t *gcnt, uint32_t *sthr, uint32_t scap);
 hipError_t launch_card_from_hist(hipStream_t st, const uint32_t *hist, const uint32_t *keys, uint64_t first, uint64_t n, int p,
                                  int estim, double *card);
 // position index of every 128-column block of the plane layout (perm == nullptr: identity) and the per-column side
@@ -42,16 +42,18 @@ hipError_t launch_pair_counts(hipStream_t st, int kc, int cum_bytes, const uint3
                               const uint4 *tiles, const uint4 *items, uint32_t nitems, void *cum,
                               uint64_t nslots);
 
-// sparse outer planes (kernels_sparseplane.hip; plan.h, Tuning::sparse_planes).  launch_sparse_build: for each of the nslabs
-// {block, plane} of `slabs`, from that plane's words of the bit-plane matrix, tab[slab][2^p][4] (bit j of a position's 128:
-// column j of the block has a register >= the plane's threshold there), lists[slab][128][cap] (every column's such
-// positions, 16-bit) and len[slab][128] (their number; cleared here first).  cap: a multiple of 8.  wordmajor: the table as
+// sparse outer planes (kernels_sparseplane.hip; plan.h, Tuning::sparse_planes, sparse_sided).  launch_sparse_build: for each
+// of the nslabs {block, plane | plan::kSpSlab* flags} of `slabs`, from that plane's words of the bit-plane matrix,
+// tab[slab][2^p][4] (bit j of a position's 128: column j of the block is in the slab's set there -- its register >= the
+// plane's threshold, or with kSpSlabA < it), lists[slab][128][cap] (every column's such positions, 16-bit; none for a
+// kSpSlabTableOnly slab) and len[slab][128] (the size of every set; cleared here first).  cap: a multiple of 8.  wordmajor: the table as
 // tab[slab][4][2^p], which the LDS placement of the counting kernel stages a word of (2^p <= 2^15); the two launchers of
 // a call take the same value.
 hipError_t launch_sparse_build(hipStream_t st, const uint32_t *planes, uint32_t Npad, uint32_t W, uint64_t ncols, const uint2 *slabs,
                                uint32_t nslabs, uint32_t cap, int wordmajor, uint32_t *tab, uint16_t *lists, uint32_t *len);
-// one workgroup per item {tile index in band, plane, slab of the row block, slab of the column block}: the plane's C(v) of
-// the tile's 128 x 128 pairs, stored where the tile kernel stores it; m = 2^p
+// one workgroup per item {tile index in band, plane | plan::kSpItem* flags, slab of the row block, slab of the column block}:
+// the plane's C(v) of the tile's 128 x 128 pairs, stored where the tile kernel stores it; m = 2^p.  The flags name the
+// polarities of the list side and the table side, and whether the list side is the column block (a transposed item)
 hipError_t launch_sparse_count(hipStream_t st, int cum_bytes, const uint4 *items, uint32_t nitems, int wordmajor, const uint32_t *tab,
                                const uint16_t *lists, const uint32_t *len, uint32_t cap, uint32_t m, void *cum, uint64_t nslots);
 

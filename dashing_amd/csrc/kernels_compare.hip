@@ -62,7 +62,8 @@ __global__ __launch_bounds__(256, 4) void k_selfhist_card(const uint8_t *__restr
                                                         uint32_t *__restrict__ exc_n,
                                                         uint32_t *__restrict__ keys,
                                                         uint8_t *__restrict__ tailhist,
-                                                        uint32_t *__restrict__ gcnt)
+                                                        uint32_t *__restrict__ gcnt,
+                                                        uint32_t *__restrict__ sthr, uint32_t scap)
 {
     __shared__ uint32_t hist[4][64];
     __shared__ uint32_t sub[4][8][72];  // 8 privatised copies per wave: the register values pile up in ~8 bins, so
@@ -154,6 +155,16 @@ __global__ __launch_bounds__(256, 4) void k_selfhist_card(const uint8_t *__restr
         // >= T - 1, the sizes of the sets the two top planes' complements are, saturating 16-bit each
         const uint32_t g0 = cnt + h[T], g1 = g0 + (T > 0 ? h[T - 1] : 0u);
         gcnt[s] = (g0 < 65535u ? g0 : 65535u) | ((g1 < 65535u ? g1 : 65535u) << 16);
+        // and the two thresholds of the sided route at the cap scap (plan.h, Layout::blk_vU / blk_vA): vU = the smallest v
+        // with #{a >= v} <= scap, vA = the largest v with #{a < v} <= scap (v in 0 .. 64); vU | vA << 8.  The route exists from
+        // p = 13 (below it a set and its complement can both fit a cap): below that no walk, and thresholds that admit nothing
+        int vU = 64, vA = 0;
+        if (p >= 13) {
+            uint32_t up = 0, dn = 0;
+            while (vU > 0 && up + h[vU - 1] <= scap) up += h[--vU];
+            while (vA < 64 && dn + h[vA] <= scap) dn += h[vA++];
+        }
+        sthr[s] = (uint32_t)vU | ((uint32_t)vA << 8);
     }
     if (s < n && __any(bad != 0) && lane == 0) atomicOr(&keys[s], 0x80000000u);  // (after lane 0's plain store above)
     __syncthreads();
@@ -1643,16 +1654,16 @@ hipError_t launch_upload(hipStream_t st, void *dst, const void *src_pinned, size
 // launch wrappers (host)
 hipError_t launch_selfhist_card(hipStream_t st, const uint8_t *regs, uint64_t first, uint64_t n, int p, int estim,
                                 int emax, int elow, uint32_t *hist, void *exc, uint8_t *excv, uint32_t *exc_n,
-                                uint32_t *keys, uint8_t *tailhist, uint32_t *gcnt)
+                                uint32_t *keys, uint8_t *tailhist, uint32_t *gcnt, uint32_t *sthr, uint32_t scap)
 {
     if (n <= first) return hipSuccess;
     const uint32_t blocks = (uint32_t)((n - first + 3) / 4);
     if (p <= 15)
         hipLaunchKernelGGL(k_selfhist_card<uint16_t>, dim3(blocks), dim3(256), 0, st, regs, first, n, p, estim, emax, elow,
-                           hist, (uint16_t *)exc, excv, exc_n, keys, tailhist, gcnt);
+                           hist, (uint16_t *)exc, excv, exc_n, keys, tailhist, gcnt, sthr, scap);
     else
         hipLaunchKernelGGL(k_selfhist_card<uint32_t>, dim3(blocks), dim3(256), 0, st, regs, first, n, p, estim, emax, elow,
-                           hist, (uint32_t *)exc, excv, exc_n, keys, tailhist, gcnt);
+                           hist, (uint32_t *)exc, excv, exc_n, keys, tailhist, gcnt, sthr, scap);
     return hipGetLastError();
 }
 

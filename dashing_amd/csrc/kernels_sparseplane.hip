@@ -22,14 +22,29 @@
 // columns, 2^p x 4 bytes: 64 KiB at p = 14 -- is staged in LDS by each of FOUR workgroups per item (k_sparse_count_lds),
 // the four lanes of a row take a quarter of its list each and add their counters at the end.  At p = 16 a word is
 // 256 KiB, more than a CU holds: the global placement stays, and there the sets are sparse enough for it to pay well.
+// The sided route (plan.h, Tuning::sparse_sided).  Only the LIST side has to be sparse -- the table costs the same at any
+// density -- and a set may be U(v) or A(v) = {t : a_t < v}, the plane's words as they are: a slab carries its polarity, an
+// item the polarities of its two sides, and C(v) comes from cnt = |R_list & S_table| by one of four formulas (sp_values).
+// An item whose sparse side is the COLUMN block is transposed: the lanes walk the column block's lists against the row
+// block's table, a lane then owns one column and 32 rows, and the values are turned through LDS before they are stored.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <algorithm>
+
 #include "kernels.h"
+#include "plan.h"
 
 namespace dsh {
 
 namespace {
+
+using plan::kSpItemListA;
+using plan::kSpItemTabA;
+using plan::kSpItemTransposed;
+using plan::kSpPlaneMask;
+using plan::kSpSlabA;
+using plan::kSpSlabTableOnly;
 
 constexpr int kSpChunk = 16;     // plane words a wave of k_sparse_build takes
 constexpr int kSpCounters = 11;  // counter words of k_sparse_count: sets up to 2047 (plan.h, kSparseCapMax)
@@ -44,45 +59,43 @@ __global__ __launch_bounds__(256) void k_sparse_build(const uint32_t *__restrict
     const uint64_t unit = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (unit >= (uint64_t)nslabs * 2 * nch) return;  // (wave-uniform)
     const uint32_t ch = (uint32_t)(unit % nch), h = (uint32_t)(unit / nch) & 1u, s = (uint32_t)(unit / (2 * (uint64_t)nch));
-    const uint2 sl = slabs[s];  // {block, plane}
+    const uint2 sl = slabs[s];  // {block, plane | kSpSlab* flags}
+    const uint32_t plane = sl.y & kSpPlaneMask;
+    const uint32_t flip = sl.y & kSpSlabA ? 0u : 0xFFFFFFFFu;  // (the words are A(v); their complement is U(v))
     const uint32_t row = h * 64 + lane;
     const uint64_t col = (uint64_t)sl.x * kTile + row;
     const uint32_t w0 = ch * kSpChunk;
-    const uint32_t *src = planes + ((uint64_t)sl.y * W + w0) * Npad + col;
-    // (a padding column's plane words are zero: it is in no set)
+    const uint32_t *src = planes + ((uint64_t)plane * W + w0) * Npad + col;
+    // (a padding column's plane words are zero: it is in no set of either polarity)
     const uint32_t real = col < ncols ? 0xFFFFFFFFu : 0u;
     uint32_t x[kSpChunk];
 #pragma unroll
-    for (int k = 0; k < kSpChunk; ++k) x[k] = ~src[(uint64_t)k * Npad] & real;
-    // the table: the 32 x 64 bit transpose of every word, a ballot per bit; lane b keeps bit b's and stores it
+    for (int k = 0; k < kSpChunk; ++k) x[k] = (src[(uint64_t)k * Npad] ^ flip) & real;
+    // The table: every word's bits turned, 32 lanes x 32 bits at a time in either half of the wave, by five rounds of lane
+    // exchanges (blocks of j x j bits swap across lanes j apart, j = 16 .. 1): lane b of a half then holds bit b of its 32
+    // columns -- a word of position w0 * 32 + k * 32 + b -- and stores it.  (A ballot per bit took five times the instructions.)
     const uint64_t m = (uint64_t)W * 32;
-    uint32_t *trow = tab + ((uint64_t)s * m + (uint64_t)w0 * 32 + lane) * 4 + 2 * h;       // position-major: [position][word]
-    uint32_t *tcol = tab + ((uint64_t)s * 4 + 2 * h) * m + (uint64_t)w0 * 32 + (lane & 31u);  // word-major: [word][position]
+    const uint32_t q = 2 * h + (lane >> 5), b5 = lane & 31u;  // the table word this lane's half fills; the position in the plane word
+    uint32_t *tpos = tab + ((uint64_t)s * m + (uint64_t)w0 * 32 + b5) * 4 + q;  // position-major: [position][word]
+    uint32_t *tcol = tab + ((uint64_t)s * 4 + q) * m + (uint64_t)w0 * 32 + b5;  // word-major: [word][position]
 #pragma unroll
     for (int k = 0; k < kSpChunk; ++k) {
-        const uint32_t xx = x[k];
-        uint32_t lo = 0, hi = 0;
+        uint32_t t = x[k];
 #pragma unroll
-        for (uint32_t b = 0; b < 32; ++b) {
-            const unsigned long long bal = __ballot((xx >> b) & 1u);
-            if (lane == b) {
-                lo = (uint32_t)bal;
-                hi = (uint32_t)(bal >> 32);
-            }
+        for (uint32_t j = 16, mk = 0x0000FFFFu; j; j >>= 1, mk ^= mk << j) {  // mk: the bits whose index has bit j clear
+            const uint32_t o = __shfl_xor(t, (int)j, 64);
+            t = lane & j ? (t & ~mk) | ((o >> j) & mk) : (t & mk) | ((o & mk) << j);
         }
-        if (wordmajor) {  // (lanes 32 .. 63 hold zeros: they get their copy of lane - 32's pair and write the second word)
-            const uint32_t hi2 = __shfl(hi, (int)(lane & 31u), 64);
-            tcol[(lane >> 5) * m + (uint64_t)k * 32] = lane < 32 ? lo : hi2;
-        } else if (lane < 32) {
-            *reinterpret_cast<uint2 *>(trow + (uint64_t)k * 32 * 4) = make_uint2(lo, hi);
-        }
+        if (wordmajor) tcol[(uint64_t)k * 32] = t;
+        else tpos[(uint64_t)k * 32 * 4] = t;
     }
     // the column's list: its slots from one atomic per chunk
     uint32_t mine = 0;
 #pragma unroll
     for (int k = 0; k < kSpChunk; ++k) mine += (uint32_t)__popc(x[k]);
     if (!mine) return;
-    uint32_t slot = atomicAdd(&len[(uint64_t)s * kTile + row], mine);
+    uint32_t slot = atomicAdd(&len[(uint64_t)s * kTile + row], mine);  // (the true size of the set: the formulas read it)
+    if (sl.y & kSpSlabTableOnly) return;                               // (wave-uniform: no item walks this slab's lists)
     uint16_t *dst = lists + ((uint64_t)s * kTile + row) * cap;
 #pragma unroll
     for (int k = 0; k < kSpChunk; ++k) {
@@ -116,22 +129,64 @@ __device__ __forceinline__ void put32(uint32_t *dst, const uint32_t (&v)[32])
     for (int q = 0; q < 8; ++q) reinterpret_cast<uint4 *>(dst)[q] = make_uint4(v[4 * q], v[4 * q + 1], v[4 * q + 2], v[4 * q + 3]);
 }
 
-// One workgroup per item {tile index in band, plane, slab of the row block, slab of the column block}; 512 lanes as
-// (row, column word).  cap is a multiple of 8: a lane reads its list eight 16-bit positions at a time.
+// The 32 values of a lane from its counter words: bit cc of every word is cnt = |R & S| of the lane's list row against table
+// column cc.  With the list set's size ll and the table set's size lt[cc], by the polarities of the item's flags fl:
+//     list U, table U: m - ll - lt + cnt     list A, table A: cnt     list U, table A: lt - cnt     list A, table U: ll - cnt
+template <typename CT>
+__device__ __forceinline__ void sp_values(uint32_t (&out)[32], const uint32_t (&c)[kSpCounters], uint32_t fl, uint32_t m, uint32_t ll,
+                                          const uint32_t *lt)
+{
+    const bool la = (fl & kSpItemListA) != 0, ta = (fl & kSpItemTabA) != 0;  // (wave-uniform: per item)
+    const uint32_t kl = !la && !ta ? m - ll : la && !ta ? ll : 0u;
+    const uint32_t tsub = !la && !ta ? 0xFFFFFFFFu : 0u, tadd = !la && ta ? 0xFFFFFFFFu : 0u;  // the table set's size: minus | plus | not at all
+    const uint32_t cneg = la != ta ? 0xFFFFFFFFu : 0u;                                           // cnt: minus | plus
+#pragma unroll
+    for (int cc = 0; cc < 32; ++cc) {
+        uint32_t cnt = 0;
+#pragma unroll
+        for (int b = 0; b < kSpCounters; ++b) cnt |= ((c[b] >> cc) & 1u) << b;
+        const uint32_t t = lt[cc];
+        out[cc] = (kl + (t & tadd) - (t & tsub) + ((cnt ^ cneg) - cneg)) & (sizeof(CT) == 2 ? 0xFFFFu : 0xFFFFFFFFu);
+    }
+}
+
+// A transposed item's 32 x 128 values, staged as st[row][column] words, stored as whole rows by the workgroup's 512 lanes:
+// dst = the first of the 32 rows in the tile's C(v) block.
+template <typename CT>
+__device__ __forceinline__ void sp_store_rows(const uint32_t *st, CT *dst, uint32_t tid)
+{
+    if (sizeof(CT) == 2) {
+        const uint32_t at = (tid >> 4) * kTile + (tid & 15u) * 8;
+        const uint4 a = *reinterpret_cast<const uint4 *>(st + at), b = *reinterpret_cast<const uint4 *>(st + at + 4);
+        *reinterpret_cast<uint4 *>(dst + at) = make_uint4(a.x | (a.y << 16), a.z | (a.w << 16), b.x | (b.y << 16), b.z | (b.w << 16));
+    } else {
+#pragma unroll
+        for (uint32_t h = 0; h < 2; ++h) {
+            const uint32_t g = tid + 512 * h, at = (g >> 5) * kTile + (g & 31u) * 4;
+            *reinterpret_cast<uint4 *>(dst + at) = *reinterpret_cast<const uint4 *>(st + at);
+        }
+    }
+}
+
+// One workgroup per item {tile index in band, plane | kSpItem* flags, slab of the row block, slab of the column block}; 512
+// lanes as (list row, table word).  cap is a multiple of 8: a lane reads its list eight 16-bit positions at a time.
 template <typename CT>
 __global__ __launch_bounds__(512) void k_sparse_count(const uint4 *__restrict__ items, const uint32_t *__restrict__ tab,
                                                       const uint16_t *__restrict__ lists, const uint32_t *__restrict__ len, uint32_t cap,
                                                       uint32_t m, CT *__restrict__ cum, uint64_t nslots)
 {
     __shared__ uint32_t lenj[kTile];
+    __shared__ __attribute__((aligned(16))) uint32_t turn[32 * kTile];  // (transposed items) 32 rows of the tile on their way out
     const uint4 it = items[blockIdx.x];
+    const bool tr = (it.y & kSpItemTransposed) != 0;  // (uniform over the workgroup)
+    const uint32_t ls = tr ? it.w : it.z, ts = tr ? it.z : it.w, plane = it.y & kSpPlaneMask;  // list slab, table slab
     const uint32_t tid = threadIdx.x, r = tid >> 2, w = tid & 3u;
-    if (tid < kTile) lenj[tid] = len[(uint64_t)it.w * kTile + tid];
+    if (tid < kTile) lenj[tid] = len[(uint64_t)ts * kTile + tid];
     __syncthreads();
-    const uint32_t li_all = len[(uint64_t)it.z * kTile + r];
+    const uint32_t li_all = len[(uint64_t)ls * kTile + r];
     const uint32_t li = li_all < cap ? li_all : cap;
-    const uint16_t *lp = lists + ((uint64_t)it.z * kTile + r) * cap;
-    const uint32_t *tb = tab + (uint64_t)it.w * m * 4 + w;
+    const uint16_t *lp = lists + ((uint64_t)ls * kTile + r) * cap;
+    const uint32_t *tb = tab + (uint64_t)ts * m * 4 + w;
     uint32_t c[kSpCounters];
 #pragma unroll
     for (int b = 0; b < kSpCounters; ++b) c[b] = 0;
@@ -162,20 +217,28 @@ __global__ __launch_bounds__(512) void k_sparse_count(const uint4 *__restrict__ 
         }
     }
     // column cc of this lane's word: bit cc of every counter word
-    const uint32_t base = m - li_all;
     uint32_t out[32];
-#pragma unroll
-    for (int cc = 0; cc < 32; ++cc) {
-        uint32_t cnt = 0;
-#pragma unroll
-        for (int b = 0; b < kSpCounters; ++b) cnt |= ((c[b] >> cc) & 1u) << b;
-        out[cc] = (base - lenj[w * 32 + cc] + cnt) & (sizeof(CT) == 2 ? 0xFFFFu : 0xFFFFFFFFu);
+    sp_values<CT>(out, c, it.y, m, li_all, lenj + w * 32);
+    CT *blk = cum + (uint64_t)plane * nslots + (uint64_t)it.x * (kTile * kTile);
+    if (!tr) {
+        put32(blk + (uint64_t)r * kTile + w * 32, out);
+        return;
     }
-    put32(cum + (uint64_t)it.y * nslots + (uint64_t)it.x * (kTile * kTile) + (uint64_t)r * kTile + w * 32, out);
+    // transposed: lane (r, w) holds column r of the rows w * 32 .. w * 32 + 31; a quarter of the tile at a time
+    for (uint32_t k = 0; k < 4; ++k) {
+        if (w == k) {
+#pragma unroll
+            for (int cc = 0; cc < 32; ++cc) turn[cc * kTile + r] = out[cc];
+        }
+        __syncthreads();
+        sp_store_rows<CT>(turn, blk + (uint64_t)k * 32 * kTile, tid);
+        __syncthreads();
+    }
 }
 
 // The LDS placement: workgroup g of a group of 32 takes item (g / 32) * 8 + g % 8 -- so that an item's launch position
-// still names its XCD (plan.cpp) -- and column word (g / 8) % 4.  lds: [2^p] the word's table, then the 32 columns' set sizes.
+// still names its XCD (plan.cpp) -- and table word (g / 8) % 4.  lds: [max(2^p, 4096)] the word's table -- and, once the
+// counting is done, a transposed item's 32 x 128 values -- then the 32 table columns' set sizes.
 template <typename CT>
 __global__ __launch_bounds__(512) void k_sparse_count_lds(const uint4 *__restrict__ items, uint32_t nitems, const uint32_t *__restrict__ tabw,
                                                           const uint16_t *__restrict__ lists, const uint32_t *__restrict__ len, uint32_t cap,
@@ -185,14 +248,17 @@ __global__ __launch_bounds__(512) void k_sparse_count_lds(const uint4 *__restric
     const uint32_t g = blockIdx.x, item = (g >> 5) * 8 + (g & 7u), w = (g >> 3) & 3u;
     if (item >= nitems) return;  // (the whole workgroup, in front of the barrier)
     const uint4 it = items[item];
+    const bool tr = (it.y & kSpItemTransposed) != 0;  // (uniform over the workgroup)
+    const uint32_t ls = tr ? it.w : it.z, ts = tr ? it.z : it.w, plane = it.y & kSpPlaneMask;  // list slab, table slab
     const uint32_t tid = threadIdx.x, r = tid >> 2, q = tid & 3u;
-    const uint4 *src = reinterpret_cast<const uint4 *>(tabw + ((uint64_t)it.w * 4 + w) * m);
+    const uint32_t lenat = m < 32u * kTile ? 32u * kTile : m;  // (launch_sparse_count sizes the LDS by the same rule)
+    const uint4 *src = reinterpret_cast<const uint4 *>(tabw + ((uint64_t)ts * 4 + w) * m);
     for (uint32_t i = tid; i < m / 4; i += 512) reinterpret_cast<uint4 *>(sp_lds)[i] = src[i];
-    if (tid < 32) sp_lds[m + tid] = len[(uint64_t)it.w * kTile + w * 32 + tid];
+    if (tid < 32) sp_lds[lenat + tid] = len[(uint64_t)ts * kTile + w * 32 + tid];
     __syncthreads();
-    const uint32_t li_all = len[(uint64_t)it.z * kTile + r];
+    const uint32_t li_all = len[(uint64_t)ls * kTile + r];
     const uint32_t li = li_all < cap ? li_all : cap;
-    const uint16_t *lp = lists + ((uint64_t)it.z * kTile + r) * cap;
+    const uint16_t *lp = lists + ((uint64_t)ls * kTile + r) * cap;
     uint32_t c[kSpCounters];
 #pragma unroll
     for (int b = 0; b < kSpCounters; ++b) c[b] = 0;
@@ -235,17 +301,25 @@ __global__ __launch_bounds__(512) void k_sparse_count_lds(const uint4 *__restric
             c[b] = sum;
         }
     }
-    if (q != 0) return;
-    const uint32_t base = m - li_all;
-    uint32_t out[32];
-#pragma unroll
-    for (int cc = 0; cc < 32; ++cc) {
-        uint32_t cnt = 0;
-#pragma unroll
-        for (int b = 0; b < kSpCounters; ++b) cnt |= ((c[b] >> cc) & 1u) << b;
-        out[cc] = (base - sp_lds[m + cc] + cnt) & (sizeof(CT) == 2 ? 0xFFFFu : 0xFFFFFFFFu);
+    CT *blk = cum + (uint64_t)plane * nslots + (uint64_t)it.x * (kTile * kTile);
+    if (!tr) {
+        if (q != 0) return;
+        uint32_t out[32];
+        sp_values<CT>(out, c, it.y, m, li_all, sp_lds + lenat);
+        put32(blk + (uint64_t)r * kTile + w * 32, out);
+        return;
     }
-    put32(cum + (uint64_t)it.y * nslots + (uint64_t)it.x * (kTile * kTile) + (uint64_t)r * kTile + w * 32, out);
+    // transposed: lane (r, 0) holds column r of the rows w * 32 .. w * 32 + 31.  The staged table word is dead behind the
+    // barrier: the 32 x 128 values are turned there and leave as whole rows
+    __syncthreads();
+    if (q == 0) {
+        uint32_t out[32];
+        sp_values<CT>(out, c, it.y, m, li_all, sp_lds + lenat);
+#pragma unroll
+        for (int cc = 0; cc < 32; ++cc) sp_lds[cc * kTile + r] = out[cc];
+    }
+    __syncthreads();
+    sp_store_rows<CT>(sp_lds, blk + (uint64_t)w * 32 * kTile, tid);
 }
 
 }  // namespace
@@ -270,7 +344,7 @@ hipError_t launch_sparse_count(hipStream_t st, int cum_bytes, const uint4 *items
     if (cap % 8 || cap > 2047) return hipErrorInvalidValue;
     if (wordmajor) {
         if (m < 512 || m > (1u << 15)) return hipErrorInvalidValue;  // (a word of the table in a CU's LDS)
-        const size_t lds = (size_t)m * 4 + 32 * 4;
+        const size_t lds = (size_t)std::max<uint32_t>(m, 32u * kTile) * 4 + 32 * 4;  // (a word of the table, or the turned values of a transposed item)
         const uint32_t grid = (nitems + 7) / 8 * 32;
 #define DSH_SPL(CT)                                                                                                                   \
     do {                                                                                                                              \

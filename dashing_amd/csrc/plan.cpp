@@ -491,7 +491,7 @@ void tile_planes(const Layout &L, uint32_t ti, uint32_t tj, int &pb, int &pe)
 
 void build_layout(const uint32_t *k32, uint64_t n, int want_sorted, uint64_t rb, uint64_t re,
                   const std::vector<uint64_t> &parts, Layout &L, uint32_t rowsorted_nparts, const std::vector<uint64_t> *extra_in,
-                  const uint32_t *gcnt)
+                  const uint32_t *gcnt, const uint32_t *thr, uint32_t thr_cap)
 {
     if (re > n) re = n;
     if (!want_sorted) rb = 0, re = n;
@@ -601,6 +601,9 @@ void build_layout(const uint32_t *k32, uint64_t n, int want_sorted, uint64_t rb,
     L.blk_hi.assign(NT, 0);
     L.blk_g0.assign(gcnt ? NT : 0, 0);
     L.blk_g1.assign(gcnt ? NT : 0, 0);
+    L.blk_vU.assign(thr ? NT : 0, 0);
+    L.blk_vA.assign(thr ? NT : 0, 64);
+    L.thr_cap = thr ? thr_cap : 0;
     int pbase = vr[2];
     const uint32_t *perm = L.perm.data();
     for (uint32_t b = 0; b < NT; ++b) {  // (a block at a time, its four statistics in registers)
@@ -629,6 +632,16 @@ void build_layout(const uint32_t *k32, uint64_t n, int want_sorted, uint64_t rb,
             }
             L.blk_g0[b] = (uint16_t)g0;
             L.blk_g1[b] = (uint16_t)g1;
+        }
+        if (thr) {
+            uint32_t vU = 0, vA = 64;
+            for (uint64_t s = s0; s < s1; ++s) {
+                const uint32_t t = thr[perm[s]];
+                vU = std::max(vU, t & 0xFFu);
+                vA = std::min(vA, (t >> 8) & 0xFFu);
+            }
+            L.blk_vU[b] = (uint8_t)vU;
+            L.blk_vA[b] = (uint8_t)vA;
         }
     }
     // dense planes cover v in (pbase, Tmax]: below the smallest low threshold every C(v) comes from the list join
@@ -680,6 +693,31 @@ static uint32_t sparse_route(const Layout &L, uint32_t cap, int nplanes, const U
     return k;
 }
 
+int sided_depth(const Layout &L, uint32_t b, int v)
+{
+    if (b >= L.blk_vU.size()) return -1;
+    return std::max(v - (int)L.blk_vU[b], (int)L.blk_vA[b] - v);
+}
+
+int sided_polarity(const Layout &L, uint32_t b, int v)
+{
+    if (b >= L.blk_vU.size() || v >= (int)L.blk_vU[b]) return 0;
+    return v <= (int)L.blk_vA[b] ? 1 : 0;
+}
+
+// the sided route of the tile {ti, tj, pb, pe}: `above` planes leave from the top of its range and `below` from its bottom
+static void sided_route(const Layout &L, const U4 &t, uint32_t &below, uint32_t &above)
+{
+    const uint32_t np = t.w - t.z;
+    auto routed = [&](uint32_t pl) {
+        const int v = L.pbase + 1 + (int)pl;
+        return sided_depth(L, t.x, v) >= 0 || sided_depth(L, t.y, v) >= 0;
+    };
+    above = below = 0;
+    while (above < np && routed(t.w - 1 - above)) ++above;
+    while (below + above < np && routed(t.z + below)) ++below;
+}
+
 static void tile_vrange(const Layout &L, const U4 &t, int &lo, int &hi)
 {
     lo = std::min<int>(L.blk_lo[t.x], L.blk_lo[t.y]);
@@ -698,6 +736,7 @@ bool build_tiles(const Layout &L, const PairQuery &job, const Tuning &tu, PairPl
     pp.band_frags.clear();
     pp.band_round.clear();
     pp.sp.clear();
+    pp.spb.clear();
     pp.sp_items.clear();
     pp.band_sp_items.clear();
     pp.slabs.clear();
@@ -759,6 +798,13 @@ bool build_tiles(const Layout &L, const PairQuery &job, const Tuning &tu, PairPl
     uint64_t job_planes = 0;
     for (const U4 &t : T) job_planes += t.w - t.z;
     const int sp_planes_job = job_planes > sp_min_planes ? sp_planes : 0;  // (what the cuts below are estimated with)
+    // the sided route (plan.h, Tuning::sparse_sided): the same calls, p >= 13, thresholds of this plan's cap; automatic
+    // where the two-plane route is automatic, behind the same gate
+    const bool sd_can = !job.rect && !job.sorted_rows && L.sorted && !L.blk_vU.empty() && L.thr_cap == sp_cap && tu.lockstep && tu.nsplit == 0 &&
+                        tu.W >= (uint32_t)tu.kc && tu.p >= 13 && tu.p <= 16;
+    const bool sd_forced = sd_can && tu.sparse_sided > 0;
+    const bool sd_auto = sd_can && tu.sparse_sided < 0 && tu.sparse_planes < 0 && kSparseSidedAuto;
+    const bool sided_job = sd_forced || (sd_auto && job_planes > sp_min_planes);
     // bands bounded by the cum scratch budget
     pp.per_tile_bytes = (uint64_t)kTile * kTile * tu.cum_bytes * std::max<uint32_t>(L.P, 1);
     // (at most 2^16 tiles per band: k_finalize addresses a pair slot of the band with 32 bits)
@@ -801,7 +847,14 @@ bool build_tiles(const Layout &L, const PairQuery &job, const Tuning &tu, PairPl
         // a longer launch takes pieces of 2-4 planes, i.e. longer rounds.  Jobs of up to 64 rounds are therefore cut into
         // bands of at most 16: the head as well as the tails (2 ranks of BASELINE configs[2]: 27 rounds = 15 + 9 + 3
         // instead of ONE launch of 15 two-plane rounds whose first part is final after 6 ms).
-        auto dense_planes = [&](const U4 &t) -> uint64_t { return t.w - t.z - (sp_planes_job ? sparse_route(L, sp_cap, sp_planes_job, t) : 0u); };
+        auto dense_planes = [&](const U4 &t) -> uint64_t {
+            if (sided_job) {
+                uint32_t lo, hi;
+                sided_route(L, t, lo, hi);
+                return t.w - t.z - lo - hi;
+            }
+            return t.w - t.z - (sp_planes_job ? sparse_route(L, sp_cap, sp_planes_job, t) : 0u);
+        };
         uint64_t items = 0;
         for (const U4 &t : T) items += dense_planes(t);
         const uint64_t R = (items + RI - 1) / RI;
@@ -890,33 +943,63 @@ bool build_tiles(const Layout &L, const PairQuery &job, const Tuning &tu, PairPl
     // sparse outer planes: band by band (the automatic rule looks at the band), the routed planes of every tile, one sparse
     // item each -- ordered by column block, whose table the items of a column share in L2 -- and the slabs they read
     pp.sp.assign(T.size(), 0);
+    pp.spb.assign(T.size(), 0);
+    pp.sided_items = pp.transposed_items = pp.table_slabs = 0;
     pp.band_sp_items.assign(pp.bands.size(), std::make_pair((size_t)0, (size_t)0));
-    if (sp_planes) {
+    if (sp_planes || sd_forced || sd_auto) {
         pp.slab_of.assign((size_t)NT * std::max<uint32_t>(L.P, 1), -1);
-        auto slab = [&](uint32_t b, uint32_t pl) -> uint32_t {
+        std::vector<uint8_t> listed;  // per slab: an item reads lists from it
+        auto slab = [&](uint32_t b, uint32_t pl, bool lists) -> uint32_t {
             int32_t &s = pp.slab_of[(size_t)b * L.P + pl];
             if (s < 0) {
                 s = (int32_t)pp.slabs.size();
-                pp.slabs.push_back(U2{b, pl});
+                // (the two-plane route's sets are U: where the thresholds are this plan's, that is what sided_polarity says too)
+                pp.slabs.push_back(U2{b, pl | (sd_can && sided_polarity(L, b, L.pbase + 1 + (int)pl) ? kSpSlabA : 0u)});
+                listed.push_back(0);
             }
+            if (lists) listed[(size_t)s] = 1;
             return (uint32_t)s;
         };
+        // the block whose table an item reads: its column block, the row block of a transposed one
+        auto table_block = [&](const std::pair<size_t, size_t> &bd, const U4 &it) { return it.y & kSpItemTransposed ? T[bd.first + it.x].x : T[bd.first + it.x].y; };
         for (size_t bi = 0; bi < pp.bands.size(); ++bi) {
             const auto &bd = pp.bands[bi];
             const size_t i0 = pp.sp_items.size();
             uint64_t band_planes = 0;
             for (size_t t = bd.first; t < bd.second; ++t) band_planes += T[t].w - T[t].z;
-            if (band_planes > sp_min_planes)
+            if (sd_forced || (sd_auto && band_planes > sp_min_planes)) {
+                for (size_t t = bd.first; t < bd.second; ++t) {
+                    uint32_t below, above;
+                    sided_route(L, T[t], below, above);
+                    const uint32_t k = below + above;
+                    if (!k || pp.slabs.size() + 2 * k > tu.sparse_max_slabs) continue;
+                    pp.sp[t] = (uint8_t)above;
+                    pp.spb[t] = (uint8_t)below;
+                    for (uint32_t x = 0; x < k; ++x) {
+                        const uint32_t pl = x < above ? T[t].w - 1 - x : T[t].z + (x - above);
+                        const int v = L.pbase + 1 + (int)pl;
+                        const bool tr = T[t].x != T[t].y && sided_depth(L, T[t].y, v) > sided_depth(L, T[t].x, v);
+                        const uint32_t lb = tr ? T[t].y : T[t].x, tb = tr ? T[t].x : T[t].y;
+                        const uint32_t fl = (sided_polarity(L, lb, v) ? kSpItemListA : 0u) | (sided_polarity(L, tb, v) ? kSpItemTabA : 0u) |
+                                            (tr ? kSpItemTransposed : 0u);
+                        pp.sp_items.push_back(U4{(uint32_t)(t - bd.first), pl | fl, slab(T[t].x, pl, !tr), slab(T[t].y, pl, tr || T[t].x == T[t].y)});
+                        ++pp.sided_items;
+                        pp.transposed_items += tr;
+                    }
+                }
+            } else if (sp_planes && band_planes > sp_min_planes) {
                 for (size_t t = bd.first; t < bd.second; ++t) {
                     const uint32_t k = sparse_route(L, sp_cap, sp_planes, T[t]);
                     if (!k || pp.slabs.size() + 2 * k > tu.sparse_max_slabs) continue;
                     pp.sp[t] = (uint8_t)k;
                     for (uint32_t x = 0; x < k; ++x) {
                         const uint32_t pl = T[t].w - 1 - x;
-                        pp.sp_items.push_back(U4{(uint32_t)(t - bd.first), pl, slab(T[t].x, pl), slab(T[t].y, pl)});
+                        pp.sp_items.push_back(U4{(uint32_t)(t - bd.first), pl, slab(T[t].x, pl, true), slab(T[t].y, pl, true)});
                     }
                 }
-            // Launch order.  An item gathers from its column block's table (16 bytes per position: 256 KiB at p = 14), which
+            }
+            // Launch order (a transposed item's table is its ROW block's: read "column block" as table_block() below).
+            // An item gathers from its column block's table (16 bytes per position: 256 KiB at p = 14), which
             // only pays while the table stays in L2; workgroup w runs on XCD w % 8 (xcd_order above).  So every column
             // block is given to ONE XCD -- the blocks with the most items first, each to the XCD with the fewest so far --
             // its items follow each other there, and the eight lists are interleaved one item at a time.
@@ -924,7 +1007,7 @@ bool build_tiles(const Layout &L, const PairQuery &job, const Tuning &tu, PairPl
             if (cnt > 1) {
                 constexpr size_t nx = 8;
                 std::vector<uint32_t> per_col(NT, 0), cols;
-                for (size_t k = i0; k < pp.sp_items.size(); ++k) per_col[T[bd.first + pp.sp_items[k].x].y]++;
+                for (size_t k = i0; k < pp.sp_items.size(); ++k) per_col[table_block(bd, pp.sp_items[k])]++;
                 for (uint32_t b = 0; b < NT; ++b)
                     if (per_col[b]) cols.push_back(b);
                 std::stable_sort(cols.begin(), cols.end(), [&](uint32_t a, uint32_t b) { return per_col[a] > per_col[b]; });
@@ -938,11 +1021,12 @@ bool build_tiles(const Layout &L, const PairQuery &job, const Tuning &tu, PairPl
                     load[x] += per_col[b];
                 }
                 std::vector<U4> lists[nx];
-                for (size_t k = i0; k < pp.sp_items.size(); ++k) lists[xcd_of[T[bd.first + pp.sp_items[k].x].y]].push_back(pp.sp_items[k]);
+                for (size_t k = i0; k < pp.sp_items.size(); ++k) lists[xcd_of[table_block(bd, pp.sp_items[k])]].push_back(pp.sp_items[k]);
                 for (auto &l : lists)
                     std::stable_sort(l.begin(), l.end(), [&](const U4 &a, const U4 &b) {
                         const U4 &ta = T[bd.first + a.x], &tb = T[bd.first + b.x];
-                        return ta.y != tb.y ? ta.y < tb.y : a.y != b.y ? a.y > b.y : ta.x < tb.x;
+                        const uint32_t ca = table_block(bd, a), cb = table_block(bd, b), pa = a.y & kSpPlaneMask, pb = b.y & kSpPlaneMask;
+                        return ca != cb ? ca < cb : pa != pb ? pa > pb : ta.x + ta.y < tb.x + tb.y;
                     });
                 size_t q = i0;
                 for (size_t r = 0; q < pp.sp_items.size(); ++r)
@@ -951,15 +1035,18 @@ bool build_tiles(const Layout &L, const PairQuery &job, const Tuning &tu, PairPl
             }
             pp.band_sp_items[bi] = std::make_pair(i0, pp.sp_items.size());
         }
+        // a slab that only serves as a table needs no lists (the sided route only: the two-plane route lists both blocks)
+        for (size_t k = 0; k < pp.slabs.size(); ++k)
+            if (!listed[k]) pp.slabs[k].y |= kSpSlabTableOnly, ++pp.table_slabs;
     }
     // chunk range of every tile (the work items of a band are cut from these: build_band_items); the planes routed sparse
-    // are the top of the tile's range and simply left out
+    // are the top (and, with the sided route, the bottom) of the tile's range and simply left out
     const uint32_t KC = (uint32_t)tu.kc;
     const uint32_t cpp = tu.W >= KC ? tu.W / KC : 1;  // chunks per plane when a plane spans chunks
     std::vector<U2> &CR = pp.chunks;
     CR.resize(T.size());
     if (tu.W >= KC) {  // whole chunks per plane (both powers of two)
-        for (size_t t = 0; t < T.size(); ++t) CR[t] = U2{T[t].z * cpp, (T[t].w - pp.sp[t]) * cpp};
+        for (size_t t = 0; t < T.size(); ++t) CR[t] = U2{(T[t].z + pp.spb[t]) * cpp, (T[t].w - pp.sp[t]) * cpp};
     } else {
         for (size_t t = 0; t < T.size(); ++t)
             CR[t] = U2{(uint32_t)(((uint64_t)T[t].z * tu.W) / KC), (uint32_t)(((uint64_t)T[t].w * tu.W + KC - 1) / KC)};

@@ -161,6 +161,12 @@ struct Layout {
     // (sparse outer planes, below) per block, with T = blk_T: no sketch of it has more than blk_g0 registers >= v for any
     // v >= T, nor more than blk_g1 registers >= T - 1 (saturating at 65535); empty when the layout was built without counts
     std::vector<uint16_t> blk_g0, blk_g1;
+    // (the sided route, Tuning::sparse_sided) per block: the largest vU and the smallest vA of its sketches, where a sketch has
+    // at most thr_cap registers >= v for v >= vU and at most thr_cap registers < v for v <= vA.  The block can carry the
+    // lists of plane v as U(v) = {a >= v} where v >= blk_vU and as A(v) = {a < v} where v <= blk_vA.  The thresholds belong
+    // to the cap they were computed for: a plan at another sparse_cap keeps the sided route off.  Empty without thresholds.
+    std::vector<uint8_t> blk_vU, blk_vA;
+    uint32_t thr_cap = 0;
     int vlo = 0, vhi = 0;         // register value range of the columns
     int pbase = 0;                // plane pl is the threshold pbase + 1 + pl
     uint32_t P = 0;               // dense planes
@@ -173,9 +179,11 @@ struct Layout {
 // extra (sorted layouts only): further wanted segments; the wanted range is then ONE part (`parts` is ignored).
 // gcnt (or nullptr: no plane is ever routed sparse): per sketch, next to its key, g0 | g1 << 16 of k_selfhist_card -- how
 // many of its registers are >= its T and >= T - 1
+// thr (or nullptr: no sided route), thr_cap: per sketch vU | vA << 8 of k_selfhist_card and the cap they were computed at
 void build_layout(const uint32_t *keys, uint64_t n, int want_sorted, uint64_t rb, uint64_t re,
                   const std::vector<uint64_t> &parts, Layout &L, uint32_t rowsorted_nparts = 0,
-                  const std::vector<uint64_t> *extra = nullptr, const uint32_t *gcnt = nullptr);
+                  const std::vector<uint64_t> *extra = nullptr, const uint32_t *gcnt = nullptr, const uint32_t *thr = nullptr,
+                  uint32_t thr_cap = 0);
 
 // dense plane range of the tile (ti, tj): C(v) is needed for v in (max(larger of the two minima, smaller of the two
 // low thresholds), larger of the two high thresholds] -- below that every C(v) is 0 or comes from the low-list join
@@ -189,8 +197,19 @@ struct PairQuery {
     uint64_t row_begin = 0, row_end = 0, col_begin = 0, col_end = 0;
 };
 
-constexpr uint32_t kSparseCapDefault = 1280, kSparseCapMax = 2040;  // sparse outer planes (Tuning): 11 counter words hold sets up to 2047
+// sparse outer planes (Tuning): 11 counter words hold sets up to 2047.  The default cap, measured with the sided route
+// (profiles/sparse2): an item whose lists are 1 280 .. 2 040 long costs 0.94 of the dense plane it replaces at 10 000 x p=14
+// (0.69 at p = 16) and its slab costs prepare: the step at 2 040 is 0.32 ms slower there and 0.28 ms faster at 5 000 x p=16,
+// which is inside three times the parent's range.  Items up to 1 280 cost 0.34 .. 0.42 of a dense plane.  No length class
+// costs more than a dense plane, so the planner leaves none dense.
+constexpr uint32_t kSparseCapDefault = 1280, kSparseCapMax = 2040;
 constexpr int kSparseAutoPlanes = 2;
+constexpr bool kSparseSidedAuto = true;  // whether sparse_sided = -1 turns the sided route on behind the automatic gate
+// flags of a sparse item (PairPlan::sp_items, .y above the plane) and of a slab (PairPlan::slabs, .y above the plane).
+// Polarity 0: the set U(v) = {a >= v}, the complement of the plane's words; 1: A(v) = {a < v}, the words as they are.
+constexpr uint32_t kSpPlaneMask = 0xFFu;
+constexpr uint32_t kSpItemListA = 1u << 8, kSpItemTabA = 1u << 9, kSpItemTransposed = 1u << 10;
+constexpr uint32_t kSpSlabA = 1u << 8, kSpSlabTableOnly = 1u << 9;
 
 struct Tuning {
     uint32_t W = 0;        // 32-bit words per plane
@@ -239,6 +258,17 @@ struct Tuning {
     int sparse_planes = 0;
     uint32_t sparse_cap = kSparseCapDefault;
     uint32_t sparse_max_slabs = 1u << 16;  // (block, plane) tables the caller has room for
+    // The sided route.  The counting kernel walks ONE side's lists and reads the other side's bits from a table that costs
+    // the same whatever its density, so only the list side has to be sparse, in either polarity:
+    //     list U, table U: C = m - |U_i| - |U_j| + cnt        list A, table A: C = cnt
+    //     list U, table A: C = |A_table| - cnt                list A, table U: C = |A_list| - cnt      (cnt = |R_list & S_table|)
+    // Plane v of a tile is routed iff one of its blocks can carry lists at v (Layout::blk_vU / blk_vA): a suffix and a
+    // prefix of the tile's range, the dense remainder stays one range.  The list side is the block deeper inside its bound
+    // (the row block on a tie); an item whose list side is the column block is TRANSPOSED.  The two-plane limit does not
+    // apply.  -1 automatic: on exactly where sparse_planes == -1 and its gate lets the band route; 0 off; 1 forced: the
+    // gate is ignored, the cap never, p >= 13 only (below that a set and its complement can both fit the cap).  Off
+    // whenever Layout::thr_cap is not the cap of this plan.
+    int sparse_sided = 0;
     int p = 0;                              // precision (the automatic rule, and the 16-bit positions)
 };
 
@@ -266,14 +296,20 @@ struct PairPlan {
     std::vector<uint32_t> sort_first;                    // scratch of the item sort
     std::vector<U4> sort_tmp;
     // sparse outer planes (Tuning): the tile's top sp[t] planes are not in its chunk range; each is one sparse item
-    std::vector<uint8_t> sp;                             // per tile: 0, 1 or 2
-    std::vector<U4> sp_items;                            // {tile index in band, plane, slab of the row block, slab of the column block}
+    std::vector<uint8_t> sp;                             // per tile: planes routed from the top of its range (0, 1 or 2 without the sided route)
+    std::vector<uint8_t> spb;                            // per tile: planes routed from the bottom of its range (the sided route only)
+    std::vector<U4> sp_items;                            // {tile index in band, plane | kSpItem* flags, slab of the row block, slab of the column block}
+    uint64_t sided_items = 0, transposed_items = 0, table_slabs = 0;  // items the sided route planned, transposed ones, table-only slabs
     std::vector<std::pair<size_t, size_t>> band_sp_items;  // sparse item ranges of the bands
-    std::vector<U2> slabs;                               // {block, plane}: the (table, row lists) the call's sparse items read
+    std::vector<U2> slabs;                               // {block, plane | kSpSlab* flags}: the (table, row lists) the call's sparse items read
     std::vector<int32_t> slab_of;                        // scratch: block * P + plane -> slab, or -1
 };
 // the bound on |{t : a_t >= v}| over the sketches of block b (v at most one below the block's T), else 65535
 uint32_t sparse_bound(const Layout &L, uint32_t b, int v);
+// the sided route: how far block b is inside its bound at v (>= 0: it can carry lists; the larger of v - blk_vU and
+// blk_vA - v), and the polarity its slab of plane v has (1: A) -- the one it qualifies in, U where it does not
+int sided_depth(const Layout &L, uint32_t b, int v);
+int sided_polarity(const Layout &L, uint32_t b, int v);
 
 // returns false when there is nothing to compute
 bool build_pairs(const Layout &L, const PairQuery &q, const Tuning &t, PairPlan &pp);

@@ -1066,6 +1066,13 @@ int dsh_finalize_phase_cycles(dsh_ctx *ctx, uint64_t *out16);
  *                                           launches of more than 512 planes.  Triangle calls on key-ordered columns only.
  *                                           Results do not depend on it.
  *                 "sparse_cap"              0..2040 (default 1280): the longest such set a routed plane may have
+ *                 "sparse_sided"            -1 auto | 0 off | 1 forced: a plane of a tile is counted from position lists
+ *                                           wherever ONE of its two blocks has every set -- registers at or above the
+ *                                           threshold, or below it -- within "sparse_cap"; the other block only serves as
+ *                                           a table.  Planes leave both ends of a tile's range, any number of them.  auto =
+ *                                           where "sparse_planes" is -1 and its rule routes; forced: at p >= 13 whatever
+ *                                           the size of the launch.  Off for a call whose "sparse_cap" is not the one the
+ *                                           per-sketch pass of the attached matrix ran with.  Results do not depend on it.
  *                 "sparse_lds"              1 (default) | 0: up to p = 15 the counting kernel stages a word of the block's
  *                                           position table in LDS; 0 = it gathers from global memory, as at p = 16
  *   exchange      "part_band_tiles"         a part of at least this many tiles also ends a launch of the tile kernel (2048)
@@ -1085,7 +1092,7 @@ int dsh_finalize_phase_cycles(dsh_ctx *ctx, uint64_t *out16);
  * ("pair_mfma" exists only in a library built with `make WHATIF=1`: the matrix-core what-if the north star excludes.) */
 int dsh_set_option(dsh_ctx *ctx, const char *name, int64_t value);
 /* Derived state of the last prepared sketch matrix: "planes" (dense bit-planes used), "vlo",
- * "vhi", "pbase", "threshold", "emax", "elow", "kc", "pair_groups" (as the last prepare put them into effect), "pair_round" (work items per round of the last dist call's first launch of the tile kernel: 256 x the items per workgroup it ran with), "tile", "npad", "kpad", "cum_bytes", "sorted", "ncols", "lockstep", "tiles", "bands", "items" (work items of the tile kernel), "sparse_items" ((tile, plane) items counted from position lists instead: option "sparse_planes"), "sparse_plane_us" (with profiling on: the device time of their counting kernel in the last dist call; it is part of the pair phase of dsh_last_kernel_ms), "sparse_planes", "sparse_cap",
+ * "vhi", "pbase", "threshold", "emax", "elow", "kc", "pair_groups" (as the last prepare put them into effect), "pair_round" (work items per round of the last dist call's first launch of the tile kernel: 256 x the items per workgroup it ran with), "tile", "npad", "kpad", "cum_bytes", "sorted", "ncols", "lockstep", "tiles", "bands", "items" (work items of the tile kernel), "sparse_items" ((tile, plane) items counted from position lists instead: option "sparse_planes"), "sparse_plane_us" (with profiling on: the device time of their counting kernel in the last dist call; it is part of the pair phase of dsh_last_kernel_ms), "sparse_sided_items" (those of them that the option "sparse_sided" planned), "sparse_transposed_items" (those whose lists are the column block's), "sparse_slabs" ((block, plane) slabs -- a table and position lists -- the last dist call's items read), "sparse_table_slabs" ((block, plane) tables of the last dist call built without lists), "sparse_planes", "sparse_sided", "sparse_cap",
  * "words_per_plane", "avg_tile_planes_x100" (of the last dist call), "frag_items", "parts_done", "parts_signalled",
  * "place_kernel_us" (with profiling on: device time of the last dsh_exchange_place_device's placement kernel),
  * "sketch_kernel_us" / "fastx_decode_us" (with profiling on: k_sketch / the FASTA-FASTQ decode kernels of the last sketch call),

@@ -41,6 +41,7 @@ PAIR_KC = 16     # k-rows of an LDS stage of the tile kernel with three items pe
 SPARSE_CAP = 1280        # kSparseCapDefault
 SPARSE_CAP_MAX = 2040    # kSparseCapMax
 SPARSE_AUTO_PLANES = 2   # kSparseAutoPlanes
+SPARSE_SIDED_AUTO = True  # kSparseSidedAuto: the sided route is on where the automatic rule routes
 SPARSE_MIN_BAND = 512    # the automatic rule: a band of more planes than this (Tuning::small_round_items under pair_groups = auto)
 
 # name -> what it stands for in the code.  The order is the order of the report.
@@ -123,10 +124,47 @@ def sparse_counts(regs, T):
     return np.minimum(g0, 65535), np.minimum(g1, 65535)
 
 
-def census(regs, p, emax=None, elow=None, sort=True, kc=PAIR_KC, sparse_planes=-1, sparse_cap=SPARSE_CAP):
+def sided_thresholds(regs, cap):
+    """k_selfhist_card's thresholds of the sided route at `cap`, per sketch: vU = the smallest v with #{a >= v} <= cap,
+    vA = the largest v with #{a < v} <= cap (v in 0 .. 64)"""
+    regs = np.asarray(regs)
+    h = np.stack([np.bincount(r, minlength=64)[:64] for r in regs]).astype(np.int64)
+    below = np.concatenate([np.zeros((len(regs), 1), np.int64), np.cumsum(h, axis=1)], axis=1)  # [:, v] = #{a < v}, v = 0 .. 64
+    at_or_above = below[:, -1:] - below                                                          # [:, v] = #{a >= v}
+    vU = (at_or_above <= cap).argmax(axis=1)
+    vA = 64 - (below <= cap)[:, ::-1].argmax(axis=1)
+    return vU, vA
+
+
+def sided_plane_counts(lists, tables, v, list_a, table_a):
+    """C(v) = #{t : a_t < v and b_t < v} of every (list sketch, table sketch) as the sided route counts it
+    (kernels_sparseplane.hip, sp_values): the list side's position lists R, the table side's table S -- each U(v) = {a >= v}
+    or, with its flag, A(v) = {a < v} -- cnt = |R & S| read off the table, and one of the four formulas"""
+    lists, tables = np.asarray(lists), np.asarray(tables)
+    m = lists.shape[1]
+    table = (tables.T < v) if table_a else (tables.T >= v)  # [m positions][table sketches]
+    lt = table.sum(axis=0).astype(np.int64)
+    out = np.empty((lists.shape[0], tables.shape[0]), np.int64)
+    for i, r in enumerate(lists):
+        pos = np.flatnonzero(r < v if list_a else r >= v)
+        ll, cnt = pos.size, table[pos].sum(axis=0)
+        if not list_a and not table_a:
+            out[i] = m - ll - lt + cnt
+        elif list_a and table_a:
+            out[i] = cnt
+        elif not list_a and table_a:
+            out[i] = lt - cnt
+        else:
+            out[i] = ll - cnt
+    return out
+
+
+def census(regs, p, emax=None, elow=None, sort=True, kc=PAIR_KC, sparse_planes=-1, sparse_cap=SPARSE_CAP, sparse_sided=0):
     """regs: [n, 2^p] uint8 (legal registers, <= 64 - p + 1); emax / elow: the list caps (None: plan::auto_list_cap);
     sort: the key-ordered column layout (True) or the identity (False); the whole triangle; sparse_planes / sparse_cap:
-    the two options of the sparse outer planes (-1: the automatic rule)"""
+    the two options of the sparse outer planes (-1: the automatic rule); sparse_sided: the sided route (plan.h,
+    Tuning::sparse_sided: -1 automatic, 0 off, 1 forced) -- every tile then has "below" and "sided", its items as
+    (plane, list A, table A, transposed), and the plan "sparse_sided_items", "sparse_transposed_items", "sparse_table_slabs" """
     regs = np.ascontiguousarray(regs, np.uint8)
     n = regs.shape[0]
     assert n >= 1 and regs.shape[1] == 1 << p and int(regs.max()) <= 64 - p + 1
@@ -219,11 +257,49 @@ def census(regs, p, emax=None, elow=None, sort=True, kc=PAIR_KC, sparse_planes=-
     if sparse_planes < 0 and sum(planes) <= SPARSE_MIN_BAND:  # (the automatic rule: one band here)
         for t in tiles:
             t["sparse"] = 0
-    sparse_items = sum(t["sparse"] for t in tiles)
+    # the sided route (plan.cpp, sided_route and build_tiles): per block the largest vU and the smallest vA
+    for t in tiles:
+        t["below"], t["sided"] = 0, []
+    sided_items = transposed = table_slabs = 0
+    sd_can = sort and inst["tile_kernel"] == "lockstep" and 13 <= p <= 16
+    if sd_can and (sparse_sided > 0 or (sparse_sided < 0 and sparse_planes < 0 and SPARSE_SIDED_AUTO and sum(planes) > SPARSE_MIN_BAND)):
+        vU, vA = sided_thresholds(regs, sp_cap)
+        for b in blk:
+            b["vU"], b["vA"] = int(vU[b["cols"]].max()), int(vA[b["cols"]].min())
+
+        def depth(b, v):
+            return max(v - b["vU"], b["vA"] - v)
+
+        def polarity(b, v):
+            return 0 if v >= b["vU"] else 1 if v <= b["vA"] else 0
+
+        listed = {}  # (block, plane) -> an item reads lists from it
+        for t in tiles:
+            bi, bj = blk[t["bi"]], blk[t["bj"]]
+            pb, pe = t["Lp"] - pbase, t["T"] - pbase
+            routed = [depth(bi, pbase + 1 + pl) >= 0 or depth(bj, pbase + 1 + pl) >= 0 for pl in range(pb, pe)]
+            above = below = 0
+            while above < pe - pb and routed[pe - pb - 1 - above]:
+                above += 1
+            while below + above < pe - pb and routed[below]:
+                below += 1
+            t["sparse"], t["below"] = above, below
+            for pl in [pe - 1 - x for x in range(above)] + [pb + x for x in range(below)]:
+                v = pbase + 1 + pl
+                tr = t["bi"] != t["bj"] and depth(bj, v) > depth(bi, v)
+                lb, tb = (bj, bi) if tr else (bi, bj)
+                t["sided"].append((pl, polarity(lb, v), polarity(tb, v), int(tr)))
+                for key, lists in (((t["bi"], pl), not tr), ((t["bj"], pl), tr or t["bi"] == t["bj"])):
+                    listed[key] = listed.get(key, False) or lists
+                sided_items += 1
+                transposed += int(tr)
+        table_slabs = sum(1 for x in listed.values() if not x)
+    sparse_items = sum(t["sparse"] + t["below"] for t in tiles)
     plan = {"planes": P, "pbase": pbase, "kpad": (P * W + kc - 1) // kc * kc, "tiles": len(planes), "sum_tile_planes": int(sum(planes)),
             "avg_tile_planes_x100": int(sum(planes)) * 100 // len(planes), "cum_bytes": inst["CT"],
             "lockstep": int(inst["tile_kernel"] == "lockstep"), "sorted": int(bool(sort)),
-            "sparse_items": sparse_items, "dense_planes": int(sum(planes)) - sparse_items}
+            "sparse_items": sparse_items, "dense_planes": int(sum(planes)) - sparse_items, "sparse_sided_items": sided_items,
+            "sparse_transposed_items": transposed, "sparse_table_slabs": table_slabs}
     return Census(inst, counts, plan, joins, tiles, blk)
 
 
