@@ -129,9 +129,12 @@ int prepare(dsh_ctx *c, int estim, int want_sorted, bool card_only, uint64_t wan
                             (unsigned long long)i, 64 - c->p + 1, c->p);
         c->planes_valid = false;  // (the cached layout is overwritten from here on)
         plan::Layout &L = c->lay;
-        if (!reuse_host_layout)
-            plan::build_layout(k32, n, want_sorted, want_rb, want_re, parts, L, rowsorted ? std::max<uint32_t>(nparts, 1) : 0,
-                               extra->empty() ? nullptr : extra, c->hg32, c->hv32, c->pass_sparse_cap);
+        if (!reuse_host_layout) {
+            const plan::SketchWords words{k32, c->hg32, c->hv32, c->pass_sparse_cap};
+            const plan::LayoutQuery query{want_sorted, want_rb, want_re, &parts, rowsorted ? std::max<uint32_t>(nparts, 1) : 0,
+                                          extra->empty() ? nullptr : extra};
+            plan::build_layout(n, words, query, L);
+        }
         ++c->lay_serial;
         c->lay_built = true;
         c->cum_bytes = c->p <= 15 ? 2 : 4;

@@ -55,74 +55,140 @@ struct Err {
     }
 };
 
-}  // namespace
-
+// What an entry point asks plan_check for.
 // mode: 0 triangle rows [rb, re) (want_sorted decides the layout), 1 rectangle rows [rb,re) x cols [cb,ce) (identity
 // layout), 2 sorted_rows (whole sorted layout, rows [rb,re) index plane columns: shards / band-wise kNN), 3 triangle
 // rows in ROW-SORTED parts (the wanted rows one key-ordered run, parts = runs of whole tile rows of that order).
 // stats out: [0] tiles, [1] bands, [2] items, [3] parts with an event, [4] planes per tile x 100, [5] Npad, [6] P,
 // [7] rounds summed over the bands, each in its own round (a round of fragments counted as one), [8] overflow fragments,
-// [9] (with round_items given) the round the first band was planned for.
-// round_items: the tile kernel's round (256 x the items per workgroup, engine.hip); 0 = the planner's default
-// extra: further wanted segments {b0, e0, ...} (plan.h, row sets; modes 0 and 3 with a sorted layout only)
-static int plan_check(uint64_t n, const uint32_t *keys, int mode, int want_sorted, uint64_t rb, uint64_t re, uint64_t cb,
-                      uint64_t ce, uint32_t nparts, int want_parts, int p, uint64_t cum_budget, int lockstep, int nsplit,
-                      int ls_item_chunks, const std::vector<uint64_t> &extra, uint64_t *stats, char *err, size_t cap,
-                      uint32_t round_items = 0, const SparseCheck *sc = nullptr)
+// [9] the round the first band was planned for, [10] sparse items, [11] slabs, [12] items of the sided route,
+// [13] transposed items, [14] table-only slabs -- as many of them as the entry point's caller has slots for (stats_slots).
+struct CheckJob {
+    uint64_t n = 0;
+    const uint32_t *keys = nullptr;
+    int mode = 0, want_sorted = 0;
+    uint64_t rb = 0, re = 0, cb = 0, ce = 0;
+    uint32_t nparts = 1;
+    int want_parts = 0, p = 0;
+    uint64_t cum_budget = 0;
+    int lockstep = 1, nsplit = 0, ls_item_chunks = 64;
+    std::vector<uint64_t> extra;  // further wanted segments {b0, e0, ...} (plan.h, row sets; modes 0 and 3 with a sorted layout only)
+    uint32_t round_items = 0;     // the tile kernel's round (256 x the items per workgroup, engine.hip); 0 = the planner's default
+    const SparseCheck *sc = nullptr;
+    uint64_t *stats = nullptr;
+    int stats_slots = 9;
+    // (resolve()) the layout's wanted range, and mode 3 spelled out
+    bool rowsorted = false;
+    uint64_t lrb = 0, lre = 0;
+
+    void resolve()
+    {
+        if (re > n) re = n;
+        rowsorted = mode == 3;
+        if (rowsorted) mode = 0, want_sorted = 1, want_parts = 1;
+        if (mode == 1 || !want_sorted) want_sorted = mode == 2 ? 1 : 0;
+        if (mode == 2) want_sorted = 1;
+        lrb = 0, lre = n;
+        if (want_sorted && mode == 0) lrb = rb, lre = re;
+    }
+    bool plan_parts() const { return want_parts && mode == 0 && want_sorted; }
+    // the wanted segments in the wanted order: extra segments first, then the main range
+    std::vector<std::pair<uint64_t, uint64_t>> wanted_segments() const
+    {
+        std::vector<std::pair<uint64_t, uint64_t>> wsegs;
+        wanted_order(n, lrb, lre, &extra, wsegs, rowsorted);
+        return wsegs;
+    }
+};
+
+bool in_rows(const std::vector<std::pair<uint64_t, uint64_t>> &wsegs, uint64_t i)
 {
-    Err E{err, cap};
-    if (re > n) re = n;
-    const bool rowsorted = mode == 3;
-    if (rowsorted) mode = 0, want_sorted = 1, want_parts = 1;
-    if (mode == 1 || !want_sorted) want_sorted = mode == 2 ? 1 : 0;
-    if (mode == 2) want_sorted = 1;
+    for (auto &w : wsegs)
+        if (i >= w.first && i < w.second) return true;
+    return false;
+}
+
+uint32_t chunks_per_plane(const Tuning &tu) { return tu.W >= (uint32_t)tu.kc ? tu.W / tu.kc : 1; }
+
+// layout, options and plan of a resolved job, exactly as engine.hip makes them
+void job_layout(const CheckJob &job, Layout &L)
+{
     std::vector<uint64_t> parts;
-    uint64_t lrb = 0, lre = n;
-    if (want_sorted && mode == 0) lrb = rb, lre = re;
-    if (want_sorted && !rowsorted) range_parts(n, lrb, lre, std::max<uint32_t>(want_parts ? nparts : 1, 1), parts);
-    if (!extra.empty() && !(want_sorted && mode == 0)) return E.fail("extra segments need a sorted triangle layout");
-    Layout L;
-    build_layout(keys, n, want_sorted, lrb, lre, parts, L, rowsorted ? std::max<uint32_t>(nparts, 1) : 0, extra.empty() ? nullptr : &extra,
-                 sc ? sc->gcnt : nullptr, sc ? sc->thr : nullptr, sc ? sc->thr_cap : 0);
-    // the wanted segments, main range first
-    std::vector<std::pair<uint64_t, uint64_t>> wsegs;  // (the wanted order: extra segments first, then the main range)
-    wanted_order(n, lrb, lre, &extra, wsegs, rowsorted);
-    auto in_rows = [&](uint64_t i) {
-        for (auto &w : wsegs)
-            if (i >= w.first && i < w.second) return true;
-        return false;
-    };
+    if (job.want_sorted && !job.rowsorted) range_parts(job.n, job.lrb, job.lre, std::max<uint32_t>(job.want_parts ? job.nparts : 1, 1), parts);
+    const SparseCheck *sc = job.sc;
+    const SketchWords words{job.keys, sc ? sc->gcnt : nullptr, sc ? sc->thr : nullptr, sc ? sc->thr_cap : 0};
+    const LayoutQuery query{job.want_sorted, job.lrb, job.lre, &parts, job.rowsorted ? std::max<uint32_t>(job.nparts, 1) : 0,
+                            job.extra.empty() ? nullptr : &job.extra};
+    build_layout(job.n, words, query, L);
+}
+
+bool job_plan(const CheckJob &job, const Layout &L, Tuning &tu, PairQuery &q, PairPlan &pp)
+{
+    const uint64_t m = 1ull << job.p;
+    tu.W = (uint32_t)std::max<uint64_t>(1, m / 32);
+    tu.kc = tu.W >= 32 ? 32 : 16;
+    tu.cum_bytes = job.p <= 15 ? 2 : 4;
+    tu.cum_budget = job.cum_budget;
+    tu.nsplit = job.nsplit;
+    tu.lockstep = job.lockstep && tu.W >= (uint32_t)tu.kc;
+    tu.ls_item_chunks = job.ls_item_chunks;
+    if (job.round_items) tu.round_items = job.round_items;
+    if (job.round_items > 512) tu.small_round_items = 512;  // (as engine.hip under pair_groups = auto)
+    tu.p = job.p;
+    if (job.sc) tu.sparse_planes = job.sc->planes, tu.sparse_cap = job.sc->cap, tu.sparse_sided = job.sc->sided;
+    q.rect = job.mode == 1;
+    q.sorted_rows = job.mode == 2;
+    q.want_parts = job.plan_parts();
+    q.row_begin = job.rb;
+    q.row_end = job.re;
+    q.col_begin = job.cb;
+    q.col_end = job.ce;
+    return build_pairs(L, q, tu, pp);
+}
+
+// ---- the checks: each returns at its first failure ---------------------------------------------------------------------
+
+// row-sorted: one key-ordered run per wanted segment, cuts on whole tile rows of the wanted order, row offsets of the rank's buffer
+int check_rowsorted(const CheckJob &job, const Layout &L, Err &E)
+{
+    const uint64_t n = job.n, lrb = job.lrb;
+    const uint32_t *keys = job.keys;
+    const auto wsegs = job.wanted_segments();
     uint64_t nw = 0, wspan = 0;
     for (auto &w : wsegs) nw += w.second - w.first, wspan += tri_span(n, w.first, w.second);
-    if (want_sorted && mode == 0 && L.nwanted != nw) return E.fail("nwanted %llu != %llu", (unsigned long long)L.nwanted, (unsigned long long)nw);
-    if (rowsorted) {  // one key-ordered run per wanted segment, cuts on whole tile rows of the wanted order, row offsets of the rank's buffer
-        auto skey = [&](uint32_t g) { return ((uint32_t)key_T(keys[g]) << 12) | ((uint32_t)key_L(keys[g]) << 6) | (uint32_t)key_hi(keys[g]); };
-        for (auto &w : wsegs)
-            for (uint64_t s = w.first - lrb + 1; s < w.second - lrb; ++s)
-                if (skey(L.perm[s - 1]) > skey(L.perm[s])) return E.fail("row-sorted: a wanted segment is not one key-ordered run at %llu", (unsigned long long)s);
-        if (L.part_w.empty() || L.part_w.front() != 0 || L.part_w.back() != nw) return E.fail("row-sorted: part cuts do not span the wanted rows");
-        for (size_t q = 1; q + 1 < L.part_w.size(); ++q) {  // every cut at the start of a tile row of the wanted order
-            if (L.part_w[q] <= L.part_w[q - 1]) return E.fail("row-sorted: cut %zu at %llu", q, (unsigned long long)L.part_w[q]);
-            uint64_t w0 = 0;
-            bool ok = false;
-            for (auto &w : wsegs) {
-                if (L.part_w[q] >= w0 && L.part_w[q] < w0 + (w.second - w.first)) ok = (L.part_w[q] - w0) % kTile == 0;
-                w0 += w.second - w.first;
-            }
-            if (!ok) return E.fail("row-sorted: cut %zu at %llu is not at a tile row of the wanted order", q, (unsigned long long)L.part_w[q]);
+    auto skey = [&](uint32_t g) { return ((uint32_t)key_T(keys[g]) << 12) | ((uint32_t)key_L(keys[g]) << 6) | (uint32_t)key_hi(keys[g]); };
+    for (auto &w : wsegs)
+        for (uint64_t s = w.first - lrb + 1; s < w.second - lrb; ++s)
+            if (skey(L.perm[s - 1]) > skey(L.perm[s])) return E.fail("row-sorted: a wanted segment is not one key-ordered run at %llu", (unsigned long long)s);
+    if (L.part_w.empty() || L.part_w.front() != 0 || L.part_w.back() != nw) return E.fail("row-sorted: part cuts do not span the wanted rows");
+    for (size_t q = 1; q + 1 < L.part_w.size(); ++q) {  // every cut at the start of a tile row of the wanted order
+        if (L.part_w[q] <= L.part_w[q - 1]) return E.fail("row-sorted: cut %zu at %llu", q, (unsigned long long)L.part_w[q]);
+        uint64_t w0 = 0;
+        bool ok = false;
+        for (auto &w : wsegs) {
+            if (L.part_w[q] >= w0 && L.part_w[q] < w0 + (w.second - w.first)) ok = (L.part_w[q] - w0) % kTile == 0;
+            w0 += w.second - w.first;
         }
-        if (L.part_w.size() - 1 > std::max<uint32_t>(nparts, 1)) return E.fail("row-sorted: more parts than asked for");
-        uint64_t acc = 0, w_ = 0;
-        if (L.rowoff_w.size() != nw + 1) return E.fail("row-sorted: rowoff_w size");
-        for (auto &w : wsegs)
-            for (uint64_t s = w.first - lrb; s < w.second - lrb; ++s, ++w_) {
-                if (s >= L.rowoff.size() || L.rowoff[s] != acc || L.rowoff_w[w_] != acc) return E.fail("row-sorted: rowoff[%llu]", (unsigned long long)s);
-                acc += n - 1 - L.perm[s];
-            }
-        if (L.rowoff_w.back() != acc || acc != wspan) return E.fail("row-sorted: the rows do not add up to the span");
+        if (!ok) return E.fail("row-sorted: cut %zu at %llu is not at a tile row of the wanted order", q, (unsigned long long)L.part_w[q]);
     }
-    // ---- layout: perm is a permutation of the columns; the parts hold exactly their rows; block stats are right
-    const uint64_t col0 = want_sorted ? lrb : 0;
+    if (L.part_w.size() - 1 > std::max<uint32_t>(job.nparts, 1)) return E.fail("row-sorted: more parts than asked for");
+    uint64_t acc = 0, w_ = 0;
+    if (L.rowoff_w.size() != nw + 1) return E.fail("row-sorted: rowoff_w size");
+    for (auto &w : wsegs)
+        for (uint64_t s = w.first - lrb; s < w.second - lrb; ++s, ++w_) {
+            if (s >= L.rowoff.size() || L.rowoff[s] != acc || L.rowoff_w[w_] != acc) return E.fail("row-sorted: rowoff[%llu]", (unsigned long long)s);
+            acc += n - 1 - L.perm[s];
+        }
+    if (L.rowoff_w.back() != acc || acc != wspan) return E.fail("row-sorted: the rows do not add up to the span");
+    return 0;
+}
+
+// layout: perm is a permutation of the columns; the parts hold exactly their rows; block stats are right
+int check_layout(const CheckJob &job, const Layout &L, Err &E)
+{
+    const uint64_t n = job.n, lrb = job.lrb, lre = job.lre;
+    const auto wsegs = job.wanted_segments();
+    const uint64_t col0 = job.want_sorted ? lrb : 0;
     if (L.ncols != n - col0) return E.fail("ncols %llu != %llu", (unsigned long long)L.ncols, (unsigned long long)(n - col0));
     if (L.Npad % kTile || L.Npad < L.ncols || L.Npad >= L.ncols + kTile) return E.fail("bad Npad %u", L.Npad);
     std::vector<uint8_t> seen(n, 0);
@@ -131,91 +197,66 @@ static int plan_check(uint64_t n, const uint32_t *keys, int mode, int want_sorte
         if (g < col0 || g >= n || seen[g]) return E.fail("perm[%llu] = %u is out of range or repeated", (unsigned long long)s, g);
         seen[g] = 1;
     }
-    if (want_sorted) {
-        uint64_t s = 0;
-        for (size_t q = 0; q + 1 < L.parts.size(); ++q)
-            for (uint64_t r = L.parts[q]; r < L.parts[q + 1]; ++r, ++s)
-                if (L.perm[s] < L.parts[q] || L.perm[s] >= L.parts[q + 1])
-                    return E.fail("column %llu holds sketch %u, not a row of part %zu", (unsigned long long)s, L.perm[s], q);
-        if (!rowsorted && extra.empty()) {
-            if (L.part_pos.size() != L.parts.size()) return E.fail("part positions and parts differ in number");
-            for (size_t q = 0; q < L.parts.size(); ++q)
-                if (L.part_pos[q] != L.parts[q] - lrb) return E.fail("part position %zu", q);
-        }
-        for (; s < L.ncols; ++s)
-            if (L.perm[s] < lre) return E.fail("column %llu (after the wanted rows) holds wanted row %u", (unsigned long long)s, L.perm[s]);
-        // every run holds exactly its rows: a wanted segment's positions hold its rows; every block is wanted or not as a whole
-        for (auto &w : wsegs)
-            for (uint64_t s2 = w.first - lrb; s2 < w.second - lrb; ++s2)
-                if (L.perm[s2] < w.first || L.perm[s2] >= w.second) return E.fail("position %llu of a wanted segment holds row %u", (unsigned long long)s2, L.perm[s2]);
-        if (!extra.empty())
-            for (uint64_t s2 = 0; s2 < L.ncols; ++s2) {
-                // rows to the right of a position are larger unless they share its run: position order = row order between runs
-                const uint64_t b = s2 / kTile * kTile;
-                if (in_rows(L.perm[s2]) != in_rows(L.perm[b])) return E.fail("block %llu mixes wanted and other rows", (unsigned long long)(b / kTile));
-            }
-        if (L.whole)
-            for (uint64_t i = 0; i < n; ++i)
-                if (L.perm[n + L.perm[i]] != i) return E.fail("inverse permutation wrong at %llu", (unsigned long long)i);
+    if (!job.want_sorted) return 0;
+    uint64_t s = 0;
+    for (size_t q = 0; q + 1 < L.parts.size(); ++q)
+        for (uint64_t r = L.parts[q]; r < L.parts[q + 1]; ++r, ++s)
+            if (L.perm[s] < L.parts[q] || L.perm[s] >= L.parts[q + 1])
+                return E.fail("column %llu holds sketch %u, not a row of part %zu", (unsigned long long)s, L.perm[s], q);
+    if (!job.rowsorted && job.extra.empty()) {
+        if (L.part_pos.size() != L.parts.size()) return E.fail("part positions and parts differ in number");
+        for (size_t q = 0; q < L.parts.size(); ++q)
+            if (L.part_pos[q] != L.parts[q] - lrb) return E.fail("part position %zu", q);
     }
-    Tuning tu;
-    const uint64_t m = 1ull << p;
-    tu.W = (uint32_t)std::max<uint64_t>(1, m / 32);
-    tu.kc = tu.W >= 32 ? 32 : 16;
-    tu.cum_bytes = p <= 15 ? 2 : 4;
-    tu.cum_budget = cum_budget;
-    tu.nsplit = nsplit;
-    tu.lockstep = lockstep && tu.W >= (uint32_t)tu.kc;
-    tu.ls_item_chunks = ls_item_chunks;
-    if (round_items) tu.round_items = round_items;
-    if (round_items > 512) tu.small_round_items = 512;  // (as engine.hip under pair_groups = auto)
-    tu.p = p;
-    if (sc) tu.sparse_planes = sc->planes, tu.sparse_cap = sc->cap, tu.sparse_sided = sc->sided;
-    PairQuery q;
-    q.rect = mode == 1;
-    q.sorted_rows = mode == 2;
-    q.want_parts = want_parts && mode == 0 && want_sorted;
-    q.row_begin = rb;
-    q.row_end = re;
-    q.col_begin = cb;
-    q.col_end = ce;
-    PairPlan pp;
-    const bool any = build_pairs(L, q, tu, pp);
-    for (int i = 0; i < 9; ++i) stats[i] = 0;
-    stats[5] = L.Npad;
-    stats[6] = L.P;
-    // ---- every wanted pair is owned by exactly one (tile, lane) -- the `active` predicate of k_finalize
-    std::vector<uint8_t> hit;
+    for (; s < L.ncols; ++s)
+        if (L.perm[s] < lre) return E.fail("column %llu (after the wanted rows) holds wanted row %u", (unsigned long long)s, L.perm[s]);
+    // every run holds exactly its rows: a wanted segment's positions hold its rows; every block is wanted or not as a whole
+    for (auto &w : wsegs)
+        for (uint64_t s2 = w.first - lrb; s2 < w.second - lrb; ++s2)
+            if (L.perm[s2] < w.first || L.perm[s2] >= w.second) return E.fail("position %llu of a wanted segment holds row %u", (unsigned long long)s2, L.perm[s2]);
+    if (!job.extra.empty())
+        for (uint64_t s2 = 0; s2 < L.ncols; ++s2) {
+            // rows to the right of a position are larger unless they share its run: position order = row order between runs
+            const uint64_t b = s2 / kTile * kTile;
+            if (in_rows(wsegs, L.perm[s2]) != in_rows(wsegs, L.perm[b])) return E.fail("block %llu mixes wanted and other rows", (unsigned long long)(b / kTile));
+        }
+    if (L.whole)
+        for (uint64_t i = 0; i < n; ++i)
+            if (L.perm[n + L.perm[i]] != i) return E.fail("inverse permutation wrong at %llu", (unsigned long long)i);
+    return 0;
+}
+
+// the pairs the job wants
+uint64_t wanted_pairs(const CheckJob &job)
+{
+    const uint64_t n = job.n, rb = job.rb, re = job.re;
+    if (job.mode == 1) return (re > rb ? re - rb : 0) * (job.ce > job.cb ? job.ce - job.cb : 0);
     uint64_t wanted = 0;
-    auto orig = [&](uint64_t s) -> uint64_t { return L.perm[s]; };
-    if (mode == 1) {
-        const uint64_t nr = re > rb ? re - rb : 0, nc = ce > cb ? ce - cb : 0;
-        wanted = nr * nc;
-        hit.assign(wanted, 0);
-    } else {
-        hit.assign(n * n, 0);
-        for (uint64_t i = rb; i < re; ++i) wanted += n - 1 - i;
-        for (size_t x = 0; x + 1 < extra.size(); x += 2)
-            for (uint64_t i = extra[x]; i < extra[x + 1]; ++i) wanted += n - 1 - i;
-        if (mode == 2) {
-            wanted = 0;
-            for (uint64_t si = rb; si < re; ++si) wanted += n - 1 - si;
-        }
-    }
-    if (!any) {
-        if (wanted) return E.fail("nothing planned although %llu pairs are wanted", (unsigned long long)wanted);
-        return 0;
-    }
-    const std::vector<U4> &T = pp.T;
-    uint64_t got = 0, planes_sum = 0;
-    for (const U4 &t : T) {
+    for (uint64_t i = rb; i < re; ++i) wanted += n - 1 - i;
+    if (job.mode == 2) return wanted;  // (rows of the layout: si = rb .. re - 1)
+    for (size_t x = 0; x + 1 < job.extra.size(); x += 2)
+        for (uint64_t i = job.extra[x]; i < job.extra[x + 1]; ++i) wanted += n - 1 - i;
+    return wanted;
+}
+
+// coverage: every wanted pair is owned by exactly one (tile, lane) -- the `active` predicate of k_finalize
+int check_coverage(const CheckJob &job, const Layout &L, const PairPlan &pp, Err &E)
+{
+    const uint64_t n = job.n, rb = job.rb, re = job.re, cb = job.cb, ce = job.ce;
+    const int mode = job.mode;
+    const uint32_t *keys = job.keys;
+    const std::vector<uint64_t> &extra = job.extra;
+    const auto wsegs = job.wanted_segments();
+    const uint64_t wanted = wanted_pairs(job);
+    std::vector<uint8_t> hit(mode == 1 ? wanted : n * n, 0);
+    uint64_t got = 0;
+    for (const U4 &t : pp.T) {
         if (t.z > t.w || t.w > L.P) return E.fail("tile (%u,%u) has the plane range [%u,%u) of %u", t.x, t.y, t.z, t.w, L.P);
-        planes_sum += t.w - t.z;
         for (uint32_t a = 0; a < kTile; ++a)
             for (uint32_t b = 0; b < kTile; ++b) {
                 const uint64_t si = (uint64_t)t.x * kTile + a, sj = (uint64_t)t.y * kTile + b;
                 if (si >= L.ncols || sj >= L.ncols) continue;
-                const uint64_t i = orig(si), j = orig(sj);
+                const uint64_t i = L.perm[si], j = L.perm[sj];
                 bool active;
                 uint64_t slot;
                 if (mode == 1) {
@@ -229,7 +270,7 @@ static int plan_check(uint64_t n, const uint32_t *keys, int mode, int want_sorte
                     const uint64_t oi = std::min(i, j), oj = std::max(i, j);
                     active = si < sj && oi >= rb && oi < (extra.empty() ? re : n);
                     slot = oi * n + oj;
-                    if (active && !extra.empty() && !in_rows(oi))
+                    if (active && !extra.empty() && !in_rows(wsegs, oi))
                         return E.fail("tile (%u,%u) computes the pair (%llu,%llu) of a row this rank does not hold", t.x, t.y, (unsigned long long)oi, (unsigned long long)oj);
                 }
                 if (!active) continue;
@@ -245,7 +286,15 @@ static int plan_check(uint64_t n, const uint32_t *keys, int mode, int want_sorte
             }
     }
     if (got != wanted) return E.fail("%llu of %llu wanted pairs are covered", (unsigned long long)got, (unsigned long long)wanted);
-    // ---- bands cover the tiles in order and respect the scratch budget (a single tile may exceed it)
+    return 0;
+}
+
+// bands cover the tiles in order and respect the scratch budget (a single tile may exceed it); segments follow each other and
+// complete the parts in order; the items of a band cover every tile's chunk range exactly once
+int check_bands_and_items(const CheckJob &job, const Layout &L, const Tuning &tu, const PairPlan &pp, Err &E)
+{
+    const std::vector<U4> &T = pp.T;
+    const uint32_t cpp_ = chunks_per_plane(tu);
     size_t at = 0;
     if (pp.bands.size() != pp.segs.size() || pp.bands.size() != pp.band_items.size()) return E.fail("band bookkeeping sizes differ");
     std::vector<int> part_done(pp.nparts, 0);
@@ -254,8 +303,8 @@ static int plan_check(uint64_t n, const uint32_t *keys, int mode, int want_sorte
         const auto &bd = pp.bands[bi];
         if (bd.first != at || bd.second <= bd.first || bd.second > T.size()) return E.fail("band %zu = [%zu,%zu) does not follow %zu", bi, bd.first, bd.second, at);
         at = bd.second;
-        if (bd.second - bd.first > 1 && (bd.second - bd.first) * pp.per_tile_bytes > cum_budget)
-            return E.fail("band %zu needs %llu bytes of C(v), budget %llu", bi, (unsigned long long)((bd.second - bd.first) * pp.per_tile_bytes), (unsigned long long)cum_budget);
+        if (bd.second - bd.first > 1 && (bd.second - bd.first) * pp.per_tile_bytes > job.cum_budget)
+            return E.fail("band %zu needs %llu bytes of C(v), budget %llu", bi, (unsigned long long)((bd.second - bd.first) * pp.per_tile_bytes), (unsigned long long)job.cum_budget);
         size_t sa = bd.first;
         for (const Seg &sg : pp.segs[bi]) {
             if (sg.b != sa || sg.e <= sg.b || sg.e > bd.second) return E.fail("segment [%zu,%zu) of band %zu does not follow %zu", sg.b, sg.e, bi, sa);
@@ -266,7 +315,7 @@ static int plan_check(uint64_t n, const uint32_t *keys, int mode, int want_sorte
                 last_part = sg.part;
             }
             // every tile of the segment belongs to the part that is current (parts are runs of the WANTED order)
-            if (q.want_parts)
+            if (job.plan_parts())
                 for (size_t t = sg.b; t < sg.e; ++t) {
                     uint64_t pos0 = ~0ull;  // wanted rows in front of the tile's row block
                     for (size_t k = 0; k < L.wtr.size(); ++k)
@@ -280,19 +329,14 @@ static int plan_check(uint64_t n, const uint32_t *keys, int mode, int want_sorte
         // items of the band cover every tile's chunk range exactly once
         const auto &bi_ = pp.band_items[bi];
         if (band_item_count(tu, pp, bi) != bi_.second - bi_.first) return E.fail("band %zu: band_item_count disagrees with the items built", bi);
-        std::vector<uint32_t> next(bd.second - bd.first);
-        for (size_t t = bd.first; t < bd.second; ++t) next[t - bd.first] = pp.chunks[t].x;
         std::vector<std::vector<std::pair<uint32_t, uint32_t>>> per(bd.second - bd.first);
-        const uint32_t cpp_ = tu.W >= (uint32_t)tu.kc ? tu.W / tu.kc : 1;
         // overflow fragments (plan.h): the band's LAST band_frags items, each inside one plane, equal in length, at most one
         // round of them; the whole items in front of them a whole number of rounds
         const uint32_t nfr = bi < pp.band_frags.size() ? pp.band_frags[bi] : 0u;
         const uint32_t bri = bi < pp.band_round.size() ? pp.band_round[bi] : 0u;  // the round this band was planned for
         if (bri != tu.round_items && !(tu.small_round_items && bri == tu.small_round_items)) return E.fail("band %zu: round of %u items", bi, bri);
-        if (bi == 0 && round_items) stats[9] = bri;  // (dshh_plan_check_ri only: its callers pass ten slots)
         if (nfr > bi_.second - bi_.first || nfr > bri) return E.fail("band %zu: %u fragments", bi, nfr);
         if (nfr && (!tu.lockstep || (bi_.second - bi_.first - nfr) % bri)) return E.fail("band %zu: fragments behind %zu whole items", bi, bi_.second - bi_.first - nfr);
-        stats[8] += nfr;
         for (size_t it = bi_.first; it < bi_.second; ++it) {
             const U4 &I = pp.items[it];
             if (I.x >= per.size() || I.y >= I.z) return E.fail("item %zu is malformed", it);
@@ -320,112 +364,135 @@ static int plan_check(uint64_t n, const uint32_t *keys, int mode, int want_sorte
         }
     }
     if (at != T.size()) return E.fail("bands end at %zu of %zu tiles", at, T.size());
-    // ---- sparse outer planes: every plane of a tile's range is in the tile's chunk range (checked above against
-    // pp.chunks) or has exactly one sparse item, never both; a routed plane's sets are inside the cap
-    // With the sided route every plane of a tile's range is in exactly one route: the dense remainder [pb + below, pe - above)
-    // -- one range -- or one sparse item; an item's list block is within its bound, in the item's polarity, for every sketch.
+    return 0;
+}
+
+// sparse outer planes: every plane of a tile's range is in the tile's chunk range (check_bands_and_items holds the items to
+// pp.chunks) or has exactly one sparse item, never both; a routed plane's sets are inside the cap.
+// With the sided route every plane of a tile's range is in exactly one route: the dense remainder [pb + below, pe - above)
+// -- one range -- or one sparse item; an item's list block is within its bound, in the item's polarity, for every sketch.
+// Then the routes, items and slabs go to the caller that asked for them.
+int check_sparse(const CheckJob &job, const Layout &L, const Tuning &tu, const PairPlan &pp, Err &E)
+{
+    const std::vector<U4> &T = pp.T;
+    const SparseCheck *sc = job.sc;
+    const uint32_t *keys = job.keys;
     if (pp.sp.size() != T.size() || pp.spb.size() != T.size() || pp.band_sp_items.size() != pp.bands.size()) return E.fail("sparse bookkeeping sizes differ");
     const bool sided_chk = sc && sc->thr && sc->sided != 0 && pp.sided_items > 0;
-    {
-        const uint32_t cpp_ = tu.W >= (uint32_t)tu.kc ? tu.W / tu.kc : 1;
-        std::vector<uint8_t> seen_pl;
-        size_t sat = 0;
-        for (size_t bi = 0; bi < pp.bands.size(); ++bi) {
-            const auto &bd = pp.bands[bi];
-            const auto &rg = pp.band_sp_items[bi];
-            if (rg.first != sat || rg.second < rg.first || rg.second > pp.sp_items.size()) return E.fail("sparse items of band %zu do not follow %zu", bi, sat);
-            sat = rg.second;
-            seen_pl.assign((bd.second - bd.first) * 64, 0);
-            for (size_t k = rg.first; k < rg.second; ++k) {
-                const U4 &I = pp.sp_items[k];
-                if (I.x >= bd.second - bd.first) return E.fail("sparse item %zu names tile %u of band %zu", k, I.x, bi);
-                const size_t t = bd.first + I.x;
-                const uint32_t sp = pp.sp[t], spb = pp.spb[t], Ipl = I.y & kSpPlaneMask;
-                if (Ipl >= T[t].w || Ipl < T[t].z || (Ipl + sp < T[t].w && Ipl >= T[t].z + spb))
-                    return E.fail("sparse item %zu: plane %u is not one of the top %u or bottom %u of tile %zu", k, Ipl, sp, spb, t);
-                if (T[t].w - T[t].z > 64) return E.fail("tile %zu has %u planes: register values are below 64", t, T[t].w - T[t].z);
-                if (seen_pl[I.x * 64 + (Ipl - T[t].z)]++) return E.fail("plane %u of tile %zu has two sparse items", Ipl, t);
-                if (I.z >= pp.slabs.size() || I.w >= pp.slabs.size() || pp.slabs[I.z].x != T[t].x || (pp.slabs[I.z].y & kSpPlaneMask) != Ipl ||
-                    pp.slabs[I.w].x != T[t].y || (pp.slabs[I.w].y & kSpPlaneMask) != Ipl)
-                    return E.fail("sparse item %zu names the wrong slabs", k);
-                const int v = L.pbase + 1 + (int)Ipl;
-                if (sided_chk) {
-                    const bool tr = (I.y & kSpItemTransposed) != 0, la = (I.y & kSpItemListA) != 0, ta = (I.y & kSpItemTabA) != 0;
-                    if (tr && T[t].x == T[t].y) return E.fail("sparse item %zu: a diagonal tile is transposed", k);
-                    const U2 &lsl = pp.slabs[tr ? I.w : I.z], &tsl = pp.slabs[tr ? I.z : I.w];
-                    if (((lsl.y & kSpSlabA) != 0) != la || ((tsl.y & kSpSlabA) != 0) != ta) return E.fail("sparse item %zu: polarities differ from its slabs'", k);
-                    if (lsl.y & kSpSlabTableOnly) return E.fail("sparse item %zu reads lists from a table-only slab", k);
-                    if (L.thr_cap != tu.sparse_cap) return E.fail("sparse item %zu planned on thresholds of cap %u at cap %u", k, L.thr_cap, tu.sparse_cap);
+    const uint32_t cpp_ = chunks_per_plane(tu);
+    std::vector<uint8_t> seen_pl;
+    size_t sat = 0;
+    for (size_t bi = 0; bi < pp.bands.size(); ++bi) {
+        const auto &bd = pp.bands[bi];
+        const auto &rg = pp.band_sp_items[bi];
+        if (rg.first != sat || rg.second < rg.first || rg.second > pp.sp_items.size()) return E.fail("sparse items of band %zu do not follow %zu", bi, sat);
+        sat = rg.second;
+        seen_pl.assign((bd.second - bd.first) * 64, 0);
+        for (size_t k = rg.first; k < rg.second; ++k) {
+            const U4 &I = pp.sp_items[k];
+            if (I.x >= bd.second - bd.first) return E.fail("sparse item %zu names tile %u of band %zu", k, I.x, bi);
+            const size_t t = bd.first + I.x;
+            const uint32_t sp = pp.sp[t], spb = pp.spb[t], Ipl = I.y & kSpPlaneMask;
+            if (Ipl >= T[t].w || Ipl < T[t].z || (Ipl + sp < T[t].w && Ipl >= T[t].z + spb))
+                return E.fail("sparse item %zu: plane %u is not one of the top %u or bottom %u of tile %zu", k, Ipl, sp, spb, t);
+            if (T[t].w - T[t].z > 64) return E.fail("tile %zu has %u planes: register values are below 64", t, T[t].w - T[t].z);
+            if (seen_pl[I.x * 64 + (Ipl - T[t].z)]++) return E.fail("plane %u of tile %zu has two sparse items", Ipl, t);
+            if (I.z >= pp.slabs.size() || I.w >= pp.slabs.size() || pp.slabs[I.z].x != T[t].x || (pp.slabs[I.z].y & kSpPlaneMask) != Ipl ||
+                pp.slabs[I.w].x != T[t].y || (pp.slabs[I.w].y & kSpPlaneMask) != Ipl)
+                return E.fail("sparse item %zu names the wrong slabs", k);
+            const int v = L.pbase + 1 + (int)Ipl;
+            if (sided_chk) {
+                const bool tr = (I.y & kSpItemTransposed) != 0, la = (I.y & kSpItemListA) != 0, ta = (I.y & kSpItemTabA) != 0;
+                if (tr && T[t].x == T[t].y) return E.fail("sparse item %zu: a diagonal tile is transposed", k);
+                const U2 &lsl = pp.slabs[tr ? I.w : I.z], &tsl = pp.slabs[tr ? I.z : I.w];
+                if (((lsl.y & kSpSlabA) != 0) != la || ((tsl.y & kSpSlabA) != 0) != ta) return E.fail("sparse item %zu: polarities differ from its slabs'", k);
+                if (lsl.y & kSpSlabTableOnly) return E.fail("sparse item %zu reads lists from a table-only slab", k);
+                if (L.thr_cap != tu.sparse_cap) return E.fail("sparse item %zu planned on thresholds of cap %u at cap %u", k, L.thr_cap, tu.sparse_cap);
+                for (uint32_t a = 0; a < kTile; ++a) {
+                    const uint64_t sx = (uint64_t)lsl.x * kTile + a;
+                    if (sx >= L.ncols) continue;
+                    const uint32_t th = sc->thr[L.perm[sx]];
+                    if (la ? v > (int)((th >> 8) & 0xFFu) : v < (int)(th & 0xFFu))
+                        return E.fail("sparse item %zu: sketch %llu of the list block is outside its bound at v = %d", k, (unsigned long long)L.perm[sx], v);
+                }
+                continue;
+            }
+            if (I.y != Ipl || pp.slabs[I.z].y != Ipl || pp.slabs[I.w].y != Ipl) return E.fail("sparse item %zu carries flags without the sided route", k);
+            if (sparse_bound(L, T[t].x, v) > tu.sparse_cap || sparse_bound(L, T[t].y, v) > tu.sparse_cap) return E.fail("sparse item %zu: a set may exceed the cap", k);
+            // the bound holds for every sketch of the two blocks (what the lists and counters are sized by)
+            if (sc && sc->gcnt)
+                for (int side = 0; side < 2; ++side)
                     for (uint32_t a = 0; a < kTile; ++a) {
-                        const uint64_t sx = (uint64_t)lsl.x * kTile + a;
+                        const uint64_t sx = (uint64_t)(side ? T[t].y : T[t].x) * kTile + a;
                         if (sx >= L.ncols) continue;
-                        const uint32_t th = sc->thr[orig(sx)];
-                        if (la ? v > (int)((th >> 8) & 0xFFu) : v < (int)(th & 0xFFu))
-                            return E.fail("sparse item %zu: sketch %llu of the list block is outside its bound at v = %d", k, (unsigned long long)orig(sx), v);
+                        const uint32_t key = keys[L.perm[sx]], g = sc->gcnt[L.perm[sx]];
+                        const uint32_t own = v >= key_T(key) ? (g & 0xFFFFu) : v == key_T(key) - 1 ? g >> 16 : 65535u;
+                        if (own > tu.sparse_cap) return E.fail("sparse item %zu: sketch %llu may hold %u positions", k, (unsigned long long)L.perm[sx], own);
                     }
-                    continue;
-                }
-                if (I.y != Ipl || pp.slabs[I.z].y != Ipl || pp.slabs[I.w].y != Ipl) return E.fail("sparse item %zu carries flags without the sided route", k);
-                if (sparse_bound(L, T[t].x, v) > tu.sparse_cap || sparse_bound(L, T[t].y, v) > tu.sparse_cap) return E.fail("sparse item %zu: a set may exceed the cap", k);
-                // the bound holds for every sketch of the two blocks (what the lists and counters are sized by)
-                if (sc && sc->gcnt)
-                    for (int side = 0; side < 2; ++side)
-                        for (uint32_t a = 0; a < kTile; ++a) {
-                            const uint64_t sx = (uint64_t)(side ? T[t].y : T[t].x) * kTile + a;
-                            if (sx >= L.ncols) continue;
-                            const uint32_t key = keys[orig(sx)], g = sc->gcnt[orig(sx)];
-                            const uint32_t own = v >= key_T(key) ? (g & 0xFFFFu) : v == key_T(key) - 1 ? g >> 16 : 65535u;
-                            if (own > tu.sparse_cap) return E.fail("sparse item %zu: sketch %llu may hold %u positions", k, (unsigned long long)orig(sx), own);
-                        }
-            }
-            for (size_t t = bd.first; t < bd.second; ++t) {
-                const uint32_t sp = pp.sp[t], spb = pp.spb[t], np = T[t].w - T[t].z;
-                if ((!sided_chk && (sp > 2 || spb)) || sp + spb > np) return E.fail("tile %zu routes %u + %u planes of %u", t, spb, sp, np);
-                if (np > 64) return E.fail("tile %zu has %u planes: register values are below 64", t, np);
-                for (uint32_t x = 0; x < np; ++x)
-                    if ((seen_pl[(t - bd.first) * 64 + x] != 0) != (x < spb || x + sp >= np))
-                        return E.fail("plane %u of tile %zu: routed and sparse item disagree", T[t].z + x, t);
-                if (tu.W >= (uint32_t)tu.kc && (pp.chunks[t].x != (T[t].z + spb) * cpp_ || pp.chunks[t].y != (T[t].w - sp) * cpp_))
-                    return E.fail("tile %zu: the dense chunk range is not the planes left over", t);
-            }
         }
-        if (sat != pp.sp_items.size()) return E.fail("sparse items end at %zu of %zu", sat, pp.sp_items.size());
-        if (sc && sc->routes) {
-            if (T.size() > sc->routes_cap) return E.fail("%zu tiles, room for %llu routes", T.size(), (unsigned long long)sc->routes_cap);
-            for (size_t t = 0; t < T.size(); ++t) {
-                uint32_t *o = sc->routes + 5 * t;
-                o[0] = T[t].x, o[1] = T[t].y, o[2] = T[t].z, o[3] = T[t].w, o[4] = pp.sp[t];
-            }
-        }
-        if (sc && sc->routes6) {
-            if (T.size() > sc->routes_cap || pp.sp_items.size() > sc->items_cap || pp.slabs.size() > sc->slabs_cap)
-                return E.fail("%zu tiles, %zu items, %zu slabs: no room", T.size(), pp.sp_items.size(), pp.slabs.size());
-            for (size_t t = 0; t < T.size(); ++t) {
-                uint32_t *o = sc->routes6 + 6 * t;
-                o[0] = T[t].x, o[1] = T[t].y, o[2] = T[t].z, o[3] = T[t].w, o[4] = pp.spb[t], o[5] = pp.sp[t];
-            }
-            for (size_t bi = 0; bi < pp.bands.size(); ++bi)
-                for (size_t k = pp.band_sp_items[bi].first; k < pp.band_sp_items[bi].second; ++k) {
-                    const U4 &I = pp.sp_items[k];
-                    uint32_t *o = sc->items5 + 5 * k;
-                    o[0] = (uint32_t)(pp.bands[bi].first + I.x), o[1] = I.y & kSpPlaneMask, o[2] = I.y >> 8, o[3] = I.z, o[4] = I.w;
-                }
-            for (size_t k = 0; k < pp.slabs.size(); ++k) {
-                uint32_t *o = sc->slabs3 + 3 * k;
-                o[0] = pp.slabs[k].x, o[1] = pp.slabs[k].y & kSpPlaneMask, o[2] = pp.slabs[k].y >> 8;
-            }
+        for (size_t t = bd.first; t < bd.second; ++t) {
+            const uint32_t sp = pp.sp[t], spb = pp.spb[t], np = T[t].w - T[t].z;
+            if ((!sided_chk && (sp > 2 || spb)) || sp + spb > np) return E.fail("tile %zu routes %u + %u planes of %u", t, spb, sp, np);
+            if (np > 64) return E.fail("tile %zu has %u planes: register values are below 64", t, np);
+            for (uint32_t x = 0; x < np; ++x)
+                if ((seen_pl[(t - bd.first) * 64 + x] != 0) != (x < spb || x + sp >= np))
+                    return E.fail("plane %u of tile %zu: routed and sparse item disagree", T[t].z + x, t);
+            if (tu.W >= (uint32_t)tu.kc && (pp.chunks[t].x != (T[t].z + spb) * cpp_ || pp.chunks[t].y != (T[t].w - sp) * cpp_))
+                return E.fail("tile %zu: the dense chunk range is not the planes left over", t);
         }
     }
+    if (sat != pp.sp_items.size()) return E.fail("sparse items end at %zu of %zu", sat, pp.sp_items.size());
+    if (sc && sc->routes) {
+        if (T.size() > sc->routes_cap) return E.fail("%zu tiles, room for %llu routes", T.size(), (unsigned long long)sc->routes_cap);
+        for (size_t t = 0; t < T.size(); ++t) {
+            uint32_t *o = sc->routes + 5 * t;
+            o[0] = T[t].x, o[1] = T[t].y, o[2] = T[t].z, o[3] = T[t].w, o[4] = pp.sp[t];
+        }
+    }
+    if (sc && sc->routes6) {
+        if (T.size() > sc->routes_cap || pp.sp_items.size() > sc->items_cap || pp.slabs.size() > sc->slabs_cap)
+            return E.fail("%zu tiles, %zu items, %zu slabs: no room", T.size(), pp.sp_items.size(), pp.slabs.size());
+        for (size_t t = 0; t < T.size(); ++t) {
+            uint32_t *o = sc->routes6 + 6 * t;
+            o[0] = T[t].x, o[1] = T[t].y, o[2] = T[t].z, o[3] = T[t].w, o[4] = pp.spb[t], o[5] = pp.sp[t];
+        }
+        for (size_t bi = 0; bi < pp.bands.size(); ++bi)
+            for (size_t k = pp.band_sp_items[bi].first; k < pp.band_sp_items[bi].second; ++k) {
+                const U4 &I = pp.sp_items[k];
+                uint32_t *o = sc->items5 + 5 * k;
+                o[0] = (uint32_t)(pp.bands[bi].first + I.x), o[1] = I.y & kSpPlaneMask, o[2] = I.y >> 8, o[3] = I.z, o[4] = I.w;
+            }
+        for (size_t k = 0; k < pp.slabs.size(); ++k) {
+            uint32_t *o = sc->slabs3 + 3 * k;
+            o[0] = pp.slabs[k].x, o[1] = pp.slabs[k].y & kSpPlaneMask, o[2] = pp.slabs[k].y >> 8;
+        }
+    }
+    return 0;
+}
+
+// every part completes once, and the tile counts the signalling k_finalize waits for add up
+int check_parts(const CheckJob &job, const Layout &L, const PairPlan &pp, Err &E)
+{
+    std::vector<int> part_done(pp.nparts, 0);
+    for (const auto &sv : pp.segs)
+        for (const Seg &sg : sv)
+            if (sg.part >= 0) ++part_done[sg.part];  // (in range: check_bands_and_items)
     for (uint32_t qd = 0; qd < pp.nparts; ++qd)
         if (part_done[qd] != 1) return E.fail("part %u never completes", qd);
-    if (pp.nparts) {  // the tile counts the signalling k_finalize waits for
+    if (pp.nparts) {
         uint64_t tsum = 0;
         if (pp.part_tiles.size() != pp.nparts) return E.fail("part_tiles has %zu entries for %u parts", pp.part_tiles.size(), pp.nparts);
         for (uint32_t c : pp.part_tiles) tsum += c;
-        if (tsum != T.size()) return E.fail("the parts hold %llu tiles of %zu", (unsigned long long)tsum, T.size());
+        if (tsum != pp.T.size()) return E.fail("the parts hold %llu tiles of %zu", (unsigned long long)tsum, pp.T.size());
     }
-    if (q.want_parts && pp.nparts + 1 != L.part_w.size()) return E.fail("%u parts planned, layout has %zu", pp.nparts, L.part_w.size() - 1);
-    // ---- the two device lists describe the same tiles
+    if (job.plan_parts() && pp.nparts + 1 != L.part_w.size()) return E.fail("%u parts planned, layout has %zu", pp.nparts, L.part_w.size() - 1);
+    return 0;
+}
+
+// the two device lists describe the same tiles
+int check_device_lists(const Layout &L, const PairPlan &pp, Err &E)
+{
+    const std::vector<U4> &T = pp.T;
     std::vector<U4> dt(T.size()), df(T.size());
     emit_tile_lists(L, pp, dt.data(), df.data());
     for (size_t bi = 0; bi < pp.bands.size(); ++bi)
@@ -449,36 +516,90 @@ static int plan_check(uint64_t n, const uint32_t *keys, int mode, int want_sorte
                 const int lo = (int)((f.z >> 16) & 0xFFu), hi = (int)(f.z >> 24);
                 if (hi - lo + 1 > sg.hist_bins) return E.fail("segment hist_bins %d too small for tile %zu", sg.hist_bins, src);
             }
-            {  // tile row by tile row inside the segment, columns ascending (the tile rows come in the wanted order: the
-               // extra segments' first)
-                std::vector<uint32_t> rows_seen;
-                for (size_t t = sg.b + 1; t < sg.e; ++t) {
-                    if (df[t - 1].x == df[t].x) {
-                        if (df[t - 1].y >= df[t].y) return E.fail("finalize list of a segment is not row-major at %zu", t);
-                    } else {
-                        rows_seen.push_back(df[t - 1].x);
-                        if (std::find(rows_seen.begin(), rows_seen.end(), df[t].x) != rows_seen.end())
-                            return E.fail("finalize list of a segment returns to tile row %u at %zu", df[t].x, t);
-                    }
+            // tile row by tile row inside the segment, columns ascending (the tile rows come in the wanted order: the
+            // extra segments' first)
+            std::vector<uint32_t> rows_seen;
+            for (size_t t = sg.b + 1; t < sg.e; ++t) {
+                if (df[t - 1].x == df[t].x) {
+                    if (df[t - 1].y >= df[t].y) return E.fail("finalize list of a segment is not row-major at %zu", t);
+                } else {
+                    rows_seen.push_back(df[t - 1].x);
+                    if (std::find(rows_seen.begin(), rows_seen.end(), df[t].x) != rows_seen.end())
+                        return E.fail("finalize list of a segment returns to tile row %u at %zu", df[t].x, t);
                 }
             }
         }
-    stats[0] = T.size();
-    stats[1] = pp.bands.size();
-    stats[2] = pp.items.size();
-    stats[3] = pp.nparts;
-    stats[4] = T.empty() ? 0 : planes_sum * 100 / T.size();
-    // rounds of the lockstep tile kernel over all bands (a band of k items takes ceil(k / round_items) rounds)
-    if (sc) stats[10] = pp.sp_items.size(), stats[11] = pp.slabs.size();
-    if (sc && sc->routes6) stats[12] = pp.sided_items, stats[13] = pp.transposed_items, stats[14] = pp.table_slabs;
-    stats[7] = 0;
-    for (size_t b = 0; b < pp.band_items.size(); ++b) {
-        const uint32_t nfr = b < pp.band_frags.size() ? pp.band_frags[b] : 0u;
-        const uint32_t bri = pp.band_round[b];
-        stats[7] += (pp.band_items[b].second - pp.band_items[b].first - nfr + bri - 1) / bri + (nfr ? 1 : 0);
-    }
     return 0;
 }
+
+// the stats, as many as the caller has slots for (CheckJob); `any`: something was planned
+void fill_stats(const CheckJob &job, const Layout &L, const PairPlan &pp, bool any)
+{
+    uint64_t full[15] = {0};
+    full[5] = L.Npad;
+    full[6] = L.P;
+    if (any) {
+        uint64_t planes_sum = 0;
+        for (const U4 &t : pp.T) planes_sum += t.w - t.z;
+        full[0] = pp.T.size();
+        full[1] = pp.bands.size();
+        full[2] = pp.items.size();
+        full[3] = pp.nparts;
+        full[4] = planes_sum * 100 / pp.T.size();
+        // rounds of the lockstep tile kernel over all bands (a band of k items takes ceil(k / its round) rounds)
+        for (size_t b = 0; b < pp.band_items.size(); ++b) {
+            const uint32_t nfr = pp.band_frags[b], bri = pp.band_round[b];
+            full[7] += (pp.band_items[b].second - pp.band_items[b].first - nfr + bri - 1) / bri + (nfr ? 1 : 0);
+            full[8] += nfr;
+        }
+        full[9] = pp.band_round[0];
+        full[10] = pp.sp_items.size(), full[11] = pp.slabs.size();
+        full[12] = pp.sided_items, full[13] = pp.transposed_items, full[14] = pp.table_slabs;
+    }
+    // (nothing planned: the slots above the first nine keep what the entry point put there)
+    for (int i = 0; i < (any ? std::min(job.stats_slots, 15) : 9); ++i) job.stats[i] = full[i];
+}
+
+// the fields every entry point gives
+CheckJob base_job(uint64_t n, const uint32_t *keys, int mode, int want_sorted, uint64_t rb, uint64_t re, uint32_t nparts, int want_parts, int p,
+                  uint64_t cum_budget)
+{
+    CheckJob job;
+    job.n = n, job.keys = keys, job.mode = mode, job.want_sorted = want_sorted, job.rb = rb, job.re = re;
+    job.nparts = nparts, job.want_parts = want_parts, job.p = p, job.cum_budget = cum_budget;
+    return job;
+}
+
+int plan_check(CheckJob job, char *err, size_t cap)
+{
+    Err E{err, cap};
+    job.resolve();
+    if (!job.extra.empty() && !(job.want_sorted && job.mode == 0)) return E.fail("extra segments need a sorted triangle layout");
+    Layout L;
+    job_layout(job, L);
+    uint64_t nw = 0;
+    for (auto &w : job.wanted_segments()) nw += w.second - w.first;
+    if (job.want_sorted && job.mode == 0 && L.nwanted != nw) return E.fail("nwanted %llu != %llu", (unsigned long long)L.nwanted, (unsigned long long)nw);
+    if (job.rowsorted && check_rowsorted(job, L, E)) return -1;
+    if (check_layout(job, L, E)) return -1;
+    Tuning tu;
+    PairQuery q;
+    PairPlan pp;
+    const bool any = job_plan(job, L, tu, q, pp);
+    fill_stats(job, L, pp, false);
+    if (!any) {
+        const uint64_t wanted = wanted_pairs(job);
+        if (wanted) return E.fail("nothing planned although %llu pairs are wanted", (unsigned long long)wanted);
+        return 0;
+    }
+    if (check_coverage(job, L, pp, E) || check_bands_and_items(job, L, tu, pp, E) || check_sparse(job, L, tu, pp, E) || check_parts(job, L, pp, E) ||
+        check_device_lists(L, pp, E))
+        return -1;
+    fill_stats(job, L, pp, true);
+    return 0;
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -486,8 +607,11 @@ int dshh_plan_check(uint64_t n, const uint32_t *keys, int mode, int want_sorted,
                     uint64_t ce, uint32_t nparts, int want_parts, int p, uint64_t cum_budget, int lockstep, int nsplit,
                     int ls_item_chunks, uint64_t *stats, char *err, size_t cap)
 {
-    return plan_check(n, keys, mode, want_sorted, rb, re, cb, ce, nparts, want_parts, p, cum_budget, lockstep, nsplit, ls_item_chunks,
-                      std::vector<uint64_t>(), stats, err, cap);
+    CheckJob job = base_job(n, keys, mode, want_sorted, rb, re, nparts, want_parts, p, cum_budget);
+    job.cb = cb, job.ce = ce;
+    job.lockstep = lockstep, job.nsplit = nsplit, job.ls_item_chunks = ls_item_chunks;
+    job.stats = stats, job.stats_slots = 9;
+    return plan_check(job, err, cap);
 }
 
 // the same check with the tile kernel's round given (a multiple of 256: 256 x the items per workgroup)
@@ -497,8 +621,12 @@ int dshh_plan_check_ri(uint64_t n, const uint32_t *keys, int mode, int want_sort
 {
     Err E{err, cap};
     if (round_items == 0 || round_items % 256) return E.fail("round_items %u is not a positive multiple of 256", round_items);
-    return plan_check(n, keys, mode, want_sorted, rb, re, cb, ce, nparts, want_parts, p, cum_budget, lockstep, nsplit, ls_item_chunks,
-                      std::vector<uint64_t>(), stats, err, cap, round_items);
+    CheckJob job = base_job(n, keys, mode, want_sorted, rb, re, nparts, want_parts, p, cum_budget);
+    job.cb = cb, job.ce = ce;
+    job.lockstep = lockstep, job.nsplit = nsplit, job.ls_item_chunks = ls_item_chunks;
+    job.round_items = round_items;
+    job.stats = stats, job.stats_slots = 10;
+    return plan_check(job, err, cap);
 }
 
 // the same with the sparse outer planes planned (plan.h, Tuning::sparse_planes): gcnt = the per-sketch counts g0 | g1 << 16
@@ -517,8 +645,11 @@ int dshh_plan_check_sparse(uint64_t n, const uint32_t *keys, const uint32_t *gcn
     sc.routes = routes;
     sc.routes_cap = routes_cap;
     stats[10] = stats[11] = 0;
-    return plan_check(n, keys, mode, want_sorted, rb, re, 0, 0, nparts, want_parts, p, cum_budget, 1, 0, 64, std::vector<uint64_t>(), stats, err,
-                      cap, round_items, &sc);
+    CheckJob job = base_job(n, keys, mode, want_sorted, rb, re, nparts, want_parts, p, cum_budget);
+    job.round_items = round_items;
+    job.sc = &sc;
+    job.stats = stats, job.stats_slots = 12;
+    return plan_check(job, err, cap);
 }
 
 // the same with the sided route planned (plan.h, Tuning::sparse_sided): thr = the per-sketch thresholds vU | vA << 8 at the cap
@@ -545,8 +676,11 @@ int dshh_plan_check_sparse_sided(uint64_t n, const uint32_t *keys, const uint32_
     sc.items5 = items, sc.items_cap = items_cap;
     sc.slabs3 = slabs, sc.slabs_cap = slabs_cap;
     for (int i = 10; i < 15; ++i) stats[i] = 0;
-    return plan_check(n, keys, mode, want_sorted, rb, re, 0, 0, nparts, want_parts, p, cum_budget, 1, 0, 64, std::vector<uint64_t>(), stats, err,
-                      cap, round_items, &sc);
+    CheckJob job = base_job(n, keys, mode, want_sorted, rb, re, nparts, want_parts, p, cum_budget);
+    job.round_items = round_items;
+    job.sc = &sc;
+    job.stats = stats, job.stats_slots = 15;
+    return plan_check(job, err, cap);
 }
 
 // the rows of ONE rank of a row-set table (plan.h): main range + extra segments, row-sorted parts (rowsorted != 0: what a
@@ -563,7 +697,157 @@ int dshh_plan_check_rowset(uint64_t n, const uint32_t *keys, const uint64_t *tab
     rs.rank_rows(rank, rb, re, extra);
     for (int i = 0; i < 9; ++i) stats[i] = 0;
     if (rb >= re) return 0;
-    return plan_check(n, keys, rowsorted ? 3 : 0, 1, rb, re, 0, 0, rowsorted ? nparts : 1, 1, p, cum_budget, 1, 0, 64, extra, stats, err, cap);
+    CheckJob job = base_job(n, keys, rowsorted ? 3 : 0, 1, rb, re, rowsorted ? nparts : 1, 1, p, cum_budget);
+    job.extra = extra;
+    job.stats = stats, job.stats_slots = 9;
+    return plan_check(job, err, cap);
+}
+
+}  // extern "C"
+
+namespace {
+
+// ---- dshh_plan_digest: what a layout and a plan ARE, section by section (tests/test_plan_digest.py) ---------------------
+// the sections, in the order their digests are written
+const char *const kDigestNames =
+    "perm,parts,part_w,part_pos,rowoff,rowoff_w,wtr,wtr_w,blk_T,blk_lo,blk_L,blk_hi,blk_g0,blk_g1,blk_vU,blk_vA,"
+    "Npad,ncols,nwanted,pbase,P,vlo,vhi,whole,rowsorted,thr_cap,"
+    "T,bands,band_items,band_round,band_frags,segs,items,rank,chunks,part_tiles,part_first,sp,spb,sp_items,band_sp_items,slabs,"
+    "per_tile_bytes,max_band,nparts,sided_items,transposed_items,table_slabs,"
+    "dev_tiles,dev_ftiles,band_item_count";
+constexpr uint32_t kDigestSections = 51;
+
+// 64-bit FNV-1a over the values of a section, every value as eight little-endian bytes (so that no padding and no host
+// type width enters a digest)
+struct Fnv {
+    uint64_t h = 1469598103934665603ull;
+    void add(uint64_t v)
+    {
+        for (int i = 0; i < 8; ++i) h = (h ^ ((v >> (8 * i)) & 0xFFu)) * 1099511628211ull;
+    }
+    void add(const U4 &v) { add(v.x), add(v.y), add(v.z), add(v.w); }
+    void add(const U2 &v) { add(v.x), add(v.y); }
+    template <class A, class B>
+    void add(const std::pair<A, B> &v) { add((uint64_t)v.first), add((uint64_t)v.second); }
+    void add(const Seg &s) { add((uint64_t)s.b), add((uint64_t)s.e), add((uint64_t)(int64_t)s.part), add((uint64_t)(int64_t)s.hist_bins); }
+};
+
+struct DigestOut {
+    uint64_t *out;
+    uint32_t at = 0;
+    template <class T>
+    void vec(const std::vector<T> &v)
+    {
+        Fnv f;
+        for (const T &x : v) f.add(x);
+        out[at++] = f.h;
+    }
+    void scalar(uint64_t v)
+    {
+        Fnv f;
+        f.add(v);
+        out[at++] = f.h;
+    }
+};
+
+// the digests of a layout and its plan (`any`: build_pairs planned something), and which branches of the planner the case reached
+uint64_t digest_plan(const Layout &L, const Tuning &tu, const PairQuery &q, const PairPlan &pp, bool any, uint64_t *out)
+{
+    DigestOut D{out};
+    D.vec(L.perm), D.vec(L.parts), D.vec(L.part_w), D.vec(L.part_pos), D.vec(L.rowoff), D.vec(L.rowoff_w), D.vec(L.wtr), D.vec(L.wtr_w);
+    D.vec(L.blk_T), D.vec(L.blk_lo), D.vec(L.blk_L), D.vec(L.blk_hi), D.vec(L.blk_g0), D.vec(L.blk_g1), D.vec(L.blk_vU), D.vec(L.blk_vA);
+    D.scalar(L.Npad), D.scalar(L.ncols), D.scalar(L.nwanted), D.scalar((uint64_t)(int64_t)L.pbase), D.scalar(L.P);
+    D.scalar((uint64_t)(int64_t)L.vlo), D.scalar((uint64_t)(int64_t)L.vhi), D.scalar(L.whole), D.scalar((uint64_t)L.rowsorted), D.scalar(L.thr_cap);
+    D.vec(pp.T), D.vec(pp.bands), D.vec(pp.band_items), D.vec(pp.band_round), D.vec(pp.band_frags);
+    {
+        Fnv f;
+        for (const auto &sv : pp.segs) {
+            f.add((uint64_t)sv.size());
+            for (const Seg &s : sv) f.add(s);
+        }
+        D.out[D.at++] = f.h;
+    }
+    D.vec(pp.items), D.vec(pp.rank), D.vec(pp.chunks), D.vec(pp.part_tiles), D.vec(pp.part_first), D.vec(pp.sp), D.vec(pp.spb);
+    D.vec(pp.sp_items), D.vec(pp.band_sp_items), D.vec(pp.slabs);
+    D.scalar(pp.per_tile_bytes), D.scalar(pp.max_band), D.scalar(pp.nparts), D.scalar(pp.sided_items), D.scalar(pp.transposed_items);
+    D.scalar(pp.table_slabs);
+    std::vector<U4> dt(any ? pp.T.size() : 0), df(dt.size());
+    std::vector<uint64_t> counts;
+    if (any) {
+        emit_tile_lists(L, pp, dt.data(), df.data());
+        for (size_t bi = 0; bi < pp.bands.size(); ++bi) counts.push_back(band_item_count(tu, pp, bi));
+    }
+    D.vec(dt), D.vec(df), D.vec(counts);
+    // ---- the feature word
+    uint64_t F = 0;
+    auto bit = [&](int b, bool on) { F |= on ? 1ull << b : 0; };
+    bit(5, pp.nparts > 1), bit(6, L.rowsorted != 0), bit(7, L.rowsorted && L.parts.size() == 3), bit(8, !L.extra.empty());
+    bit(9, q.rect != 0), bit(10, q.sorted_rows != 0), bit(11, !L.sorted), bit(12, tu.W < (uint32_t)tu.kc), bit(13, tu.nsplit > 0);
+    bit(14, !tu.lockstep), bit(20, tu.cum_bytes == 4);
+    if (!any) return F;
+    bit(0, pp.bands.size() > 1);
+    const uint64_t max_tiles = std::min<uint64_t>(65536, std::max<uint64_t>(1, tu.cum_budget / std::max<uint64_t>(pp.per_tile_bytes, 1)));
+    for (size_t bi = 0; bi + 1 < pp.bands.size(); ++bi) {  // why a band ends before the tiles do
+        const size_t e = pp.bands[bi].second;
+        bool by_part = false;
+        for (uint32_t qd = 0; qd < pp.nparts; ++qd) by_part |= pp.part_first[qd + 1] == e && pp.part_tiles[qd] >= tu.part_band_tiles;
+        bit(1, by_part);
+        bit(2, !by_part && e - pp.bands[bi].first < max_tiles);
+    }
+    for (size_t bi = 0; bi < pp.bands.size(); ++bi) {
+        bit(3, pp.band_frags[bi] > 0);
+        bit(4, tu.small_round_items && tu.small_round_items < tu.round_items && pp.band_round[bi] == tu.small_round_items);
+    }
+    bit(15, pp.sp_items.size() > pp.sided_items), bit(16, pp.sided_items > 0), bit(17, pp.transposed_items > 0), bit(18, pp.table_slabs > 0);
+    for (uint8_t b : pp.spb) bit(19, b > 0);
+    return F;
+}
+
+}  // namespace
+
+extern "C" {
+
+// The characterization hook: layout and plan built exactly as the checks above build them (the inputs of
+// dshh_plan_check_sparse_sided and, as dshh_plan_check has them, cb, ce, lockstep, nsplit, ls_item_chunks; round_items 0 =
+// the planner's default; extra = n_extra words {b0, e0, ...}), nothing checked.  digests gets one 64-bit FNV-1a value per
+// section of dshh_plan_digest_names() (comma-separated, in order), *features which branches the case reached: bit 0 more
+// than one band, 1 a band cut by a large part, 2 a tail cut, 3 overflow fragments, 4 a band at small_round_items, 5 parts
+// > 1, 6 row-sorted, 7 a two-run row-sorted range, 8 extra segments, 9 rectangle, 10 sorted_rows, 11 identity layout,
+// 12 W < kc, 13 nsplit > 0, 14 not lockstep, 15 two-plane items, 16 sided items, 17 transposed items, 18 table-only slabs,
+// 19 planes routed from the bottom of a range, 20 cum_bytes = 4.  Returns the number of sections, -1 on a bad argument.
+const char *dshh_plan_digest_names(void) { return kDigestNames; }
+
+int dshh_plan_digest(uint64_t n, const uint32_t *keys, const uint32_t *gcnt, const uint32_t *thr, uint32_t thr_cap, int mode, int want_sorted,
+                     uint64_t rb, uint64_t re, uint64_t cb, uint64_t ce, uint32_t nparts, int want_parts, int p, uint64_t cum_budget, int lockstep,
+                     int nsplit, int ls_item_chunks, uint32_t round_items, int sparse_planes, int sparse_sided, uint32_t sparse_cap,
+                     const uint64_t *extra, uint32_t n_extra, uint64_t *digests, uint32_t digests_cap, uint64_t *features, char *err, size_t cap)
+{
+    Err E{err, cap};
+    if (round_items % 256) return E.fail("round_items %u is not a multiple of 256", round_items);
+    if (!digests || !features || digests_cap < kDigestSections || n_extra % 2) return E.fail("digests, features and whole extra segments are wanted");
+    SparseCheck sc;
+    sc.gcnt = gcnt;
+    sc.planes = sparse_planes;
+    sc.cap = sparse_cap;
+    sc.thr = thr;
+    sc.thr_cap = thr_cap;
+    sc.sided = sparse_sided;
+    CheckJob job = base_job(n, keys, mode, want_sorted, rb, re, nparts, want_parts, p, cum_budget);
+    job.cb = cb, job.ce = ce;
+    job.lockstep = lockstep, job.nsplit = nsplit, job.ls_item_chunks = ls_item_chunks;
+    job.extra.assign(extra, extra + (extra ? n_extra : 0));
+    job.round_items = round_items;
+    job.sc = &sc;
+    job.resolve();
+    if (!job.extra.empty() && !(job.want_sorted && job.mode == 0)) return E.fail("extra segments need a sorted triangle layout");
+    Layout L;
+    job_layout(job, L);
+    Tuning tu;
+    PairQuery q;
+    PairPlan pp;
+    const bool any = job_plan(job, L, tu, q, pp);
+    *features = digest_plan(L, tu, q, pp, any, digests);
+    return (int)kDigestSections;
 }
 
 // first row of the second run of a row-sorted range (plan::rowsorted_split), re when the range stays one run

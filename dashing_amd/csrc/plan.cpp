@@ -481,119 +481,88 @@ void rowsorted_offsets(uint64_t n, const uint32_t *order, uint64_t cnt, std::vec
     rowoff[cnt] = acc;
 }
 
-void tile_planes(const Layout &L, uint32_t ti, uint32_t tj, int &pb, int &pe)
+// column order: identity, or a counting sort by (threshold, min value, max value): the first
+// two make the 128-column blocks need few planes, the third keeps the 64 pairs of a finalize
+// wave alike in their largest register, i.e. in the trip count of the estimator's loops.
+// With a row range the wanted rows [rb,re) come first (their tile rows are the only ones computed),
+// then the later rows; each part is key-ordered on its own.
+static void order_columns(const uint32_t *k32, Layout &L)
 {
-    const int lo_t = std::max<int>(std::max<int>(L.blk_lo[ti], L.blk_lo[tj]), std::min<int>(L.blk_L[ti], L.blk_L[tj]));
-    const int T_t = std::max<int>(L.blk_T[ti], L.blk_T[tj]);
-    pb = std::max(0, lo_t - L.pbase);
-    pe = std::max(pb, T_t - L.pbase);
+    const uint64_t n = L.n, rb = L.rb, re = L.re;
+    const std::vector<uint64_t> &extra = L.extra;
+    L.perm.resize(L.ncols);
+    if (!L.sorted) {
+        for (uint64_t i = 0; i < n; ++i) L.perm[i] = (uint32_t)i;
+        return;
+    }
+    // the runs, in row order (a run of rows [lo, hi) lies at the positions [lo - rb, hi - rb)): the parts of the
+    // wanted range, then the later rows -- cut into [gap | extra segment | gap ...] where extra segments lie
+    for (size_t q = 0; q + 1 < L.parts.size(); ++q)
+        sort_rows_by_key(k32, L.parts[q], L.parts[q + 1], L.perm.data() + (L.parts[q] - rb), L.sort_a);
+    uint64_t at = re;
+    for (size_t x = 0; x + 1 < extra.size(); x += 2) {
+        if (extra[x] > at) sort_rows_by_key(k32, at, extra[x], L.perm.data() + (at - rb), L.sort_a);
+        sort_rows_by_key(k32, extra[x], extra[x + 1], L.perm.data() + (extra[x] - rb), L.sort_a);
+        at = extra[x + 1];
+    }
+    if (at < n) sort_rows_by_key(k32, at, n, L.perm.data() + (at - rb), L.sort_a);
+    // (whole collection only) the inverse for the un-permute of the shard path
+    if (L.whole) {
+        L.perm.resize(2 * n);
+        for (uint64_t s = 0; s < n; ++s) L.perm[n + L.perm[s]] = (uint32_t)s;
+    }
 }
 
-void build_layout(const uint32_t *k32, uint64_t n, int want_sorted, uint64_t rb, uint64_t re,
-                  const std::vector<uint64_t> &parts, Layout &L, uint32_t rowsorted_nparts, const std::vector<uint64_t> *extra_in,
-                  const uint32_t *gcnt, const uint32_t *thr, uint32_t thr_cap)
+// the tables of the WANTED ORDER (extra segments first, then the main range: the order of the tile list, of the parts and
+// of a row-sorted buffer): wtr, wtr_w, part_w, part_pos, rowoff, rowoff_w
+static void wanted_tables(uint32_t rowsorted_nparts, Layout &L)
 {
-    if (re > n) re = n;
-    if (!want_sorted) rb = 0, re = n;
-    if (rb > re) rb = re;
-    static const std::vector<uint64_t> kNoExtra;
-    const std::vector<uint64_t> &extra = (want_sorted && extra_in && rb < re) ? *extra_in : kNoExtra;
-    // the plane matrix holds the sketches col0 .. n-1 (a row range [rb,re) of the triangle never looks at
-    // sketches before rb); value range and thresholds are taken over those only
-    const uint64_t col0 = want_sorted ? rb : 0;
-    const uint64_t ncols = n - col0;
-    int vr[3] = {63, 0, 0};  // min register value anywhere, max value, max threshold
-    for (uint64_t i = col0; i < n; ++i) {
-        const uint32_t key = k32[i];
-        vr[0] = std::min<int>(vr[0], key_lo(key));
-        vr[1] = std::max<int>(vr[1], key_hi(key));
-        vr[2] = std::max<int>(vr[2], key_T(key));
-    }
-    if (ncols == 0) vr[0] = vr[1] = vr[2] = 0;
-    L.sorted = want_sorted;
-    L.rb = rb;
-    L.re = re;
-    L.rowsorted = want_sorted && rowsorted_nparts > 0;
-    L.extra = extra;
-    if (L.rowsorted) {  // ONE key-ordered run, or two (rowsorted_split)
-        const uint64_t x = rowsorted_split(n, rb, re);
-        if (x > rb && x < re) L.parts = {rb, x, re};
-        else L.parts = {rb, re};
-    } else if (!extra.empty()) {
-        L.parts = {rb, re};
-    } else {
-        L.parts = want_sorted ? parts : std::vector<uint64_t>();
-    }
-    L.n = n;
-    L.vlo = vr[0];
-    L.vhi = vr[1];
-    L.ncols = ncols;
-    L.Npad = (uint32_t)((ncols + kTile - 1) / kTile * kTile);
-    L.whole = want_sorted && rb == 0 && re == n;
-    // column order: identity, or a counting sort by (threshold, min value, max value): the first
-    // two make the 128-column blocks need few planes, the third keeps the 64 pairs of a finalize
-    // wave alike in their largest register, i.e. in the trip count of the estimator's loops.
-    // With a row range the wanted rows [rb,re) come first (their tile rows are the only ones computed),
-    // then the later rows; each part is key-ordered on its own.
-    L.perm.resize(ncols);
+    const uint64_t n = L.n, rb = L.rb, re = L.re;
+    const std::vector<uint64_t> &extra = L.extra;
     L.part_pos.clear();
     L.part_w.clear();
     L.rowoff.clear();
     L.rowoff_w.clear();
     L.wtr.clear();
     L.wtr_w.clear();
-    L.nwanted = want_sorted ? rowset_rows(rb, re, extra) : n;
-    if (want_sorted) {
-        // the runs, in row order (a run of rows [lo, hi) lies at the positions [lo - rb, hi - rb)): the parts of the
-        // wanted range, then the later rows -- cut into [gap | extra segment | gap ...] where extra segments lie
-        for (size_t q = 0; q + 1 < L.parts.size(); ++q)
-            sort_rows_by_key(k32, L.parts[q], L.parts[q + 1], L.perm.data() + (L.parts[q] - rb), L.sort_a);
-        uint64_t at = re;
-        for (size_t x = 0; x + 1 < extra.size(); x += 2) {
-            if (extra[x] > at) sort_rows_by_key(k32, at, extra[x], L.perm.data() + (at - rb), L.sort_a);
-            sort_rows_by_key(k32, extra[x], extra[x + 1], L.perm.data() + (extra[x] - rb), L.sort_a);
-            at = extra[x + 1];
-        }
-        if (at < n) sort_rows_by_key(k32, at, n, L.perm.data() + (at - rb), L.sort_a);
-        // tile rows that hold wanted rows, in the WANTED ORDER (extra segments first, then the main range: the order of the
-        // tile list, of the parts and of a row-sorted buffer), and the wanted rows in front of each of these ranges
-        std::vector<std::pair<uint64_t, uint64_t>> wsegs;
-        wanted_order(n, rb, re, &extra, wsegs, L.rowsorted);
-        uint64_t wrows = 0;
-        for (auto &sg : wsegs) {
-            L.wtr.emplace_back((uint32_t)((sg.first - rb) / kTile), (uint32_t)((sg.second - rb + kTile - 1) / kTile));
-            L.wtr_w.push_back(wrows);
-            wrows += sg.second - sg.first;
-        }
-        const uint64_t wend = extra.empty() ? re - rb : extra.back() - rb;  // position behind the last wanted row
-        if (L.rowsorted) {
-            rowsorted_part_positions(n, rb, re, rowsorted_nparts, L.part_w, &extra);
-            // wanted order -> the rows' offsets in the rank's buffer, and the same by layout position
-            L.rowoff_w.resize(L.nwanted + 1);
-            L.rowoff.assign(wend + 1, 0);
-            uint64_t acc = 0, w = 0;
-            for (auto &sg : wsegs)
-                for (uint64_t s = sg.first - rb; s < sg.second - rb; ++s, ++w) {
-                    L.rowoff_w[w] = L.rowoff[s] = acc;
-                    acc += n - 1 - L.perm[s];
-                }
-            L.rowoff_w[L.nwanted] = acc;
-        } else if (!extra.empty()) {
-            L.part_w = {0, L.nwanted};
-        } else {
-            for (uint64_t r : L.parts) L.part_w.push_back(r - rb);
-        }
-        // (layout positions of the cuts: only meaningful where the wanted order is the layout order -- no extra segments)
-        if (extra.empty()) L.part_pos = L.part_w;
-        else L.part_pos = {0, wend};
-        // (whole collection only) the inverse for the un-permute of the shard path
-        if (L.whole) {
-            L.perm.resize(2 * n);
-            for (uint64_t s = 0; s < n; ++s) L.perm[n + L.perm[s]] = (uint32_t)s;
-        }
-    } else {
-        for (uint64_t i = 0; i < n; ++i) L.perm[i] = (uint32_t)i;
+    L.nwanted = L.sorted ? rowset_rows(rb, re, extra) : n;
+    if (!L.sorted) return;
+    // tile rows that hold wanted rows, in the wanted order, and the wanted rows in front of each of these ranges
+    std::vector<std::pair<uint64_t, uint64_t>> wsegs;
+    wanted_order(n, rb, re, &extra, wsegs, L.rowsorted);
+    uint64_t wrows = 0;
+    for (auto &sg : wsegs) {
+        L.wtr.emplace_back((uint32_t)((sg.first - rb) / kTile), (uint32_t)((sg.second - rb + kTile - 1) / kTile));
+        L.wtr_w.push_back(wrows);
+        wrows += sg.second - sg.first;
     }
+    const uint64_t wend = extra.empty() ? re - rb : extra.back() - rb;  // position behind the last wanted row
+    if (L.rowsorted) {
+        rowsorted_part_positions(n, rb, re, rowsorted_nparts, L.part_w, &extra);
+        // wanted order -> the rows' offsets in the rank's buffer, and the same by layout position
+        L.rowoff_w.resize(L.nwanted + 1);
+        L.rowoff.assign(wend + 1, 0);
+        uint64_t acc = 0, w = 0;
+        for (auto &sg : wsegs)
+            for (uint64_t s = sg.first - rb; s < sg.second - rb; ++s, ++w) {
+                L.rowoff_w[w] = L.rowoff[s] = acc;
+                acc += n - 1 - L.perm[s];
+            }
+        L.rowoff_w[L.nwanted] = acc;
+    } else if (!extra.empty()) {
+        L.part_w = {0, L.nwanted};
+    } else {
+        for (uint64_t r : L.parts) L.part_w.push_back(r - rb);
+    }
+    // (layout positions of the cuts: only meaningful where the wanted order is the layout order -- no extra segments)
+    if (extra.empty()) L.part_pos = L.part_w;
+    else L.part_pos = {0, wend};
+}
+
+// the per-block statistics of the column order, and from them pbase and P (Tmax: the largest threshold of any column)
+static void block_stats(const SketchWords &w, int Tmax, Layout &L)
+{
+    const uint32_t *k32 = w.keys, *gcnt = w.gcnt, *thr = w.thr;
     const uint32_t NT = L.Npad / kTile;
     L.blk_T.assign(NT, 0);
     L.blk_lo.assign(NT, 255);
@@ -603,11 +572,11 @@ void build_layout(const uint32_t *k32, uint64_t n, int want_sorted, uint64_t rb,
     L.blk_g1.assign(gcnt ? NT : 0, 0);
     L.blk_vU.assign(thr ? NT : 0, 0);
     L.blk_vA.assign(thr ? NT : 0, 64);
-    L.thr_cap = thr ? thr_cap : 0;
-    int pbase = vr[2];
+    L.thr_cap = thr ? w.thr_cap : 0;
+    int pbase = Tmax;
     const uint32_t *perm = L.perm.data();
     for (uint32_t b = 0; b < NT; ++b) {  // (a block at a time, its four statistics in registers)
-        const uint64_t s0 = (uint64_t)b * kTile, s1 = std::min<uint64_t>(ncols, s0 + kTile);
+        const uint64_t s0 = (uint64_t)b * kTile, s1 = std::min<uint64_t>(L.ncols, s0 + kTile);
         int bt = 0, blo = 255, bl = 255, bhi = 0;
         for (uint64_t s = s0; s < s1; ++s) {
             const uint32_t key = k32[perm[s]];
@@ -646,7 +615,54 @@ void build_layout(const uint32_t *k32, uint64_t n, int want_sorted, uint64_t rb,
     }
     // dense planes cover v in (pbase, Tmax]: below the smallest low threshold every C(v) comes from the list join
     L.pbase = pbase;
-    L.P = (uint32_t)(vr[2] - pbase);
+    L.P = (uint32_t)(Tmax - pbase);
+}
+
+void build_layout(uint64_t n, const SketchWords &words, const LayoutQuery &query, Layout &L)
+{
+    const uint32_t *k32 = words.keys;
+    const int want_sorted = query.want_sorted;
+    uint64_t rb = query.rb, re = query.re;
+    if (re > n) re = n;
+    if (!want_sorted) rb = 0, re = n;
+    if (rb > re) rb = re;
+    static const std::vector<uint64_t> kNoExtra;
+    const std::vector<uint64_t> &extra = (want_sorted && query.extra && rb < re) ? *query.extra : kNoExtra;
+    // the plane matrix holds the sketches col0 .. n-1 (a row range [rb,re) of the triangle never looks at
+    // sketches before rb); value range and thresholds are taken over those only
+    const uint64_t col0 = want_sorted ? rb : 0;
+    const uint64_t ncols = n - col0;
+    int vr[3] = {63, 0, 0};  // min register value anywhere, max value, max threshold
+    for (uint64_t i = col0; i < n; ++i) {
+        const uint32_t key = k32[i];
+        vr[0] = std::min<int>(vr[0], key_lo(key));
+        vr[1] = std::max<int>(vr[1], key_hi(key));
+        vr[2] = std::max<int>(vr[2], key_T(key));
+    }
+    if (ncols == 0) vr[0] = vr[1] = vr[2] = 0;
+    L.sorted = want_sorted;
+    L.rb = rb;
+    L.re = re;
+    L.rowsorted = want_sorted && query.rowsorted_nparts > 0;
+    L.extra = extra;
+    if (L.rowsorted) {  // ONE key-ordered run, or two (rowsorted_split)
+        const uint64_t x = rowsorted_split(n, rb, re);
+        if (x > rb && x < re) L.parts = {rb, x, re};
+        else L.parts = {rb, re};
+    } else if (!extra.empty()) {
+        L.parts = {rb, re};
+    } else {
+        L.parts = want_sorted && query.parts ? *query.parts : std::vector<uint64_t>();
+    }
+    L.n = n;
+    L.vlo = vr[0];
+    L.vhi = vr[1];
+    L.ncols = ncols;
+    L.Npad = (uint32_t)((ncols + kTile - 1) / kTile * kTile);
+    L.whole = want_sorted && rb == 0 && re == n;
+    order_columns(k32, L);
+    wanted_tables(query.rowsorted_nparts, L);
+    block_stats(words, vr[2], L);
 }
 
 // Order the tiles of a segment so that workgroups that run on the same XCD (block b -> XCD b % 8,
@@ -682,17 +698,6 @@ uint32_t sparse_bound(const Layout &L, uint32_t b, int v)
     return v >= Tb ? L.blk_g0[b] : v == Tb - 1 ? L.blk_g1[b] : 65535u;
 }
 
-// how many planes of the tile {ti, tj, pb, pe} leave the tile kernel, from the top of its range (plan.h, Tuning)
-static uint32_t sparse_route(const Layout &L, uint32_t cap, int nplanes, const U4 &t)
-{
-    uint32_t k = 0;
-    for (; (int)k < nplanes && t.w - k > t.z; ++k) {
-        const int v = L.pbase + (int)(t.w - k);  // plane pl is the threshold pbase + 1 + pl; pl = t.w - 1 - k
-        if (std::max(sparse_bound(L, t.x, v), sparse_bound(L, t.y, v)) > cap) break;
-    }
-    return k;
-}
-
 int sided_depth(const Layout &L, uint32_t b, int v)
 {
     if (b >= L.blk_vU.size()) return -1;
@@ -705,17 +710,63 @@ int sided_polarity(const Layout &L, uint32_t b, int v)
     return v <= (int)L.blk_vA[b] ? 1 : 0;
 }
 
-// the sided route of the tile {ti, tj, pb, pe}: `above` planes leave from the top of its range and `below` from its bottom
-static void sided_route(const Layout &L, const U4 &t, uint32_t &below, uint32_t &above)
+// The two sparse routes (plan.h, Tuning::sparse_planes and ::sparse_sided): which calls may route at all, decided once
+// per job.  Both want a triangle call on a key-ordered layout and whole-plane items (lockstep, nsplit = 0) at p <= 16
+// (positions are 16-bit); the two-plane route also the per-sketch counts and p >= 9, automatic only from p = 13; the sided
+// route the thresholds of THIS plan's cap and p >= 13 (below that a set and its complement can both fit the cap) -- automatic
+// where the two-plane route is automatic, behind the same gate.
+enum class Route { None, TwoPlane, Sided };
+struct SparseGate {
+    uint32_t cap = 0;         // min(sparse_cap, kSparseCapMax)
+    int planes = 0;           // the two-plane route: planes of a tile at most, 0 = off
+    uint64_t min_planes = 0;  // automatic: only a scope (a job, a band) with more planes than this routes -- a second launch does not pay on a small one
+    uint64_t job_planes = 0;  // planes of all the job's tiles
+    bool sided_can = false, sided_forced = false, sided_auto = false;
+    bool any() const { return planes || sided_forced || sided_auto; }
+    // the route of the tiles of a scope with this many planes.  build_tiles asks twice on purpose: tail_cuts with the job's
+    // planes (an estimate of the dense items, before there are bands), route_sparse with every band's own
+    Route route_for(uint64_t planes_in_scope) const
+    {
+        if (sided_forced || (sided_auto && planes_in_scope > min_planes)) return Route::Sided;
+        return planes && planes_in_scope > min_planes ? Route::TwoPlane : Route::None;
+    }
+};
+
+static SparseGate sparse_gate(const Layout &L, const PairQuery &job, const Tuning &tu, uint64_t job_planes)
+{
+    SparseGate g;
+    g.cap = std::min(tu.sparse_cap, kSparseCapMax);
+    g.job_planes = job_planes;
+    const bool shared = !job.rect && !job.sorted_rows && L.sorted && tu.lockstep && tu.nsplit == 0 && tu.W >= (uint32_t)tu.kc && tu.p <= 16;
+    const bool two_can = shared && tu.sparse_planes != 0 && !L.blk_g0.empty() && tu.p >= 9 && (tu.sparse_planes > 0 || tu.p >= 13);
+    g.planes = !two_can ? 0 : tu.sparse_planes < 0 ? kSparseAutoPlanes : std::min(tu.sparse_planes, 2);
+    g.min_planes = tu.sparse_planes < 0 ? std::max<uint64_t>(tu.small_round_items, 512) : 0;
+    g.sided_can = shared && !L.blk_vU.empty() && L.thr_cap == g.cap && tu.p >= 13;
+    g.sided_forced = g.sided_can && tu.sparse_sided > 0;
+    g.sided_auto = g.sided_can && tu.sparse_sided < 0 && tu.sparse_planes < 0 && kSparseSidedAuto;
+    return g;
+}
+
+// how many planes of the tile {ti, tj, pb, pe} leave the tile kernel: `above` from the top of its range and `below` from
+// its bottom.  Two-plane route: from the top only, at most gate.planes, while the sets of both blocks are within the cap.
+// Sided route: every plane one of the two blocks can carry lists at, a suffix and a prefix of the range.
+static void tile_route(const Layout &L, const SparseGate &gate, Route route, const U4 &t, uint32_t &below, uint32_t &above)
 {
     const uint32_t np = t.w - t.z;
-    auto routed = [&](uint32_t pl) {
-        const int v = L.pbase + 1 + (int)pl;
-        return sided_depth(L, t.x, v) >= 0 || sided_depth(L, t.y, v) >= 0;
-    };
     above = below = 0;
-    while (above < np && routed(t.w - 1 - above)) ++above;
-    while (below + above < np && routed(t.z + below)) ++below;
+    if (route == Route::TwoPlane) {
+        for (; (int)above < gate.planes && above < np; ++above) {
+            const int v = L.pbase + (int)(t.w - above);  // plane pl is the threshold pbase + 1 + pl; pl = t.w - 1 - above
+            if (std::max(sparse_bound(L, t.x, v), sparse_bound(L, t.y, v)) > gate.cap) break;
+        }
+    } else if (route == Route::Sided) {
+        auto routed = [&](uint32_t pl) {
+            const int v = L.pbase + 1 + (int)pl;
+            return sided_depth(L, t.x, v) >= 0 || sided_depth(L, t.y, v) >= 0;
+        };
+        while (above < np && routed(t.w - 1 - above)) ++above;
+        while (below + above < np && routed(t.z + below)) ++below;
+    }
 }
 
 static void tile_vrange(const Layout &L, const U4 &t, int &lo, int &hi)
@@ -725,28 +776,16 @@ static void tile_vrange(const Layout &L, const U4 &t, int &lo, int &hi)
     if (hi < lo) hi = lo;  // (blocks of padding only)
 }
 
-bool build_tiles(const Layout &L, const PairQuery &job, const Tuning &tu, PairPlan &pp)
+// ---- build_tiles, step by step (each step fills what it owns; build_tiles below calls them in this order) -----------------
+
+// tile list: {row block, col block, plane begin, plane end} (tile_planes) in one of three shapes: a rectangle, the tile
+// rows of a row range of plane columns, the wanted tile rows of a sorted layout in the wanted order -- for the last also
+// the first tile of every tile row and the wanted rows in front of it.  false: nothing to compute.
+// (a row of tiles at a time, the row block's statistics in registers: at 100 000 sketches this loop writes 306 000
+// tiles and the host's planning is not hidden behind anything the GPU does -- profiles/r4y)
+static bool list_tiles(const Layout &L, const PairQuery &job, std::vector<U4> &T, std::vector<size_t> &trow_first, std::vector<uint64_t> &trow_w)
 {
-    std::vector<U4> &T = pp.T;
-    T.clear();
-    pp.bands.clear();
-    pp.band_items.clear();
-    pp.segs.clear();
-    pp.items.clear();
-    pp.band_frags.clear();
-    pp.band_round.clear();
-    pp.sp.clear();
-    pp.spb.clear();
-    pp.sp_items.clear();
-    pp.band_sp_items.clear();
-    pp.slabs.clear();
-    pp.nparts = 0;
-    pp.max_band = 0;
     const uint32_t NT = L.Npad / kTile;
-    // tile list: {row block, col block, plane begin, plane end}; a tile only needs the planes
-    // v in (max(min lo of its two blocks), max threshold of its two blocks]
-    // (a row of tiles at a time, the row block's statistics in registers: at 100 000 sketches this loop writes 306 000
-    // tiles and the host's planning is not hidden behind anything the GPU does -- profiles/r4y)
     const uint8_t *bLo = L.blk_lo.data(), *bL = L.blk_L.data(), *bT = L.blk_T.data();
     const int pbase = L.pbase;
     auto tile_row = [&](uint32_t ti, uint32_t c0, uint32_t c1) {
@@ -754,14 +793,12 @@ bool build_tiles(const Layout &L, const PairQuery &job, const Tuning &tu, PairPl
         T.resize(at + (c1 - c0));
         U4 *out = T.data() + at;
         const int lo_i = bLo[ti], L_i = bL[ti], T_i = bT[ti];
-        for (uint32_t tj = c0; tj < c1; ++tj) {  // tile_planes(), inlined
-            const int lo_t = std::max(std::max<int>(lo_i, bLo[tj]), std::min<int>(L_i, bL[tj]));
-            const int pb = std::max(0, lo_t - pbase), pe = std::max(pb, std::max<int>(T_i, bT[tj]) - pbase);
+        for (uint32_t tj = c0; tj < c1; ++tj) {
+            int pb, pe;
+            tile_planes(lo_i, L_i, T_i, bLo[tj], bL[tj], bT[tj], pbase, pb, pe);
             *out++ = U4{ti, tj, (uint32_t)pb, (uint32_t)pe};
         }
     };
-    std::vector<size_t> trow_first;   // (wanted tile rows of a sorted layout) first tile of the tile row ...
-    std::vector<uint64_t> trow_w;     // ... and the wanted rows in front of it (wanted order)
     if (job.rect) {
         if (job.row_begin >= job.row_end || job.col_begin >= job.col_end) return false;
         const uint32_t r0 = (uint32_t)(job.row_begin / kTile), r1 = (uint32_t)((job.row_end + kTile - 1) / kTile);
@@ -788,39 +825,27 @@ bool build_tiles(const Layout &L, const PairQuery &job, const Tuning &tu, PairPl
                 }
         }
     }
-    if (T.empty()) return false;
-    // sparse outer planes (plan.h, Tuning): which calls may route at all, and how many planes of a tile at most
-    const uint32_t sp_cap = std::min(tu.sparse_cap, kSparseCapMax);
-    const bool sp_can = tu.sparse_planes != 0 && !job.rect && !job.sorted_rows && L.sorted && !L.blk_g0.empty() && tu.lockstep &&
-                        tu.nsplit == 0 && tu.W >= (uint32_t)tu.kc && tu.p >= 9 && tu.p <= 16 && (tu.sparse_planes > 0 || tu.p >= 13);
-    const int sp_planes = !sp_can ? 0 : tu.sparse_planes < 0 ? kSparseAutoPlanes : std::min(tu.sparse_planes, 2);
-    const uint64_t sp_min_planes = tu.sparse_planes < 0 ? std::max<uint64_t>(tu.small_round_items, 512) : 0;  // a band with more than this
-    uint64_t job_planes = 0;
-    for (const U4 &t : T) job_planes += t.w - t.z;
-    const int sp_planes_job = job_planes > sp_min_planes ? sp_planes : 0;  // (what the cuts below are estimated with)
-    // the sided route (plan.h, Tuning::sparse_sided): the same calls, p >= 13, thresholds of this plan's cap; automatic
-    // where the two-plane route is automatic, behind the same gate
-    const bool sd_can = !job.rect && !job.sorted_rows && L.sorted && !L.blk_vU.empty() && L.thr_cap == sp_cap && tu.lockstep && tu.nsplit == 0 &&
-                        tu.W >= (uint32_t)tu.kc && tu.p >= 13 && tu.p <= 16;
-    const bool sd_forced = sd_can && tu.sparse_sided > 0;
-    const bool sd_auto = sd_can && tu.sparse_sided < 0 && tu.sparse_planes < 0 && kSparseSidedAuto;
-    const bool sided_job = sd_forced || (sd_auto && job_planes > sp_min_planes);
-    // bands bounded by the cum scratch budget
-    pp.per_tile_bytes = (uint64_t)kTile * kTile * tu.cum_bytes * std::max<uint32_t>(L.P, 1);
-    // (at most 2^16 tiles per band: k_finalize addresses a pair slot of the band with 32 bits)
-    const uint64_t max_tiles = std::min<uint64_t>(65536, std::max<uint64_t>(1, tu.cum_budget / pp.per_tile_bytes));
-    // Parts (dsh_dist_rows_parts_device_async): k_finalize runs once per SEGMENT -- the tiles of one part inside one
-    // band -- and an event marks the end of a part's last segment: the part's span of the matrix is final and can travel
-    // while the other parts are computed.  The tile kernel runs once per band; a band is also cut at a part boundary
-    // when the part is large (>= kPartBandTiles tiles: a cut costs 0.2-0.3 ms -- two tails and a pipeline bubble,
-    // profiles/r3g -- nothing against the ~1 ms per 1 000 tiles the part takes, and the first part can leave after 1/nparts of
-    // the compute instead of after the whole tile kernel); small parts (C3 / 8 ranks: ~50-400 tiles) only cut k_finalize.
-    // A layout with ONE part (a short range) still gets its event: the exchange of every rank looks the same.
-    const size_t kPartBandTiles = tu.part_band_tiles;
+    return !T.empty();
+}
+
+// the part of tile t: the last part that starts at or before it (part_first: first tile of every part, + the end)
+static size_t part_of_tile(const std::vector<size_t> &part_first, size_t t)
+{
+    return (size_t)(std::upper_bound(part_first.begin(), part_first.end() - 1, t) - part_first.begin()) - 1;
+}
+
+// Parts (dsh_dist_rows_parts_device_async): k_finalize runs once per SEGMENT -- the tiles of one part inside one
+// band -- and an event marks the end of a part's last segment: the part's span of the matrix is final and can travel
+// while the other parts are computed.  A layout with ONE part (a short range) still gets its event: the exchange of every
+// rank looks the same.  Fills nparts (0: the call has no parts), part_first and part_tiles.
+static void part_starts(const Layout &L, const PairQuery &job, const std::vector<size_t> &trow_first, const std::vector<uint64_t> &trow_w, PairPlan &pp)
+{
     const bool parts_on = job.want_parts && !job.rect && !job.sorted_rows && L.sorted && L.part_w.size() >= 2;
     // first tile of every part: T holds the wanted tile rows in the wanted order and a part is a run of whole tile rows of
     // that order, so the part of a tile is monotone
-    std::vector<size_t> pstart{0};
+    std::vector<size_t> &pstart = pp.part_first;
+    pstart.assign(1, 0);
+    pp.part_tiles.clear();
     if (parts_on) {
         size_t q = 0;
         for (size_t r = 0; r < trow_first.size(); ++r)
@@ -830,217 +855,248 @@ bool build_tiles(const Layout &L, const PairQuery &job, const Tuning &tu, PairPl
             }
         pp.nparts = (uint32_t)pstart.size();
     }
-    pstart.push_back(T.size());
-    pp.part_first = pstart;
-    pp.part_tiles.clear();
+    pstart.push_back(pp.T.size());
     if (parts_on)
         for (size_t q = 0; q + 1 < pstart.size(); ++q) pp.part_tiles.push_back((uint32_t)(pstart[q + 1] - pstart[q]));
-    auto part_of_tile = [&](size_t t) -> size_t {
-        return (size_t)(std::upper_bound(pstart.begin(), pstart.end() - 1, t) - pstart.begin()) - 1;
-    };
-    // tail bands (plan.h, Tuning): cuts of the tile list at whole rounds of the tile kernel
+}
+
+// tail bands (plan.h, Tuning): cuts of the tile list at whole rounds of the tile kernel
+static std::vector<size_t> tail_cuts(const Layout &L, const Tuning &tu, const SparseGate &gate, const PairPlan &pp)
+{
+    const std::vector<U4> &T = pp.T;
     std::vector<size_t> cuts;
     // (a call with ONE part has nothing to send early: the destination of an exchange computes its rows that way)
-    if (parts_on && pp.nparts >= 2 && tu.tail_bands > 0 && tu.lockstep && tu.W >= (uint32_t)tu.kc && tu.nsplit == 0 && tu.round_items > 0) {
-        const uint64_t RI = tu.round_items;
-        // one item per plane of a tile while a BAND holds at most 16 rounds of them (build_band_items: piece = one plane);
-        // a longer launch takes pieces of 2-4 planes, i.e. longer rounds.  Jobs of up to 64 rounds are therefore cut into
-        // bands of at most 16: the head as well as the tails (2 ranks of BASELINE configs[2]: 27 rounds = 15 + 9 + 3
-        // instead of ONE launch of 15 two-plane rounds whose first part is final after 6 ms).
-        auto dense_planes = [&](const U4 &t) -> uint64_t {
-            if (sided_job) {
-                uint32_t lo, hi;
-                sided_route(L, t, lo, hi);
-                return t.w - t.z - lo - hi;
-            }
-            return t.w - t.z - (sp_planes_job ? sparse_route(L, sp_cap, sp_planes_job, t) : 0u);
-        };
-        uint64_t items = 0;
-        for (const U4 &t : T) items += dense_planes(t);
-        const uint64_t R = (items + RI - 1) / RI;
-        constexpr uint64_t kBandRounds = 16;
-        for (uint32_t ntails = tu.tail_bands; ntails >= 1 && cuts.empty() && items <= 4 * kBandRounds * RI && R >= 3; --ntails) {
-            std::vector<uint64_t> tails;  // rounds of the tail bands, last band first
-            uint64_t left = R;
-            for (uint32_t b = 0; b < ntails; ++b) {
-                const uint64_t pm = b == 0 ? tu.tail_permille : tu.tail_permille2;
-                const uint64_t r = std::max<uint64_t>(1, (left * pm + 500) / 1000);
-                // (a tail in front of the last one only pays where the head keeps enough rounds for its parts' transfer to
-                // hide behind it: 14 rounds -> 8 + 5 + 1, but 7 rounds -> 6 + 1, profiles/rd5d)
-                if (left < r + 2 || (b > 0 && left < r + tu.tail_head_min_rounds)) break;
-                tails.push_back(r);
-                left -= r;
-            }
-            // the head takes `left` rounds (in bands of at most 16), then the tails in reverse; a band ends at the last
-            // tile that still fits
-            std::vector<uint64_t> quota;
-            {
-                const uint64_t nb = (left + kBandRounds - 1) / kBandRounds;
-                for (uint64_t b = 0; b < nb; ++b) quota.push_back(left / nb + (b < left % nb ? 1 : 0));
-            }
-            for (size_t b = tails.size(); b-- > 0;) {
-                const uint64_t nb = (tails[b] + kBandRounds - 1) / kBandRounds;
-                for (uint64_t x = 0; x < nb; ++x) quota.push_back(tails[b] / nb + (x < tails[b] % nb ? 1 : 0));
-            }
-            // (the quota is the band's own: what a band leaves of its last round must not slide into the next band and
-            // push that one over a round boundary)
-            uint64_t acc = 0, rounds = 0, band_items = 0;
-            size_t t = 0;
-            for (size_t b = 0; b + 1 < quota.size(); ++b) {
-                while (t < T.size() && band_items + dense_planes(T[t]) <= quota[b] * RI) {
-                    acc += dense_planes(T[t]);
-                    band_items += dense_planes(T[t]);
-                    ++t;
-                }
-                if (t == 0 || t >= T.size() || (!cuts.empty() && cuts.back() == t)) continue;
-                cuts.push_back(t);
-                rounds += (band_items + RI - 1) / RI;
-                band_items = 0;
-            }
-            rounds += (items - acc + band_items + RI - 1) / RI;
-            // a cut that costs a round is worse than none -- except for a long job, where one round in twenty buys parts that
-            // leave milliseconds earlier and one-plane rounds instead of two-plane ones
-            if (rounds != R && !(R > kBandRounds && rounds == R + 1)) cuts.clear();
+    if (pp.nparts < 2 || tu.tail_bands == 0 || !tu.lockstep || tu.W < (uint32_t)tu.kc || tu.nsplit != 0 || tu.round_items == 0) return cuts;
+    const uint64_t RI = tu.round_items;
+    // one item per plane of a tile while a BAND holds at most 16 rounds of them (build_band_items: piece = one plane);
+    // a longer launch takes pieces of 2-4 planes, i.e. longer rounds.  Jobs of up to 64 rounds are therefore cut into
+    // bands of at most 16: the head as well as the tails (2 ranks of BASELINE configs[2]: 27 rounds = 15 + 9 + 3
+    // instead of ONE launch of 15 two-plane rounds whose first part is final after 6 ms).
+    const Route route = gate.route_for(gate.job_planes);  // (the job's route, not yet a band's: an estimate)
+    auto dense_planes = [&](const U4 &t) -> uint64_t {
+        uint32_t below, above;
+        tile_route(L, gate, route, t, below, above);
+        return t.w - t.z - below - above;
+    };
+    uint64_t items = 0;
+    for (const U4 &t : T) items += dense_planes(t);
+    const uint64_t R = (items + RI - 1) / RI;
+    constexpr uint64_t kBandRounds = 16;
+    for (uint32_t ntails = tu.tail_bands; ntails >= 1 && cuts.empty() && items <= 4 * kBandRounds * RI && R >= 3; --ntails) {
+        std::vector<uint64_t> tails;  // rounds of the tail bands, last band first
+        uint64_t left = R;
+        for (uint32_t b = 0; b < ntails; ++b) {
+            const uint64_t pm = b == 0 ? tu.tail_permille : tu.tail_permille2;
+            const uint64_t r = std::max<uint64_t>(1, (left * pm + 500) / 1000);
+            // (a tail in front of the last one only pays where the head keeps enough rounds for its parts' transfer to
+            // hide behind it: 14 rounds -> 8 + 5 + 1, but 7 rounds -> 6 + 1, profiles/rd5d)
+            if (left < r + 2 || (b > 0 && left < r + tu.tail_head_min_rounds)) break;
+            tails.push_back(r);
+            left -= r;
         }
+        // the head takes `left` rounds (in bands of at most 16), then the tails in reverse; a band ends at the last
+        // tile that still fits
+        std::vector<uint64_t> quota;
+        {
+            const uint64_t nb = (left + kBandRounds - 1) / kBandRounds;
+            for (uint64_t b = 0; b < nb; ++b) quota.push_back(left / nb + (b < left % nb ? 1 : 0));
+        }
+        for (size_t b = tails.size(); b-- > 0;) {
+            const uint64_t nb = (tails[b] + kBandRounds - 1) / kBandRounds;
+            for (uint64_t x = 0; x < nb; ++x) quota.push_back(tails[b] / nb + (x < tails[b] % nb ? 1 : 0));
+        }
+        // (the quota is the band's own: what a band leaves of its last round must not slide into the next band and
+        // push that one over a round boundary)
+        uint64_t acc = 0, rounds = 0, band_items = 0;
+        size_t t = 0;
+        for (size_t b = 0; b + 1 < quota.size(); ++b) {
+            while (t < T.size() && band_items + dense_planes(T[t]) <= quota[b] * RI) {
+                acc += dense_planes(T[t]);
+                band_items += dense_planes(T[t]);
+                ++t;
+            }
+            if (t == 0 || t >= T.size() || (!cuts.empty() && cuts.back() == t)) continue;
+            cuts.push_back(t);
+            rounds += (band_items + RI - 1) / RI;
+            band_items = 0;
+        }
+        rounds += (items - acc + band_items + RI - 1) / RI;
+        // a cut that costs a round is worse than none -- except for a long job, where one round in twenty buys parts that
+        // leave milliseconds earlier and one-plane rounds instead of two-plane ones
+        if (rounds != R && !(R > kBandRounds && rounds == R + 1)) cuts.clear();
     }
+    return cuts;
+}
+
+// bands: bounded by the cum scratch budget, ended by a large part and by the tail cuts.  The tile kernel runs once per
+// band; a band is also cut at a part boundary when the part is large (>= part_band_tiles tiles: a cut costs 0.2-0.3 ms --
+// two tails and a pipeline bubble, profiles/r3g -- nothing against the ~1 ms per 1 000 tiles the part takes, and the first
+// part can leave after 1/nparts of the compute instead of after the whole tile kernel); small parts (C3 / 8 ranks: ~50-400
+// tiles) only cut k_finalize.
+static void cut_bands(const Layout &L, const Tuning &tu, const std::vector<size_t> &cuts, PairPlan &pp)
+{
+    pp.per_tile_bytes = (uint64_t)kTile * kTile * tu.cum_bytes * std::max<uint32_t>(L.P, 1);
+    // (at most 2^16 tiles per band: k_finalize addresses a pair slot of the band with 32 bits)
+    const uint64_t max_tiles = std::min<uint64_t>(65536, std::max<uint64_t>(1, tu.cum_budget / pp.per_tile_bytes));
+    const std::vector<size_t> &pstart = pp.part_first;
     size_t next_cut = 0;
-    for (size_t b = 0; b < T.size();) {
-        size_t e = std::min<size_t>(T.size(), b + max_tiles);
-        if (parts_on) {  // a large part also ends the band
-            const size_t q = part_of_tile(b);
-            if (pstart[q + 1] - pstart[q] >= kPartBandTiles) e = std::min(e, pstart[q + 1]);
+    for (size_t b = 0; b < pp.T.size();) {
+        size_t e = std::min<size_t>(pp.T.size(), b + max_tiles);
+        if (pp.nparts) {  // a large part also ends the band
+            const size_t q = part_of_tile(pstart, b);
+            if (pstart[q + 1] - pstart[q] >= tu.part_band_tiles) e = std::min(e, pstart[q + 1]);
         }
         while (next_cut < cuts.size() && cuts[next_cut] <= b) ++next_cut;
         if (next_cut < cuts.size()) e = std::min(e, cuts[next_cut]);
         pp.bands.emplace_back(b, e);
         b = e;
     }
+}
+
+// segments: the tiles of one part inside one band, with the histogram columns their k_finalize launch needs
+static void cut_segments(const Layout &L, PairPlan &pp)
+{
+    const std::vector<size_t> &pstart = pp.part_first;
     pp.segs.resize(pp.bands.size());
     for (size_t bi = 0; bi < pp.bands.size(); ++bi) {
         size_t b = pp.bands[bi].first;
         while (b < pp.bands[bi].second) {
-            const size_t q = part_of_tile(b);  // part of a tile = part of its tile row (parts are runs of whole tile rows)
+            const size_t q = part_of_tile(pstart, b);  // part of a tile = part of its tile row (parts are runs of whole tile rows)
             const size_t e = std::min(pp.bands[bi].second, pstart[q + 1]);
             const bool last_of_part = e == pstart[q + 1];
-            Seg sg{b, e, parts_on && last_of_part ? (int)q : -1, 1};
+            Seg sg{b, e, pp.nparts && last_of_part ? (int)q : -1, 1};
             for (size_t t = b; t < e; ++t) {
                 int lo, hi;
-                tile_vrange(L, T[t], lo, hi);
+                tile_vrange(L, pp.T[t], lo, hi);
                 sg.hist_bins = std::max(sg.hist_bins, hi - lo + 1);
             }
             pp.segs[bi].push_back(sg);
             b = e;
         }
     }
-    // rank[t] = position of tile t in the row-major order of its segment (the order k_finalize walks)
-    std::vector<uint32_t> &rank = pp.rank;
-    rank.resize(T.size());
+}
+
+// rank[t] = position of tile t in the row-major order of its segment (the order k_finalize walks), then the launch order
+// of the tile kernel inside every segment (xcd_order)
+static void order_tiles(const Tuning &tu, PairPlan &pp)
+{
+    pp.rank.resize(pp.T.size());
     for (auto &sv : pp.segs)
         for (auto &sg : sv)
-            for (size_t t = sg.b; t < sg.e; ++t) rank[t] = (uint32_t)(t - sg.b);
+            for (size_t t = sg.b; t < sg.e; ++t) pp.rank[t] = (uint32_t)(t - sg.b);
     for (auto &sv : pp.segs)
-        for (auto &sg : sv) xcd_order(T, rank, sg.b, sg.e, tu.lockstep ? 2 : 1);
-    // sparse outer planes: band by band (the automatic rule looks at the band), the routed planes of every tile, one sparse
-    // item each -- ordered by column block, whose table the items of a column share in L2 -- and the slabs they read
+        for (auto &sg : sv) xcd_order(pp.T, pp.rank, sg.b, sg.e, tu.lockstep ? 2 : 1);
+}
+
+// Launch order of the sparse items [first, last) of a band (a transposed item's table is its ROW block's: read "column
+// block" as table_block() below).
+// An item gathers from its column block's table (16 bytes per position: 256 KiB at p = 14), which
+// only pays while the table stays in L2; workgroup w runs on XCD w % 8 (xcd_order above).  So every column
+// block is given to ONE XCD -- the blocks with the most items first, each to the XCD with the fewest so far --
+// its items follow each other there, and the eight lists are interleaved one item at a time.
+static void order_sparse_items(const std::vector<U4> &T, const std::pair<size_t, size_t> &bd, uint32_t NT, size_t first, size_t last, std::vector<U4> &sp_items)
+{
+    if (last - first <= 1) return;
+    // the block whose table an item reads: its column block, the row block of a transposed one
+    auto table_block = [&](const U4 &it) { return it.y & kSpItemTransposed ? T[bd.first + it.x].x : T[bd.first + it.x].y; };
+    constexpr size_t nx = 8;
+    std::vector<uint32_t> per_col(NT, 0), cols;
+    for (size_t k = first; k < last; ++k) per_col[table_block(sp_items[k])]++;
+    for (uint32_t b = 0; b < NT; ++b)
+        if (per_col[b]) cols.push_back(b);
+    std::stable_sort(cols.begin(), cols.end(), [&](uint32_t a, uint32_t b) { return per_col[a] > per_col[b]; });
+    std::vector<uint32_t> xcd_of(NT, 0);
+    size_t load[nx] = {0};
+    for (uint32_t b : cols) {
+        size_t x = 0;
+        for (size_t y = 1; y < nx; ++y)
+            if (load[y] < load[x]) x = y;
+        xcd_of[b] = (uint32_t)x;
+        load[x] += per_col[b];
+    }
+    std::vector<U4> lists[nx];
+    for (size_t k = first; k < last; ++k) lists[xcd_of[table_block(sp_items[k])]].push_back(sp_items[k]);
+    for (auto &l : lists)
+        std::stable_sort(l.begin(), l.end(), [&](const U4 &a, const U4 &b) {
+            const U4 &ta = T[bd.first + a.x], &tb = T[bd.first + b.x];
+            const uint32_t ca = table_block(a), cb = table_block(b), pa = a.y & kSpPlaneMask, pb = b.y & kSpPlaneMask;
+            return ca != cb ? ca < cb : pa != pb ? pa > pb : ta.x + ta.y < tb.x + tb.y;
+        });
+    size_t q = first;
+    for (size_t r = 0; q < last; ++r)
+        for (size_t x = 0; x < nx; ++x)
+            if (r < lists[x].size()) sp_items[q++] = lists[x][r];
+}
+
+// sparse routing: band by band (the automatic rule looks at the band), the routed planes of every tile, one sparse item
+// each -- ordered by column block, whose table the items of a column share in L2 -- and the slabs they read.  One loop for
+// both routes: a two-plane item has no flags and lists on both blocks, a sided item its polarities and transposition.
+static void route_sparse(const Layout &L, const Tuning &tu, const SparseGate &gate, PairPlan &pp)
+{
+    const std::vector<U4> &T = pp.T;
+    const uint32_t NT = L.Npad / kTile;
     pp.sp.assign(T.size(), 0);
     pp.spb.assign(T.size(), 0);
     pp.sided_items = pp.transposed_items = pp.table_slabs = 0;
     pp.band_sp_items.assign(pp.bands.size(), std::make_pair((size_t)0, (size_t)0));
-    if (sp_planes || sd_forced || sd_auto) {
-        pp.slab_of.assign((size_t)NT * std::max<uint32_t>(L.P, 1), -1);
-        std::vector<uint8_t> listed;  // per slab: an item reads lists from it
-        auto slab = [&](uint32_t b, uint32_t pl, bool lists) -> uint32_t {
-            int32_t &s = pp.slab_of[(size_t)b * L.P + pl];
-            if (s < 0) {
-                s = (int32_t)pp.slabs.size();
-                // (the two-plane route's sets are U: where the thresholds are this plan's, that is what sided_polarity says too)
-                pp.slabs.push_back(U2{b, pl | (sd_can && sided_polarity(L, b, L.pbase + 1 + (int)pl) ? kSpSlabA : 0u)});
-                listed.push_back(0);
-            }
-            if (lists) listed[(size_t)s] = 1;
-            return (uint32_t)s;
-        };
-        // the block whose table an item reads: its column block, the row block of a transposed one
-        auto table_block = [&](const std::pair<size_t, size_t> &bd, const U4 &it) { return it.y & kSpItemTransposed ? T[bd.first + it.x].x : T[bd.first + it.x].y; };
-        for (size_t bi = 0; bi < pp.bands.size(); ++bi) {
-            const auto &bd = pp.bands[bi];
-            const size_t i0 = pp.sp_items.size();
-            uint64_t band_planes = 0;
-            for (size_t t = bd.first; t < bd.second; ++t) band_planes += T[t].w - T[t].z;
-            if (sd_forced || (sd_auto && band_planes > sp_min_planes)) {
-                for (size_t t = bd.first; t < bd.second; ++t) {
-                    uint32_t below, above;
-                    sided_route(L, T[t], below, above);
-                    const uint32_t k = below + above;
-                    if (!k || pp.slabs.size() + 2 * k > tu.sparse_max_slabs) continue;
-                    pp.sp[t] = (uint8_t)above;
-                    pp.spb[t] = (uint8_t)below;
-                    for (uint32_t x = 0; x < k; ++x) {
-                        const uint32_t pl = x < above ? T[t].w - 1 - x : T[t].z + (x - above);
-                        const int v = L.pbase + 1 + (int)pl;
-                        const bool tr = T[t].x != T[t].y && sided_depth(L, T[t].y, v) > sided_depth(L, T[t].x, v);
-                        const uint32_t lb = tr ? T[t].y : T[t].x, tb = tr ? T[t].x : T[t].y;
-                        const uint32_t fl = (sided_polarity(L, lb, v) ? kSpItemListA : 0u) | (sided_polarity(L, tb, v) ? kSpItemTabA : 0u) |
-                                            (tr ? kSpItemTransposed : 0u);
-                        pp.sp_items.push_back(U4{(uint32_t)(t - bd.first), pl | fl, slab(T[t].x, pl, !tr), slab(T[t].y, pl, tr || T[t].x == T[t].y)});
-                        ++pp.sided_items;
-                        pp.transposed_items += tr;
-                    }
-                }
-            } else if (sp_planes && band_planes > sp_min_planes) {
-                for (size_t t = bd.first; t < bd.second; ++t) {
-                    const uint32_t k = sparse_route(L, sp_cap, sp_planes, T[t]);
-                    if (!k || pp.slabs.size() + 2 * k > tu.sparse_max_slabs) continue;
-                    pp.sp[t] = (uint8_t)k;
-                    for (uint32_t x = 0; x < k; ++x) {
-                        const uint32_t pl = T[t].w - 1 - x;
-                        pp.sp_items.push_back(U4{(uint32_t)(t - bd.first), pl, slab(T[t].x, pl, true), slab(T[t].y, pl, true)});
-                    }
-                }
-            }
-            // Launch order (a transposed item's table is its ROW block's: read "column block" as table_block() below).
-            // An item gathers from its column block's table (16 bytes per position: 256 KiB at p = 14), which
-            // only pays while the table stays in L2; workgroup w runs on XCD w % 8 (xcd_order above).  So every column
-            // block is given to ONE XCD -- the blocks with the most items first, each to the XCD with the fewest so far --
-            // its items follow each other there, and the eight lists are interleaved one item at a time.
-            const size_t cnt = pp.sp_items.size() - i0;
-            if (cnt > 1) {
-                constexpr size_t nx = 8;
-                std::vector<uint32_t> per_col(NT, 0), cols;
-                for (size_t k = i0; k < pp.sp_items.size(); ++k) per_col[table_block(bd, pp.sp_items[k])]++;
-                for (uint32_t b = 0; b < NT; ++b)
-                    if (per_col[b]) cols.push_back(b);
-                std::stable_sort(cols.begin(), cols.end(), [&](uint32_t a, uint32_t b) { return per_col[a] > per_col[b]; });
-                std::vector<uint32_t> xcd_of(NT, 0);
-                size_t load[nx] = {0};
-                for (uint32_t b : cols) {
-                    size_t x = 0;
-                    for (size_t y = 1; y < nx; ++y)
-                        if (load[y] < load[x]) x = y;
-                    xcd_of[b] = (uint32_t)x;
-                    load[x] += per_col[b];
-                }
-                std::vector<U4> lists[nx];
-                for (size_t k = i0; k < pp.sp_items.size(); ++k) lists[xcd_of[table_block(bd, pp.sp_items[k])]].push_back(pp.sp_items[k]);
-                for (auto &l : lists)
-                    std::stable_sort(l.begin(), l.end(), [&](const U4 &a, const U4 &b) {
-                        const U4 &ta = T[bd.first + a.x], &tb = T[bd.first + b.x];
-                        const uint32_t ca = table_block(bd, a), cb = table_block(bd, b), pa = a.y & kSpPlaneMask, pb = b.y & kSpPlaneMask;
-                        return ca != cb ? ca < cb : pa != pb ? pa > pb : ta.x + ta.y < tb.x + tb.y;
-                    });
-                size_t q = i0;
-                for (size_t r = 0; q < pp.sp_items.size(); ++r)
-                    for (size_t x = 0; x < nx; ++x)
-                        if (r < lists[x].size()) pp.sp_items[q++] = lists[x][r];
-            }
-            pp.band_sp_items[bi] = std::make_pair(i0, pp.sp_items.size());
+    if (!gate.any()) return;
+    pp.slab_of.assign((size_t)NT * std::max<uint32_t>(L.P, 1), -1);
+    std::vector<uint8_t> listed;  // per slab: an item reads lists from it
+    auto slab = [&](uint32_t b, uint32_t pl, bool lists) -> uint32_t {
+        int32_t &s = pp.slab_of[(size_t)b * L.P + pl];
+        if (s < 0) {
+            s = (int32_t)pp.slabs.size();
+            // (the two-plane route's sets are U: where the thresholds are this plan's, that is what sided_polarity says too)
+            pp.slabs.push_back(U2{b, pl | (gate.sided_can && sided_polarity(L, b, L.pbase + 1 + (int)pl) ? kSpSlabA : 0u)});
+            listed.push_back(0);
         }
-        // a slab that only serves as a table needs no lists (the sided route only: the two-plane route lists both blocks)
-        for (size_t k = 0; k < pp.slabs.size(); ++k)
-            if (!listed[k]) pp.slabs[k].y |= kSpSlabTableOnly, ++pp.table_slabs;
+        if (lists) listed[(size_t)s] = 1;
+        return (uint32_t)s;
+    };
+    for (size_t bi = 0; bi < pp.bands.size(); ++bi) {
+        const auto &bd = pp.bands[bi];
+        const size_t i0 = pp.sp_items.size();
+        uint64_t band_planes = 0;
+        for (size_t t = bd.first; t < bd.second; ++t) band_planes += T[t].w - T[t].z;
+        const Route route = gate.route_for(band_planes);
+        for (size_t t = bd.first; t < bd.second && route != Route::None; ++t) {
+            uint32_t below, above;
+            tile_route(L, gate, route, T[t], below, above);
+            const uint32_t k = below + above;
+            if (!k || pp.slabs.size() + 2 * k > tu.sparse_max_slabs) continue;
+            pp.sp[t] = (uint8_t)above;
+            pp.spb[t] = (uint8_t)below;
+            for (uint32_t x = 0; x < k; ++x) {
+                const uint32_t pl = x < above ? T[t].w - 1 - x : T[t].z + (x - above);
+                bool tr = false;               // the list side is the column block
+                bool both = true;              // both blocks carry lists (the two-plane route)
+                uint32_t fl = 0;
+                if (route == Route::Sided) {
+                    const int v = L.pbase + 1 + (int)pl;
+                    tr = T[t].x != T[t].y && sided_depth(L, T[t].y, v) > sided_depth(L, T[t].x, v);
+                    both = T[t].x == T[t].y;
+                    const uint32_t lb = tr ? T[t].y : T[t].x, tb = tr ? T[t].x : T[t].y;
+                    fl = (sided_polarity(L, lb, v) ? kSpItemListA : 0u) | (sided_polarity(L, tb, v) ? kSpItemTabA : 0u) | (tr ? kSpItemTransposed : 0u);
+                    ++pp.sided_items;
+                    pp.transposed_items += tr;
+                }
+                // (braces: the row block's slab is made before the column block's -- the order decides the slab indices)
+                pp.sp_items.push_back(U4{(uint32_t)(t - bd.first), pl | fl, slab(T[t].x, pl, both || !tr), slab(T[t].y, pl, both || tr)});
+            }
+        }
+        order_sparse_items(T, bd, NT, i0, pp.sp_items.size(), pp.sp_items);
+        pp.band_sp_items[bi] = std::make_pair(i0, pp.sp_items.size());
     }
-    // chunk range of every tile (the work items of a band are cut from these: build_band_items); the planes routed sparse
-    // are the top (and, with the sided route, the bottom) of the tile's range and simply left out
+    // a slab that only serves as a table needs no lists (the sided route only: the two-plane route lists both blocks)
+    for (size_t k = 0; k < pp.slabs.size(); ++k)
+        if (!listed[k]) pp.slabs[k].y |= kSpSlabTableOnly, ++pp.table_slabs;
+}
+
+// chunk range of every tile (the work items of a band are cut from these: build_band_items); the planes routed sparse
+// are the top (and, with the sided route, the bottom) of the tile's range and simply left out.  And the largest band.
+static void chunk_ranges(const Tuning &tu, PairPlan &pp)
+{
+    const std::vector<U4> &T = pp.T;
     const uint32_t KC = (uint32_t)tu.kc;
     const uint32_t cpp = tu.W >= KC ? tu.W / KC : 1;  // chunks per plane when a plane spans chunks
     std::vector<U2> &CR = pp.chunks;
@@ -1052,6 +1108,36 @@ bool build_tiles(const Layout &L, const PairQuery &job, const Tuning &tu, PairPl
             CR[t] = U2{(uint32_t)(((uint64_t)T[t].z * tu.W) / KC), (uint32_t)(((uint64_t)T[t].w * tu.W + KC - 1) / KC)};
     }
     for (auto &bd : pp.bands) pp.max_band = std::max(pp.max_band, bd.second - bd.first);
+}
+
+bool build_tiles(const Layout &L, const PairQuery &job, const Tuning &tu, PairPlan &pp)
+{
+    pp.T.clear();
+    pp.bands.clear();
+    pp.band_items.clear();
+    pp.segs.clear();
+    pp.items.clear();
+    pp.band_frags.clear();
+    pp.band_round.clear();
+    pp.sp.clear();
+    pp.spb.clear();
+    pp.sp_items.clear();
+    pp.band_sp_items.clear();
+    pp.slabs.clear();
+    pp.nparts = 0;
+    pp.max_band = 0;
+    std::vector<size_t> trow_first;  // (wanted tile rows of a sorted layout) first tile of the tile row ...
+    std::vector<uint64_t> trow_w;    // ... and the wanted rows in front of it (wanted order)
+    if (!list_tiles(L, job, pp.T, trow_first, trow_w)) return false;
+    uint64_t job_planes = 0;
+    for (const U4 &t : pp.T) job_planes += t.w - t.z;
+    const SparseGate gate = sparse_gate(L, job, tu, job_planes);
+    part_starts(L, job, trow_first, trow_w, pp);
+    cut_bands(L, tu, tail_cuts(L, tu, gate, pp), pp);
+    cut_segments(L, pp);
+    order_tiles(tu, pp);
+    route_sparse(L, tu, gate, pp);
+    chunk_ranges(tu, pp);
     return true;
 }
 
@@ -1079,30 +1165,48 @@ static uint32_t band_round_items(const Tuning &tu, uint64_t ni)
     return ni <= 2 * (uint64_t)tu.small_round_items ? tu.small_round_items : tu.round_items;
 }
 
+// THE piece rule: the items of a band are pieces of at most `piece` chunks of its tiles' chunk ranges.  build_band_items
+// cuts them and band_item_count counts them (the device and staging buffers are sized before the first band is launched),
+// both from here.
+struct BandShape {
+    uint64_t piece;   // chunks of an item at most: whole planes
+    uint32_t cpp;     // chunks per plane when a plane spans chunks, else 1
+    uint64_t total;   // chunks of all the band's tiles
+    uint32_t maxlen;  // chunks of its longest tile
+};
+static BandShape band_shape(const Tuning &tu, const PairPlan &pp, size_t bi)
+{
+    const auto &bd = pp.bands[bi];
+    const uint32_t KC = (uint32_t)tu.kc;
+    BandShape s{1, tu.W >= KC ? tu.W / KC : 1, 0, 0};
+    for (size_t t = bd.first; t < bd.second; ++t) {
+        const uint32_t len = pp.chunks[t].y - pp.chunks[t].x;
+        s.total += len;
+        s.maxlen = std::max(s.maxlen, len);
+    }
+    const size_t nt = bd.second - bd.first;
+    // piece size: whole planes, aiming at >= 16 items per resident workgroup slot (512)
+    s.piece = tu.nsplit > 0 ? std::max<uint64_t>(1, (s.total / std::max<size_t>(nt, 1) + tu.nsplit - 1) / tu.nsplit)
+                            : std::max<uint64_t>(1, s.total / (16 * 512));
+    if (tu.nsplit == 0 && tu.lockstep)  // equal, short items: the two items of a workgroup run in lockstep
+        s.piece = std::min<uint64_t>(s.piece, std::max<uint64_t>(s.cpp, (uint64_t)tu.ls_item_chunks));
+    s.piece = (s.piece + s.cpp - 1) / s.cpp * s.cpp;
+    return s;
+}
+// items of a tile of `len` chunks
+static uint64_t pieces_of(uint64_t len, uint64_t piece) { return (len + piece - 1) / piece; }
+
 // work items of band bi, appended to pp.items (bands in order): {tile index in band, chunk begin, chunk end, fragment?}
 void build_band_items(const Tuning &tu, PairPlan &pp, size_t bi)
 {
     const auto &bd = pp.bands[bi];
     const std::vector<U2> &CR = pp.chunks;
     std::vector<U4> &I = pp.items;
-    const uint32_t KC = (uint32_t)tu.kc;
-    const uint32_t cpp = tu.W >= KC ? tu.W / KC : 1;
-    const size_t nt = bd.second - bd.first;
-    uint64_t tot = 0;
-    uint32_t maxlen = 0;
-    for (size_t t = bd.first; t < bd.second; ++t) {
-        const uint32_t len = CR[t].y - CR[t].x;
-        tot += len;
-        maxlen = std::max(maxlen, len);
-    }
-    // piece size: whole planes, aiming at >= 16 items per resident workgroup slot (512)
-    uint64_t piece = tu.nsplit > 0 ? std::max<uint64_t>(1, (tot / std::max<size_t>(nt, 1) + tu.nsplit - 1) / tu.nsplit)
-                                   : std::max<uint64_t>(1, tot / (16 * 512));
-    if (tu.nsplit == 0 && tu.lockstep)  // equal, short items: the two items of a workgroup run in lockstep
-        piece = std::min<uint64_t>(piece, std::max<uint64_t>(cpp, (uint64_t)tu.ls_item_chunks));
-    piece = (piece + cpp - 1) / cpp * cpp;
+    const BandShape shape = band_shape(tu, pp, bi);
+    const uint64_t piece = shape.piece;
+    const uint32_t cpp = shape.cpp;
     const size_t i0 = I.size();
-    const uint32_t maxpieces = (uint32_t)((maxlen + piece - 1) / piece);
+    const uint32_t maxpieces = (uint32_t)pieces_of(shape.maxlen, piece);
     // Piece-major, so that neighbours in launch order share planes.  The lockstep kernel runs 2 or 3 consecutive items side by side: inside
     // a group of pieces equal lengths are kept together, longest first, tiles in order (only a tile's last piece can be
     // shorter; with whole-plane pieces every item of the group has the same length and nothing moves).  One counting
@@ -1196,34 +1300,20 @@ void emit_band_lists(const Layout &L, const PairPlan &pp, size_t bi, U4 *pinT, U
             const size_t at = sg.b + pp.rank[t];
             // (w: the tile's C(v) block in its band -- at most 2^16 tiles per band -- and, above it, the tile's part: the
             // signalling k_finalize counts a finished tile into that part)
-            const uint32_t part = pp.nparts ? (uint32_t)((std::upper_bound(pp.part_first.begin(), pp.part_first.end() - 1, t) - pp.part_first.begin()) - 1) : 0u;
+            const uint32_t part = pp.nparts ? (uint32_t)part_of_tile(pp.part_first, t) : 0u;
             pinF[at] = U4{T[t].x, T[t].y, pl | ((uint32_t)lo << 16) | ((uint32_t)hi << 24), (uint32_t)(t - b0) | (part << 16)};
         }
 }
 
 uint64_t band_item_count(const Tuning &tu, const PairPlan &pp, size_t bi)
 {
-    // (the arithmetic of build_band_items, without writing anything: the device and staging buffers are sized before the
-    // first band is launched)
     const auto &bd = pp.bands[bi];
-    const std::vector<U2> &CR = pp.chunks;
-    const uint32_t KC = (uint32_t)tu.kc;
-    const uint32_t cpp = tu.W >= KC ? tu.W / KC : 1;
-    const size_t nt = bd.second - bd.first;
-    uint64_t tot = 0;
-    for (size_t t = bd.first; t < bd.second; ++t) tot += CR[t].y - CR[t].x;
-    uint64_t piece = tu.nsplit > 0 ? std::max<uint64_t>(1, (tot / std::max<size_t>(nt, 1) + tu.nsplit - 1) / tu.nsplit)
-                                   : std::max<uint64_t>(1, tot / (16 * 512));
-    if (tu.nsplit == 0 && tu.lockstep) piece = std::min<uint64_t>(piece, std::max<uint64_t>(cpp, (uint64_t)tu.ls_item_chunks));
-    piece = (piece + cpp - 1) / cpp * cpp;
+    const BandShape shape = band_shape(tu, pp, bi);
     uint64_t cnt = 0;
-    for (size_t t = bd.first; t < bd.second; ++t) {
-        const uint64_t len = CR[t].y - CR[t].x;
-        cnt += len <= piece ? (len ? 1 : 0) : (len + piece - 1) / piece;
-    }
+    for (size_t t = bd.first; t < bd.second; ++t) cnt += pieces_of(pp.chunks[t].y - pp.chunks[t].x, shape.piece);
     uint64_t over = 0;
     uint32_t f = 1;
-    overflow_fragments(tu, band_round_items(tu, cnt), cpp, piece, cnt, over, f);
+    overflow_fragments(tu, band_round_items(tu, cnt), shape.cpp, shape.piece, cnt, over, f);
     return cnt - over + over * f;
 }
 

@@ -10,11 +10,16 @@
 //     later rows, each part ordered by the per-sketch key (T, L, hi) -- and the per-128-column-block statistics the
 //     per-tile plane ranges come from;
 //   * PairPlan: tiles, bands (bounded by the C(v) scratch), segments (tiles of one part inside one band: one k_finalize
-//     launch each), work items of the tile kernel, and the two device tile lists.
+//     launch each), work items of the tile kernel, and the two device tile lists.  build_tiles is a sequence of steps in
+//     plan.cpp, each filling what it owns: list_tiles (the tile list), sparse_gate (which calls may route sparse at all),
+//     part_starts, tail_cuts, cut_bands, cut_segments, order_tiles (rank and the XCD order), route_sparse (both sparse
+//     routes, through one tile_route and one item loop; order_sparse_items), chunk_ranges.  The items of a band follow
+//     one piece rule (band_shape, pieces_of) in build_band_items and band_item_count.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
 
+#include <algorithm>
 #include <utility>
 #include <vector>
 
@@ -173,21 +178,40 @@ struct Layout {
     std::vector<uint32_t> sort_a;  // scratch of the column sort
 };
 
-// keys: the n per-sketch keys (only [rb, n) is read for a sorted layout).  `parts` as range_parts() gives them
-// (ignored for the identity layout).
-// rowsorted_nparts > 0 (sorted layouts only): row-sorted parts, `parts` is ignored.
-// extra (sorted layouts only): further wanted segments; the wanted range is then ONE part (`parts` is ignored).
-// gcnt (or nullptr: no plane is ever routed sparse): per sketch, next to its key, g0 | g1 << 16 of k_selfhist_card -- how
-// many of its registers are >= its T and >= T - 1
-// thr (or nullptr: no sided route), thr_cap: per sketch vU | vA << 8 of k_selfhist_card and the cap they were computed at
-void build_layout(const uint32_t *keys, uint64_t n, int want_sorted, uint64_t rb, uint64_t re,
-                  const std::vector<uint64_t> &parts, Layout &L, uint32_t rowsorted_nparts = 0,
-                  const std::vector<uint64_t> *extra = nullptr, const uint32_t *gcnt = nullptr, const uint32_t *thr = nullptr,
-                  uint32_t thr_cap = 0);
+// the per-sketch words of k_selfhist_card a layout is built from, n of each
+struct SketchWords {
+    const uint32_t *keys = nullptr;  // the per-sketch keys (only [rb, n) is read for a sorted layout)
+    // (or nullptr: no plane is ever routed sparse) per sketch, next to its key, g0 | g1 << 16 -- how many of its registers are
+    // >= its T and >= T - 1
+    const uint32_t *gcnt = nullptr;
+    const uint32_t *thr = nullptr;   // (or nullptr: no sided route) per sketch vU | vA << 8 ...
+    uint32_t thr_cap = 0;            // ... and the cap they were computed at
+};
+// which layout: the wanted rows and how they are cut
+struct LayoutQuery {
+    int want_sorted = 0;             // 0: the identity layout over all n sketches (everything below is ignored)
+    uint64_t rb = 0, re = 0;         // the wanted rows
+    const std::vector<uint64_t> *parts = nullptr;  // the parts of the wanted rows as range_parts() gives them
+    uint32_t rowsorted_nparts = 0;   // > 0: row-sorted parts, `parts` is ignored
+    const std::vector<uint64_t> *extra = nullptr;  // further wanted segments; the wanted range is then ONE part (`parts` is ignored)
+};
+// three steps: the column order (order_columns), the tables of the wanted order (wanted_tables: wtr, part_w, part_pos,
+// rowoff), the per-block statistics (block_stats)
+void build_layout(uint64_t n, const SketchWords &words, const LayoutQuery &query, Layout &L);
 
-// dense plane range of the tile (ti, tj): C(v) is needed for v in (max(larger of the two minima, smaller of the two
-// low thresholds), larger of the two high thresholds] -- below that every C(v) is 0 or comes from the low-list join
-void tile_planes(const Layout &L, uint32_t ti, uint32_t tj, int &pb, int &pe);
+// dense plane range of a tile from the statistics of its two blocks (min value, min low threshold, max high threshold):
+// C(v) is needed for v in (max(larger of the two minima, smaller of the two low thresholds), larger of the two high
+// thresholds] -- below that every C(v) is 0 or comes from the low-list join
+inline void tile_planes(int lo_i, int L_i, int T_i, int lo_j, int L_j, int T_j, int pbase, int &pb, int &pe)
+{
+    const int lo_t = std::max(std::max(lo_i, lo_j), std::min(L_i, L_j));
+    pb = std::max(0, lo_t - pbase);
+    pe = std::max(pb, std::max(T_i, T_j) - pbase);
+}
+inline void tile_planes(const Layout &L, uint32_t ti, uint32_t tj, int &pb, int &pe)
+{
+    tile_planes(L.blk_lo[ti], L.blk_L[ti], L.blk_T[ti], L.blk_lo[tj], L.blk_L[tj], L.blk_T[tj], L.pbase, pb, pe);
+}
 
 // ---- the pair plan ------------------------------------------------------------------------------------------------------
 struct PairQuery {

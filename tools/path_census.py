@@ -213,7 +213,7 @@ def census(regs, p, emax=None, elow=None, sort=True, kc=PAIR_KC, sparse_planes=-
             Lp, Tt = pbase + pb, pbase + pe
             vlo, vhi = min(blk[bi]["lo"], blk[bj]["lo"]), max(blk[bi]["hi"], blk[bj]["hi"])
             planes.append(pe - pb)
-            sp = 0  # planes routed sparse, from the top of the range (plan.cpp, sparse_route)
+            sp = 0  # planes routed sparse, from the top of the range (plan.cpp, tile_route: the two-plane route)
             while sp < sp_planes and pe - sp > pb and max(sparse_bound(blk[bi], Tt - sp), sparse_bound(blk[bj], Tt - sp)) <= sp_cap:
                 sp += 1
             w0 = (Tt + 1) >> 4
@@ -257,7 +257,7 @@ def census(regs, p, emax=None, elow=None, sort=True, kc=PAIR_KC, sparse_planes=-
     if sparse_planes < 0 and sum(planes) <= SPARSE_MIN_BAND:  # (the automatic rule: one band here)
         for t in tiles:
             t["sparse"] = 0
-    # the sided route (plan.cpp, sided_route and build_tiles): per block the largest vU and the smallest vA
+    # the sided route (plan.cpp, tile_route and route_sparse): per block the largest vU and the smallest vA
     for t in tiles:
         t["below"], t["sided"] = 0, []
     sided_items = transposed = table_slabs = 0
