@@ -1,7 +1,9 @@
 // ctx.h -- the per-GPU context behind the opaque dsh_ctx of include/dashing_hip.h, the owners of what it holds on the
 // device and in page-locked memory (DevBuf, PinBuf, Event, Stream, Staging: each releases itself, so `delete` of a
 // context is its whole release list), and the internal entry points the translation units of libdashing_hip.so share:
-//   abi.hip       context, resident sketches, sketch waist, cardinalities, compare entry points, tickets, options
+//   abi.hip       context, resident sketches, cardinalities, compare entry points, tickets, shards, options
+//   sketch.hip    the sketch waist: dsh_sketch_batch*, dsh_sketch_records*, dsh_sketch_fastx_batch_async
+//   sketch_plan.h (header, no HIP types) the lists the host fills for the sketch kernels and the planners that cut them
 //   engine.hip    prepare() (per-sketch pass, layout, bit-planes, position index) and run_pairs() (tile kernel + k_finalize)
 //   knn.hip       dsh_knn
 //   bands.h       (header) the band walk of the five consumers of dense bands: threshold, cluster, greedy, greedy_extend,
@@ -17,7 +19,7 @@
 //   hist.hip      dsh_dist_histogram*, dsh_dist_rect_histogram (the distribution of the values over caller-given edges)
 //   derive.hip    dsh_fold*, dsh_upload_sketches_folded*, dsh_union_groups* (new sketches out of resident ones)
 //   exchange.hip  RCCL: dsh_comm_*, dsh_collect_*, dsh_allgather_device, dsh_dist_collect
-//   plan.cpp      the pure-host planner (layout, tiles, bands, parts, work items, row partitions)
+//   plan.cpp      the pure-host planner (layout, tiles, bands, parts, work items, row partitions, shard bounds)
 // State that one of these modules uses alone is a named member struct of dsh_ctx (c->cc.parent, c->xch.comm); what the
 // compare path shares with every module stays flat.
 #pragma once
@@ -273,11 +275,11 @@ struct dsh_ctx {
     size_t ev_used = 0;
 
     // ---- state of ONE module each ----
-    // sketch waist (abi.hip): the sequence of a batch, the k_sketch work list of the call in flight, the runs, segments
+    // sketch waist (sketch.hip): the sequence of a batch, the k_sketch work list of the call in flight, the runs, segments
     // and rows to clear of dsh_sketch_records; dsh_sketch_fastx_batch_async: raw FASTA bytes of a batch, the decoder's
     // tables and scratch (kernels_fastx.hip)
     struct {
-        DevBuf seqbuf, workbuf, recbuf;
+        DevBuf seqbuf, workbuf, recbuf;  // (workbuf: dsh_unpermute_blocks_device of abi.hip borrows it for its per-tile deltas)
         Staging work, rec;
         DevBuf rawbuf, fx_tab, fx_summ, fx_state, fx_declen, fx_status;
         Staging fx;

@@ -3,8 +3,8 @@
 // dist_loop / perform_core_op (src/sketch_and_cmp.h:785-880, :699-710) is unit-tested without a GPU
 // (tests/test_plan.py).  Also the sequential build of the clusters' union-find (dsh_plan_uf_labels, at the end) and the band rule of
 // the greedy representatives (dshh_greedy_bands) and the band walk all five band consumers share (dshh_threshold_bands), and the
-// sequential build of the linkage clusters (dsh_plan_linkage_labels, dsh_plan_linkage_loose: ../linkage.h).  Built into
-// libdashing_host.so; not part of the GPU C-ABI.
+// sequential build of the linkage clusters (dsh_plan_linkage_labels, dsh_plan_linkage_loose: ../linkage.h), and the sketch
+// path's planners (dshh_sketch_plan: ../sketch_plan.h).  Built into libdashing_host.so; not part of the GPU C-ABI.
 #include <algorithm>
 #include <cstdarg>
 #include <cstdio>
@@ -14,6 +14,7 @@
 #include "../linkage.h"
 #include "../mst.h"
 #include "../plan.h"
+#include "../sketch_plan.h"
 #include "../uf.h"
 
 using namespace dsh;
@@ -1005,6 +1006,79 @@ int dsh_plan_mst(uint64_t n, const float *tri, int descending, float cutoff, uin
     if (labels)
         for (uint64_t x = 0; x < n; ++x) labels[x] = uf_find<UfPlain>(parent.data(), (uint32_t)x, (uint32_t)n + 1);
     return 0;
+}
+
+}  // extern "C"
+
+namespace {
+
+template <class T>
+bool hand_back(const std::vector<T> &v, void *buf, uint64_t &count)
+{
+    const uint64_t cap = count;
+    count = v.size();
+    if (!buf) return true;
+    if (cap < v.size()) return false;
+    if (!v.empty()) std::memcpy(buf, v.data(), v.size() * sizeof(T));
+    return true;
+}
+
+}  // namespace
+
+extern "C" {
+
+// the sketch path's planners (../sketch_plan.h) on a caller's offsets off[n + 1], as sketch.hip runs them behind its checks
+// (tests/test_sketch_plan.py).  kind 0: plan_genomes -> list 0 = SketchWork.  kind 1: plan_records -> lists RecRun, RecSeg, rows to
+// clear (uint32), SketchWork; info[1] = 1 where the records kernel takes the call (0: all n rows are cleared at once, every record
+// is a genome).  kind 2: plan_fastx -> lists FastxGenome, FastxChunk, from the first byte and the raw length of every genome's
+// file (the planner reads nothing else of the raw bytes).  counts[4] gets the lists' lengths in elements; with bufs == NULL that
+// is all, else bufs[i] (where not NULL) has room for counts[i] elements on entry and gets list i.  Returns 0, -1 for arguments
+// sketch.hip's check refuses (offsets not monotone, slots beyond 2^32) or unusable here, -2 for a buffer too small, and a FASTX
+// refusal's code (kFastxPlan*) with info[0] = the genome.
+int dshh_sketch_plan(int kind, const uint64_t *off, uint32_t n, uint64_t first_slot, int k, int p, const uint8_t *first_byte,
+                     const uint64_t *raw_len, void *const *bufs, uint64_t *counts, uint32_t *info)
+{
+    if (!off || !counts || !info || kind < 0 || kind > 2 || first_slot + n > 0xFFFFFFFFull) return -1;
+    info[0] = info[1] = 0;
+    void *const none[4] = {nullptr, nullptr, nullptr, nullptr};
+    if (!bufs) bufs = none;
+    bool fits = true;
+    if (kind == 2) {
+        // (a genome's region may end before the next begins for the planner, which refuses it: no monotone check in front)
+        if (!raw_len || !first_byte) return -1;
+        uint64_t hi = 0;
+        for (uint32_t g = 0; g <= n; ++g) hi = std::max(hi, off[g]);
+        if (hi >= (1ull << 28)) return -1;  // the raw buffer is made here
+        std::vector<uint8_t> raw(hi + 1, 0);
+        for (uint32_t g = 0; g < n; ++g) raw[off[g]] = first_byte[g];
+        std::vector<FastxGenome> gen;
+        std::vector<FastxChunk> chunks;
+        const int rc = plan_fastx(raw.data(), off, raw_len, n, gen, chunks, &info[0]);
+        if (rc) return rc;
+        info[0] = 0;
+        fits = hand_back(gen, bufs[0], counts[0]);
+        fits = hand_back(chunks, bufs[1], counts[1]) && fits;
+        counts[2] = counts[3] = 0;
+        return fits ? 0 : -2;
+    }
+    for (uint32_t g = 0; g < n; ++g)
+        if (off[g + 1] < off[g]) return -1;
+    std::vector<SketchWork> work;
+    if (kind == 0) {
+        plan_genomes(off, n, first_slot, k, p, work);
+        fits = hand_back(work, bufs[0], counts[0]);
+        counts[1] = counts[2] = counts[3] = 0;
+        return fits ? 0 : -2;
+    }
+    std::vector<RecRun> runs;
+    std::vector<RecSeg> segs;
+    std::vector<uint32_t> zero;
+    info[1] = plan_records(off, n, first_slot, k, p, runs, segs, zero, work) ? 1 : 0;
+    fits = hand_back(runs, bufs[0], counts[0]);
+    fits = hand_back(segs, bufs[1], counts[1]) && fits;
+    fits = hand_back(zero, bufs[2], counts[2]) && fits;
+    fits = hand_back(work, bufs[3], counts[3]) && fits;
+    return fits ? 0 : -2;
 }
 
 }  // extern "C"

@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "consts.h"
+#include "sketch_plan.h"
 
 namespace dsh {
 
@@ -370,50 +371,17 @@ hipError_t launch_union_groups(hipStream_t st, const uint8_t *src, int p, const 
 // in-order upload of a small page-locked host buffer by a kernel (no runtime copy on the ctx stream)
 hipError_t launch_upload(hipStream_t st, void *dst, const void *src_pinned, size_t bytes);
 
-// sketch path
-struct SketchWork {
-    uint64_t gbeg;   // absolute offset of the genome's first base in the device seq buffer
-    uint64_t gend;   // one past its last base
-    uint64_t start;  // absolute, 32-aligned offset of this workgroup's first base
-    uint32_t nsub;   // number of 8192-base sub-chunks this workgroup walks
-    uint32_t slot;   // row of the resident sketch matrix
-};
+// sketch path: the lists the host fills (SketchWork, RecRun, RecSeg, FastxChunk, FastxGenome) are sketch_plan.h's
 hipError_t launch_sketch(hipStream_t st, const uint8_t *seq, const SketchWork *work,
                          uint32_t nwork, int k, int p, int canon, uint8_t *regs);
-
-// per-record sketches (dsh_sketch_records, k_sketch_records): a run is a stretch of whole, consecutive records that one
-// workgroup owns -- their bases lie in [base, base + span) with span <= kRecRunSpan, their rows are slots
-// [slot0, slot0 + nrec).  The records with at least one base are the run's segments: segs[seg0 + i] = {start of
-// segment i relative to base, its slot relative to slot0}, starts strictly increasing, nseg <= kRecRunSegs.
-constexpr uint32_t kRecRunSpan = 8192;  // bases of a run, counted from its 32-aligned base (256 lanes x 32)
-constexpr uint32_t kRecRunSegs = 256;   // segments of a run (a k-mer's entry keeps its segment in 8 bits at p = 17)
-constexpr uint32_t kRecRunRecs = 4096;  // records of a run, empty ones included
-constexpr int kMaxPRecords = 17;        // largest p the records kernel takes (above: k_sketch's GLOBAL variant)
-struct RecRun {
-    uint64_t base;   // absolute, 32-aligned offset of the run's first base in the device seq buffer
-    uint32_t seg0, nseg;
-    uint32_t slot0, nrec;
-    uint32_t span;   // end of the run's last base, relative to base
-    uint32_t pad_;
-};
+// per-record sketches (k_sketch_records): a workgroup per run; segs holds the planner's RecSeg entries
+static_assert(sizeof(RecSeg) == sizeof(uint2) && alignof(RecSeg) <= alignof(uint2), "k_sketch_records reads a RecSeg as a uint2");
 hipError_t launch_sketch_records(hipStream_t st, const uint8_t *seq, const RecRun *runs, uint32_t nruns, const uint2 *segs,
                                  int k, int p, int canon, uint8_t *regs);
 // zero the rows slots[0 .. nslots) of the matrix (2^p bytes each)
 hipError_t launch_zero_rows(hipStream_t st, const uint32_t *slots, uint32_t nslots, int p, uint8_t *regs);
 
-// FASTA text -> clean base stream on the device (kernels_fastx.hip).  A genome's raw file bytes lie at [off, off + rawlen)
-// of the raw buffer (off 32-aligned) and are decoded to the same offset of the output buffer, the rest of the region up to
-// region_end filled with 'N'; a chunk is what one workgroup takes (begin 32-aligned, len <= kFastxChunk).
-constexpr uint32_t kFastxChunk = 16384;
-struct FastxChunk {
-    uint64_t begin;
-    uint32_t len, genome;
-};
-struct FastxGenome {
-    uint64_t off, rawlen, region_end;
-    uint32_t chunk0, nchunks;
-    uint32_t fmt, pad_;  // 0: FASTA (begins with '>'), 1: FASTQ in strict four-line records (begins with '@')
-};
+// FASTA text -> clean base stream on the device (kernels_fastx.hip)
 struct FastxSumm {  // what a chunk tells the per-genome scan (kernels_fastx.hip, k_fastx_scan)
     uint32_t fn, bad8;
     uint32_t a[4], b[4];

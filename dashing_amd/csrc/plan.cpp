@@ -1317,6 +1317,48 @@ uint64_t band_item_count(const Tuning &tu, const PairPlan &pp, size_t bi)
     return cnt - over + over * f;
 }
 
+// cost model for balancing shards: a tile costs its dense planes plus ~5 plane-equivalents of
+// finalize work (6.6 ms finalize vs 1.4 ms per plane on the C3 workload, profiles/r1f)
+constexpr double kShardC0 = 5.0;           // finalize work of a tile in plane-equivalents
+constexpr double kAssemblerPermille = 21;  // the un-permute (0.42 ms) on rank 0 of a 19.9 ms pass (profiles/r1k)
+void shard_bounds(const Layout &L, uint32_t nshards, std::vector<uint32_t> &tb)
+{
+    const uint32_t NT = L.Npad / kTile;
+    std::vector<double> rowcost(NT, 0.);
+    double total = 0;
+    for (uint32_t ti = 0; ti < NT; ++ti) {
+        for (uint32_t tj = ti; tj < NT; ++tj) {
+            int pb, pe;
+            tile_planes(L, ti, tj, pb, pe);
+            rowcost[ti] += (pe - pb) + kShardC0;
+        }
+        total += rowcost[ti];
+    }
+    // Contiguous tile-row ranges that minimise the largest shard (linear partition by bisection on the
+    // limit + greedy fill).  Shard 0 belongs to the rank that also assembles the result (the un-permute,
+    // about assembler_permille/1000 of a single-GPU pass): it carries that as extra cost.
+    const double extra0 = nshards > 1 ? total * kAssemblerPermille / 1000.0 : 0.0;
+    auto fill = [&](double limit, std::vector<uint32_t> *out) -> bool {
+        uint32_t ti = 0;
+        for (uint32_t r = 0; r < nshards; ++r) {
+            double acc = r == 0 ? extra0 : 0.0;
+            if (out) (*out)[r] = ti;
+            while (ti < NT && acc + rowcost[ti] <= limit) acc += rowcost[ti++];
+        }
+        if (out) (*out)[nshards] = NT;
+        return ti == NT;
+    };
+    double lo = 0, hi = total + extra0;
+    for (uint32_t ti = 0; ti < NT; ++ti) lo = std::max(lo, rowcost[ti]);  // a shard holds whole tile rows
+    for (int it = 0; it < 60 && hi - lo > 1e-9 * (hi + 1); ++it) {
+        const double mid = 0.5 * (lo + hi);
+        if (fill(mid, nullptr)) hi = mid;
+        else lo = mid;
+    }
+    tb.assign(nshards + 1, NT);
+    fill(hi, &tb);  // (the greedy fill front-loads: later shards may be lighter, the maximum is what counts)
+}
+
 }  // namespace plan
 }  // namespace dsh
 

@@ -213,6 +213,12 @@ inline void tile_planes(const Layout &L, uint32_t ti, uint32_t tj, int &pb, int 
     tile_planes(L.blk_lo[ti], L.blk_L[ti], L.blk_T[ti], L.blk_lo[tj], L.blk_L[tj], L.blk_T[tj], L.pbase, pb, pe);
 }
 
+// shards of the whole sorted triangle (dsh_shard_plan, dsh_dist_shard_device, dsh_unpermute_*): tb[nshards + 1], shard r
+// holds the tile rows [tb[r], tb[r + 1]) -- contiguous ranges that balance the tiles' cost (plan.cpp)
+void shard_bounds(const Layout &L, uint32_t nshards, std::vector<uint32_t> &tb);
+// the first row of shard r (r = nshards: the end of the last) among the n rows of the layout
+inline uint64_t shard_row(const std::vector<uint32_t> &tb, uint32_t r, uint64_t n) { return std::min<uint64_t>(n, (uint64_t)tb[r] * kTile); }
+
 // ---- the pair plan ------------------------------------------------------------------------------------------------------
 struct PairQuery {
     int rect = 0;          // rows x columns rectangle (identity layout) instead of triangle rows

@@ -110,7 +110,10 @@ int dsh_attach_device_sketches(dsh_ctx *ctx, const void *d_regs, uint64_t n, int
  * Canonical k-mers iff canon != 0 (-C clears it, src/distmain.cpp:65).  k in [1,32].
  * Registers go to slots [first_slot, first_slot+n_genomes) of the resident matrix (max-merged
  * into what is there, so a genome may be fed in several calls) and, if regs_out != NULL, are
- * also copied to the host.  Bit-exact with the CPU definition (max is order-independent). */
+ * also copied to the host.  Bit-exact with the CPU definition (max is order-independent).
+ * Errors of every sketch entry point, returned before anything is enqueued: DSH_EINVAL for offsets
+ * that decrease, a k outside [1,32], slots out of range or beyond 2^32 (the work lists keep a slot
+ * in 32 bits); DSH_ESTATE before dsh_sketches_alloc. */
 int dsh_sketch_batch(dsh_ctx *ctx, const uint8_t *seq, const uint64_t *genome_off,
                      uint32_t n_genomes, uint64_t first_slot, int k, int canon,
                      uint8_t *regs_out);

@@ -224,6 +224,58 @@ def test_async_batches_from_pinned_staging(ctx, oracle):
     assert (ctx.download() == want).all()
 
 
+@pytest.mark.parametrize("p", [10, 14])
+@pytest.mark.parametrize("records", [False, True])
+def test_three_forms_agree(ctx, oracle, p, records):
+    """The blocking call, the _async call from page-locked memory + wait() and the _device call write identical rows, the
+    oracle's, for batches and for records.  The host forms start at offset 13 of the caller's sequence (the staged span is
+    shifted to keep its place within 32 bytes); the rows are slots 2 ..., between neighbours whose registers must survive."""
+    import torch
+
+    from test_gpu_records import EDGE
+
+    rng = np.random.default_rng(10 * p + records)
+    lens = EDGE + [9000] if records else [0, 30, 31, 8193, 16 * 8192 + 5]
+    n, first, lead, k = len(lens), 2, 13, 31
+    seq = np.frombuffer(b"ACGT", np.uint8)[rng.integers(0, 4, lead + sum(lens))]
+    seq[rng.integers(0, seq.size, 20)] = ord("N")
+    off = np.zeros(n + 1, np.uint64)
+    off[1:] = np.cumsum(lens)
+    off += np.uint64(lead)
+    want = oracle.sketch_batch(seq, off, k, p, True)
+    before = rng.integers(0, 64 - p + 2, (n + 4, 1 << p)).astype(np.uint8)
+    kind = "records" if records else "batch"
+
+    def reset():
+        ctx.upload(before)
+        if not records:  # a batch is max-merged into its rows
+            ctx.clear(first, n)
+
+    def check(form):
+        whole = ctx.download()
+        assert (whole[first:first + n] == want).all(), form
+        assert (whole[:first] == before[:first]).all() and (whole[first + n:] == before[first + n:]).all(), form
+
+    ctx.alloc(n + 4, p)
+    reset()
+    got = getattr(ctx, "sketch_" + kind)(seq, off, first, k, True)
+    assert (got == want).all()
+    check("blocking")
+    pin = dashing_amd.PinnedArray(seq.size, np.uint8)
+    pin.array[:] = seq
+    reset()
+    getattr(ctx, "sketch_%s_async" % kind)(pin.array, off, first, k, True)
+    ctx.wait()
+    check("async")
+    dseq, doff = synth.concat_for_device([seq[int(off[i]):int(off[i + 1])] for i in range(n)])
+    d = torch.zeros(dseq.size + 256, dtype=torch.uint8, device="cuda")
+    d[: dseq.size] = torch.from_numpy(dseq).to("cuda")
+    torch.cuda.synchronize()
+    reset()
+    getattr(ctx, "sketch_%s_device" % kind)(d.data_ptr(), doff, first, k, True)
+    check("device")
+
+
 def test_preload_loads_the_code_objects_without_a_context():
     """dsh_preload: no context, any thread; unknown bits are ignored, a device that does not exist is refused"""
     lib = dashing_amd.load_library()
