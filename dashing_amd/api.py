@@ -18,6 +18,7 @@ SYMMETRIC_CONTAINMENT_INDEX, SYMMETRIC_CONTAINMENT_DIST = 7, 8
 GREEDY_FIRST, GREEDY_BEST = 0, 1  # assign_mode of dsh_greedy_extend* and dsh_dbscan_*
 DBSCAN_NOISE, DBSCAN_BORDER, DBSCAN_CORE = 0, 1, 2  # DSH_DBSCAN_*: kind[] of dsh_dbscan_*
 HIST_MAX_EDGES = 4096  # DSH_HIST_MAX_EDGES: the edges of one dsh_dist_histogram* call
+CURVE_BINS = 64  # DSH_CURVE_BINS: the bins of a prefix's register histogram (union_curve)
 LINKAGE_SINGLE, LINKAGE_COMPLETE, LINKAGE_AVERAGE = 0, 1, 2  # DSH_LINKAGE_*
 STATS_FRAC_BITS = 30  # DSH_STATS_FRAC_BITS: sums of dsh_group_stats* are in units of 2^-30
 # the measures for which a larger value is better (the others are the *_DIST forms; SIZES has no order)
@@ -49,6 +50,7 @@ SYMBOLS = [
     "dsh_linkage_threshold", "dsh_linkage_threshold_device", "dsh_linkage_tri",
     "dsh_mst", "dsh_mst_tri", "dsh_mst_linkage",
     "dsh_dbscan_threshold", "dsh_dbscan_threshold_device", "dsh_dbscan_tri", "dsh_degree_threshold", "dsh_degree_threshold_device",
+    "dsh_union_curve", "dsh_union_curve_device", "dsh_curve_permutations",
     "dsh_fold", "dsh_fold_device", "dsh_upload_sketches_folded", "dsh_upload_sketches_folded_device", "dsh_union_groups", "dsh_union_groups_device", "dsh_shard_plan", "dsh_dist_shard_device", "dsh_unpermute_device", "dsh_unpermute_staged_device", "dsh_unpermute_blocks_device", "dsh_tri_span", "dsh_tri_index", "dsh_partition_rows", "dsh_balance_rows", "dsh_balance_rowsets", "dsh_rowsets_from_bounds", "dsh_rowsets_rank", "dsh_alloc_host", "dsh_free_host",
     "dsh_set_profiling", "dsh_last_kernel_ms", "dsh_last_part_info", "dsh_finalize_phase_cycles", "dsh_set_option", "dsh_get_info", "dsh_stream",
 ]
@@ -202,7 +204,9 @@ def load_library():
                        ("dsh_dbscan_threshold_device", [vp, i32, i32, i32, C.c_float, C.c_uint32, i32, vp, vp, vp, C.POINTER(u64), C.POINTER(u64)]),
                        ("dsh_dbscan_tri", [vp, u64, vp, i32, C.c_float, C.c_uint32, i32, vp, vp, vp, C.POINTER(u64), C.POINTER(u64)]),
                        ("dsh_degree_threshold", [vp, i32, i32, i32, C.c_float, vp]),
-                       ("dsh_degree_threshold_device", [vp, i32, i32, i32, C.c_float, vp])):
+                       ("dsh_degree_threshold_device", [vp, i32, i32, i32, C.c_float, vp]),
+                       ("dsh_union_curve", [vp, i32, vp, u64, u64, vp, vp]), ("dsh_union_curve_device", [vp, i32, vp, u64, u64, vp, vp]),
+                       ("dsh_curve_permutations", [u64, u64, u64, vp])):
         fn = getattr(lib, name, None)
         if fn is not None:
             fn.argtypes = args
@@ -394,6 +398,19 @@ def histogram_hits(counts, result_type):
     return np.cumsum(body[..., ::-1], axis=-1, dtype=np.uint64)[..., ::-1][..., 1:]
 
 
+def curve_permutations(n, n_perm, seed):
+    """uint32 [n_perm][n]: the permutations of 0 .. n - 1 that dsh_curve_permutations draws (a pure function of n, seed
+    and the row: the CLI's --curve-permutations orders)"""
+    fn = getattr(load_library(), "dsh_curve_permutations", None)
+    if fn is None:
+        raise DshError(-22, "%s does not export dsh_curve_permutations: rebuild it" % lib_path())
+    out = np.zeros((int(n_perm), int(n)), np.uint32)
+    rc = fn(int(n), int(n_perm), int(seed) & 0xFFFFFFFFFFFFFFFF, out.ctypes.data)
+    if rc:
+        raise DshError(rc, "dsh_curve_permutations(n=%d, n_perm=%d)" % (n, n_perm))
+    return out
+
+
 def mst_linkage(n, lhs, rhs, val):
     """(za, zb, zv, zsize): the sorted edge list of Context.mst / mst_tri as a merge table in scipy's Z convention -- leaves
     0 .. n - 1, step s joins the current clusters of lhs[s] and rhs[s] into cluster n + s; za < zb.  Pure host."""
@@ -566,6 +583,26 @@ class Context:
     def union_groups_device(self, out_ptr, group_ptr, members):
         gp, mem = self._groups(group_ptr, members)
         self._ck(self._derive("dsh_union_groups_device")(self._h, gp.ctypes.data, mem.ctypes.data, gp.size - 1, C.c_void_p(out_ptr)))
+
+    # ---- union growth curves
+    def union_curve(self, orders, estim=ESTIM_ERTL_MLE, want_hist=False):
+        """float64 [n_orders][len]: entry [o][i] = the estimate of the union of the resident rows orders[o][0 .. i]; with
+        want_hist also uint32 [n_orders][len][64], the register histograms of those unions.  A 1-D order gives 1-D results."""
+        ords = np.ascontiguousarray(orders, np.uint32)
+        assert ords.ndim in (1, 2)
+        flat = ords.reshape(1, -1) if ords.ndim == 1 else ords
+        n_orders, length = flat.shape
+        card = np.zeros((n_orders, length), np.float64)
+        hist = np.zeros((n_orders, length, CURVE_BINS), np.uint32) if want_hist else None
+        self._ck(self._derive("dsh_union_curve")(self._h, estim, flat.ctypes.data, length, n_orders, card.ctypes.data,
+                                                 hist.ctypes.data if want_hist else None))
+        if ords.ndim == 1:
+            card, hist = card[0], (hist[0] if want_hist else None)
+        return (card, hist) if want_hist else card
+
+    def union_curve_device(self, orders_ptr, length, n_orders, card_ptr, hist_ptr=None, estim=ESTIM_ERTL_MLE):
+        self._ck(self._derive("dsh_union_curve_device")(self._h, estim, C.c_void_p(orders_ptr), length, n_orders, C.c_void_p(card_ptr),
+                                                        C.c_void_p(hist_ptr) if hist_ptr else None))
 
     # ---- sketch waist
     def sketch_batch(self, seq, genome_off, first_slot=0, k=31, canon=True, want_regs=True):

@@ -636,6 +636,8 @@ static const IntOption kIntOptions[] = {
     {"linkage_lds_max", 0, 6144, "must be in [0, 6144]", OPT_TO(lk.lds_max, uint32_t)},
     {"greedy_band_rows", 1, kGreedyMaxRows, "must be in [1, 8192]", OPT_TO(gr.band_rows, uint64_t)},
     {"derive_chunk_bytes", 1, INT64_MAX, "must be at least 1", OPT_TO(derive.chunk_bytes, uint64_t)},
+    {"curve_segment", 0, INT64_MAX, "must be >= 0 (0 = the planner's)", OPT_TO(curve.segment, uint64_t)},
+    {"curve_scratch_bytes", 1, INT64_MAX, "must be at least 1", OPT_TO(curve.scratch_bytes, uint64_t)},
     {"sort", -1, 1, "must be -1, 0 or 1", OPT_TO(sort_mode, int)},
     {"nsplit", 0, 64, "must be in [0,64]", OPT_TO(nsplit, int)},
     {"part_band_tiles", 1, 1 << 30, "out of range", OPT_TO(part_band_tiles, int)},

@@ -18,6 +18,8 @@
 //   group_stats.hip    dsh_group_stats* (per-group statistics and medoids of a labelling)
 //   hist.hip      dsh_dist_histogram*, dsh_dist_rect_histogram (the distribution of the values over caller-given edges)
 //   derive.hip    dsh_fold*, dsh_upload_sketches_folded*, dsh_union_groups* (new sketches out of resident ones)
+//   curve.hip     dsh_union_curve*, dsh_curve_permutations (the growth of the union along orders of resident sketches)
+//   curve_plan.h  (header, no HIP types) the cut of those orders into segments and batches
 //   exchange.hip  RCCL: dsh_comm_*, dsh_collect_*, dsh_allgather_device, dsh_dist_collect
 //   plan.cpp      the pure-host planner (layout, tiles, bands, parts, work items, row partitions, shard bounds)
 // State that one of these modules uses alone is a named member struct of dsh_ctx (c->cc.parent, c->xch.comm); what the
@@ -350,6 +352,13 @@ struct dsh_ctx {
         DevBuf err, stage, ptr, mem, dst, part[2], out;
         uint64_t chunk_bytes = (uint64_t)256 << 20;  // option derive_chunk_bytes: source rows staged per step of the host forms
     } derive;
+    // dsh_union_curve* (curve.hip): the error word, the orders and the segments' bounds, and per batch the deltas, the
+    // segments' start rows, the scan's chunk sums and the counters the estimator reads; the host form's results on their way out
+    struct {
+        DevBuf err, ord, ptr, delta, start, sums, cnt, card, hist;
+        uint64_t scratch_bytes = (uint64_t)256 << 20;  // option curve_scratch_bytes: delta + start rows + counters of a batch of orders
+        uint64_t segment = 0;                          // option curve_segment: members per segment, 0 = the planner's (curve_plan.h)
+    } curve;
     // multi-GPU exchange (exchange.hip, dsh_comm_*): an RCCL communicator over the ranks' contexts (not owned here:
     // comm_release destroys it while the library is loaded)
     struct {

@@ -149,6 +149,16 @@ static void usage(const char *sub)
             "  --histogram-labels FILE  with --histogram: FILE is the -b output of --cluster or --representatives over the same\n"
             "                           inputs in the same order; every line gets two counts, the pairs inside a group and the\n"
             "                           pairs between groups (-b: two planes).\n"
+            "  --union-curve            emit how the UNION of the inputs grows as they are added one after the other, in input\n"
+            "                           order: the k-mer pangenome growth (collector's) curve, computed on the device from the\n"
+            "                           resident sketches (dsh_union_curve).  Text: '#UnionCurve<TAB>estimator<TAB>permutations=N\n"
+            "                           <TAB>seed=S', '#step<TAB>name<TAB>union_size<TAB>new[<TAB>perm_mean<TAB>perm_min<TAB>perm_max]',\n"
+            "                           then one line per input: its 1-based step, its name, the size of the union up to it and\n"
+            "                           what it added (%%.3f).  --curve-permutations N [0]: also the mean, minimum and maximum of\n"
+            "                           each step over N random orders (dsh_curve_permutations; --curve-seed S [0]).  -b: u64 n,\n"
+            "                           u64 N, f64 curve[1 + N][n]: the given order's curve, then each permutation's.  Not with\n"
+            "                           --threshold, --cluster, --representatives, --nearest-neighbors, --histogram, --mst,\n"
+            "                           --pairs, --groups, -Q, -U, -T, dist_by_seq or several devices.\n"
             "  --mst                    emit the minimum spanning tree of the pair values instead of the values: the\n"
             "                           single-linkage dendrogram, n - 1 edges that give the --cluster components at EVERY\n"
             "                           threshold (dsh_mst).  Text: '#MST<TAB>measure<TAB>n<TAB>n_edges', then\n"
@@ -199,6 +209,9 @@ struct Opts {
     bool has_hist = false;  // --histogram SPEC: the distribution of the values over the edges of SPEC (dsh_dist_histogram)
     std::vector<float> hist_edges;
     std::string hist_labels_file;  // --histogram-labels FILE: counts split into intra-group and inter-group pairs
+    bool has_curve = false;  // --union-curve [--curve-permutations N] [--curve-seed S]: the growth of the union in input order (dsh_union_curve)
+    bool has_curve_perms = false, has_curve_seed = false;
+    uint64_t curve_perms = 0, curve_seed = 0;
     std::string extend_file;  // --extend FILE: the labels of an earlier --representatives -b run over the first inputs
     std::string groups_file;  // --groups FILE: the unions of named groups are compared instead of the inputs (dsh_union_groups)
     std::string pairs_file, measures;  // --pairs FILE [--measures LIST]: only the listed pairs (dsh_dist_pairs)
@@ -314,7 +327,7 @@ static float float_option(const char *flag, const char *arg)
     return v;
 }
 
-enum { OPT_PRESKETCHED = 1000, OPT_AVOID_SORT, OPT_DEVICE, OPT_NPERBATCH, OPT_NN, OPT_NGPUS, OPT_DEVICES, OPT_RCCL, OPT_THRESHOLD, OPT_CLUSTER, OPT_LINKAGE, OPT_MIN_PTS, OPT_REPS, OPT_ASSIGN, OPT_EXTEND, OPT_STATS, OPT_HISTOGRAM, OPT_HISTOGRAM_LABELS, OPT_MST, OPT_MST_CUTOFF, OPT_DENDROGRAM, OPT_PAIRS, OPT_MEASURES, OPT_GROUPS, OPT_UNSUPPORTED };
+enum { OPT_PRESKETCHED = 1000, OPT_AVOID_SORT, OPT_DEVICE, OPT_NPERBATCH, OPT_NN, OPT_NGPUS, OPT_DEVICES, OPT_RCCL, OPT_THRESHOLD, OPT_CLUSTER, OPT_LINKAGE, OPT_MIN_PTS, OPT_REPS, OPT_ASSIGN, OPT_EXTEND, OPT_STATS, OPT_HISTOGRAM, OPT_HISTOGRAM_LABELS, OPT_UNION_CURVE, OPT_CURVE_PERMS, OPT_CURVE_SEED, OPT_MST, OPT_MST_CUTOFF, OPT_DENDROGRAM, OPT_PAIRS, OPT_MEASURES, OPT_GROUPS, OPT_UNSUPPORTED };
 
 static Opts parse(int argc, char **argv, bool is_dist)
 {
@@ -345,6 +358,8 @@ static Opts parse(int argc, char **argv, bool is_dist)
         {"assign", required_argument, nullptr, OPT_ASSIGN}, {"extend", required_argument, nullptr, OPT_EXTEND},
         {"stats", no_argument, nullptr, OPT_STATS},
         {"histogram", required_argument, nullptr, OPT_HISTOGRAM}, {"histogram-labels", required_argument, nullptr, OPT_HISTOGRAM_LABELS},
+        {"union-curve", no_argument, nullptr, OPT_UNION_CURVE}, {"curve-permutations", required_argument, nullptr, OPT_CURVE_PERMS},
+        {"curve-seed", required_argument, nullptr, OPT_CURVE_SEED},
         {"mst", no_argument, nullptr, OPT_MST}, {"mst-cutoff", required_argument, nullptr, OPT_MST_CUTOFF}, {"dendrogram", no_argument, nullptr, OPT_DENDROGRAM},
         {"pairs", required_argument, nullptr, OPT_PAIRS}, {"groups", required_argument, nullptr, OPT_GROUPS}, {"measures", required_argument, nullptr, OPT_MEASURES},
         // second arm of result_cmp (src/dashing.h:577-588); flag numbers as in DIST_LONG_OPTS
@@ -441,6 +456,16 @@ static Opts parse(int argc, char **argv, bool is_dist)
             o.has_hist = true;
             break;
         case OPT_HISTOGRAM_LABELS: o.hist_labels_file = optarg; break;
+        case OPT_UNION_CURVE: o.has_curve = true; break;
+        case OPT_CURVE_PERMS: case OPT_CURVE_SEED: {
+            const char *name = co == OPT_CURVE_PERMS ? "--curve-permutations" : "--curve-seed";
+            char *end = nullptr;
+            const unsigned long long v = std::strtoull(optarg, &end, 10);
+            if (end == optarg || *end || *optarg == '-' || (co == OPT_CURVE_PERMS && v > 0xFFFFFFFFull)) die("%s needs a count of at least 0, got '%s'", name, optarg);
+            if (co == OPT_CURVE_PERMS) o.curve_perms = v, o.has_curve_perms = true;
+            else o.curve_seed = v, o.has_curve_seed = true;
+            break;
+        }
         case OPT_PAIRS: o.pairs_file = optarg; break;
         case OPT_MEASURES: o.measures = optarg; break;
         case OPT_GROUPS: o.groups_file = optarg; break;
@@ -1252,6 +1277,23 @@ static void refuse_conflicts(const Opts &o, bool by_seq)
         if (o.fmt == FULL_TSV) die("--histogram does not go with -T: the output is one line per class.");
         if (o.devices.size() > 1 || o.rccl) die("--histogram runs on one device: --ngpus / --devices are not supported.");
     }
+    if (o.has_curve) {
+        if (by_seq) die("--union-curve does not go with dist_by_seq: the curve is that of input files.");
+        if (o.has_threshold) die("--union-curve does not go with --threshold: the curve compares no pairs.");
+        if (o.has_cluster) die("--union-curve does not go with --cluster: choose the curve or the clusters.");
+        if (o.has_reps) die("--union-curve does not go with --representatives: choose the curve or the representatives.");
+        if (o.nneighbors) die("--union-curve does not go with --nearest-neighbors: choose one selection.");
+        if (o.has_hist) die("--union-curve does not go with --histogram: choose the curve or the distribution.");
+        if (o.has_mst) die("--union-curve does not go with --mst: choose the curve or the tree.");
+        if (with_pairs) die("--union-curve does not go with --pairs: the curve compares no pairs.");
+        if (!o.groups_file.empty()) die("--union-curve does not go with --groups: the curve is that of the inputs.");
+        if (!o.querypaths.empty()) die("--union-curve does not go with -Q: the curve takes every input in turn.");
+        if (o.fmt == UPPER_TRIANGULAR) die("--union-curve does not go with -U: the output is one line per input.");
+        if (o.fmt == FULL_TSV) die("--union-curve does not go with -T: the output is one line per input.");
+        if (o.devices.size() > 1 || o.rccl) die("--union-curve runs on one device: --ngpus / --devices are not supported.");
+    }
+    if (o.has_curve_perms && !o.has_curve) die("--curve-permutations goes with --union-curve only.");
+    if (o.has_curve_seed && !o.has_curve) die("--curve-seed goes with --union-curve only.");
     if (o.has_mst) {  // (what --cluster refuses, and the other selections)
         if (o.has_cluster) die("--mst does not go with --cluster: the tree gives the clusters at every threshold.");
         if (o.has_reps) die("--mst does not go with --representatives: choose the tree or the representatives.");
@@ -1332,7 +1374,7 @@ static void order_paths(DistRun &r)
     // asymmetric measure without -Q: all references are also the queries
     // (--cluster, --representatives and --histogram take every pair once, in the triangle's orientation: no query/reference format
     // of their own making for them)
-    r.symmetric = o.has_cluster || o.has_reps || o.has_hist || o.has_mst || !(o.result_type == 4 || o.result_type == 5 || o.result_type == 6);  // src/dashing.h:389-399
+    r.symmetric = o.has_cluster || o.has_reps || o.has_hist || o.has_mst || o.has_curve || !(o.result_type == 4 || o.result_type == 5 || o.result_type == 6);  // src/dashing.h:389-399
     if (o.querypaths.empty() && !r.symmetric && o.pairs_file.empty() && o.groups_file.empty()) {  // (a pair list names its own pairs, each in one orientation; the groups take their turn in union_groups)
         o.querypaths = o.inpaths;
         std::fprintf(stderr, "Note: No query files provided, but an asymmetric distance was requested. Switching to a query/reference format with all references as queries.\n");
@@ -1765,6 +1807,41 @@ static void emit_histogram(const DistRun &r, std::FILE *fp)
     }
 }
 
+// --union-curve: the size of the union of the first i + 1 inputs for every i (dsh_union_curve), and with --curve-permutations N
+// the mean (summed in the permutations' order, divided once), minimum and maximum of every step over the N orders of
+// dsh_curve_permutations(n, N, seed)
+static void emit_union_curve(const DistRun &r, std::FILE *fp)
+{
+    static const char *const kEstimNames[3] = {"ORIGINAL", "ERTL_IMPROVED", "ERTL_MLE"};
+    const Opts &o = r.o;
+    const uint64_t n = r.n, N = o.curve_perms;
+    std::vector<uint32_t> orders((1 + N) * n);
+    for (uint64_t i = 0; i < n; ++i) orders[i] = (uint32_t)i;
+    if (dsh_curve_permutations(n, N, o.curve_seed, orders.data() + n) != DSH_OK) die("--curve-permutations: %llu inputs are too many", (unsigned long long)n);
+    std::vector<double> card((1 + N) * n);
+    DSH(r.ctx, dsh_union_curve(r.ctx, o.estim, orders.data(), n, 1 + N, card.data(), nullptr));
+    if (o.fmt == BINARY) {
+        const uint64_t hdr[2] = {n, N};
+        if (std::fwrite(hdr, sizeof(uint64_t), 2, fp) != 2 || std::fwrite(card.data(), sizeof(double), card.size(), fp) != card.size())
+            die("Error writing to binary file");
+        return;
+    }
+    std::fprintf(fp, "#UnionCurve\t%s\tpermutations=%llu\tseed=%llu\n", kEstimNames[o.estim], (unsigned long long)N, (unsigned long long)o.curve_seed);
+    std::fprintf(fp, "#step\tname\tunion_size\tnew%s\n", N ? "\tperm_mean\tperm_min\tperm_max" : "");
+    for (uint64_t i = 0; i < n; ++i) {
+        std::fprintf(fp, "%llu\t%s\t%.3f\t%.3f", (unsigned long long)(i + 1), o.inpaths[i].c_str(), card[i], i ? card[i] - card[i - 1] : card[i]);
+        if (N) {
+            double sum = 0, lo = card[n + i], hi = card[n + i];
+            for (uint64_t q = 0; q < N; ++q) {
+                const double v = card[(1 + q) * n + i];
+                sum += v, lo = std::min(lo, v), hi = std::max(hi, v);
+            }
+            std::fprintf(fp, "\t%.3f\t%.3f\t%.3f", sum / (double)N, lo, hi);
+        }
+        std::fputc('\n', fp);
+    }
+}
+
 // --threshold: only the pairs that pass (dsh_dist_threshold / dsh_dist_rect_threshold): no dense matrix
 static void emit_threshold(const DistRun &r, std::FILE *fp)
 {
@@ -2019,6 +2096,7 @@ static int dist_main(int argc, char **argv, bool by_seq = false)
     else if (o.has_cluster && o.has_min_pts) emit_dbscan(r, pairofp);
     else if (o.has_cluster || o.has_reps) emit_labelling(r, pairofp);
     else if (o.has_hist) emit_histogram(r, pairofp);
+    else if (o.has_curve) emit_union_curve(r, pairofp);
     else if (o.has_mst) emit_mst(r, pairofp);
     else if (o.has_threshold) emit_threshold(r, pairofp);
     else if (o.nneighbors) emit_nearest_neighbors(r, pairofp);

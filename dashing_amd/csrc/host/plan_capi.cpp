@@ -4,7 +4,7 @@
 // (tests/test_plan.py).  Also the sequential build of the clusters' union-find (dsh_plan_uf_labels, at the end) and the band rule of
 // the greedy representatives (dshh_greedy_bands) and the band walk all five band consumers share (dshh_threshold_bands), and the
 // sequential build of the linkage clusters (dsh_plan_linkage_labels, dsh_plan_linkage_loose: ../linkage.h), and the sketch
-// path's planners (dshh_sketch_plan: ../sketch_plan.h).  Built into libdashing_host.so; not part of the GPU C-ABI.
+// path's planners (dshh_sketch_plan: ../sketch_plan.h), and the union curve's (dshh_curve_plan: ../curve_plan.h).  Built into libdashing_host.so; not part of the GPU C-ABI.
 #include <algorithm>
 #include <cstdarg>
 #include <cstdio>
@@ -1079,6 +1079,26 @@ int dshh_sketch_plan(int kind, const uint64_t *off, uint32_t n, uint64_t first_s
     fits = hand_back(zero, bufs[2], counts[2]) && fits;
     fits = hand_back(work, bufs[3], counts[3]) && fits;
     return fits ? 0 : -2;
+}
+
+}  // extern "C"
+
+#include "../curve_plan.h"
+
+extern "C" {
+
+// the planner of dsh_union_curve* (../curve_plan.h) as curve.hip runs it (tests/test_curve_plan.py).  info[5] = S, segments per
+// order, orders per batch, scratch bytes of one order, scratch bytes of a batch.  bounds (or NULL) has room for `cap` words and
+// gets the segments' begins and the end of the order: nseg + 1 words.  Returns 0, -1 for unusable arguments, -2 for a buffer too small.
+int dshh_curve_plan(uint64_t n_orders, uint64_t len, int p, uint64_t budget, uint64_t forced_S, uint64_t *info, uint64_t *bounds, uint64_t cap)
+{
+    if (!info || p < 4 || p > 24) return -1;
+    const dsh::curve::Plan pl = dsh::curve::plan(n_orders, len, p, budget, forced_S);
+    info[0] = pl.S, info[1] = pl.nseg, info[2] = pl.batch, info[3] = pl.order_bytes, info[4] = pl.scratch_bytes();
+    if (!bounds) return 0;
+    if (cap < pl.nseg + 1) return -2;
+    for (uint64_t s = 0; s <= pl.nseg; ++s) bounds[s] = pl.begin(s, len);
+    return 0;
 }
 
 }  // extern "C"

@@ -368,6 +368,22 @@ hipError_t launch_fold(hipStream_t st, const uint8_t *src, uint64_t n, int ps, i
 hipError_t launch_union_groups(hipStream_t st, const uint8_t *src, int p, const uint64_t *ptr, const uint32_t *mem,
                                const uint32_t *dst, uint64_t nv, uint8_t *out_a, uint8_t *out_b);
 
+// union growth curves (kernels_curve.hip, curve.hip); the cut into segments and batches is curve_plan.h's
+constexpr int kCurveLoadsInFlight = 4;     // rows whose loads a lane of k_curve_walk has in flight
+constexpr uint32_t kCurveScanChunk = 128;  // steps per chunk of k_curve_scan* (curve_plan.h: kScanChunk)
+// the `orders` orders ord[o * len + j] (slots below n; others are skipped), each cut into nseg segments of S members:
+// delta[o * len + j][64] (int32, zeroed by the caller) gets -1 at the bin a register leaves and +1 at the bin it reaches at
+// step j.  start (nseg > 1): row o * nseg + s = the union of the members in front of segment s (launch_curve_starts).
+// *err (device, starts at ~0) = min over the members that hold a register above 64 - p + 1.
+hipError_t launch_curve_walk(hipStream_t st, const uint8_t *regs, uint64_t n, int p, const uint32_t *ord, uint64_t len, uint64_t S,
+                             uint64_t nseg, uint64_t orders, const uint8_t *start, int *delta, unsigned long long *err);
+// rows o * nseg + s of start, s = 0 .. nseg - 1: the segments' unions on entry, the unions of the segments in front of each on exit
+hipError_t launch_curve_starts(hipStream_t st, uint8_t *start, int p, uint64_t nseg, uint64_t orders);
+// cnt[o * len + i][64] = the histogram of the union of the first i + 1 members of order o: 2^p in bin 0 plus the deltas up to
+// step i, in launch_pairs_card's layout (uint16 for p <= kPairsMaxP16, uint32 above); the same as uint32 to hist where not
+// null.  sums: scratch, [orders * ceil(len / kCurveScanChunk)][64] int32 (not read where that is one chunk per order).
+hipError_t launch_curve_scan(hipStream_t st, const int *delta, int *sums, uint64_t len, uint64_t orders, int p, void *cnt, uint32_t *hist);
+
 // in-order upload of a small page-locked host buffer by a kernel (no runtime copy on the ctx stream)
 hipError_t launch_upload(hipStream_t st, void *dst, const void *src_pinned, size_t bytes);
 

@@ -65,7 +65,8 @@ typedef struct dsh_ctx dsh_ctx;
  * dsh_cluster_csr, dsh_greedy_threshold, dsh_greedy_threshold_device, dsh_greedy_extend, dsh_greedy_extend_device,
  * dsh_group_stats, dsh_group_stats_device, dsh_dist_histogram, dsh_dist_histogram_device, dsh_dist_rect_histogram,
  * dsh_linkage_threshold, dsh_linkage_threshold_device, dsh_linkage_tri, dsh_mst, dsh_mst_tri, dsh_mst_linkage,
- * dsh_dbscan_threshold, dsh_dbscan_threshold_device, dsh_dbscan_tri, dsh_degree_threshold, dsh_degree_threshold_device. */
+ * dsh_dbscan_threshold, dsh_dbscan_threshold_device, dsh_dbscan_tri, dsh_degree_threshold, dsh_degree_threshold_device,
+ * dsh_union_curve, dsh_union_curve_device, dsh_curve_permutations. */
 #define DSH_ABI_VERSION 7
 int dsh_abi_version(void);
 
@@ -361,6 +362,56 @@ int dsh_upload_sketches_folded_device(dsh_ctx *ctx, const void *d_regs, int src_
 /* out[g] = max over members[group_ptr[g] .. group_ptr[g+1]) of the resident rows; group_ptr, members on the HOST */
 int dsh_union_groups(dsh_ctx *ctx, const uint64_t *group_ptr, const uint32_t *members, uint64_t n_groups, uint8_t *regs_out);
 int dsh_union_groups_device(dsh_ctx *ctx, const uint64_t *group_ptr, const uint32_t *members, uint64_t n_groups, void *d_out);
+
+/* ---- union growth curves: how the union grows along an order of resident sketches ---------------------
+ * The k-mer pangenome growth (collector's) curve: the cardinality of the union of the first i + 1 sketches of an order,
+ * for every i, and over many orders (permutations) its mean and spread.  The registers of that union are the running
+ * byte-wise maximum along the order and the cardinality is the estimator on that row's histogram, so the curve is exact
+ * for the HLLs that are resident; a register moves about ln(len) times, so the per-prefix histograms are the prefix sums
+ * of a sparse stream of "moved from bin a to bin b at step i" events and every order reads every row ONCE.
+ *   Orders.  orders is row-major uint32 [n_orders][len]; every entry is a slot < n.  Repeats are legal: a repeated slot
+ *     changes nothing.  HOST memory in dsh_union_curve, DEVICE memory in dsh_union_curve_device.
+ *   Outputs.  card_out[o * len + i] (float64) is the `estim` estimate (DSH_ESTIM_ORIGINAL, _ERTL_IMPROVED, _ERTL_MLE) of the
+ *     union of the sketches orders[o][0 .. i], computed by the estimator kernel of dsh_dist_pairs from the prefix's
+ *     histogram: two prefixes with equal histograms carry bit-identical doubles.  hist_out / d_hist may be NULL; otherwise
+ *     it is uint32 [n_orders][len][DSH_CURVE_BINS]: bin v = the number of registers of that union holding v; every prefix's
+ *     histogram sums to 2^p.  Exactly n_orders * len doubles and n_orders * len * 64 uint32 are written, nothing else.
+ *     d_card is 8-byte, d_hist 4-byte aligned device memory.
+ *   len == 0 or n_orders == 0 returns DSH_OK, writes nothing and launches nothing.
+ *   Errors.  DSH_EINVAL: a NULL context, a bad estim, a NULL orders / card pointer; an entry >= n (the message names the
+ *     order and the position); a NAMED sketch that holds a register above 64 - p + 1 (the message names the smallest such
+ *     slot, in the words of dsh_dist_pairs) -- a sketch no order names is not judged.  DSH_ESTATE without resident
+ *     sketches.  DSH_ENOMEM, with a message, when scratch cannot be allocated: never a partial result.  The entries are
+ *     validated on the host before any launch (the device form copies them back for that: 4 bytes per step).  On an error
+ *     dsh_union_curve leaves card_out / hist_out untouched; dsh_union_curve_device leaves unspecified contents but never
+ *     writes outside the caller's spans.
+ *   State.  Reads the resident rows, owned or attached; neither reads nor invalidates the compare path's derived state
+ *     (a dense call before and after gives the same bytes).  A dsh_upload_sketches between two calls is seen by the second.
+ *   Execution.  Synchronous, on the ctx stream; one wait for the device at the end.  Orders run in batches whose deltas
+ *     (256 bytes per step), counters (128, above p = 15 256) and segment start rows stay within "curve_scratch_bytes"
+ *     (option, default 256 MiB; one order alone that needs more grows the scratch to that).  A long order is cut into
+ *     segments of "curve_segment" members (option; 0 = the planner's choice, about 2048 workgroups per launch and no
+ *     segment below 64 members) whose unions come from the kernel of dsh_union_groups, so that one order fills the
+ *     device.  No result depends on either option.  The host form also holds the orders (4 bytes per step), the
+ *     cardinalities (8) and one batch's histograms on the device, and with several batches the histograms in host memory
+ *     of its own until the call is known to succeed.
+ *   Cost model: (1 or 2) x n_orders x len x 2^p bytes of rows (2 with segments), plus n_orders x len x 256
+ *     bytes of deltas written and read once.  Measured on one MI355X (tools/bench_curve.py, profiles/curve1): 10 000 x p=14
+ *     one order 0.28 ms, 100 permutations 6.1 ms (device copies of the same rows: 7.3 ms); 100 000 x p=10 one order 0.74 ms,
+ *     20 permutations 4.0 ms (the copies: 0.82 ms; at p = 10 the deltas and counters are 37 % of the row bytes again).
+ *   dsh_curve_permutations writes n_perm permutations of 0 .. n - 1 as uint32 [n_perm][n]; pure host, a pure function of
+ *     (n, seed, r).  Permutation r runs splitmix64 from the state x = seed + r (wrapping); next() is x += 0x9E3779B97F4A7C15,
+ *     z = x, z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9, z = (z ^ z >> 27) * 0x94D049BB133111EB, return z ^ z >> 31.  The shuffle is
+ *     Fisher-Yates from the identity: for i = n - 1 down to 1, swap [i] and [next() % (i + 1)].  n >= 2^32 and a NULL out
+ *     with n * n_perm > 0 give DSH_EINVAL.
+ *   Not built: a multi-GPU form, orders over a second context's rows, --groups in the CLI (curves per group), and the
+ *     greedy "largest gain next" order. */
+#define DSH_CURVE_BINS 64
+int dsh_union_curve(dsh_ctx *ctx, int estim, const uint32_t *orders, uint64_t len, uint64_t n_orders,
+                    double *card_out, uint32_t *hist_out);
+int dsh_union_curve_device(dsh_ctx *ctx, int estim, const void *d_orders, uint64_t len, uint64_t n_orders,
+                           void *d_card, void *d_hist);
+int dsh_curve_permutations(uint64_t n, uint64_t n_perm, uint64_t seed, uint32_t *out);   /* pure host */
 
 /* ---- clusters at a threshold: connected components on the device --------------------------------------
  * Replaces what a dereplication or clustering client does with the hits of dsh_dist_threshold*: build the graph whose
@@ -1046,6 +1097,9 @@ int dsh_finalize_phase_cycles(dsh_ctx *ctx, uint64_t *out16);
  *                                           per-row state in LDS, larger ones in global scratch
  *                 "derive_chunk_bytes"      the host forms of dsh_fold / dsh_upload_sketches_folded move at most this many bytes
  *                                           of source rows per step (256 MiB; at least one row)
+ *                 "curve_scratch_bytes"     dsh_union_curve* runs batches of orders whose deltas, start rows and counters
+ *                                           stay within this (256 MiB; at least one order)
+ *                 "curve_segment"           members per segment of an order of dsh_union_curve*; 0 (default) = the planner's
  *   layout        "sort"                    -1 auto | 0 | 1: key-ordered plane columns (0 = identity: the slow, simple layout)
  *                 "range_sort_min_rows"     row ranges shorter than this keep the cached identity layout (default 1024)
  *                 "emax" / "elow"           caps of the listed upper / lower register tail, 0..255, -1 auto (per precision);
