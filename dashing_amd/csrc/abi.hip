@@ -598,6 +598,13 @@ int dsh_get_info(dsh_ctx *c, const char *name, int64_t *out)
     else if (!std::strcmp(name, "sparse_transposed_items")) *out = (int64_t)c->pp.transposed_items;  // ... with the lists on the column block ...
     else if (!std::strcmp(name, "sparse_slabs")) *out = (int64_t)c->pp.slabs.size();  // (block, plane) tables and lists the last dist call's items read
     else if (!std::strcmp(name, "sparse_table_slabs")) *out = (int64_t)c->pp.table_slabs;  // ... and the slabs of the last call built without lists
+    else if (!std::strcmp(name, "sparse_table_fills")) {  // table words the LDS placement staged in the last call's launches (plan.h)
+        uint64_t f = 0;
+        if (c->sparse_run_used)
+            for (const auto &rg : c->pp.band_sp_items) f += plan::sparse_table_fills(c->pp.sp_items.data() + rg.first, rg.second - rg.first, c->sparse_run_used);
+        *out = (int64_t)f;
+    }
+    else if (!std::strcmp(name, "sparse_run")) *out = c->sparse_run > 0 ? c->sparse_run : (int64_t)plan::kSparseRunDefault;  // (in effect)
     else if (!std::strcmp(name, "sparse_planes")) *out = c->sparse_planes;
     else if (!std::strcmp(name, "sparse_sided")) *out = c->sparse_sided;
     else if (!std::strcmp(name, "sparse_cap")) *out = c->sparse_cap;
@@ -621,7 +628,7 @@ struct IntOption {
     void (*set)(dsh_ctx *c, int64_t v);
 };
 #define OPT_TO(member, T) [](dsh_ctx *c, int64_t v) { c->member = (T)v; }
-static_assert(kGreedyMaxRows == 8192 && plan::kSparseCapMax == 2040, "the ranges below name these");
+static_assert(kGreedyMaxRows == 8192 && plan::kSparseCapMax == 2040 && plan::kSparseRunMax == 65536, "the ranges below name these");
 static const IntOption kIntOptions[] = {
     {"cum_budget_bytes", 1 << 20, INT64_MAX, "too small", OPT_TO(cum_budget, uint64_t)},
     {"knn_square_budget_bytes", 0, INT64_MAX, "must be >= 0", OPT_TO(knn_square_budget, uint64_t)},
@@ -646,6 +653,7 @@ static const IntOption kIntOptions[] = {
     {"sparse_planes", -1, 2, "is -1 (auto), 0 (off), 1 or 2", OPT_TO(sparse_planes, int)},  // sparse outer planes (plan.h, Tuning)
     {"sparse_sided", -1, 1, "is -1 (auto), 0 (off) or 1 (forced)", OPT_TO(sparse_sided, int)},  // the sided route (plan.h, Tuning)
     {"sparse_lds", 0, 1, "must be 0 or 1", OPT_TO(sparse_lds, int)},
+    {"sparse_run", 0, plan::kSparseRunMax, "must be in [0, 65536]", OPT_TO(sparse_run, int)},
     {"sparse_cap", 0, plan::kSparseCapMax, "must be in [0, 2040]", OPT_TO(sparse_cap, int)},
     {"xch_recv_gate", -1, 1, "is -1 (auto), 0 or 1", OPT_TO(xch.recv_gate, int)},
     {"finalize_signal", -1, 1, "is -1 (auto), 0 or 1", OPT_TO(finalize_signal, int)},

@@ -247,6 +247,8 @@ struct dsh_ctx {
     int sparse_cap = (int)dsh::plan::kSparseCapDefault;  // the longest set a routed plane may have
     int sparse_sided = -1;   // the sided route (plan.h, Tuning::sparse_sided): -1 auto, 0 off, 1 forced
     int sparse_lds = 1;      // the table of the counting kernel staged in LDS where a word of it fits (p <= 15); 0: gathered
+    int sparse_run = 0;      // items a workgroup of the LDS placement takes one behind the other (plan.h, sparse_table_fills); 0: kSparseRunDefault
+    uint32_t sparse_run_used = 0;  // the run of the last call's launches of the LDS placement; 0: it had none
     DevBuf sp_tab, sp_lists, sp_len, sp_slabs, sp_items;  // the slabs of the last call that routed planes (kernels_sparseplane.hip) and its items
     Staging st_sparse;               // slabs then sparse items on their way to the device
     std::vector<dsh::plan::U2> sp_have;  // the slabs sp_tab / sp_lists / sp_len hold ...

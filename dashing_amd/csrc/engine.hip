@@ -288,6 +288,8 @@ uint32_t sparse_list_stride(const dsh_ctx *c)
 // the table's placement: a word of it staged in LDS up to p = 15 (option sparse_lds = 0: gathered from global memory, the
 // arm the measurements compare against); at p = 16 a word is 256 KiB and the table is always gathered
 int sparse_wordmajor(const dsh_ctx *c) { return c->sparse_lds && c->p <= 15 ? 1 : 0; }
+// the items a workgroup of the LDS placement takes one behind the other (option sparse_run; 0: the measured default)
+uint32_t sparse_run_of(const dsh_ctx *c) { return c->sparse_run > 0 ? (uint32_t)c->sparse_run : plan::kSparseRunDefault; }
 uint64_t sparse_slab_bytes(const dsh_ctx *c)
 {
     return ((uint64_t)16 << c->p) + (uint64_t)kTile * sparse_list_stride(c) * sizeof(uint16_t) + kTile * sizeof(uint32_t);
@@ -481,8 +483,9 @@ int launch_sparse_items(dsh_ctx *c, size_t bi, uint64_t nslots)
     if (rg.first == rg.second) return DSH_OK;
     hipEvent_t a = c->profiling ? next_event(c) : nullptr, b = c->profiling ? next_event(c) : nullptr;
     if (a && b) (void)hipEventRecord(a, c->stream);
+    if (sparse_wordmajor(c)) c->sparse_run_used = sparse_run_of(c);
     HIPCHK(c, launch_sparse_count(c->stream, c->cum_bytes, (const uint4 *)c->sp_items.ptr + rg.first, (uint32_t)(rg.second - rg.first),
-                                  sparse_wordmajor(c), (const uint32_t *)c->sp_tab.ptr, (const uint16_t *)c->sp_lists.ptr, (const uint32_t *)c->sp_len.ptr,
+                                  sparse_run_of(c), sparse_wordmajor(c), (const uint32_t *)c->sp_tab.ptr, (const uint16_t *)c->sp_lists.ptr, (const uint32_t *)c->sp_len.ptr,
                                   sparse_list_stride(c), 1u << c->p, c->cum.ptr, nslots));
     if (a && b) {
         (void)hipEventRecord(b, c->stream);
@@ -673,6 +676,7 @@ int run_pairs(dsh_ctx *c, const PairJob &job)
     }
     r.fin = finalize_invariants(c, job, jl.with_extra);
     c->ev_sparse.clear();
+    c->sparse_run_used = 0;
     if (!pp.sp_items.empty() && (rc = prepare_sparse(c))) return rc;
     for (size_t bi = 0; bi < pp.bands.size(); ++bi) {
         const uint64_t nslots = (uint64_t)(pp.bands[bi].second - pp.bands[bi].first) * kTile * kTile;

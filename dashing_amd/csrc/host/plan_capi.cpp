@@ -851,6 +851,15 @@ int dshh_plan_digest(uint64_t n, const uint32_t *keys, const uint32_t *gcnt, con
     return (int)kDigestSections;
 }
 
+// the table stagings of one launch of the LDS placement of the sparse counting kernel (plan::sparse_table_fills): items4 = n
+// items of four words {tile, plane | flags << 8 (plan.h, kSpItem*), slab of the row block, slab of the column block}, in
+// launch order; run as the option sparse_run in effect (tests/test_sparse_runs_model.py)
+uint64_t dshh_sparse_table_fills(const uint32_t *items4, uint64_t n, uint32_t run)
+{
+    static_assert(sizeof(U4) == 4 * sizeof(uint32_t), "an item is four words");
+    return sparse_table_fills(reinterpret_cast<const U4 *>(items4), (size_t)n, run);
+}
+
 // first row of the second run of a row-sorted range (plan::rowsorted_split), re when the range stays one run
 uint64_t dshh_rowsorted_split(uint64_t n, uint64_t rb, uint64_t re) { return rowsorted_split(n, rb, re); }
 

@@ -20,7 +20,10 @@
 // one 16-byte piece) the kernel is bound by its gathers -- 16 scattered pieces per wave instruction; at C3 an item costs
 // 0.39 (top plane) to 0.64 (the one below) of a dense one (profiles/sparse1).  So up to p = 15 one word of the table -- 32
 // columns, 2^p x 4 bytes: 64 KiB at p = 14 -- is staged in LDS by each of FOUR workgroups per item (k_sparse_count_lds),
-// the four lanes of a row take a quarter of its list each and add their counters at the end.  At p = 16 a word is
+// the four lanes of a row take a quarter of its list each, add their counters at the end and read out eight of the
+// word's 32 columns each.  A workgroup takes a RUN of items of its XCD residue (option sparse_run, default
+// plan::kSparseRunDefault) and stages the word again only where the table slab changes; at 10 000 x p=14 the walk is 0.7 of
+// the kernel's 1.0 ms, the stagings 0.1, the read-out 0.13 (profiles/sparse3).  At p = 16 a word is
 // 256 KiB, more than a CU holds: the global placement stays, and there the sets are sparse enough for it to pay well.
 // The sided route (plan.h, Tuning::sparse_sided).  Only the LIST side has to be sparse -- the table costs the same at any
 // density -- and a set may be U(v) or A(v) = {t : a_t < v}, the plane's words as they are: a slab carries its polarity, an
@@ -31,6 +34,7 @@
 #include <stdint.h>
 
 #include <algorithm>
+#include <cstdlib>
 
 #include "kernels.h"
 #include "plan.h"
@@ -129,24 +133,28 @@ __device__ __forceinline__ void put32(uint32_t *dst, const uint32_t (&v)[32])
     for (int q = 0; q < 8; ++q) reinterpret_cast<uint4 *>(dst)[q] = make_uint4(v[4 * q], v[4 * q + 1], v[4 * q + 2], v[4 * q + 3]);
 }
 
-// The 32 values of a lane from its counter words: bit cc of every word is cnt = |R & S| of the lane's list row against table
-// column cc.  With the list set's size ll and the table set's size lt[cc], by the polarities of the item's flags fl:
+// A lane's N values from its counter words, for the table columns c0 .. c0 + N - 1 of the word: bit cc of every word is
+// cnt = |R & S| of the lane's list row against table column cc.  With the list set's size ll and the table set's size
+// lt[j] of column c0 + j, by the polarities of the item's flags fl:
 //     list U, table U: m - ll - lt + cnt     list A, table A: cnt     list U, table A: lt - cnt     list A, table U: ll - cnt
-template <typename CT>
-__device__ __forceinline__ void sp_values(uint32_t (&out)[32], const uint32_t (&c)[kSpCounters], uint32_t fl, uint32_t m, uint32_t ll,
-                                          const uint32_t *lt)
+template <typename CT, int N>
+__device__ __forceinline__ void sp_values(uint32_t (&out)[N], const uint32_t (&c)[kSpCounters], uint32_t c0, uint32_t fl, uint32_t m,
+                                          uint32_t ll, const uint32_t *lt)
 {
     const bool la = (fl & kSpItemListA) != 0, ta = (fl & kSpItemTabA) != 0;  // (wave-uniform: per item)
     const uint32_t kl = !la && !ta ? m - ll : la && !ta ? ll : 0u;
     const uint32_t tsub = !la && !ta ? 0xFFFFFFFFu : 0u, tadd = !la && ta ? 0xFFFFFFFFu : 0u;  // the table set's size: minus | plus | not at all
     const uint32_t cneg = la != ta ? 0xFFFFFFFFu : 0u;                                           // cnt: minus | plus
+    uint32_t cs[kSpCounters];
 #pragma unroll
-    for (int cc = 0; cc < 32; ++cc) {
+    for (int b = 0; b < kSpCounters; ++b) cs[b] = c[b] >> c0;
+#pragma unroll
+    for (int j = 0; j < N; ++j) {
         uint32_t cnt = 0;
 #pragma unroll
-        for (int b = 0; b < kSpCounters; ++b) cnt |= ((c[b] >> cc) & 1u) << b;
-        const uint32_t t = lt[cc];
-        out[cc] = (kl + (t & tadd) - (t & tsub) + ((cnt ^ cneg) - cneg)) & (sizeof(CT) == 2 ? 0xFFFFu : 0xFFFFFFFFu);
+        for (int b = 0; b < kSpCounters; ++b) cnt |= ((cs[b] >> j) & 1u) << b;
+        const uint32_t t = lt[j];
+        out[j] = (kl + (t & tadd) - (t & tsub) + ((cnt ^ cneg) - cneg)) & (sizeof(CT) == 2 ? 0xFFFFu : 0xFFFFFFFFu);
     }
 }
 
@@ -218,7 +226,7 @@ __global__ __launch_bounds__(512) void k_sparse_count(const uint4 *__restrict__ 
     }
     // column cc of this lane's word: bit cc of every counter word
     uint32_t out[32];
-    sp_values<CT>(out, c, it.y, m, li_all, lenj + w * 32);
+    sp_values<CT, 32>(out, c, 0u, it.y, m, li_all, lenj + w * 32);
     CT *blk = cum + (uint64_t)plane * nslots + (uint64_t)it.x * (kTile * kTile);
     if (!tr) {
         put32(blk + (uint64_t)r * kTile + w * 32, out);
@@ -236,90 +244,141 @@ __global__ __launch_bounds__(512) void k_sparse_count(const uint4 *__restrict__ 
     }
 }
 
-// The LDS placement: workgroup g of a group of 32 takes item (g / 32) * 8 + g % 8 -- so that an item's launch position
-// still names its XCD (plan.cpp) -- and table word (g / 8) % 4.  lds: [max(2^p, 4096)] the word's table -- and, once the
-// counting is done, a transposed item's 32 x 128 values -- then the 32 table columns' set sizes.
+__device__ __forceinline__ void put8(uint16_t *dst, const uint32_t (&v)[8])
+{
+    *reinterpret_cast<uint4 *>(dst) = make_uint4(v[0] | (v[1] << 16), v[2] | (v[3] << 16), v[4] | (v[5] << 16), v[6] | (v[7] << 16));
+}
+__device__ __forceinline__ void put8(uint32_t *dst, const uint32_t (&v)[8])
+{
+    reinterpret_cast<uint4 *>(dst)[0] = make_uint4(v[0], v[1], v[2], v[3]);
+    reinterpret_cast<uint4 *>(dst)[1] = make_uint4(v[4], v[5], v[6], v[7]);
+}
+
+// One step of a lane's walk against the table word in LDS: the eight 16-bit positions of pk, of which `left` are in the
+// list (kPartial: fewer than eight may be -- behind the list's end nothing is read at whatever the slot holds).
+template <bool kPartial>
+__device__ __forceinline__ void sp_step_lds(uint32_t (&c)[kSpCounters], const uint32_t *tabl, const uint4 pk, uint32_t left)
+{
+    const uint32_t pw[4] = {pk.x, pk.y, pk.z, pk.w};
+    uint32_t x[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const bool valid = !kPartial || (uint32_t)j < left;
+        const uint32_t pos = valid ? (pw[j >> 1] >> (16 * (j & 1))) & 0xFFFFu : 0u;
+        const uint32_t v = tabl[pos];
+        x[j] = valid ? v : 0u;
+    }
+    uint32_t t0, t1, t2, t3, f0, f1, e;
+    csa(t0, c[0], c[0], x[0], x[1]);
+    csa(t1, c[0], c[0], x[2], x[3]);
+    csa(f0, c[1], c[1], t0, t1);
+    csa(t2, c[0], c[0], x[4], x[5]);
+    csa(t3, c[0], c[0], x[6], x[7]);
+    csa(f1, c[1], c[1], t2, t3);
+    csa(e, c[2], c[2], f0, f1);
+#pragma unroll
+    for (int b = 3; b < kSpCounters; ++b) {  // the eights' carry ripples up
+        const uint32_t carry = c[b] & e;
+        c[b] ^= e;
+        e = carry;
+    }
+}
+
+// The LDS placement: workgroup g of a group of 32 is (x, w, c) = (g % 8, (g / 8) % 4, g / 32).  It takes table word w and
+// a RUN of `run` items of the launch, x + 8 * (c * run + i) for i < run: every eighth item, so that an item's launch
+// position still names its XCD, and one behind the other there the planner puts items of one table block (plan.cpp,
+// order_sparse_items).  The word is staged only where an item's table slab is not the one the item before it in the run
+// left there (plan.h, sparse_table_fills counts by the same rule); the set sizes lt of the lane's eight table columns
+// stay in registers as long.  After the four lanes of a row have added their counters, lane q reads out the columns
+// 8 q .. 8 q + 7 of the word.  lds: [2^p] the word's table, then CT [32][128]: the values of a transposed item on their
+// way out, in a place of their own, so that the table outlives the item.
+// DSH_SPARSE_CUT (a measuring build, `make SPCUT=1`, never the product library): an item ends after phase `stop` -- 1 the
+// fill, 2 the walk, 3 the lanes' addition -- and the results are meaningless; stop = 0 is the whole kernel.
 template <typename CT>
-__global__ __launch_bounds__(512) void k_sparse_count_lds(const uint4 *__restrict__ items, uint32_t nitems, const uint32_t *__restrict__ tabw,
-                                                          const uint16_t *__restrict__ lists, const uint32_t *__restrict__ len, uint32_t cap,
-                                                          uint32_t m, CT *__restrict__ cum, uint64_t nslots)
+__global__ __launch_bounds__(512) void k_sparse_count_lds(const uint4 *__restrict__ items, uint32_t nitems, uint32_t run,
+                                                          const uint32_t *__restrict__ tabw, const uint16_t *__restrict__ lists,
+                                                          const uint32_t *__restrict__ len, uint32_t cap, uint32_t m, CT *__restrict__ cum,
+                                                          uint64_t nslots, uint32_t stop)
 {
     extern __shared__ __attribute__((aligned(16))) uint32_t sp_lds[];
-    const uint32_t g = blockIdx.x, item = (g >> 5) * 8 + (g & 7u), w = (g >> 3) & 3u;
-    if (item >= nitems) return;  // (the whole workgroup, in front of the barrier)
-    const uint4 it = items[item];
-    const bool tr = (it.y & kSpItemTransposed) != 0;  // (uniform over the workgroup)
-    const uint32_t ls = tr ? it.w : it.z, ts = tr ? it.z : it.w, plane = it.y & kSpPlaneMask;  // list slab, table slab
-    const uint32_t tid = threadIdx.x, r = tid >> 2, q = tid & 3u;
-    const uint32_t lenat = m < 32u * kTile ? 32u * kTile : m;  // (launch_sparse_count sizes the LDS by the same rule)
-    const uint4 *src = reinterpret_cast<const uint4 *>(tabw + ((uint64_t)ts * 4 + w) * m);
-    for (uint32_t i = tid; i < m / 4; i += 512) reinterpret_cast<uint4 *>(sp_lds)[i] = src[i];
-    if (tid < 32) sp_lds[lenat + tid] = len[(uint64_t)ts * kTile + w * 32 + tid];
-    __syncthreads();
-    const uint32_t li_all = len[(uint64_t)ls * kTile + r];
-    const uint32_t li = li_all < cap ? li_all : cap;
-    const uint16_t *lp = lists + ((uint64_t)ls * kTile + r) * cap;
-    uint32_t c[kSpCounters];
-#pragma unroll
-    for (int b = 0; b < kSpCounters; ++b) c[b] = 0;
-    for (uint32_t k0 = 8 * q; k0 < li; k0 += 32) {  // (lane q of the row's four: every fourth group of eight entries)
-        const uint4 pk = *reinterpret_cast<const uint4 *>(lp + k0);
-        const uint32_t pw[4] = {pk.x, pk.y, pk.z, pk.w};
-        uint32_t x[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const bool valid = k0 + j < li;  // (behind the list's end: no read at whatever the slot holds)
-            const uint32_t pos = valid ? (pw[j >> 1] >> (16 * (j & 1))) & 0xFFFFu : 0u;
-            const uint32_t v = sp_lds[pos];
-            x[j] = valid ? v : 0u;
+#ifdef DSH_SPARSE_CUT
+    const uint32_t cut = stop;
+#else
+    constexpr uint32_t cut = 0;
+#endif
+    CT *turn = reinterpret_cast<CT *>(sp_lds + m);
+    const uint32_t g = blockIdx.x, x = g & 7u, w = (g >> 3) & 3u, first = (g >> 5) * run;
+    const uint32_t tid = threadIdx.x, r = tid >> 2, q = tid & 3u, c0 = 8 * q;
+    uint32_t have = 0xFFFFFFFFu;  // the table slab whose word the LDS holds
+    uint32_t lt[8];
+    // (every condition on the way to a barrier is uniform over the workgroup: the item, its slabs and its flags)
+    for (uint32_t i = 0; i < run; ++i) {
+        const uint32_t item = x + 8 * (first + i);
+        if (item >= nitems) break;  // a ragged last run
+        const uint4 it = items[item];
+        const bool tr = (it.y & kSpItemTransposed) != 0;
+        const uint32_t ls = tr ? it.w : it.z, ts = tr ? it.z : it.w, plane = it.y & kSpPlaneMask;  // list slab, table slab
+        if (ts != have) {
+            if (i) __syncthreads();  // the walk of the item before is over in every wave
+            const uint4 *src = reinterpret_cast<const uint4 *>(tabw + ((uint64_t)ts * 4 + w) * m);
+            for (uint32_t k = tid; k < m / 4; k += 512) reinterpret_cast<uint4 *>(sp_lds)[k] = src[k];
+            const uint4 *lq = reinterpret_cast<const uint4 *>(len + (uint64_t)ts * kTile + w * 32 + c0);
+            const uint4 l0 = lq[0], l1 = lq[1];
+            lt[0] = l0.x, lt[1] = l0.y, lt[2] = l0.z, lt[3] = l0.w, lt[4] = l1.x, lt[5] = l1.y, lt[6] = l1.z, lt[7] = l1.w;
+            __syncthreads();
+            have = ts;
         }
-        uint32_t t0, t1, t2, t3, f0, f1, e;
-        csa(t0, c[0], c[0], x[0], x[1]);
-        csa(t1, c[0], c[0], x[2], x[3]);
-        csa(f0, c[1], c[1], t0, t1);
-        csa(t2, c[0], c[0], x[4], x[5]);
-        csa(t3, c[0], c[0], x[6], x[7]);
-        csa(f1, c[1], c[1], t2, t3);
-        csa(e, c[2], c[2], f0, f1);
+        if (cut == 1) continue;
+        const uint32_t li_all = len[(uint64_t)ls * kTile + r];
+        const uint32_t li = li_all < cap ? li_all : cap;
+        const uint16_t *lp = lists + ((uint64_t)ls * kTile + r) * cap;
+        uint32_t c[kSpCounters];
 #pragma unroll
-        for (int b = 3; b < kSpCounters; ++b) {
-            const uint32_t carry = c[b] & e;
-            c[b] ^= e;
-            e = carry;
+        for (int b = 0; b < kSpCounters; ++b) c[b] = 0;
+        // lane q of the row's four: every fourth group of eight entries; only the list's last group can be partial
+        uint32_t k0 = 8 * q;
+        for (; k0 + 8 <= li; k0 += 32) sp_step_lds<false>(c, sp_lds, *reinterpret_cast<const uint4 *>(lp + k0), 8);
+        if (k0 < li) sp_step_lds<true>(c, sp_lds, *reinterpret_cast<const uint4 *>(lp + k0), li - k0);
+        if (cut == 2) continue;
+        // the four lanes of a row add their counters: a bit-sliced adder, twice (every lane of the wave takes part)
+#pragma unroll
+        for (int d = 1; d <= 2; d <<= 1) {
+            uint32_t carry = 0;
+#pragma unroll
+            for (int b = 0; b < kSpCounters; ++b) {
+                const uint32_t o = __shfl_xor(c[b], d, 64);
+                const uint32_t u = c[b] ^ o;
+                const uint32_t sum = u ^ carry;
+                carry = (c[b] & o) | (u & carry);
+                c[b] = sum;
+            }
         }
-    }
-    // the four lanes of a row add their counters: a bit-sliced adder, twice (every lane of the wave takes part)
+        if (cut == 3) {  // (the sum leaves the lane, so that the phase is not compiled away; no value of a real item is all ones)
+            uint32_t all = 0xFFFFFFFFu;
 #pragma unroll
-    for (int d = 1; d <= 2; d <<= 1) {
-        uint32_t carry = 0;
-#pragma unroll
-        for (int b = 0; b < kSpCounters; ++b) {
-            const uint32_t o = __shfl_xor(c[b], d, 64);
-            const uint32_t u = c[b] ^ o;
-            const uint32_t sum = u ^ carry;
-            carry = (c[b] & o) | (u & carry);
-            c[b] = sum;
+            for (int b = 0; b < kSpCounters; ++b) all &= c[b];
+            if (all == 0xFFFFFFFFu && cap == 1) turn[tid] = (CT)all;
+            continue;
         }
-    }
-    CT *blk = cum + (uint64_t)plane * nslots + (uint64_t)it.x * (kTile * kTile);
-    if (!tr) {
-        if (q != 0) return;
-        uint32_t out[32];
-        sp_values<CT>(out, c, it.y, m, li_all, sp_lds + lenat);
-        put32(blk + (uint64_t)r * kTile + w * 32, out);
-        return;
-    }
-    // transposed: lane (r, 0) holds column r of the rows w * 32 .. w * 32 + 31.  The staged table word is dead behind the
-    // barrier: the 32 x 128 values are turned there and leave as whole rows
-    __syncthreads();
-    if (q == 0) {
-        uint32_t out[32];
-        sp_values<CT>(out, c, it.y, m, li_all, sp_lds + lenat);
+        // all four lanes of a row now hold the row's counters: lane q reads out 8 of the word's 32 columns
+        uint32_t out[8];
+        sp_values<CT, 8>(out, c, c0, it.y, m, li_all, lt);
+        CT *blk = cum + (uint64_t)plane * nslots + (uint64_t)it.x * (kTile * kTile);
+        if (!tr) {  // a row's four lanes store 32 values side by side
+            put8(blk + (uint64_t)r * kTile + w * 32 + c0, out);
+            continue;
+        }
+        // transposed: lane (r, q) holds column r of the rows w * 32 + 8 q .. + 7.  The 32 x 128 values are turned in LDS
+        // and leave as whole rows, which lie one behind the other in the tile's block.  The first barrier: the rows of a
+        // transposed item before this one have left
+        __syncthreads();
 #pragma unroll
-        for (int cc = 0; cc < 32; ++cc) sp_lds[cc * kTile + r] = out[cc];
+        for (int j = 0; j < 8; ++j) turn[(c0 + j) * kTile + r] = (CT)out[j];
+        __syncthreads();
+        const uint4 *ts4 = reinterpret_cast<const uint4 *>(turn);
+        uint4 *dst = reinterpret_cast<uint4 *>(blk + (uint64_t)w * 32 * kTile);
+        for (uint32_t k = tid; k < 32 * kTile * sizeof(CT) / 16; k += 512) dst[k] = ts4[k];
     }
-    __syncthreads();
-    sp_store_rows<CT>(sp_lds, blk + (uint64_t)w * 32 * kTile, tid);
 }
 
 }  // namespace
@@ -337,20 +396,29 @@ hipError_t launch_sparse_build(hipStream_t st, const uint32_t *planes, uint32_t 
     return hipGetLastError();
 }
 
-hipError_t launch_sparse_count(hipStream_t st, int cum_bytes, const uint4 *items, uint32_t nitems, int wordmajor, const uint32_t *tab,
-                               const uint16_t *lists, const uint32_t *len, uint32_t cap, uint32_t m, void *cum, uint64_t nslots)
+hipError_t launch_sparse_count(hipStream_t st, int cum_bytes, const uint4 *items, uint32_t nitems, uint32_t run, int wordmajor,
+                               const uint32_t *tab, const uint16_t *lists, const uint32_t *len, uint32_t cap, uint32_t m, void *cum,
+                               uint64_t nslots)
 {
     if (nitems == 0) return hipSuccess;
-    if (cap % 8 || cap > 2047) return hipErrorInvalidValue;
+    if (cap % 8 || cap > 2047 || run == 0) return hipErrorInvalidValue;
     if (wordmajor) {
         if (m < 512 || m > (1u << 15)) return hipErrorInvalidValue;  // (a word of the table in a CU's LDS)
-        const size_t lds = (size_t)std::max<uint32_t>(m, 32u * kTile) * 4 + 32 * 4;  // (a word of the table, or the turned values of a transposed item)
-        const uint32_t grid = (nitems + 7) / 8 * 32;
+        const uint32_t per_x = (nitems + 7) / 8;  // the items of an XCD residue
+        run = std::min(run, per_x);
+        const uint32_t grid = (per_x + run - 1) / run * 32;
+        uint32_t stop = 0;
+#ifdef DSH_SPARSE_CUT
+        if (const char *s = std::getenv("DSH_SPARSE_STOP")) stop = (uint32_t)std::atoi(s);
+#endif
+        // a word of the table and the turned values of a transposed item: 72 KiB at p = 14 and 16-bit C(v), two workgroups a CU
 #define DSH_SPL(CT)                                                                                                                   \
     do {                                                                                                                              \
+        const size_t lds = (size_t)m * 4 + 32 * kTile * sizeof(CT);                                                                   \
         const hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void *>(k_sparse_count_lds<CT>), lds);                          \
         if (e != hipSuccess) return e;                                                                                                \
-        hipLaunchKernelGGL(k_sparse_count_lds<CT>, dim3(grid), dim3(512), lds, st, items, nitems, tab, lists, len, cap, m, (CT *)cum, nslots); \
+        hipLaunchKernelGGL(k_sparse_count_lds<CT>, dim3(grid), dim3(512), lds, st, items, nitems, run, tab, lists, len, cap, m,        \
+                           (CT *)cum, nslots, stop);                                                                                  \
     } while (0)
         if (cum_bytes == 2) DSH_SPL(uint16_t);
         else DSH_SPL(uint32_t);

@@ -1028,6 +1028,22 @@ static void order_sparse_items(const std::vector<U4> &T, const std::pair<size_t,
             if (r < lists[x].size()) sp_items[q++] = lists[x][r];
 }
 
+uint64_t sparse_table_fills(const U4 *items, size_t n, uint32_t run)
+{
+    if (run == 0) return 0;
+    uint64_t fills = 0;
+    for (size_t x = 0; x < 8 && x < n; ++x) {
+        uint32_t have = 0;
+        size_t i = 0;  // the item's place in its run
+        for (size_t k = x; k < n; k += 8, i = i + 1 == run ? 0 : i + 1) {
+            const uint32_t ts = items[k].y & kSpItemTransposed ? items[k].z : items[k].w;
+            if (i == 0 || ts != have) fills += 4;
+            have = ts;
+        }
+    }
+    return fills;
+}
+
 // sparse routing: band by band (the automatic rule looks at the band), the routed planes of every tile, one sparse item
 // each -- ordered by column block, whose table the items of a column share in L2 -- and the slabs they read.  One loop for
 // both routes: a two-plane item has no flags and lists on both blocks, a sided item its polarities and transposition.

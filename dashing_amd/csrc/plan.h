@@ -240,6 +240,12 @@ constexpr bool kSparseSidedAuto = true;  // whether sparse_sided = -1 turns the 
 constexpr uint32_t kSpPlaneMask = 0xFFu;
 constexpr uint32_t kSpItemListA = 1u << 8, kSpItemTabA = 1u << 9, kSpItemTransposed = 1u << 10;
 constexpr uint32_t kSpSlabA = 1u << 8, kSpSlabTableOnly = 1u << 9;
+// The LDS placement of the counting kernel (kernels_sparseplane.hip, k_sparse_count_lds) takes the n items of a launch in
+// RUNS: workgroup (x, w, c) has table word w and the items x + 8 * (c * run + i), i < run, and stages the word wherever an
+// item's table slab (.w, .z of a transposed item) is not that of the item before it in the run.  The number of stagings
+// of the launch, by that rule: four words a fill.  kSparseRunDefault: option sparse_run = 0 (profiles/sparse3).
+constexpr uint32_t kSparseRunDefault = 4, kSparseRunMax = 1u << 16;
+uint64_t sparse_table_fills(const U4 *items, size_t n, uint32_t run);
 
 struct Tuning {
     uint32_t W = 0;        // 32-bit words per plane
