@@ -1,7 +1,7 @@
 // abi.hip -- the C-ABI of libdashing_hip.so (include/dashing_hip.h) over the gfx950 kernels: context, resident sketch
 // matrix, cardinalities, the compare entry points, per-call completion tickets, shards of the sorted triangle, options.
-// Argument checks and call sequencing live here; the work is in engine.hip (prepare / run_pairs), knn.hip and
-// exchange.hip; the sketch entry points are sketch.hip's; the pure entry points (dsh_tri_*, dsh_partition_rows,
+// Argument checks and call sequencing live here; the work is in engine.hip (prepare / run_pairs), knn.hip,
+// comm.hip and exchange.hip; the sketch entry points are sketch.hip's; the pure entry points (dsh_tri_*, dsh_partition_rows,
 // dsh_balance_rows, dsh_range_parts) and the shard bounds are in plan.cpp.  No CPU fallback lives here: without a HIP
 // device dsh_create fails with DSH_ENODEV.
 #include <algorithm>

@@ -15,6 +15,7 @@ constexpr int kMaxPCompare = 24;  // the compare path takes every p the sketches
 constexpr int kMaxP = 24;      // largest p for sketching / cardinalities / up- and download (positions are 24-bit)
 constexpr uint32_t kThrChunk = 4096;  // values of a band row that one wave walks (kernels.h: ThrRows)
 constexpr uint32_t kBandMaxRows = 1u << 20;  // rows of a band of the dense path's consumers (plan.h: tri_band_end, rect_band_rows)
+constexpr uint32_t kSigMaxParts = 256;  // parts of a call that k_finalize can announce by a flag (kernels.h: kSig*; exchange_plan.h)
 constexpr uint32_t kSketchSub = 8192;  // bases per sub-chunk (256 threads x 32 start positions)
 
 }  // namespace dsh

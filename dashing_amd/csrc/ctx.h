@@ -20,7 +20,10 @@
 //   derive.hip    dsh_fold*, dsh_upload_sketches_folded*, dsh_union_groups* (new sketches out of resident ones)
 //   curve.hip     dsh_union_curve*, dsh_curve_permutations (the growth of the union along orders of resident sketches)
 //   curve_plan.h  (header, no HIP types) the cut of those orders into segments and batches
-//   exchange.hip  RCCL: dsh_comm_*, dsh_collect_*, dsh_allgather_device, dsh_dist_collect
+//   comm.hip      RCCL: the loader, dsh_comm_*, dsh_allgather_device, the guarded wait, the poster of a grouped round
+//   exchange.hip  dsh_collect_*, dsh_exchange_*, dsh_dist_collect, the one-GPU diagnostics of the exchange
+//   exchange_plan.h  (header, no HIP types) the modes of the ranks, the round schedule of dsh_exchange_collect_async
+//   kernels_exchange.hip  row placement at the destination, the un-permute, the diagnostics' kernels
 //   plan.cpp      the pure-host planner (layout, tiles, bands, parts, work items, row partitions, shard bounds)
 // State that one of these modules uses alone is a named member struct of dsh_ctx (c->cc.parent, c->xch.comm); what the
 // compare path shares with every module stays flat.
@@ -361,7 +364,7 @@ struct dsh_ctx {
         uint64_t scratch_bytes = (uint64_t)256 << 20;  // option curve_scratch_bytes: delta + start rows + counters of a batch of orders
         uint64_t segment = 0;                          // option curve_segment: members per segment, 0 = the planner's (curve_plan.h)
     } curve;
-    // multi-GPU exchange (exchange.hip, dsh_comm_*): an RCCL communicator over the ranks' contexts (not owned here:
+    // multi-GPU exchange (comm.hip, exchange.hip): an RCCL communicator over the ranks' contexts (not owned here:
     // comm_release destroys it while the library is loaded)
     struct {
         ncclComm_t comm = nullptr;
@@ -579,7 +582,26 @@ uint32_t *cc_err(dsh_ctx *c);
 uint32_t cc_cap(uint64_t n);
 int cc_finish(dsh_ctx *c, uint64_t n, uint32_t *d_labels, uint32_t *h_labels, uint64_t *n_clusters);
 
-// exchange.hip: waits for both streams of the communicator's traffic and destroys it (no-op without one)
+// comm.hip: waits for both streams of the communicator's traffic and destroys it (no-op without one)
 int comm_release(dsh_ctx *c);
+// the world and this context's rank (1, 0 without a communicator), and whether there is a communicator
+struct CommWho {
+    int world, rank;
+    bool comm;
+};
+CommWho comm_who(const dsh_ctx *c);
+// fails with "dsh_comm_init first" unless there is a communicator or the call concerns this rank alone
+int need_comm(dsh_ctx *c, bool alone_ok);
+// waits for a stream that carries RCCL traffic, with a deadline (DSH_COMM_TIMEOUT_S)
+int sync_guarded(dsh_ctx *c, hipStream_t st, const char *what);
+int validate_bounds(dsh_ctx *c, uint64_t n, const uint64_t *bounds, int world, int dst);
+// one operation of a grouped round: cnt floats from (send) or to `ptr`, with rank `peer`
+struct GroupOp {
+    bool send;
+    void *ptr;
+    uint64_t cnt;
+    int peer;
+};
+int post_group(dsh_ctx *c, hipStream_t st, const GroupOp *ops, size_t nops);
 
 }  // namespace dsh

@@ -4,7 +4,8 @@
 // (tests/test_plan.py).  Also the sequential build of the clusters' union-find (dsh_plan_uf_labels, at the end) and the band rule of
 // the greedy representatives (dshh_greedy_bands) and the band walk all five band consumers share (dshh_threshold_bands), and the
 // sequential build of the linkage clusters (dsh_plan_linkage_labels, dsh_plan_linkage_loose: ../linkage.h), and the sketch
-// path's planners (dshh_sketch_plan: ../sketch_plan.h), and the union curve's (dshh_curve_plan: ../curve_plan.h).  Built into libdashing_host.so; not part of the GPU C-ABI.
+// path's planners (dshh_sketch_plan: ../sketch_plan.h), and the union curve's (dshh_curve_plan: ../curve_plan.h), and the exchange's round schedule
+// (dshh_exchange_plan: ../exchange_plan.h).  Built into libdashing_host.so; not part of the GPU C-ABI.
 #include <algorithm>
 #include <cstdarg>
 #include <cstdio>
@@ -1108,6 +1109,81 @@ int dshh_curve_plan(uint64_t n_orders, uint64_t len, int p, uint64_t budget, uin
     if (cap < pl.nseg + 1) return -2;
     for (uint64_t s = 0; s <= pl.nseg; ++s) bounds[s] = pl.begin(s, len);
     return 0;
+}
+
+}  // extern "C"
+
+#include "../exchange_plan.h"
+
+extern "C" {
+
+// the planning of dsh_exchange_collect_async (../exchange_plan.h) for ONE calling rank of the row-set table `tab`, as
+// exchange.hip runs it (tests/test_exchange_plan.py): the modes (fine != 0: the caller cut finely, as a rank whose parts
+// are signalled does), the tables of the row-sorted ranks the caller knows -- the destination derives every source's from
+// the keys, a source takes its own from its layout, built here as engine.hip builds it -- and the schedule.  The lists:
+//   0 total u64[world] | 1 messages u64[M * world][2] {first, cnt} | 2 post u8[M] | 3 gate u32[M] | 4 part_end u64[] |
+//   5 stage_off u64[world] | 6 tab_off u64[world] | 7 entries u64[][4] {src, pos0, row0, nrows} | 8 round_ent u32[M + 1] |
+//   9 round_rows u32[M] | 10 rowoff u64, the known ranks' one behind the other in rank order | 11 order u32, the same |
+//   12 modes u32[world][3] {rowsorted, parts, parts asked for} | 13 the calling rank's cut u64[] (XMode::cut)
+// info[3] = stage_total, ent_off, tab_bytes.  counts[14] gets the lists' lengths in elements; with bufs == NULL that is all,
+// else bufs[i] (where not NULL) has room for counts[i] elements on entry and gets list i.  Returns 0, -1 for unusable
+// arguments, -2 for a buffer too small.
+int dshh_exchange_plan(uint64_t n, const uint32_t *keys, const uint64_t *tab, uint32_t nparts, int dst, int rank, int fine, void *const *bufs,
+                       uint64_t *counts, uint64_t *info)
+{
+    RowSets rs;
+    if (!keys || !tab || !counts || !info || nparts == 0 || parse_rowsets(tab, n, rs) || dst < 0 || (uint32_t)dst >= rs.world || rank < 0 ||
+        (uint32_t)rank >= rs.world)
+        return -1;
+    const std::vector<xplan::XMode> modes = xplan::xmodes(n, rs, nparts, dst, fine ? rank : -1);
+    std::vector<std::vector<uint64_t>> rowoff(rs.world);
+    std::vector<std::vector<uint32_t>> order(rs.world);
+    std::vector<uint32_t> scratch;
+    for (uint32_t r = 0; r < rs.world; ++r) {
+        const xplan::XMode &m = modes[r];
+        if ((int)r == dst || !m.rowsorted) continue;
+        if (rank == dst) {
+            xplan::rowsorted_tables(keys, n, m, order[r], rowoff[r], scratch);
+        } else if ((int)r == rank) {
+            Layout L;
+            const std::vector<uint64_t> no_parts;
+            build_layout(n, SketchWords{keys, nullptr, nullptr, 0}, LayoutQuery{1, m.rb, m.re, &no_parts, m.kreq, m.extra.empty() ? nullptr : &m.extra}, L);
+            std::vector<std::pair<uint64_t, uint64_t>> wsegs;
+            wanted_order(n, m.rb, m.re, &m.extra, wsegs, true);
+            for (auto &w : wsegs)
+                for (uint64_t s = w.first - m.rb; s < w.second - m.rb; ++s) order[r].push_back(L.perm[s]);
+            rowoff[r] = L.rowoff_w;
+        }
+    }
+    const xplan::Schedule S = xplan::schedule(n, modes, nparts, dst, rank, rowoff);
+    std::vector<uint64_t> msgs, ents, ro;
+    std::vector<uint32_t> ord, md;
+    for (size_t q = 0; q < S.M; ++q)
+        for (int src = 0; src < S.world; ++src) msgs.push_back(S.msg(q, src).first), msgs.push_back(S.msg(q, src).cnt);
+    for (const xplan::Ent &e : S.ents) ents.insert(ents.end(), {(uint64_t)e.src, e.pos0, (uint64_t)e.row0, (uint64_t)e.nrows});
+    for (uint32_t r = 0; r < rs.world; ++r) {
+        ro.insert(ro.end(), rowoff[r].begin(), rowoff[r].end());
+        ord.insert(ord.end(), order[r].begin(), order[r].end());
+        md.insert(md.end(), {modes[r].rowsorted ? 1u : 0u, (uint32_t)modes[r].nparts(), modes[r].kreq});
+    }
+    info[0] = S.stage_total, info[1] = S.ent_off, info[2] = S.tab_bytes;
+    void *const none[14] = {};
+    if (!bufs) bufs = none;
+    bool fits = hand_back(S.total, bufs[0], counts[0]);
+    fits = hand_back(msgs, bufs[1], counts[1]) && fits;
+    fits = hand_back(S.post, bufs[2], counts[2]) && fits;
+    fits = hand_back(S.gate, bufs[3], counts[3]) && fits;
+    fits = hand_back(S.part_end, bufs[4], counts[4]) && fits;
+    fits = hand_back(S.stage_off, bufs[5], counts[5]) && fits;
+    fits = hand_back(S.tab_off, bufs[6], counts[6]) && fits;
+    fits = hand_back(ents, bufs[7], counts[7]) && fits;
+    fits = hand_back(S.round_ent, bufs[8], counts[8]) && fits;
+    fits = hand_back(S.round_rows, bufs[9], counts[9]) && fits;
+    fits = hand_back(ro, bufs[10], counts[10]) && fits;
+    fits = hand_back(ord, bufs[11], counts[11]) && fits;
+    fits = hand_back(md, bufs[12], counts[12]) && fits;
+    fits = hand_back(modes[(size_t)rank].cut, bufs[13], counts[13]) && fits;
+    return fits ? 0 : -2;
 }
 
 }  // extern "C"

@@ -140,7 +140,6 @@ hipError_t launch_finalize(hipStream_t st, const FinalizeLaunch &f);
 // the signal block of a call with parts, in 32-bit words: per part a flag (= the generation of the call that completed
 // it), a count of finished tiles, the tiles it holds in all, a 64-bit wall-clock stamp of its completion; the stamp of the
 // call's start; per tile of the band in flight a count of finished rows
-constexpr uint32_t kSigMaxParts = 256;
 constexpr uint32_t kSigPartFlag = 0, kSigPartCnt = kSigMaxParts, kSigPartTotal = 2 * kSigMaxParts,
                    kSigGen = 3 * kSigMaxParts, kSigStamp = kSigGen + 1,  // (uploaded with the totals: kSigMaxParts + 2 words)
                    kSigPartTime = 3 * kSigMaxParts + 2, kSigT0 = 5 * kSigMaxParts + 2, kSigTileCnt = 5 * kSigMaxParts + 4,
@@ -162,7 +161,8 @@ struct UploadSegs {
 };
 hipError_t launch_upload_segs(hipStream_t st, const UploadSegs &u, uint32_t nseg);
 hipError_t launch_wall_stamp(hipStream_t st, unsigned long long *out);
-// ---- exchange.hip: row placement at the destination of an exchange, the older shard scheme's un-permute
+// ---- kernels_exchange.hip: row placement at the destination of an exchange, the older shard scheme's un-permute, the
+// kernels of the one-GPU diagnostics
 // (k_rows_place) the rows of one source's part in a round of the exchange: positions [pos0, pos0 + nrows) of its key order
 struct PlaceEnt {
     const float *src;         // the source's staged buffer
@@ -179,6 +179,9 @@ hipError_t launch_unpermute_staged(hipStream_t st, const float *in, const uint32
                                    const int64_t *rowdelta, uint64_t n, float *out);
 // destination-driven (coalesced writes, gathered reads through inv, the inverse of perm)
 hipError_t launch_unpermute(hipStream_t st, const float *in, const uint32_t *inv, uint64_t n, float *out);
+// (diagnostics) cnt floats copied by plain loads and stores; a kernel that waits on a mapped word of host memory
+hipError_t launch_probe_copy(hipStream_t st, const float *src, float *dst, uint64_t cnt);
+hipError_t launch_diag_spin(hipStream_t st, uint32_t nblocks, uint32_t threads, uint32_t lds_bytes, const uint32_t *flag, unsigned long long max_ticks);
 
 // ---- knn.hip: nearest-neighbour selection (k_topk: one pass over a matrix of values)
 hipError_t launch_topk(hipStream_t st, const float *vals, uint64_t rows, uint64_t ncols,
@@ -416,7 +419,7 @@ hipError_t preload_compare_kernels();
 hipError_t preload_hist_kernels();      // (part of the compare set)
 hipError_t preload_sparseplane_kernels();  // (part of the compare set: kernels_sparseplane.hip)
 hipError_t preload_knn_kernels();       // (part of the compare set: knn.hip)
-hipError_t preload_exchange_kernels();  // (part of the compare set: exchange.hip)
+hipError_t preload_exchange_kernels();  // (part of the compare set: kernels_exchange.hip)
 hipError_t preload_fastx_kernels();
 hipError_t preload_sketch_kernels();
 

@@ -32,7 +32,7 @@
 //   k_finalize_signal the plain triangle's instance that announces the parts of a call from inside the launch
 //   k_upload(_segs)   in-order list uploads;  k_wall_stamp  the device's wall clock
 // (the nearest-neighbour selection kernels live in knn.hip, the exchange's row placement and the older shard scheme's
-// un-permute in exchange.hip)
+// un-permute in kernels_exchange.hip)
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
