@@ -49,8 +49,9 @@ def test_precisions(ctx, oracle, p):
 @pytest.mark.parametrize("p", [18, 20, 24])
 def test_large_precisions_hbm_registers(ctx, oracle, p):
     """p > 17 does not fit LDS: the GLOBAL variant of k_sketch updates the registers in HBM directly.
-    Same bit-exact contract; cardinalities too; the compare path takes these precisions as well (position bitmap in LDS
-    up to p = 19, hash-only probing of the exception lists above)."""
+    Same bit-exact contract; cardinalities too; the compare path takes these precisions as well (32-bit listed
+    positions from p = 16; above p = 14 a bucket of the column block's position index, k_build_colindex, is a group of
+    2^(p - 14) positions and k_finalize's join drops the entries of another position of the group)."""
     gs = synth.synthetic_genomes(2, 150013, seed=p, decorate=True)
     regs = run(ctx, oracle, gs, 31, p)
     got = ctx.cardinalities()
