@@ -555,6 +555,7 @@ int dsh_get_info(dsh_ctx *c, const char *name, int64_t *out)
     else if (!std::strcmp(name, "host_layout_us")) *out = (int64_t)c->host_layout_us;
     else if (!std::strcmp(name, "host_lists_us")) *out = (int64_t)c->host_lists_us;
     else if (!std::strcmp(name, "host_keys_wait_us")) *out = (int64_t)c->host_keys_wait_us;
+    else if (!std::strcmp(name, "host_sparse_us")) *out = (int64_t)c->host_sparse_us;  // the sparse items' emission (plan.h), behind the first tile kernel
     else if (!std::strcmp(name, "emax")) *out = c->emax;
     else if (!std::strcmp(name, "elow")) *out = c->elow;
     else if (!std::strcmp(name, "kc")) *out = c->kc;

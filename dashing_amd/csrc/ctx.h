@@ -231,6 +231,7 @@ struct dsh_ctx {
     uint32_t pass_sparse_cap = 0;       // ... sparse_cap had when the per-sketch pass ran (plan.h, Layout::thr_cap)
     bool hk32_valid = false;
     double host_layout_us = 0, host_lists_us = 0, host_keys_wait_us = 0;  // host time of the last call (dsh_get_info)
+    double host_sparse_us = 0;  // ... and of its plan::emit_sparse_items, which runs behind the first band's tile kernel
     Staging st_perm;                    // lay.perm, then (row-sorted parts) lay.rowoff from the next 16-byte boundary on
     DevBuf rowoff;                      // (row-sorted parts) offset of the row at layout position s in the rank's buffer
     Staging st_lists;                   // tiles then items of the call in flight

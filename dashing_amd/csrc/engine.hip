@@ -250,7 +250,8 @@ struct PairRun {
     FinalizeLaunch fin{};     // the call-invariant arguments of k_finalize; the band and the segment fill in theirs
     hipEvent_t e_call0 = nullptr;                             // (profiling, with parts) the call's start
     std::vector<std::pair<size_t, hipEvent_t>> ev_part_t;     // (profiling) part -> a timing event behind its last segment
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> evp, evf;  // (profiling) per band: around the tile kernel, around k_finalize
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> evp, evf;  // (profiling) per band: around the tile kernel and the counting kernel, around k_finalize
+    double build_in_pair_ms = 0;  // (profiling) k_sparse_build, which runs between the first band's two kernels and counts into prep_ms
 };
 
 // Triangle rows [rb,re): the plane matrix is laid out for exactly that range (wanted rows first, both
@@ -437,7 +438,8 @@ int upload_band(dsh_ctx *c, PairRun &r, size_t bi)
 }
 
 // The slabs of the call's sparse items (built unless the buffers hold exactly them, of this layout) and the items
-// themselves on the device.  Behind prepare() on the same stream: the bit-plane matrix the slabs are made from is there.
+// themselves on the device, once per call behind plan::emit_sparse_items.  Behind prepare() on the same stream: the
+// bit-plane matrix the slabs are made from is there.
 int prepare_sparse(dsh_ctx *c)
 {
     const plan::PairPlan &pp = c->pp;
@@ -474,7 +476,7 @@ int prepare_sparse(dsh_ctx *c)
     return DSH_OK;
 }
 
-// the band's sparse items, in front of its tile kernel: both fill the band's C(v), k_finalize needs both
+// the band's sparse items, behind its tile kernel: both fill the band's C(v), k_finalize needs both
 int launch_sparse_items(dsh_ctx *c, size_t bi, uint64_t nslots)
 {
     const plan::PairPlan &pp = c->pp;
@@ -567,6 +569,7 @@ int read_profile(dsh_ctx *c, const PairRun &r)
         c->pair_ms += ms;
         if (c->Kpad) c->pair_launches++;
     }
+    c->pair_ms -= r.build_in_pair_ms;  // (the first band's interval holds k_sparse_build: that is prep_ms')
     for (auto &e : r.evf) {
         float ms = 0;
         (void)hipEventElapsedTime(&ms, e.first, e.second);
@@ -652,7 +655,8 @@ int run_pairs(dsh_ctx *c, const PairJob &job)
     r.tu = tuning_of(c);
     // Tiles, bands and segments of the whole job first; the work items and the two device lists are made, uploaded and
     // launched BAND BY BAND: the host plans band b + 1 while the GPU runs band b (at 100 000 x p=10 the plan of 306 000
-    // tiles took the host 8 ms that nothing hid, round 4 / profiles/r4y).
+    // tiles took the host 8 ms that nothing hid, round 4 / profiles/r4y).  Of the sparse routes build_tiles only decides
+    // which planes leave the tile kernel; their items are emitted in the band loop below, behind the first tile kernel.
     if (!plan::build_tiles(c->lay, q, r.tu, pp)) {
         pp.T.clear();
         return DSH_OK;
@@ -677,7 +681,7 @@ int run_pairs(dsh_ctx *c, const PairJob &job)
     r.fin = finalize_invariants(c, job, jl.with_extra);
     c->ev_sparse.clear();
     c->sparse_run_used = 0;
-    if (!pp.sp_items.empty() && (rc = prepare_sparse(c))) return rc;
+    c->host_sparse_us = 0;
     for (size_t bi = 0; bi < pp.bands.size(); ++bi) {
         const uint64_t nslots = (uint64_t)(pp.bands[bi].second - pp.bands[bi].first) * kTile * kTile;
         if ((rc = upload_band(c, r, bi))) return rc;
@@ -688,13 +692,24 @@ int run_pairs(dsh_ctx *c, const PairJob &job)
             d = next_event(c);
             if (a) (void)hipEventRecord(a, c->stream);
         }
-        if ((rc = launch_sparse_items(c, bi, nslots))) return rc;
         if ((rc = launch_tile_kernel(c, r, bi, nslots))) return rc;
-        if (b) (void)hipEventRecord(b, c->stream);
         if (bi == 0) {  // (the destination of an exchange may post its receives behind its first tile kernel, exchange.hip)
             HIPCHK(c, c->ev_first_tiles.ensure());
             HIPCHK(c, hipEventRecord(c->ev_first_tiles, c->stream));
         }
+        // The sparse items of the whole call are emitted and ordered here, behind the first band's tile kernel: only the
+        // counting kernel needs them, and the host's time for them (host_sparse_us) passes while that kernel runs.  The two
+        // kernels write disjoint slots of the band's C(v); k_finalize below is behind both.
+        if (bi == 0 && pp.sp_count) {
+            const auto t_s0 = std::chrono::steady_clock::now();
+            plan::emit_sparse_items(c->lay, pp);
+            c->host_sparse_us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_s0).count();
+            const double prep0 = c->prep_ms;
+            if ((rc = prepare_sparse(c))) return rc;
+            r.build_in_pair_ms = c->prep_ms - prep0;
+        }
+        if ((rc = launch_sparse_items(c, bi, nslots))) return rc;
+        if (b) (void)hipEventRecord(b, c->stream);
         r.fin.a.nslots = nslots;  // (the band's stride: the distance between two planes of its C(v))
         if ((rc = finalize_band(c, r, bi))) return rc;
         if (d) (void)hipEventRecord(d, c->stream);

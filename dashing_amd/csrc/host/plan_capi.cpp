@@ -40,6 +40,7 @@ struct SparseCheck {
     int sided = 0;
     uint32_t *routes6 = nullptr, *items5 = nullptr, *slabs3 = nullptr;
     uint64_t items_cap = 0, slabs_cap = 0;
+    uint32_t max_slabs = 0;  // Tuning::sparse_max_slabs (dshh_plan_sparse_items); 0 = the planner's default
 };
 
 struct Err {
@@ -124,7 +125,8 @@ void job_layout(const CheckJob &job, Layout &L)
     build_layout(job.n, words, query, L);
 }
 
-bool job_plan(const CheckJob &job, const Layout &L, Tuning &tu, PairQuery &q, PairPlan &pp)
+// two_step: build_tiles, emit_sparse_items and the bands' items one after the other, as engine.hip calls them
+bool job_plan(const CheckJob &job, const Layout &L, Tuning &tu, PairQuery &q, PairPlan &pp, bool two_step = false)
 {
     const uint64_t m = 1ull << job.p;
     tu.W = (uint32_t)std::max<uint64_t>(1, m / 32);
@@ -138,6 +140,7 @@ bool job_plan(const CheckJob &job, const Layout &L, Tuning &tu, PairQuery &q, Pa
     if (job.round_items > 512) tu.small_round_items = 512;  // (as engine.hip under pair_groups = auto)
     tu.p = job.p;
     if (job.sc) tu.sparse_planes = job.sc->planes, tu.sparse_cap = job.sc->cap, tu.sparse_sided = job.sc->sided;
+    if (job.sc && job.sc->max_slabs) tu.sparse_max_slabs = job.sc->max_slabs;
     q.rect = job.mode == 1;
     q.sorted_rows = job.mode == 2;
     q.want_parts = job.plan_parts();
@@ -145,7 +148,14 @@ bool job_plan(const CheckJob &job, const Layout &L, Tuning &tu, PairQuery &q, Pa
     q.row_end = job.re;
     q.col_begin = job.cb;
     q.col_end = job.ce;
-    return build_pairs(L, q, tu, pp);
+    if (!two_step) return build_pairs(L, q, tu, pp);
+    if (!build_tiles(L, q, tu, pp)) return false;
+    for (size_t bi = 0; bi < pp.bands.size(); ++bi) {  // (the dense path first: it must not need the emission)
+        if (bi == 1) emit_sparse_items(L, pp);
+        build_band_items(tu, pp, bi);
+    }
+    if (pp.bands.size() < 2) emit_sparse_items(L, pp);
+    return true;
 }
 
 // ---- the checks: each returns at its first failure ---------------------------------------------------------------------
@@ -850,6 +860,66 @@ int dshh_plan_digest(uint64_t n, const uint32_t *keys, const uint32_t *gcnt, con
     const bool any = job_plan(job, L, tu, q, pp);
     *features = digest_plan(L, tu, q, pp, any, digests);
     return (int)kDigestSections;
+}
+
+// The sparse items of a plan as the device gets them (read-only; tests/test_sparse_order.py, tests/test_sparse_emit.py): the
+// layout and plan of a triangle job built as dshh_plan_check_sparse_sided builds them, with Tuning::sparse_max_slabs given
+// (0: the planner's default) and, two_step != 0, through build_tiles + emit_sparse_items + build_band_items in the order
+// engine.hip calls them instead of build_pairs.  Nothing is checked.  tiles6: per tile {row block, column block, plane begin,
+// plane end, planes routed below, planes routed above} in launch order; bands4: per band {first tile, end tile, first
+// sparse item, end sparse item}; items4: per sparse item, in LAUNCH order, {tile index in its band, plane | flags << 8
+// (plan.h, kSpItem*), slab of the row block, slab of the column block}; slabs2: per slab {block, plane | flags << 8
+// (kSpSlab*)}; chunks2: per tile its dense chunk range.  counts: [0] tiles, [1] bands, [2] sparse items, [3] slabs,
+// [4] items of the sided route, [5] transposed items, [6] table-only slabs, [7] dense items, [8] the blocks of the layout
+// (NT).  Returns 0; -1 on a bad argument or when a list does not fit its cap (counts are set then too).
+int dshh_plan_sparse_items(uint64_t n, const uint32_t *keys, const uint32_t *gcnt, const uint32_t *thr, uint32_t thr_cap, uint64_t rb, uint64_t re,
+                           uint32_t nparts, int want_parts, int p, uint64_t cum_budget, uint32_t round_items, int sparse_planes, int sparse_sided,
+                           uint32_t sparse_cap, uint32_t sparse_max_slabs, int two_step, uint64_t *counts, uint32_t *tiles6, uint64_t tiles_cap,
+                           uint64_t *bands4, uint64_t bands_cap, uint32_t *items4, uint64_t items_cap, uint32_t *slabs2, uint64_t slabs_cap,
+                           uint32_t *chunks2, char *err, size_t cap)
+{
+    Err E{err, cap};
+    if (round_items == 0 || round_items % 256) return E.fail("round_items %u is not a positive multiple of 256", round_items);
+    if (!counts || !tiles6 || !bands4 || !items4 || !slabs2 || !chunks2) return E.fail("every list is wanted");
+    SparseCheck sc;
+    sc.gcnt = gcnt;
+    sc.planes = sparse_planes;
+    sc.cap = sparse_cap;
+    sc.thr = thr;
+    sc.thr_cap = thr_cap;
+    sc.sided = sparse_sided;
+    sc.max_slabs = sparse_max_slabs;
+    CheckJob job = base_job(n, keys, 0, 1, rb, re, nparts, want_parts, p, cum_budget);
+    job.round_items = round_items;
+    job.sc = &sc;
+    job.resolve();
+    Layout L;
+    job_layout(job, L);
+    Tuning tu;
+    PairQuery q;
+    PairPlan pp;
+    for (int i = 0; i < 9; ++i) counts[i] = 0;
+    counts[8] = L.Npad / kTile;
+    if (!job_plan(job, L, tu, q, pp, two_step != 0)) return 0;
+    counts[0] = pp.T.size(), counts[1] = pp.bands.size(), counts[2] = pp.sp_items.size(), counts[3] = pp.slabs.size();
+    counts[4] = pp.sided_items, counts[5] = pp.transposed_items, counts[6] = pp.table_slabs, counts[7] = pp.items.size();
+    if (pp.T.size() > tiles_cap || pp.bands.size() > bands_cap || pp.sp_items.size() > items_cap || pp.slabs.size() > slabs_cap)
+        return E.fail("%zu tiles, %zu bands, %zu items, %zu slabs: no room", pp.T.size(), pp.bands.size(), pp.sp_items.size(), pp.slabs.size());
+    for (size_t t = 0; t < pp.T.size(); ++t) {
+        uint32_t *o = tiles6 + 6 * t;
+        o[0] = pp.T[t].x, o[1] = pp.T[t].y, o[2] = pp.T[t].z, o[3] = pp.T[t].w, o[4] = pp.spb[t], o[5] = pp.sp[t];
+        chunks2[2 * t] = pp.chunks[t].x, chunks2[2 * t + 1] = pp.chunks[t].y;
+    }
+    for (size_t bi = 0; bi < pp.bands.size(); ++bi) {
+        uint64_t *o = bands4 + 4 * bi;
+        o[0] = pp.bands[bi].first, o[1] = pp.bands[bi].second, o[2] = pp.band_sp_items[bi].first, o[3] = pp.band_sp_items[bi].second;
+    }
+    for (size_t k = 0; k < pp.sp_items.size(); ++k) {
+        uint32_t *o = items4 + 4 * k;
+        o[0] = pp.sp_items[k].x, o[1] = pp.sp_items[k].y, o[2] = pp.sp_items[k].z, o[3] = pp.sp_items[k].w;
+    }
+    for (size_t k = 0; k < pp.slabs.size(); ++k) slabs2[2 * k] = pp.slabs[k].x, slabs2[2 * k + 1] = pp.slabs[k].y;
+    return 0;
 }
 
 // the table stagings of one launch of the LDS placement of the sparse counting kernel (plan::sparse_table_fills): items4 = n

@@ -989,43 +989,86 @@ static void order_tiles(const Tuning &tu, PairPlan &pp)
 }
 
 // Launch order of the sparse items [first, last) of a band (a transposed item's table is its ROW block's: read "column
-// block" as table_block() below).
+// block" as the item's table block below).
 // An item gathers from its column block's table (16 bytes per position: 256 KiB at p = 14), which
 // only pays while the table stays in L2; workgroup w runs on XCD w % 8 (xcd_order above).  So every column
-// block is given to ONE XCD -- the blocks with the most items first, each to the XCD with the fewest so far --
-// its items follow each other there, and the eight lists are interleaved one item at a time.
-static void order_sparse_items(const std::vector<U4> &T, const std::pair<size_t, size_t> &bd, uint32_t NT, size_t first, size_t last, std::vector<U4> &sp_items)
+// block is given to ONE XCD -- the blocks with the most items first (stable), each to the XCD with the fewest so far (the
+// lowest on a tie) -- its items follow each other there, by (block ascending, plane descending, ti + tj ascending), stable
+// in emission order, and the eight lists are interleaved one item at a time.
+// Every component of that key is a small integer, so the order is made by counting passes over records that hold the
+// packed key, computed once per item by emit_sparse_items (rec[k] = {table block << 40 | plane << 32 | ti + tj, k}; kr: the
+// range of planes and of ti + tj among them), on scratch the plan keeps: time linear in the items, no comparator.
+struct SpKeyRange {
+    uint32_t pmin = ~0u, pmax = 0, smin = ~0u, smax = 0;
+};
+static void order_sparse_items(uint32_t NT, size_t first, size_t last, const SpKeyRange &kr, PairPlan &pp)
 {
-    if (last - first <= 1) return;
-    // the block whose table an item reads: its column block, the row block of a transposed one
-    auto table_block = [&](const U4 &it) { return it.y & kSpItemTransposed ? T[bd.first + it.x].x : T[bd.first + it.x].y; };
+    const size_t n = last - first;
+    if (n <= 1) return;
     constexpr size_t nx = 8;
-    std::vector<uint32_t> per_col(NT, 0), cols;
-    for (size_t k = first; k < last; ++k) per_col[table_block(sp_items[k])]++;
+    std::vector<PairPlan::SpRec> &ra = pp.sp_rec_a, &rb = pp.sp_rec_b;
+    std::vector<uint32_t> &cnt = pp.sp_cnt, &per_col = pp.sp_per_col, &cols = pp.sp_cols, &by_count = pp.sp_cols_tmp, &brank = pp.sp_brank;
+    // the blocks that have items, ascending, and the most items of any
+    per_col.assign(NT, 0);
+    for (size_t k = 0; k < n; ++k) ++per_col[ra[k].key >> 40];
+    cols.clear();
+    uint32_t maxc = 0;
     for (uint32_t b = 0; b < NT; ++b)
-        if (per_col[b]) cols.push_back(b);
-    std::stable_sort(cols.begin(), cols.end(), [&](uint32_t a, uint32_t b) { return per_col[a] > per_col[b]; });
-    std::vector<uint32_t> xcd_of(NT, 0);
-    size_t load[nx] = {0};
-    for (uint32_t b : cols) {
+        if (per_col[b]) cols.push_back(b), maxc = std::max(maxc, per_col[b]);
+    // ... by item count descending, stable: one counting pass over the counts
+    cnt.assign((size_t)maxc + 1, 0);
+    for (uint32_t b : cols) ++cnt[maxc - per_col[b] + 1];
+    for (size_t v = 1; v <= maxc; ++v) cnt[v] += cnt[v - 1];
+    by_count.resize(cols.size());
+    for (uint32_t b : cols) by_count[cnt[maxc - per_col[b]]++] = b;
+    // each to the least loaded of the eight lists; brank[b]: the list of block b, then its place among the blocks in
+    // the order (list, block ascending) -- the leading component of the key
+    brank.resize(NT);
+    size_t load[nx] = {0}, nblk[nx] = {0}, at[nx];
+    for (uint32_t b : by_count) {
         size_t x = 0;
         for (size_t y = 1; y < nx; ++y)
             if (load[y] < load[x]) x = y;
-        xcd_of[b] = (uint32_t)x;
+        brank[b] = (uint32_t)x;
         load[x] += per_col[b];
+        ++nblk[x];
     }
-    std::vector<U4> lists[nx];
-    for (size_t k = first; k < last; ++k) lists[xcd_of[table_block(sp_items[k])]].push_back(sp_items[k]);
-    for (auto &l : lists)
-        std::stable_sort(l.begin(), l.end(), [&](const U4 &a, const U4 &b) {
-            const U4 &ta = T[bd.first + a.x], &tb = T[bd.first + b.x];
-            const uint32_t ca = table_block(a), cb = table_block(b), pa = a.y & kSpPlaneMask, pb = b.y & kSpPlaneMask;
-            return ca != cb ? ca < cb : pa != pb ? pa > pb : ta.x + ta.y < tb.x + tb.y;
-        });
-    size_t q = first;
-    for (size_t r = 0; q < last; ++r)
+    at[0] = 0;
+    for (size_t x = 1; x < nx; ++x) at[x] = at[x - 1] + nblk[x - 1];
+    for (uint32_t b : cols) brank[b] = (uint32_t)at[brank[b]]++;
+    // the sort: least significant digit first, every pass stable.  (plane descending, ti + tj ascending) is one digit
+    // where its range is small, else two; the block's place is the last
+    const uint64_t srange = (uint64_t)kr.smax - kr.smin + 1, prange = (uint64_t)kr.pmax - kr.pmin + 1;
+    auto pass = [&](std::vector<PairPlan::SpRec> &src, std::vector<PairPlan::SpRec> &dst, size_t nb, auto digit) {
+        cnt.assign(nb + 1, 0);
+        for (size_t k = 0; k < n; ++k) ++cnt[digit(src[k].key) + 1];
+        for (size_t v = 1; v <= nb; ++v) cnt[v] += cnt[v - 1];
+        dst.resize(n);
+        for (size_t k = 0; k < n; ++k) dst[cnt[digit(src[k].key)]++] = src[k];
+    };
+    const uint32_t pmax = kr.pmax, smin = kr.smin;
+    auto d_s = [&](uint64_t key) { return (size_t)((uint32_t)key - smin); };
+    auto d_p = [&](uint64_t key) { return (size_t)(pmax - (uint32_t)((key >> 32) & 0xFFu)); };
+    if (srange * prange <= (1u << 16)) {
+        pass(ra, rb, (size_t)(srange * prange), [&](uint64_t key) { return d_p(key) * (size_t)srange + d_s(key); });
+    } else {
+        pass(ra, rb, (size_t)srange, d_s);
+        pass(rb, ra, (size_t)prange, d_p);
+        ra.swap(rb);
+    }
+    pass(rb, ra, cols.size(), [&](uint64_t key) { return (size_t)brank[key >> 40]; });
+    // list x is now ra[off[x] .. off[x] + load[x]); one item of each in turn
+    size_t off[nx];
+    off[0] = 0;
+    for (size_t x = 1; x < nx; ++x) off[x] = off[x - 1] + load[x - 1];
+    std::vector<U4> &tmp = pp.sort_tmp;
+    tmp.resize(n);
+    U4 *I = pp.sp_items.data() + first;
+    size_t q = 0;
+    for (size_t r = 0; q < n; ++r)
         for (size_t x = 0; x < nx; ++x)
-            if (r < lists[x].size()) sp_items[q++] = lists[x][r];
+            if (r < load[x]) tmp[q++] = I[ra[off[x] + r].idx];
+    std::copy(tmp.begin(), tmp.end(), I);
 }
 
 uint64_t sparse_table_fills(const U4 *items, size_t n, uint32_t run)
@@ -1044,9 +1087,10 @@ uint64_t sparse_table_fills(const U4 *items, size_t n, uint32_t run)
     return fills;
 }
 
-// sparse routing: band by band (the automatic rule looks at the band), the routed planes of every tile, one sparse item
-// each -- ordered by column block, whose table the items of a column share in L2 -- and the slabs they read.  One loop for
-// both routes: a two-plane item has no flags and lists on both blocks, a sided item its polarities and transposition.
+// sparse routing, the DECISIONS: band by band (the automatic rule looks at the band), the planes of every tile that leave
+// the tile kernel (sp, spb) and the slabs their items will read -- made here, in the order of the items' emission, because
+// a tile routes only while the call has room for its slabs (sparse_max_slabs) and because that order is the slabs' indices.
+// This is all the dense path needs (chunk_ranges); the items themselves are emit_sparse_items'.
 static void route_sparse(const Layout &L, const Tuning &tu, const SparseGate &gate, PairPlan &pp)
 {
     const std::vector<U4> &T = pp.T;
@@ -1054,27 +1098,24 @@ static void route_sparse(const Layout &L, const Tuning &tu, const SparseGate &ga
     pp.sp.assign(T.size(), 0);
     pp.spb.assign(T.size(), 0);
     pp.sided_items = pp.transposed_items = pp.table_slabs = 0;
+    pp.sp_count = 0;
     pp.band_sp_items.assign(pp.bands.size(), std::make_pair((size_t)0, (size_t)0));
+    pp.band_route.assign(pp.bands.size(), (uint8_t)Route::None);
     if (!gate.any()) return;
     pp.slab_of.assign((size_t)NT * std::max<uint32_t>(L.P, 1), -1);
-    std::vector<uint8_t> listed;  // per slab: an item reads lists from it
-    auto slab = [&](uint32_t b, uint32_t pl, bool lists) -> uint32_t {
+    auto slab = [&](uint32_t b, uint32_t pl) {
         int32_t &s = pp.slab_of[(size_t)b * L.P + pl];
-        if (s < 0) {
-            s = (int32_t)pp.slabs.size();
-            // (the two-plane route's sets are U: where the thresholds are this plan's, that is what sided_polarity says too)
-            pp.slabs.push_back(U2{b, pl | (gate.sided_can && sided_polarity(L, b, L.pbase + 1 + (int)pl) ? kSpSlabA : 0u)});
-            listed.push_back(0);
-        }
-        if (lists) listed[(size_t)s] = 1;
-        return (uint32_t)s;
+        if (s >= 0) return;
+        s = (int32_t)pp.slabs.size();
+        // (the two-plane route's sets are U: where the thresholds are this plan's, that is what sided_polarity says too)
+        pp.slabs.push_back(U2{b, pl | (gate.sided_can && sided_polarity(L, b, L.pbase + 1 + (int)pl) ? kSpSlabA : 0u)});
     };
     for (size_t bi = 0; bi < pp.bands.size(); ++bi) {
         const auto &bd = pp.bands[bi];
-        const size_t i0 = pp.sp_items.size();
         uint64_t band_planes = 0;
         for (size_t t = bd.first; t < bd.second; ++t) band_planes += T[t].w - T[t].z;
         const Route route = gate.route_for(band_planes);
+        pp.band_route[bi] = (uint8_t)route;
         for (size_t t = bd.first; t < bd.second && route != Route::None; ++t) {
             uint32_t below, above;
             tile_route(L, gate, route, T[t], below, above);
@@ -1082,12 +1123,49 @@ static void route_sparse(const Layout &L, const Tuning &tu, const SparseGate &ga
             if (!k || pp.slabs.size() + 2 * k > tu.sparse_max_slabs) continue;
             pp.sp[t] = (uint8_t)above;
             pp.spb[t] = (uint8_t)below;
+            pp.sp_count += k;
+            // (plane by plane as the items will come, the row block's slab before the column block's)
+            for (uint32_t x = 0; x < k; ++x) {
+                const uint32_t pl = x < above ? T[t].w - 1 - x : T[t].z + (x - above);
+                slab(T[t].x, pl);
+                slab(T[t].y, pl);
+            }
+        }
+    }
+}
+
+// sparse routing, the EMISSION: one sparse item for every plane route_sparse took from a tile, band by band in launch
+// order (order_sparse_items: by column block, whose table the items of a column share in L2), and which slabs only serve as
+// tables.  One loop for both routes: a two-plane item has no flags and lists on both blocks, a sided item its polarities
+// and transposition.
+void emit_sparse_items(const Layout &L, PairPlan &pp)
+{
+    const std::vector<U4> &T = pp.T;
+    const uint32_t NT = L.Npad / kTile;
+    pp.sp_items.clear();
+    pp.sided_items = pp.transposed_items = pp.table_slabs = 0;
+    pp.band_sp_items.assign(pp.bands.size(), std::make_pair((size_t)0, (size_t)0));
+    if (!pp.sp_count) return;
+    pp.sp_items.reserve(pp.sp_count);
+    std::vector<uint8_t> &listed = pp.sp_listed;  // per slab: an item reads lists from it
+    listed.assign(pp.slabs.size(), 0);
+    std::vector<PairPlan::SpRec> &rec = pp.sp_rec_a;
+    for (size_t bi = 0; bi < pp.bands.size(); ++bi) {
+        const auto &bd = pp.bands[bi];
+        const size_t i0 = pp.sp_items.size();
+        const bool sided = pp.band_route[bi] == (uint8_t)Route::Sided;
+        SpKeyRange kr;
+        rec.clear();
+        for (size_t t = bd.first; t < bd.second && pp.band_route[bi] != (uint8_t)Route::None; ++t) {
+            const uint32_t above = pp.sp[t], k = above + pp.spb[t];
+            const uint32_t s = T[t].x + T[t].y;
+            if (k) kr.smin = std::min(kr.smin, s), kr.smax = std::max(kr.smax, s);
             for (uint32_t x = 0; x < k; ++x) {
                 const uint32_t pl = x < above ? T[t].w - 1 - x : T[t].z + (x - above);
                 bool tr = false;               // the list side is the column block
                 bool both = true;              // both blocks carry lists (the two-plane route)
                 uint32_t fl = 0;
-                if (route == Route::Sided) {
+                if (sided) {
                     const int v = L.pbase + 1 + (int)pl;
                     tr = T[t].x != T[t].y && sided_depth(L, T[t].y, v) > sided_depth(L, T[t].x, v);
                     both = T[t].x == T[t].y;
@@ -1096,16 +1174,23 @@ static void route_sparse(const Layout &L, const Tuning &tu, const SparseGate &ga
                     ++pp.sided_items;
                     pp.transposed_items += tr;
                 }
-                // (braces: the row block's slab is made before the column block's -- the order decides the slab indices)
-                pp.sp_items.push_back(U4{(uint32_t)(t - bd.first), pl | fl, slab(T[t].x, pl, both || !tr), slab(T[t].y, pl, both || tr)});
+                const uint32_t si = (uint32_t)pp.slab_of[(size_t)T[t].x * L.P + pl], sj = (uint32_t)pp.slab_of[(size_t)T[t].y * L.P + pl];
+                if (both || !tr) listed[si] = 1;
+                if (both || tr) listed[sj] = 1;
+                // the block whose table the item reads: its column block, the row block of a transposed one
+                rec.push_back(PairPlan::SpRec{(uint64_t)(tr ? T[t].x : T[t].y) << 40 | (uint64_t)pl << 32 | s, (uint32_t)(pp.sp_items.size() - i0)});
+                kr.pmin = std::min(kr.pmin, pl), kr.pmax = std::max(kr.pmax, pl);
+                pp.sp_items.push_back(U4{(uint32_t)(t - bd.first), pl | fl, si, sj});
             }
         }
-        order_sparse_items(T, bd, NT, i0, pp.sp_items.size(), pp.sp_items);
+        order_sparse_items(NT, i0, pp.sp_items.size(), kr, pp);
         pp.band_sp_items[bi] = std::make_pair(i0, pp.sp_items.size());
     }
     // a slab that only serves as a table needs no lists (the sided route only: the two-plane route lists both blocks)
-    for (size_t k = 0; k < pp.slabs.size(); ++k)
+    for (size_t k = 0; k < pp.slabs.size(); ++k) {
+        pp.slabs[k].y &= ~kSpSlabTableOnly;
         if (!listed[k]) pp.slabs[k].y |= kSpSlabTableOnly, ++pp.table_slabs;
+    }
 }
 
 // chunk range of every tile (the work items of a band are cut from these: build_band_items); the planes routed sparse
@@ -1140,6 +1225,8 @@ bool build_tiles(const Layout &L, const PairQuery &job, const Tuning &tu, PairPl
     pp.sp_items.clear();
     pp.band_sp_items.clear();
     pp.slabs.clear();
+    pp.band_route.clear();
+    pp.sp_count = 0;
     pp.nparts = 0;
     pp.max_band = 0;
     std::vector<size_t> trow_first;  // (wanted tile rows of a sorted layout) first tile of the tile row ...
@@ -1285,6 +1372,7 @@ void build_band_items(const Tuning &tu, PairPlan &pp, size_t bi)
 bool build_pairs(const Layout &L, const PairQuery &q, const Tuning &t, PairPlan &pp)
 {
     if (!build_tiles(L, q, t, pp)) return false;
+    emit_sparse_items(L, pp);
     for (size_t bi = 0; bi < pp.bands.size(); ++bi) build_band_items(t, pp, bi);
     return true;
 }

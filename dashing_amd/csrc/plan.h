@@ -12,9 +12,10 @@
 //   * PairPlan: tiles, bands (bounded by the C(v) scratch), segments (tiles of one part inside one band: one k_finalize
 //     launch each), work items of the tile kernel, and the two device tile lists.  build_tiles is a sequence of steps in
 //     plan.cpp, each filling what it owns: list_tiles (the tile list), sparse_gate (which calls may route sparse at all),
-//     part_starts, tail_cuts, cut_bands, cut_segments, order_tiles (rank and the XCD order), route_sparse (both sparse
-//     routes, through one tile_route and one item loop; order_sparse_items), chunk_ranges.  The items of a band follow
-//     one piece rule (band_shape, pieces_of) in build_band_items and band_item_count.
+//     part_starts, tail_cuts, cut_bands, cut_segments, order_tiles (rank and the XCD order), route_sparse (what both sparse
+//     routes take from every tile, through one tile_route, and the slabs), chunk_ranges.  The sparse items themselves
+//     come from emit_sparse_items (one item loop for both routes; order_sparse_items), which only the sparse kernels
+//     wait for.  The items of a band follow one piece rule (band_shape, pieces_of) in build_band_items and band_item_count.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -339,6 +340,17 @@ struct PairPlan {
     std::vector<std::pair<size_t, size_t>> band_sp_items;  // sparse item ranges of the bands
     std::vector<U2> slabs;                               // {block, plane | kSpSlab* flags}: the (table, row lists) the call's sparse items read
     std::vector<int32_t> slab_of;                        // scratch: block * P + plane -> slab, or -1
+    // what build_tiles decides of the sparse routes and emit_sparse_items turns into items: the planes routed in all
+    // (the sum of sp and spb: nothing is emitted for 0), every band's route (0 none, 1 two-plane, 2 sided)
+    uint64_t sp_count = 0;
+    std::vector<uint8_t> band_route;
+    // scratch of emit_sparse_items, kept from call to call like sort_first / sort_tmp: per slab "an item reads lists from
+    // it"; the records of the item sort (the packed key of an item, computed once, and its place in the band) and its
+    // counters; per block its item count and its place among the blocks that have items; those blocks
+    struct SpRec { uint64_t key; uint32_t idx; };
+    std::vector<uint8_t> sp_listed;
+    std::vector<uint32_t> sp_cnt, sp_per_col, sp_cols, sp_cols_tmp, sp_brank;
+    std::vector<SpRec> sp_rec_a, sp_rec_b;
 };
 // the bound on |{t : a_t >= v}| over the sketches of block b (v at most one below the block's T), else 65535
 uint32_t sparse_bound(const Layout &L, uint32_t b, int v);
@@ -349,10 +361,16 @@ int sided_polarity(const Layout &L, uint32_t b, int v);
 
 // returns false when there is nothing to compute
 bool build_pairs(const Layout &L, const PairQuery &q, const Tuning &t, PairPlan &pp);
-// the same in two steps, so that a caller can launch band b while it plans band b + 1 (engine.hip): tiles, bands,
-// segments and chunk ranges of the whole job, then the work items of one band at a time (in band order)
+// the same in steps, so that a caller can launch band b while it plans band b + 1 (engine.hip): tiles, bands,
+// segments and chunk ranges of the whole job -- with the DECISIONS of the sparse routes (sp, spb, the slabs in the order
+// that gives them their indices, sp_count, band_route): everything the dense path needs -- then the work items of one
+// band at a time (in band order)
 bool build_tiles(const Layout &L, const PairQuery &q, const Tuning &t, PairPlan &pp);
 void build_band_items(const Tuning &t, PairPlan &pp, size_t band);
+// the EMISSION of the sparse routes build_tiles decided, behind it (L is build_tiles'): sp_items in launch order band by
+// band, band_sp_items, the table-only marks of the slabs, sided_items / transposed_items / table_slabs.  Only the sparse
+// kernels need it, so engine.hip calls it behind the first band's tile kernel; build_pairs calls it itself.
+void emit_sparse_items(const Layout &L, PairPlan &pp);
 // the two device lists: the tile kernel's {row block, col block, pb | pe << 8, lo | hi << 8} in launch order and
 // k_finalize's {row block, col block, pb | pe << 8 | lo << 16 | hi << 24, index of the tile's C(v) block in its band},
 // every segment row-major
