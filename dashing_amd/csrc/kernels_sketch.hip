@@ -151,7 +151,8 @@ __device__ __forceinline__ uint64_t valid_windows(uint64_t V, int k)
 // min, the guard bit and the + 1; a lane remembers whether one of its high words was zero and applies the exact rule to
 // those k-mers behind the sub-chunk (idempotent max).  A/B in separate processes (profiles/rd6w/sk_ab.jsonl): p = 10
 // 8.72e11 -> 9.48e11 bases/s (+8.7 %), p = 14 +6 %; the path behind the zero word is exercised by k-mers made for it
-// (the hash is invertible: tests/test_gpu_sketch.py::test_kmers_whose_hash_has_32_zero_bits_behind_the_index).
+// (the hash is invertible: tests/test_gpu_sketch.py::test_kmers_whose_hash_has_32_zero_bits_behind_the_index, and
+// tests/test_gpu_sketch_values.py, which holds every instance to the values 32, 33, 34 and q - 1, q, q + 1 at every p).
 template <bool GLOBAL, bool CANON, bool REG32, int KC, int NT>
 __global__ __launch_bounds__(NT) void k_sketch(const uint8_t *__restrict__ seq,
                                                  const SketchWork *__restrict__ work, int k,

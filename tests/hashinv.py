@@ -1,5 +1,6 @@
 """The inverse of Thomas Wang's 64-bit hash and the reverse complement of a 2-bit k-mer: helpers of the tests that MAKE k-mers
-with a wanted hash (tests/test_gpu_sketch.py::test_kmers_whose_hash_has_32_zero_bits_behind_the_index); checked against the
+with a wanted hash (tests/test_gpu_sketch.py::test_kmers_whose_hash_has_32_zero_bits_behind_the_index, and tests/kmer_cases.py,
+the maker of a k-mer for any (precision, index, value)); checked against the
 Python oracle on the CPU by tests/test_oracle.py::test_wang_hash_inverse."""
 _M64 = (1 << 64) - 1
 
