@@ -8,6 +8,7 @@ import collections
 import ctypes as C
 import math
 import os
+import re
 
 import numpy as np
 
@@ -35,6 +36,7 @@ SYMBOLS = [
     "dsh_backend_name", "dsh_device_count", "dsh_create", "dsh_destroy", "dsh_last_error",
     "dsh_synchronize", "dsh_sketches_alloc", "dsh_upload_sketches", "dsh_download_sketches", "dsh_copy_sketches_device",
     "dsh_attach_device_sketches", "dsh_sketch_batch", "dsh_sketch_batch_async", "dsh_sketch_batch_device", "dsh_sketch_fastx_batch_async",
+    "dsh_sketch_fastx_records",
     "dsh_sketch_records", "dsh_sketch_records_async", "dsh_sketch_records_device",
     "dsh_clear_sketches", "dsh_cardinalities", "dsh_dist_rows", "dsh_dist_rows_device",
     "dsh_dist_rows_async", "dsh_dist_rows_device_async", "dsh_wait", "dsh_wait_event",
@@ -57,6 +59,7 @@ SYMBOLS = [
 
 
 ERANGE = -34  # DSH_ERANGE: dist_threshold_device's capacity was too small (the exception carries n_hits)
+_NAME = re.compile(rb"[^ \t\n\v\f\r]*")  # a record's kseq name: the bytes behind '>' / '@' up to the first isspace byte
 
 
 class DshError(RuntimeError):
@@ -125,6 +128,7 @@ def load_library():
     lib.dsh_sketch_batch.argtypes = [vp, vp, vp, C.c_uint32, u64, i32, i32, vp]
     lib.dsh_sketch_batch_async.argtypes = [vp, vp, vp, C.c_uint32, u64, i32, i32]
     lib.dsh_sketch_fastx_batch_async.argtypes = [vp, vp, vp, vp, C.c_uint32, u64, i32, i32, vp]
+    lib.dsh_sketch_fastx_records.argtypes = [vp, vp, vp, vp, C.c_uint32, vp, i32, i32, vp, vp, vp]
     lib.dsh_sketch_batch_device.argtypes = [vp, vp, vp, C.c_uint32, u64, i32, i32]
     lib.dsh_sketch_records.argtypes = [vp, vp, vp, C.c_uint32, u64, i32, i32, vp]
     lib.dsh_sketch_records_async.argtypes = [vp, vp, vp, C.c_uint32, u64, i32, i32]
@@ -638,6 +642,60 @@ class Context:
             self._h, raw.ctypes.data, off.ctypes.data, lens.ctypes.data, ng, first_slot, k, int(bool(canon)), status.ctypes.data))
         self.wait()
         return status[:ng]
+
+    @staticmethod
+    def _fastx_regions(files):
+        """the raw buffer of the fastx entry points: every file in a region of its own that starts on a multiple of 32"""
+        ng = len(files)
+        off = np.zeros(ng + 1, np.uint64)
+        lens = np.array([len(f) for f in files], np.uint64).reshape(ng)
+        for g in range(ng):
+            off[g + 1] = off[g] + ((int(lens[g]) + 1 + 31) & ~31)
+        raw = np.full(max(int(off[-1]), 1), 0x4E, np.uint8)
+        for g, f in enumerate(files):
+            raw[int(off[g]): int(off[g]) + len(f)] = np.frombuffer(f, np.uint8)
+        return raw, off, lens
+
+    def sketch_fastx_records(self, files, slot_ptr=None, k=31, canon=True):
+        """Per-record sketches of raw FASTA / FASTQ texts, parsed on the device (dsh_sketch_fastx_records).  files: one
+        bytes object per file; slot_ptr[len(files) + 1]: file f owns the rows [slot_ptr[f], slot_ptr[f + 1]), its record
+        r goes to row slot_ptr[f] + r.  Returns (status, n_rec, names): status[f] != 0 = refused (no row written, n_rec[f] =
+        0: parse it on the host and use sketch_records), n_rec[f] = the file's records, names = one bytes object per slot
+        of the span (b"" for the slots of a refused file).  slot_ptr None: count only -- nothing is sketched, names is
+        None, and no matrix is needed.  A count that differs from its span raises DshError with code ERANGE, the
+        complete counts in its attribute n_rec and the status words in status; no row was written."""
+        nf = len(files)
+        raw, off, lens = self._fastx_regions(files)
+        status = np.zeros(max(nf, 1), np.uint32)
+        n_rec = np.zeros(max(nf, 1), np.uint64)
+        sp = hdr = None
+        if slot_ptr is not None:
+            sp = np.ascontiguousarray(slot_ptr, np.uint64).reshape(-1)
+            assert sp.size == nf + 1
+            hdr = np.zeros(max(int(sp[-1]) - int(sp[0]), 1) if sp[-1] >= sp[0] else 1, np.uint64)
+        rc = self._lib.dsh_sketch_fastx_records(
+            self._h, raw.ctypes.data, off.ctypes.data, lens.ctypes.data, nf, sp.ctypes.data if sp is not None else None, k,
+            int(bool(canon)), status.ctypes.data, n_rec.ctypes.data, hdr.ctypes.data if hdr is not None else None)
+        if rc == ERANGE:
+            err = DshError(rc, self._lib.dsh_last_error(self._h).decode())
+            err.n_rec, err.status = n_rec[:nf].copy(), status[:nf].copy()
+            raise err
+        self._ck(rc)
+        if sp is None:
+            return status[:nf], n_rec[:nf], None
+        buf = raw.tobytes()
+        names = [b""] * (int(sp[-1]) - int(sp[0]))
+        for f in range(nf):
+            end = int(off[f]) + int(lens[f])
+            for r in range(int(n_rec[f])):
+                e = int(sp[f]) - int(sp[0]) + r
+                names[e] = _NAME.match(buf, int(hdr[e]) + 1, end).group()
+        return status[:nf], n_rec[:nf], names
+
+    def count_fastx_records(self, files):
+        """(status, n_rec) of sketch_fastx_records in count-only mode: the early refusals and every file's record count"""
+        status, n_rec, _ = self.sketch_fastx_records(files, None)
+        return status, n_rec
 
     def sketch_batch_device(self, seq_ptr, genome_off, first_slot=0, k=31, canon=True):
         off = np.ascontiguousarray(genome_off, np.uint64)

@@ -290,6 +290,7 @@ struct dsh_ctx {
         DevBuf seqbuf, workbuf, recbuf;  // (workbuf: dsh_unpermute_blocks_device of abi.hip borrows it for its per-tile deltas)
         Staging work, rec;
         DevBuf rawbuf, fx_tab, fx_summ, fx_state, fx_declen, fx_status;
+        DevBuf fx_rec;  // dsh_sketch_fastx_records: the record index and its scratch
         Staging fx;
     } sketch;
     // dsh_dist_threshold* (threshold.hip): a band's per-chunk counts and offsets, the running total, and for the host forms

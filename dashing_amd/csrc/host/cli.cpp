@@ -17,6 +17,7 @@
 #include <algorithm>
 #include <cstdarg>
 #include <chrono>
+#include <functional>
 #include <future>
 #include <memory>
 #include <cstdio>
@@ -75,7 +76,7 @@ static void usage(const char *sub)
         std::fprintf(stderr, "  (by-seq: every sequence RECORD of every input, in input order, is one sketch, labelled by its name -- the\n"
                              "   header up to the first space or tab; sketch_by_seq writes them with -o into this tool's own `sketch -o`\n"
                              "   container + FILE.labels.gz, not upstream's by-seq layout; dist_by_seq --presketched FILE reads that back;\n"
-                             "   dist_by_seq refuses -Q, more than one device and -W)\n");
+                             "   dist_by_seq refuses -Q, more than one device and -W; DSH_DEVICE_PARSE=1: plain files are parsed on the device)\n");
     if (!std::strcmp(sub, "sketch") || !std::strcmp(sub, "sketch_by_seq")) {
         std::fprintf(stderr, "  -c, --skip-cached        skip genomes whose .hll already exists\n"
                              "  -o FILE                  write all sketches into one file (+ FILE.labels.gz) instead of one .hll per genome\n");
@@ -1113,14 +1114,15 @@ static std::vector<std::string> read_labels_gz(const std::string &path)
     return v;
 }
 
-// the records into slots [first, first + n): batches of at most kRecordsBatchBytes bases (or one record, if longer)
+// the records (all, or [rb, re)) into slots [first, first + n): batches of at most kRecordsBatchBytes bases (or one record, if longer)
 // through two page-locked buffers that take turns behind tickets, dsh_sketch_records_async (rows overwritten)
 static const size_t kRecordsBatchBytes = (size_t)256 << 20;
-static void sketch_records_batched(dsh_ctx *ctx, const Records &R, uint64_t first, int k, int canon)
+static void sketch_records_batched(dsh_ctx *ctx, const Records &R, uint64_t first, int k, int canon, size_t rb = 0, size_t re = (size_t)-1)
 {
-    const size_t n = R.names.size();
+    const size_t n = std::min(re, R.names.size());  // (the records [rb, n) into the slots from `first` on)
+    if (rb >= n) return;
     size_t cap = kRecordsBatchBytes;
-    for (size_t r = 0; r < n; ++r) cap = std::max<size_t>(cap, R.off[r + 1] - R.off[r]);
+    for (size_t r = rb; r < n; ++r) cap = std::max<size_t>(cap, R.off[r + 1] - R.off[r]);
     cap = std::min<size_t>(cap, std::max<size_t>(R.seq.size(), 1));
     uint8_t *buf[2] = {(uint8_t *)dsh_alloc_host(cap), (uint8_t *)dsh_alloc_host(cap)};
     if (!buf[0] || !buf[1]) die("could not allocate %zu bytes of pinned host memory", cap);
@@ -1128,7 +1130,7 @@ static void sketch_records_batched(dsh_ctx *ctx, const Records &R, uint64_t firs
     bool used[2] = {false, false};
     std::vector<uint64_t> off;
     int b = 0;
-    for (size_t r0 = 0; r0 < n;) {
+    for (size_t r0 = rb; r0 < n;) {
         size_t r1 = r0 + 1;
         while (r1 < n && R.off[r1 + 1] - R.off[r0] <= cap && r1 - r0 < ((size_t)1 << 30)) ++r1;
         if (used[b]) DSH(ctx, dsh_event_wait(ctx, ticket[b]));
@@ -1136,7 +1138,7 @@ static void sketch_records_batched(dsh_ctx *ctx, const Records &R, uint64_t firs
         if (bytes) std::memcpy(buf[b], R.seq.data() + R.off[r0], bytes);
         off.assign(R.off.begin() + r0, R.off.begin() + r1 + 1);
         for (auto &x : off) x -= R.off[r0];
-        DSH(ctx, dsh_sketch_records_async(ctx, buf[b], off.data(), (uint32_t)(r1 - r0), first + r0, k, canon));
+        DSH(ctx, dsh_sketch_records_async(ctx, buf[b], off.data(), (uint32_t)(r1 - r0), first + (r0 - rb), k, canon));
         DSH(ctx, dsh_event_record(ctx, &ticket[b]));
         used[b] = true;
         b ^= 1;
@@ -1145,6 +1147,194 @@ static void sketch_records_batched(dsh_ctx *ctx, const Records &R, uint64_t firs
     DSH(ctx, dsh_wait(ctx));
     dsh_free_host(buf[0]);
     dsh_free_host(buf[1]);
+}
+
+
+// The same with the parse on the device (dsh_sketch_fastx_records), for plain regular files; compressed
+// inputs, pipes and what the device refuses keep the host parser.  Two passes over the inputs, each in batches of raw bytes
+// through two page-locked buffers that take turns (the next batch is read while the device works on this one; a file is
+// never split: the buffers hold the largest):
+//   1. count-only calls: every file's verdict and record count; the refused and the other files are parsed on the host now.
+//      Then every file's first slot is known and the matrix is allocated.
+//   2. the accepted files again, into their slots, their names read from the staged bytes; the host-parsed files through
+//      sketch_records_batched into theirs.
+// names and rows ([n][2^S], downloaded) keep the inputs' order and the records' order inside a file.  false: nothing is to
+// be used -- a file changed between the passes or was refused only by the full decode (a FASTQ record whose quality has
+// another length than its sequence): the caller takes the host path for the whole run.
+// Off by default: the host path is, until measurements say otherwise; DSH_DEVICE_PARSE=1 selects
+// this one, DSH_HOST_PARSE=1 overrules it as for `sketch` / `dist`.
+static const bool g_records_device_parse = g_device_parse && std::getenv("DSH_DEVICE_PARSE") != nullptr;
+
+struct RawBatch {
+    size_t f0, f1;  // the inputs [f0, f1), all of them staged
+};
+static uint64_t raw_region(uint64_t size) { return (size + 1 + 31) & ~(uint64_t)31; }
+// runs of consecutive inputs with take[i] set, cut where the regions would exceed cap
+static std::vector<RawBatch> raw_batches(const std::vector<uint64_t> &size, const std::vector<char> &take, uint64_t cap)
+{
+    std::vector<RawBatch> out;
+    for (size_t f = 0; f < size.size();) {
+        if (!take[f]) {
+            ++f;
+            continue;
+        }
+        size_t e = f;
+        uint64_t bytes = 0;
+        while (e < size.size() && take[e] && (e == f || bytes + raw_region(size[e]) <= cap) && e - f < ((size_t)1 << 20)) bytes += raw_region(size[e++]);
+        out.push_back(RawBatch{f, e});
+        f = e;
+    }
+    return out;
+}
+
+static bool device_records(const Opts &o, dsh_ctx *ctx, std::vector<std::string> &names, std::vector<uint8_t> &rows)
+{
+    const double t0 = now_s();
+    const size_t nf = o.inpaths.size();
+    std::vector<uint64_t> size(nf, 0), count(nf, 0);
+    std::vector<char> dev(nf, 0);
+    uint64_t cap = kRecordsBatchBytes, total_raw = 0;
+    for (size_t f = 0; f < nf; ++f) {
+        struct stat st;
+        if (::stat(o.inpaths[f].c_str(), &st) != 0) die("Could not open %s", o.inpaths[f].c_str());
+        if (!S_ISREG(st.st_mode) || is_gzip_file(o.inpaths[f])) continue;
+        dev[f] = 1;
+        size[f] = (uint64_t)st.st_size;
+        cap = std::max(cap, raw_region(size[f]));
+        total_raw += raw_region(size[f]);
+    }
+    cap = std::min(cap, std::max<uint64_t>(total_raw, 32));
+    uint8_t *buf[2] = {(uint8_t *)dsh_alloc_host(cap), (uint8_t *)dsh_alloc_host(cap)};
+    if (!buf[0] || !buf[1]) die("could not allocate %llu bytes of pinned host memory", (unsigned long long)cap);
+    std::vector<uint64_t> boff[2], blen[2];
+    std::atomic<bool> changed{false};  // a file no longer fits the size it had: it grew
+    // a batch's raw bytes into buffer x, every file in its region (sized from its stat: nothing is written behind it)
+    auto stage = [&](const RawBatch &b, int x) {
+        boff[x].assign(1, 0);
+        blen[x].clear();
+        for (size_t f = b.f0; f < b.f1; ++f) {
+            size_t len = 0;
+            const long rc = read_raw_into(o.inpaths[f], buf[x] + boff[x].back(), (size_t)size[f], len);
+            if (rc == -1) die("Could not open %s", o.inpaths[f].c_str());
+            if (rc == -2) changed = true;
+            blen[x].push_back(len);
+            boff[x].push_back(boff[x].back() + raw_region(size[f]));
+        }
+    };
+    // fn(batch, buffer) for every batch, the next one being read meanwhile; false as soon as fn says so
+    auto for_batches = [&](const std::vector<RawBatch> &bs, const std::function<bool(const RawBatch &, int)> &fn) {
+        if (bs.empty()) return true;
+        stage(bs[0], 0);
+        for (size_t i = 0; i < bs.size(); ++i) {
+            std::future<void> next;
+            if (i + 1 < bs.size()) next = std::async(std::launch::async, [&, i]() { stage(bs[i + 1], (int)((i + 1) & 1)); });
+            const bool go = !changed && fn(bs[i], (int)(i & 1));
+            if (next.valid()) next.get();
+            if (!go || changed) return false;
+        }
+        return true;
+    };
+    auto done = [&](bool ok) {
+        dsh_free_host(buf[0]);
+        dsh_free_host(buf[1]);
+        return ok;
+    };
+    std::vector<uint32_t> status;
+    std::vector<uint64_t> nrec;
+
+    // pass 1: verdicts and counts
+    if (!for_batches(raw_batches(size, dev, cap), [&](const RawBatch &b, int x) {
+            const uint32_t n = (uint32_t)(b.f1 - b.f0);
+            status.assign(n, 0);
+            nrec.assign(n, 0);
+            DSH(ctx, dsh_sketch_fastx_records(ctx, buf[x], boff[x].data(), blen[x].data(), n, nullptr, o.k, o.canon, status.data(), nrec.data(), nullptr));
+            for (uint32_t i = 0; i < n; ++i) {
+                if (status[i]) dev[b.f0 + i] = 0;
+                else count[b.f0 + i] = nrec[i];
+            }
+            return true;
+        }))
+        return done(false);
+    const double t1 = now_s();
+    Records H;  // the records of the files the host parses, file after file
+    std::vector<size_t> hfirst(nf + 1, 0);
+    for (size_t f = 0; f < nf; ++f) {
+        hfirst[f] = H.names.size();
+        if (dev[f]) continue;
+        std::vector<uint64_t> st;
+        if (append_fastx_records(o.inpaths[f], H.seq, st, H.names) < 0) die("Could not open %s", o.inpaths[f].c_str());
+        H.off.insert(H.off.end(), st.begin(), st.end());
+        count[f] = H.names.size() - hfirst[f];
+    }
+    hfirst[nf] = H.names.size();
+    H.off.push_back(H.seq.size());
+    std::vector<uint64_t> slot0(nf + 1, 0);
+    for (size_t f = 0; f < nf; ++f) slot0[f + 1] = slot0[f] + count[f];
+    const uint64_t total = slot0[nf];
+    if (total == 0) die("No sequence records in the inputs.");
+    const double t2 = now_s();
+    DSH(ctx, dsh_sketches_alloc(ctx, total, o.S));
+    names.assign(total, std::string());
+
+    // pass 2: the accepted files into their slots
+    std::vector<uint64_t> hdr;
+    if (!for_batches(raw_batches(size, dev, cap), [&](const RawBatch &b, int x) {
+            const uint32_t n = (uint32_t)(b.f1 - b.f0);
+            status.assign(n, 0);
+            nrec.assign(n, 0);
+            hdr.assign((size_t)(slot0[b.f1] - slot0[b.f0]) + 1, 0);
+            const int rc = dsh_sketch_fastx_records(ctx, buf[x], boff[x].data(), blen[x].data(), n, slot0.data() + b.f0, o.k, o.canon, status.data(),
+                                                    nrec.data(), hdr.data());
+            if (rc == DSH_ERANGE) return false;  // (the file is not what pass 1 counted)
+            if (rc) die("[dashing-amd] dsh_sketch_fastx_records failed (%d): %s", rc, dsh_last_error(ctx));
+            for (uint32_t i = 0; i < n; ++i) {
+                if (status[i]) return false;  // (refused by the full decode only)
+                const size_t f = b.f0 + i;
+                const char *end = (const char *)buf[x] + boff[x][i] + blen[x][i];
+                for (uint64_t r = 0; r < count[f]; ++r) {
+                    const char *p = (const char *)buf[x] + hdr[(size_t)(slot0[f] - slot0[b.f0] + r)] + 1;
+                    names[(size_t)(slot0[f] + r)].assign(p, fastx_name_len(p, (size_t)(end - p)));
+                }
+            }
+            return true;
+        }))
+        return done(false);
+    const double t3 = now_s();
+    size_t ndev = 0;
+    for (size_t f = 0; f < nf; ++f) {
+        ndev += dev[f] ? 1 : 0;
+        if (dev[f]) continue;
+        for (size_t r = hfirst[f]; r < hfirst[f + 1]; ++r) names[(size_t)slot0[f] + (r - hfirst[f])] = H.names[r];
+        sketch_records_batched(ctx, H, slot0[f], o.k, o.canon, hfirst[f], hfirst[f + 1]);
+    }
+    rows.resize((size_t)total << o.S);
+    DSH(ctx, dsh_download_sketches(ctx, 0, total, rows.data()));
+    if (g_timing) {
+        std::fprintf(stderr, "[timing] by_seq: %zu files (%llu records) decoded on the device, %zu files (%zu records) on the host\n", ndev,
+                     (unsigned long long)(total - H.names.size()), nf - ndev, H.names.size());
+        std::fprintf(stderr, "[timing] by_seq: count pass %.3f s, host parse %.3f s, sketch pass %.3f s, host files + download %.3f s\n", t1 - t0,
+                     t2 - t1, t3 - t2, now_s() - t3);
+    }
+    return done(true);
+}
+
+// names and rows of every record of the inputs through device_records, on a context of its own; false: take the host path
+static bool records_by_device(const Opts &o, std::vector<std::string> &names, std::vector<uint8_t> &rows)
+{
+    if (!g_records_device_parse) return false;
+    const double t0 = now_s();
+    dsh_ctx *ctx = nullptr;
+    if (int rc = dsh_create(o.device, &ctx)) die("[dashing-amd] no usable gfx950 device (dsh_create = %d); there is no CPU fallback", rc);
+    const bool ok = device_records(o, ctx, names, rows);
+    dsh_destroy(ctx);
+    if (!ok) {
+        names.clear();
+        rows.clear();
+        if (g_timing) std::fprintf(stderr, "[timing] by_seq: an input changed or was refused late; the host parser takes all of them\n");
+    } else if (g_timing) {
+        std::fprintf(stderr, "[timing] by_seq: records on the device path after %.3f s\n", now_s() - t0);
+    }
+    return ok;
 }
 
 static int sketch_by_seq_main(int argc, char **argv)
@@ -1156,6 +1346,13 @@ static int sketch_by_seq_main(int argc, char **argv)
         usage("sketch_by_seq");
     }
     Records R;
+    std::vector<uint8_t> rows;
+    if (records_by_device(o, R.names, rows)) {
+        if (write_hll_multi(output_file, rows.data(), R.names.size(), o.S, o.estim)) die("Failed to write sketches to file");
+        if (write_labels_gz(output_file + ".labels.gz", R.names)) die("Failed to write sequence labels to file");
+        leave(nullptr);
+        return EXIT_SUCCESS;
+    }
     read_records(o, R);
     const size_t n = R.names.size(), m = (size_t)1 << o.S;
     CtxFuture cf(o.device, n, o.S);
@@ -1343,7 +1540,7 @@ static void read_records_or_presketched(DistRun &r)
         if (p != o.S) die("Sketches in %s have p=%d but -S is %d", o.inpaths[0].c_str(), p, o.S);
         r.R.names = read_labels_gz(o.inpaths[0] + ".labels.gz");
         if (r.R.names.size() != cnt) die("%s holds %zu sketches but its labels %zu names", o.inpaths[0].c_str(), cnt, r.R.names.size());
-    } else {
+    } else if (!records_by_device(o, r.R.names, r.pre)) {  // (device-parsed records arrive as rows, like a sketch_by_seq file's)
         read_records(o, r.R);
     }
     o.inpaths = r.R.names;
@@ -1455,7 +1652,7 @@ static void load_records(dsh_ctx *ctx, const DistRun &r)
     const Opts &o = r.o;
     const size_t nrec = r.R.names.size();
     for (size_t s0 = 0; s0 < r.n; s0 += nrec) {
-        if (o.presketched) DSH(ctx, dsh_upload_sketches(ctx, r.pre.data(), s0, nrec));
+        if (!r.pre.empty()) DSH(ctx, dsh_upload_sketches(ctx, r.pre.data(), s0, nrec));
         else sketch_records_batched(ctx, r.R, s0, o.k, o.canon);
     }
 }

@@ -451,8 +451,7 @@ struct FastxParser {
                 break;
             }
             case NAME: {
-                size_t t = i;
-                while (t < N && !std::isspace((unsigned char)buf[t])) ++t;
+                const size_t t = i + fastx_name_len(buf + i, N - i);
                 if (names) names->back().append(buf + i, t - i);
                 if (t > i) got = true;
                 i = t;

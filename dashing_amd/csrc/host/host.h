@@ -45,6 +45,15 @@ long append_fastx_into(const std::string &path, uint8_t *dst, size_t cap, size_t
 // inputs as append_fastx (FASTA, FASTQ also multi-line, gzip, zstd, pipes, CRLF).  Returns the number of records, or -1.
 long append_fastx_records(const std::string &path, std::vector<uint8_t> &out, std::vector<uint64_t> &starts,
                           std::vector<std::string> &names);
+// A record's kseq name: the bytes behind its '>' / '@' up to the first isspace byte (' ', '\t', '\n', '\v', '\f', '\r') or the
+// end of what is there.  p: the first byte behind the header character; returns the name's length.  One rule for the host
+// parser (its NAME state) and for the names the CLI reads from raw bytes the device has indexed (dsh_sketch_fastx_records).
+inline size_t fastx_name_len(const char *p, size_t n)
+{
+    size_t t = 0;
+    while (t < n && !(p[t] == ' ' || (p[t] >= '\t' && p[t] <= '\r'))) ++t;
+    return t;
+}
 // The raw bytes of a plain file, as they lie on disk, appended at dst[len...] (the parse happens on the device:
 // dsh_sketch_fastx_batch_async).  Returns 0, -1 if the file cannot be opened or read, -2 if `cap` would not hold it (the
 // file grew since it was sized).

@@ -90,6 +90,9 @@ long dshh_append_fastx_records(const char *path, uint8_t *out, size_t cap, size_
     return n;
 }
 
+// the length of the kseq name at p[0 .. n): up to the first isspace byte (host.h: fastx_name_len)
+size_t dshh_fastx_name_len(const char *p, size_t n) { return fastx_name_len(p, n); }
+
 // the CLI's streaming loader path: parse straight into caller-owned (page-locked) memory at dst[*len ..), no growth
 long dshh_append_fastx_into(const char *path, uint8_t *dst, size_t cap, size_t *len)
 {

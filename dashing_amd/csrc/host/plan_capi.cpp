@@ -1107,6 +1107,23 @@ bool hand_back(const std::vector<T> &v, void *buf, uint64_t &count)
 
 extern "C" {
 
+// The host arithmetic of dsh_sketch_fastx_records (../sketch_plan.h), for tests/test_fastx_records_plan.py:
+//   dshh_fastx_tail_records   the records to add to a file's markers (-1, 0, +1)
+//   dshh_fastx_line_start     the first byte of the line that holds file[pos]
+//   dshh_fastx_record_offsets off[n + 1] from the markers' decoded positions and the file's decoded end
+int dshh_fastx_tail_records(const uint8_t *file, uint64_t len, uint32_t fmt, uint32_t end_line)
+{
+    return fastx_tail_records(file, len, fmt, end_line);
+}
+uint64_t dshh_fastx_line_start(const uint8_t *file, uint64_t pos) { return fastx_line_start(file, pos); }
+void dshh_fastx_record_offsets(const uint64_t *dpos, uint64_t markers, uint64_t n, uint64_t end, uint64_t *off)
+{
+    std::vector<uint64_t> v;
+    fastx_record_offsets(dpos, markers, n, end, v);
+    std::copy(v.begin(), v.end(), off);
+}
+
+
 // the sketch path's planners (../sketch_plan.h) on a caller's offsets off[n + 1], as sketch.hip runs them behind its checks
 // (tests/test_sketch_plan.py).  kind 0: plan_genomes -> list 0 = SketchWork.  kind 1: plan_records -> lists RecRun, RecSeg, rows to
 // clear (uint32), SketchWork; info[1] = 1 where the records kernel takes the call (0: all n rows are cleared at once, every record

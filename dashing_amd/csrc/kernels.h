@@ -413,6 +413,19 @@ struct FastxSumm {  // what a chunk tells the per-genome scan (kernels_fastx.hip
 hipError_t launch_fastx_decode(hipStream_t st, const uint8_t *raw, const FastxChunk *chunks, uint32_t nchunks,
                                const FastxGenome *genomes, uint32_t ngenomes, FastxSumm *summ, uint4 *state, uint64_t *declen,
                                uint32_t *status, unsigned long long *fingerprint, uint8_t *out);
+// The record index (dsh_sketch_fastx_records): in the decoded stream every record begins with one
+// marker byte -- FASTA a header's first byte, FASTQ the newline that ends a header line, both emitted as 'N' -- which a
+// literal N of a sequence cannot be told from afterwards, so separate instances of the three kernels write them down.  FastxSumm and
+// the genome path's kernels stay as they are.  Positions count from the start of the raw / decoded buffer.
+struct FastxRecIndex {
+    uint32_t *cnt;         // [nchunks][3] scratch: a FASTA chunk's markers under each carry (pass A -> B)
+    uint32_t *nrec;        // [ngenomes][2]: the file's markers; the carry behind its last byte (FASTQ: the line index it ends on)
+    const uint64_t *rec0;  // [ngenomes + 1] a file's first entry and, one further, the end of its entries; NULL: count only
+    uint64_t *dpos, *rpos; // [rec0[ngenomes]] a marker's place in the decoded and in the raw buffer
+};
+hipError_t launch_fastx_decode_records(hipStream_t st, const uint8_t *raw, const FastxChunk *chunks, uint32_t nchunks,
+                                       const FastxGenome *genomes, uint32_t ngenomes, FastxSumm *summ, uint4 *state, uint64_t *declen,
+                                       uint32_t *status, unsigned long long *fingerprint, uint8_t *out, const FastxRecIndex &ix);
 
 // dsh_preload: load the code objects of the kernel translation units now (else: at the first launch from each)
 hipError_t preload_compare_kernels();

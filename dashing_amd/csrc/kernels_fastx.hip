@@ -25,6 +25,11 @@
 // decides those), a FASTQ '\r' that does not vanish or that begins a line (kseq counts it) -- raises the genome's status word:
 // nothing of it is emitted (its region becomes all 'N': no k-mer) and the host parses that file itself.  HBM-bound
 // byte work: no MFMA.
+// The record index (dsh_sketch_fastx_records: one sketch per RECORD).  Every record begins with exactly one marker byte in
+// the decoded stream -- FASTA a header's first byte, FASTQ the newline that ends a header line, both emitted as 'N' --, and
+// a sequence's own N cannot be told from it afterwards: the _rec instances of the three kernels count the markers per
+// chunk (pass A), number every chunk's first one (pass B) and write each marker's decoded and raw position to its file's
+// span of the index (pass C).  The instances without it are the genome path's, unchanged.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -179,6 +184,13 @@ __device__ __forceinline__ uint32_t wave_sum(uint32_t v)
     return v;
 }
 
+// the bit of this lane that is its file's last raw byte (0: the file ends elsewhere).  A header character there starts no
+// record: kseq finds no name behind it and ends the file.  Its 'N' is emitted all the same (harmless), it is not indexed.
+__device__ __forceinline__ uint64_t file_tail_bit(const FastxChunk &ck, const FastxGenome &g, uint32_t at, uint32_t have)
+{
+    return (have && ck.begin + at + have == g.off + g.rawlen) ? 1ull << (have - 1) : 0ull;
+}
+
 }  // namespace
 
 // pass A: every chunk's transfer function and what it emits under each possible carry.
@@ -186,16 +198,22 @@ __device__ __forceinline__ uint32_t wave_sum(uint32_t v)
 //   FASTQ: relative to a carry of 0, a[j] = bytes (no newline, no '\r') on lines of index j, b[j] = newlines that end a line
 //   of index j, bad8 bit j / bit 4 + j = a line of index j is followed by a line that does not begin with '@' / '+', bit 8 + j
 //   = ... by a line that begins with '@', '>' or '+' (k_fastx_offsets, which knows the carry, rotates them into place).
-__global__ __launch_bounds__(256) void k_fastx_scan(const uint8_t *__restrict__ raw, const FastxChunk *__restrict__ chunks,
-                                                     const FastxGenome *__restrict__ genomes, FastxSumm *__restrict__ summ,
-                                                     uint32_t *__restrict__ status)
+//   REC (the record index, dsh_sketch_fastx_records): FASTA also ix.cnt[3 chunk + s] = the record markers under carry s (FASTQ:
+//   b[] holds them already -- a record's marker is the newline that ends a line of index 0).
+namespace {
+template <bool REC>
+__device__ __forceinline__ void fastx_scan(const uint8_t *__restrict__ raw, const FastxChunk *__restrict__ chunks,
+                                           const FastxGenome *__restrict__ genomes, FastxSumm *__restrict__ summ,
+                                           uint32_t *__restrict__ status, const FastxRecIndex &ix)
 {
     __shared__ uint8_t sh[256];
     __shared__ uint32_t acc[9];
+    __shared__ uint32_t racc[REC ? 3 : 1];
     const FastxChunk ck = chunks[blockIdx.x];
     const FastxGenome g = genomes[ck.genome];
     const int t = threadIdx.x;
     if (t < 9) acc[t] = 0;
+    if (REC && t < 3) racc[t] = 0;
     const uint32_t at = (uint32_t)t * 64u;
     const uint32_t have = at < ck.len ? (ck.len - at < 64u ? ck.len - at : 64u) : 0u;
     LaneMasks m;
@@ -222,6 +240,19 @@ __global__ __launch_bounds__(256) void k_fastx_scan(const uint8_t *__restrict__ 
             const uint32_t s = fn_apply(ex, x);
             const uint32_t v = wave_sum(s == FX_HDR ? c[0] : (s == FX_SEQ ? c[1] : c[2]));
             if ((t & 63) == 0) atomicAdd(&acc[x], v);
+        }
+        if constexpr (REC) {
+            // the markers: every header start (the same under HDR and SEQ) but one that is the file's last byte
+            uint64_t h_seq, h_fresh;
+            lane_out(m, FX_SEQ, h_seq);
+            lane_out(m, FX_FRESH, h_fresh);
+            const uint64_t tail = file_tail_bit(ck, g, at, have);
+            const uint32_t r_seq = (uint32_t)__popcll(h_seq & ~tail), r_fresh = (uint32_t)__popcll(h_fresh & ~tail);
+#pragma unroll
+            for (uint32_t x = 0; x < 3; ++x) {
+                const uint32_t v = wave_sum(fn_apply(ex, x) == FX_FRESH ? r_fresh : r_seq);
+                if ((t & 63) == 0) atomicAdd(&racc[x], v);
+            }
         }
     } else {
         if (have && ck.begin + at == g.off && (m.w[0] & 0xFFu) != '@') atomicOr(&status[ck.genome], 1u);
@@ -261,6 +292,21 @@ __global__ __launch_bounds__(256) void k_fastx_scan(const uint8_t *__restrict__ 
         for (int j = 0; j < 4; ++j) o.a[j] = acc[j], o.b[j] = acc[4 + j];
         summ[blockIdx.x] = o;
     }
+    if (REC && g.fmt == 0 && t < 3) ix.cnt[3 * blockIdx.x + t] = racc[t];
+}
+}  // namespace
+
+__global__ __launch_bounds__(256) void k_fastx_scan(const uint8_t *__restrict__ raw, const FastxChunk *__restrict__ chunks,
+                                                     const FastxGenome *__restrict__ genomes, FastxSumm *__restrict__ summ,
+                                                     uint32_t *__restrict__ status)
+{
+    fastx_scan<false>(raw, chunks, genomes, summ, status, FastxRecIndex{});
+}
+__global__ __launch_bounds__(256) void k_fastx_scan_rec(const uint8_t *__restrict__ raw, const FastxChunk *__restrict__ chunks,
+                                                         const FastxGenome *__restrict__ genomes, FastxSumm *__restrict__ summ,
+                                                         uint32_t *__restrict__ status, FastxRecIndex ix)
+{
+    fastx_scan<true>(raw, chunks, genomes, summ, status, ix);
 }
 
 namespace {
@@ -274,16 +320,25 @@ __device__ __forceinline__ uint32_t chunk_emits(const FastxSumm &s, uint32_t fmt
     bad = bad || ((s.bad8 >> ((3u - c) & 3u)) & 1u) || ((s.bad8 >> (4u + ((1u - c) & 3u))) & 1u) || ((s.bad8 >> (8u + ((0u - c) & 3u))) & 1u);
     return s.a[(1u - c) & 3u] + s.b[(0u - c) & 3u];
 }
-}  // namespace
+// ... and its record markers (FASTQ: the newlines that end a header line)
+__device__ __forceinline__ uint32_t chunk_markers(const FastxSumm &s, const uint32_t *__restrict__ cnt, uint32_t chunk, uint32_t fmt, uint32_t c)
+{
+    return fmt == 0 ? cnt[3 * chunk + (c < 3 ? c : 2)] : s.b[(0u - c) & 3u];
+}
 
 // pass B: one workgroup per genome -- every chunk's carry and where its output starts; the decoded length; the verdict
-__global__ __launch_bounds__(256) void k_fastx_offsets(const FastxGenome *__restrict__ genomes, const FastxSumm *__restrict__ summ,
-                                                        uint32_t *__restrict__ status, uint4 *__restrict__ state,
-                                                        uint64_t *__restrict__ declen)
+//   REC: also the number of every chunk's first record marker (the fourth word of its state) and, per file, ix.nrec[2 f] = its
+//   markers, ix.nrec[2 f + 1] = the carry behind its last byte (FASTQ: the index of the line the file ends on -- the host
+//   needs it to count a header or a '+' line that the file's end cuts off as kseq does, sketch_plan.h: fastx_tail_records)
+template <bool REC>
+__device__ __forceinline__ void fastx_offsets(const FastxGenome *__restrict__ genomes, const FastxSumm *__restrict__ summ,
+                                              uint32_t *__restrict__ status, uint4 *__restrict__ state,
+                                              uint64_t *__restrict__ declen, const FastxRecIndex &ix)
 {
     __shared__ uint8_t sf[256];
     __shared__ uint64_t sn[256];
     __shared__ uint32_t sl[256];
+    __shared__ uint32_t sr[REC ? 256 : 1];
     __shared__ uint32_t sbad;
     const FastxGenome g = genomes[blockIdx.x];
     const int t = threadIdx.x;
@@ -307,53 +362,85 @@ __global__ __launch_bounds__(256) void k_fastx_offsets(const FastxGenome *__rest
     // 2. with the carries known: what every chunk emits; prefix sum over the lanes' runs
     uint64_t mine = 0;
     uint32_t lines = 0;  // newlines of this lane's chunks (FASTQ: the line number of a byte = the newlines in front of it)
+    uint32_t recs = 0;   // (REC) record markers of this lane's chunks
     bool bad = false;
     uint32_t carry = carry0;
     for (uint32_t c = c0; c < c1; ++c) {
         const FastxSumm s = summ[g.chunk0 + c];
         mine += chunk_emits(s, g.fmt, carry, bad);
+        if constexpr (REC) recs += chunk_markers(s, ix.cnt, g.chunk0 + c, g.fmt, carry);
         lines += s.b[0] + s.b[1] + s.b[2] + s.b[3];
         carry = fn_apply(s.fn, carry);
     }
     sn[t] = mine;
     sl[t] = lines;
+    if constexpr (REC) sr[t] = recs;
     if (bad) atomicOr(&sbad, 1u);
     __syncthreads();
     for (int d = 1; d < 256; d <<= 1) {
         uint64_t v = sn[t];
-        uint32_t w = sl[t];
-        if (t >= d) v += sn[t - d], w += sl[t - d];
+        uint32_t w = sl[t], r = REC ? sr[t] : 0u;
+        if (t >= d) {
+            v += sn[t - d], w += sl[t - d];
+            if constexpr (REC) r += sr[t - d];
+        }
         __syncthreads();
         sn[t] = v;
         sl[t] = w;
+        if constexpr (REC) sr[t] = r;
         __syncthreads();
     }
     if (sbad != 0) {  // the host will parse this one: nothing is emitted
         for (uint32_t c = t; c < g.nchunks; c += 256) state[g.chunk0 + c] = make_uint4(0xFFFFFFFFu, 0xFFu, 0u, 0u);
         if (t == 0) declen[blockIdx.x] = 0, status[blockIdx.x] = 1u;
+        if (REC && t == 0) ix.nrec[2 * blockIdx.x] = 0u, ix.nrec[2 * blockIdx.x + 1] = 0u;
         return;
     }
     uint64_t off = t ? sn[t - 1] : 0;
     lines = t ? sl[t - 1] : 0;
+    recs = (REC && t) ? sr[t - 1] : 0u;
     carry = carry0;
     for (uint32_t c = c0; c < c1; ++c) {
         const FastxSumm s = summ[g.chunk0 + c];
-        state[g.chunk0 + c] = make_uint4((uint32_t)off, carry | ((uint32_t)(off >> 32) << 8), lines, 0u);
+        state[g.chunk0 + c] = make_uint4((uint32_t)off, carry | ((uint32_t)(off >> 32) << 8), lines, recs);
         bool db = false;
         off += chunk_emits(s, g.fmt, carry, db);
         lines += s.b[0] + s.b[1] + s.b[2] + s.b[3];
+        if constexpr (REC) recs += chunk_markers(s, ix.cnt, g.chunk0 + c, g.fmt, carry);
         carry = fn_apply(s.fn, carry);
     }
     if (t == 255) declen[blockIdx.x] = sn[255];
+    if (REC && t == 255) ix.nrec[2 * blockIdx.x] = sr[255], ix.nrec[2 * blockIdx.x + 1] = carry;  // (lane 255 ends behind the last chunk)
+}
+}  // namespace
+
+__global__ __launch_bounds__(256) void k_fastx_offsets(const FastxGenome *__restrict__ genomes, const FastxSumm *__restrict__ summ,
+                                                        uint32_t *__restrict__ status, uint4 *__restrict__ state,
+                                                        uint64_t *__restrict__ declen)
+{
+    fastx_offsets<false>(genomes, summ, status, state, declen, FastxRecIndex{});
+}
+__global__ __launch_bounds__(256) void k_fastx_offsets_rec(const FastxGenome *__restrict__ genomes, const FastxSumm *__restrict__ summ,
+                                                            uint32_t *__restrict__ status, uint4 *__restrict__ state,
+                                                            uint64_t *__restrict__ declen, FastxRecIndex ix)
+{
+    fastx_offsets<true>(genomes, summ, status, state, declen, ix);
 }
 
 // pass C: the chunk's emitted bytes, compacted through LDS, to out + (genome offset + the chunk's offset)
-__global__ __launch_bounds__(256) void k_fastx_compact(const uint8_t *__restrict__ raw, const FastxChunk *__restrict__ chunks,
-                                                        const FastxGenome *__restrict__ genomes, const uint4 *__restrict__ state,
-                                                        uint8_t *__restrict__ out, unsigned long long *__restrict__ fingerprint)
+//   REC: every record marker's place in the decoded and in the raw buffer, at entry ix.rec0[file] + the record's number (the
+//   chunk's first, plus the markers of the lanes in front, plus its rank in the lane) -- nothing at or behind the file's last
+//   entry, ix.rec0[file + 1]: a file with more records than the caller gave it is reported by its count, not written
+namespace {
+template <bool REC>
+__device__ __forceinline__ void fastx_compact(const uint8_t *__restrict__ raw, const FastxChunk *__restrict__ chunks,
+                                              const FastxGenome *__restrict__ genomes, const uint4 *__restrict__ state,
+                                              uint8_t *__restrict__ out, unsigned long long *__restrict__ fingerprint,
+                                              const FastxRecIndex &ix)
 {
     __shared__ uint8_t sh[256];
     __shared__ uint32_t wsum[4], lsum[4];
+    __shared__ uint32_t rsum[REC ? 4 : 1];
     __shared__ __attribute__((aligned(16))) uint8_t stage[kFastxChunk + 32];
     const uint4 st = state[blockIdx.x];
     if ((st.y & 0xFFu) == 0xFFu) return;  // (a refused genome)
@@ -428,6 +515,18 @@ __global__ __launch_bounds__(256) void k_fastx_compact(const uint8_t *__restrict
         if ((t & 63) >= o) inc += v;
     }
     if ((t & 63) == 63) wsum[t >> 6] = inc;
+    uint64_t marks = 0;  // (REC) the markers of this lane that are records
+    uint32_t rinc = 0;
+    if constexpr (REC) {
+        marks = hs & keep & ~(g.fmt == 0 ? file_tail_bit(ck, g, at, have) : 0ull);
+        rinc = (uint32_t)__popcll(marks);
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const uint32_t v = __shfl_up(rinc, o);
+            if ((t & 63) >= o) rinc += v;
+        }
+        if ((t & 63) == 63) rsum[t >> 6] = rinc;
+    }
     __syncthreads();
     uint32_t base = 0, total = 0;
 #pragma unroll
@@ -438,6 +537,17 @@ __global__ __launch_bounds__(256) void k_fastx_compact(const uint8_t *__restrict
     const uint64_t dst0 = g.off + (((uint64_t)(st.y >> 8) << 32) | st.x);
     const uint32_t A = (uint32_t)(dst0 & 15u);
     uint32_t pos = A + base + inc - mine;
+    if constexpr (REC) {
+        uint64_t rec = (uint64_t)st.w + rinc - (uint32_t)__popcll(marks);
+        for (int w = 0; w < (t >> 6); ++w) rec += rsum[w];
+        const uint64_t e0 = ix.rec0[ck.genome], cap = ix.rec0[ck.genome + 1] - e0;
+        for (uint64_t b = marks; b; b &= b - 1, ++rec) {
+            if (rec >= cap) break;
+            const uint32_t bit = (uint32_t)__ffsll((unsigned long long)b) - 1u;
+            ix.dpos[e0 + rec] = (dst0 - A) + pos + (uint32_t)__popcll(keep & ((1ull << bit) - 1ull));
+            ix.rpos[e0 + rec] = ck.begin + at + bit;
+        }
+    }
 #pragma unroll
     for (int k = 0; k < 16; ++k) {
 #pragma unroll
@@ -459,6 +569,21 @@ __global__ __launch_bounds__(256) void k_fastx_compact(const uint8_t *__restrict
         const uint32_t x = (g1 << 4) + (uint32_t)(t - 32);
         if (x < end && x >= A) base_out[x] = stage[x];
     }
+}
+}  // namespace
+
+__global__ __launch_bounds__(256) void k_fastx_compact(const uint8_t *__restrict__ raw, const FastxChunk *__restrict__ chunks,
+                                                        const FastxGenome *__restrict__ genomes, const uint4 *__restrict__ state,
+                                                        uint8_t *__restrict__ out, unsigned long long *__restrict__ fingerprint)
+{
+    fastx_compact<false>(raw, chunks, genomes, state, out, fingerprint, FastxRecIndex{});
+}
+__global__ __launch_bounds__(256) void k_fastx_compact_rec(const uint8_t *__restrict__ raw, const FastxChunk *__restrict__ chunks,
+                                                            const FastxGenome *__restrict__ genomes, const uint4 *__restrict__ state,
+                                                            uint8_t *__restrict__ out, unsigned long long *__restrict__ fingerprint,
+                                                            FastxRecIndex ix)
+{
+    fastx_compact<true>(raw, chunks, genomes, state, out, fingerprint, ix);
 }
 
 // what the decoded genome leaves of its region: 'N' (no k-mer starts there)
@@ -500,6 +625,24 @@ hipError_t launch_fastx_decode(hipStream_t st, const uint8_t *raw, const FastxCh
     hipLaunchKernelGGL(k_fastx_offsets, dim3(ngenomes), dim3(256), 0, st, genomes, summ, status, state, declen);
     if (nchunks) {
         hipLaunchKernelGGL(k_fastx_compact, dim3(nchunks), dim3(256), 0, st, raw, chunks, genomes, state, out, fingerprint);
+    }
+    hipLaunchKernelGGL(k_fastx_pad, dim3(ngenomes, 16), dim3(256), 0, st, genomes, declen, fingerprint, status, out);
+    return hipGetLastError();
+}
+
+// the same with the record index; ix.rec0 == NULL: passes A and B alone (counts and the early verdicts, nothing emitted)
+hipError_t launch_fastx_decode_records(hipStream_t st, const uint8_t *raw, const FastxChunk *chunks, uint32_t nchunks,
+                                       const FastxGenome *genomes, uint32_t ngenomes, FastxSumm *summ, uint4 *state, uint64_t *declen,
+                                       uint32_t *status, unsigned long long *fingerprint, uint8_t *out, const FastxRecIndex &ix)
+{
+    if (ngenomes == 0) return hipSuccess;
+    if (nchunks) {
+        hipLaunchKernelGGL(k_fastx_scan_rec, dim3(nchunks), dim3(256), 0, st, raw, chunks, genomes, summ, status, ix);
+    }
+    hipLaunchKernelGGL(k_fastx_offsets_rec, dim3(ngenomes), dim3(256), 0, st, genomes, summ, status, state, declen, ix);
+    if (!ix.rec0) return hipGetLastError();
+    if (nchunks) {
+        hipLaunchKernelGGL(k_fastx_compact_rec, dim3(nchunks), dim3(256), 0, st, raw, chunks, genomes, state, out, fingerprint, ix);
     }
     hipLaunchKernelGGL(k_fastx_pad, dim3(ngenomes, 16), dim3(256), 0, st, genomes, declen, fingerprint, status, out);
     return hipGetLastError();

@@ -2,6 +2,8 @@
 // decoder (kernels_sketch.hip, kernels_fastx.hip), and the pure functions that cut a call's offsets into those lists.
 // No HIP types here: sketch.hip runs the planners for the device, libdashing_host.so for the CPU tests
 // (host/plan_capi.cpp: dshh_sketch_plan, tests/test_sketch_plan.py), tools/cabi/sketch_plan_walk.cpp under the sanitizers.
+// Also the arithmetic between the decoder's record index and plan_records (fastx_tail_records, fastx_line_start,
+// fastx_record_offsets: tests/test_fastx_records_plan.py, tools/cabi/fastx_records_walk.cpp).
 // Sketch results do not depend on the work list (the merge is a byte-wise max): only these tests notice a changed cut.
 // The planners take offsets that are monotone and slots that fit 32 bits (sketch.hip: sketch_enter).
 #pragma once
@@ -165,6 +167,38 @@ inline int plan_fastx(const uint8_t *raw, const uint64_t *off, const uint64_t *r
         if (chunks.size() > 0x7FFFFFFFull) return kFastxPlanTooLarge;
     }
     return kFastxPlanOk;
+}
+
+// dsh_sketch_fastx_records: kseq's records of an ACCEPTED file from the decoder's record markers (kernels.h: FastxRecIndex).
+// Every marker is one record, but at the end of a FASTQ file (FASTA: the decoder itself leaves out a header character that
+// is the file's last byte).  end_line is the index, modulo 4, of the line the file ends on; a file that ends with '\n' ends
+// on a line nothing is on.  Returns the records to add to the markers:
+//   +1  the file ends inside a header line of two bytes or more: kseq reads a name there and returns a last, empty record
+//       (no newline ends that header, so it has no marker); "@" alone is kseq's ordinary end of file
+//   -1  it ends on the '+' line with no newline behind it: kseq finds no quality string, an error -- its record is not
+//       returned (the decoder accepted the file, so that record's sequence is empty)
+inline int fastx_tail_records(const uint8_t *file, uint64_t len, uint32_t fmt, uint32_t end_line)
+{
+    if (fmt == 0 || len == 0 || file[len - 1] == '\n') return 0;
+    if ((end_line & 3u) == 0) return (len >= 2 && file[len - 2] != '\n') ? 1 : 0;
+    return (end_line & 3u) == 2 ? -1 : 0;
+}
+
+// the first byte of the line that holds file[pos] (a FASTQ marker is the newline that ENDS its header line)
+inline uint64_t fastx_line_start(const uint8_t *file, uint64_t pos)
+{
+    while (pos && file[pos - 1] != '\n') --pos;
+    return pos;
+}
+
+// plan_records' offsets for the n records of an accepted file: record r runs from its marker dpos[r] (the marker byte is
+// invalid: it adds no k-mer) to the next one, the last to `end` -- the file's decoded end, not its region's: behind it lies
+// padding, for FASTQ half the region.  Records without a marker (r >= markers: the +1 above) are empty, at `end`.
+inline void fastx_record_offsets(const uint64_t *dpos, uint64_t markers, uint64_t n, uint64_t end, std::vector<uint64_t> &off)
+{
+    off.resize(n + 1);
+    for (uint64_t r = 0; r < n; ++r) off[r] = r < markers ? dpos[r] : end;
+    off[n] = end;
 }
 
 }  // namespace dsh

@@ -66,7 +66,7 @@ typedef struct dsh_ctx dsh_ctx;
  * dsh_group_stats, dsh_group_stats_device, dsh_dist_histogram, dsh_dist_histogram_device, dsh_dist_rect_histogram,
  * dsh_linkage_threshold, dsh_linkage_threshold_device, dsh_linkage_tri, dsh_mst, dsh_mst_tri, dsh_mst_linkage,
  * dsh_dbscan_threshold, dsh_dbscan_threshold_device, dsh_dbscan_tri, dsh_degree_threshold, dsh_degree_threshold_device,
- * dsh_union_curve, dsh_union_curve_device, dsh_curve_permutations. */
+ * dsh_union_curve, dsh_union_curve_device, dsh_curve_permutations, dsh_sketch_fastx_records. */
 #define DSH_ABI_VERSION 7
 int dsh_abi_version(void);
 
@@ -164,6 +164,31 @@ int dsh_sketch_records_device(dsh_ctx *ctx, const void *d_seq, const uint64_t *r
 int dsh_sketch_fastx_batch_async(dsh_ctx *ctx, const uint8_t *raw_pinned, const uint64_t *genome_off,
                                  const uint64_t *raw_len, uint32_t n_genomes, uint64_t first_slot, int k, int canon,
                                  uint32_t *status_out_pinned);
+/* Per-record sketches from raw file bytes: the device decodes the files as dsh_sketch_fastx_batch_async does and keeps, next
+ * to the base stream, an index of where every record begins; then every record of every accepted file gets a row of its
+ * own, OVERWRITTEN as by dsh_sketch_records.  Blocking.  `raw`, file_off[n_files + 1] and raw_len[n_files] are those of
+ * dsh_sketch_fastx_batch_async (regions start on multiples of 32 and hold their file's raw bytes); one unit is ONE file,
+ * and any host memory is taken (page-locked memory copies faster).
+ *   slot_ptr[n_files + 1], monotone: file f owns the slots [slot_ptr[f], slot_ptr[f + 1]); its record r, in file order,
+ *     goes to row slot_ptr[f] + r.
+ *   status_out[n_files]: nonzero where the file is refused -- by the rules of dsh_sketch_fastx_batch_async, the early ones
+ *     and the late one (the FASTQ length fingerprint).  A refused file writes no row and no hdr_off_out entry and reports
+ *     n_rec_out[f] = 0: the caller parses it itself and uses dsh_sketch_records for its span.
+ *   n_rec_out[n_files]: the records kseq reads from an accepted file (a header character that is the file's last byte
+ *     starts none; a FASTQ file that ends inside a header line of two bytes or more ends with one more, empty record).
+ *   hdr_off_out[slot_ptr[n_files] - slot_ptr[0]] or NULL: entry (slot - slot_ptr[0]) is the offset in `raw` of the record's
+ *     '>' / '@'.  The record's name are the bytes behind it up to the first isspace byte or the file's end.
+ * Count-only mode, slot_ptr == NULL: only the two scanning passes run; status_out (the EARLY refusals only: a file that
+ * the full call refuses late is still counted here) and n_rec_out are filled, nothing is sketched; allowed before
+ * dsh_sketches_alloc -- this is how a caller sizes its matrix.
+ * If an accepted file's count differs from its span: DSH_ERANGE with a message in dsh_last_error, n_rec_out complete, NO
+ * row of any file written (the convention of dsh_dist_threshold_device: call again with room).
+ * Refused before anything is enqueued: DSH_EINVAL for k outside [1,32], a region that does not start on a multiple of 32 or
+ * does not hold its raw_len, a slot_ptr that decreases, slots out of range; DSH_ESTATE before dsh_sketches_alloc (unless
+ * count-only). */
+int dsh_sketch_fastx_records(dsh_ctx *ctx, const uint8_t *raw, const uint64_t *file_off, const uint64_t *raw_len,
+                             uint32_t n_files, const uint64_t *slot_ptr, int k, int canon, uint32_t *status_out,
+                             uint64_t *n_rec_out, uint64_t *hdr_off_out);
 int dsh_clear_sketches(dsh_ctx *ctx, uint64_t first_slot, uint64_t n);
 
 /* ---- cardinalities ------------------------------------------------------------------------
