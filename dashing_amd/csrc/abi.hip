@@ -606,6 +606,7 @@ int dsh_get_info(dsh_ctx *c, const char *name, int64_t *out)
         *out = (int64_t)f;
     }
     else if (!std::strcmp(name, "sparse_run")) *out = c->sparse_run > 0 ? c->sparse_run : (int64_t)plan::kSparseRunDefault;  // (in effect)
+    else if (!std::strcmp(name, "sparse_words")) *out = sparse_words_of(c);  // (in effect; 0: the table is gathered)
     else if (!std::strcmp(name, "sparse_planes")) *out = c->sparse_planes;
     else if (!std::strcmp(name, "sparse_sided")) *out = c->sparse_sided;
     else if (!std::strcmp(name, "sparse_cap")) *out = c->sparse_cap;
@@ -655,6 +656,7 @@ static const IntOption kIntOptions[] = {
     {"sparse_sided", -1, 1, "is -1 (auto), 0 (off) or 1 (forced)", OPT_TO(sparse_sided, int)},  // the sided route (plan.h, Tuning)
     {"sparse_lds", 0, 1, "must be 0 or 1", OPT_TO(sparse_lds, int)},
     {"sparse_run", 0, plan::kSparseRunMax, "must be in [0, 65536]", OPT_TO(sparse_run, int)},
+    {"sparse_words", 0, 2, "must be 0 (auto), 1 or 2", OPT_TO(sparse_words, int)},
     {"sparse_cap", 0, plan::kSparseCapMax, "must be in [0, 2040]", OPT_TO(sparse_cap, int)},
     {"xch_recv_gate", -1, 1, "is -1 (auto), 0 or 1", OPT_TO(xch.recv_gate, int)},
     {"finalize_signal", -1, 1, "is -1 (auto), 0 or 1", OPT_TO(finalize_signal, int)},

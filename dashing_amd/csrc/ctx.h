@@ -252,6 +252,7 @@ struct dsh_ctx {
     int sparse_sided = -1;   // the sided route (plan.h, Tuning::sparse_sided): -1 auto, 0 off, 1 forced
     int sparse_lds = 1;      // the table of the counting kernel staged in LDS where a word of it fits (p <= 15); 0: gathered
     int sparse_run = 0;      // items a workgroup of the LDS placement takes one behind the other (plan.h, sparse_table_fills); 0: kSparseRunDefault
+    int sparse_words = 0;    // table words a workgroup of the LDS placement stages side by side: 1 | 2 (p <= 14); 0: 1, the measured choice
     uint32_t sparse_run_used = 0;  // the run of the last call's launches of the LDS placement; 0: it had none
     DevBuf sp_tab, sp_lists, sp_len, sp_slabs, sp_items;  // the slabs of the last call that routed planes (kernels_sparseplane.hip) and its items
     Staging st_sparse;               // slabs then sparse items on their way to the device
@@ -450,6 +451,18 @@ struct DeviceTimer {
 
 // slots [first, first + cnt) inside [0, total) -- written so that first + cnt cannot wrap
 inline bool slots_ok(uint64_t first, uint64_t cnt, uint64_t total) { return first <= total && cnt <= total - first; }
+
+// the sparse counting kernel's table (kernels_sparseplane.hip): a word of it staged in LDS up to p = 15 (option sparse_lds
+// = 0: gathered from global memory, the arm the measurements compare against); at p = 16 a word is 256 KiB and the table
+// is always gathered
+inline int sparse_wordmajor(const dsh_ctx *c) { return c->sparse_lds && c->p <= 15 ? 1 : 0; }
+// the table words a workgroup of that LDS placement stages side by side (option sparse_words; 0: one, the measured choice
+// at every p -- profiles/sparse4); 0 where the table is gathered
+inline int sparse_words_of(const dsh_ctx *c)
+{
+    if (!sparse_wordmajor(c)) return 0;
+    return c->sparse_words > 0 ? c->sparse_words : 1;
+}
 
 inline bool use_lockstep(const dsh_ctx *c)
 {

@@ -286,9 +286,6 @@ uint32_t sparse_list_stride(const dsh_ctx *c)
 {
     return std::max<uint32_t>(8, (std::min<uint32_t>((uint32_t)c->sparse_cap, plan::kSparseCapMax) + 7) / 8 * 8);
 }
-// the table's placement: a word of it staged in LDS up to p = 15 (option sparse_lds = 0: gathered from global memory, the
-// arm the measurements compare against); at p = 16 a word is 256 KiB and the table is always gathered
-int sparse_wordmajor(const dsh_ctx *c) { return c->sparse_lds && c->p <= 15 ? 1 : 0; }
 // the items a workgroup of the LDS placement takes one behind the other (option sparse_run; 0: the measured default)
 uint32_t sparse_run_of(const dsh_ctx *c) { return c->sparse_run > 0 ? (uint32_t)c->sparse_run : plan::kSparseRunDefault; }
 uint64_t sparse_slab_bytes(const dsh_ctx *c)
@@ -487,7 +484,7 @@ int launch_sparse_items(dsh_ctx *c, size_t bi, uint64_t nslots)
     if (a && b) (void)hipEventRecord(a, c->stream);
     if (sparse_wordmajor(c)) c->sparse_run_used = sparse_run_of(c);
     HIPCHK(c, launch_sparse_count(c->stream, c->cum_bytes, (const uint4 *)c->sp_items.ptr + rg.first, (uint32_t)(rg.second - rg.first),
-                                  sparse_run_of(c), sparse_wordmajor(c), (const uint32_t *)c->sp_tab.ptr, (const uint16_t *)c->sp_lists.ptr, (const uint32_t *)c->sp_len.ptr,
+                                  sparse_run_of(c), sparse_wordmajor(c), sparse_words_of(c), (const uint32_t *)c->sp_tab.ptr, (const uint16_t *)c->sp_lists.ptr, (const uint32_t *)c->sp_len.ptr,
                                   sparse_list_stride(c), 1u << c->p, c->cum.ptr, nslots));
     if (a && b) {
         (void)hipEventRecord(b, c->stream);
@@ -642,6 +639,7 @@ int run_pairs(dsh_ctx *c, const PairJob &job)
     if (job.result_type < 0 || job.result_type > 8)
         return fail(c, DSH_EINVAL, "unsupported result_type %d", job.result_type);
     if (job.k < 1) return fail(c, DSH_EINVAL, "bad k %d", job.k);
+    if (sparse_words_of(c) == 2 && c->p > 14) return fail(c, DSH_EINVAL, "sparse_words = 2 needs p <= 14: a word pair of the table at p = %d does not fit a CU's LDS", c->p);
     const auto t_l0 = std::chrono::steady_clock::now();
     plan::PairPlan &pp = c->pp;
     plan::PairQuery q;

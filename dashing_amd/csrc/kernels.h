@@ -56,8 +56,9 @@ hipError_t launch_sparse_build(hipStream_t st, const uint32_t *planes, uint32_t 
 // the plane's C(v) of the tile's 128 x 128 pairs, stored where the tile kernel stores it; m = 2^p.  The flags name the
 // polarities of the list side and the table side, and whether the list side is the column block (a transposed item).
 // run >= 1 (wordmajor only; the gathered kernel ignores it): a workgroup of the LDS placement takes that many items of an
-// XCD residue one behind the other and stages the table where it changes (plan.h, sparse_table_fills); 1 = one item each
-hipError_t launch_sparse_count(hipStream_t st, int cum_bytes, const uint4 *items, uint32_t nitems, uint32_t run, int wordmajor,
+// XCD residue one behind the other and stages the table where it changes (plan.h, sparse_table_fills); 1 = one item each.
+// words = 1 | 2 (wordmajor only): the table words a workgroup stages side by side; 2 needs 2^p <= 2^14, refused otherwise
+hipError_t launch_sparse_count(hipStream_t st, int cum_bytes, const uint4 *items, uint32_t nitems, uint32_t run, int wordmajor, int words,
                                const uint32_t *tab, const uint16_t *lists, const uint32_t *len, uint32_t cap, uint32_t m, void *cum,
                                uint64_t nslots);
 

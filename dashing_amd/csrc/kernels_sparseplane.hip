@@ -18,12 +18,15 @@
 // words a step): one lane step serves 32 pairs.  The counters are then read out column by column.
 // Two placements of the table.  Gathered from global memory (k_sparse_count: position-major, the four lanes of a row read
 // one 16-byte piece) the kernel is bound by its gathers -- 16 scattered pieces per wave instruction; at C3 an item costs
-// 0.39 (top plane) to 0.64 (the one below) of a dense one (profiles/sparse1).  So up to p = 15 one word of the table -- 32
-// columns, 2^p x 4 bytes: 64 KiB at p = 14 -- is staged in LDS by each of FOUR workgroups per item (k_sparse_count_lds),
-// the four lanes of a row take a quarter of its list each, add their counters at the end and read out eight of the
-// word's 32 columns each.  A workgroup takes a RUN of items of its XCD residue (option sparse_run, default
-// plan::kSparseRunDefault) and stages the word again only where the table slab changes; at 10 000 x p=14 the walk is 0.7 of
-// the kernel's 1.0 ms, the stagings 0.1, the read-out 0.13 (profiles/sparse3).  At p = 16 a word is
+// 0.39 (top plane) to 0.64 (the one below) of a dense one (profiles/sparse1).  So up to p = 15 the table is staged in LDS
+// (k_sparse_count_lds), NW = 1 or 2 of its words -- 32 columns each, 2^p x 4 bytes: 64 KiB at p = 14 -- by each of 4 / NW
+// workgroups per item (option sparse_words; 2 where the pair fits a CU's 160 KiB beside the turn area, p <= 14, else 1).
+// The 4 NW lanes of a row take every (4 NW)th group of eight entries of its list, add their counters at the end and read
+// out eight of the 32 NW columns each.  The walk was bound by its LDS gathers: the lanes of a wave read random positions,
+// which conflict on the banks; a 64-bit read of an interleaved word pair meets the same conflicts and returns twice the
+// columns, so at NW = 2 a list entry costs half the LDS cycles per column, and the lists are read by half as many
+// workgroups.  A workgroup takes a RUN of items of its XCD residue (option sparse_run, default plan::kSparseRunDefault)
+// and stages its words again only where the table slab changes (profiles/sparse3, profiles/sparse4).  At p = 16 a word is
 // 256 KiB, more than a CU holds: the global placement stays, and there the sets are sparse enough for it to pay well.
 // The sided route (plan.h, Tuning::sparse_sided).  Only the LIST side has to be sparse -- the table costs the same at any
 // density -- and a set may be U(v) or A(v) = {t : a_t < v}, the plane's words as they are: a slab carries its polarity, an
@@ -254,51 +257,133 @@ __device__ __forceinline__ void put8(uint32_t *dst, const uint32_t (&v)[8])
     reinterpret_cast<uint4 *>(dst)[1] = make_uint4(v[4], v[5], v[6], v[7]);
 }
 
-// One step of a lane's walk against the table word in LDS: the eight 16-bit positions of pk, of which `left` are in the
-// list (kPartial: fewer than eight may be -- behind the list's end nothing is read at whatever the slot holds).
-template <bool kPartial>
-__device__ __forceinline__ void sp_step_lds(uint32_t (&c)[kSpCounters], const uint32_t *tabl, const uint4 pk, uint32_t left)
+// The carry-save adder of the LDS placement as sum and majority, one v_bitop3_b32 each (truth tables 0x96, 0xE8).  Through
+// the builtin: written with &, | and ^ the compiler rebuilds it from v_xor and v_bfi, four to five instructions an adder.
+// (csa above stays as the gathered kernel has it.)
+__device__ __forceinline__ void csa_sm(uint32_t &h, uint32_t &l, uint32_t a, uint32_t b, uint32_t c)
+{
+    h = __builtin_amdgcn_bitop3_b32(a, b, c, 0xE8);
+    l = __builtin_amdgcn_bitop3_b32(a, b, c, 0x96);
+}
+
+// The gathers of one step of a lane's walk against the NW table words in LDS: the eight 16-bit positions of pk, of which
+// `left` are in the list (kPartial: fewer than eight may be -- behind the list's end nothing is read at whatever the slot
+// holds, and the words are zero).
+template <int NW, bool kPartial>
+__device__ __forceinline__ void sp_gather(uint32_t (&x)[NW][8], const uint32_t *tabl, const uint4 pk, uint32_t left)
 {
     const uint32_t pw[4] = {pk.x, pk.y, pk.z, pk.w};
-    uint32_t x[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
         const bool valid = !kPartial || (uint32_t)j < left;
         const uint32_t pos = valid ? (pw[j >> 1] >> (16 * (j & 1))) & 0xFFFFu : 0u;
-        const uint32_t v = tabl[pos];
-        x[j] = valid ? v : 0u;
+        if constexpr (NW == 2) {
+            const uint2 v = reinterpret_cast<const uint2 *>(tabl)[pos];  // one ds_read_b64: the position's word pair
+            x[0][j] = valid ? v.x : 0u;
+            x[1][j] = valid ? v.y : 0u;
+        } else {
+            x[0][j] = valid ? tabl[pos] : 0u;
+        }
     }
+}
+
+// Eight words into the ones, twos and fours of a counter set; the carry of weight eight is returned.
+__device__ __forceinline__ uint32_t sp_tree8(uint32_t (&c)[kSpCounters], const uint32_t (&x)[8])
+{
     uint32_t t0, t1, t2, t3, f0, f1, e;
-    csa(t0, c[0], c[0], x[0], x[1]);
-    csa(t1, c[0], c[0], x[2], x[3]);
-    csa(f0, c[1], c[1], t0, t1);
-    csa(t2, c[0], c[0], x[4], x[5]);
-    csa(t3, c[0], c[0], x[6], x[7]);
-    csa(f1, c[1], c[1], t2, t3);
-    csa(e, c[2], c[2], f0, f1);
+    csa_sm(t0, c[0], c[0], x[0], x[1]);
+    csa_sm(t1, c[0], c[0], x[2], x[3]);
+    csa_sm(f0, c[1], c[1], t0, t1);
+    csa_sm(t2, c[0], c[0], x[4], x[5]);
+    csa_sm(t3, c[0], c[0], x[6], x[7]);
+    csa_sm(f1, c[1], c[1], t2, t3);
+    csa_sm(e, c[2], c[2], f0, f1);
+    return e;
+}
+
+// a carry of weight 2^B ripples up the counter words
+template <int B>
+__device__ __forceinline__ void sp_ripple(uint32_t (&c)[kSpCounters], uint32_t e)
+{
 #pragma unroll
-    for (int b = 3; b < kSpCounters; ++b) {  // the eights' carry ripples up
+    for (int b = B; b < kSpCounters; ++b) {
         const uint32_t carry = c[b] & e;
         c[b] ^= e;
         e = carry;
     }
 }
 
-// The LDS placement: workgroup g of a group of 32 is (x, w, c) = (g % 8, (g / 8) % 4, g / 32).  It takes table word w and
-// a RUN of `run` items of the launch, x + 8 * (c * run + i) for i < run: every eighth item, so that an item's launch
-// position still names its XCD, and one behind the other there the planner puts items of one table block (plan.cpp,
-// order_sparse_items).  The word is staged only where an item's table slab is not the one the item before it in the run
-// left there (plan.h, sparse_table_fills counts by the same rule); the set sizes lt of the lane's eight table columns
-// stay in registers as long.  After the four lanes of a row have added their counters, lane q reads out the columns
-// 8 q .. 8 q + 7 of the word.  lds: [2^p] the word's table, then CT [32][128]: the values of a transposed item on their
-// way out, in a place of their own, so that the table outlives the item.
+// A lane's walk: the groups of eight entries at k0, k0 + S, ... of the list lp[0 .. li).  Four whole steps at a time as a
+// Harley-Seal tree over 32 entries -- the four carries of weight eight go through the eights and the sixteens, and ONE
+// carry of weight 32 ripples into the upper words -- then what is left step by step, each one's eights rippled; only the
+// list's last group can be partial.  Exact at every length: the counter words hold a set of up to 2047.
+template <int NW, uint32_t S>
+__device__ __forceinline__ void sp_walk(uint32_t (&c)[NW][kSpCounters], const uint32_t *tabl, const uint16_t *lp, uint32_t li, uint32_t k0)
+{
+    uint32_t x[NW][8];
+    for (; k0 + 3 * S + 8 <= li; k0 += 4 * S) {
+        uint32_t e[NW][4];
+#pragma unroll
+        for (uint32_t t = 0; t < 4; ++t) {
+            sp_gather<NW, false>(x, tabl, *reinterpret_cast<const uint4 *>(lp + k0 + t * S), 8);
+#pragma unroll
+            for (int n = 0; n < NW; ++n) e[n][t] = sp_tree8(c[n], x[n]);
+        }
+#pragma unroll
+        for (int n = 0; n < NW; ++n) {
+            uint32_t sa, sb, th;
+            csa_sm(sa, c[n][3], c[n][3], e[n][0], e[n][1]);
+            csa_sm(sb, c[n][3], c[n][3], e[n][2], e[n][3]);
+            csa_sm(th, c[n][4], c[n][4], sa, sb);
+            sp_ripple<5>(c[n], th);
+        }
+    }
+    for (; k0 + 8 <= li; k0 += S) {
+        sp_gather<NW, false>(x, tabl, *reinterpret_cast<const uint4 *>(lp + k0), 8);
+#pragma unroll
+        for (int n = 0; n < NW; ++n) sp_ripple<3>(c[n], sp_tree8(c[n], x[n]));
+    }
+    if (k0 < li) {
+        sp_gather<NW, true>(x, tabl, *reinterpret_cast<const uint4 *>(lp + k0), li - k0);
+#pragma unroll
+        for (int n = 0; n < NW; ++n) sp_ripple<3>(c[n], sp_tree8(c[n], x[n]));
+    }
+}
+
+// a += the same counter words of the lane d away (a bit-sliced adder; every lane of the wave takes part)
+__device__ __forceinline__ void sp_add_lane(uint32_t (&a)[kSpCounters], const uint32_t (&give)[kSpCounters], int d)
+{
+    uint32_t carry = 0;
+#pragma unroll
+    for (int b = 0; b < kSpCounters; ++b) {
+        const uint32_t o = __shfl_xor(give[b], d, 64);
+        const uint32_t u = a[b] ^ o;
+        const uint32_t sum = u ^ carry;
+        carry = (a[b] & o) | (u & carry);
+        a[b] = sum;
+    }
+}
+
+// The LDS placement, NW = 1 | 2 table words a workgroup (option sparse_words): 32 NW columns of the table slab, staged as
+// [2^p positions][NW words] -- at NW = 2 a lane's ds_read_b64 returns the 64 column bits of a position for the LDS-array
+// cycles a 32-bit read of one word takes, and the random positions of a wave's lanes conflict on the banks as often either
+// way.  4 / NW workgroups per item, 512 NW lanes as (list row, 4 NW lanes of the row): lane q walks every (4 NW)th group of
+// eight list entries into NW counter sets, the lanes of a row add their counters, and lane q reads out the columns
+// 8 q .. 8 q + 7 of the 32 NW.  Workgroup g is (x, w, c) = (g % 8, (g / 8) % (4 / NW), g / 8 / (4 / NW)).  It takes the
+// table words w NW .. and a RUN of `run` items of the launch, x + 8 * (c * run + i) for i < run: every eighth item, so that
+// an item's launch position still names its XCD, and one behind the other there the planner puts items of one table block
+// (plan.cpp, order_sparse_items).  The words are staged only where an item's table slab is not the one the item before it
+// in the run left there (plan.h, sparse_table_fills counts by the same rule: four words per staging of an item's
+// workgroups, at either NW); the set sizes lt of the lane's eight table columns stay in registers as long.
+// lds: [2^p][NW] the table, then CT [32 NW][128]: the values of a transposed item on their way out, in a place of their
+// own, so that the table outlives the item: 72 KiB at p = 14, NW = 1 and 16-bit C(v), 144 KiB at NW = 2.
 // DSH_SPARSE_CUT (a measuring build, `make SPCUT=1`, never the product library): an item ends after phase `stop` -- 1 the
 // fill, 2 the walk, 3 the lanes' addition -- and the results are meaningless; stop = 0 is the whole kernel.
-template <typename CT>
-__global__ __launch_bounds__(512) void k_sparse_count_lds(const uint4 *__restrict__ items, uint32_t nitems, uint32_t run,
-                                                          const uint32_t *__restrict__ tabw, const uint16_t *__restrict__ lists,
-                                                          const uint32_t *__restrict__ len, uint32_t cap, uint32_t m, CT *__restrict__ cum,
-                                                          uint64_t nslots, uint32_t stop)
+template <typename CT, int NW>
+__global__ __launch_bounds__(512 * NW) void k_sparse_count_lds(const uint4 *__restrict__ items, uint32_t nitems, uint32_t run,
+                                                               const uint32_t *__restrict__ tabw, const uint16_t *__restrict__ lists,
+                                                               const uint32_t *__restrict__ len, uint32_t cap, uint32_t m,
+                                                               CT *__restrict__ cum, uint64_t nslots, uint32_t stop)
 {
     extern __shared__ __attribute__((aligned(16))) uint32_t sp_lds[];
 #ifdef DSH_SPARSE_CUT
@@ -306,10 +391,11 @@ __global__ __launch_bounds__(512) void k_sparse_count_lds(const uint4 *__restric
 #else
     constexpr uint32_t cut = 0;
 #endif
-    CT *turn = reinterpret_cast<CT *>(sp_lds + m);
-    const uint32_t g = blockIdx.x, x = g & 7u, w = (g >> 3) & 3u, first = (g >> 5) * run;
-    const uint32_t tid = threadIdx.x, r = tid >> 2, q = tid & 3u, c0 = 8 * q;
-    uint32_t have = 0xFFFFFFFFu;  // the table slab whose word the LDS holds
+    constexpr uint32_t kThreads = 512 * NW, kLanes = 4 * NW, kGroups = 4 / NW, kCols = 32 * NW;  // lanes of a row; workgroups of an item; their columns
+    CT *turn = reinterpret_cast<CT *>(sp_lds + (size_t)m * NW);
+    const uint32_t g = blockIdx.x, x = g & 7u, w = (g >> 3) % kGroups, first = (g >> 3) / kGroups * run;
+    const uint32_t tid = threadIdx.x, r = tid / kLanes, q = tid % kLanes, c0 = 8 * q;
+    uint32_t have = 0xFFFFFFFFu;  // the table slab whose words the LDS holds
     uint32_t lt[8];
     // (every condition on the way to a barrier is uniform over the workgroup: the item, its slabs and its flags)
     for (uint32_t i = 0; i < run; ++i) {
@@ -320,9 +406,18 @@ __global__ __launch_bounds__(512) void k_sparse_count_lds(const uint4 *__restric
         const uint32_t ls = tr ? it.w : it.z, ts = tr ? it.z : it.w, plane = it.y & kSpPlaneMask;  // list slab, table slab
         if (ts != have) {
             if (i) __syncthreads();  // the walk of the item before is over in every wave
-            const uint4 *src = reinterpret_cast<const uint4 *>(tabw + ((uint64_t)ts * 4 + w) * m);
-            for (uint32_t k = tid; k < m / 4; k += 512) reinterpret_cast<uint4 *>(sp_lds)[k] = src[k];
-            const uint4 *lq = reinterpret_cast<const uint4 *>(len + (uint64_t)ts * kTile + w * 32 + c0);
+            const uint4 *src = reinterpret_cast<const uint4 *>(tabw + ((uint64_t)ts * 4 + w * NW) * m);
+            uint4 *dst = reinterpret_cast<uint4 *>(sp_lds);
+            if constexpr (NW == 2) {  // the two word-major words, interleaved by position
+                for (uint32_t k = tid; k < m / 4; k += kThreads) {
+                    const uint4 a = src[k], b = src[m / 4 + k];
+                    dst[2 * k] = make_uint4(a.x, b.x, a.y, b.y);
+                    dst[2 * k + 1] = make_uint4(a.z, b.z, a.w, b.w);
+                }
+            } else {
+                for (uint32_t k = tid; k < m / 4; k += kThreads) dst[k] = src[k];
+            }
+            const uint4 *lq = reinterpret_cast<const uint4 *>(len + (uint64_t)ts * kTile + w * kCols + c0);
             const uint4 l0 = lq[0], l1 = lq[1];
             lt[0] = l0.x, lt[1] = l0.y, lt[2] = l0.z, lt[3] = l0.w, lt[4] = l1.x, lt[5] = l1.y, lt[6] = l1.z, lt[7] = l1.w;
             __syncthreads();
@@ -331,53 +426,51 @@ __global__ __launch_bounds__(512) void k_sparse_count_lds(const uint4 *__restric
         if (cut == 1) continue;
         const uint32_t li_all = len[(uint64_t)ls * kTile + r];
         const uint32_t li = li_all < cap ? li_all : cap;
-        const uint16_t *lp = lists + ((uint64_t)ls * kTile + r) * cap;
-        uint32_t c[kSpCounters];
+        uint32_t c[NW][kSpCounters];
 #pragma unroll
-        for (int b = 0; b < kSpCounters; ++b) c[b] = 0;
-        // lane q of the row's four: every fourth group of eight entries; only the list's last group can be partial
-        uint32_t k0 = 8 * q;
-        for (; k0 + 8 <= li; k0 += 32) sp_step_lds<false>(c, sp_lds, *reinterpret_cast<const uint4 *>(lp + k0), 8);
-        if (k0 < li) sp_step_lds<true>(c, sp_lds, *reinterpret_cast<const uint4 *>(lp + k0), li - k0);
+        for (int n = 0; n < NW; ++n)
+#pragma unroll
+            for (int b = 0; b < kSpCounters; ++b) c[n][b] = 0;
+        sp_walk<NW, 8 * kLanes>(c, sp_lds, lists + ((uint64_t)ls * kTile + r) * cap, li, c0);
         if (cut == 2) continue;
-        // the four lanes of a row add their counters: a bit-sliced adder, twice (every lane of the wave takes part)
+        // The lanes of a row add their counters.  At NW = 2 the lanes 4 apart first swap halves: a lane gives away the set
+        // it will not read out and keeps the row's sum of the other; then, as at NW = 1, the four lanes of that half.
+        uint32_t s[kSpCounters];
 #pragma unroll
-        for (int d = 1; d <= 2; d <<= 1) {
-            uint32_t carry = 0;
+        for (int b = 0; b < kSpCounters; ++b) s[b] = NW == 2 && (q & 4u) ? c[NW - 1][b] : c[0][b];
+        if constexpr (NW == 2) {
+            uint32_t give[kSpCounters];
 #pragma unroll
-            for (int b = 0; b < kSpCounters; ++b) {
-                const uint32_t o = __shfl_xor(c[b], d, 64);
-                const uint32_t u = c[b] ^ o;
-                const uint32_t sum = u ^ carry;
-                carry = (c[b] & o) | (u & carry);
-                c[b] = sum;
-            }
+            for (int b = 0; b < kSpCounters; ++b) give[b] = q & 4u ? c[0][b] : c[1][b];
+            sp_add_lane(s, give, 4);
         }
+        sp_add_lane(s, s, 1);
+        sp_add_lane(s, s, 2);
         if (cut == 3) {  // (the sum leaves the lane, so that the phase is not compiled away; no value of a real item is all ones)
             uint32_t all = 0xFFFFFFFFu;
 #pragma unroll
-            for (int b = 0; b < kSpCounters; ++b) all &= c[b];
+            for (int b = 0; b < kSpCounters; ++b) all &= s[b];
             if (all == 0xFFFFFFFFu && cap == 1) turn[tid] = (CT)all;
             continue;
         }
-        // all four lanes of a row now hold the row's counters: lane q reads out 8 of the word's 32 columns
+        // every lane of a row now holds the row's counters of its word: lane q reads out 8 of the 32 NW columns
         uint32_t out[8];
-        sp_values<CT, 8>(out, c, c0, it.y, m, li_all, lt);
+        sp_values<CT, 8>(out, s, c0 & 31u, it.y, m, li_all, lt);
         CT *blk = cum + (uint64_t)plane * nslots + (uint64_t)it.x * (kTile * kTile);
-        if (!tr) {  // a row's four lanes store 32 values side by side
-            put8(blk + (uint64_t)r * kTile + w * 32 + c0, out);
+        if (!tr) {  // a row's lanes store 32 NW values side by side
+            put8(blk + (uint64_t)r * kTile + w * kCols + c0, out);
             continue;
         }
-        // transposed: lane (r, q) holds column r of the rows w * 32 + 8 q .. + 7.  The 32 x 128 values are turned in LDS
-        // and leave as whole rows, which lie one behind the other in the tile's block.  The first barrier: the rows of a
-        // transposed item before this one have left
+        // transposed: lane (r, q) holds column r of the rows w * 32 NW + 8 q .. + 7.  The 32 NW x 128 values are turned in
+        // LDS and leave as whole rows, which lie one behind the other in the tile's block.  The first barrier: the rows of
+        // a transposed item before this one have left
         __syncthreads();
 #pragma unroll
         for (int j = 0; j < 8; ++j) turn[(c0 + j) * kTile + r] = (CT)out[j];
         __syncthreads();
         const uint4 *ts4 = reinterpret_cast<const uint4 *>(turn);
-        uint4 *dst = reinterpret_cast<uint4 *>(blk + (uint64_t)w * 32 * kTile);
-        for (uint32_t k = tid; k < 32 * kTile * sizeof(CT) / 16; k += 512) dst[k] = ts4[k];
+        uint4 *dst = reinterpret_cast<uint4 *>(blk + (uint64_t)w * kCols * kTile);
+        for (uint32_t k = tid; k < kCols * kTile * sizeof(CT) / 16; k += kThreads) dst[k] = ts4[k];
     }
 }
 
@@ -396,34 +489,46 @@ hipError_t launch_sparse_build(hipStream_t st, const uint32_t *planes, uint32_t 
     return hipGetLastError();
 }
 
-hipError_t launch_sparse_count(hipStream_t st, int cum_bytes, const uint4 *items, uint32_t nitems, uint32_t run, int wordmajor,
+namespace {
+
+// NW words of the table and the turned values of a transposed item: at p = 14 and 16-bit C(v) 72 KiB (NW = 1: two
+// workgroups of 512 lanes a CU) or 144 KiB (NW = 2: one of 1 024)
+template <typename CT, int NW>
+hipError_t launch_sparse_count_lds(hipStream_t st, uint32_t runs, const uint4 *items, uint32_t nitems, uint32_t run, const uint32_t *tab,
+                                   const uint16_t *lists, const uint32_t *len, uint32_t cap, uint32_t m, void *cum, uint64_t nslots)
+{
+    const size_t lds = ((size_t)m * 4 + 32 * kTile * sizeof(CT)) * NW;
+    if (lds > 160 * 1024) return hipErrorInvalidValue;  // (the NW words of the table in a CU's LDS)
+    const hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void *>(k_sparse_count_lds<CT, NW>), lds);
+    if (e != hipSuccess) return e;
+    uint32_t stop = 0;
+#ifdef DSH_SPARSE_CUT
+    if (const char *s = std::getenv("DSH_SPARSE_STOP")) stop = (uint32_t)std::atoi(s);
+#endif
+    hipLaunchKernelGGL((k_sparse_count_lds<CT, NW>), dim3(runs * 8 * (4 / NW)), dim3(512 * NW), lds, st, items, nitems, run, tab, lists, len,
+                       cap, m, (CT *)cum, nslots, stop);
+    return hipGetLastError();
+}
+
+}  // namespace
+
+hipError_t launch_sparse_count(hipStream_t st, int cum_bytes, const uint4 *items, uint32_t nitems, uint32_t run, int wordmajor, int words,
                                const uint32_t *tab, const uint16_t *lists, const uint32_t *len, uint32_t cap, uint32_t m, void *cum,
                                uint64_t nslots)
 {
     if (nitems == 0) return hipSuccess;
     if (cap % 8 || cap > 2047 || run == 0) return hipErrorInvalidValue;
     if (wordmajor) {
-        if (m < 512 || m > (1u << 15)) return hipErrorInvalidValue;  // (a word of the table in a CU's LDS)
+        if (m < 512 || m > (1u << 15) || (words != 1 && words != 2)) return hipErrorInvalidValue;
         const uint32_t per_x = (nitems + 7) / 8;  // the items of an XCD residue
         run = std::min(run, per_x);
-        const uint32_t grid = (per_x + run - 1) / run * 32;
-        uint32_t stop = 0;
-#ifdef DSH_SPARSE_CUT
-        if (const char *s = std::getenv("DSH_SPARSE_STOP")) stop = (uint32_t)std::atoi(s);
-#endif
-        // a word of the table and the turned values of a transposed item: 72 KiB at p = 14 and 16-bit C(v), two workgroups a CU
-#define DSH_SPL(CT)                                                                                                                   \
-    do {                                                                                                                              \
-        const size_t lds = (size_t)m * 4 + 32 * kTile * sizeof(CT);                                                                   \
-        const hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void *>(k_sparse_count_lds<CT>), lds);                          \
-        if (e != hipSuccess) return e;                                                                                                \
-        hipLaunchKernelGGL(k_sparse_count_lds<CT>, dim3(grid), dim3(512), lds, st, items, nitems, run, tab, lists, len, cap, m,        \
-                           (CT *)cum, nslots, stop);                                                                                  \
-    } while (0)
-        if (cum_bytes == 2) DSH_SPL(uint16_t);
-        else DSH_SPL(uint32_t);
-#undef DSH_SPL
-        return hipGetLastError();
+        const uint32_t runs = (per_x + run - 1) / run;
+        if (words == 2) {  // (16-bit C(v) only: it is 32 bits wide at p = 16, where the table is gathered)
+            if (cum_bytes != 2) return hipErrorInvalidValue;
+            return launch_sparse_count_lds<uint16_t, 2>(st, runs, items, nitems, run, tab, lists, len, cap, m, cum, nslots);
+        }
+        return cum_bytes == 2 ? launch_sparse_count_lds<uint16_t, 1>(st, runs, items, nitems, run, tab, lists, len, cap, m, cum, nslots)
+                              : launch_sparse_count_lds<uint32_t, 1>(st, runs, items, nitems, run, tab, lists, len, cap, m, cum, nslots);
     }
     if (cum_bytes == 2)
         hipLaunchKernelGGL(k_sparse_count<uint16_t>, dim3(nitems), dim3(512), 0, st, items, tab, lists, len, cap, m, (uint16_t *)cum, nslots);

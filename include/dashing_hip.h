@@ -1160,6 +1160,11 @@ int dsh_finalize_phase_cycles(dsh_ctx *ctx, uint64_t *out16);
  *                 "sparse_run"              0..65536 (default 0 = 4, the measured one): the items a workgroup of that LDS
  *                                           placement takes one behind the other, staging the table only where it changes;
  *                                           1 = one item per workgroup.  Results do not depend on it.
+ *                 "sparse_words"            0 (default) | 1 | 2: the words of the table -- 32 columns each -- a workgroup
+ *                                           of that placement stages side by side and a lane gathers in one LDS read;
+ *                                           0 = 1, the faster one where it was measured (the pair leaves room for one
+ *                                           workgroup a CU).  2 needs p <= 14, where the pair fits a CU's LDS: with it a
+ *                                           compare call at p = 15 fails with DSH_EINVAL.  Results do not depend on it.
  *   exchange      "part_band_tiles"         a part of at least this many tiles also ends a launch of the tile kernel (2048)
  *                 "xch_tail_bands"          0..8 (default 2): a job with parts of at most 64 rounds has its tile kernel cut
  *                                           at whole rounds into a head and this many tails, so that the head's parts
@@ -1177,7 +1182,7 @@ int dsh_finalize_phase_cycles(dsh_ctx *ctx, uint64_t *out16);
  * ("pair_mfma" exists only in a library built with `make WHATIF=1`: the matrix-core what-if the north star excludes.) */
 int dsh_set_option(dsh_ctx *ctx, const char *name, int64_t value);
 /* Derived state of the last prepared sketch matrix: "planes" (dense bit-planes used), "vlo",
- * "vhi", "pbase", "threshold", "emax", "elow", "kc", "pair_groups" (as the last prepare put them into effect), "pair_round" (work items per round of the last dist call's first launch of the tile kernel: 256 x the items per workgroup it ran with), "tile", "npad", "kpad", "cum_bytes", "sorted", "ncols", "lockstep", "tiles", "bands", "items" (work items of the tile kernel), "sparse_items" ((tile, plane) items counted from position lists instead: option "sparse_planes"), "sparse_plane_us" (with profiling on: the device time of their counting kernel in the last dist call; it is part of the pair phase of dsh_last_kernel_ms), "sparse_sided_items" (those of them that the option "sparse_sided" planned), "sparse_transposed_items" (those whose lists are the column block's), "sparse_slabs" ((block, plane) slabs -- a table and position lists -- the last dist call's items read), "sparse_table_slabs" ((block, plane) tables of the last dist call built without lists), "sparse_table_fills" (table words the LDS placement of the counting kernel staged in the last dist call's launches: four per table; 0 where the table is gathered), "sparse_run" (the option in effect: 0 reads as the default), "sparse_planes", "sparse_sided", "sparse_cap",
+ * "vhi", "pbase", "threshold", "emax", "elow", "kc", "pair_groups" (as the last prepare put them into effect), "pair_round" (work items per round of the last dist call's first launch of the tile kernel: 256 x the items per workgroup it ran with), "tile", "npad", "kpad", "cum_bytes", "sorted", "ncols", "lockstep", "tiles", "bands", "items" (work items of the tile kernel), "sparse_items" ((tile, plane) items counted from position lists instead: option "sparse_planes"), "sparse_plane_us" (with profiling on: the device time of their counting kernel in the last dist call; it is part of the pair phase of dsh_last_kernel_ms), "sparse_sided_items" (those of them that the option "sparse_sided" planned), "sparse_transposed_items" (those whose lists are the column block's), "sparse_slabs" ((block, plane) slabs -- a table and position lists -- the last dist call's items read), "sparse_table_slabs" ((block, plane) tables of the last dist call built without lists), "sparse_table_fills" (table words the LDS placement of the counting kernel staged in the last dist call's launches: four per table; 0 where the table is gathered), "sparse_run" (the option in effect: 0 reads as the default), "sparse_words" (the option in effect for the attached matrix: 1 or 2; 0 where the table is gathered), "sparse_planes", "sparse_sided", "sparse_cap",
  * "words_per_plane", "avg_tile_planes_x100" (of the last dist call), "frag_items", "parts_done", "parts_signalled",
  * "place_kernel_us" (with profiling on: device time of the last dsh_exchange_place_device's placement kernel),
  * "sketch_kernel_us" / "fastx_decode_us" (with profiling on: k_sketch / the FASTA-FASTQ decode kernels of the last sketch call),
